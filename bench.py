@@ -11,6 +11,12 @@ One "step" = one full pass of the hot path over one batch per rank: host tiling,
 H2D of uint8 crops, ViT (2 crops/image, both computed), projector, 730-token
 image prefill, prompt prefill, 32 lockstep decode steps, D2H of token ids (and,
 for N>1, the RCCL gather of ids on rank 0).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints that line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds per timed step).  --full adds everything
+else after the timed region: parity against the reference fixtures, the eager profiling step
+(roofline, phase times), single-image latency, the auxiliary legs and the CPU baseline.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -65,7 +71,25 @@ def parse():
                          "images/GPU; detect13_fp8: the same in the fp8 mode = BASELINE configs[4] (256 images over 8 GPUs)")
     ap.add_argument("--selftest-dist", action="store_true",
                     help="only exercise the launch + collective plumbing (gloo on a CPU-only box) and print a JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: parity against the reference fixtures, the eager profiling step "
+                         "(roofline, phase times), single-image latency, the auxiliary legs and the CPU baseline.  Without it "
+                         "a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (caption leg: the token ids; detect "
+                         "legs: the object boxes) as DIR/<name>.npy in float32 / float64")
     return ap.parse_args()
+
+
+def dump_outputs(directory, arrays):
+    """``--dump-outputs DIR``: one DIR/<name>.npy per array, float32 or float64, so that two builds can be compared output
+    for output on identical (seeded) inputs."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        assert a.nbytes <= 64 << 20, (name, a.shape)
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def selftest_dist(args):
@@ -592,7 +616,8 @@ def detect_job(engine, cfg, args, fp8):
     scaling: every rank runs ``--detect13-batch`` 768x1024 images per step through the pipelined detect engine
     (``DataParallelEngine.batch_detect_pipelined``: per-rank lockstep object loop, next step's host tiling under the current
     step's GPU time, objects gathered on rank 0 inside the step); W untimed steps, K timed between barrier + synchronize,
-    max over ranks.  Rank 0 checks the first images' objects against the reference's (tests/golden/md2b_detect13.npz)."""
+    max over ranks.  With --full, rank 0 checks the first images' objects against the reference's
+    (tests/golden/md2b_detect13.npz) and one more, non-overlapped step gives the phase times."""
     from moondream_amd import parity as P
     from moondream_amd import synth
 
@@ -630,15 +655,24 @@ def detect_job(engine, cfg, args, fp8):
     per_rank_ms = engine.gather_floats(elapsed / args.steps * 1e3)
     elapsed = engine.max_over_ranks(elapsed)
     seen = engine.ranks_seen()
-    model.collect_timing = True
-    model.batch_detect(imgs, [obj] * len(imgs), settings=st)
-    torch.cuda.synchronize()
-    model.collect_timing = False
-    phase = {k: round(v, 2) for k, v in model.last_phase_ms.items()}
+    phase = {}
+    if args.full:
+        model.collect_timing = True
+        model.batch_detect(imgs, [obj] * len(imgs), settings=st)
+        torch.cuda.synchronize()
+        model.collect_timing = False
+        phase = {k: round(v, 2) for k, v in model.last_phase_ms.items()}
     if rank != 0:
         return
     res = outs[-1]
     assert len(res) == n_total
+    if args.dump_outputs:
+        # [image, object, (x_min, y_min, x_max, y_max)], NaN past an image's last object
+        boxes = np.full((n_total, max(max_objects, max(len(r["objects"]) for r in res)), 4), np.nan)
+        for i, r in enumerate(res):
+            for k, o in enumerate(r["objects"]):
+                boxes[i, k] = [o[f] for f in ("x_min", "y_min", "x_max", "y_max")]
+        dump_outputs(args.dump_outputs, {"objects": boxes})
     mode = "FP8 (md_gemm_f8 for ViT / projector / prefill, e4m3 decode weights + KV copy; region head bf16)" if fp8 else "bf16"
     line = {
         "metric": "images_per_sec", "value": n_total * args.steps / elapsed, "unit": "images/s", "n_gpus": world, "steps": args.steps,
@@ -649,8 +683,11 @@ def detect_job(engine, cfg, args, fp8):
                                f"each), detect prompt, max_objects {max_objects} (every sequence runs all rounds), seeded synthetic weights",
                    "batch_per_gpu": B2, "global_batch": n_total, "parallelism": f"dp{world}",
                    "host_latency_hiding": "pipelined detect engine: step i+1's PIL tiling on background workers under step i's GPU time"},
-        "phase_ms": phase,
     }
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        return
+    line["phase_ms"] = phase
     if phase.get("vision"):
         fl = len(imgs) * (n_crops * FLOP_VIT_PER_CROP + 51.98e9)
         tf = fl / (phase["vision"] * 1e-3) / 1e12
@@ -741,9 +778,12 @@ def main():
     per_rank_ms = engine.gather_floats(elapsed / args.steps * 1e3)  # every rank's own clock, on rank 0
     elapsed = engine.max_over_ranks(elapsed)
     ranks_seen = engine.ranks_seen()  # an RCCL all-reduce of ones: the ranks that really took part
+    if args.dump_outputs and rank == 0:
+        # the LAST timed step's ids, gathered on rank 0 in image order: [n_total images, T tokens]
+        dump_outputs(args.dump_outputs, {"token_ids": torch.cat([b.cpu() for b in out[-1]], 0).numpy()})
     # parity of the timed configuration: the LAST timed step's ids (gathered on rank 0, image order)
     parity = None
-    if rank == 0 and out and out[-1] is not None and not args.only_timed_steps:
+    if args.full and rank == 0 and out and out[-1] is not None and not args.only_timed_steps:
         ids_all = torch.cat([b.cpu() for b in out[-1]], 0).tolist()
         second = None
         if world == 1 and not args.no_second_oracle and args.model == "2b" and args.seed == 1 and args.prompt == "caption":
@@ -762,6 +802,46 @@ def main():
     if args.only_timed_steps:
         if rank == 0:
             print(json.dumps({"only_timed_steps": args.steps, "ms_per_step": elapsed / args.steps * 1e3}), flush=True)
+        return
+    result = {
+        "metric": "images_per_sec",
+        "value": n_total * args.steps / elapsed,
+        "unit": "images/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "ranks_seen": ranks_seen,
+        "weights_broadcast": weights_broadcast,
+        "cpu_binding": engine.cpu_binding,   # rank 0's share of the host's cores (dist.bind_rank_cpus; every rank binds its own)
+        "per_rank_ms_per_step": [round(x, 3) for x in per_rank_ms] if per_rank_ms else None,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16",
+        "data": "synthetic",
+        "config": {
+            "workload": f"Moondream-{args.model.upper()} bf16 batch_generate ({args.prompt}): {B} images/GPU x 378x378 "
+                        f"(2 crops each, both encoded), {len(prompt)}-token prompt, {T} greedy decode tokens, "
+                        f"seeded synthetic weights",
+            "batch_per_gpu": B, "decode_tokens": T, "parallelism": f"dp{world}",
+            # two HIP streams (encode of step i+1, decode of step i).  Their kernels do overlap on the GPU, and that is worth
+            # 3 % of a step against one in-order stream (same box: 260.5 vs 269 ms, profiles/r04_pipelined_engine_streams_ab.txt);
+            # the rest of what the pipelining buys (no-pipeline: 292.8 ms) is host work hidden: tiling, launches, D2H
+            "host_latency_hiding": "none" if args.no_pipeline else "step i+1's host tiling (thread pool) + encode launches run while step i "
+                                   "decodes on a second, higher-priority HIP stream; step i's ids are collected (pinned, async D2H) after "
+                                   "step i+1 is queued; kernels of the two streams overlap on the GPU (3 % of a step vs one in-order stream)"
+                                   + ("; the decode of two consecutive steps runs as ONE lockstep of 128 sequences (each step is still "
+                                      "encoded on its own, 64 images per launch; md_decode_step takes 65..128 rows in one pass over the "
+                                      "weights, bit-identical to two passes of 64)" if model.pair_decode and 2 * args.batch <= 128 else ""),
+            # every row of [bos | 729 image embeddings | prompt] goes through every decoder block, as in the reference;
+            # the reference does it as two passes over the weights (encode_image, then the prompt)
+            "prefill": "image prefix + prompt in one decoder pass" if model.fused_prefill else "image prefix, then prompt (two passes)",
+        },
+    }
+    if not args.full:   # the headline alone: what the timed steps did
+        if rank == 0:
+            print(json.dumps(result), flush=True)
         return
     # Dominant kernel (bf16 MFMA tile GEMM): algorithmic flops / HIP-event time of its launches,
     # taken on ONE extra, non-overlapped, eagerly launched step right after the timed region:
@@ -812,41 +892,7 @@ def main():
         })
     except (OSError, KeyError, ValueError, ZeroDivisionError, StopIteration):
         pass
-    result = {
-        "metric": "images_per_sec",
-        "value": n_total * args.steps / elapsed,
-        "unit": "images/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "ranks_seen": ranks_seen,
-        "weights_broadcast": weights_broadcast,
-        "cpu_binding": engine.cpu_binding,   # rank 0's share of the host's cores (dist.bind_rank_cpus; every rank binds its own)
-        "per_rank_ms_per_step": [round(x, 3) for x in per_rank_ms] if per_rank_ms else None,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16",
-        "data": "synthetic",
-        "config": {
-            "workload": f"Moondream-{args.model.upper()} bf16 batch_generate ({args.prompt}): {B} images/GPU x 378x378 "
-                        f"(2 crops each, both encoded), {len(prompt)}-token prompt, {T} greedy decode tokens, "
-                        f"seeded synthetic weights",
-            "batch_per_gpu": B, "decode_tokens": T, "parallelism": f"dp{world}",
-            # two HIP streams (encode of step i+1, decode of step i).  Their kernels do overlap on the GPU, and that is worth
-            # 3 % of a step against one in-order stream (same box: 260.5 vs 269 ms, profiles/r04_pipelined_engine_streams_ab.txt);
-            # the rest of what the pipelining buys (no-pipeline: 292.8 ms) is host work hidden: tiling, launches, D2H
-            "host_latency_hiding": "none" if args.no_pipeline else "step i+1's host tiling (thread pool) + encode launches run while step i "
-                                   "decodes on a second, higher-priority HIP stream; step i's ids are collected (pinned, async D2H) after "
-                                   "step i+1 is queued; kernels of the two streams overlap on the GPU (3 % of a step vs one in-order stream)"
-                                   + ("; the decode of two consecutive steps runs as ONE lockstep of 128 sequences (each step is still "
-                                      "encoded on its own, 64 images per launch; md_decode_step takes 65..128 rows in one pass over the "
-                                      "weights, bit-identical to two passes of 64)" if model.pair_decode and 2 * args.batch <= 128 else ""),
-            # every row of [bos | 729 image embeddings | prompt] goes through every decoder block, as in the reference;
-            # the reference does it as two passes over the weights (encode_image, then the prompt)
-            "prefill": "image prefix + prompt in one decoder pass" if model.fused_prefill else "image prefix, then prompt (two passes)",
-        },
+    result.update({
         "roofline": {
             "bound": "mfma",
             "kernel": "gemm_w4_kernel: 256x256 tile GEMM, four waves (one per SIMD) x 128x128 on v_mfma_f32_16x16x32_bf16, operands global -> LDS by LDS-DMA, persistent; "
@@ -874,7 +920,7 @@ def main():
             "committed_profile": decode_gemm_trace_figure(args),
         },
         "phase_ms": phase_ms,
-    }
+    })
     if parity is not None:
         result.update(parity)
     if args.model == "2b" and phase_ms.get("vision"):

@@ -15,10 +15,11 @@ and records, for fixed seeded inputs, the per-stage activations, KV rows,
 logits, greedy token ids and top-1/top-2 margins that the oracle
 (``oracle/moondream_oracle.py``) and the HIP path are compared against.
 
-Usage:  python oracle/make_golden.py [tiny] [layers] [multicrop] [crops] [textonly] [detect] [sampling] [reasoning] [lora] [0.5b] [2b] [bench64] [vqa64] [detect13] [reftime]
+Usage:  python oracle/make_golden.py [tiny] [layers] [multicrop] [crops] [textonly] [detect] [sampling] [reasoning] [lora] [0.5b] [2b] [bench64] [vqa64] [detect13] [reftime] [refdata]
 """
 from __future__ import annotations
 
+import json
 import os
 import sys
 import time
@@ -917,6 +918,126 @@ def gen_lora(name="tiny_lora", cfg_name="tiny", seed=1, rank=8, n_cases=2, max_t
     print(f"[{name}] wrote {path}", flush=True)
 
 
+def _dataclass_tree(obj):
+    """A dataclass instance as JSON-able data, dataclass nodes marked, so that a test can walk its own config the same way."""
+    import dataclasses
+
+    if dataclasses.is_dataclass(obj):
+        return {"__dataclass__": {f.name: _dataclass_tree(getattr(obj, f.name)) for f in dataclasses.fields(obj)}}
+    return json.loads(json.dumps(obj))
+
+
+def gen_refdata(name="reference_host"):
+    """What the host-side CPU tests compare with, recorded from the reference so that they run without it:
+    int4 dequantisation (layers.py:38-44), the shipped JSON configs through the reference's dataclasses (config.py),
+    tilings / crop bytes / stitched grids for random image sizes (image_crops.py, PIL branch), the pyvips branch under
+    the tests' stand-in module, and the attention masks + positions the reference passes through its seam
+    (tests/test_weights_cpu.py, test_image_crops.py, test_parity_cpu.py)."""
+    import dataclasses
+    import importlib.util
+
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import test_image_crops as tic
+
+    out = {}
+    # int4: the reference's dequantize_tensor (layers.py imports torchao, absent here: evaluate just that function)
+    src = open(os.path.join(REFERENCE, "moondream", "torch", "layers.py")).read()
+    start = src.index("def dequantize_tensor")
+    ns = {"torch": torch}
+    exec(compile(src[start:src.index("\n\n\n", start)], "reference:layers.py", "exec"), ns)
+    g = torch.Generator().manual_seed(0)
+    packed = torch.randint(0, 256, (96, 128), dtype=torch.uint8, generator=g)
+    scale = torch.rand(192, 1, generator=g) * 0.02 + 1e-3
+    zero = torch.rand(192, 1, generator=g) * 15
+    ref = ns["dequantize_tensor"](packed, scale, zero, (48, 512))
+    assert ref.dtype == torch.bfloat16
+    out.update({"int4_packed": packed.numpy(), "int4_scale": scale.numpy(), "int4_zero": zero.numpy(),
+                "int4_out_bf16_bits": ref.contiguous().view(torch.int16).numpy()})
+
+    # configs: defaults and the two shipped JSON files through the reference's own dataclasses
+    def load(modname, path):
+        spec = importlib.util.spec_from_file_location(modname, path)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod
+
+    rc = load("ref_config", os.path.join(REFERENCE, "moondream", "torch", "config.py"))
+    cfgs = {"defaults": {"input": None, "parsed": _dataclass_tree(rc.MoondreamConfig())}}
+    for fn in ("config_md2.json", "config_md05.json"):
+        with open(os.path.join(REFERENCE, "moondream", "config", fn)) as f:
+            d = json.load(f)
+        cfgs[fn] = {"input": d, "parsed": _dataclass_tree(rc.MoondreamConfig.from_dict(d))}
+    out["configs_json"] = np.array(json.dumps(cfgs, sort_keys=True))
+
+    # random image sizes (the draw order of test_random_sizes_against_the_reference_itself)
+    ric = load("ref_image_crops", os.path.join(REFERENCE, "moondream", "torch", "image_crops.py"))
+    rng = np.random.default_rng(7)
+    sizes = [(378, 378), (1, 1), (2, 3000), (3000, 2), (379, 378), (1200, 1600), (4000, 3000), (100, 1000)]
+    sizes += [(int(rng.integers(16, 2200)), int(rng.integers(16, 2200))) for _ in range(12)]
+    rows = []
+    for h, w in sizes:
+        sel = list(ric.select_tiling(h, w, 378, 12))
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        b = ric.overlap_crop_image(img, overlap_margin=4, max_crops=12)
+        crops = np.ascontiguousarray(np.asarray(b["crops"]))
+        th, tw = b["tiling"]
+        feats = [torch.from_numpy(rng.standard_normal((27, 27, 8)).astype(np.float32)) for _ in range(th * tw)]
+        rb = ric.reconstruct_from_crops(feats, (th, tw), overlap_margin=4, patch_size=1)
+        rows.append([h, w, *sel, th, tw, crops.shape[0], zlib.crc32(crops.tobytes()), *rb.shape, zlib.crc32(rb.contiguous().numpy().tobytes())])
+    out["crops_random"] = np.array(rows, dtype=np.int64)
+
+    # the pyvips branch under the tests' stand-in module
+    calls = []
+    sys.modules["pyvips"] = tic.fake_pyvips(calls)
+    try:
+        rv = load("ref_image_crops_vips", os.path.join(REFERENCE, "moondream", "torch", "image_crops.py"))
+        assert rv.HAS_VIPS
+        rng = np.random.default_rng(5)
+        cases, all_calls = [], []
+        for h, w in tic.VIPS_SIZES:
+            img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+            calls.clear()
+            b = rv.overlap_crop_image(img, overlap_margin=4, max_crops=12)
+            assert len(calls) == 2, calls
+            crops = np.ascontiguousarray(np.asarray(b["crops"]))
+            cases.append([h, w, *b["tiling"], crops.shape[0], zlib.crc32(crops.tobytes())])
+            all_calls.append(list(calls))
+    finally:
+        del sys.modules["pyvips"]
+    out["vips_cases"] = np.array(cases, dtype=np.int64)
+    out["vips_calls"] = np.array(all_calls, dtype=np.float64)
+
+    # the masks and positions the unmodified reference passes through _prefill / _decode_one_tok
+    cfg = get_config("tiny")
+    model, _ = load_reference(cfg, synth.synthetic_state_dict(cfg, seed=1))
+    seen = []
+    orig_prefill, orig_decode = model._prefill, model._decode_one_tok
+
+    def prefill_tap(x, mask, pos_ids, lora):
+        seen.append(("prefill", mask, pos_ids))
+        return orig_prefill(x, mask, pos_ids, lora)
+
+    def decode_tap(x, mask, pos_ids, lora):
+        seen.append(("decode", mask, pos_ids))
+        return orig_decode(x, mask, pos_ids, lora)
+
+    model._prefill, model._decode_one_tok = prefill_tap, decode_tap
+    from PIL import Image
+    img = Image.fromarray(synth.synthetic_image_array(0, 1, (378, 378)), "RGB")
+    model.caption(img, settings={"temperature": 0, "max_tokens": 3, "variant": None})
+    model.query(None, "11 12 13", settings={"temperature": 0, "max_tokens": 3})
+    out["seam_kinds"] = np.array([k for k, _, _ in seen])
+    for i, (_, mask, pos) in enumerate(seen):
+        assert mask is not None and mask.dtype == torch.bool, (i, mask)
+        m = mask.cpu().numpy()
+        out[f"seam{i}_shape"] = np.array(m.shape, dtype=np.int64)
+        out[f"seam{i}_bits"] = np.packbits(m.reshape(-1, m.shape[-1]), axis=-1)
+        out[f"seam{i}_pos"] = pos.cpu().numpy().astype(np.int64)
+    path = os.path.join(GOLD, f"{name}.npz")
+    np.savez_compressed(path, **out)
+    print(f"[refdata] wrote {path} ({os.path.getsize(path)} bytes, {len(seen)} seam calls)")
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(os.cpu_count() or 1)
@@ -924,6 +1045,8 @@ def main():
     which = sys.argv[1:] or ["tiny", "multicrop", "crops"]
     if "crops" in which:
         gen_crops()
+    if "refdata" in which:     # host-side data of the reference for the CPU tests (tests/golden/reference_host.npz)
+        gen_refdata()
     if "tiny" in which:
         gen_model_case("tiny_seed1", "tiny", 1, [(378, 378)], 24, True, n_images=3)
     if "layers" in which:

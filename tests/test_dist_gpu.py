@@ -10,6 +10,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.multiprocessing as mp
@@ -45,16 +46,19 @@ def test_bench_selftest_over_rccl_single_rank_group():
     assert line["weights_broadcast"]["equal_to_local_copy_on_every_rank"] is True
 
 
-def test_bench_under_torchrun_one_rank_over_rccl():
+def test_bench_under_torchrun_one_rank_over_rccl(tmp_path):
     """The driver's multi-GPU command line with N = 1 and the one-rank group: the REAL bench step (tiny model, 2 steps) with the
     RCCL weight broadcast (verified against the local copy), the per-step id gather on its own stream, the barrier and the
-    max-over-ranks around the timed region."""
+    max-over-ranks around the timed region; --dump-outputs writes the last timed step's gathered ids."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(mdist.free_port()), os.path.join(REPO, "bench.py"), "--gpus", "1", "--model", "tiny", "--batch", "4",
-           "--tokens", "8", "--steps", "2", "--warmup", "2", "--no-vqa-leg", "--no-strict-leg", "--no-detect13-leg", "--no-dedup-leg",
-           "--no-fp8-leg", "--no-fp8-full-leg", "--no-cpu-baseline", "--no-second-oracle", "--latency-runs", "0"]
+           "--tokens", "8", "--steps", "2", "--warmup", "2", "--full", "--no-vqa-leg", "--no-strict-leg", "--no-detect13-leg",
+           "--no-dedup-leg", "--no-fp8-leg", "--no-fp8-full-leg", "--no-cpu-baseline", "--no-second-oracle", "--latency-runs", "0",
+           "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, text=True)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["ranks_seen"] == 1 and line["value"] > 0
     assert line["weights_broadcast"]["equal_to_local_copy_on_every_rank"] is True and line["weights_broadcast"]["bytes"] > 0
+    ids = np.load(tmp_path / "out" / "token_ids.npy")
+    assert ids.dtype == np.float32 and ids.shape == (4, 8) and (ids == np.round(ids)).all() and (ids >= 0).all()
