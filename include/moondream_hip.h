@@ -582,6 +582,20 @@ md_status md_text_forward(const md_text_model* m, const void* x, void* hidden, i
                           int32_t q_len, const int32_t* pos0, const md_kv_cache* kv,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* md_text_forward where sequence b's K / V live in slot slots[b] of kv (slot 0 at kv->k / kv->v, slot j at j * batch_stride),
+ * not in slot b -- the library side of continuous batching: rows of one launch address any slots of a slab, so finished
+ * sequences leave a decode step and new ones take their slots without moving a cache row.
+ * slots: device int32 [batch], or NULL (== md_text_forward).  n_slots: slots addressable from kv (n_slots * batch_stride <=
+ * layer_stride).
+ * q_len == 1 only: a row whose slot is < 0 or >= n_slots is IDLE -- its hidden / logits rows are computed but unspecified, and it
+ * reads and writes no slab memory (no K / V write, no attention over a slab; its attention output is zero).
+ * q_len > 1 (prefill): every slot must be valid and distinct (caller contract, as pos0 is today).
+ * The slot table changes addresses only: a row gets the same bits from its slot as md_text_forward gives it in slot b.
+ * Workspace: md_text_workspace_bytes(m, batch, q_len). */
+md_status md_text_forward_slots(const md_text_model* m, const void* x, void* hidden, int32_t batch, int32_t q_len,
+                                const int32_t* pos0, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* LoRA "variant" side path (reference: lora.py:54-79 -> text.py:31-32,55-56 and layers.py:129-146 with lora != None).
  * delta(x) = (x A^T) B^T with A [r][k] and B [n][r] packed as bias-free md_linear (r zero-padded to 64); a pair with
  * a.w == NULL is absent.  Per block, in the reference's order and with its bf16 roundings:
@@ -652,6 +666,14 @@ md_status md_decode_step(const md_text_model* m, const int32_t* tokens, int32_t*
                          int64_t ld_logits, void* workspace, size_t workspace_bytes, void* stream);
 
 size_t md_decode_workspace_bytes(const md_text_model* m, int32_t batch);
+
+/* md_decode_step with the slot table of md_text_forward_slots (embed -> md_text_forward_slots -> lm_head -> suppress -> argmax;
+ * pos[b] += 1 for every row, idle ones included).  slots == NULL: md_decode_step.  An idle row's next[b] is unspecified.
+ * Workspace: md_decode_workspace_bytes(m, batch). */
+md_status md_decode_step_slots(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos,
+                               int32_t batch, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
+                               int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

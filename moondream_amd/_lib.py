@@ -203,6 +203,8 @@ SIGNATURES = {
     "md_text_workspace_bytes": (c_size_t, [P(MdTextModel), c_int32, c_int32]),
     "md_text_forward": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_int32, c_int32, c_void_p, P(MdKvCache),
                                   c_void_p, c_size_t, c_void_p]),
+    "md_text_forward_slots": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                        P(MdKvCache), c_void_p, c_size_t, c_void_p]),
     "md_text_lora_workspace_bytes": (c_size_t, [P(MdTextModel), c_int32, c_int32]),
     "md_text_forward_lora": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, P(MdKvCache),
                                        c_void_p, c_size_t, c_void_p]),
@@ -219,6 +221,8 @@ SIGNATURES = {
     "md_decode_workspace_bytes": (c_size_t, [P(MdTextModel), c_int32]),
     "md_decode_step": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_void_p, c_int32, P(MdKvCache), c_int32,
                                  c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "md_decode_step_slots": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, P(MdKvCache),
+                                       c_int32, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -1,0 +1,547 @@
+"""Continuous batching for token generation: per-sequence exit and KV-slot refill in the decode loop.
+
+``MoondreamModel.batch_generate_ids`` decodes a batch in lockstep: a sequence that has emitted EOS (or reached its length)
+keeps its row in every later step and its KV slot until the whole batch ends.  Here every request owns one KV slot of a slab
+sized once; each decode step runs only the live requests (``md_decode_step_slots``: row r attends over and writes slot
+``slots[r]``, rows of slot -1 are idle and touch no slab memory), finished requests leave at the next chunk boundary and
+queued ones are prefilled straight into the freed slots.
+
+Exactness: every batched kernel's accumulation order is a function of the layer shape, never of the number of rows in the
+launch (``batch_generate_ids``; MD_TILE_PINNED, MD_TILE_DECODE_TALL), and the slot table changes addresses only.  So a
+request's ids do not depend on what else is live: they equal, bit for bit, what the lockstep path gives the same
+(image, prompt) in a batch of more than one sequence.  The engine never uses the single-sequence persistent kernel and
+always pins the tile config; the prompt pass of the two-pass prefill (EncodedImage inputs, ``fused_prefill`` off) runs
+in launches of <= 64 rows, as ``set_strict_batch_invariance`` does, for the same reason.
+
+``SlotScheduler`` is the pure-Python part (no GPU): slot pool, FIFO admission queue, per-request state, chunk plans and
+retirement.  ``ContinuousEngine`` drives it with the library.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from collections import deque
+from dataclasses import dataclass, field
+from typing import Callable, Deque, Dict, Iterator, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+DEFAULT_MAX_TOKENS = 768  # moondream.py (the reference's default, moondream.py:50-53)
+DEFAULT_TOP_P = 0.3
+MAX_GRAPHS = 16  # captured decode chunks per (model, stream)
+IDLE_SLOT = -1
+
+
+def row_buckets(max_live: int) -> List[int]:
+    """Row counts a decode chunk is padded to: powers of two below 32, then multiples of a step (32, doubled while there would
+    be more than MAX_GRAPHS buckets), the last one max_live.  A chunk's launch shapes -- and its captured graph -- depend on
+    the bucket only, never on which requests are live."""
+    if max_live < 1:
+        raise ValueError("max_live must be >= 1")
+    small = [b for b in (1, 2, 4, 8, 16) if b < max_live]
+    step = 32
+    while len(small) + (max_live + step - 1) // step > MAX_GRAPHS:
+        step *= 2
+    big = list(range(step, max_live, step)) + [max_live]
+    return sorted(set(small + [b for b in big if b >= 32] + [max_live]))
+
+
+@dataclass(eq=False)  # identity: a request is itself, whatever its fields
+class Request:
+    """One generation request.  ``pos`` is the position of the next token to decode (the prompt's end after the prefill);
+    ``step_limit`` the decode steps it may take: min(max_tokens - 1, max_context - 1 - pos) -- with the first token from the
+    prefill that is MoondreamModel._truncate's length rule, and the context rule of the lockstep loop per request."""
+
+    rid: int
+    image: object
+    prompt: List[int]
+    max_tokens: int
+    eos_id: Optional[int]
+    seed: Optional[int] = None
+    slot: int = IDLE_SLOT
+    pos: int = 0
+    ids: List[int] = field(default_factory=list)
+    last: int = 0
+    steps: int = 0
+    step_limit: int = 0
+    done: bool = False
+    generator: object = None
+
+    @property
+    def remaining(self) -> int:
+        return 0 if self.done else max(0, self.step_limit - self.steps)
+
+
+@dataclass
+class ChunkPlan:
+    """``n`` decode steps over ``bucket`` rows: ``rows[r]`` is the request of row r (rows past len(rows) are padding);
+    ``slots[i][r]`` the slot row r addresses in step i (IDLE_SLOT: padding, or a request past its step limit)."""
+
+    rows: List[Request]
+    bucket: int
+    n: int
+    slots: np.ndarray   # int32 [n, bucket]
+    tokens: np.ndarray  # int32 [bucket]: the token each row consumes in step 0
+    pos: np.ndarray     # int32 [bucket]: its position
+
+    @property
+    def live_row_steps(self) -> int:
+        return int((self.slots >= 0).sum())
+
+
+@dataclass
+class EngineStats:
+    decode_steps: int = 0
+    padded_row_steps: int = 0
+    live_row_steps: int = 0
+    admissions: int = 0
+    prefill_passes: int = 0
+    graph_captures: int = 0
+
+
+class SlotScheduler:
+    """Slot pool of ``max_live`` KV slots, FIFO admission queue, chunk plans and retirement (no GPU, no torch).
+
+    Admission: when at least ``admit_threshold`` slots are free, or nothing is live, the head of the queue takes free slots
+    (a freed slot goes to the back of the free list: slots are reused first-in first-out).  A request retires when it
+    emits its ``eos_id`` (not part of its ids), when its ids reach ``max_tokens``, or when its next position reaches
+    ``max_context - 1``."""
+
+    def __init__(self, max_live: int, max_context: int, chunk: int = 16, admit_threshold: Optional[int] = None):
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        self.max_live = int(max_live)
+        self.max_context = int(max_context)
+        self.chunk = int(chunk)
+        self.buckets = row_buckets(self.max_live)
+        self.admit_threshold = max(1, int(admit_threshold if admit_threshold is not None else self.max_live // 8))
+        self.free: Deque[int] = deque(range(self.max_live))
+        self.queue: Deque[Request] = deque()
+        self.live: List[Request] = []  # admission order = row order of every plan (stable)
+        self.stats = EngineStats()
+
+    # ---- admission / retirement
+    def submit(self, req: Request) -> None:
+        self.queue.append(req)
+
+    def pending(self) -> bool:
+        return bool(self.queue or self.live)
+
+    def take_admissions(self) -> List[Request]:
+        """Requests to prefill now, each with its slot assigned (in queue order)."""
+        if not self.queue or not self.free or (self.live and len(self.free) < self.admit_threshold):
+            return []
+        out = []
+        while self.queue and self.free:
+            r = self.queue.popleft()
+            r.slot = self.free.popleft()
+            out.append(r)
+        self.stats.admissions += 1
+        return out
+
+    def start(self, req: Request, first: int, pos: int) -> bool:
+        """The prefill of ``req`` picked ``first`` with the next token at position ``pos``.  Returns True if the request is
+        already finished (it then no longer holds its slot)."""
+        req.pos = int(pos)
+        req.steps = 0
+        req.step_limit = max(0, min(req.max_tokens - 1, self.max_context - 1 - req.pos))
+        req.last = int(first)
+        if req.max_tokens <= 0 or (req.eos_id is not None and first == req.eos_id):
+            req.ids = []
+            return self._retire(req)
+        req.ids = [int(first)]
+        if req.step_limit == 0:
+            return self._retire(req)
+        self.live.append(req)
+        return False
+
+    def _retire(self, req: Request) -> bool:
+        req.done = True
+        if req in self.live:
+            self.live.remove(req)
+        if req.slot >= 0:
+            self.free.append(req.slot)
+        req.slot = IDLE_SLOT
+        return True
+
+    # ---- chunks
+    def bucket_for(self, rows: int) -> int:
+        for b in self.buckets:
+            if b >= rows:
+                return b
+        raise AssertionError((rows, self.buckets))
+
+    def plan(self) -> Optional[ChunkPlan]:
+        if not self.live:
+            return None
+        rows = list(self.live)
+        bucket = self.bucket_for(len(rows))
+        n = min(self.chunk, max(r.remaining for r in rows))
+        slots = np.full((n, bucket), IDLE_SLOT, dtype=np.int32)
+        tokens = np.zeros(bucket, dtype=np.int32)
+        pos = np.zeros(bucket, dtype=np.int32)
+        for i, r in enumerate(rows):
+            slots[: min(n, r.remaining), i] = r.slot  # past its step limit a row is idle: no cache row beyond its context
+            tokens[i] = r.last
+            pos[i] = r.pos
+        return ChunkPlan(rows, bucket, n, slots, tokens, pos)
+
+    def commit(self, plan: ChunkPlan, out: np.ndarray) -> List[Request]:
+        """``out[i][r]``: the token row r produced in step i.  Advances every row, retires the finished ones (their slots
+        return to the pool) and returns them in row order."""
+        self.stats.decode_steps += plan.n
+        self.stats.padded_row_steps += plan.n * plan.bucket
+        self.stats.live_row_steps += plan.live_row_steps
+        finished = []
+        for r_idx, r in enumerate(plan.rows):
+            fin = False
+            for i in range(min(plan.n, r.remaining)):
+                tok = int(out[i][r_idx])
+                r.steps += 1
+                r.pos += 1
+                r.last = tok
+                if r.eos_id is not None and tok == r.eos_id:
+                    fin = True
+                    break
+                r.ids.append(tok)
+                if r.steps >= r.step_limit:
+                    fin = True
+                    break
+            if fin:
+                self._retire(r)
+                finished.append(r)
+        return finished
+
+    def run(self, admit: Callable[[List[Request]], Sequence[Tuple[int, int]]],
+            step: Callable[[ChunkPlan], np.ndarray]) -> Iterator[Request]:
+        """Drive the schedule: ``admit(requests)`` prefills them and returns (first token, next position) per request,
+        ``step(plan)`` runs a chunk and returns its tokens [n, bucket].  Yields requests in completion order."""
+        while self.pending():
+            adm = self.take_admissions()
+            if adm:
+                for r, (first, pos) in zip(adm, admit(adm)):
+                    if self.start(r, first, pos):
+                        yield r
+            plan = self.plan()
+            if plan is None:
+                continue
+            yield from self.commit(plan, step(plan))
+
+
+class ContinuousEngine:
+    """Continuous-batching generation on a ``MoondreamModel``.
+
+        eng = ContinuousEngine(model, max_live=64)
+        for img, n in work:
+            eng.submit(img, prompt_ids, max_tokens=n)
+        for rid, ids in eng.run():   # completion order
+            ...
+
+    ``max_live`` KV slots are allocated once, before the first admission, and never grown during a run.  With
+    ``model.compile()`` decode chunks are replayed from hipGraphs keyed by the padded row count (at most MAX_GRAPHS per
+    model and stream); the token, position, slot-table and uniform buffers of a bucket keep their addresses and are
+    refreshed before each replay.  ``temperature`` > 0 samples with md_sample_top_p; each request draws its uniforms from its
+    own generator (``seed``), so its tokens do not depend on which other requests share its steps."""
+
+    def __init__(self, model, max_live: int = 64, chunk: int = 16, temperature: float = 0.0, top_p: float = DEFAULT_TOP_P,
+                 admit_threshold: Optional[int] = None):
+        self.model = model
+        self.max_live = int(max_live)
+        self.chunk = int(chunk)
+        self.temperature = float(temperature)
+        self.top_p = float(top_p)
+        self.admit_threshold = admit_threshold
+        t = model.config.text
+        self.sched = SlotScheduler(self.max_live, t.max_context, self.chunk, admit_threshold)
+        self._next_rid = 0
+
+    @property
+    def stats(self) -> EngineStats:
+        return self.sched.stats
+
+    # ---- submission
+    def submit(self, image, prompt_ids: Sequence[int], max_tokens: int = DEFAULT_MAX_TOKENS, eos_id: Optional[int] = None,
+               seed: Optional[int] = None, ignore_eos: bool = False, variant: Optional[str] = None) -> int:
+        """Queue one request; ``image`` is a PIL image or an EncodedImage.  ``eos_id`` None: the tokenizer's EOS
+        (``ignore_eos``: none).  Returns its id."""
+        from PIL import Image
+
+        from .moondream import EncodedImage
+
+        if variant is not None:
+            raise ValueError("continuous batching has no LoRA side path (md_text_forward_lora has no slot table)")
+        if not isinstance(image, (Image.Image, EncodedImage)):
+            raise ValueError("image must be a PIL Image or EncodedImage")
+        prompt = [int(p) for p in prompt_ids]
+        if not prompt:
+            raise ValueError("empty prompt")
+        t = self.model.config.text
+        prefix = image.pos if isinstance(image, EncodedImage) else 1 + self.model.config.vision.n_patches
+        if prefix + len(prompt) > t.max_context:
+            raise ValueError(f"image prefix + prompt ({prefix + len(prompt)} positions) do not fit the {t.max_context}-slot context")
+        eos = None if ignore_eos else (self.model.config.tokenizer.eos_id if eos_id is None else int(eos_id))
+        rid = self._next_rid
+        self._next_rid += 1
+        self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed))
+        return rid
+
+    def submit_caption(self, image, length: str = "normal", **kw) -> int:
+        """The prompt ``batch_caption`` builds."""
+        tpl = self.model.config.tokenizer.templates["caption"]
+        if tpl is None:
+            raise NotImplementedError("Model does not support captioning.")
+        if length not in tpl:
+            raise ValueError(f"Model does not support caption length '{length}'.")
+        return self.submit(image, tpl[length], **kw)
+
+    def submit_query(self, image, question: str, **kw) -> int:
+        """The prompt ``batch_query`` builds."""
+        tpl = self.model.config.tokenizer.templates["query"]
+        if tpl is None:
+            raise NotImplementedError("Model does not support querying.")
+        prompt = list(tpl["prefix"]) + list(self.model.tokenizer.encode(question).ids) + list(tpl["suffix"]) + list(tpl["suffix"])
+        return self.submit(image, prompt, **kw)
+
+    # ---- running
+    def run(self) -> Iterator[Tuple[int, List[int]]]:
+        """Generate every queued request; yields (rid, ids) in completion order.  Requests submitted while this runs are
+        admitted too.  ``stats`` counts this run."""
+        import torch
+
+        self.sched.stats = EngineStats()
+        with torch.inference_mode():
+            self._prepare_run()
+            for r in self.sched.run(self._admit, self._step):
+                yield r.rid, list(r.ids)
+
+    def _prepare_run(self) -> None:
+        """Size the KV slab (once, before the first admission: never grown during a run) and the decode buffers of the
+        largest bucket, so that arena growth does not invalidate captured chunks mid-run."""
+        m = self.model
+        m._ensure_batch(self.max_live)
+        m._select_kernels(2)  # MD_TILE_PINNED: a request's bits do not depend on what else is launched
+        top = self.sched.buckets[-1]
+        m._decode_logits(top)
+        m._workspace(m.lib.md_decode_workspace_bytes(C.byref(m.w.text), top), 2)
+        self._kv_ptr = m._kv_k.data_ptr()
+
+    def run_text(self) -> Iterator[Tuple[int, str]]:
+        for rid, ids in self.run():
+            yield rid, self.model.tokenizer.decode(ids)
+
+    def generate(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
+                 eos_id: Optional[int] = None, ignore_eos: bool = False, seeds: Optional[Sequence[Optional[int]]] = None,
+                 variant: Optional[str] = None) -> List[List[int]]:
+        """Ids for (images[i], prompts[i]) in input order; ``max_tokens`` one int or one per request."""
+        n = len(images)
+        if len(prompts) != n:
+            raise ValueError("images and prompts differ in length")
+        mt = [int(max_tokens)] * n if isinstance(max_tokens, (int, np.integer)) else [int(x) for x in max_tokens]
+        if len(mt) != n:
+            raise ValueError("one max_tokens per request")
+        seeds = list(seeds) if seeds is not None else [None] * n
+        rids = [self.submit(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant) for i in range(n)]
+        got = dict(self.run())
+        return [got[r] for r in rids]
+
+    # ---- the GPU side of the schedule
+    def _generator(self, r: Request):
+        import torch
+
+        if r.generator is None:
+            g = torch.Generator()
+            if r.seed is None:
+                g.seed()
+            else:
+                g.manual_seed(int(r.seed))
+            r.generator = g
+        return r.generator
+
+    def _uniforms(self, r: Request, n: int):
+        import torch
+
+        return torch.rand(n, dtype=torch.float32, generator=self._generator(r))
+
+    def _forward_slots(self, x, pos0: int, slots: List[int]):
+        """x [k, T, D] -> hidden [k, T, D] through md_text_forward_slots; K / V rows written into ``slots``."""
+        import torch
+
+        from . import _lib
+
+        m = self.model
+        k, t, _ = x.shape
+        x = x.contiguous()
+        hidden = torch.empty_like(x)
+        pos_d = torch.full((k,), int(pos0), dtype=torch.int32, device=m.device)
+        slots_d = m._h2d(torch.tensor(slots, dtype=torch.int32))
+        ws = m._workspace(m.lib.md_text_workspace_bytes(C.byref(m.w.text), k, t))
+        kv = m._kv_struct(0)
+        _lib.check(m.lib.md_text_forward_slots(C.byref(m.w.text), x.data_ptr(), hidden.data_ptr(), k, t, pos_d.data_ptr(),
+                                               slots_d.data_ptr(), self.max_live, C.byref(kv), ws.data_ptr(), ws.numel(),
+                                               m._stream()), "md_text_forward_slots")
+        self.stats.prefill_passes += 1
+        return hidden
+
+    def _first_tokens(self, hidden, reqs: List[Request]):
+        """hidden [k, T, D] of a prefill -> the first token of each request from its last row, as _prepare_sequences picks it (argmax, or
+        md_sample_top_p with the request's first uniform; no suppression).  lm_head in launches of <= 64 rows: the
+        decode-regime kernels, whatever the admission size."""
+        import torch
+
+        from . import _lib
+
+        m = self.model
+        out = []
+        for i0 in range(0, len(reqs), 64):
+            part = reqs[i0 : i0 + 64]
+            lg = m._lm_head(hidden[i0 : i0 + len(part)])
+            if self.temperature == 0:
+                out.append(m._pick(lg, 0.0, 0.0))
+                continue
+            u = m._h2d(torch.cat([self._uniforms(r, 1) for r in part]))
+            nxt = torch.empty(len(part), dtype=torch.int32, device=m.device)
+            _lib.check(m.lib.md_sample_top_p(lg.data_ptr(), lg.stride(0), len(part), m.config.text.vocab_size, -1, self.temperature,
+                                             self.top_p, u.data_ptr(), nxt.data_ptr(), None, 0, m._stream()), "md_sample_top_p")
+            out.append(nxt)
+        return torch.cat(out)
+
+    def _admit(self, reqs: List[Request]) -> List[Tuple[int, int]]:
+        """ViT over the admitted raw images as one batch, then the prefill into their slots with the choices of
+        _prepare_sequences: [bos | image | prompt] in one pass per prompt length when every image is raw and
+        ``fused_prefill`` is on; otherwise [bos | image] passes and EncodedImage slot copies, then one prompt pass per
+        (prefix, prompt length) in launches of <= 64 rows."""
+        import torch
+        from PIL import Image
+
+        m = self.model
+        tk = m.config.tokenizer
+        m._select_kernels(2)  # (again: another call on the model may have run between two chunks of this generator)
+        raw = [i for i, r in enumerate(reqs) if isinstance(r.image, Image.Image)]
+        img_emb = m._run_vision_encoder_batch([reqs[i].image for i in raw]) if raw else None
+        emb_of = {i: j for j, i in enumerate(raw)}
+        firsts: Dict[int, int] = {}
+        pos_of: Dict[int, int] = {}
+
+        def groups(keyf):
+            g: Dict[object, List[int]] = {}
+            for i in range(len(reqs)):
+                g.setdefault(keyf(i), []).append(i)
+            return list(g.values())
+
+        if len(raw) == len(reqs) and m.fused_prefill:
+            for idx in groups(lambda i: len(reqs[i].prompt)):
+                k = len(idx)
+                bos = m._embed(torch.full((k, 1), tk.bos_id, dtype=torch.int32))
+                pe = m._embed(torch.tensor([reqs[i].prompt for i in idx], dtype=torch.int32))
+                x = torch.cat([bos, img_emb[[emb_of[i] for i in idx]], pe], dim=1)
+                hidden = self._forward_slots(x, 0, [reqs[i].slot for i in idx])
+                first = self._first_tokens(hidden, [reqs[i] for i in idx]).tolist()
+                for i, f in zip(idx, first):
+                    firsts[i], pos_of[i] = int(f), x.shape[1]
+        else:
+            prefix: Dict[int, int] = {}
+            if raw:
+                bos = m._embed(torch.full((len(raw), 1), tk.bos_id, dtype=torch.int32))
+                x = torch.cat([bos, img_emb], dim=1)
+                self._forward_slots(x, 0, [reqs[i].slot for i in raw])
+                for i in raw:
+                    prefix[i] = x.shape[1]
+            for i, r in enumerate(reqs):
+                if i not in prefix:
+                    m.load_encoded_image(r.image, r.slot)
+                    prefix[i] = int(r.image.pos)
+            for idx in groups(lambda i: (prefix[i], len(reqs[i].prompt))):
+                t = len(reqs[idx[0]].prompt)
+                per = max(1, 64 // t) if t <= 64 else len(idx)
+                for j0 in range(0, len(idx), per):
+                    sub = idx[j0 : j0 + per]
+                    pe = m._embed(torch.tensor([reqs[i].prompt for i in sub], dtype=torch.int32))
+                    hidden = self._forward_slots(pe, prefix[sub[0]], [reqs[i].slot for i in sub])
+                    first = self._first_tokens(hidden, [reqs[i] for i in sub]).tolist()
+                    for i, f in zip(sub, first):
+                        firsts[i], pos_of[i] = int(f), prefix[i] + t
+        return [(firsts[i], pos_of[i]) for i in range(len(reqs))]
+
+    def _buffers(self, bucket: int):
+        """Fixed-address buffers of a (chunk, bucket): int32 device state [slots (chunk x bucket) | pos (bucket) | tokens ((chunk + 1) x
+        bucket)] with its pinned host staging (one H2D copy of everything a chunk reads), and fp32 uniforms [chunk x bucket]."""
+        import torch
+
+        bufs = self.model.__dict__.setdefault("_continuous_bufs", {})  # on the model: engines of one model share captured chunks
+        key = (self.chunk, bucket)
+        b = bufs.get(key)
+        if b is None:
+            c = self.chunk
+            n_in = c * bucket + bucket + bucket
+            dev = torch.zeros(n_in + c * bucket, dtype=torch.int32, device=self.model.device)
+            with torch.inference_mode(False):
+                host = torch.zeros(n_in, dtype=torch.int32, pin_memory=True)
+                u_host = torch.zeros(c * bucket, dtype=torch.float32, pin_memory=True)
+            u_dev = torch.zeros(c * bucket, dtype=torch.float32, device=self.model.device)
+            b = bufs[key] = (dev, host, u_dev, u_host, n_in)
+        return b
+
+    def _step(self, plan: ChunkPlan) -> np.ndarray:
+        import torch
+
+        from . import _lib
+
+        m = self.model
+        if m._kv_k.data_ptr() != self._kv_ptr:
+            raise RuntimeError("the KV slab was reallocated during a continuous-batching run")
+        t = m.config.text
+        c, B, n = self.chunk, plan.bucket, plan.n
+        dev, host, u_dev, u_host, n_in = self._buffers(B)
+        slots_d = dev[: c * B].view(c, B)
+        pos_d = dev[c * B : c * B + B]
+        hist = dev[c * B + B :].view(c + 1, B)
+        hs = host.numpy()
+        hs[: c * B].reshape(c, B)[:n] = plan.slots
+        hs[c * B : c * B + B] = plan.pos
+        hs[c * B + B :] = plan.tokens
+        dev[:n_in].copy_(host, non_blocking=True)
+        sample = self.temperature != 0
+        if sample:
+            uh = u_host.numpy().reshape(c, B)
+            uh[:] = 0.5
+            for r_idx, r in enumerate(plan.rows):
+                k = min(n, r.remaining)
+                uh[:k, r_idx] = self._uniforms(r, k).numpy()
+            u_dev.copy_(u_host, non_blocking=True)
+        u2 = u_dev.view(c, B)
+        logits = m._decode_logits(B)
+        ws = m._workspace(m.lib.md_decode_workspace_bytes(C.byref(m.w.text), B), 2)
+        kv = m._kv_struct(0)
+
+        def one_step(i):
+            _lib.check(m.lib.md_decode_step_slots(C.byref(m.w.text), hist[i].data_ptr(), hist[i + 1].data_ptr(), pos_d.data_ptr(), B,
+                                                  slots_d[i].data_ptr(), self.max_live, C.byref(kv), m.config.tokenizer.answer_id,
+                                                  logits.data_ptr(), t.vocab_size, ws.data_ptr(), ws.numel(), m._stream()),
+                       "md_decode_step_slots")
+            if sample:  # the step left its logits in ``logits``: draw from them instead of the argmax it wrote
+                _lib.check(m.lib.md_sample_top_p(logits.data_ptr(), logits.stride(0), B, t.vocab_size, m.config.tokenizer.answer_id,
+                                                 self.temperature, self.top_p, u2[i].data_ptr(), hist[i + 1].data_ptr(), None, 0,
+                                                 m._stream()), "md_sample_top_p")
+
+        if not m.use_graphs:
+            for i in range(n):
+                one_step(i)
+        else:
+            stream = torch.cuda.current_stream(m.device).cuda_stream
+            key = ("continuous", stream, B, n, dev.data_ptr(), ws.data_ptr(), m._kv_k.data_ptr(), logits.data_ptr(), self.temperature,
+                   self.top_p)
+            g = m._graphs.get(key)
+            if g is not None:
+                g.replay()
+            else:
+                for i in range(n):  # the first chunk of a shape runs eagerly (KV side effects: no warm-up on scratch state)
+                    one_step(i)
+                ours = [k for k in m._graphs if isinstance(k, tuple) and k and k[0] == "continuous" and k[1] == stream]
+                if len(ours) < MAX_GRAPHS:
+                    torch.cuda.synchronize(m.device)
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        for i in range(n):
+                            one_step(i)
+                    m._graphs[key] = g  # captured, not executed
+                    self.stats.graph_captures += 1
+        return hist[1 : n + 1].cpu().numpy()  # the chunk's one D2H copy (the lockstep loop syncs here too)

@@ -198,12 +198,14 @@ TextWs text_layout(const md_text_model* m, int batch, int q_len, void* base) {
 // per token row of a prefill: the (cos, sin) row of its position and its byte offset in a layer's K / V slab -- what the fused
 // RoPE / KV-write epilogue of the qkv GEMM (MD_EPI_QKV_ROPE) needs per row, computed once per forward for all layers
 __global__ __launch_bounds__(256) void rope_rowinfo_kernel(const int32_t* __restrict__ pos0, const float* __restrict__ freqs, float* __restrict__ row_cs,
-                                                           uint32_t* __restrict__ row_kv, int q_len, int rows, int64_t slab_bs, int hd, int half2) {
+                                                           uint32_t* __restrict__ row_kv, int q_len, int rows, int64_t slab_bs, int hd, int half2,
+                                                           const int32_t* __restrict__ slots) {
   const int m = blockIdx.x * 8 + (threadIdx.x >> 5), l = threadIdx.x & 31;
   if (m >= rows) return;
   const int b = m / q_len, t = m - b * q_len, pos = pos0[b] + t;
+  const int64_t sb = slots ? slots[b] : b;  // slot table of md_text_forward_slots (prefill: every slot valid)
   if (l < half2) row_cs[(int64_t)m * half2 + l] = freqs[(int64_t)pos * half2 + l];
-  if (l == 0) row_kv[m] = (uint32_t)(((int64_t)b * slab_bs + (int64_t)pos * hd) * 2);
+  if (l == 0) row_kv[m] = (uint32_t)((sb * slab_bs + (int64_t)pos * hd) * 2);
 }
 
 __global__ void kv_len_kernel(const int32_t* pos0, int32_t* kv_len, int q_len, int n) {
@@ -411,20 +413,44 @@ extern "C" size_t md_text_workspace_bytes(const md_text_model* m, int32_t batch,
   return need;
 }
 
+// the slot-table forms of the kernels' host entry points (slots == nullptr: sequence b in slot b)
 md_status md_kv_quantize_f8_layer(const md_kv_cache* kv, int layer, const int32_t* pos0, int pos_fixed, int batch, int n_heads, int n_pos,
-                                  hipStream_t s);
+                                  hipStream_t s, const int32_t* slots, int n_slots);
 md_status md_attention_decode_rope_f8_launch(const void* qkv, int64_t ld, void* o, int64_t ldo, const float* freqs, void* k_slab, void* v_slab,
                                              void* k8_slab, void* v8_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len,
                                              int32_t batch, int32_t n_heads, int32_t rot_dim, float scale, float k_scale, float v_scale,
-                                             hipStream_t s);
+                                             hipStream_t s, const int32_t* slots, int32_t n_slots);
+md_status md_rope_kv_write_slots(void* qkv, int64_t ld, const float* freqs, const int32_t* pos0, void* k_slab, void* v_slab,
+                                 int64_t slab_batch_stride, int32_t ctx, int32_t batch, int32_t q_len, int32_t n_heads,
+                                 int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim, const int32_t* slots, int32_t n_slots,
+                                 hipStream_t stream);
+md_status md_attention_prefill_slots(const md_attn_args* a, const int32_t* slots, hipStream_t stream);
+md_status md_attention_decode_slots(const void* q, int64_t ldq, void* o, int64_t ldo, const void* k_slab, const void* v_slab,
+                                    int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch, int32_t n_heads,
+                                    int32_t n_kv_heads, int32_t head_dim, float scale, const int32_t* slots, int32_t n_slots,
+                                    hipStream_t stream);
+md_status md_attention_decode_rope_slots(const void* qkv, int64_t ld, void* o, int64_t ldo, const float* freqs, void* k_slab,
+                                         void* v_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch,
+                                         int32_t n_heads, int32_t head_dim, int32_t rot_dim, float scale, const int32_t* slots,
+                                         int32_t n_slots, hipStream_t stream);
 
-// reference: text.py:128-160 (text_decoder) with text.py:16-60 (attn)
 extern "C" md_status md_text_forward(const md_text_model* m, const void* x_in, void* hidden,
                                      int32_t batch, int32_t q_len, const int32_t* pos0,
                                      const md_kv_cache* kv, void* workspace, size_t workspace_bytes,
                                      void* stream) {
+  return md_text_forward_slots(m, x_in, hidden, batch, q_len, pos0, nullptr, 0, kv, workspace, workspace_bytes, stream);
+}
+
+// reference: text.py:128-160 (text_decoder) with text.py:16-60 (attn).  slots == nullptr: sequence b in slot b (md_text_forward);
+// otherwise every place that addresses a slab -- the RoPE / KV-write epilogue's row offsets, rope_kv_kernel, the prefill and
+// decode attention, the e4m3 copy -- takes slot slots[b], and a decode row whose slot is outside [0, n_slots) is idle.
+extern "C" md_status md_text_forward_slots(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
+                                           const int32_t* pos0, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
   MD_CHECK_ARG(m && x_in && hidden && pos0 && kv && kv->k && kv->v && workspace && m->blocks);
   MD_CHECK_ARG(batch > 0 && q_len > 0 && m->dim % m->n_heads == 0);
+  MD_CHECK_ARG(slots == nullptr || n_slots > 0);
+  if (slots == nullptr) n_slots = batch;  // the slots a contiguous call addresses
   MD_CHECK_ARG(tile_policy_ok(m->tile_policy));
   TilePolicyScope tile_scope(m->tile_policy);
   // the e4m3 copy of the KV cache (fp8 mode) keeps the 64-row blocks: its attention kernel is part of an opt-in mode tuned there
@@ -436,14 +462,19 @@ extern "C" md_status md_text_forward(const md_text_model* m, const void* x_in, v
     // streamed once per block; the big-tile kernels this replaces ran the step ~1.5x slower at 128 rows.
     for (int b0 = 0; b0 < batch; b0 += block_rows) {
       const int nb = std::min(block_rows, batch - b0);
+      const void* xb = (const char*)x_in + (int64_t)b0 * m->dim * 2;
+      void* hb = (char*)hidden + (int64_t)b0 * m->dim * 2;
+      if (slots != nullptr) {  // slot table: the slab base stays, the block's rows take their own entries of the table
+        MD_TRY(md_text_forward_slots(m, xb, hb, nb, 1, pos0 + b0, slots + b0, n_slots, kv, workspace, workspace_bytes, stream));
+        continue;
+      }
       md_kv_cache sub = *kv;
       sub.k = (char*)kv->k + (int64_t)b0 * kv->batch_stride * 2;
       sub.v = (char*)kv->v + (int64_t)b0 * kv->batch_stride * 2;
       // the e4m3 copy of the cache (fp8 mode) has the same slot layout at one byte per element
       if (kv->k8) sub.k8 = (char*)kv->k8 + (int64_t)b0 * kv->batch_stride;
       if (kv->v8) sub.v8 = (char*)kv->v8 + (int64_t)b0 * kv->batch_stride;
-      MD_TRY(md_text_forward(m, (const char*)x_in + (int64_t)b0 * m->dim * 2, (char*)hidden + (int64_t)b0 * m->dim * 2, nb, 1,
-                             pos0 + b0, &sub, workspace, workspace_bytes, stream));
+      MD_TRY(md_text_forward_slots(m, xb, hb, nb, 1, pos0 + b0, nullptr, 0, &sub, workspace, workspace_bytes, stream));
     }
     return MD_OK;
   }
@@ -481,10 +512,10 @@ extern "C" md_status md_text_forward(const md_text_model* m, const void* x_in, v
   // shape: MHA, head_dim 64, rot_dim 32, slab offsets in 32 bits.  Per-row positions / slab offsets once per forward.
   const uint64_t slab_bytes = (uint64_t)kv->layer_stride * 2;
   bool rope_in_gemm = w.rope_cs != nullptr && q_len > 1 && M > 64 && m->n_kv_heads == m->n_heads && hd == 64 && m->rot_dim == 32 &&
-                      m->blocks[0].qkv_fc1.w != nullptr && slab_bytes < 0xfffff000ull && kv->layer_stride >= (int64_t)batch * kv->batch_stride;
+                      m->blocks[0].qkv_fc1.w != nullptr && slab_bytes < 0xfffff000ull && kv->layer_stride >= (int64_t)n_slots * kv->batch_stride;
   if (rope_in_gemm)
     hipLaunchKernelGGL(rope_rowinfo_kernel, dim3((M + 7) / 8), dim3(256), 0, s, pos0, m->freqs, w.rope_cs, w.rope_kv, q_len, M,
-                       kv->batch_stride, hd, m->rot_dim);
+                       kv->batch_stride, hd, m->rot_dim, slots);
   bool rope_done = false;  // set per block when the fused launch took it
   bool rope_done_kv8 = false;  // ... and also wrote the e4m3 copy of the rows (fp8 mode)
 
@@ -493,21 +524,21 @@ extern "C" md_status md_text_forward(const md_text_model* m, const void* x_in, v
     bf16_t* kl = (bf16_t*)kv->k + (int64_t)l * kv->layer_stride;
     bf16_t* vl = (bf16_t*)kv->v + (int64_t)l * kv->layer_stride;
     if (!fuse_rope && !rope_done)
-      MD_TRY(md_rope_kv_write(w.qkv, qld, m->freqs, pos0, kl, vl, kv->batch_stride, kv->ctx, batch,
-                              q_len, m->n_heads, m->n_kv_heads, hd, m->rot_dim, s));
+      MD_TRY(md_rope_kv_write_slots(w.qkv, qld, m->freqs, pos0, kl, vl, kv->batch_stride, kv->ctx, batch,
+                                    q_len, m->n_heads, m->n_kv_heads, hd, m->rot_dim, slots, n_slots, s));
     // attention over the slab                                   (text.py:48-51)
     const bool kv8 = kv->k8 && kv->v8 && kv->k_scale && kv->v_scale && m->n_kv_heads == m->n_heads && hd == 64;
     if (fuse_rope && kv8) {
       // fp8 mode: the step attends over the e4m3 copy of the cache and writes the new row into both copies
       MD_TRY(md_attention_decode_rope_f8_launch(w.qkv, qld, w.att, Dp, m->freqs, kl, vl, (uint8_t*)kv->k8 + (int64_t)l * kv->layer_stride,
                                                 (uint8_t*)kv->v8 + (int64_t)l * kv->layer_stride, kv->batch_stride, kv->ctx, kv_len, batch,
-                                                m->n_heads, m->rot_dim, scale, kv->k_scale[l], kv->v_scale[l], s));
+                                                m->n_heads, m->rot_dim, scale, kv->k_scale[l], kv->v_scale[l], s, slots, n_slots));
     } else if (fuse_rope) {
-      MD_TRY(md_attention_decode_rope(w.qkv, qld, w.att, Dp, m->freqs, kl, vl, kv->batch_stride, kv->ctx, kv_len,
-                                      batch, m->n_heads, hd, m->rot_dim, scale, s));
+      MD_TRY(md_attention_decode_rope_slots(w.qkv, qld, w.att, Dp, m->freqs, kl, vl, kv->batch_stride, kv->ctx, kv_len,
+                                            batch, m->n_heads, hd, m->rot_dim, scale, slots, n_slots, s));
     } else if (q_len == 1) {
-      MD_TRY(md_attention_decode(w.qkv, qld, w.att, Dp, kl, vl, kv->batch_stride, kv->ctx, kv_len, batch,
-                                 m->n_heads, m->n_kv_heads, hd, scale, s));
+      MD_TRY(md_attention_decode_slots(w.qkv, qld, w.att, Dp, kl, vl, kv->batch_stride, kv->ctx, kv_len, batch,
+                                       m->n_heads, m->n_kv_heads, hd, scale, slots, n_slots, s));
     } else {
       md_attn_args a = {};
       a.q = w.qkv;
@@ -540,10 +571,10 @@ extern "C" md_status md_text_forward(const md_text_model* m, const void* x_in, v
         a.o8_ts = Dp;
         a.o8_inv_scale = att8_inv_scale;
       }
-      MD_TRY(md_attention_prefill(&a, s));
+      MD_TRY(md_attention_prefill_slots(&a, slots, s));
     }
     // fp8 mode: the rows this pass wrote (bf16) also go into the e4m3 copy the decode steps read
-    if (kv8 && !fuse_rope && !rope_done_kv8) MD_TRY(md_kv_quantize_f8_layer(kv, l, pos0, 0, batch, m->n_heads, q_len, s));
+    if (kv8 && !fuse_rope && !rope_done_kv8) MD_TRY(md_kv_quantize_f8_layer(kv, l, pos0, 0, batch, m->n_heads, q_len, s, slots, n_slots));
     return MD_OK;
   };
 
@@ -801,12 +832,21 @@ extern "C" size_t md_decode_workspace_bytes(const md_text_model* m, int32_t batc
          md_text_workspace_bytes(m, batch, 1);
 }
 
-// reference: the generator loop body of moondream.py:512-530, device resident
 extern "C" md_status md_decode_step(const md_text_model* m, const int32_t* tokens, int32_t* next,
                                     int32_t* pos, int32_t batch, const md_kv_cache* kv,
                                     int32_t suppress_id, void* logits, int64_t ld_logits,
                                     void* workspace, size_t workspace_bytes, void* stream) {
+  return md_decode_step_slots(m, tokens, next, pos, batch, nullptr, 0, kv, suppress_id, logits, ld_logits, workspace,
+                              workspace_bytes, stream);
+}
+
+// reference: the generator loop body of moondream.py:512-530, device resident; slots as in md_text_forward_slots
+extern "C" md_status md_decode_step_slots(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos,
+                                          int32_t batch, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
+                                          int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
   MD_CHECK_ARG(m && tokens && next && pos && kv && logits && workspace && batch > 0);
+  MD_CHECK_ARG(slots == nullptr || n_slots > 0);
   if (workspace_bytes < md_decode_workspace_bytes(m, batch)) return MD_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   Arena a{(char*)workspace, 0};
@@ -815,7 +855,7 @@ extern "C" md_status md_decode_step(const md_text_model* m, const int32_t* token
   void* tws = a.take(0);
   const size_t tws_bytes = workspace_bytes - a.off;
   MD_TRY(md_embed_tokens(tokens, m->wte, m->dim, x, m->dim, batch, m->dim, s));
-  MD_TRY(md_text_forward(m, x, x, batch, 1, pos, kv, tws, tws_bytes, s));
+  MD_TRY(md_text_forward_slots(m, x, x, batch, 1, pos, slots, n_slots, kv, tws, tws_bytes, s));
   if (decode_tall_rows(m, batch, 1) && !(kv->k8 && kv->v8)) {
     // the step's lm_head at 65 .. 128 rows: the by-shape config of the same MFMA family as the <= 64-row regime (never the
     // pinned four-wave kernel: a sequence must get the same logits in a step of 128 as in a step of 64)

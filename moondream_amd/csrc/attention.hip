@@ -48,6 +48,7 @@ struct AttnK {
   int64_t o8_bs, o8_ts;
   float o8_inv_scale;
   int head_dim;
+  const int32_t* slots;  // md_text_forward_slots: sequence b's K / V rows are those of slot slots[b] (nullptr: slot b); q / o stay row-indexed
   int skip_dead;  // LDS-DMA prefill kernel, exact work skipping: bit 0 = the second 32-key half of a last tile with no live key in it, bit 1 = waves with no live query row
 };
 
@@ -117,8 +118,9 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const AttnK p) {
     for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
 
-  const bf16_t* kbase = p.k + (int64_t)b * p.k_bs + (int64_t)hk * p.k_hs;
-  const bf16_t* vbase = p.v + (int64_t)b * p.v_bs + (int64_t)hk * p.v_hs;
+  const int64_t kvb = p.slots ? p.slots[b] : b;
+  const bf16_t* kbase = p.k + kvb * p.k_bs + (int64_t)hk * p.k_hs;
+  const bf16_t* vbase = p.v + kvb * p.v_bs + (int64_t)hk * p.v_hs;
 
   // ---- K/V staging, split (cdna guide T14): the global loads of tile t+1 are issued
   // before tile t is computed and written to LDS after it, so their latency hides
@@ -380,8 +382,9 @@ __global__ __launch_bounds__(256) void attn_prefill_dma_kernel(const AttnK p) {
     for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
 
-  const bf16_t* kbase = p.k + (int64_t)b * p.k_bs + (int64_t)hk * p.k_hs;
-  const bf16_t* vbase = p.v + (int64_t)b * p.v_bs + (int64_t)hk * p.v_hs;
+  const int64_t kvb = p.slots ? p.slots[b] : b;
+  const bf16_t* kbase = p.k + kvb * p.k_bs + (int64_t)hk * p.k_hs;
+  const bf16_t* vbase = p.v + kvb * p.v_bs + (int64_t)hk * p.v_hs;
 
   // LDS-DMA pieces: chunk c = 256 j + tid of the tile image, lane-linear in LDS.  The source
   // pointers run ahead one tile per issue; only a tile that reaches past kv_len (the last one)
@@ -653,7 +656,8 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* __re
                                                               bf16_t* __restrict__ vslab,
                                                               int64_t slab_bs, int ctx, const int32_t* kv_len_p,
                                                               int n_heads, int kv_group, float scale_log2,
-                                                              const float* __restrict__ freqs, int rot) {
+                                                              const float* __restrict__ freqs, int rot,
+                                                              const int32_t* __restrict__ slots, int n_slots) {
   static_assert(NW == 4 || NW == 16, "waves per workgroup");
   constexpr int CPT = 16 / NW;            // classes per thread group
   constexpr int NU = (NW == 16) ? 4 : 1;  // class quarters that live in different waves
@@ -668,10 +672,20 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* __re
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 3, c = lane & 7;
   const int b = blockIdx.y, h = blockIdx.x, hk = h / kv_group;
+  // slot table (md_text_forward_slots): row b's K / V live in slot slots[b].  A slot outside [0, n_slots) is an IDLE row:
+  // zero output, no slab read or write (uniform per workgroup, before any barrier)
+  int sb = b;
+  if (slots != nullptr) {
+    sb = slots[b];
+    if (sb < 0 || sb >= n_slots) {
+      if (tid < 64) o[(int64_t)b * ldo + h * 64 + tid] = f2bf(0.f);
+      return;
+    }
+  }
   const int kv_len = kv_len_p[b];
   const int pos = kv_len - 1;
-  bf16_t* kb = kslab + (int64_t)b * slab_bs + (int64_t)hk * ctx * 64;
-  bf16_t* vb = vslab + (int64_t)b * slab_bs + (int64_t)hk * ctx * 64;
+  bf16_t* kb = kslab + (int64_t)sb * slab_bs + (int64_t)hk * ctx * 64;
+  bf16_t* vb = vslab + (int64_t)sb * slab_bs + (int64_t)hk * ctx * 64;
   // residue and first class of this thread group
   const int res = (NW == 16) ? ((wave & 3) * 8 + g) : (wave * 8 + g);
   const int u0 = (NW == 16) ? (wave >> 2) : 0;
@@ -838,7 +852,8 @@ bool decode_attn_nt() {  // MD_ATTN_DECODE_NT=0: plain loads (A/B)
 
 }  // namespace
 
-extern "C" md_status md_attention_prefill(const md_attn_args* a, void* stream) {
+// internal (api.hip): md_attention_prefill with the slot table of md_text_forward_slots (slots == nullptr: slot b)
+md_status md_attention_prefill_slots(const md_attn_args* a, const int32_t* slots, hipStream_t stream) {
   MD_CHECK_ARG(a && a->q && a->k && a->v && (a->o || a->o8));
   MD_CHECK_ARG(a->batch > 0 && a->n_heads > 0 && a->n_kv_heads > 0 && a->q_len > 0);
   MD_CHECK_ARG(a->n_heads % a->n_kv_heads == 0);
@@ -867,6 +882,7 @@ extern "C" md_status md_attention_prefill(const md_attn_args* a, void* stream) {
   k.kv_len = a->kv_len;
   k.scale_log2 = a->scale * 1.4426950408889634f;
   k.skip_dead = g_attn_skip_dead;
+  k.slots = slots;
   k.o8 = (uint8_t*)a->o8;
   k.o8_bs = a->o8_bs;
   k.o8_ts = a->o8_ts;
@@ -877,7 +893,7 @@ extern "C" md_status md_attention_prefill(const md_attn_args* a, void* stream) {
   k.n_bh = a->batch * a->n_heads;
   k.n_heads = a->n_heads;
   const dim3 grid1(8 * k.n_qblk * ((k.n_bh + 7) / 8));
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = stream;
   // MD_ATTN_VARIANT = reg | dma (default) | pipe for A/B runs
   static const int variant = [] {
     const char* e = getenv("MD_ATTN_VARIANT");
@@ -904,28 +920,66 @@ extern "C" md_status md_attention_prefill(const md_attn_args* a, void* stream) {
   return md_launch_status();
 }
 
+extern "C" md_status md_attention_prefill(const md_attn_args* a, void* stream) {
+  return md_attention_prefill_slots(a, nullptr, (hipStream_t)stream);
+}
+
+// internal (api.hip): md_attention_decode with the slot table of md_text_forward_slots (slots == nullptr: slot b)
+md_status md_attention_decode_slots(const void* q, int64_t ldq, void* o, int64_t ldo, const void* k_slab, const void* v_slab,
+                                    int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch, int32_t n_heads,
+                                    int32_t n_kv_heads, int32_t head_dim, float scale, const int32_t* slots, int32_t n_slots,
+                                    hipStream_t stream) {
+  MD_CHECK_ARG(q && o && k_slab && v_slab && kv_len);
+  MD_CHECK_ARG(head_dim == 64 && ctx <= DEC_MAX_CTX && batch > 0 && n_heads % n_kv_heads == 0);
+  MD_CHECK_ARG(ldq % 8 == 0 && ldo % 8 == 0 && ldq >= n_heads * 64 && ldo >= n_heads * 64);
+  if (decode_attn_waves(batch, n_heads) == 16)
+    hipLaunchKernelGGL((attn_decode_kernel<false, 16>), dim3(n_heads, batch), dim3(1024), 0, stream,
+                       (const bf16_t*)q, ldq, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
+                       slab_batch_stride, ctx, kv_len, n_heads, n_heads / n_kv_heads,
+                       scale * 1.4426950408889634f, (const float*)nullptr, 0, slots, n_slots);
+  else if (n_heads == n_kv_heads && decode_attn_nt())
+    hipLaunchKernelGGL((attn_decode_kernel<false, 4, true>), dim3(n_heads, batch), dim3(256), 0, stream,
+                       (const bf16_t*)q, ldq, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
+                       slab_batch_stride, ctx, kv_len, n_heads, 1, scale * 1.4426950408889634f, (const float*)nullptr, 0,
+                       slots, n_slots);
+  else
+    hipLaunchKernelGGL((attn_decode_kernel<false, 4>), dim3(n_heads, batch), dim3(256), 0, stream,
+                       (const bf16_t*)q, ldq, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
+                       slab_batch_stride, ctx, kv_len, n_heads, n_heads / n_kv_heads,
+                       scale * 1.4426950408889634f, (const float*)nullptr, 0, slots, n_slots);
+  return md_launch_status();
+}
+
 extern "C" md_status md_attention_decode(const void* q, int64_t ldq, void* o, int64_t ldo,
                                          const void* k_slab, const void* v_slab,
                                          int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len,
                                          int32_t batch, int32_t n_heads, int32_t n_kv_heads,
                                          int32_t head_dim, float scale, void* stream) {
-  MD_CHECK_ARG(q && o && k_slab && v_slab && kv_len);
-  MD_CHECK_ARG(head_dim == 64 && ctx <= DEC_MAX_CTX && batch > 0 && n_heads % n_kv_heads == 0);
-  MD_CHECK_ARG(ldq % 8 == 0 && ldo % 8 == 0 && ldq >= n_heads * 64 && ldo >= n_heads * 64);
+  return md_attention_decode_slots(q, ldq, o, ldo, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads, n_kv_heads,
+                                   head_dim, scale, nullptr, 0, (hipStream_t)stream);
+}
+
+// internal (api.hip): md_attention_decode_rope with the slot table of md_text_forward_slots (slots == nullptr: slot b)
+md_status md_attention_decode_rope_slots(const void* qkv, int64_t ld, void* o, int64_t ldo, const float* freqs, void* k_slab,
+                                         void* v_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch,
+                                         int32_t n_heads, int32_t head_dim, int32_t rot_dim, float scale, const int32_t* slots,
+                                         int32_t n_slots, hipStream_t stream) {
+  MD_CHECK_ARG(qkv && o && freqs && k_slab && v_slab && kv_len);
+  MD_CHECK_ARG(head_dim == 64 && ctx <= DEC_MAX_CTX && batch > 0 && n_heads > 0);
+  MD_CHECK_ARG(rot_dim % 2 == 0 && rot_dim > 0 && rot_dim <= 64 && ld % 8 == 0 && ldo % 8 == 0);
+  MD_CHECK_ARG(ld >= 3 * n_heads * 64 && ldo >= n_heads * 64);
   if (decode_attn_waves(batch, n_heads) == 16)
-    hipLaunchKernelGGL((attn_decode_kernel<false, 16>), dim3(n_heads, batch), dim3(1024), 0, (hipStream_t)stream,
-                       (const bf16_t*)q, ldq, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                       slab_batch_stride, ctx, kv_len, n_heads, n_heads / n_kv_heads,
-                       scale * 1.4426950408889634f, (const float*)nullptr, 0);
-  else if (n_heads == n_kv_heads && decode_attn_nt())
-    hipLaunchKernelGGL((attn_decode_kernel<false, 4, true>), dim3(n_heads, batch), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)q, ldq, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                       slab_batch_stride, ctx, kv_len, n_heads, 1, scale * 1.4426950408889634f, (const float*)nullptr, 0);
+    hipLaunchKernelGGL((attn_decode_kernel<true, 16>), dim3(n_heads, batch), dim3(1024), 0, stream,
+                       (const bf16_t*)qkv, ld, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
+                       slab_batch_stride, ctx, kv_len, n_heads, 1, scale * 1.4426950408889634f, freqs, rot_dim, slots, n_slots);
+  else if (decode_attn_nt())
+    hipLaunchKernelGGL((attn_decode_kernel<true, 4, true>), dim3(n_heads, batch), dim3(256), 0, stream,
+                       (const bf16_t*)qkv, ld, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
+                       slab_batch_stride, ctx, kv_len, n_heads, 1, scale * 1.4426950408889634f, freqs, rot_dim, slots, n_slots);
   else
-    hipLaunchKernelGGL((attn_decode_kernel<false, 4>), dim3(n_heads, batch), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)q, ldq, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                       slab_batch_stride, ctx, kv_len, n_heads, n_heads / n_kv_heads,
-                       scale * 1.4426950408889634f, (const float*)nullptr, 0);
+    hipLaunchKernelGGL((attn_decode_kernel<true, 4>), dim3(n_heads, batch), dim3(256), 0, stream,
+                       (const bf16_t*)qkv, ld, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
+                       slab_batch_stride, ctx, kv_len, n_heads, 1, scale * 1.4426950408889634f, freqs, rot_dim, slots, n_slots);
   return md_launch_status();
 }
 
@@ -934,21 +988,6 @@ extern "C" md_status md_attention_decode_rope(const void* qkv, int64_t ld, void*
                                               int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len,
                                               int32_t batch, int32_t n_heads, int32_t head_dim,
                                               int32_t rot_dim, float scale, void* stream) {
-  MD_CHECK_ARG(qkv && o && freqs && k_slab && v_slab && kv_len);
-  MD_CHECK_ARG(head_dim == 64 && ctx <= DEC_MAX_CTX && batch > 0 && n_heads > 0);
-  MD_CHECK_ARG(rot_dim % 2 == 0 && rot_dim > 0 && rot_dim <= 64 && ld % 8 == 0 && ldo % 8 == 0);
-  MD_CHECK_ARG(ld >= 3 * n_heads * 64 && ldo >= n_heads * 64);
-  if (decode_attn_waves(batch, n_heads) == 16)
-    hipLaunchKernelGGL((attn_decode_kernel<true, 16>), dim3(n_heads, batch), dim3(1024), 0, (hipStream_t)stream,
-                       (const bf16_t*)qkv, ld, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                       slab_batch_stride, ctx, kv_len, n_heads, 1, scale * 1.4426950408889634f, freqs, rot_dim);
-  else if (decode_attn_nt())
-    hipLaunchKernelGGL((attn_decode_kernel<true, 4, true>), dim3(n_heads, batch), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)qkv, ld, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                       slab_batch_stride, ctx, kv_len, n_heads, 1, scale * 1.4426950408889634f, freqs, rot_dim);
-  else
-    hipLaunchKernelGGL((attn_decode_kernel<true, 4>), dim3(n_heads, batch), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)qkv, ld, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                       slab_batch_stride, ctx, kv_len, n_heads, 1, scale * 1.4426950408889634f, freqs, rot_dim);
-  return md_launch_status();
+  return md_attention_decode_rope_slots(qkv, ld, o, ldo, freqs, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads,
+                                        head_dim, rot_dim, scale, nullptr, 0, (hipStream_t)stream);
 }

@@ -40,7 +40,8 @@ __device__ __forceinline__ float deq1(uint32_t byte) {  // one e4m3 byte (low 8 
 // 16-byte bf16 chunk (8 features) per thread
 __global__ __launch_bounds__(256) void kv_quantize_kernel(const bf16_t* __restrict__ ks, const bf16_t* __restrict__ vs, uint8_t* __restrict__ k8,
                                                           uint8_t* __restrict__ v8, float ik, float iv, const int32_t* __restrict__ pos0,
-                                                          int pos_fixed, int64_t batch_stride, int ctx, int batch, int n_heads, int n_pos) {
+                                                          int pos_fixed, int64_t batch_stride, int ctx, int batch, int n_heads, int n_pos,
+                                                          const int32_t* __restrict__ slots, int n_slots) {
   const int64_t total = (int64_t)batch * n_heads * n_pos * 8;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     int64_t r = i;
@@ -49,9 +50,11 @@ __global__ __launch_bounds__(256) void kv_quantize_kernel(const bf16_t* __restri
     const int t = (int)(r % n_pos);
     r /= n_pos;
     const int h = (int)(r % n_heads), b = (int)(r / n_heads);
+    const int sb = slots ? slots[b] : b;  // slot table (md_text_forward_slots); an idle row has no rows to quantise
+    if (sb < 0 || (slots && sb >= n_slots)) continue;
     const int pos = (pos0 ? pos0[b] : pos_fixed) + t;
     if (pos >= ctx) continue;
-    const int64_t off = (int64_t)b * batch_stride + ((int64_t)h * ctx + pos) * 64 + ch * 8;
+    const int64_t off = (int64_t)sb * batch_stride + ((int64_t)h * ctx + pos) * 64 + ch * 8;
     const u32x4 kq = *(const u32x4*)(ks + off), vq = *(const u32x4*)(vs + off);
     u32x2 ko, vo;
     ko[0] = pack_fp8x4(lo_bf(kq[0]) * ik, hi_bf(kq[0]) * ik, lo_bf(kq[1]) * ik, hi_bf(kq[1]) * ik);
@@ -70,7 +73,7 @@ __global__ __launch_bounds__(256) void attn_decode_f8_kernel(const bf16_t* __res
                                                              const float* __restrict__ freqs, bf16_t* __restrict__ kslab, bf16_t* __restrict__ vslab,
                                                              uint8_t* __restrict__ k8slab, uint8_t* __restrict__ v8slab, int64_t slab_bs, int ctx,
                                                              const int32_t* __restrict__ kv_len_p, int n_heads, float scale_log2, int rot,
-                                                             float k_scale, float v_scale) {
+                                                             float k_scale, float v_scale, const int32_t* __restrict__ slots, int n_slots) {
   __shared__ float sc[F8_MAX_CTX];
   __shared__ float red[64][64 + 1];  // [row group][feature | sum of p]
   __shared__ float red_m[4];
@@ -81,8 +84,18 @@ __global__ __launch_bounds__(256) void attn_decode_f8_kernel(const bf16_t* __res
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 2, c = lane & 3;
   const int b = blockIdx.y, h = blockIdx.x;
+  // slot table (md_text_forward_slots): row b's K / V live in slot slots[b]; an idle row (slot outside [0, n_slots)) writes a
+  // zero output and touches neither copy of the cache (uniform per workgroup, before any barrier)
+  int sb = b;
+  if (slots != nullptr) {
+    sb = slots[b];
+    if (sb < 0 || sb >= n_slots) {
+      if (tid < 64) o[(int64_t)b * ldo + h * 64 + tid] = f2bf(0.f);
+      return;
+    }
+  }
   const int kv_len = kv_len_p[b], pos = kv_len - 1;
-  const int64_t head_off = (int64_t)b * slab_bs + (int64_t)h * ctx * 64;
+  const int64_t head_off = (int64_t)sb * slab_bs + (int64_t)h * ctx * 64;
   const uint8_t* kb = k8slab + head_off;
   const uint8_t* vb = v8slab + head_off;
 
@@ -205,7 +218,7 @@ __global__ __launch_bounds__(256) void attn_decode_f8_kernel(const bf16_t* __res
 
 // internal (api.hip)
 md_status md_kv_quantize_f8_layer(const md_kv_cache* kv, int layer, const int32_t* pos0, int pos_fixed, int batch, int n_heads, int n_pos,
-                                  hipStream_t s) {
+                                  hipStream_t s, const int32_t* slots, int n_slots) {
   MD_CHECK_ARG(kv && kv->k && kv->v && kv->k8 && kv->v8 && kv->k_scale && kv->v_scale && kv->k_scale[layer] > 0.f && kv->v_scale[layer] > 0.f);
   const int64_t total = (int64_t)batch * n_heads * n_pos * 8;
   if (total <= 0) return MD_OK;
@@ -213,27 +226,28 @@ md_status md_kv_quantize_f8_layer(const md_kv_cache* kv, int layer, const int32_
   const int64_t lo = (int64_t)layer * kv->layer_stride;
   hipLaunchKernelGGL(kv_quantize_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)kv->k + lo, (const bf16_t*)kv->v + lo,
                      (uint8_t*)kv->k8 + lo, (uint8_t*)kv->v8 + lo, 1.0f / kv->k_scale[layer], 1.0f / kv->v_scale[layer], pos0, pos_fixed,
-                     kv->batch_stride, kv->ctx, batch, n_heads, n_pos);
+                     kv->batch_stride, kv->ctx, batch, n_heads, n_pos, slots, n_slots);
   return md_launch_status();
 }
 
 extern "C" md_status md_kv_quantize_f8(const md_kv_cache* kv, int32_t n_layers, int32_t batch, int32_t n_heads, const int32_t* pos0,
                                        int32_t pos_fixed, int32_t n_pos, void* stream) {
   MD_CHECK_ARG(kv && n_layers > 0 && batch > 0 && n_heads > 0 && n_pos > 0 && pos_fixed >= 0);
-  for (int l = 0; l < n_layers; ++l) MD_TRY(md_kv_quantize_f8_layer(kv, l, pos0, pos_fixed, batch, n_heads, n_pos, (hipStream_t)stream));
+  for (int l = 0; l < n_layers; ++l)
+    MD_TRY(md_kv_quantize_f8_layer(kv, l, pos0, pos_fixed, batch, n_heads, n_pos, (hipStream_t)stream, nullptr, 0));
   return MD_OK;
 }
 
 md_status md_attention_decode_rope_f8_launch(const void* qkv, int64_t ld, void* o, int64_t ldo, const float* freqs, void* k_slab, void* v_slab,
                                              void* k8_slab, void* v8_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len,
                                              int32_t batch, int32_t n_heads, int32_t rot_dim, float scale, float k_scale, float v_scale,
-                                             hipStream_t s) {
+                                             hipStream_t s, const int32_t* slots, int32_t n_slots) {
   MD_CHECK_ARG(qkv && o && freqs && k_slab && v_slab && k8_slab && v8_slab && kv_len);
   MD_CHECK_ARG(ctx <= F8_MAX_CTX && batch > 0 && n_heads > 0 && rot_dim % 2 == 0 && rot_dim > 0 && rot_dim <= 64);
   MD_CHECK_ARG(ld % 8 == 0 && ldo % 8 == 0 && ld >= 3 * n_heads * 64 && ldo >= n_heads * 64 && k_scale > 0.f && v_scale > 0.f);
   hipLaunchKernelGGL(attn_decode_f8_kernel, dim3(n_heads, batch), dim3(256), 0, s, (const bf16_t*)qkv, ld, (bf16_t*)o, ldo, freqs,
                      (bf16_t*)k_slab, (bf16_t*)v_slab, (uint8_t*)k8_slab, (uint8_t*)v8_slab, slab_batch_stride, ctx, kv_len, n_heads,
-                     scale * 1.4426950408889634f, rot_dim, k_scale, v_scale);
+                     scale * 1.4426950408889634f, rot_dim, k_scale, v_scale, slots, n_slots);
   return md_launch_status();
 }
 
@@ -242,5 +256,5 @@ extern "C" md_status md_attention_decode_rope_f8(const void* qkv, int64_t ld, vo
                                                  const int32_t* kv_len, int32_t batch, int32_t n_heads, int32_t rot_dim, float scale,
                                                  float k_scale, float v_scale, void* stream) {
   return md_attention_decode_rope_f8_launch(qkv, ld, o, ldo, freqs, k_slab, v_slab, k8_slab, v8_slab, slab_batch_stride, ctx, kv_len, batch,
-                                            n_heads, rot_dim, scale, k_scale, v_scale, (hipStream_t)stream);
+                                            n_heads, rot_dim, scale, k_scale, v_scale, (hipStream_t)stream, nullptr, 0);
 }

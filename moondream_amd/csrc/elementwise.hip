@@ -232,9 +232,17 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(bf16_t* __restrict__ qkv, 
                                                       bf16_t* __restrict__ kslab,
                                                       bf16_t* __restrict__ vslab, int64_t slab_bs,
                                                       int ctx, int q_len, int n_heads,
-                                                      int n_kv_heads, int hd, int rot) {
+                                                      int n_kv_heads, int hd, int rot,
+                                                      const int32_t* __restrict__ slots, int n_slots) {
   const int tok = blockIdx.x;
   const int b = tok / q_len, t = tok % q_len;
+  // slot table (md_text_forward_slots): sequence b's K / V live in slot slots[b]; an out-of-range slot is an idle row of a
+  // decode step -- nothing to rotate into the cache and no slab write (uniform per workgroup, before the barrier)
+  int sb = b;
+  if (slots != nullptr) {
+    sb = slots[b];
+    if (sb < 0 || sb >= n_slots) return;
+  }
   const int pos = pos0[b] + t;
   bf16_t* row = qkv + (int64_t)tok * ld;
   const int half = rot >> 1;
@@ -272,7 +280,7 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(bf16_t* __restrict__ qkv, 
       *(uint32_t*)(row + head * hd + 2 * j) = w;  // q stays in the activation, rotated in place
     } else {
       const int hk = head - n_heads;
-      *(uint32_t*)(kslab + (int64_t)b * slab_bs + ((int64_t)hk * ctx + pos) * hd + 2 * j) = w;
+      *(uint32_t*)(kslab + (int64_t)sb * slab_bs + ((int64_t)hk * ctx + pos) * hd + 2 * j) = w;
     }
   }
   // pass-through half of k, and all of v, in 16-byte chunks
@@ -280,12 +288,12 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(bf16_t* __restrict__ qkv, 
   for (int it = threadIdx.x; it < n_kv_heads * cpk; it += 256) {
     const int hk = it / cpk, ch = it % cpk;
     const u32x4 q = *(const u32x4*)(row + (n_heads + hk) * hd + rot + ch * 8);
-    *(u32x4*)(kslab + (int64_t)b * slab_bs + ((int64_t)hk * ctx + pos) * hd + rot + ch * 8) = q;
+    *(u32x4*)(kslab + (int64_t)sb * slab_bs + ((int64_t)hk * ctx + pos) * hd + rot + ch * 8) = q;
   }
   for (int it = threadIdx.x; it < n_kv_heads * cpv; it += 256) {
     const int hk = it / cpv, ch = it % cpv;
     const u32x4 q = *(const u32x4*)(row + (n_heads + n_kv_heads + hk) * hd + ch * 8);
-    *(u32x4*)(vslab + (int64_t)b * slab_bs + ((int64_t)hk * ctx + pos) * hd + ch * 8) = q;
+    *(u32x4*)(vslab + (int64_t)sb * slab_bs + ((int64_t)hk * ctx + pos) * hd + ch * 8) = q;
   }
 }
 
@@ -510,19 +518,28 @@ extern "C" md_status md_patchify_bf16(const void* crops, void* out, int64_t ld_o
   return md_launch_status();
 }
 
+// internal (api.hip): md_rope_kv_write with the slot table of md_text_forward_slots (slots == nullptr: slot b)
+md_status md_rope_kv_write_slots(void* qkv, int64_t ld, const float* freqs, const int32_t* pos0, void* k_slab, void* v_slab,
+                                 int64_t slab_batch_stride, int32_t ctx, int32_t batch, int32_t q_len, int32_t n_heads,
+                                 int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim, const int32_t* slots, int32_t n_slots,
+                                 hipStream_t stream) {
+  MD_CHECK_ARG(qkv && freqs && pos0 && k_slab && v_slab && batch > 0 && q_len > 0);
+  MD_CHECK_ARG(head_dim % 8 == 0 && rot_dim % 8 == 0 && rot_dim <= head_dim && ld % 8 == 0);
+  MD_CHECK_ARG((n_heads + n_kv_heads) * (rot_dim / 2) <= 1024);
+  MD_CHECK_ARG(ld >= (int64_t)(n_heads + 2 * n_kv_heads) * head_dim);
+  hipLaunchKernelGGL(rope_kv_kernel, dim3(batch * q_len), dim3(256), 0, stream,
+                     (bf16_t*)qkv, ld, freqs, pos0, (bf16_t*)k_slab, (bf16_t*)v_slab,
+                     slab_batch_stride, ctx, q_len, n_heads, n_kv_heads, head_dim, rot_dim, slots, n_slots);
+  return md_launch_status();
+}
+
 extern "C" md_status md_rope_kv_write(void* qkv, int64_t ld, const float* freqs, const int32_t* pos0,
                                       void* k_slab, void* v_slab, int64_t slab_batch_stride,
                                       int32_t ctx, int32_t batch, int32_t q_len, int32_t n_heads,
                                       int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim,
                                       void* stream) {
-  MD_CHECK_ARG(qkv && freqs && pos0 && k_slab && v_slab && batch > 0 && q_len > 0);
-  MD_CHECK_ARG(head_dim % 8 == 0 && rot_dim % 8 == 0 && rot_dim <= head_dim && ld % 8 == 0);
-  MD_CHECK_ARG((n_heads + n_kv_heads) * (rot_dim / 2) <= 1024);
-  MD_CHECK_ARG(ld >= (int64_t)(n_heads + 2 * n_kv_heads) * head_dim);
-  hipLaunchKernelGGL(rope_kv_kernel, dim3(batch * q_len), dim3(256), 0, (hipStream_t)stream,
-                     (bf16_t*)qkv, ld, freqs, pos0, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                     slab_batch_stride, ctx, q_len, n_heads, n_kv_heads, head_dim, rot_dim);
-  return md_launch_status();
+  return md_rope_kv_write_slots(qkv, ld, freqs, pos0, k_slab, v_slab, slab_batch_stride, ctx, batch, q_len, n_heads, n_kv_heads,
+                                head_dim, rot_dim, nullptr, 0, (hipStream_t)stream);
 }
 
 extern "C" md_status md_add_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo,

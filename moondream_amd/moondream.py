@@ -1244,6 +1244,17 @@ class MoondreamModel:
             self.last_phase_ms = {marks[i][0]: marks[i - 1][1].elapsed_time(marks[i][1]) for i in range(1, len(marks))}
         return results  # type: ignore[return-value]
 
+    def batch_generate_ids_continuous(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
+                                      eos_id: Optional[int] = None, ignore_eos: bool = False, max_live: int = 64, chunk: int = 16,
+                                      temperature: float = 0.0, top_p: float = DEFAULT_TOP_P, seeds=None,
+                                      variant: Optional[str] = None) -> List[List[int]]:
+        """``batch_generate_ids`` with continuous batching (moondream_amd/continuous.py): per-request ``max_tokens`` and EOS
+        exit, freed KV slots refilled from the queue mid-decode; same greedy ids as the lockstep path."""
+        from .continuous import ContinuousEngine
+
+        return ContinuousEngine(self, max_live, chunk, temperature, top_p).generate(images, prompts, max_tokens, eos_id, ignore_eos,
+                                                                                   seeds, variant)
+
     def teacher_forced_logits(self, images, prompts: Sequence[Sequence[int]], forced_ids, gather_idx) -> torch.Tensor:
         """Parity instrument (tests / bench.py): the logits of every greedy decision when each sequence is FORCED to follow
         ``forced_ids[i]`` (the reference's ids) instead of its own argmax, gathered at ``gather_idx[i][j]`` (the reference's
