@@ -362,6 +362,18 @@ md_status md_attention_decode_rope(const void* qkv, int64_t ld, void* o, int64_t
                                    const int32_t* kv_len, int32_t batch, int32_t n_heads, int32_t head_dim,
                                    int32_t rot_dim, float scale, void* stream);
 
+/* md_attention_decode / md_attention_decode_rope with the slot table of md_text_forward_slots and the shared-prefix table of
+ * md_text_forward_shared (slots, n_slots, prefix_slots, prefix_len: see there), so that tests reach the grouped kernel
+ * directly.  prefix_slots == NULL: the slot-table launch.  The _rope form is MHA only. */
+md_status md_attention_decode_shared(const void* q, int64_t ldq, void* o, int64_t ldo, const void* k_slab, const void* v_slab,
+                                     int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch, int32_t n_heads,
+                                     int32_t n_kv_heads, int32_t head_dim, float scale, const int32_t* slots, int32_t n_slots,
+                                     const int32_t* prefix_slots, const int32_t* prefix_len, void* stream);
+md_status md_attention_decode_rope_shared(const void* qkv, int64_t ld, void* o, int64_t ldo, const float* freqs, void* k_slab,
+                                          void* v_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch,
+                                          int32_t n_heads, int32_t head_dim, int32_t rot_dim, float scale, const int32_t* slots,
+                                          int32_t n_slots, const int32_t* prefix_slots, const int32_t* prefix_len, void* stream);
+
 /* Partial RoPE + KV-cache write (reference: rope.py:20-48, text.py:42-46,
  * moondream.py:74-78).  qkv: bf16 [batch*q_len][ld] rows laid out q|k|v.  The
  * first rot_dim features of every q and k head are read half-split, rotated in
@@ -596,6 +608,23 @@ md_status md_text_forward_slots(const md_text_model* m, const void* x, void* hid
                                 const int32_t* pos0, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* md_text_forward_slots with a SHARED KV PREFIX: row b reads key positions j < prefix_len[b] from slot prefix_slots[b] and
+ * keys j >= prefix_len[b] from its own slot slots[b] -- one image prefix, prefilled once, serves many prompts without a copy.
+ * prefix_slots, prefix_len: device int32 [batch]; prefix_slots[b] < 0 (or >= n_slots): no shared prefix for the row.
+ * prefix_slots == NULL: md_text_forward_slots (the same launches).  Otherwise slots must not be NULL.  Every write goes to
+ * slots[b]; the prefix slots are only read.  Caller contract (checked by the Python layer): pos0[b] >= prefix_len[b], and no
+ * row's own slot is another row's prefix slot in the same call.  Idle rows as in md_text_forward_slots.
+ * Bits: every output of a row (hidden, the K / V rows written) equals md_text_forward_slots' over a slot into which keys
+ * [0, prefix_len[b]) of the prefix slot have been copied.  The decode attention groups rows: one K / V load of a prefix row
+ * serves every row of a group sharing its prefix slot.
+ * kv->k8 / kv->v8 (the e4m3 copy of the fp8 mode) set, NULL kv, slots with n_slots <= 0: MD_ERR_INVALID_ARG.
+ * The prefill attention takes the shared-prefix instantiation of whichever variant MD_ATTN_VARIANT selects.
+ * Workspace: md_text_workspace_bytes(m, batch, q_len). */
+md_status md_text_forward_shared(const md_text_model* m, const void* x, void* hidden, int32_t batch, int32_t q_len,
+                                 const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
+                                 const int32_t* prefix_len, const md_kv_cache* kv, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
 /* LoRA "variant" side path (reference: lora.py:54-79 -> text.py:31-32,55-56 and layers.py:129-146 with lora != None).
  * delta(x) = (x A^T) B^T with A [r][k] and B [n][r] packed as bias-free md_linear (r zero-padded to 64); a pair with
  * a.w == NULL is absent.  Per block, in the reference's order and with its bf16 roundings:
@@ -674,6 +703,13 @@ md_status md_decode_step_slots(const md_text_model* m, const int32_t* tokens, in
                                int32_t batch, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
                                int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
                                size_t workspace_bytes, void* stream);
+
+/* md_decode_step_slots with the shared-prefix table of md_text_forward_shared (prefix_slots == NULL: md_decode_step_slots).
+ * Workspace: md_decode_workspace_bytes(m, batch). */
+md_status md_decode_step_shared(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos, int32_t batch,
+                                const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots, const int32_t* prefix_len,
+                                const md_kv_cache* kv, int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
+                                size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

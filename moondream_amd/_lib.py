@@ -183,6 +183,12 @@ SIGNATURES = {
                                       c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "md_attention_decode_rope": (C.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                            c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "md_attention_decode_shared": (C.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32,
+                                             c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_int32, c_void_p,
+                                             c_void_p, c_void_p]),
+    "md_attention_decode_rope_shared": (C.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                                  c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_int32,
+                                                  c_void_p, c_void_p, c_void_p]),
     "md_rope_kv_write": (C.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                    c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "md_embed_tokens": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
@@ -205,6 +211,8 @@ SIGNATURES = {
                                   c_void_p, c_size_t, c_void_p]),
     "md_text_forward_slots": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                         P(MdKvCache), c_void_p, c_size_t, c_void_p]),
+    "md_text_forward_shared": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                         c_void_p, c_void_p, P(MdKvCache), c_void_p, c_size_t, c_void_p]),
     "md_text_lora_workspace_bytes": (c_size_t, [P(MdTextModel), c_int32, c_int32]),
     "md_text_forward_lora": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, P(MdKvCache),
                                        c_void_p, c_size_t, c_void_p]),
@@ -223,6 +231,8 @@ SIGNATURES = {
                                  c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
     "md_decode_step_slots": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, P(MdKvCache),
                                        c_int32, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "md_decode_step_shared": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
+                                        c_void_p, P(MdKvCache), c_int32, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -425,6 +425,13 @@ md_status md_rope_kv_write_slots(void* qkv, int64_t ld, const float* freqs, cons
                                  int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim, const int32_t* slots, int32_t n_slots,
                                  hipStream_t stream);
 md_status md_attention_prefill_slots(const md_attn_args* a, const int32_t* slots, hipStream_t stream);
+md_status md_attention_prefill_shared(const md_attn_args* a, const int32_t* slots, const int32_t* pfx_slots, const int32_t* pfx_len,
+                                      int32_t n_slots, hipStream_t stream);
+md_status md_attention_decode_shared_any(bool fused, const void* q, int64_t ldq, void* o, int64_t ldo, const float* freqs, void* k_slab,
+                                         void* v_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch,
+                                         int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim, float scale,
+                                         const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots, const int32_t* prefix_len,
+                                         hipStream_t stream);
 md_status md_attention_decode_slots(const void* q, int64_t ldq, void* o, int64_t ldo, const void* k_slab, const void* v_slab,
                                     int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch, int32_t n_heads,
                                     int32_t n_kv_heads, int32_t head_dim, float scale, const int32_t* slots, int32_t n_slots,
@@ -441,12 +448,46 @@ extern "C" md_status md_text_forward(const md_text_model* m, const void* x_in, v
   return md_text_forward_slots(m, x_in, hidden, batch, q_len, pos0, nullptr, 0, kv, workspace, workspace_bytes, stream);
 }
 
-// reference: text.py:128-160 (text_decoder) with text.py:16-60 (attn).  slots == nullptr: sequence b in slot b (md_text_forward);
-// otherwise every place that addresses a slab -- the RoPE / KV-write epilogue's row offsets, rope_kv_kernel, the prefill and
-// decode attention, the e4m3 copy -- takes slot slots[b], and a decode row whose slot is outside [0, n_slots) is idle.
+static md_status text_forward_impl(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
+                                   const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* pfx_slots,
+                                   const int32_t* pfx_len, const md_kv_cache* kv, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
 extern "C" md_status md_text_forward_slots(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
                                            const int32_t* pos0, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
                                            void* workspace, size_t workspace_bytes, void* stream) {
+  return text_forward_impl(m, x_in, hidden, batch, q_len, pos0, slots, n_slots, nullptr, nullptr, kv, workspace, workspace_bytes,
+                           stream);
+}
+
+// the checks of the shared-prefix entry points that need no device: a table needs the slot table, and the e4m3 KV copy (fp8
+// mode) is not supported with one
+static md_status shared_args_ok(const md_kv_cache* kv, const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
+                                const int32_t* prefix_len) {
+  MD_CHECK_ARG(kv && kv->k8 == nullptr && kv->v8 == nullptr);
+  MD_CHECK_ARG(slots == nullptr || n_slots > 0);  // as md_text_forward_slots
+  MD_CHECK_ARG(prefix_slots == nullptr || (slots != nullptr && prefix_len != nullptr));
+  return MD_OK;
+}
+
+extern "C" md_status md_text_forward_shared(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
+                                            const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
+                                            const int32_t* prefix_len, const md_kv_cache* kv, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  MD_TRY(shared_args_ok(kv, slots, n_slots, prefix_slots, prefix_len));
+  return text_forward_impl(m, x_in, hidden, batch, q_len, pos0, slots, n_slots, prefix_slots, prefix_len, kv, workspace,
+                           workspace_bytes, stream);
+}
+
+// reference: text.py:128-160 (text_decoder) with text.py:16-60 (attn).  slots == nullptr: sequence b in slot b (md_text_forward);
+// otherwise every place that addresses a slab -- the RoPE / KV-write epilogue's row offsets, rope_kv_kernel, the prefill and
+// decode attention, the e4m3 copy -- takes slot slots[b], and a decode row whose slot is outside [0, n_slots) is idle.
+// pfx_slots != nullptr (md_text_forward_shared): the prefill and decode attention read keys [0, pfx_len[b]) from slot
+// pfx_slots[b]; every write still goes to slot slots[b].
+static md_status text_forward_impl(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
+                                   const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* pfx_slots,
+                                   const int32_t* pfx_len, const md_kv_cache* kv, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
   MD_CHECK_ARG(m && x_in && hidden && pos0 && kv && kv->k && kv->v && workspace && m->blocks);
   MD_CHECK_ARG(batch > 0 && q_len > 0 && m->dim % m->n_heads == 0);
   MD_CHECK_ARG(slots == nullptr || n_slots > 0);
@@ -464,8 +505,9 @@ extern "C" md_status md_text_forward_slots(const md_text_model* m, const void* x
       const int nb = std::min(block_rows, batch - b0);
       const void* xb = (const char*)x_in + (int64_t)b0 * m->dim * 2;
       void* hb = (char*)hidden + (int64_t)b0 * m->dim * 2;
-      if (slots != nullptr) {  // slot table: the slab base stays, the block's rows take their own entries of the table
-        MD_TRY(md_text_forward_slots(m, xb, hb, nb, 1, pos0 + b0, slots + b0, n_slots, kv, workspace, workspace_bytes, stream));
+      if (slots != nullptr) {  // slot table: the slab base stays, the block's rows take their own entries of the table(s)
+        MD_TRY(text_forward_impl(m, xb, hb, nb, 1, pos0 + b0, slots + b0, n_slots, pfx_slots ? pfx_slots + b0 : nullptr,
+                                 pfx_slots ? pfx_len + b0 : nullptr, kv, workspace, workspace_bytes, stream));
         continue;
       }
       md_kv_cache sub = *kv;
@@ -533,6 +575,11 @@ extern "C" md_status md_text_forward_slots(const md_text_model* m, const void* x
       MD_TRY(md_attention_decode_rope_f8_launch(w.qkv, qld, w.att, Dp, m->freqs, kl, vl, (uint8_t*)kv->k8 + (int64_t)l * kv->layer_stride,
                                                 (uint8_t*)kv->v8 + (int64_t)l * kv->layer_stride, kv->batch_stride, kv->ctx, kv_len, batch,
                                                 m->n_heads, m->rot_dim, scale, kv->k_scale[l], kv->v_scale[l], s, slots, n_slots));
+    } else if (pfx_slots != nullptr && q_len == 1) {
+      // shared prefix: the grouped decode kernel (FUSED: with RoPE and the new row's K / V write, as below)
+      MD_TRY(md_attention_decode_shared_any(fuse_rope, w.qkv, qld, w.att, Dp, m->freqs, kl, vl, kv->batch_stride, kv->ctx, kv_len,
+                                            batch, m->n_heads, m->n_kv_heads, hd, m->rot_dim, scale, slots, n_slots, pfx_slots,
+                                            pfx_len, s));
     } else if (fuse_rope) {
       MD_TRY(md_attention_decode_rope_slots(w.qkv, qld, w.att, Dp, m->freqs, kl, vl, kv->batch_stride, kv->ctx, kv_len,
                                             batch, m->n_heads, hd, m->rot_dim, scale, slots, n_slots, s));
@@ -571,7 +618,7 @@ extern "C" md_status md_text_forward_slots(const md_text_model* m, const void* x
         a.o8_ts = Dp;
         a.o8_inv_scale = att8_inv_scale;
       }
-      MD_TRY(md_attention_prefill_slots(&a, slots, s));
+      MD_TRY(pfx_slots ? md_attention_prefill_shared(&a, slots, pfx_slots, pfx_len, n_slots, s) : md_attention_prefill_slots(&a, slots, s));
     }
     // fp8 mode: the rows this pass wrote (bf16) also go into the e4m3 copy the decode steps read
     if (kv8 && !fuse_rope && !rope_done_kv8) MD_TRY(md_kv_quantize_f8_layer(kv, l, pos0, 0, batch, m->n_heads, q_len, s, slots, n_slots));
@@ -840,11 +887,34 @@ extern "C" md_status md_decode_step(const md_text_model* m, const int32_t* token
                               workspace_bytes, stream);
 }
 
-// reference: the generator loop body of moondream.py:512-530, device resident; slots as in md_text_forward_slots
+static md_status decode_step_impl(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos, int32_t batch,
+                                  const int32_t* slots, int32_t n_slots, const int32_t* pfx_slots, const int32_t* pfx_len,
+                                  const md_kv_cache* kv, int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 extern "C" md_status md_decode_step_slots(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos,
                                           int32_t batch, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
                                           int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
                                           size_t workspace_bytes, void* stream) {
+  return decode_step_impl(m, tokens, next, pos, batch, slots, n_slots, nullptr, nullptr, kv, suppress_id, logits, ld_logits, workspace,
+                          workspace_bytes, stream);
+}
+
+extern "C" md_status md_decode_step_shared(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos,
+                                           int32_t batch, const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
+                                           const int32_t* prefix_len, const md_kv_cache* kv, int32_t suppress_id, void* logits,
+                                           int64_t ld_logits, void* workspace, size_t workspace_bytes, void* stream) {
+  MD_TRY(shared_args_ok(kv, slots, n_slots, prefix_slots, prefix_len));
+  return decode_step_impl(m, tokens, next, pos, batch, slots, n_slots, prefix_slots, prefix_len, kv, suppress_id, logits, ld_logits,
+                          workspace, workspace_bytes, stream);
+}
+
+// reference: the generator loop body of moondream.py:512-530, device resident; slots as in md_text_forward_slots, the prefix
+// table as in md_text_forward_shared
+static md_status decode_step_impl(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos, int32_t batch,
+                                  const int32_t* slots, int32_t n_slots, const int32_t* pfx_slots, const int32_t* pfx_len,
+                                  const md_kv_cache* kv, int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
   MD_CHECK_ARG(m && tokens && next && pos && kv && logits && workspace && batch > 0);
   MD_CHECK_ARG(slots == nullptr || n_slots > 0);
   if (workspace_bytes < md_decode_workspace_bytes(m, batch)) return MD_ERR_WORKSPACE;
@@ -855,7 +925,7 @@ extern "C" md_status md_decode_step_slots(const md_text_model* m, const int32_t*
   void* tws = a.take(0);
   const size_t tws_bytes = workspace_bytes - a.off;
   MD_TRY(md_embed_tokens(tokens, m->wte, m->dim, x, m->dim, batch, m->dim, s));
-  MD_TRY(md_text_forward_slots(m, x, x, batch, 1, pos, slots, n_slots, kv, tws, tws_bytes, s));
+  MD_TRY(text_forward_impl(m, x, x, batch, 1, pos, slots, n_slots, pfx_slots, pfx_len, kv, tws, tws_bytes, s));
   if (decode_tall_rows(m, batch, 1) && !(kv->k8 && kv->v8)) {
     // the step's lm_head at 65 .. 128 rows: the by-shape config of the same MFMA family as the <= 64-row regime (never the
     // pinned four-wave kernel: a sequence must get the same logits in a step of 128 as in a step of 64)

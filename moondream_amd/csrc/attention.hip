@@ -50,6 +50,11 @@ struct AttnK {
   int head_dim;
   const int32_t* slots;  // md_text_forward_slots: sequence b's K / V rows are those of slot slots[b] (nullptr: slot b); q / o stay row-indexed
   int skip_dead;  // LDS-DMA prefill kernel, exact work skipping: bit 0 = the second 32-key half of a last tile with no live key in it, bit 1 = waves with no live query row
+  // md_text_forward_shared: keys [0, pfx_len[b]) of sequence b are read from slot pfx_slots[b] (when in [0, pfx_n_slots)), the
+  // rest from its own slot -- addresses only (nullptr: no shared prefix)
+  const int32_t* pfx_slots;
+  const int32_t* pfx_len;
+  int pfx_n_slots;
 };
 
 template <int HD>
@@ -66,7 +71,19 @@ struct Cfg {
   static constexpr int LDS = (K_BYTES + V_BYTES) > O_BYTES ? (K_BYTES + V_BYTES) : O_BYTES;
 };
 
-template <int HD>
+// md_text_forward_shared: the shared prefix of sequence b (own slot kvb) as a key count and the element offsets from the own
+// slot's K / V rows to the prefix slot's; no prefix (or none valid): plen 0 and both offsets 0 -- the addresses of the slot table
+__device__ __forceinline__ void shared_prefix_delta(const AttnK& p, int b, int64_t kvb, int& plen, int64_t& pdk, int64_t& pdv) {
+  if (p.pfx_slots == nullptr) return;
+  const int ps = p.pfx_slots[b];
+  if (ps < 0 || ps >= p.pfx_n_slots) return;
+  plen = max(p.pfx_len[b], 0);
+  pdk = ((int64_t)ps - kvb) * p.k_bs;
+  pdv = ((int64_t)ps - kvb) * p.v_bs;
+}
+
+// SHP: the shared-prefix addressing of md_text_forward_shared (per key row); the other instantiations compile without it
+template <int HD, bool SHP = false>
 __global__ __launch_bounds__(256) void attn_prefill_kernel(const AttnK p) {
   using C = Cfg<HD>;
   __shared__ __attribute__((aligned(16))) char smem[C::LDS];
@@ -121,6 +138,9 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const AttnK p) {
   const int64_t kvb = p.slots ? p.slots[b] : b;
   const bf16_t* kbase = p.k + kvb * p.k_bs + (int64_t)hk * p.k_hs;
   const bf16_t* vbase = p.v + kvb * p.v_bs + (int64_t)hk * p.v_hs;
+  int plen = 0;           // SHP: keys below plen come from the shared prefix slot, at kbase / vbase + pdk / pdv
+  int64_t pdk = 0, pdv = 0;
+  if constexpr (SHP) shared_prefix_delta(p, b, kvb, plen, pdk, pdv);
 
   // ---- K/V staging, split (cdna guide T14): the global loads of tile t+1 are issued
   // before tile t is computed and written to LDS after it, so their latency hides
@@ -139,8 +159,8 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const AttnK p) {
         // rows past kv_len replay the last valid row: their scores are masked to -inf
         // below, so P is exactly 0 and the (finite) V values never contribute
         const int j = min(kv0 + 2 * rp + e, kv_len - 1);
-        kreg[u][e] = *(const u32x4*)(kbase + (int64_t)j * p.k_ts + ch * 8);
-        vreg[u][e] = *(const u32x4*)(vbase + (int64_t)j * p.v_ts + ch * 8);
+        kreg[u][e] = *(const u32x4*)(kbase + ((SHP && j < plen) ? pdk : 0) + (int64_t)j * p.k_ts + ch * 8);
+        vreg[u][e] = *(const u32x4*)(vbase + ((SHP && j < plen) ? pdv : 0) + (int64_t)j * p.v_ts + ch * 8);
       }
     }
   };
@@ -336,7 +356,8 @@ struct CfgD {
 // in the same basic block as the exp2 / pack work of tile t and the P V MFMAs of tile t, so
 // one wave keeps the matrix pipe and the VALU busy at the same time (22 MFMAs x 32 cycles
 // against ~110 VALU instructions per tile) instead of alternating between them.
-template <int HD, bool PIPE>
+// SHP: the shared-prefix addressing of md_text_forward_shared; the other instantiations compile without it
+template <int HD, bool PIPE, bool SHP = false>
 __global__ __launch_bounds__(256) void attn_prefill_dma_kernel(const AttnK p) {
   using C = CfgD<HD>;
   __shared__ __attribute__((aligned(16))) char smem[C::LDS];
@@ -385,10 +406,13 @@ __global__ __launch_bounds__(256) void attn_prefill_dma_kernel(const AttnK p) {
   const int64_t kvb = p.slots ? p.slots[b] : b;
   const bf16_t* kbase = p.k + kvb * p.k_bs + (int64_t)hk * p.k_hs;
   const bf16_t* vbase = p.v + kvb * p.v_bs + (int64_t)hk * p.v_hs;
+  int plen = 0;           // SHP: keys below plen come from the shared prefix slot, at kbase / vbase + pdk / pdv
+  int64_t pdk = 0, pdv = 0;
+  if constexpr (SHP) shared_prefix_delta(p, b, kvb, plen, pdk, pdv);
 
   // LDS-DMA pieces: chunk c = 256 j + tid of the tile image, lane-linear in LDS.  The source
   // pointers run ahead one tile per issue; only a tile that reaches past kv_len (the last one)
-  // takes the clamped path.
+  // or straddles the shared prefix's end takes the per-row path.
   int krow[3], kcol[3], vrow[3], vcol[3];
   const bf16_t* ksrc[3];
   const bf16_t* vsrc[3];
@@ -421,29 +445,35 @@ __global__ __launch_bounds__(256) void attn_prefill_dma_kernel(const AttnK p) {
   };
   auto issue_k = [&](int kv0, int buf) {
     char* kb = smem + buf * C::BUF + 64 * wave * 16;
-    if (kv0 + 64 <= kv_len) {  // wave-uniform: every row of the tile exists
-      dma16(ksrc[0], kb);
-      dma16(ksrc[1], kb + 4096);
-      if (wave < C::K_LAST_WAVES) dma16(ksrc[2], kb + 8192);
+    if (kv0 + 64 <= kv_len && (!SHP || kv0 >= plen || kv0 + 64 <= plen)) {  // wave-uniform: every row of the tile exists, in one slot
+      const int64_t d = (SHP && kv0 + 64 <= plen) ? pdk : 0;
+      dma16(ksrc[0] + d, kb);
+      dma16(ksrc[1] + d, kb + 4096);
+      if (wave < C::K_LAST_WAVES) dma16(ksrc[2] + d, kb + 8192);
     } else {
       // rows past kv_len replay the last valid row: their scores are masked to -inf, P is exactly 0
 #pragma unroll
       for (int j = 0; j < 3; ++j)
-        if (j < 2 || wave < C::K_LAST_WAVES)
-          dma16(kbase + (int64_t)min(kv0 + krow[j], kv_len - 1) * p.k_ts + kcol[j], kb + 4096 * j);
+        if (j < 2 || wave < C::K_LAST_WAVES) {
+          const int r = min(kv0 + krow[j], kv_len - 1);
+          dma16(kbase + ((SHP && r < plen) ? pdk : 0) + (int64_t)r * p.k_ts + kcol[j], kb + 4096 * j);
+        }
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) ksrc[j] += k_step;
   };
   auto issue_v = [&](int kv0, int buf) {
     char* vb = smem + buf * C::BUF + C::K_BYTES + 64 * wave * 16;
-    if (kv0 + 64 <= kv_len) {
+    if (kv0 + 64 <= kv_len && (!SHP || kv0 >= plen || kv0 + 64 <= plen)) {
+      const int64_t d = (SHP && kv0 + 64 <= plen) ? pdv : 0;
 #pragma unroll
-      for (int j = 0; j < 3; ++j) dma16(vsrc[j], vb + 4096 * j);
+      for (int j = 0; j < 3; ++j) dma16(vsrc[j] + d, vb + 4096 * j);
     } else {
 #pragma unroll
-      for (int j = 0; j < 3; ++j)
-        dma16(vbase + (int64_t)min(kv0 + vrow[j], kv_len - 1) * p.v_ts + vcol[j], vb + 4096 * j);
+      for (int j = 0; j < 3; ++j) {
+        const int r = min(kv0 + vrow[j], kv_len - 1);
+        dma16(vbase + ((SHP && r < plen) ? pdv : 0) + (int64_t)r * p.v_ts + vcol[j], vb + 4096 * j);
+      }
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) vsrc[j] += v_step;
@@ -850,10 +880,297 @@ bool decode_attn_nt() {  // MD_ATTN_DECODE_NT=0: plain loads (A/B)
   return on;
 }
 
+// ---------------------------------------------------------------------------
+// decode with a shared KV prefix (md_text_forward_shared): G query rows per workgroup
+// ---------------------------------------------------------------------------
+// Row b reads keys [0, plen_b) from slot pslots[b] and keys [plen_b, kv_len_b) from its own slot slots[b].  One workgroup
+// serves one head and SHG consecutive rows.  When every live row of the group has the same prefix slot, the keys below the
+// group's smallest plen (whole 128-key rounds of them) are loaded ONCE and applied to all SHG queries, held in registers;
+// every other key is loaded per row, from the slot the row's own rule names.  The thread mapping and the arithmetic are
+// those of attn_decode_kernel<NW = 16>: thread group (wave, g) owns class 32 (wave >> 2) + 8 (wave & 3) + g, accumulated in
+// fp32 in ascending key order, the same butterfly for each score, probabilities rounded to bf16 before P.V, classes of a
+// residue combined as (u0 + u1) + (u2 + u3), residues summed in ascending order -- so each row gets the bits the
+// one-row-per-workgroup kernel gives it over a slot holding the prefix (a row whose kv_len is below the group's longest
+// runs masked rounds, which add exact zeros).  LDS: scores [SHG][DEC_MAX_CTX] fp32 (32 KiB at SHG = 4) + one row's
+// reduction (32.5 KiB, reused row by row) + FUSED new rows: 66 304 B plain, 67 840 B FUSED.
+// NT: the per-row (suffix) K / V rows are requested non-temporally, as in attn_decode_kernel; the shared prefix rows
+// always with the default policy -- the group's neighbours of the same head read them again.
+constexpr int SHG = 4;
+
+template <bool FUSED, bool NT>
+__global__ __launch_bounds__(1024) void attn_decode_shared_kernel(const bf16_t* __restrict__ q, int64_t ldq,
+                                                                  bf16_t* __restrict__ o, int64_t ldo,
+                                                                  bf16_t* __restrict__ kslab, bf16_t* __restrict__ vslab,
+                                                                  int64_t slab_bs, int ctx, const int32_t* __restrict__ kv_len_p,
+                                                                  int batch, int n_heads, int kv_group, float scale_log2,
+                                                                  const float* __restrict__ freqs, int rot,
+                                                                  const int32_t* __restrict__ slots, int n_slots,
+                                                                  const int32_t* __restrict__ pslots,
+                                                                  const int32_t* __restrict__ plen_p) {
+  constexpr int G = SHG;
+  constexpr int UNRS = 4;  // shared rounds whose loads are issued together
+  __shared__ float sc[G][DEC_MAX_CTX];
+  __shared__ float red[4][32][64 + 1];  // one row at a time: [class quarter][residue][feature | sum of p]
+  __shared__ float red_m[G][16];
+  __shared__ __attribute__((aligned(16))) bf16_t newrow[FUSED ? G : 1][3][64];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g8 = lane >> 3, c = lane & 7;
+  const int h = blockIdx.x, hk = h / kv_group, b0 = blockIdx.y * G;
+  const int res = (wave & 3) * 8 + g8, u0 = wave >> 2;
+  const int64_t head_off = (int64_t)hk * ctx * 64;
+
+  // per-row state, uniform per workgroup.  A row past batch is absent; a slot outside [0, n_slots) is an IDLE row (zero
+  // output, no slab read or write, as in attn_decode_kernel); a prefix slot outside [0, n_slots) means no shared prefix.
+  bool live[G];
+  int kvl[G], plen[G];
+  int64_t own[G], pre[G];  // element offsets of the row's own slot / of the slot its keys below plen come from
+  int shared_slot = -1, min_plen = DEC_MAX_CTX, kv_max = 0;
+  bool same = true, any_live = false;
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int b = b0 + g;
+    live[g] = false;
+    kvl[g] = 0;
+    plen[g] = 0;
+    own[g] = pre[g] = 0;
+    if (b >= batch) continue;
+    const int sb = slots[b];
+    if (sb < 0 || sb >= n_slots) {
+      if (tid < 64) o[(int64_t)b * ldo + h * 64 + tid] = f2bf(0.f);
+      continue;
+    }
+    live[g] = any_live = true;
+    kvl[g] = kv_len_p[b];
+    own[g] = (int64_t)sb * slab_bs + head_off;
+    const int ps = pslots[b];
+    const int pl = (ps >= 0 && ps < n_slots) ? min(max(plen_p[b], 0), kvl[g] - 1) : 0;
+    plen[g] = pl;
+    pre[g] = (pl > 0 ? (int64_t)ps * slab_bs + head_off : own[g]);
+    if (pl == 0) same = false;
+    else if (shared_slot < 0) shared_slot = ps;
+    else if (shared_slot != ps) same = false;
+    min_plen = min(min_plen, pl);
+    kv_max = max(kv_max, kvl[g]);
+  }
+  if (!any_live) return;  // uniform, before any barrier
+  // whole 128-key rounds below every live row's prefix end: one load per key for the whole group
+  const int n_shared = (same && shared_slot >= 0) ? min_plen / 128 : 0;
+  const int64_t shared_off = (n_shared > 0) ? (int64_t)shared_slot * slab_bs + head_off : 0;
+
+  if constexpr (FUSED) {
+    // per row, as attn_decode_kernel<FUSED>: rotated q and k of the new token, its v; 256 threads per row
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      if (!live[g] || (tid >> 8) != (g & 3)) continue;
+      const int t = tid & 255, pos = kvl[g] - 1;
+      const bf16_t* row = q + (int64_t)(b0 + g) * ldq;
+      const int half = rot >> 1;
+      if (t < 2 * half) {
+        const int which = t / half, j = t % half;
+        const bf16_t* hp = row + (which ? (n_heads + h) : h) * 64;
+        const float re = bf2f(hp[j]), im = bf2f(hp[half + j]);
+        const float cs = freqs[((int64_t)pos * half + j) * 2], sn = freqs[((int64_t)pos * half + j) * 2 + 1];
+        float o_re, o_im;
+        md_rope_pair(re, im, cs, sn, o_re, o_im);
+        newrow[g][which][2 * j] = f2bf(o_re);
+        newrow[g][which][2 * j + 1] = f2bf(o_im);
+      } else if (t >= 64 && t < 64 + 2 * (64 - rot)) {
+        const int t2 = t - 64, which = t2 / (64 - rot), i = rot + t2 % (64 - rot);
+        newrow[g][which][i] = row[(which ? (n_heads + h) : h) * 64 + i];
+      } else if (t >= 192 && t < 256) {
+        const int i = t - 192;
+        newrow[g][2][i] = row[(2 * n_heads + h) * 64 + i];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      if (!live[g] || (tid >> 7) != g) continue;
+      const int t = tid & 127, pos = kvl[g] - 1;
+      if (t < 64) kslab[own[g] + (int64_t)pos * 64 + t] = newrow[g][1][t];
+      else vslab[own[g] + (int64_t)pos * 64 + t - 64] = newrow[g][2][t - 64];
+    }
+  }
+
+  // the G query rows stay packed (bf16); their scaled fp32 values are formed where they are used -- the same products as the
+  // qv[] of attn_decode_kernel, at half the registers
+  u32x4 qp[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    qp[g] = u32x4{0, 0, 0, 0};
+    if (live[g]) qp[g] = FUSED ? *(const u32x4*)(&newrow[g][0][c * 8]) : *(const u32x4*)(q + (int64_t)(b0 + g) * ldq + h * 64 + c * 8);
+  }
+  // score of key row kk for row g: the per-lane partial and butterfly of attn_decode_kernel
+  auto score = [&](int g, const u32x4& kk) {
+    float qv[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      qv[2 * e] = lo_bf(qp[g][e]) * scale_log2;
+      qv[2 * e + 1] = hi_bf(qp[g][e]) * scale_log2;
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s += qv[2 * e] * lo_bf(kk[e]) + qv[2 * e + 1] * hi_bf(kk[e]);
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 4, 64);
+    return s;
+  };
+
+  // ---- pass 1: scores --------------------------------------------------------
+  float mx[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) mx[g] = -INFINITY;
+  for (int i0 = 0; i0 < n_shared; i0 += UNRS) {
+    u32x4 kq[UNRS];
+#pragma unroll
+    for (int r = 0; r < UNRS; ++r) {
+      const int j = 128 * min(i0 + r, n_shared - 1) + 32 * u0 + res;
+      kq[r] = load_kv_row<false>(kslab + shared_off + (int64_t)j * 64 + c * 8);
+    }
+#pragma unroll
+    for (int r = 0; r < UNRS; ++r) {
+      if (i0 + r >= n_shared) break;  // uniform
+      const int j = 128 * (i0 + r) + 32 * u0 + res;
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        if (!live[g]) continue;
+        const float s = score(g, kq[r]);  // j < plen <= kv_len - 1 for every live row
+        if (c == 0) sc[g][j] = s;
+        mx[g] = fmaxf(mx[g], s);
+      }
+    }
+  }
+  for (int i = n_shared; i * 128 < kv_max; ++i) {
+    const int j = 128 * i + 32 * u0 + res;
+    u32x4 kq[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      kq[g] = u32x4{0, 0, 0, 0};
+      if (live[g] && j < kvl[g]) kq[g] = load_kv_row<NT>(kslab + (j < plen[g] ? pre[g] : own[g]) + (int64_t)j * 64 + c * 8);
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      if (!live[g]) continue;
+      // (FUSED: the newest key is not yet visible in global memory to this CU: take it from LDS)
+      const u32x4 kk = (FUSED && j == kvl[g] - 1) ? *(const u32x4*)(&newrow[FUSED ? g : 0][1][c * 8]) : kq[g];
+      const float s = score(g, kk);
+      if (j < kvl[g]) {
+        if (c == 0) sc[g][j] = s;
+        mx[g] = fmaxf(mx[g], s);
+      }
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    mx[g] = wave_max(mx[g]);
+    if (lane == 0) red_m[g][wave] = mx[g];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    mx[g] = red_m[g][0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) mx[g] = fmaxf(mx[g], red_m[g][w]);
+  }
+
+  // ---- pass 2: probabilities and P.V ----------------------------------------
+  float acc[G][8], l[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    l[g] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
+  }
+  auto accumulate = [&](int g, int j, bool valid, const u32x4& vv) {
+    const float pj = valid ? __builtin_amdgcn_exp2f(sc[g][j] - mx[g]) : 0.f;
+    l[g] += pj;
+    const float pr = bf2f(f2bf(pj));  // probabilities enter the second contraction as bf16
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      acc[g][2 * e] += pr * lo_bf(vv[e]);
+      acc[g][2 * e + 1] += pr * hi_bf(vv[e]);
+    }
+  };
+  for (int i0 = 0; i0 < n_shared; i0 += UNRS) {
+    u32x4 vq[UNRS];
+#pragma unroll
+    for (int r = 0; r < UNRS; ++r) {
+      const int j = 128 * min(i0 + r, n_shared - 1) + 32 * u0 + res;
+      vq[r] = load_kv_row<false>(vslab + shared_off + (int64_t)j * 64 + c * 8);
+    }
+#pragma unroll
+    for (int r = 0; r < UNRS; ++r) {
+      if (i0 + r >= n_shared) break;
+      const int j = 128 * (i0 + r) + 32 * u0 + res;
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+        if (live[g]) accumulate(g, j, true, vq[r]);
+    }
+  }
+  for (int i = n_shared; i * 128 < kv_max; ++i) {
+    const int j = 128 * i + 32 * u0 + res;
+    u32x4 vq[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      vq[g] = u32x4{0, 0, 0, 0};  // masked keys: p = 0 times 0, an exact zero
+      if (live[g] && j < kvl[g]) vq[g] = load_kv_row<NT>(vslab + (j < plen[g] ? pre[g] : own[g]) + (int64_t)j * 64 + c * 8);
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      if (!live[g]) continue;
+      const u32x4 vv = (FUSED && j == kvl[g] - 1) ? *(const u32x4*)(&newrow[FUSED ? g : 0][2][c * 8]) : vq[g];
+      accumulate(g, j, j < kvl[g], vv);
+    }
+  }
+  // one row at a time through the reduction arrays: (u0 + u1) + (u2 + u3), residues in ascending order
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    if (!live[g]) continue;  // uniform
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[u0][res][c * 8 + e] = acc[g][e];
+    if (c == 0) red[u0][res][64] = l[g];
+    __syncthreads();
+    if (tid < 64) {
+      float s = 0.f, lt = 0.f;
+      for (int r = 0; r < 32; ++r) {
+        s += (red[0][r][tid] + red[1][r][tid]) + (red[2][r][tid] + red[3][r][tid]);
+        lt += (red[0][r][64] + red[1][r][64]) + (red[2][r][64] + red[3][r][64]);
+      }
+      o[(int64_t)(b0 + g) * ldo + h * 64 + tid] = f2bf(lt > 0.f ? s / lt : 0.f);
+    }
+    __syncthreads();
+  }
+}
+
+// the decode attention of md_text_forward_shared (pslots != nullptr; slots required)
+md_status attn_decode_shared_launch(bool fused, const void* q, int64_t ldq, void* o, int64_t ldo, const float* freqs, void* k_slab,
+                                    void* v_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch,
+                                    int32_t n_heads, int32_t n_kv_heads, int32_t rot_dim, float scale, const int32_t* slots,
+                                    int32_t n_slots, const int32_t* pslots, const int32_t* plen, hipStream_t stream) {
+  const dim3 grid(n_heads, (batch + SHG - 1) / SHG);
+  const float sl2 = scale * 1.4426950408889634f;
+  const int kv_group = n_heads / n_kv_heads;
+  const bool nt = n_heads == n_kv_heads && decode_attn_nt();
+#define MD_SHARED_LAUNCH(F, N)                                                                                              \
+  hipLaunchKernelGGL((attn_decode_shared_kernel<F, N>), grid, dim3(1024), 0, stream, (const bf16_t*)q, ldq, (bf16_t*)o, ldo, \
+                     (bf16_t*)k_slab, (bf16_t*)v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads, kv_group, sl2, freqs,  \
+                     rot_dim, slots, n_slots, pslots, plen)
+  if (fused && nt) MD_SHARED_LAUNCH(true, true);
+  else if (fused) MD_SHARED_LAUNCH(true, false);
+  else if (nt) MD_SHARED_LAUNCH(false, true);
+  else MD_SHARED_LAUNCH(false, false);
+#undef MD_SHARED_LAUNCH
+  return md_launch_status();
+}
+
 }  // namespace
 
-// internal (api.hip): md_attention_prefill with the slot table of md_text_forward_slots (slots == nullptr: slot b)
-md_status md_attention_prefill_slots(const md_attn_args* a, const int32_t* slots, hipStream_t stream) {
+// internal (api.hip): md_attention_prefill with the slot table of md_text_forward_slots (slots == nullptr: slot b) and the shared
+// prefix table of md_text_forward_shared (pfx_slots == nullptr: none)
+md_status md_attention_prefill_shared(const md_attn_args* a, const int32_t* slots, const int32_t* pfx_slots, const int32_t* pfx_len,
+                                      int32_t n_slots, hipStream_t stream) {
   MD_CHECK_ARG(a && a->q && a->k && a->v && (a->o || a->o8));
   MD_CHECK_ARG(a->batch > 0 && a->n_heads > 0 && a->n_kv_heads > 0 && a->q_len > 0);
   MD_CHECK_ARG(a->n_heads % a->n_kv_heads == 0);
@@ -883,6 +1200,9 @@ md_status md_attention_prefill_slots(const md_attn_args* a, const int32_t* slots
   k.scale_log2 = a->scale * 1.4426950408889634f;
   k.skip_dead = g_attn_skip_dead;
   k.slots = slots;
+  k.pfx_slots = pfx_slots;
+  k.pfx_len = pfx_len;
+  k.pfx_n_slots = n_slots;
   k.o8 = (uint8_t*)a->o8;
   k.o8_bs = a->o8_bs;
   k.o8_ts = a->o8_ts;
@@ -901,7 +1221,23 @@ md_status md_attention_prefill_slots(const md_attn_args* a, const int32_t* slots
     if (e && e[0] == 'p') return 2;
     return 1;
   }();
-  if (variant == 0) {
+  // shared prefix: the SHP instantiation of the variant the slot-table call would take (same arithmetic, other addresses)
+  if (pfx_slots != nullptr && variant == 0) {
+    if (a->head_dim == 72)
+      hipLaunchKernelGGL((attn_prefill_kernel<72, true>), grid, dim3(256), 0, s, k);
+    else
+      hipLaunchKernelGGL((attn_prefill_kernel<64, true>), grid, dim3(256), 0, s, k);
+  } else if (pfx_slots != nullptr && variant == 1) {
+    if (a->head_dim == 72)
+      hipLaunchKernelGGL((attn_prefill_dma_kernel<72, false, true>), grid1, dim3(256), 0, s, k);
+    else
+      hipLaunchKernelGGL((attn_prefill_dma_kernel<64, false, true>), grid1, dim3(256), 0, s, k);
+  } else if (pfx_slots != nullptr) {
+    if (a->head_dim == 72)
+      hipLaunchKernelGGL((attn_prefill_dma_kernel<72, true, true>), grid1, dim3(256), 0, s, k);
+    else
+      hipLaunchKernelGGL((attn_prefill_dma_kernel<64, true, true>), grid1, dim3(256), 0, s, k);
+  } else if (variant == 0) {
     if (a->head_dim == 72)
       hipLaunchKernelGGL(attn_prefill_kernel<72>, grid, dim3(256), 0, s, k);
     else
@@ -918,6 +1254,10 @@ md_status md_attention_prefill_slots(const md_attn_args* a, const int32_t* slots
       hipLaunchKernelGGL((attn_prefill_dma_kernel<64, true>), grid1, dim3(256), 0, s, k);
   }
   return md_launch_status();
+}
+
+md_status md_attention_prefill_slots(const md_attn_args* a, const int32_t* slots, hipStream_t stream) {
+  return md_attention_prefill_shared(a, slots, nullptr, nullptr, 0, stream);
 }
 
 extern "C" md_status md_attention_prefill(const md_attn_args* a, void* stream) {
@@ -990,4 +1330,52 @@ extern "C" md_status md_attention_decode_rope(const void* qkv, int64_t ld, void*
                                               int32_t rot_dim, float scale, void* stream) {
   return md_attention_decode_rope_slots(qkv, ld, o, ldo, freqs, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads,
                                         head_dim, rot_dim, scale, nullptr, 0, (hipStream_t)stream);
+}
+
+// internal (api.hip) and the kernel-level entry points of the shared-prefix decode: prefix_slots == nullptr is the slot-table
+// function (the same launch); otherwise the grouped kernel
+md_status md_attention_decode_shared_any(bool fused, const void* q, int64_t ldq, void* o, int64_t ldo, const float* freqs, void* k_slab,
+                                         void* v_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch,
+                                         int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim, float scale,
+                                         const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots, const int32_t* prefix_len,
+                                         hipStream_t stream) {
+  MD_CHECK_ARG((slots == nullptr || n_slots > 0) && n_heads > 0 && n_kv_heads > 0);
+  MD_CHECK_ARG(prefix_slots == nullptr || (prefix_len != nullptr && slots != nullptr));
+  if (prefix_slots == nullptr) {
+    if (fused)
+      return md_attention_decode_rope_slots(q, ldq, o, ldo, freqs, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads,
+                                            head_dim, rot_dim, scale, slots, n_slots, stream);
+    return md_attention_decode_slots(q, ldq, o, ldo, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads, n_kv_heads,
+                                     head_dim, scale, slots, n_slots, stream);
+  }
+  MD_CHECK_ARG(q && o && k_slab && v_slab && kv_len);
+  MD_CHECK_ARG(head_dim == 64 && ctx <= DEC_MAX_CTX && batch > 0 && n_heads % n_kv_heads == 0 && ldq % 8 == 0 && ldo % 8 == 0);
+  if (fused) {
+    MD_CHECK_ARG(freqs && n_heads == n_kv_heads && rot_dim % 2 == 0 && rot_dim > 0 && rot_dim <= 64);
+    MD_CHECK_ARG(ldq >= 3 * n_heads * 64 && ldo >= n_heads * 64);
+  } else {
+    MD_CHECK_ARG(ldq >= n_heads * 64 && ldo >= n_heads * 64);
+  }
+  return attn_decode_shared_launch(fused, q, ldq, o, ldo, fused ? freqs : nullptr, k_slab, v_slab, slab_batch_stride, ctx, kv_len,
+                                   batch, n_heads, n_kv_heads, fused ? rot_dim : 0, scale, slots, n_slots, prefix_slots, prefix_len,
+                                   stream);
+}
+
+extern "C" md_status md_attention_decode_shared(const void* q, int64_t ldq, void* o, int64_t ldo, const void* k_slab,
+                                                const void* v_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len,
+                                                int32_t batch, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, float scale,
+                                                const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
+                                                const int32_t* prefix_len, void* stream) {
+  return md_attention_decode_shared_any(false, q, ldq, o, ldo, nullptr, (void*)k_slab, (void*)v_slab, slab_batch_stride, ctx, kv_len,
+                                        batch, n_heads, n_kv_heads, head_dim, 0, scale, slots, n_slots, prefix_slots, prefix_len,
+                                        (hipStream_t)stream);
+}
+
+extern "C" md_status md_attention_decode_rope_shared(const void* qkv, int64_t ld, void* o, int64_t ldo, const float* freqs,
+                                                     void* k_slab, void* v_slab, int64_t slab_batch_stride, int32_t ctx,
+                                                     const int32_t* kv_len, int32_t batch, int32_t n_heads, int32_t head_dim,
+                                                     int32_t rot_dim, float scale, const int32_t* slots, int32_t n_slots,
+                                                     const int32_t* prefix_slots, const int32_t* prefix_len, void* stream) {
+  return md_attention_decode_shared_any(true, qkv, ld, o, ldo, freqs, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads,
+                                        n_heads, head_dim, rot_dim, scale, slots, n_slots, prefix_slots, prefix_len, (hipStream_t)stream);
 }

@@ -32,6 +32,7 @@ from .config import MoondreamConfig
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
 from .lora import variant_state_dict
+from .shared_prefix import check_shared_table, plan_shared_prefix
 from .weights import PackedLora, PackedModel
 
 BF16 = torch.bfloat16
@@ -50,6 +51,20 @@ class EncodedImage:
 
     pos: int
     caches: List[Tuple[torch.Tensor, torch.Tensor]]
+
+
+class _SharedTable:
+    """Device int32 tables of md_text_forward_shared / md_decode_step_shared for B rows: own slots, prefix slots, prefix
+    lengths (views of one buffer), and the number of slots the KV slabs address."""
+
+    def __init__(self, slots: torch.Tensor, prefix_slots: torch.Tensor, prefix_len: torch.Tensor, n_slots: int):
+        self.slots, self.prefix_slots, self.prefix_len, self.n_slots = slots, prefix_slots, prefix_len, int(n_slots)
+
+    def sub(self, r0: int, r1: int) -> "_SharedTable":
+        return _SharedTable(self.slots[r0:r1], self.prefix_slots[r0:r1], self.prefix_len[r0:r1], self.n_slots)
+
+    def args(self):
+        return self.slots.data_ptr(), self.n_slots, self.prefix_slots.data_ptr(), self.prefix_len.data_ptr()
 
 
 class IdTokenizer:
@@ -431,11 +446,14 @@ class MoondreamModel:
         return st
 
     def _text_forward(self, x: torch.Tensor, pos0: Union[int, Sequence[int]], slot0: int = 0, causal: bool = False,
-                      pos_dev: Optional[torch.Tensor] = None, lora: Optional[PackedLora] = None) -> torch.Tensor:
+                      pos_dev: Optional[torch.Tensor] = None, lora: Optional[PackedLora] = None,
+                      shared: Optional[_SharedTable] = None) -> torch.Tensor:
         """x [B,T,D] embeddings -> hidden [B,T,D]; K,V written at pos0[b]..pos0[b]+T-1.
         ``pos0`` is host data (one int for the whole batch or one per sequence): the slab has
         max_context slots per head and the kernels do not bounds-check, so the check is here
-        (the reference fails at this point too: its index_put / mask indexing raises)."""
+        (the reference fails at this point too: its index_put / mask indexing raises).
+        ``shared``: row b lives in slot shared.slots[b] and reads its image prefix from a shared slot
+        (md_text_forward_shared; ``slot0`` unused) -- the table was checked by ``_shared_plan``."""
         b, t, d = x.shape
         if self.strict_batch_invariance and lora is None and pos_dev is None and 1 < t <= 64 and b * t > 64:
             # The library picks the split-K decode-regime kernels by the ROW COUNT of a launch (<= 64 rows), and split-K sums
@@ -446,7 +464,8 @@ class MoondreamModel:
             outs = []
             for i0 in range(0, b, per):
                 p0 = pos0 if isinstance(pos0, int) else list(pos0)[i0 : i0 + per]
-                outs.append(self._text_forward(x[i0 : i0 + per], p0, slot0 + i0, causal=causal))
+                sh = shared.sub(i0, min(b, i0 + per)) if shared is not None else None
+                outs.append(self._text_forward(x[i0 : i0 + per], p0, slot0 + i0, causal=causal, shared=sh))
             return torch.cat(outs, dim=0)
         hi = pos0 if isinstance(pos0, int) else max(int(p) for p in pos0)
         lo = pos0 if isinstance(pos0, int) else min(int(p) for p in pos0)
@@ -464,10 +483,22 @@ class MoondreamModel:
             assert len(pos0) == b
             pos0 = self._h2d(torch.tensor([int(p) for p in pos0], dtype=torch.int32))
         text = self._causal_text_struct() if causal else self.w.text
-        self._ensure_batch(slot0 + b)
+        self._ensure_batch(shared.n_slots if shared is not None else slot0 + b)
         x = x.contiguous()
         hidden = torch.empty_like(x)
-        kv = self._kv_struct(slot0)
+        kv = self._kv_struct(0 if shared is not None else slot0)
+        if shared is not None:
+            assert lora is None and not causal and shared.slots.numel() == b
+            need = self.lib.md_text_workspace_bytes(C.byref(text), b, t)
+            ws = self._workspace(need)
+            _lib.check(
+                self.lib.md_text_forward_shared(
+                    C.byref(text), x.data_ptr(), hidden.data_ptr(), b, t, pos0.data_ptr(), *shared.args(), C.byref(kv),
+                    ws.data_ptr(), ws.numel(), self._stream(),
+                ),
+                "md_text_forward_shared",
+            )
+            return hidden
         if lora is not None:  # LoRA side path: unfused kernels + low-rank pairs (text.py:31-32,55-56; layers.py:129-146)
             need = self.lib.md_text_lora_workspace_bytes(C.byref(text), b, t)
             ws = self._workspace(need)
@@ -850,7 +881,8 @@ class MoondreamModel:
 
     # --------------------------------------------------------------- sampling
     def _pick(self, logits: torch.Tensor, temperature: float, top_p: float, suppress_id: int = -1,
-              generator: Optional[torch.Generator] = None, probs_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              generator: Optional[torch.Generator] = None, probs_out: Optional[torch.Tensor] = None,
+              row_perm: Optional[torch.Tensor] = None) -> torch.Tensor:
         """[B,V] -> int32 [B]   (reference: moondream.py:313-318,521-528).  Greedy: argmax, ties to the
         lowest id.  Otherwise temperature + top-p on the device (md_sample_top_p): the reference's
         softmax / _apply_top_p / multinomial semantics with one uniform per sequence from torch's
@@ -864,6 +896,8 @@ class MoondreamModel:
             )
             return nxt
         u = torch.rand(b, device=self._device, dtype=torch.float32, generator=generator)
+        if row_perm is not None:  # row i draws the uniform of row row_perm[i] (the shared-prefix rows in the copy path's order)
+            u = u[row_perm]
         _lib.check(
             self.lib.md_sample_top_p(
                 logits.data_ptr(), logits.stride(0), b, v, suppress_id, float(temperature), float(top_p), u.data_ptr(),
@@ -888,14 +922,15 @@ class MoondreamModel:
     def _decode_greedy(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
                        slot0: int = 0, eos_id: Optional[int] = None, check_every: int = 16,
                        lora: Optional[PackedLora] = None, allow_b1: bool = True, temperature: float = 0.0, top_p: float = 0.0,
-                       generator: Optional[torch.Generator] = None) -> torch.Tensor:
+                       generator: Optional[torch.Generator] = None, shared: Optional[_SharedTable] = None,
+                       row_perm: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``_decode_greedy_impl`` plus the safety net of the persistent single-sequence kernel: its software grid barriers
         need every workgroup resident; if one times out (the GPU was shared with another persistent kernel) the kernel
         raises an error word and finishes with garbage.  That state is fully re-initialised by decoding the same tokens
         again (K / V rows at positions >= ``pos``, the id history, the position buffer), so the call is repeated on the
         batched kernels and the persistent kernel is switched off for this model."""
         hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, slot0, eos_id, check_every, lora, allow_b1,
-                                        temperature, top_p, generator)
+                                        temperature, top_p, generator, shared, row_perm)
         if self._b1_used:
             torch.cuda.current_stream(self._device).synchronize()
             if int(self._b1_sync[64 * 11]) != 0:
@@ -913,7 +948,8 @@ class MoondreamModel:
     def _decode_greedy_impl(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
                             slot0: int = 0, eos_id: Optional[int] = None, check_every: int = 16,
                             lora: Optional[PackedLora] = None, allow_b1: bool = True, temperature: float = 0.0,
-                            top_p: float = 0.0, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+                            top_p: float = 0.0, generator: Optional[torch.Generator] = None,
+                            shared: Optional[_SharedTable] = None, row_perm: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Device-resident decode loop: returns int32 [steps+1, B] (row 0 = ``first``).  ``temperature`` 0: greedy.  Otherwise every
         step draws each sequence's token with the reference's rule (moondream.py:521-528: softmax(logits / T), _apply_top_p,
         multinomial) from the step's own logits on the device (md_sample_top_p), with one uniform per (step, sequence) taken
@@ -921,10 +957,13 @@ class MoondreamModel:
         reference: the generator of moondream.py:471-530 without its per-token host sync.
         ``pos`` is the position of the next token, one int or one per sequence (sequences whose
         prompts differ in length decode in the same lockstep batch).
-        With ``compile()`` the steps are replayed from a captured hipGraph in chunks."""
+        With ``compile()`` the steps are replayed from a captured hipGraph in chunks.
+        ``shared``: the steps are md_decode_step_shared over that table (``slot0`` unused); ``row_perm``: row i draws the
+        uniforms of row row_perm[i], so that sampled rows in another order see the draws of the copy path."""
         b = first.shape[0]
         t = self.config.text
-        self._ensure_batch(slot0 + b)
+        assert shared is None or lora is None
+        self._ensure_batch(shared.n_slots if shared is not None else slot0 + b)
         pos_list = [int(pos)] * b if isinstance(pos, int) else [int(p) for p in pos]
         assert len(pos_list) == b
         max_tokens = max(0, min(max_tokens, t.max_context - 1 - max(pos_list)))
@@ -936,16 +975,19 @@ class MoondreamModel:
         logits = self._decode_logits(b)
         need = self.lib.md_decode_workspace_bytes(C.byref(self.w.text), b)
         ws = self._workspace(need, 2)
-        kv = self._kv_struct(slot0)
+        kv = self._kv_struct(0 if shared is not None else slot0)
         pos_base = self._h2d(torch.tensor(pos_list, dtype=torch.int32))
         sample = temperature != 0
         uniforms = (torch.rand(max_tokens, b, device=self._device, dtype=torch.float32, generator=generator) if sample else None)
+        if sample and row_perm is not None:
+            uniforms = uniforms[:, row_perm].contiguous()
 
         # one sequence, greedy, no side path: the whole step as ONE persistent launch (csrc/decode_b1.hip) when the library
         # says this model / cache / device fits its static limits and its grid can be co-resident; anything else decodes on
         # the batched kernels.  Never from the pipelined engine (allow_b1 = False): a second stream's persistent GEMMs
         # could keep workgroups of the grid off the chip and its software barriers would time out.
-        b1 = (b == 1 and allow_b1 and not sample and self.single_sequence_kernel and lora is None and not bool(self.w.text.fp8)
+        b1 = (b == 1 and allow_b1 and not sample and self.single_sequence_kernel and lora is None and shared is None
+              and not bool(self.w.text.fp8)
               and bool(self.lib.md_decode_step_b1_supported(C.byref(self.w.text), C.byref(kv))))
         self._b1_used = b1
         if b1:
@@ -965,13 +1007,22 @@ class MoondreamModel:
                     "md_decode_step_b1",
                 )
                 return
-            _lib.check(
-                self.lib.md_decode_step(
-                    C.byref(self.w.text), tok_in.data_ptr(), tok_out.data_ptr(), pos_buf.data_ptr(), b, C.byref(kv),
-                    suppress_id, logits.data_ptr(), t.vocab_size, ws.data_ptr(), ws.numel(), self._stream(),
-                ),
-                "md_decode_step",
-            )
+            if shared is not None:
+                _lib.check(
+                    self.lib.md_decode_step_shared(
+                        C.byref(self.w.text), tok_in.data_ptr(), tok_out.data_ptr(), pos_buf.data_ptr(), b, *shared.args(),
+                        C.byref(kv), suppress_id, logits.data_ptr(), t.vocab_size, ws.data_ptr(), ws.numel(), self._stream(),
+                    ),
+                    "md_decode_step_shared",
+                )
+            else:
+                _lib.check(
+                    self.lib.md_decode_step(
+                        C.byref(self.w.text), tok_in.data_ptr(), tok_out.data_ptr(), pos_buf.data_ptr(), b, C.byref(kv),
+                        suppress_id, logits.data_ptr(), t.vocab_size, ws.data_ptr(), ws.numel(), self._stream(),
+                    ),
+                    "md_decode_step",
+                )
             if sample:  # the step left its logits [B, V] in ``logits``: draw from them instead of the argmax it wrote
                 _lib.check(
                     self.lib.md_sample_top_p(
@@ -1018,7 +1069,8 @@ class MoondreamModel:
             # a graph is replayed only on the stream (context) it was captured for: the pipelined engine's
             # decode stream and the default stream each keep their own captures
             key = ("decode", b, slot0, n, suppress_id, ws.data_ptr(), self._kv_k.data_ptr(), logits.data_ptr(),
-                   torch.cuda.current_stream(self._device).cuda_stream, b1, float(temperature), float(top_p))
+                   torch.cuda.current_stream(self._device).cuda_stream, b1, float(temperature), float(top_p),
+                   shared.args() if shared is not None else None)
             entry = self._graphs.get(key)
             if entry is None:
                 buf = torch.zeros(n + 1, b, dtype=torch.int32, device=self._device)
@@ -1172,6 +1224,82 @@ class MoondreamModel:
         mark("prompt_prefill")
         return order, first, hidden_last, next_pos
 
+    def _shares_prefix(self, lora: Optional[PackedLora]) -> bool:
+        """The shared-prefix path serves the base model over the bf16 cache; a LoRA variant or the fp8 mode's e4m3 KV copy
+        takes the copy path (same results)."""
+        return lora is None and self._kv8_scales is None
+
+    def _encode_distinct(self, images, settings: Optional[dict]) -> List[EncodedImage]:
+        """Each distinct image object encoded once (``encode_image``), repeated per row: the copy path's input."""
+        enc: Dict[int, EncodedImage] = {}
+        for im in images:
+            if id(im) not in enc:
+                enc[id(im)] = self.encode_image(im, settings)
+        return [enc[id(im)] for im in images]
+
+    def _prepare_sequences_shared(self, images, prompts: Sequence[Sequence[int]], mark=None, sampler=None):
+        """``_prepare_sequences`` with a SHARED image prefix (moondream_amd/shared_prefix.py): each distinct image (by identity)
+        is prefilled or loaded ONCE, into prefix slot k < P; the rows take slots P + r and read the prefix from there.  Raw
+        images go through one ViT batch and ``_prefill_images``; EncodedImages are loaded once.  One prompt prefill per
+        distinct length (md_text_forward_shared).  Returns (order, first, hidden_last, next_pos, table, row_perm): the first
+        four as ``_prepare_sequences`` returns them, in this path's row order; ``row_perm`` maps a row to its row in the copy
+        path's order (sampling draws).  Must run under torch.inference_mode()."""
+        mark = mark or (lambda name: None)
+        plan = plan_shared_prefix(list(images), [len(p) for p in prompts])
+        if any(len(p) == 0 for p in prompts):
+            raise ValueError("empty prompt")
+        b, n_img = len(plan.order), len(plan.distinct)
+        self._select_kernels(b)
+        prompts = [list(prompts[i]) for i in plan.order]
+        for im in plan.distinct:
+            if not isinstance(im, (EncodedImage, Image.Image)):
+                raise ValueError("image must be a PIL Image or EncodedImage")
+        self._ensure_batch(plan.n_slots)
+        mark("start")
+        pos = None
+        raw = [k for k, im in enumerate(plan.distinct) if not isinstance(im, EncodedImage)]
+        if raw:
+            img_emb = self._run_vision_encoder_batch([plan.distinct[k] for k in raw], mark)
+            mark("vision")
+            j = 0
+            while j < len(raw):  # every run of consecutive prefix slots in one prefill
+                k = j
+                while k + 1 < len(raw) and raw[k + 1] == raw[k] + 1:
+                    k += 1
+                pos = self._prefill_images(img_emb[j : k + 1], raw[j])
+                j = k + 1
+            mark("image_prefill")
+        for k, im in enumerate(plan.distinct):
+            if isinstance(im, EncodedImage):
+                if pos is not None and im.pos != pos:
+                    raise ValueError("EncodedImage with a different prefix length than the rest of the batch")
+                self.load_encoded_image(im, k)
+                pos = im.pos
+        check_shared_table(plan.own_slots, plan.prefix_slots, [pos] * b, [pos] * b, plan.n_slots)
+        buf = getattr(self, "_shared_buf", None)  # one persistent buffer: captured decode graphs keep its addresses
+        if buf is None or buf.numel() < 3 * b:
+            buf = torch.empty(3 * max(b, 64), dtype=torch.int32, device=self._device)
+            self._shared_buf = buf
+        buf[: 3 * b].copy_(self._h2d(torch.tensor(plan.own_slots + plan.prefix_slots + [pos] * b, dtype=torch.int32)))
+        table = _SharedTable(buf[0:b], buf[b : 2 * b], buf[2 * b : 3 * b], plan.n_slots)
+        row_perm = torch.tensor(plan.copy_rank, dtype=torch.int64, device=self._device)
+        first = torch.empty(b, dtype=torch.int32, device=self._device)
+        hidden_last = torch.empty(b, self.config.text.dim, dtype=BF16, device=self._device)
+        next_pos = [0] * b
+        for r0, r1 in plan.groups:  # one prefill per distinct prompt length
+            x = self._embed(torch.tensor(prompts[r0:r1], dtype=torch.int32))
+            hidden = self._text_forward(x, pos, shared=table.sub(r0, r1))
+            logits = self._lm_head(hidden)
+            if sampler is None:
+                first[r0:r1] = self._pick(logits, 0.0, 0.0)
+            else:  # the group's draws in the copy path's row order
+                local = row_perm[r0:r1] - min(plan.copy_rank[r0:r1])
+                first[r0:r1] = self._pick(logits, *sampler, row_perm=local)
+            hidden_last[r0:r1] = hidden[:, -1, :]
+            next_pos[r0:r1] = [pos + x.shape[1]] * (r1 - r0)
+        mark("prompt_prefill")
+        return plan.order, first, hidden_last, next_pos, table, row_perm
+
     def batch_generate_ids(
         self,
         images: Sequence[Union[Image.Image, EncodedImage]],
@@ -1183,8 +1311,15 @@ class MoondreamModel:
         temperature: float = 0.0,
         top_p: float = DEFAULT_TOP_P,
         generator: Optional[torch.Generator] = None,
+        share_prefix: bool = False,
     ) -> List[List[int]]:
         """Token ids for B (image, prompt-ids) pairs, decoded in lockstep; greedy by default.
+
+        ``share_prefix``: rows whose image is the same object (the same ``EncodedImage``, or the same PIL image by identity)
+        read ONE copy of its KV prefix -- the image is encoded / loaded once, and the decode attention loads each prefix row
+        once for a group of rows (md_decode_step_shared).  The ids are those of the same call with every image replaced by
+        its ``EncodedImage`` (the copy path), greedy or sampled with the same ``generator`` seed.  A LoRA ``variant`` or the
+        fp8 KV mode takes the copy path.
 
         ``temperature`` > 0 (round 6): every sequence SAMPLES each of its tokens -- the first from the prompt pass's logits,
         the rest inside the lockstep loop -- with the reference's rule (softmax(logits / T), ``_apply_top_p``, multinomial:
@@ -1226,12 +1361,18 @@ class MoondreamModel:
         lora = self._lora({"variant": variant})
         with torch.inference_mode():
             sampler = None if temperature == 0 else (float(temperature), float(top_p), -1, generator)
-            order, first, _, next_pos = self._prepare_sequences(list(images), prompts, mark, lora, fuse=True, sampler=sampler)
+            shared = row_perm = None
+            if share_prefix and self._shares_prefix(lora):
+                order, first, _, next_pos, shared, row_perm = self._prepare_sequences_shared(list(images), prompts, mark, sampler)
+            else:
+                if share_prefix:  # the copy path over each distinct image's EncodedImage
+                    images = self._encode_distinct(images, {"variant": variant})
+                order, first, _, next_pos = self._prepare_sequences(list(images), prompts, mark, lora, fuse=True, sampler=sampler)
             b = len(order)
             stop = None if ignore_eos else eos
             hist = self._decode_greedy(first, next_pos if len(set(next_pos)) > 1 else next_pos[0], max_tokens,
                                        tk.answer_id, 0, stop, lora=lora, temperature=float(temperature), top_p=float(top_p),
-                                       generator=generator)
+                                       generator=generator, shared=shared, row_perm=row_perm)
             mark("decode")
             cols = hist.t().tolist()
             if b == 1:
@@ -1469,15 +1610,18 @@ class MoondreamModel:
         ids = self.batch_generate_ids(images, [tpl[length]] * len(images), **self._sampling_kwargs(settings))
         return [self.tokenizer.decode(s) for s in ids]
 
-    def batch_query(self, images, questions: Sequence[str], settings: Optional[dict] = None) -> List[str]:
+    def _query_prompts(self, questions: Sequence[str]) -> List[List[int]]:
+        """The prompt ids of ``batch_query`` / ``query_many``."""
         tpl = self.config.tokenizer.templates["query"]
         if tpl is None:
             raise NotImplementedError("Model does not support querying.")
-        prompts = [
+        return [
             list(tpl["prefix"]) + list(self.tokenizer.encode(q).ids) + list(tpl["suffix"]) + list(tpl["suffix"])
             for q in questions
         ]
-        ids = self.batch_generate_ids(images, prompts, **self._sampling_kwargs(settings))
+
+    def batch_query(self, images, questions: Sequence[str], settings: Optional[dict] = None) -> List[str]:
+        ids = self.batch_generate_ids(images, self._query_prompts(questions), **self._sampling_kwargs(settings))
         return [self.tokenizer.decode(s) for s in ids]
 
     def batch_generate(self, images, prompts: Optional[Sequence[str]] = None, settings: Optional[dict] = None) -> List[str]:
@@ -1810,7 +1954,8 @@ class MoondreamModel:
         return self._lin(feats, enc)
 
     def _points_loop(self, hidden: torch.Tensor, first: torch.Tensor, pos: Sequence[int], slot0: int, include_size: bool,
-                     max_objects: int, lora: Optional[PackedLora] = None, run_all: bool = False) -> List[List[dict]]:
+                     max_objects: int, lora: Optional[PackedLora] = None, run_all: bool = False,
+                     shared: Optional[_SharedTable] = None) -> List[List[dict]]:
         """The loop of moondream.py:653-733 for B sequences in lockstep.  hidden [B, D] = last prompt
         position, first int32 [B] = the token after the prompt, pos[b] = next position."""
         b = hidden.shape[0]
@@ -1828,7 +1973,7 @@ class MoondreamModel:
 
         def step(emb):
             nonlocal pos_host, hidden
-            h = self._text_forward(emb.reshape(b, 1, -1), pos_host, slot0, pos_dev=pos_dev, lora=lora)
+            h = self._text_forward(emb.reshape(b, 1, -1), pos_host, slot0, pos_dev=pos_dev, lora=lora, shared=shared)
             pos_host = [p + 1 for p in pos_host]
             pos_dev.add_(1)
             hidden = h.reshape(b, -1)
@@ -1879,7 +2024,8 @@ class MoondreamModel:
             first = next_token.reshape(1).to(device=self._device, dtype=torch.int32)
             return self._points_loop(hidden.reshape(1, -1), first, [pos], 0, include_size, max_objects)[0]
 
-    def _batch_detect_like(self, images, objects: Sequence[str], kind: str, include_size: bool, settings: Optional[dict]):
+    def _batch_detect_like(self, images, objects: Sequence[str], kind: str, include_size: bool, settings: Optional[dict],
+                           share_prefix: bool = False):
         tpl = self.config.tokenizer.templates[kind]
         if tpl is None:
             raise NotImplementedError(f"Model does not support {kind}.")
@@ -1896,9 +2042,15 @@ class MoondreamModel:
                 marks.append((name, e))
 
         with torch.inference_mode():
-            order, first, hidden, next_pos = self._prepare_sequences(list(images), prompts, mark, lora)
+            shared = None
+            if share_prefix and self._shares_prefix(lora):
+                order, first, hidden, next_pos, shared, _ = self._prepare_sequences_shared(list(images), prompts, mark)
+            else:
+                if share_prefix:
+                    images = self._encode_distinct(images, settings)
+                order, first, hidden, next_pos = self._prepare_sequences(list(images), prompts, mark, lora)
             res = self._points_loop(hidden, first, next_pos, 0, include_size, max_objects, lora,
-                                    run_all=bool((settings or {}).get("_run_all_objects", False)))
+                                    run_all=bool((settings or {}).get("_run_all_objects", False)), shared=shared)
             mark("points_loop")
         if self.collect_timing and len(marks) > 1:
             torch.cuda.synchronize(self._device)
@@ -1914,6 +2066,29 @@ class MoondreamModel:
 
     def batch_point(self, images, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
         return [{"points": o} for o in self._batch_detect_like(images, objects, "point", False, settings)]
+
+    # ------------------------------------------------ one image, many prompts
+    def query_many(self, image, questions: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
+        """Many questions about ONE image (reference pattern: encode_image once, then query per question,
+        moondream.py:230-268,620-623), answered in one batch that reads a single copy of the image's KV prefix.  Element i ==
+        ``{"answer": batch_query([encode_image(image)] * N, questions)[i]}``.  A LoRA ``variant`` (settings) or the fp8 KV mode
+        takes the copy path, with the same results."""
+        prompts = self._query_prompts(questions)
+        enc = self.encode_image(image, settings)
+        ids = self.batch_generate_ids([enc] * len(prompts), prompts, share_prefix=True, **self._sampling_kwargs(settings))
+        return [{"answer": self.tokenizer.decode(s)} for s in ids]
+
+    def detect_many(self, image, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
+        """``detect`` of many objects in ONE image over a single copy of its KV prefix.  Element i ==
+        ``batch_detect([encode_image(image)] * N, objects)[i]``.  LoRA variant / fp8 KV mode: the copy path, same results."""
+        enc = self.encode_image(image, settings)
+        return [{"objects": o} for o in self._batch_detect_like([enc] * len(objects), objects, "detect", True, settings, True)]
+
+    def point_many(self, image, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
+        """``point`` for many objects in ONE image over a single copy of its KV prefix.  Element i ==
+        ``batch_point([encode_image(image)] * N, objects)[i]``.  LoRA variant / fp8 KV mode: the copy path, same results."""
+        enc = self.encode_image(image, settings)
+        return [{"points": o} for o in self._batch_detect_like([enc] * len(objects), objects, "point", False, settings, True)]
 
     def batch_detect_pipelined(self, batches, settings: Optional[dict] = None, kind: str = "detect"):
         """Generator over an iterable of (images, objects) batches; yields ``batch_detect`` / ``batch_point`` (``kind``) of
