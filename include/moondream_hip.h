@@ -711,6 +711,66 @@ md_status md_decode_step_shared(const md_text_model* m, const int32_t* tokens, i
                                 const md_kv_cache* kv, int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* Mixed LoRA variants in one batch (csrc/lora_multi.hip).  A BANK holds up to MD_LORA_MAX_VARIANTS resident variants; a
+ * device int32 table variant[b] names sequence b's variant, and every value outside [0, n_variants) (-1 by convention) is
+ * the base model.  Every token row of sequence b (q_len > 1: one segment) takes variant[b].  Per block, each row follows
+ * the rounding order of md_text_forward_lora's comment (the reference's): qkv = bf16(bf16(qkv(l_in)) + bf16(delta)), and so
+ * on.  A row's result does not depend on the other rows of the call or on their variants.
+ *
+ * The bank: rank[v][pair] is the packed rank of pair (0 qkv, 1 proj, 2 fc1, 3 fc2) of variant v, the true rank rounded up
+ * to 16 (0: no such pair in any layer), at most MD_LORA_MAX_RANK.  table: device memory of md_lora_bank_table_bytes(n_layers)
+ * bytes, [layer][MD_LORA_MAX_VARIANTS][pair] of (A, B) device pointers, written by md_lora_bank_set_variant; a NULL entry (a
+ * pair missing in that layer) adds nothing.  A variant's pairs are md_lora_pair of md_linear with a [rank][in] (n_pad = the
+ * packed rank, k = k_pad = in) and b [out][rank] (k_pad = the packed rank); the padding rows / columns are zero. */
+#define MD_LORA_MAX_VARIANTS 16
+#define MD_LORA_MAX_RANK 256
+#define MD_LORA_QKV 1   /* pair bits of md_lora_shrink_grouped */
+#define MD_LORA_PROJ 2
+#define MD_LORA_FC1 4
+#define MD_LORA_FC2 8
+#define MD_LORA_ADD 0   /* md_lora_expand_grouped: out = bf16(bf16(out) + bf16(delta)), then gelu on columns >= gelu_from */
+#define MD_LORA_DELTA 1 /*                         out = bf16(delta) (0 for rows without the pair) */
+typedef struct {
+  int32_t n_variants;
+  int32_t n_layers;
+  int32_t rank[MD_LORA_MAX_VARIANTS][4];
+  void* table;
+} md_lora_bank;
+
+size_t md_lora_bank_table_bytes(int32_t n_layers);
+/* An empty bank over `table` (zeroed here; host call, synchronous). */
+md_status md_lora_bank_init(md_lora_bank* bank, int32_t n_layers, void* table, size_t table_bytes);
+/* Variant `index` (<= n_variants: replace one or append) from a host array of m->n_layers md_text_block_lora.  Checks the
+ * shapes against m; a rank above MD_LORA_MAX_RANK: MD_ERR_UNSUPPORTED.  Host call, synchronous (copies into the table). */
+md_status md_lora_bank_set_variant(md_lora_bank* bank, const md_text_model* m, int32_t index, const md_text_block_lora* lora);
+
+/* Kernel-level entry points.  Shrink: t[row] = the concatenation, in pair order, of bf16(x[row] A_p^T) over the pairs p set in
+ * `pairs`, for the row's variant (a variant lacking a pair has no columns for it); x [batch * q_len][ldx] with k columns
+ * (k % 32 == 0).  Expand: for the pair `pair` of a t shrunk with `t_pairs`, out[row, :n] as MD_LORA_ADD / MD_LORA_DELTA says
+ * (n % 16 == 0; gelu_from < 0 or >= n: no GELU).  Rows of the base model: ADD leaves out (GELU still applies), DELTA writes 0. */
+md_status md_lora_shrink_grouped(const md_lora_bank* bank, int32_t layer, int32_t pairs, const int32_t* variant, int32_t batch,
+                                 int32_t q_len, const void* x, int64_t ldx, int32_t k, void* t, int64_t ldt, void* stream);
+md_status md_lora_expand_grouped(const md_lora_bank* bank, int32_t layer, int32_t pair, int32_t t_pairs, const int32_t* variant,
+                                 int32_t batch, int32_t q_len, const void* t, int64_t ldt, void* out, int64_t ldo, int32_t n,
+                                 int32_t flags, int32_t gelu_from, void* stream);
+
+/* md_text_forward_slots with per-sequence variants.  bank == NULL: exactly md_text_forward_slots.  Per layer, four launches
+ * beyond the base path: one shrink from l_in for qkv, proj and fc1 together, one expand adding the qkv and fc1 deltas (and
+ * GELU, which the fused qkv|fc1 GEMM then leaves out), the fc2 shrink, and one expand of the proj and fc2 deltas, which
+ * the fused block tail adds.  fp8 weight copies (m->fp8, m->f8) and the e4m3 KV copy: MD_ERR_UNSUPPORTED.  No host sync;
+ * capturable.  Workspace: md_text_multi_lora_workspace_bytes. */
+size_t md_text_multi_lora_workspace_bytes(const md_text_model* m, const md_lora_bank* bank, int32_t batch, int32_t q_len);
+md_status md_text_forward_multi_lora(const md_text_model* m, const md_lora_bank* bank, const int32_t* variant, const void* x,
+                                     void* hidden, int32_t batch, int32_t q_len, const int32_t* pos0, const int32_t* slots,
+                                     int32_t n_slots, const md_kv_cache* kv, void* workspace, size_t workspace_bytes, void* stream);
+/* md_decode_step_slots over md_text_forward_multi_lora (bank == NULL: exactly md_decode_step_slots).
+ * Workspace: md_decode_multi_lora_workspace_bytes. */
+size_t md_decode_multi_lora_workspace_bytes(const md_text_model* m, const md_lora_bank* bank, int32_t batch);
+md_status md_decode_step_multi_lora(const md_text_model* m, const md_lora_bank* bank, const int32_t* variant, const int32_t* tokens,
+                                    int32_t* next, int32_t* pos, int32_t batch, const int32_t* slots, int32_t n_slots,
+                                    const md_kv_cache* kv, int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

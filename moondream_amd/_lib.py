@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libmoondream_hip.so")
-SOURCES = ["gemm_bf16.hip", "gemm_w4.hip", "gemm_fp8w.hip", "gemm_f8.hip", "quant_f8.hip", "attention_f8kv.hip", "decode_b1.hip", "attention.hip", "elementwise.hip", "sampling_region.hip", "api.hip"]
+SOURCES = ["gemm_bf16.hip", "gemm_w4.hip", "gemm_fp8w.hip", "gemm_f8.hip", "quant_f8.hip", "attention_f8kv.hip", "decode_b1.hip", "attention.hip", "elementwise.hip", "sampling_region.hip", "lora_multi.hip", "api.hip"]
 
 MD_OK = 0
 ABI_VERSION = 5  # include/moondream_hip.h MD_ABI_VERSION
@@ -142,6 +142,15 @@ class MdTextBlockLora(C.Structure):
     _fields_ = [("qkv", MdLoraPair), ("proj", MdLoraPair), ("fc1", MdLoraPair), ("fc2", MdLoraPair)]
 
 
+MD_LORA_MAX_VARIANTS, MD_LORA_MAX_RANK = 16, 256
+MD_LORA_QKV, MD_LORA_PROJ, MD_LORA_FC1, MD_LORA_FC2 = 1, 2, 4, 8  # md_lora_shrink_grouped pair bits
+MD_LORA_ADD, MD_LORA_DELTA = 0, 1
+
+
+class MdLoraBank(C.Structure):
+    _fields_ = [("n_variants", c_int32), ("n_layers", c_int32), ("rank", (c_int32 * 4) * MD_LORA_MAX_VARIANTS), ("table", c_void_p)]
+
+
 class MdKvCache(C.Structure):
     _fields_ = [("k", c_void_p), ("v", c_void_p), ("layer_stride", c_int64), ("batch_stride", c_int64), ("ctx", c_int32),
                 ("k8", c_void_p), ("v8", c_void_p), ("k_scale", c_void_p), ("v_scale", c_void_p)]
@@ -216,6 +225,19 @@ SIGNATURES = {
     "md_text_lora_workspace_bytes": (c_size_t, [P(MdTextModel), c_int32, c_int32]),
     "md_text_forward_lora": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, P(MdKvCache),
                                        c_void_p, c_size_t, c_void_p]),
+    "md_lora_bank_table_bytes": (c_size_t, [c_int32]),
+    "md_lora_bank_init": (C.c_int, [P(MdLoraBank), c_int32, c_void_p, c_size_t]),
+    "md_lora_bank_set_variant": (C.c_int, [P(MdLoraBank), P(MdTextModel), c_int32, c_void_p]),
+    "md_lora_shrink_grouped": (C.c_int, [P(MdLoraBank), c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32,
+                                         c_void_p, c_int64, c_void_p]),
+    "md_lora_expand_grouped": (C.c_int, [P(MdLoraBank), c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int64,
+                                         c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
+    "md_text_multi_lora_workspace_bytes": (c_size_t, [P(MdTextModel), P(MdLoraBank), c_int32, c_int32]),
+    "md_text_forward_multi_lora": (C.c_int, [P(MdTextModel), P(MdLoraBank), c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                                             c_void_p, c_int32, P(MdKvCache), c_void_p, c_size_t, c_void_p]),
+    "md_decode_multi_lora_workspace_bytes": (c_size_t, [P(MdTextModel), P(MdLoraBank), c_int32]),
+    "md_decode_step_multi_lora": (C.c_int, [P(MdTextModel), P(MdLoraBank), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                            c_int32, P(MdKvCache), c_int32, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
     "md_add_bf16": (C.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     "md_gelu_bf16": (C.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     "md_lm_head_workspace_bytes": (c_size_t, [P(MdTextModel), c_int32]),

@@ -65,6 +65,7 @@ class Request:
     step_limit: int = 0
     done: bool = False
     generator: object = None
+    variant: int = -1  # index in the model's LoRA bank (md_lora_bank); -1: the base model
 
     @property
     def remaining(self) -> int:
@@ -267,8 +268,6 @@ class ContinuousEngine:
 
         from .moondream import EncodedImage
 
-        if variant is not None:
-            raise ValueError("continuous batching has no LoRA side path (md_text_forward_lora has no slot table)")
         if not isinstance(image, (Image.Image, EncodedImage)):
             raise ValueError("image must be a PIL Image or EncodedImage")
         prompt = [int(p) for p in prompt_ids]
@@ -279,10 +278,22 @@ class ContinuousEngine:
         if prefix + len(prompt) > t.max_context:
             raise ValueError(f"image prefix + prompt ({prefix + len(prompt)} positions) do not fit the {t.max_context}-slot context")
         eos = None if ignore_eos else (self.model.config.tokenizer.eos_id if eos_id is None else int(eos_id))
+        vidx = -1 if variant is None else self._variant_index(variant)
         rid = self._next_rid
         self._next_rid += 1
-        self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed))
+        self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed, variant=vidx))
         return rid
+
+    def _variant_index(self, variant: str) -> int:
+        """The bank index of a LoRA variant the model can resolve (registered, or in the on-disk cache); ValueError otherwise,
+        before any GPU work (the lookup precedes the packing)."""
+        resolve = getattr(self.model, "_bank_index", None)
+        if resolve is None:
+            raise ValueError(f"this model serves no LoRA variants (asked for {variant!r})")
+        try:
+            return int(resolve(variant))
+        except (FileNotFoundError, KeyError) as e:
+            raise ValueError(f"unknown LoRA variant {variant!r}") from e
 
     def submit_caption(self, image, length: str = "normal", **kw) -> int:
         """The prompt ``batch_caption`` builds."""
@@ -321,8 +332,16 @@ class ContinuousEngine:
         m._select_kernels(2)  # MD_TILE_PINNED: a request's bits do not depend on what else is launched
         top = self.sched.buckets[-1]
         m._decode_logits(top)
-        m._workspace(m.lib.md_decode_workspace_bytes(C.byref(m.w.text), top), 2)
+        m._workspace(self._decode_ws_bytes(top), 2)
         self._kv_ptr = m._kv_k.data_ptr()
+
+    def _decode_ws_bytes(self, bucket: int) -> int:
+        """A decode chunk's workspace: the multi-LoRA step's once the model has a bank (it covers the plain step too)."""
+        m = self.model
+        bank = getattr(m, "_bank", None)
+        if bank is not None and len(bank):
+            return m.lib.md_decode_multi_lora_workspace_bytes(C.byref(m.w.text), C.byref(bank.struct), bucket)
+        return m.lib.md_decode_workspace_bytes(C.byref(m.w.text), bucket)
 
     def run_text(self) -> Iterator[Tuple[int, str]]:
         for rid, ids in self.run():
@@ -361,8 +380,9 @@ class ContinuousEngine:
 
         return torch.rand(n, dtype=torch.float32, generator=self._generator(r))
 
-    def _forward_slots(self, x, pos0: int, slots: List[int]):
-        """x [k, T, D] -> hidden [k, T, D] through md_text_forward_slots; K / V rows written into ``slots``."""
+    def _forward_slots(self, x, pos0: int, slots: List[int], variants: Optional[List[int]] = None):
+        """x [k, T, D] -> hidden [k, T, D] through md_text_forward_slots; K / V rows written into ``slots``.  ``variants`` with a
+        LoRA row: md_text_forward_multi_lora with those per-row bank indices."""
         import torch
 
         from . import _lib
@@ -373,8 +393,17 @@ class ContinuousEngine:
         hidden = torch.empty_like(x)
         pos_d = torch.full((k,), int(pos0), dtype=torch.int32, device=m.device)
         slots_d = m._h2d(torch.tensor(slots, dtype=torch.int32))
-        ws = m._workspace(m.lib.md_text_workspace_bytes(C.byref(m.w.text), k, t))
         kv = m._kv_struct(0)
+        if variants is not None and any(v >= 0 for v in variants):
+            bank = C.byref(m._bank.struct)
+            var_d = m._h2d(torch.tensor(variants, dtype=torch.int32))
+            ws = m._workspace(m.lib.md_text_multi_lora_workspace_bytes(C.byref(m.w.text), bank, k, t))
+            _lib.check(m.lib.md_text_forward_multi_lora(C.byref(m.w.text), bank, var_d.data_ptr(), x.data_ptr(), hidden.data_ptr(), k, t,
+                                                        pos_d.data_ptr(), slots_d.data_ptr(), self.max_live, C.byref(kv), ws.data_ptr(),
+                                                        ws.numel(), m._stream()), "md_text_forward_multi_lora")
+            self.stats.prefill_passes += 1
+            return hidden
+        ws = m._workspace(m.lib.md_text_workspace_bytes(C.byref(m.w.text), k, t))
         _lib.check(m.lib.md_text_forward_slots(C.byref(m.w.text), x.data_ptr(), hidden.data_ptr(), k, t, pos_d.data_ptr(),
                                                slots_d.data_ptr(), self.max_live, C.byref(kv), ws.data_ptr(), ws.numel(),
                                                m._stream()), "md_text_forward_slots")
@@ -433,7 +462,7 @@ class ContinuousEngine:
                 bos = m._embed(torch.full((k, 1), tk.bos_id, dtype=torch.int32))
                 pe = m._embed(torch.tensor([reqs[i].prompt for i in idx], dtype=torch.int32))
                 x = torch.cat([bos, img_emb[[emb_of[i] for i in idx]], pe], dim=1)
-                hidden = self._forward_slots(x, 0, [reqs[i].slot for i in idx])
+                hidden = self._forward_slots(x, 0, [reqs[i].slot for i in idx], [reqs[i].variant for i in idx])
                 first = self._first_tokens(hidden, [reqs[i] for i in idx]).tolist()
                 for i, f in zip(idx, first):
                     firsts[i], pos_of[i] = int(f), x.shape[1]
@@ -442,7 +471,7 @@ class ContinuousEngine:
             if raw:
                 bos = m._embed(torch.full((len(raw), 1), tk.bos_id, dtype=torch.int32))
                 x = torch.cat([bos, img_emb], dim=1)
-                self._forward_slots(x, 0, [reqs[i].slot for i in raw])
+                self._forward_slots(x, 0, [reqs[i].slot for i in raw], [reqs[i].variant for i in raw])
                 for i in raw:
                     prefix[i] = x.shape[1]
             for i, r in enumerate(reqs):
@@ -455,7 +484,7 @@ class ContinuousEngine:
                 for j0 in range(0, len(idx), per):
                     sub = idx[j0 : j0 + per]
                     pe = m._embed(torch.tensor([reqs[i].prompt for i in sub], dtype=torch.int32))
-                    hidden = self._forward_slots(pe, prefix[sub[0]], [reqs[i].slot for i in sub])
+                    hidden = self._forward_slots(pe, prefix[sub[0]], [reqs[i].slot for i in sub], [reqs[i].variant for i in sub])
                     first = self._first_tokens(hidden, [reqs[i] for i in sub]).tolist()
                     for i, f in zip(sub, first):
                         firsts[i], pos_of[i] = int(f), prefix[i] + t
@@ -463,7 +492,8 @@ class ContinuousEngine:
 
     def _buffers(self, bucket: int):
         """Fixed-address buffers of a (chunk, bucket): int32 device state [slots (chunk x bucket) | pos (bucket) | tokens ((chunk + 1) x
-        bucket)] with its pinned host staging (one H2D copy of everything a chunk reads), and fp32 uniforms [chunk x bucket]."""
+        bucket) | row variants (bucket)] with its pinned host staging (one H2D copy of everything a chunk reads), and fp32 uniforms
+        [chunk x bucket].  The row-variant table sits next to the slot table; only chunks with a LoRA row read it."""
         import torch
 
         bufs = self.model.__dict__.setdefault("_continuous_bufs", {})  # on the model: engines of one model share captured chunks
@@ -472,9 +502,9 @@ class ContinuousEngine:
         if b is None:
             c = self.chunk
             n_in = c * bucket + bucket + bucket
-            dev = torch.zeros(n_in + c * bucket, dtype=torch.int32, device=self.model.device)
+            dev = torch.zeros(n_in + c * bucket + bucket, dtype=torch.int32, device=self.model.device)
             with torch.inference_mode(False):
-                host = torch.zeros(n_in, dtype=torch.int32, pin_memory=True)
+                host = torch.zeros(n_in + bucket, dtype=torch.int32, pin_memory=True)
                 u_host = torch.zeros(c * bucket, dtype=torch.float32, pin_memory=True)
             u_dev = torch.zeros(c * bucket, dtype=torch.float32, device=self.model.device)
             b = bufs[key] = (dev, host, u_dev, u_host, n_in)
@@ -493,12 +523,19 @@ class ContinuousEngine:
         dev, host, u_dev, u_host, n_in = self._buffers(B)
         slots_d = dev[: c * B].view(c, B)
         pos_d = dev[c * B : c * B + B]
-        hist = dev[c * B + B :].view(c + 1, B)
+        hist = dev[c * B + B : n_in + c * B].view(c + 1, B)
+        var_d = dev[n_in + c * B :]
         hs = host.numpy()
         hs[: c * B].reshape(c, B)[:n] = plan.slots
         hs[c * B : c * B + B] = plan.pos
-        hs[c * B + B :] = plan.tokens
-        dev[:n_in].copy_(host, non_blocking=True)
+        hs[c * B + B : n_in] = plan.tokens
+        row_var = [r.variant for r in plan.rows]
+        lora = any(v >= 0 for v in row_var)
+        dev[:n_in].copy_(host[:n_in], non_blocking=True)
+        if lora:
+            hs[n_in:] = -1
+            hs[n_in : n_in + len(row_var)] = row_var
+            var_d.copy_(host[n_in:], non_blocking=True)
         sample = self.temperature != 0
         if sample:
             uh = u_host.numpy().reshape(c, B)
@@ -509,14 +546,20 @@ class ContinuousEngine:
             u_dev.copy_(u_host, non_blocking=True)
         u2 = u_dev.view(c, B)
         logits = m._decode_logits(B)
-        ws = m._workspace(m.lib.md_decode_workspace_bytes(C.byref(m.w.text), B), 2)
+        ws = m._workspace(self._decode_ws_bytes(B), 2)
         kv = m._kv_struct(0)
 
         def one_step(i):
-            _lib.check(m.lib.md_decode_step_slots(C.byref(m.w.text), hist[i].data_ptr(), hist[i + 1].data_ptr(), pos_d.data_ptr(), B,
-                                                  slots_d[i].data_ptr(), self.max_live, C.byref(kv), m.config.tokenizer.answer_id,
-                                                  logits.data_ptr(), t.vocab_size, ws.data_ptr(), ws.numel(), m._stream()),
-                       "md_decode_step_slots")
+            if lora:  # a LoRA row in the chunk: the multi-LoRA step with the chunk's row-variant table
+                _lib.check(m.lib.md_decode_step_multi_lora(C.byref(m.w.text), C.byref(m._bank.struct), var_d.data_ptr(), hist[i].data_ptr(),
+                                                           hist[i + 1].data_ptr(), pos_d.data_ptr(), B, slots_d[i].data_ptr(), self.max_live,
+                                                           C.byref(kv), m.config.tokenizer.answer_id, logits.data_ptr(), t.vocab_size,
+                                                           ws.data_ptr(), ws.numel(), m._stream()), "md_decode_step_multi_lora")
+            else:
+                _lib.check(m.lib.md_decode_step_slots(C.byref(m.w.text), hist[i].data_ptr(), hist[i + 1].data_ptr(), pos_d.data_ptr(), B,
+                                                      slots_d[i].data_ptr(), self.max_live, C.byref(kv), m.config.tokenizer.answer_id,
+                                                      logits.data_ptr(), t.vocab_size, ws.data_ptr(), ws.numel(), m._stream()),
+                           "md_decode_step_slots")
             if sample:  # the step left its logits in ``logits``: draw from them instead of the argmax it wrote
                 _lib.check(m.lib.md_sample_top_p(logits.data_ptr(), logits.stride(0), B, t.vocab_size, m.config.tokenizer.answer_id,
                                                  self.temperature, self.top_p, u2[i].data_ptr(), hist[i + 1].data_ptr(), None, 0,
@@ -529,6 +572,8 @@ class ContinuousEngine:
             stream = torch.cuda.current_stream(m.device).cuda_stream
             key = ("continuous", stream, B, n, dev.data_ptr(), ws.data_ptr(), m._kv_k.data_ptr(), logits.data_ptr(), self.temperature,
                    self.top_p)
+            if lora:  # the bank's ranks are launch shapes of the capture
+                key = key + ("lora", m._bank.generation)
             g = m._graphs.get(key)
             if g is not None:
                 g.replay()

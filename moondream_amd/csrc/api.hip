@@ -3,6 +3,7 @@
 // in this library.  Nothing here allocates or synchronises; every buffer,
 // including the workspace, belongs to the caller.
 #include "gemm_internal.hpp"
+#include <climits>
 #include <cstdlib>
 
 #include <algorithm>
@@ -425,6 +426,13 @@ md_status md_rope_kv_write_slots(void* qkv, int64_t ld, const float* freqs, cons
                                  int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim, const int32_t* slots, int32_t n_slots,
                                  hipStream_t stream);
 md_status md_attention_prefill_slots(const md_attn_args* a, const int32_t* slots, hipStream_t stream);
+// lora_multi.hip / elementwise.hip: the pieces of the multi-LoRA path
+md_status lora_bank_ok(const md_lora_bank* bank);
+int32_t md_lora_shrink_cols(const md_lora_bank* bank, int32_t pairs);
+md_status md_reduce_residual_layernorm_add(void* x, int64_t ldx, const float* partial_a, int32_t slices_a, const void* bias_a,
+                                           const float* partial_b, int32_t slices_b, const void* bias_b, int64_t ld_partial,
+                                           int64_t slice_stride, void* y, int64_t ldy, const md_layernorm* ln, int32_t rows,
+                                           int32_t dim, float eps, const void* da, const void* db, int64_t ldd, void* stream);
 md_status md_attention_prefill_shared(const md_attn_args* a, const int32_t* slots, const int32_t* pfx_slots, const int32_t* pfx_len,
                                       int32_t n_slots, hipStream_t stream);
 md_status md_attention_decode_shared_any(bool fused, const void* q, int64_t ldq, void* o, int64_t ldo, const float* freqs, void* k_slab,
@@ -448,10 +456,32 @@ extern "C" md_status md_text_forward(const md_text_model* m, const void* x_in, v
   return md_text_forward_slots(m, x_in, hidden, batch, q_len, pos0, nullptr, 0, kv, workspace, workspace_bytes, stream);
 }
 
+// md_text_forward_multi_lora: the bank and the per-sequence variant table of the rows of this call
+struct LoraCall {
+  const md_lora_bank* bank;
+  const int32_t* variant;
+};
+struct LoraBufs {
+  bf16_t *t1, *t2, *d_proj, *d_fc2;  // shrink outputs [M][ld1] / [M][ld2]; proj / fc2 deltas (or outputs) [M][dim]
+  int64_t ld1, ld2;
+  size_t total;
+};
+LoraBufs lora_bufs(const md_text_model* m, const md_lora_bank* bank, size_t M, void* base) {
+  LoraBufs w;
+  Arena a{(char*)base, 0};
+  w.ld1 = md_lora_shrink_cols(bank, MD_LORA_QKV | MD_LORA_PROJ | MD_LORA_FC1);
+  w.ld2 = md_lora_shrink_cols(bank, MD_LORA_FC2);
+  w.t1 = (bf16_t*)a.take(M * w.ld1 * 2);
+  w.t2 = (bf16_t*)a.take(M * w.ld2 * 2);
+  w.d_proj = (bf16_t*)a.take(M * m->dim * 2);
+  w.d_fc2 = (bf16_t*)a.take(M * m->dim * 2);
+  w.total = a.off;
+  return w;
+}
 static md_status text_forward_impl(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
                                    const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* pfx_slots,
                                    const int32_t* pfx_len, const md_kv_cache* kv, void* workspace, size_t workspace_bytes,
-                                   void* stream);
+                                   void* stream, const LoraCall* lc = nullptr);
 
 extern "C" md_status md_text_forward_slots(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
                                            const int32_t* pos0, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
@@ -487,7 +517,7 @@ extern "C" md_status md_text_forward_shared(const md_text_model* m, const void* 
 static md_status text_forward_impl(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
                                    const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* pfx_slots,
                                    const int32_t* pfx_len, const md_kv_cache* kv, void* workspace, size_t workspace_bytes,
-                                   void* stream) {
+                                   void* stream, const LoraCall* lc) {
   MD_CHECK_ARG(m && x_in && hidden && pos0 && kv && kv->k && kv->v && workspace && m->blocks);
   MD_CHECK_ARG(batch > 0 && q_len > 0 && m->dim % m->n_heads == 0);
   MD_CHECK_ARG(slots == nullptr || n_slots > 0);
@@ -505,9 +535,11 @@ static md_status text_forward_impl(const md_text_model* m, const void* x_in, voi
       const int nb = std::min(block_rows, batch - b0);
       const void* xb = (const char*)x_in + (int64_t)b0 * m->dim * 2;
       void* hb = (char*)hidden + (int64_t)b0 * m->dim * 2;
+      LoraCall lb;  // the block's rows take their own entries of the variant table
+      if (lc) lb = LoraCall{lc->bank, lc->variant + b0};
       if (slots != nullptr) {  // slot table: the slab base stays, the block's rows take their own entries of the table(s)
         MD_TRY(text_forward_impl(m, xb, hb, nb, 1, pos0 + b0, slots + b0, n_slots, pfx_slots ? pfx_slots + b0 : nullptr,
-                                 pfx_slots ? pfx_len + b0 : nullptr, kv, workspace, workspace_bytes, stream));
+                                 pfx_slots ? pfx_len + b0 : nullptr, kv, workspace, workspace_bytes, stream, lc ? &lb : nullptr));
         continue;
       }
       md_kv_cache sub = *kv;
@@ -516,7 +548,8 @@ static md_status text_forward_impl(const md_text_model* m, const void* x_in, voi
       // the e4m3 copy of the cache (fp8 mode) has the same slot layout at one byte per element
       if (kv->k8) sub.k8 = (char*)kv->k8 + (int64_t)b0 * kv->batch_stride;
       if (kv->v8) sub.v8 = (char*)kv->v8 + (int64_t)b0 * kv->batch_stride;
-      MD_TRY(md_text_forward_slots(m, xb, hb, nb, 1, pos0 + b0, nullptr, 0, &sub, workspace, workspace_bytes, stream));
+      MD_TRY(text_forward_impl(m, xb, hb, nb, 1, pos0 + b0, nullptr, 0, nullptr, nullptr, &sub, workspace, workspace_bytes, stream,
+                               lc ? &lb : nullptr));
     }
     return MD_OK;
   }
@@ -524,6 +557,12 @@ static md_status text_forward_impl(const md_text_model* m, const void* x_in, voi
   if (hd != 64) return MD_ERR_UNSUPPORTED;
   const TextWs w = text_layout(m, batch, q_len, workspace);
   if (workspace_bytes < w.total) return MD_ERR_WORKSPACE;
+  // multi-LoRA: its buffers after the base path's (whose layout stays as it is)
+  LoraBufs lw = {};
+  if (lc) {
+    lw = lora_bufs(m, lc->bank, (size_t)batch * q_len, (char*)workspace + w.total);
+    if (workspace_bytes < w.total + lw.total) return MD_ERR_WORKSPACE;
+  }
   hipStream_t s = (hipStream_t)stream;
   const int D = m->dim, M = batch * q_len;
   const int qkv_w = (m->n_heads + 2 * m->n_kv_heads) * hd;
@@ -554,7 +593,8 @@ static md_status text_forward_impl(const md_text_model* m, const void* x_in, voi
   // shape: MHA, head_dim 64, rot_dim 32, slab offsets in 32 bits.  Per-row positions / slab offsets once per forward.
   const uint64_t slab_bytes = (uint64_t)kv->layer_stride * 2;
   bool rope_in_gemm = w.rope_cs != nullptr && q_len > 1 && M > 64 && m->n_kv_heads == m->n_heads && hd == 64 && m->rot_dim == 32 &&
-                      m->blocks[0].qkv_fc1.w != nullptr && slab_bytes < 0xfffff000ull && kv->layer_stride >= (int64_t)n_slots * kv->batch_stride;
+                      m->blocks[0].qkv_fc1.w != nullptr && slab_bytes < 0xfffff000ull && kv->layer_stride >= (int64_t)n_slots * kv->batch_stride &&
+                      lc == nullptr;
   if (rope_in_gemm)
     hipLaunchKernelGGL(rope_rowinfo_kernel, dim3((M + 7) / 8), dim3(256), 0, s, pos0, m->freqs, w.rope_cs, w.rope_kv, q_len, M,
                        kv->batch_stride, hd, m->rot_dim, slots);
@@ -629,6 +669,7 @@ static md_status text_forward_impl(const md_text_model* m, const void* x_in, voi
   const md_text_f8* f8p = m->f8;
   float* calib = (f8p && M > 64) ? f8p->calib : nullptr;  // calibration records the PREFILL's activation ranges
   const bool use_f8 = f8p && !f8p->calib && f8p->blocks && M > 64 && m->blocks[0].qkv_fc1.w != nullptr && qkv_w % 64 == 0;
+  if (lc && (use_f8 || calib)) return MD_ERR_UNSUPPORTED;
 
   for (int l = 0; l < m->n_layers; ++l) {
     const md_text_block& b = m->blocks[l];
@@ -693,6 +734,7 @@ static md_status text_forward_impl(const md_text_model* m, const void* x_in, voi
     const int64_t ffld = fused ? b.qkv_fc1.n_pad : b.fc1.n_pad;
     // decode regime with FP8 weight copies attached (opt-in): the same three launches over half the bytes
     const md_text_block_fp8* f8 = (m->fp8 && m->fp8->blocks && tail_fused && fused) ? &m->fp8->blocks[l] : nullptr;
+    if (lc && f8) return MD_ERR_UNSUPPORTED;
     if (f8 && f8->qkv_fc1.w) {
       MD_CHECK_ARG(f8->qkv_fc1.n_pad == b.qkv_fc1.n_pad && qkv_w % 64 == 0);
       MD_TRY(md_gemm_fp8w(w.h, Dp, &f8->qkv_fc1, w.qkv, qld, M, MD_EPI_GELU, 1, qkv_w, s));
@@ -702,6 +744,7 @@ static md_status text_forward_impl(const md_text_model* m, const void* x_in, voi
       md_gemm_args g;
       g.a = w.h; g.lda = Dp; g.lin = b.qkv_fc1; g.c = w.qkv; g.ldc = qld; g.r = nullptr; g.ldr = 0;
       g.res_row_mod = 0; g.m = M; g.epilogue = MD_EPI_GELU; g.store_pad_cols = 1; g.gelu_from_col = qkv_w;
+      if (lc) g.epilogue = MD_EPI_BIAS;  // GELU after the fc1 delta, in the expand
       g.splitk_ws = w.splitk; g.splitk_ws_bytes = w.splitk_bytes; g.tile_policy = t_tile_policy;
       rope_done = false;
       if (rope_in_gemm) {
@@ -719,12 +762,39 @@ static md_status text_forward_impl(const md_text_model* m, const void* x_in, voi
     } else {
       MD_TRY(gemm(w.h, Dp, b.qkv, w.qkv, qkv_w, M, MD_EPI_BIAS, nullptr, 0, 0, 0, s, w.splitk, w.splitk_bytes));
     }
+    if (lc) {
+      // multi-LoRA: fc1 without its GELU (unfused packing), one shrink from l_in for the qkv / proj / fc1 pairs, and one expand
+      // that adds the qkv and fc1 deltas and applies GELU to the fc1 columns (text.py:31-32; layers.py:130-137)
+      if (!fused) MD_TRY(gemm(w.h, Dp, b.fc1, w.ff, ffld, M, MD_EPI_BIAS, nullptr, 0, 0, 1, s, w.splitk, w.splitk_bytes));
+      MD_TRY(md_lora_shrink_grouped(lc->bank, l, MD_LORA_QKV | MD_LORA_PROJ | MD_LORA_FC1, lc->variant, batch, q_len, w.h, Dp, D,
+                                    lw.t1, lw.ld1, s));
+      ExpandSeg sg[2] = {};
+      sg[0].t = sg[1].t = lw.t1;
+      sg[0].ldt = sg[1].ldt = lw.ld1;
+      sg[0].t_pairs = sg[1].t_pairs = MD_LORA_QKV | MD_LORA_PROJ | MD_LORA_FC1;
+      sg[0].pair = 0; sg[0].out = (bf16_t*)w.qkv; sg[0].ldo = qld; sg[0].n = qkv_w; sg[0].gelu_from = INT_MAX;
+      sg[1].pair = 2; sg[1].out = (bf16_t*)w.ff; sg[1].ldo = ffld; sg[1].n = b.fc1.n; sg[1].gelu_from = 0;
+      MD_TRY(lora_expand_segments(lc->bank, l, lc->variant, batch, q_len, sg, 2, s));
+    }
     const bool fuse_rope = (q_len == 1) && (m->n_kv_heads == m->n_heads);  // decode step: rope + KV write inside attention
     MD_TRY(rope_and_attention(l, qld, fuse_rope));
     MD_TRY(calib_site(calib, 3 * l + 1, w.att, Dp, M, D, s));
     // x = (x + proj(att)) + fc2(gelu(fc1(l_in)))               (text.py:53,157-158)
-    if (!fused)
+    if (!fused && !lc)
       MD_TRY(gemm(w.h, Dp, b.fc1, w.ff, ffld, M, MD_EPI_GELU, nullptr, 0, 0, 1, s, w.splitk, w.splitk_bytes));
+    // multi-LoRA: the fc2 shrink from gelu(fc1), then ONE expand of the proj (from l_in's shrink: text.py:55) and fc2 deltas --
+    // as deltas that the fused tail adds, or added to the two linears' outputs off the tail
+    auto lora_pair_deltas = [&](bool delta) -> md_status {
+      MD_TRY(md_lora_shrink_grouped(lc->bank, l, MD_LORA_FC2, lc->variant, batch, q_len, w.ff, ffld, b.fc2.k, lw.t2, lw.ld2, s));
+      ExpandSeg sg[2] = {};
+      sg[0].t = lw.t1; sg[0].ldt = lw.ld1; sg[0].t_pairs = MD_LORA_QKV | MD_LORA_PROJ | MD_LORA_FC1; sg[0].pair = 1;
+      sg[0].out = lw.d_proj;
+      sg[1].t = lw.t2; sg[1].ldt = lw.ld2; sg[1].t_pairs = MD_LORA_FC2; sg[1].pair = 3; sg[1].out = lw.d_fc2;
+      for (ExpandSeg& g : sg) {
+        g.ldo = D; g.n = D; g.gelu_from = INT_MAX; g.delta = delta ? 1 : 0;
+      }
+      return lora_expand_segments(lc->bank, l, lc->variant, batch, q_len, sg, 2, s);
+    };
     MD_TRY(calib_site(calib, 3 * l + 2, w.ff, ffld, M, b.fc1.n, s));
     MD_CHECK_ARG(b.fc2.k_pad == b.fc1.n_pad);
     if (tail_fused) {
@@ -743,10 +813,24 @@ static md_status text_forward_impl(const md_text_model* m, const void* x_in, voi
                                         w.part_stride, s));
       }
       const bool last = (l + 1 == m->n_layers);
+      if (lc) {
+        MD_TRY(lora_pair_deltas(true));
+        MD_TRY(md_reduce_residual_layernorm_add(x, D, w.part_a, sl_a, b.proj.b, w.part_b, sl_b, b.fc2.b, w.part_ld, w.part_stride,
+                                                last ? nullptr : w.h, Dp, last ? nullptr : &m->blocks[l + 1].ln, M, D, 1e-5f,
+                                                lw.d_proj, lw.d_fc2, D, s));
+        continue;
+      }
       MD_TRY(md_reduce_residual_layernorm(x, D, w.part_a, sl_a, b.proj.b, w.part_b,
                                           sl_b, b.fc2.b, w.part_ld, w.part_stride,
                                           last ? nullptr : w.h, Dp, last ? nullptr : &m->blocks[l + 1].ln, M, D,
                                           1e-5f, s));
+    } else if (lc) {
+      // x = bf16(bf16(x + bf16(proj(att) + d_proj)) + bf16(fc2(h) + d_fc2))      (text.py:158)
+      MD_TRY(gemm(w.att, Dp, b.proj, lw.d_proj, D, M, MD_EPI_BIAS, nullptr, 0, 0, 0, s, w.splitk, w.splitk_bytes));
+      MD_TRY(gemm(w.ff, ffld, b.fc2, lw.d_fc2, D, M, MD_EPI_BIAS, nullptr, 0, 0, 0, s, w.splitk, w.splitk_bytes));
+      MD_TRY(lora_pair_deltas(false));
+      MD_TRY(md_add_bf16(x, D, lw.d_proj, D, x, D, M, D, s));
+      MD_TRY(md_add_bf16(x, D, lw.d_fc2, D, x, D, M, D, s));
     } else {
       MD_TRY(gemm(w.att, Dp, b.proj, x, D, M, MD_EPI_RESIDUAL, x, D, 0, 0, s, w.splitk, w.splitk_bytes));
       MD_TRY(gemm(w.ff, ffld, b.fc2, x, D, M, MD_EPI_RESIDUAL, x, D, 0, 0, s, w.splitk, w.splitk_bytes));
@@ -890,7 +974,7 @@ extern "C" md_status md_decode_step(const md_text_model* m, const int32_t* token
 static md_status decode_step_impl(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos, int32_t batch,
                                   const int32_t* slots, int32_t n_slots, const int32_t* pfx_slots, const int32_t* pfx_len,
                                   const md_kv_cache* kv, int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
-                                  size_t workspace_bytes, void* stream);
+                                  size_t workspace_bytes, void* stream, const LoraCall* lc = nullptr);
 
 extern "C" md_status md_decode_step_slots(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos,
                                           int32_t batch, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
@@ -914,10 +998,11 @@ extern "C" md_status md_decode_step_shared(const md_text_model* m, const int32_t
 static md_status decode_step_impl(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos, int32_t batch,
                                   const int32_t* slots, int32_t n_slots, const int32_t* pfx_slots, const int32_t* pfx_len,
                                   const md_kv_cache* kv, int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+                                  size_t workspace_bytes, void* stream, const LoraCall* lc) {
   MD_CHECK_ARG(m && tokens && next && pos && kv && logits && workspace && batch > 0);
   MD_CHECK_ARG(slots == nullptr || n_slots > 0);
-  if (workspace_bytes < md_decode_workspace_bytes(m, batch)) return MD_ERR_WORKSPACE;
+  if (workspace_bytes < (lc ? md_decode_multi_lora_workspace_bytes(m, lc->bank, batch) : md_decode_workspace_bytes(m, batch)))
+    return MD_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   Arena a{(char*)workspace, 0};
   void* x = a.take((size_t)batch * m->dim * 2);
@@ -925,7 +1010,7 @@ static md_status decode_step_impl(const md_text_model* m, const int32_t* tokens,
   void* tws = a.take(0);
   const size_t tws_bytes = workspace_bytes - a.off;
   MD_TRY(md_embed_tokens(tokens, m->wte, m->dim, x, m->dim, batch, m->dim, s));
-  MD_TRY(text_forward_impl(m, x, x, batch, 1, pos, slots, n_slots, pfx_slots, pfx_len, kv, tws, tws_bytes, s));
+  MD_TRY(text_forward_impl(m, x, x, batch, 1, pos, slots, n_slots, pfx_slots, pfx_len, kv, tws, tws_bytes, s, lc));
   if (decode_tall_rows(m, batch, 1) && !(kv->k8 && kv->v8)) {
     // the step's lm_head at 65 .. 128 rows: the by-shape config of the same MFMA family as the <= 64-row regime (never the
     // pinned four-wave kernel: a sequence must get the same logits in a step of 128 as in a step of 64)
@@ -936,6 +1021,58 @@ static md_status decode_step_impl(const md_text_model* m, const int32_t* tokens,
     MD_TRY(md_lm_head(m, x, batch, 1, logits, ld_logits, lmws, md_lm_head_workspace_bytes(m, batch), s));
   }
   return md_argmax_advance(logits, ld_logits, batch, m->vocab, suppress_id, next, pos, s);
+}
+
+// ------------------------------------------------------------- mixed LoRA variants (csrc/lora_multi.hip)
+// the checks that need no device; the fp8 modes (weight copies, e4m3 KV copy) are not served with a bank
+static md_status multi_lora_args_ok(const md_text_model* m, const md_lora_bank* bank, const int32_t* variant, int32_t batch,
+                                    const md_kv_cache* kv, const int32_t* slots, int32_t n_slots) {
+  MD_CHECK_ARG(m && m->blocks && kv && variant && batch > 0 && batch <= 1024);
+  MD_CHECK_ARG(slots == nullptr || n_slots > 0);
+  MD_TRY(lora_bank_ok(bank));
+  MD_CHECK_ARG(bank->n_layers == m->n_layers);
+  if (kv->k8 || kv->v8 || (m->fp8 && m->fp8->blocks) || m->f8) return MD_ERR_UNSUPPORTED;
+  return MD_OK;
+}
+
+extern "C" size_t md_text_multi_lora_workspace_bytes(const md_text_model* m, const md_lora_bank* bank, int32_t batch, int32_t q_len) {
+  const size_t base = md_text_workspace_bytes(m, batch, q_len);
+  if (base == 0 || bank == nullptr) return base;
+  if (lora_bank_ok(bank) != MD_OK) return 0;
+  return base + lora_bufs(m, bank, (size_t)batch * q_len, nullptr).total;
+}
+
+extern "C" size_t md_decode_multi_lora_workspace_bytes(const md_text_model* m, const md_lora_bank* bank, int32_t batch) {
+  const size_t base = md_decode_workspace_bytes(m, batch);
+  if (base == 0 || bank == nullptr) return base;
+  if (lora_bank_ok(bank) != MD_OK) return 0;
+  return base + lora_bufs(m, bank, (size_t)batch, nullptr).total;
+}
+
+extern "C" md_status md_text_forward_multi_lora(const md_text_model* m, const md_lora_bank* bank, const int32_t* variant,
+                                                const void* x_in, void* hidden, int32_t batch, int32_t q_len, const int32_t* pos0,
+                                                const int32_t* slots, int32_t n_slots, const md_kv_cache* kv, void* workspace,
+                                                size_t workspace_bytes, void* stream) {
+  if (bank == nullptr)
+    return md_text_forward_slots(m, x_in, hidden, batch, q_len, pos0, slots, n_slots, kv, workspace, workspace_bytes, stream);
+  MD_TRY(multi_lora_args_ok(m, bank, variant, batch, kv, slots, n_slots));
+  const LoraCall lc{bank, variant};
+  return text_forward_impl(m, x_in, hidden, batch, q_len, pos0, slots, n_slots, nullptr, nullptr, kv, workspace, workspace_bytes,
+                           stream, &lc);
+}
+
+extern "C" md_status md_decode_step_multi_lora(const md_text_model* m, const md_lora_bank* bank, const int32_t* variant,
+                                               const int32_t* tokens, int32_t* next, int32_t* pos, int32_t batch,
+                                               const int32_t* slots, int32_t n_slots, const md_kv_cache* kv, int32_t suppress_id,
+                                               void* logits, int64_t ld_logits, void* workspace, size_t workspace_bytes,
+                                               void* stream) {
+  if (bank == nullptr)
+    return md_decode_step_slots(m, tokens, next, pos, batch, slots, n_slots, kv, suppress_id, logits, ld_logits, workspace,
+                                workspace_bytes, stream);
+  MD_TRY(multi_lora_args_ok(m, bank, variant, batch, kv, slots, n_slots));
+  const LoraCall lc{bank, variant};
+  return decode_step_impl(m, tokens, next, pos, batch, slots, n_slots, nullptr, nullptr, kv, suppress_id, logits, ld_logits,
+                          workspace, workspace_bytes, stream, &lc);
 }
 
 extern "C" size_t md_decode_step_b1_workspace_bytes(const md_text_model* m) {

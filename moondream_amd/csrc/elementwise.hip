@@ -80,12 +80,16 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
 // -- the roundings of md_gemm_bf16's MD_EPI_RESIDUAL epilogue, in the same order; the
 // slices are summed in index order, so the result depends on the layer shape only.
 // ---------------------------------------------------------------------------
-template <int NCH>  // 16-byte chunks per thread; covers dim <= 2048 * NCH
+// ADD (the multi-LoRA tail): per-row bf16 addends da / db, each added to its linear's rounded output and rounded again
+// before the residual add, as the reference adds a LoRA delta (text.py:55-56, layers.py:140-142):
+//   t1 = bf16(bf16(sum_s A[s] + bias_a) + da)   t2 = bf16(bf16(sum_s B[s] + bias_b) + db)
+template <int NCH, bool ADD = false>  // NCH: 16-byte chunks per thread; covers dim <= 2048 * NCH
 __global__ __launch_bounds__(256) void reduce_residual_ln_kernel(
     bf16_t* __restrict__ x, int64_t ldx, const float* __restrict__ pa, int sa,
     const bf16_t* __restrict__ bias_a, const float* __restrict__ pb, int sb,
     const bf16_t* __restrict__ bias_b, int64_t ldp, int64_t slice_stride, bf16_t* __restrict__ y,
-    int64_t ldy, const bf16_t* __restrict__ lnw, const bf16_t* __restrict__ lnb, int dim, float eps) {
+    int64_t ldy, const bf16_t* __restrict__ lnw, const bf16_t* __restrict__ lnb, int dim, float eps,
+    const bf16_t* __restrict__ da, const bf16_t* __restrict__ db, int64_t ldd) {
   __shared__ float red[2][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row = blockIdx.x;
@@ -139,12 +143,19 @@ __global__ __launch_bounds__(256) void reduce_residual_ln_kernel(
       const u32x4 xq = *(const u32x4*)(xr + ch * 8);
       const u32x4 ba = *(const u32x4*)(bias_a + ch * 8);
       const u32x4 bb = *(const u32x4*)(bias_b + ch * 8);
+      u32x4 dqa = {0u, 0u, 0u, 0u}, dqb = {0u, 0u, 0u, 0u};
+      if constexpr (ADD) {
+        dqa = *(const u32x4*)(da + (int64_t)row * ldd + ch * 8);
+        dqb = *(const u32x4*)(db + (int64_t)row * ldd + ch * 8);
+      }
       u32x4 out;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const uint32_t t1 = pack_bf16x2(acc_a[2 * e] + lo_bf(ba[e]), acc_a[2 * e + 1] + hi_bf(ba[e]));
+        uint32_t t1 = pack_bf16x2(acc_a[2 * e] + lo_bf(ba[e]), acc_a[2 * e + 1] + hi_bf(ba[e]));
+        if constexpr (ADD) t1 = pack_bf16x2(lo_bf(t1) + lo_bf(dqa[e]), hi_bf(t1) + hi_bf(dqa[e]));
         const uint32_t x1 = pack_bf16x2(lo_bf(xq[e]) + lo_bf(t1), hi_bf(xq[e]) + hi_bf(t1));
-        const uint32_t t2 = pack_bf16x2(acc_b[2 * e] + lo_bf(bb[e]), acc_b[2 * e + 1] + hi_bf(bb[e]));
+        uint32_t t2 = pack_bf16x2(acc_b[2 * e] + lo_bf(bb[e]), acc_b[2 * e + 1] + hi_bf(bb[e]));
+        if constexpr (ADD) t2 = pack_bf16x2(lo_bf(t2) + lo_bf(dqb[e]), hi_bf(t2) + hi_bf(dqb[e]));
         out[e] = pack_bf16x2(lo_bf(x1) + lo_bf(t2), hi_bf(x1) + hi_bf(t2));
         v[i][2 * e] = lo_bf(out[e]);
         v[i][2 * e + 1] = hi_bf(out[e]);
@@ -489,7 +500,35 @@ extern "C" md_status md_reduce_residual_layernorm(void* x, int64_t ldx, const fl
 #define MD_RRL(NCH)                                                                                          \
   hipLaunchKernelGGL(reduce_residual_ln_kernel<NCH>, dim3(rows), dim3(256), 0, s, (bf16_t*)x, ldx, partial_a, \
                      slices_a, (const bf16_t*)bias_a, partial_b, slices_b, (const bf16_t*)bias_b, ld_partial, \
-                     slice_stride, (bf16_t*)y, ldy, lw, lb, dim, eps)
+                     slice_stride, (bf16_t*)y, ldy, lw, lb, dim, eps, nullptr, nullptr, 0)
+  if (dim <= 2048) MD_RRL(1);
+  else if (dim <= 4096) MD_RRL(2);
+  else MD_RRL(4);
+#undef MD_RRL
+  return md_launch_status();
+}
+
+// the multi-LoRA tail (api.hip): md_reduce_residual_layernorm plus the per-row addends da / db [rows][ldd] (reduce_residual_ln_kernel)
+md_status md_reduce_residual_layernorm_add(void* x, int64_t ldx, const float* partial_a, int32_t slices_a, const void* bias_a,
+                                           const float* partial_b, int32_t slices_b, const void* bias_b, int64_t ld_partial,
+                                           int64_t slice_stride, void* y, int64_t ldy, const md_layernorm* ln, int32_t rows,
+                                           int32_t dim, float eps, const void* da, const void* db, int64_t ldd, void* stream) {
+  MD_CHECK_ARG(x && partial_a && partial_b && bias_a && bias_b && da && db && rows > 0 && dim > 0 && dim % 8 == 0);
+  MD_CHECK_ARG(slices_a >= 1 && slices_b >= 1 && slices_a <= 8 && slices_b <= 8 && ldx % 8 == 0 && ldx >= dim && ld_partial % 4 == 0 && ld_partial >= dim);
+  MD_CHECK_ARG(slice_stride % 4 == 0 && dim <= 8192 && ldd % 8 == 0 && ldd >= dim);
+  MD_CHECK_ARG((((uintptr_t)x | (uintptr_t)partial_a | (uintptr_t)partial_b | (uintptr_t)bias_a | (uintptr_t)bias_b |
+                 (uintptr_t)da | (uintptr_t)db) & 15) == 0);
+  const bf16_t *lw = nullptr, *lb = nullptr;
+  if (y != nullptr) {
+    MD_CHECK_ARG(ln && ln->w && ln->b && ldy % 8 == 0 && ldy >= dim && ((uintptr_t)y & 15) == 0);
+    lw = (const bf16_t*)ln->w;
+    lb = (const bf16_t*)ln->b;
+  }
+  hipStream_t s = (hipStream_t)stream;
+#define MD_RRL(NCH)                                                                                                \
+  hipLaunchKernelGGL((reduce_residual_ln_kernel<NCH, true>), dim3(rows), dim3(256), 0, s, (bf16_t*)x, ldx, partial_a,   \
+                     slices_a, (const bf16_t*)bias_a, partial_b, slices_b, (const bf16_t*)bias_b, ld_partial,       \
+                     slice_stride, (bf16_t*)y, ldy, lw, lb, dim, eps, (const bf16_t*)da, (const bf16_t*)db, ldd)
   if (dim <= 2048) MD_RRL(1);
   else if (dim <= 4096) MD_RRL(2);
   else MD_RRL(4);

@@ -66,3 +66,19 @@ void md_gemm_w4_set_grid(int v);     // persistent workgroups per launch of the 
 void md_gemm_w4_set_debug(int half, uint32_t v);  // measurement builds: device buffer for in-kernel stamps
 void md_gemm_w4_set_variant(int v);  // measurement hook: schedule / ablation variant of the bias-epilogue kernel
 void md_attention_set_skip_dead(int v);  // attention.hip: exact work skipping of the prefill kernel (bit 0: dead half of the last key tile, bit 1: waves without a live query row)
+
+// one output segment of a grouped LoRA expand launch (lora_multi.hip; the multi-LoRA path of api.hip)
+struct ExpandSeg {
+  const bf16_t* t;  // shrink output rows (the pairs of t_pairs concatenated)
+  int64_t ldt;
+  int t_pairs;
+  int pair;
+  bf16_t* out;
+  int64_t ldo;
+  int n;          // columns, a multiple of 16
+  int gelu_from;  // ADD form: gelu(out) on columns >= gelu_from (INT_MAX: none)
+  int delta;      // 1: MD_LORA_DELTA, 0: MD_LORA_ADD
+  int tile0;      // first grid.x tile (64 columns) of this segment
+};
+md_status lora_expand_segments(const md_lora_bank* bank, int layer, const int32_t* variant, int batch, int q_len,
+                               const ExpandSeg* segs, int n_seg, hipStream_t s);

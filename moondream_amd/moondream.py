@@ -33,7 +33,7 @@ from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
 from .lora import variant_state_dict
 from .shared_prefix import check_shared_table, plan_shared_prefix
-from .weights import PackedLora, PackedModel
+from .weights import PackedLora, PackedLoraBank, PackedModel
 
 BF16 = torch.bfloat16
 
@@ -110,6 +110,13 @@ def _is_cjk_char(cp: int) -> bool:
     return (0x4E00 <= cp <= 0x9FFF) or (0x3400 <= cp <= 0x4DBF) or (0x2F800 <= cp <= 0x2FA1F)
 
 
+def _tree_to_cpu(tree):
+    """A nested dict of tensors (a LoRA variant) with every tensor copied to the host."""
+    if isinstance(tree, dict):
+        return {k: _tree_to_cpu(v) for k, v in tree.items()}
+    return tree.detach().to("cpu", copy=True) if isinstance(tree, torch.Tensor) else tree
+
+
 class MoondreamModel:
     def __init__(
         self,
@@ -146,6 +153,8 @@ class MoondreamModel:
         self.last_phase_ms: Dict[str, float] = {}
         self._region_tables = None
         self._variants: Dict[str, PackedLora] = {}
+        self._variant_src: Dict[str, dict] = {}  # registered variants as given (the bank packs its own copy on first use)
+        self._bank: Optional[PackedLoraBank] = None  # mixed-variant batches (md_lora_bank)
         # batch-1 greedy decode on the persistent single-sequence kernel (md_decode_step_b1): one launch per token for
         # all decoder blocks; False = the batched kernels at one row (bit-identical to a row of a batch)
         self.single_sequence_kernel = True
@@ -251,6 +260,34 @@ class MoondreamModel:
         """Make a LoRA variant available to ``settings={"variant": variant_id}`` without the network: ``lora`` is the
         nested dict the reference's ``variant_state_dict`` returns (lora.py:54-79)."""
         self._variants[variant_id] = PackedLora(self.config, lora, self._device)
+        # a host copy for the bank (which packs its own device copy on first use); a variant registered again under the same
+        # id replaces the bank's copy in place, so that ``variants=`` serves what ``variant=`` serves
+        self._variant_src[variant_id] = _tree_to_cpu(lora)
+        if self._bank is not None and variant_id in self._bank.index:
+            self._bank.add(variant_id, self._variant_src[variant_id], replace=True)
+
+    def _bank_index(self, variant_id: str) -> int:
+        """The index of ``variant_id`` in the model's LoRA bank, adding the variant on first use (a registered one, or the
+        on-disk cache's as ``settings={"variant": ...}`` finds it: FileNotFoundError when there is none)."""
+        if self._bank is None:
+            self._bank = PackedLoraBank(self.config, self.w.text, self._device)
+        if variant_id not in self._bank.index:
+            src = self._variant_src.get(variant_id)
+            if src is None:
+                src = variant_state_dict(variant_id, device="cpu")
+            self._bank.add(variant_id, src)
+        return self._bank.index[variant_id]
+
+    def _variant_table(self, rows: Sequence[int]) -> torch.Tensor:
+        """The per-sequence variant table of a mixed batch on the device, in one persistent buffer (captured decode graphs
+        keep its address)."""
+        b = len(rows)
+        buf = getattr(self, "_variant_buf", None)
+        if buf is None or buf.numel() < b:
+            buf = torch.empty(max(b, 64), dtype=torch.int32, device=self._device)
+            self._variant_buf = buf
+        buf[:b].copy_(self._h2d(torch.tensor(list(rows), dtype=torch.int32)))
+        return buf[:b]
 
     def _lora(self, settings: Optional[dict]) -> Optional[PackedLora]:
         """The packed variant named by ``settings["variant"]`` (reference: moondream.py:241-245,455-459), or None."""
@@ -447,13 +484,14 @@ class MoondreamModel:
 
     def _text_forward(self, x: torch.Tensor, pos0: Union[int, Sequence[int]], slot0: int = 0, causal: bool = False,
                       pos_dev: Optional[torch.Tensor] = None, lora: Optional[PackedLora] = None,
-                      shared: Optional[_SharedTable] = None) -> torch.Tensor:
+                      shared: Optional[_SharedTable] = None, multi: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x [B,T,D] embeddings -> hidden [B,T,D]; K,V written at pos0[b]..pos0[b]+T-1.
         ``pos0`` is host data (one int for the whole batch or one per sequence): the slab has
         max_context slots per head and the kernels do not bounds-check, so the check is here
         (the reference fails at this point too: its index_put / mask indexing raises).
         ``shared``: row b lives in slot shared.slots[b] and reads its image prefix from a shared slot
-        (md_text_forward_shared; ``slot0`` unused) -- the table was checked by ``_shared_plan``."""
+        (md_text_forward_shared; ``slot0`` unused) -- the table was checked by ``_shared_plan``.
+        ``multi``: row b carries the LoRA variant multi[b] of the model's bank, -1 the base model (md_text_forward_multi_lora)."""
         b, t, d = x.shape
         if self.strict_batch_invariance and lora is None and pos_dev is None and 1 < t <= 64 and b * t > 64:
             # The library picks the split-K decode-regime kernels by the ROW COUNT of a launch (<= 64 rows), and split-K sums
@@ -465,7 +503,8 @@ class MoondreamModel:
             for i0 in range(0, b, per):
                 p0 = pos0 if isinstance(pos0, int) else list(pos0)[i0 : i0 + per]
                 sh = shared.sub(i0, min(b, i0 + per)) if shared is not None else None
-                outs.append(self._text_forward(x[i0 : i0 + per], p0, slot0 + i0, causal=causal, shared=sh))
+                mt = multi[i0 : i0 + per] if multi is not None else None
+                outs.append(self._text_forward(x[i0 : i0 + per], p0, slot0 + i0, causal=causal, shared=sh, multi=mt))
             return torch.cat(outs, dim=0)
         hi = pos0 if isinstance(pos0, int) else max(int(p) for p in pos0)
         lo = pos0 if isinstance(pos0, int) else min(int(p) for p in pos0)
@@ -497,6 +536,19 @@ class MoondreamModel:
                     ws.data_ptr(), ws.numel(), self._stream(),
                 ),
                 "md_text_forward_shared",
+            )
+            return hidden
+        if multi is not None:  # per-row variants: the grouped LoRA kernels (csrc/lora_multi.hip)
+            assert lora is None and multi.dtype == torch.int32 and multi.numel() == b
+            bank = C.byref(self._bank.struct)
+            need = self.lib.md_text_multi_lora_workspace_bytes(C.byref(text), bank, b, t)
+            ws = self._workspace(need)
+            _lib.check(
+                self.lib.md_text_forward_multi_lora(
+                    C.byref(text), bank, multi.data_ptr(), x.data_ptr(), hidden.data_ptr(), b, t, pos0.data_ptr(), None, 0,
+                    C.byref(kv), ws.data_ptr(), ws.numel(), self._stream(),
+                ),
+                "md_text_forward_multi_lora",
             )
             return hidden
         if lora is not None:  # LoRA side path: unfused kernels + low-rank pairs (text.py:31-32,55-56; layers.py:129-146)
@@ -842,12 +894,13 @@ class MoondreamModel:
         self._select_kernels(1)
         return self._run_vision_encoder_batch([image])[0]
 
-    def _prefill_images(self, img_emb: torch.Tensor, slot0: int = 0, lora: Optional[PackedLora] = None) -> int:
+    def _prefill_images(self, img_emb: torch.Tensor, slot0: int = 0, lora: Optional[PackedLora] = None,
+                        multi: Optional[torch.Tensor] = None) -> int:
         """[B,729,D] -> image prefix in the KV slabs of slots [slot0, slot0+B); returns pos (730)."""
         b = img_emb.shape[0]
         bos = self._embed(torch.full((b, 1), self.config.tokenizer.bos_id, dtype=torch.int32))
         x = torch.cat([bos, img_emb], dim=1)
-        self._text_forward(x, 0, slot0, lora=lora)
+        self._text_forward(x, 0, slot0, lora=lora, multi=multi)
         return x.shape[1]
 
     def encode_image(self, image: Union[Image.Image, EncodedImage], settings: Optional[dict] = None) -> EncodedImage:
@@ -910,27 +963,27 @@ class MoondreamModel:
 
     # ---------------------------------------------------------- batched engine
     def _prefill_prompts(self, prompts: Sequence[Sequence[int]], pos: int, slot0: int = 0, prompt_embs=None,
-                         lora: Optional[PackedLora] = None):
+                         lora: Optional[PackedLora] = None, multi: Optional[torch.Tensor] = None):
         """Prefill B equal-length prompts at position ``pos``; returns (logits [B,V], hidden [B,T,D], pos+T).
         reference: moondream.py:280-321 (per sequence)."""
         b = len(prompts)
         ids = torch.tensor(prompts, dtype=torch.int32)
         x = self._embed(ids) if prompt_embs is None else prompt_embs
-        hidden = self._text_forward(x, pos, slot0, lora=lora)
+        hidden = self._text_forward(x, pos, slot0, lora=lora, multi=multi)
         return self._lm_head(hidden), hidden, pos + ids.shape[1]
 
     def _decode_greedy(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
                        slot0: int = 0, eos_id: Optional[int] = None, check_every: int = 16,
                        lora: Optional[PackedLora] = None, allow_b1: bool = True, temperature: float = 0.0, top_p: float = 0.0,
                        generator: Optional[torch.Generator] = None, shared: Optional[_SharedTable] = None,
-                       row_perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       row_perm: Optional[torch.Tensor] = None, multi: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``_decode_greedy_impl`` plus the safety net of the persistent single-sequence kernel: its software grid barriers
         need every workgroup resident; if one times out (the GPU was shared with another persistent kernel) the kernel
         raises an error word and finishes with garbage.  That state is fully re-initialised by decoding the same tokens
         again (K / V rows at positions >= ``pos``, the id history, the position buffer), so the call is repeated on the
         batched kernels and the persistent kernel is switched off for this model."""
         hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, slot0, eos_id, check_every, lora, allow_b1,
-                                        temperature, top_p, generator, shared, row_perm)
+                                        temperature, top_p, generator, shared, row_perm, multi)
         if self._b1_used:
             torch.cuda.current_stream(self._device).synchronize()
             if int(self._b1_sync[64 * 11]) != 0:
@@ -949,7 +1002,8 @@ class MoondreamModel:
                             slot0: int = 0, eos_id: Optional[int] = None, check_every: int = 16,
                             lora: Optional[PackedLora] = None, allow_b1: bool = True, temperature: float = 0.0,
                             top_p: float = 0.0, generator: Optional[torch.Generator] = None,
-                            shared: Optional[_SharedTable] = None, row_perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+                            shared: Optional[_SharedTable] = None, row_perm: Optional[torch.Tensor] = None,
+                            multi: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Device-resident decode loop: returns int32 [steps+1, B] (row 0 = ``first``).  ``temperature`` 0: greedy.  Otherwise every
         step draws each sequence's token with the reference's rule (moondream.py:521-528: softmax(logits / T), _apply_top_p,
         multinomial) from the step's own logits on the device (md_sample_top_p), with one uniform per (step, sequence) taken
@@ -959,10 +1013,12 @@ class MoondreamModel:
         prompts differ in length decode in the same lockstep batch).
         With ``compile()`` the steps are replayed from a captured hipGraph in chunks.
         ``shared``: the steps are md_decode_step_shared over that table (``slot0`` unused); ``row_perm``: row i draws the
-        uniforms of row row_perm[i], so that sampled rows in another order see the draws of the copy path."""
+        uniforms of row row_perm[i], so that sampled rows in another order see the draws of the copy path.
+        ``multi``: per-row LoRA variants of the model's bank (md_decode_step_multi_lora; device int32 [B], -1 = base)."""
         b = first.shape[0]
         t = self.config.text
         assert shared is None or lora is None
+        assert multi is None or (lora is None and shared is None and multi.numel() == b)
         self._ensure_batch(shared.n_slots if shared is not None else slot0 + b)
         pos_list = [int(pos)] * b if isinstance(pos, int) else [int(p) for p in pos]
         assert len(pos_list) == b
@@ -973,7 +1029,10 @@ class MoondreamModel:
         if max_tokens == 0:
             return hist
         logits = self._decode_logits(b)
-        need = self.lib.md_decode_workspace_bytes(C.byref(self.w.text), b)
+        if multi is not None:
+            need = self.lib.md_decode_multi_lora_workspace_bytes(C.byref(self.w.text), C.byref(self._bank.struct), b)
+        else:
+            need = self.lib.md_decode_workspace_bytes(C.byref(self.w.text), b)
         ws = self._workspace(need, 2)
         kv = self._kv_struct(0 if shared is not None else slot0)
         pos_base = self._h2d(torch.tensor(pos_list, dtype=torch.int32))
@@ -987,7 +1046,7 @@ class MoondreamModel:
         # the batched kernels.  Never from the pipelined engine (allow_b1 = False): a second stream's persistent GEMMs
         # could keep workgroups of the grid off the chip and its software barriers would time out.
         b1 = (b == 1 and allow_b1 and not sample and self.single_sequence_kernel and lora is None and shared is None
-              and not bool(self.w.text.fp8)
+              and multi is None and not bool(self.w.text.fp8)
               and bool(self.lib.md_decode_step_b1_supported(C.byref(self.w.text), C.byref(kv))))
         self._b1_used = b1
         if b1:
@@ -1007,7 +1066,16 @@ class MoondreamModel:
                     "md_decode_step_b1",
                 )
                 return
-            if shared is not None:
+            if multi is not None:
+                _lib.check(
+                    self.lib.md_decode_step_multi_lora(
+                        C.byref(self.w.text), C.byref(self._bank.struct), multi.data_ptr(), tok_in.data_ptr(), tok_out.data_ptr(),
+                        pos_buf.data_ptr(), b, None, 0, C.byref(kv), suppress_id, logits.data_ptr(), t.vocab_size, ws.data_ptr(),
+                        ws.numel(), self._stream(),
+                    ),
+                    "md_decode_step_multi_lora",
+                )
+            elif shared is not None:
                 _lib.check(
                     self.lib.md_decode_step_shared(
                         C.byref(self.w.text), tok_in.data_ptr(), tok_out.data_ptr(), pos_buf.data_ptr(), b, *shared.args(),
@@ -1070,7 +1138,8 @@ class MoondreamModel:
             # decode stream and the default stream each keep their own captures
             key = ("decode", b, slot0, n, suppress_id, ws.data_ptr(), self._kv_k.data_ptr(), logits.data_ptr(),
                    torch.cuda.current_stream(self._device).cuda_stream, b1, float(temperature), float(top_p),
-                   shared.args() if shared is not None else None)
+                   shared.args() if shared is not None else None,
+                   (multi.data_ptr(), self._bank.generation) if multi is not None else None)
             entry = self._graphs.get(key)
             if entry is None:
                 buf = torch.zeros(n + 1, b, dtype=torch.int32, device=self._device)
@@ -1134,7 +1203,8 @@ class MoondreamModel:
         return out
 
     def _prepare_sequences(self, images, prompts: Sequence[Sequence[int]], mark=None, lora: Optional[PackedLora] = None,
-                           fuse: bool = False, logits_capture: Optional[torch.Tensor] = None, sampler=None):
+                           fuse: bool = False, logits_capture: Optional[torch.Tensor] = None, sampler=None,
+                           multi: Optional[torch.Tensor] = None):
         """Everything before the first generated token, for B (image, prompt-ids) pairs: sequences are
         placed in KV slots in order of prompt length (stable), so that every group of equal-length
         prompts occupies a contiguous slot range; raw images are encoded together and prefilled
@@ -1142,10 +1212,11 @@ class MoondreamModel:
         distinct length.  Returns (order, first int32 [B], hidden_last [B, D], next_pos list) in slot
         order; ``order[slot]`` is the caller's index.  ``sampler`` = (temperature, top_p, suppress_id, generator) draws the first token
         as the reference's _prefill_prompt does (moondream.py:313-318; suppress_id -1 there); None = argmax.  Must run under
-        torch.inference_mode()."""
+        torch.inference_mode().  ``multi``: the per-row variant table (``_text_forward``), already in slot order."""
         mark = mark or (lambda name: None)
         b = len(images)
         self._select_kernels(b)
+        mv = (lambda i0, i1: multi[i0:i1]) if multi is not None else (lambda i0, i1: None)
         order = sorted(range(b), key=lambda i: len(prompts[i]))
         images = [images[i] for i in order]
         prompts = [list(prompts[i]) for i in order]
@@ -1177,7 +1248,7 @@ class MoondreamModel:
                     g1 += 1
                 pe = self._embed(torch.tensor(prompts[g0:g1], dtype=torch.int32))
                 x = torch.cat([bos[g0:g1], img_emb[g0:g1], pe], dim=1)
-                hidden = self._text_forward(x, 0, g0, lora=lora)
+                hidden = self._text_forward(x, 0, g0, lora=lora, multi=mv(g0, g1))
                 lg = self._lm_head(hidden)
                 if logits_capture is not None:
                     logits_capture[g0:g1] = lg
@@ -1197,7 +1268,7 @@ class MoondreamModel:
                 k = j
                 while k + 1 < len(raw_idx) and raw_idx[k + 1] == raw_idx[k] + 1:
                     k += 1
-                pos = self._prefill_images(img_emb[j : k + 1], raw_idx[j], lora)
+                pos = self._prefill_images(img_emb[j : k + 1], raw_idx[j], lora, multi=mv(raw_idx[j], raw_idx[k] + 1))
                 j = k + 1
             mark("image_prefill")
         for i, im in enumerate(images):
@@ -1214,7 +1285,7 @@ class MoondreamModel:
             g1 = g0
             while g1 < b and len(prompts[g1]) == len(prompts[g0]):
                 g1 += 1
-            logits, hidden, p1 = self._prefill_prompts(prompts[g0:g1], pos, g0, lora=lora)
+            logits, hidden, p1 = self._prefill_prompts(prompts[g0:g1], pos, g0, lora=lora, multi=mv(g0, g1))
             if logits_capture is not None:
                 logits_capture[g0:g1] = logits
             first[g0:g1] = self._pick(logits, 0.0, 0.0) if sampler is None else self._pick(logits, *sampler)
@@ -1312,6 +1383,7 @@ class MoondreamModel:
         top_p: float = DEFAULT_TOP_P,
         generator: Optional[torch.Generator] = None,
         share_prefix: bool = False,
+        variants: Optional[Sequence[Optional[str]]] = None,
     ) -> List[List[int]]:
         """Token ids for B (image, prompt-ids) pairs, decoded in lockstep; greedy by default.
 
@@ -1345,9 +1417,27 @@ class MoondreamModel:
         path bit for bit is ``set_strict_batch_invariance(True)`` (two passes
         everywhere, priced in bench.py's ``strict_batch_invariance`` leg).
         Tested on the 64 unfiltered bench images at 2B.
+
+        ``variants``: one LoRA variant per row (``None``: the base model), served in ONE batch -- every decode step streams
+        the base weights once, and the grouped kernels of csrc/lora_multi.hip apply each row's low-rank pairs.  Each row's
+        image prefix is prefilled under its own variant, as ``encode_image(image, settings={"variant": v})`` does.  Within
+        such a call a row's ids do not depend on the other rows' variants.  A base row of a mixed call is not bit-identical
+        to the same row in a base-only call: the mixed call rounds fc1's output to bf16 before GELU, as the reference does
+        (layers.py:130-137), where the base path applies GELU in the GEMM epilogue in fp32.  Not with ``variant=``;
+        ``share_prefix`` is ignored (copy path).
         """
         b = len(images)
         assert b == len(prompts) and b > 0
+        multi_rows = None
+        if variants is not None:
+            if variant is not None:
+                raise ValueError("batch_generate_ids: variant= and variants= cannot be combined")
+            if len(variants) != b:
+                raise ValueError(f"variants has {len(variants)} entries for {b} rows")
+            if any(v is not None for v in variants):
+                if self._kv8_scales is not None or bool(self.w.text.fp8) or bool(self.w.text.f8):
+                    raise ValueError("mixed LoRA variants are not served in the fp8 modes")
+                multi_rows = [-1 if v is None else self._bank_index(v) for v in variants]
         tk = self.config.tokenizer
         eos = tk.eos_id if eos_id is None else eos_id
         marks = []
@@ -1361,8 +1451,14 @@ class MoondreamModel:
         lora = self._lora({"variant": variant})
         with torch.inference_mode():
             sampler = None if temperature == 0 else (float(temperature), float(top_p), -1, generator)
-            shared = row_perm = None
-            if share_prefix and self._shares_prefix(lora):
+            shared = row_perm = multi = None
+            if multi_rows is not None:
+                # the slot order of _prepare_sequences (stable by prompt length), so that the table is in slot order too
+                slot_order = sorted(range(b), key=lambda i: len(prompts[i]))
+                multi = self._variant_table([multi_rows[i] for i in slot_order])
+                order, first, _, next_pos = self._prepare_sequences(list(images), prompts, mark, None, fuse=True, sampler=sampler,
+                                                                    multi=multi)
+            elif share_prefix and self._shares_prefix(lora):
                 order, first, _, next_pos, shared, row_perm = self._prepare_sequences_shared(list(images), prompts, mark, sampler)
             else:
                 if share_prefix:  # the copy path over each distinct image's EncodedImage
@@ -1372,7 +1468,7 @@ class MoondreamModel:
             stop = None if ignore_eos else eos
             hist = self._decode_greedy(first, next_pos if len(set(next_pos)) > 1 else next_pos[0], max_tokens,
                                        tk.answer_id, 0, stop, lora=lora, temperature=float(temperature), top_p=float(top_p),
-                                       generator=generator, shared=shared, row_perm=row_perm)
+                                       generator=generator, shared=shared, row_perm=row_perm, multi=multi)
             mark("decode")
             cols = hist.t().tolist()
             if b == 1:
@@ -1597,7 +1693,7 @@ class MoondreamModel:
         (moondream.py:50-53, read at :447-457): max_tokens 768, temperature 0.5, top_p 0.3.  ``settings["generator"]`` (an
         extension) seeds the draws; ``{"temperature": 0}`` is greedy."""
         st = settings or {}
-        return dict(max_tokens=st.get("max_tokens", DEFAULT_MAX_TOKENS), variant=st.get("variant"),
+        return dict(max_tokens=st.get("max_tokens", DEFAULT_MAX_TOKENS), variant=st.get("variant"), variants=st.get("variants"),
                     temperature=st.get("temperature", DEFAULT_TEMPERATURE), top_p=st.get("top_p", DEFAULT_TOP_P),
                     generator=st.get("generator"))
 

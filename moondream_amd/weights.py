@@ -357,6 +357,104 @@ class PackedLora:
         return C.cast(self.blocks, C.c_void_p)
 
 
+LORA_PAIRS = (("attn", "qkv"), ("attn", "proj"), ("mlp", "fc1"), ("mlp", "fc2"))  # md_lora_bank pair order
+
+
+def pack_lora_variant(config: MoondreamConfig, lora: dict, device="cpu"):
+    """One LoRA variant in the layout of an md_lora_bank: per pair (qkv, proj, fc1, fc2) its packed rank -- the largest true
+    rank over the layers, rounded up to 16, 0 when no layer has the pair -- and per layer the bf16 (A [rank][in],
+    B [out][rank]) zero-padded to that rank, or None.  A rank above 256 raises ValueError."""
+    t = config.text
+    hd = t.dim // t.n_heads
+    shape = {"qkv": ((t.n_heads + 2 * t.n_kv_heads) * hd, t.dim), "proj": (t.dim, t.dim), "fc1": (t.ff_dim, t.dim),
+             "fc2": (t.dim, t.ff_dim)}
+    tree = lora.get("text", {}).get("blocks", {})
+    layers = [[None] * 4 for _ in range(t.n_layers)]
+    ranks = [0, 0, 0, 0]
+    for i in range(t.n_layers):
+        layer = tree.get(str(i), {})
+        for q, (group, name) in enumerate(LORA_PAIRS):
+            pair = layer.get(group, {}).get(name)
+            if pair is None:
+                continue
+            a, b = pair["A"], pair["B"]
+            n_out, k_in = shape[name]
+            r = int(a.shape[0])
+            if tuple(a.shape) != (r, k_in) or tuple(b.shape) != (n_out, r):
+                raise ValueError(f"LoRA pair {name} of layer {i}: A {tuple(a.shape)}, B {tuple(b.shape)} for a [{n_out} x {k_in}] linear")
+            if r > 256:
+                raise ValueError(f"LoRA rank {r} of {name} (layer {i}) is above 256")
+            layers[i][q] = (a, b)
+            ranks[q] = max(ranks[q], (r + 15) // 16 * 16)
+    for i in range(t.n_layers):
+        for q in range(4):
+            if layers[i][q] is None:
+                continue
+            a, b = layers[i][q]
+            r, rp = int(a.shape[0]), ranks[q]
+            ap = torch.zeros(rp, a.shape[1], dtype=BF16, device=device)
+            bp = torch.zeros(b.shape[0], rp, dtype=BF16, device=device)
+            ap[:r] = a.to(device=device, dtype=BF16)
+            bp[:, :r] = b.to(device=device, dtype=BF16)
+            layers[i][q] = (ap.contiguous(), bp.contiguous())
+    return ranks, layers
+
+
+class PackedLoraBank:
+    """The resident adapter bank of mixed-variant batches (md_lora_bank): up to 16 variants, each packed at its true rank
+    rounded up to 16 (``pack_lora_variant``), with the device table of (A, B) pointers the grouped kernels read."""
+
+    def __init__(self, config: MoondreamConfig, text_struct, device):
+        self.config = config
+        self.device = torch.device(device)
+        self._text = text_struct
+        self.lib = _lib.load()
+        n_layers = config.text.n_layers
+        nbytes = self.lib.md_lora_bank_table_bytes(n_layers)
+        self.table = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self.struct = _lib.MdLoraBank()
+        _lib.check(self.lib.md_lora_bank_init(C.byref(self.struct), n_layers, self.table.data_ptr(), nbytes), "md_lora_bank_init")
+        self.index: Dict[str, int] = {}
+        self._keep: List[list] = []
+        self.generation = 0  # bumped on every change of the bank's ranks (launch shapes of captured graphs)
+
+    def __len__(self):
+        return len(self.index)
+
+    def add(self, variant_id: str, lora: dict, replace: bool = False) -> int:
+        """The bank index of ``variant_id``, packing ``lora`` into the bank the first time; ``replace``: repack an existing
+        variant from ``lora`` into its own index (its table entries and ranks are rewritten)."""
+        if variant_id in self.index and not replace:
+            return self.index[variant_id]
+        if variant_id not in self.index and len(self.index) >= _lib.MD_LORA_MAX_VARIANTS:
+            raise ValueError(f"the LoRA bank holds at most {_lib.MD_LORA_MAX_VARIANTS} variants")
+        ranks, layers = pack_lora_variant(self.config, lora, self.device)
+        t = self.config.text
+        blocks = (_lib.MdTextBlockLora * t.n_layers)()
+        names = ("qkv", "proj", "fc1", "fc2")
+        for i, row in enumerate(layers):
+            for q, ab in enumerate(row):
+                if ab is None:
+                    continue
+                a, b = ab
+                rp = ranks[q]
+                la = _lib.MdLinear(a.data_ptr(), None, rp, a.shape[1], rp, a.shape[1])
+                lb = _lib.MdLinear(b.data_ptr(), None, b.shape[0], rp, b.shape[0], rp)
+                setattr(blocks[i], names[q], _lib.MdLoraPair(la, lb))
+        idx = self.index.get(variant_id, len(self.index))
+        if idx < len(self._keep):
+            torch.cuda.synchronize(self.device)  # the old copy may still be read by queued launches
+        _lib.check(self.lib.md_lora_bank_set_variant(C.byref(self.struct), C.byref(self._text), idx, C.cast(blocks, C.c_void_p)),
+                   "md_lora_bank_set_variant")
+        if idx < len(self._keep):
+            self._keep[idx] = layers
+        else:
+            self._keep.append(layers)
+        self.index[variant_id] = idx
+        self.generation += 1
+        return idx
+
+
 class PackedModel:
     """All weights resident on one device + the md_vit_model / md_text_model
     structs (kept alive here; the library only borrows the pointers)."""
