@@ -711,8 +711,11 @@ bool decode_is64(int cfg) { return cfg == 10 || cfg == 16 || cfg == 17 || cfg ==
 int decode_bn() { return decode_is64(decode_cfg()) ? 64 : 128; }
 int decode_slab_floats() { return decode_is64(decode_cfg()) ? 64 * 64 : 128 * 2 * 2 * 16; }  // CT * MI * NI * 16 = the tile's outputs
 
-int decode_slices(int n_store, int k_pad) {
-  const int DEC_BN = decode_bn();
+// bn: width of the tile that runs -- decode_bn() for the <= 64-row configs, TALL_BN for the 128 x 64 tile
+constexpr int TALL_BN = 64;
+constexpr int TALL_SLAB_FLOATS = 128 * TALL_BN;
+int decode_slices(int n_store, int k_pad, int bn) {
+  const int DEC_BN = bn;
   const int tiles = (n_store + DEC_BN - 1) / DEC_BN, nk = k_pad / BK;
   if (knobs().decode_slices >= 1) return std::min(knobs().decode_slices, std::max(1, nk));  // experiments
   // measured model (profiles/r01_decode_gemm_sweep.txt): one workgroup saturates its
@@ -882,9 +885,13 @@ md_status gemm_dispatch(const md_gemm_args* a, void* stream, const md_rope_fuse*
     if (!tall) tile = decode_cfg();
     // in-launch split-K exactly where the 64-row regime splits (a function of the layer shape): the same slices, the same
     // slab summation order -- a row gets the same bits in a 128-row launch as in a 64-row one
-    const int sl = decode_slices(k.n_store, k.K);
-    const size_t tiles = (k.n_store + decode_bn() - 1) / decode_bn();
-    const size_t need = TICKET_BYTES + tiles * sl * (tall ? 128 * 64 : decode_slab_floats()) * sizeof(float);
+    // (the tall tile is 64 wide whatever the decode_cfg knob says: slices, tickets and slabs are counted in the tiles that RUN --
+    // under decode_cfg = 3 the 64-row configs are 128 wide, and counting the tall launch in those gave it half the slab and ticket
+    // space its 64-wide tiles index)
+    const int bn = tall ? TALL_BN : decode_bn();
+    const int sl = decode_slices(k.n_store, k.K, bn);
+    const size_t tiles = (k.n_store + bn - 1) / bn;
+    const size_t need = TICKET_BYTES + tiles * sl * (tall ? TALL_SLAB_FLOATS : decode_slab_floats()) * sizeof(float);
     if (sl > 1 && a->splitk_ws != nullptr && a->splitk_ws_bytes >= need && tiles * 4 <= TICKET_BYTES) {
       k.slices = sl;
       k.tickets = (unsigned*)a->splitk_ws;
@@ -1048,10 +1055,11 @@ extern "C" md_status md_gemm_partial_f32_pair(const void* a0, int64_t lda0, cons
 extern "C" size_t md_gemm_workspace_bytes(const md_linear* lin, int32_t m, int32_t store_pad_cols) {
   if (!lin || m > 128) return 0;   // (65 .. 128 rows: what a MD_TILE_DECODE_TALL launch needs; other policies ignore the workspace there)
   const int n_store = store_pad_cols ? lin->n_pad : lin->n;
-  const int sl = decode_slices(n_store, lin->k_pad);
+  const int bn = m > 64 ? TALL_BN : decode_bn();  // the tile that runs (gemm_dispatch)
+  const int sl = decode_slices(n_store, lin->k_pad, bn);
   if (sl == 1) return 0;
-  const size_t tiles = (n_store + decode_bn() - 1) / decode_bn();
-  return TICKET_BYTES + tiles * sl * (m > 64 ? 128 * 64 : decode_slab_floats()) * sizeof(float);
+  const size_t tiles = (n_store + bn - 1) / bn;
+  return TICKET_BYTES + tiles * sl * (m > 64 ? TALL_SLAB_FLOATS : decode_slab_floats()) * sizeof(float);
 }
 
 bool md_gemm_knob_rope_fuse() { return knobs().rope_fuse != 0; }

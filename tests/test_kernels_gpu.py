@@ -12,7 +12,7 @@ import torch
 
 from moondream_amd import _lib
 from moondream_amd.weights import PackedLinear, PackedLayerNorm, rope_table, reference_pixel_lut
-from util import compare, quantize_int4
+from util import compare, compare_elementwise, quantize_int4
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -45,13 +45,20 @@ def randn(*shape, scale=1.0, seed=0):
     return (torch.randn(*shape, generator=g) * scale).to(BF16).cuda()
 
 
+GUARD_BITS = 0x7FC1  # a bf16 NaN with a payload no kernel produces
 _SPLITK_WS = {}  # zeroed once; every launch leaves the ticket area zero again
 
 
 def gemm(lib, a, lin, epi=0, r=None, res_row_mod=0, store_pad=0, out=None, use_ws=True, tile_policy=0):
     m = a.shape[0]
     width = lin.n_pad if store_pad else lin.n
-    c = out if out is not None else torch.full((m, width), float("nan"), dtype=BF16, device="cuda")
+    # 64 guard rows below the result: a tile that stores a row >= m is seen (the kernel is handed the first m rows)
+    guard = None
+    if out is None:
+        guard = torch.full((m + 64, width), GUARD_BITS, dtype=torch.int16, device="cuda")
+        c = guard.view(BF16)[:m]
+    else:
+        c = out
     st = lin.struct()
     need = lib.md_gemm_workspace_bytes(C.byref(st), m, store_pad)
     ws = _SPLITK_WS.setdefault(need, torch.zeros(max(need, 16), dtype=torch.uint8, device="cuda")) if use_ws else None
@@ -61,6 +68,8 @@ def gemm(lib, a, lin, epi=0, r=None, res_row_mod=0, store_pad=0, out=None, use_w
                            need if ws is not None else 0, tile_policy)
     _lib.check(lib.md_gemm_bf16(C.byref(args), stream()), "gemm")
     torch.cuda.synchronize()
+    if guard is not None:
+        assert bool((guard[m:] == GUARD_BITS).all()), f"gemm m={m} n={lin.n} k={lin.k}: rows below the result were written"
     return c
 
 
@@ -94,6 +103,7 @@ def test_gemm_bias(lib, tile, m, k, n, force_tile):
     lin = PackedLinear(w, b, "cuda")
     c = gemm(lib, pad_k(a, lin.k_pad), lin)
     compare(f"gemm_bias {m}x{k}x{n} tile{tile}", c, ref_linear(a, w, b), 3e-3, 2e-2)
+    compare_elementwise(f"gemm_bias {m}x{k}x{n} tile{tile}", c, a, w, b, rounded=True)
 
 
 def test_gemm_tile_configs_agree_bitwise(lib, force_tile):
@@ -381,6 +391,8 @@ def test_gemm_decode_regime(lib, m, k, n, epi):
     if epi == 2:
         ref = (r.float() + ref.float()).to(BF16)
     compare(f"skinny m{m} {k}x{n} epi{epi}", c, ref, 3e-3, 2e-2)
+    if epi == 0:
+        compare_elementwise(f"skinny m{m} {k}x{n}", c, a, w, b, rounded=True)
     # same scratch, launched again (tickets were left zero), and row-subset invariance
     assert torch.equal(c, gemm(lib, pad_k(a, lin.k_pad), lin, epi=epi, r=r if epi == 2 else None))
     if m > 1:
@@ -389,6 +401,8 @@ def test_gemm_decode_regime(lib, m, k, n, epi):
     # without scratch K is not split across workgroups: still correct
     c1 = gemm(lib, pad_k(a, lin.k_pad), lin, epi=epi, r=r if epi == 2 else None, use_ws=False)
     compare(f"skinny(no scratch) m{m} {k}x{n}", c1, ref, 3e-3, 2e-2)
+    if epi == 0:
+        compare_elementwise(f"skinny(no scratch) m{m} {k}x{n}", c1, a, w, b, rounded=True)
 
 
 @pytest.mark.parametrize("m", [1, 7, 32, 33, 64])

@@ -32,6 +32,50 @@ def compare(name, got: torch.Tensor, ref: torch.Tensor, rel_rms: float, max_frac
     return rms, mx
 
 
+def elementwise_excess(got: torch.Tensor, a: torch.Tensor, w: torch.Tensor, bias, *, rounded: bool) -> torch.Tensor:
+    """``|got - exact| - bound`` per element (float64, on ``got``'s device) for ``got ~ a @ w^T + bias``; positive = violation.
+    See compare_elementwise for the bound.  ``a`` [m, K] and ``w`` [n, K] are the bf16 operands, ``bias`` [n] or None."""
+    dev = got.device
+    a64, w64 = a.detach().to(dev).double(), w.detach().to(dev).double()
+    b64 = torch.zeros(w.shape[0], dtype=torch.float64, device=dev) if bias is None else bias.detach().to(dev).double()
+    assert a64.dim() == 2 and w64.dim() == 2 and a64.shape[1] == w64.shape[1]
+    assert tuple(got.shape) == (a64.shape[0], w64.shape[0]), f"shape {tuple(got.shape)} vs {(a64.shape[0], w64.shape[0])}"
+    k = a64.shape[1]
+    exact = a64 @ w64.t() + b64
+    mag = a64.abs() @ w64.abs().t() + b64.abs()
+    g = got.detach().double()
+    bound = (k + 1) * 2.0 ** -23 * mag
+    if rounded:
+        big = torch.maximum(g.abs(), exact.abs())
+        _, e = torch.frexp(big)                       # big = f * 2^e, f in [0.5, 1): the bf16 spacing at big is 2^(e - 8)
+        ulp = torch.ldexp(torch.ones_like(big), e.clamp_min(-125) - 8)
+        bound = bound + 0.5 * torch.where(big > 0, ulp, torch.zeros_like(ulp))
+    excess = (g - exact).abs() - bound
+    return torch.where(torch.isfinite(g), excess, torch.full_like(excess, float("inf")))
+
+
+def compare_elementwise(name, got: torch.Tensor, a: torch.Tensor, w: torch.Tensor, bias, *, rounded: bool):
+    """Per-element bound for a GEMM with fp32 accumulation, derived and not measured.  With ``exact = a @ w^T + bias`` and
+    ``mag = |a| @ |w|^T + |bias|`` evaluated in float64 from the bf16 operands, EVERY element must satisfy
+
+        |got - exact| <= (0.5 * ulp_bf16(max(|got|, |exact|)) if rounded else 0) + (K + 1) * 2^-23 * mag
+
+    Each of the K fp32 accumulate steps and the bias add is charged a relative error of 2^-23 of the running magnitude (which
+    covers a truncating as well as a round-to-nearest accumulator) -- in any summation order and any split-K association; the
+    single rounding to bf16 adds half a bf16 spacing at the larger of the two values, so a result that rounds across a binade
+    is no false alarm.  ``rounded=False``: fp32 results (K-slice partial sums).  No element is excluded and there is no slack
+    factor.  Returns ``|got - exact| - bound`` per element."""
+    excess = elementwise_excess(got, a, w, bias, rounded=rounded)
+    bad = excess > 0
+    n_bad = int(bad.sum())
+    flat = int(torch.argmax(excess))
+    row, col = divmod(flat, excess.shape[1])
+    msg = f"{name}: {n_bad} of {excess.numel()} elements exceed the per-element bound; worst ({row}, {col}) by {float(excess[row, col]):.3e}"
+    print(msg if n_bad else f"{name}: all {excess.numel()} elements within the per-element bound (closest ({row}, {col}): {float(-excess[row, col]):.3e} to spare)")
+    assert n_bad == 0, msg
+    return excess
+
+
 def margin_aware_mismatches(got, ref, margins, thr=0.5):
     """Greedy ids of two correct bf16 implementations can only part ways at a decision whose
     reference top-1/top-2 logit margin is within bf16 noise.  For every sequence: the first
