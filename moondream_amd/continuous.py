@@ -18,7 +18,6 @@ retirement.  ``ContinuousEngine`` drives it with the library.
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import deque
 from dataclasses import dataclass, field
 from typing import Callable, Deque, Dict, Iterator, List, Optional, Sequence, Tuple, Union
@@ -337,11 +336,18 @@ class ContinuousEngine:
 
     def _decode_ws_bytes(self, bucket: int) -> int:
         """A decode chunk's workspace: the multi-LoRA step's once the model has a bank (it covers the plain step too)."""
-        m = self.model
-        bank = getattr(m, "_bank", None)
-        if bank is not None and len(bank):
-            return m.lib.md_decode_multi_lora_workspace_bytes(C.byref(m.w.text), C.byref(bank.struct), bucket)
-        return m.lib.md_decode_workspace_bytes(C.byref(m.w.text), bucket)
+        import torch
+
+        bank = getattr(self.model, "_bank", None)
+        none = torch.empty(0, dtype=torch.int32)  # (sizing reads which tables there are, not the tables)
+        return self.model._decode_ws_bytes(self._rows(none, none if bank is not None and len(bank) else None), bucket)
+
+    def _rows(self, slots, variants=None):
+        """The routing of a call over this engine's slab: a slot table, and with ``variants`` a row-variant table of the
+        model's bank."""
+        from .moondream import _Rows
+
+        return _Rows(slots=slots, n_slots=self.max_live, variants=variants, bank=self.model._bank if variants is not None else None)
 
     def run_text(self) -> Iterator[Tuple[int, str]]:
         for rid, ids in self.run():
@@ -381,32 +387,16 @@ class ContinuousEngine:
         return torch.rand(n, dtype=torch.float32, generator=self._generator(r))
 
     def _forward_slots(self, x, pos0: int, slots: List[int], variants: Optional[List[int]] = None):
-        """x [k, T, D] -> hidden [k, T, D] through md_text_forward_slots; K / V rows written into ``slots``.  ``variants`` with a
-        LoRA row: md_text_forward_multi_lora with those per-row bank indices."""
+        """x [k, T, D] -> hidden [k, T, D]; K / V rows written into ``slots``.  ``variants`` with a LoRA row: those per-row
+        bank indices travel with the call."""
         import torch
 
-        from . import _lib
-
         m = self.model
-        k, t, _ = x.shape
-        x = x.contiguous()
-        hidden = torch.empty_like(x)
-        pos_d = torch.full((k,), int(pos0), dtype=torch.int32, device=m.device)
         slots_d = m._h2d(torch.tensor(slots, dtype=torch.int32))
-        kv = m._kv_struct(0)
+        var_d = None
         if variants is not None and any(v >= 0 for v in variants):
-            bank = C.byref(m._bank.struct)
             var_d = m._h2d(torch.tensor(variants, dtype=torch.int32))
-            ws = m._workspace(m.lib.md_text_multi_lora_workspace_bytes(C.byref(m.w.text), bank, k, t))
-            _lib.check(m.lib.md_text_forward_multi_lora(C.byref(m.w.text), bank, var_d.data_ptr(), x.data_ptr(), hidden.data_ptr(), k, t,
-                                                        pos_d.data_ptr(), slots_d.data_ptr(), self.max_live, C.byref(kv), ws.data_ptr(),
-                                                        ws.numel(), m._stream()), "md_text_forward_multi_lora")
-            self.stats.prefill_passes += 1
-            return hidden
-        ws = m._workspace(m.lib.md_text_workspace_bytes(C.byref(m.w.text), k, t))
-        _lib.check(m.lib.md_text_forward_slots(C.byref(m.w.text), x.data_ptr(), hidden.data_ptr(), k, t, pos_d.data_ptr(),
-                                               slots_d.data_ptr(), self.max_live, C.byref(kv), ws.data_ptr(), ws.numel(),
-                                               m._stream()), "md_text_forward_slots")
+        hidden = m._text_forward(x, int(pos0), self._rows(slots_d, var_d))
         self.stats.prefill_passes += 1
         return hidden
 
@@ -416,21 +406,13 @@ class ContinuousEngine:
         decode-regime kernels, whatever the admission size."""
         import torch
 
-        from . import _lib
-
         m = self.model
         out = []
         for i0 in range(0, len(reqs), 64):
             part = reqs[i0 : i0 + 64]
             lg = m._lm_head(hidden[i0 : i0 + len(part)])
-            if self.temperature == 0:
-                out.append(m._pick(lg, 0.0, 0.0))
-                continue
-            u = m._h2d(torch.cat([self._uniforms(r, 1) for r in part]))
-            nxt = torch.empty(len(part), dtype=torch.int32, device=m.device)
-            _lib.check(m.lib.md_sample_top_p(lg.data_ptr(), lg.stride(0), len(part), m.config.text.vocab_size, -1, self.temperature,
-                                             self.top_p, u.data_ptr(), nxt.data_ptr(), None, 0, m._stream()), "md_sample_top_p")
-            out.append(nxt)
+            u = None if self.temperature == 0 else m._h2d(torch.cat([self._uniforms(r, 1) for r in part]))
+            out.append(m._pick(lg, self.temperature, self.top_p, uniforms=u))
         return torch.cat(out)
 
     def _admit(self, reqs: List[Request]) -> List[Tuple[int, int]]:
@@ -513,12 +495,9 @@ class ContinuousEngine:
     def _step(self, plan: ChunkPlan) -> np.ndarray:
         import torch
 
-        from . import _lib
-
         m = self.model
         if m._kv_k.data_ptr() != self._kv_ptr:
             raise RuntimeError("the KV slab was reallocated during a continuous-batching run")
-        t = m.config.text
         c, B, n = self.chunk, plan.bucket, plan.n
         dev, host, u_dev, u_host, n_in = self._buffers(B)
         slots_d = dev[: c * B].view(c, B)
@@ -548,45 +527,29 @@ class ContinuousEngine:
         logits = m._decode_logits(B)
         ws = m._workspace(self._decode_ws_bytes(B), 2)
         kv = m._kv_struct(0)
+        answer_id = m.config.tokenizer.answer_id
+        step_logits = logits[:B]
 
-        def one_step(i):
-            if lora:  # a LoRA row in the chunk: the multi-LoRA step with the chunk's row-variant table
-                _lib.check(m.lib.md_decode_step_multi_lora(C.byref(m.w.text), C.byref(m._bank.struct), var_d.data_ptr(), hist[i].data_ptr(),
-                                                           hist[i + 1].data_ptr(), pos_d.data_ptr(), B, slots_d[i].data_ptr(), self.max_live,
-                                                           C.byref(kv), m.config.tokenizer.answer_id, logits.data_ptr(), t.vocab_size,
-                                                           ws.data_ptr(), ws.numel(), m._stream()), "md_decode_step_multi_lora")
-            else:
-                _lib.check(m.lib.md_decode_step_slots(C.byref(m.w.text), hist[i].data_ptr(), hist[i + 1].data_ptr(), pos_d.data_ptr(), B,
-                                                      slots_d[i].data_ptr(), self.max_live, C.byref(kv), m.config.tokenizer.answer_id,
-                                                      logits.data_ptr(), t.vocab_size, ws.data_ptr(), ws.numel(), m._stream()),
-                           "md_decode_step_slots")
-            if sample:  # the step left its logits in ``logits``: draw from them instead of the argmax it wrote
-                _lib.check(m.lib.md_sample_top_p(logits.data_ptr(), logits.stride(0), B, t.vocab_size, m.config.tokenizer.answer_id,
-                                                 self.temperature, self.top_p, u2[i].data_ptr(), hist[i + 1].data_ptr(), None, 0,
-                                                 m._stream()), "md_sample_top_p")
+        def step_rows(i):  # step i's row of the slot table; a LoRA row in the chunk: the chunk's row-variant table with it
+            return self._rows(slots_d[i], var_d if lora else None)
+
+        def body():
+            for i in range(n):
+                m._decode_step(step_rows(i), hist[i], hist[i + 1], pos_d, B, answer_id, logits, ws, kv)
+                if sample:  # the step left its logits in ``logits``: draw from them instead of the argmax it wrote
+                    m._pick(step_logits, self.temperature, self.top_p, answer_id, uniforms=u2[i], out=hist[i + 1])
 
         if not m.use_graphs:
-            for i in range(n):
-                one_step(i)
+            body()
         else:
             stream = torch.cuda.current_stream(m.device).cuda_stream
+            # (the bank's generation in the routing's key part: its ranks are launch shapes of the capture)
             key = ("continuous", stream, B, n, dev.data_ptr(), ws.data_ptr(), m._kv_k.data_ptr(), logits.data_ptr(), self.temperature,
-                   self.top_p)
-            if lora:  # the bank's ranks are launch shapes of the capture
-                key = key + ("lora", m._bank.generation)
-            g = m._graphs.get(key)
-            if g is not None:
-                g.replay()
-            else:
-                for i in range(n):  # the first chunk of a shape runs eagerly (KV side effects: no warm-up on scratch state)
-                    one_step(i)
-                ours = [k for k in m._graphs if isinstance(k, tuple) and k and k[0] == "continuous" and k[1] == stream]
-                if len(ours) < MAX_GRAPHS:
-                    torch.cuda.synchronize(m.device)
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        for i in range(n):
-                            one_step(i)
-                    m._graphs[key] = g  # captured, not executed
-                    self.stats.graph_captures += 1
+                   self.top_p) + step_rows(0).key()
+
+            def below_cap():
+                return sum(1 for k in m._graphs if isinstance(k, tuple) and k and k[0] == "continuous" and k[1] == stream) < MAX_GRAPHS
+
+            if m._replay_or_capture(key, body, may_capture=below_cap):
+                self.stats.graph_captures += 1
         return hist[1 : n + 1].cpu().numpy()  # the chunk's one D2H copy (the lockstep loop syncs here too)

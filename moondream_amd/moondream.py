@@ -20,7 +20,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Any, Dict, Iterable, List, Literal, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -53,18 +53,129 @@ class EncodedImage:
     caches: List[Tuple[torch.Tensor, torch.Tensor]]
 
 
-class _SharedTable:
-    """Device int32 tables of md_text_forward_shared / md_decode_step_shared for B rows: own slots, prefix slots, prefix
-    lengths (views of one buffer), and the number of slots the KV slabs address."""
+@dataclass(frozen=True, eq=False)
+class _Rows:
+    """How the B rows of a decoder call are routed: which KV slots they live in and which adapters they carry.  Slots:
+    contiguous from ``slot0``, or ``slots`` (device int32 [B]; -1: an idle row) over ``n_slots`` slab slots.  With
+    ``prefix_slots`` / ``prefix_len`` (device int32 [B]) row b reads its first prefix_len[b] positions from slot
+    prefix_slots[b].  ``variants`` (device int32 [B], -1: the base model) gives each row a LoRA variant of ``bank``;
+    ``lora`` is one adapter for the whole call.  Which fields are set decides the library entry point, its workspace
+    function and what a captured graph bakes in -- here, in one place.  Combinations the library does not serve raise
+    ValueError.  An int where a ``_Rows`` is expected means contiguous from that slot (``of``)."""
 
-    def __init__(self, slots: torch.Tensor, prefix_slots: torch.Tensor, prefix_len: torch.Tensor, n_slots: int):
-        self.slots, self.prefix_slots, self.prefix_len, self.n_slots = slots, prefix_slots, prefix_len, int(n_slots)
+    slot0: int = 0
+    slots: Optional[torch.Tensor] = None
+    n_slots: int = 0
+    prefix_slots: Optional[torch.Tensor] = None
+    prefix_len: Optional[torch.Tensor] = None
+    variants: Optional[torch.Tensor] = None
+    bank: Optional[PackedLoraBank] = None
+    lora: Optional[PackedLora] = None
 
-    def sub(self, r0: int, r1: int) -> "_SharedTable":
-        return _SharedTable(self.slots[r0:r1], self.prefix_slots[r0:r1], self.prefix_len[r0:r1], self.n_slots)
+    #         kind: (forward, its workspace function, decode step, its workspace function)
+    _ENTRY = {
+        "": ("md_text_forward", "md_text_workspace_bytes", "md_decode_step", "md_decode_workspace_bytes"),
+        "_slots": ("md_text_forward_slots", "md_text_workspace_bytes", "md_decode_step_slots", "md_decode_workspace_bytes"),
+        "_shared": ("md_text_forward_shared", "md_text_workspace_bytes", "md_decode_step_shared", "md_decode_workspace_bytes"),
+        "_multi_lora": ("md_text_forward_multi_lora", "md_text_multi_lora_workspace_bytes", "md_decode_step_multi_lora",
+                        "md_decode_multi_lora_workspace_bytes"),
+        # the fused device-resident step has no single-adapter side path: the decode loop makes the step from its pieces
+        "_lora": ("md_text_forward_lora", "md_text_lora_workspace_bytes", None, None),
+    }
 
-    def args(self):
-        return self.slots.data_ptr(), self.n_slots, self.prefix_slots.data_ptr(), self.prefix_len.data_ptr()
+    def __post_init__(self):
+        prefix = self.prefix_slots is not None or self.prefix_len is not None
+        if prefix and (self.prefix_slots is None or self.prefix_len is None or self.slots is None):
+            raise ValueError("a prefix table needs prefix_slots, prefix_len and a slot table")
+        if prefix and (self.variants is not None or self.lora is not None):
+            raise ValueError("a prefix table is not served with LoRA variants or a PackedLora")
+        if (self.variants is None) != (self.bank is None):
+            raise ValueError("a variant table and its bank come together")
+        if self.lora is not None and (self.variants is not None or self.slots is not None):
+            raise ValueError("a PackedLora is not served with a variant table or a slot table")
+        if self.slots is not None and (self.slot0 != 0 or self.n_slots <= 0):
+            raise ValueError("a slot table addresses the whole slab: slot0 0, n_slots > 0")
+
+    @staticmethod
+    def of(rows: Union[int, "_Rows"]) -> "_Rows":
+        return rows if isinstance(rows, _Rows) else _Rows(slot0=int(rows))
+
+    @property
+    def kind(self) -> str:
+        if self.variants is not None:
+            return "_multi_lora"
+        if self.lora is not None:
+            return "_lora"
+        if self.prefix_slots is not None:
+            return "_shared"
+        return "_slots" if self.slots is not None else ""
+
+    @property
+    def plain(self) -> bool:
+        """Contiguous slots, no table, no adapter."""
+        return self.kind == ""
+
+    forward_entry = property(lambda self: self._ENTRY[self.kind][0])
+    forward_ws_entry = property(lambda self: self._ENTRY[self.kind][1])
+    step_entry = property(lambda self: self._ENTRY[self.kind][2])
+    step_ws_entry = property(lambda self: self._ENTRY[self.kind][3])
+
+    def sub(self, r0: int, r1: int) -> "_Rows":
+        """Rows [r0, r1) of the same routing."""
+        cut = lambda t: None if t is None else t[r0:r1]
+        return replace(self, slot0=self.slot0 if self.slots is not None else self.slot0 + r0, slots=cut(self.slots),
+                       prefix_slots=cut(self.prefix_slots), prefix_len=cut(self.prefix_len), variants=cut(self.variants))
+
+    def span(self, b: int) -> int:
+        """The slab slots a call over b rows addresses."""
+        return self.n_slots if self.slots is not None else self.slot0 + b
+
+    def head(self) -> tuple:
+        """The adapter arguments an entry point takes right after the model."""
+        if self.variants is not None:
+            return self.bank_arg() + (self.variants.data_ptr(),)
+        return (self.lora.ptr(),) if self.lora is not None else ()
+
+    def bank_arg(self) -> tuple:
+        """The bank argument the workspace functions of a variant table take after the model."""
+        return (C.byref(self.bank.struct),) if self.bank is not None else ()
+
+    def tail(self) -> tuple:
+        """The table arguments an entry point takes right before the KV struct."""
+        if self.slots is None:
+            return (None, 0) if self.variants is not None else ()
+        out = (self.slots.data_ptr(), self.n_slots)
+        return out + (self.prefix_slots.data_ptr(), self.prefix_len.data_ptr()) if self.prefix_slots is not None else out
+
+    def key(self) -> tuple:
+        """What a captured graph bakes in of the routing: part of every graph key."""
+        return (self.slot0 if self.slots is None else (self.slots.data_ptr(), self.n_slots),
+                (self.prefix_slots.data_ptr(), self.prefix_len.data_ptr()) if self.prefix_slots is not None else None,
+                (self.variants.data_ptr(), self.bank.generation) if self.variants is not None else None)
+
+
+def _runs(idx: Sequence[int]) -> List[Tuple[int, int]]:
+    """[j0, j1) ranges of ``idx`` (ascending ints) that hold consecutive values."""
+    out, j = [], 0
+    while j < len(idx):
+        k = j
+        while k + 1 < len(idx) and idx[k + 1] == idx[k] + 1:
+            k += 1
+        out.append((j, k + 1))
+        j = k + 1
+    return out
+
+
+def _length_groups(prompts: Sequence[Sequence[int]]) -> List[Tuple[int, int]]:
+    """[g0, g1) ranges of consecutive prompts of equal length."""
+    out, g0 = [], 0
+    while g0 < len(prompts):
+        g1 = g0
+        while g1 < len(prompts) and len(prompts[g1]) == len(prompts[g0]):
+            g1 += 1
+        out.append((g0, g1))
+        g0 = g1
+    return out
 
 
 class IdTokenizer:
@@ -367,7 +478,7 @@ class MoondreamModel:
         try:
             with torch.inference_mode():
                 n = len(calibration_images)
-                self._prepare_sequences(list(calibration_images), [prompt] * n, None, None, fuse=True)
+                self._prepare_sequences(list(calibration_images), [prompt] * n, fuse=True)
                 torch.cuda.synchronize(self._device)
                 t = self.config.text
                 p1 = t.prefix_attn + len(prompt)
@@ -482,18 +593,17 @@ class MoondreamModel:
         self._text_causal = st
         return st
 
-    def _text_forward(self, x: torch.Tensor, pos0: Union[int, Sequence[int]], slot0: int = 0, causal: bool = False,
-                      pos_dev: Optional[torch.Tensor] = None, lora: Optional[PackedLora] = None,
-                      shared: Optional[_SharedTable] = None, multi: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _text_forward(self, x: torch.Tensor, pos0: Union[int, Sequence[int]], rows: Union[int, _Rows] = 0, causal: bool = False,
+                      pos_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x [B,T,D] embeddings -> hidden [B,T,D]; K,V written at pos0[b]..pos0[b]+T-1.
         ``pos0`` is host data (one int for the whole batch or one per sequence): the slab has
         max_context slots per head and the kernels do not bounds-check, so the check is here
         (the reference fails at this point too: its index_put / mask indexing raises).
-        ``shared``: row b lives in slot shared.slots[b] and reads its image prefix from a shared slot
-        (md_text_forward_shared; ``slot0`` unused) -- the table was checked by ``_shared_plan``.
-        ``multi``: row b carries the LoRA variant multi[b] of the model's bank, -1 the base model (md_text_forward_multi_lora)."""
+        ``rows``: where the rows live and what adapters they carry (``_Rows``; an int: contiguous from that slot).  A prefix
+        table was checked by ``check_shared_table``."""
+        rows = _Rows.of(rows)
         b, t, d = x.shape
-        if self.strict_batch_invariance and lora is None and pos_dev is None and 1 < t <= 64 and b * t > 64:
+        if self.strict_batch_invariance and rows.lora is None and pos_dev is None and 1 < t <= 64 and b * t > 64:
             # The library picks the split-K decode-regime kernels by the ROW COUNT of a launch (<= 64 rows), and split-K sums
             # fp32 partials in another association than the sequential-K tile kernels.  A short prompt pass would so take
             # different kernels alone (t rows) and in a batch (b x t rows).  Strict mode keeps every launch of a short pass
@@ -502,9 +612,7 @@ class MoondreamModel:
             outs = []
             for i0 in range(0, b, per):
                 p0 = pos0 if isinstance(pos0, int) else list(pos0)[i0 : i0 + per]
-                sh = shared.sub(i0, min(b, i0 + per)) if shared is not None else None
-                mt = multi[i0 : i0 + per] if multi is not None else None
-                outs.append(self._text_forward(x[i0 : i0 + per], p0, slot0 + i0, causal=causal, shared=sh, multi=mt))
+                outs.append(self._text_forward(x[i0 : i0 + per], p0, rows.sub(i0, min(b, i0 + per)), causal=causal))
             return torch.cat(outs, dim=0)
         hi = pos0 if isinstance(pos0, int) else max(int(p) for p in pos0)
         lo = pos0 if isinstance(pos0, int) else min(int(p) for p in pos0)
@@ -521,57 +629,41 @@ class MoondreamModel:
         else:
             assert len(pos0) == b
             pos0 = self._h2d(torch.tensor([int(p) for p in pos0], dtype=torch.int32))
+        for tab in (rows.slots, rows.variants):
+            assert tab is None or (tab.dtype == torch.int32 and tab.numel() == b)
+        assert not (causal and rows.prefix_slots is not None)
         text = self._causal_text_struct() if causal else self.w.text
-        self._ensure_batch(shared.n_slots if shared is not None else slot0 + b)
+        self._ensure_batch(rows.span(b))
         x = x.contiguous()
         hidden = torch.empty_like(x)
-        kv = self._kv_struct(0 if shared is not None else slot0)
-        if shared is not None:
-            assert lora is None and not causal and shared.slots.numel() == b
-            need = self.lib.md_text_workspace_bytes(C.byref(text), b, t)
-            ws = self._workspace(need)
-            _lib.check(
-                self.lib.md_text_forward_shared(
-                    C.byref(text), x.data_ptr(), hidden.data_ptr(), b, t, pos0.data_ptr(), *shared.args(), C.byref(kv),
-                    ws.data_ptr(), ws.numel(), self._stream(),
-                ),
-                "md_text_forward_shared",
-            )
-            return hidden
-        if multi is not None:  # per-row variants: the grouped LoRA kernels (csrc/lora_multi.hip)
-            assert lora is None and multi.dtype == torch.int32 and multi.numel() == b
-            bank = C.byref(self._bank.struct)
-            need = self.lib.md_text_multi_lora_workspace_bytes(C.byref(text), bank, b, t)
-            ws = self._workspace(need)
-            _lib.check(
-                self.lib.md_text_forward_multi_lora(
-                    C.byref(text), bank, multi.data_ptr(), x.data_ptr(), hidden.data_ptr(), b, t, pos0.data_ptr(), None, 0,
-                    C.byref(kv), ws.data_ptr(), ws.numel(), self._stream(),
-                ),
-                "md_text_forward_multi_lora",
-            )
-            return hidden
-        if lora is not None:  # LoRA side path: unfused kernels + low-rank pairs (text.py:31-32,55-56; layers.py:129-146)
-            need = self.lib.md_text_lora_workspace_bytes(C.byref(text), b, t)
-            ws = self._workspace(need)
-            _lib.check(
-                self.lib.md_text_forward_lora(
-                    C.byref(text), lora.ptr(), x.data_ptr(), hidden.data_ptr(), b, t, pos0.data_ptr(), C.byref(kv),
-                    ws.data_ptr(), ws.numel(), self._stream(),
-                ),
-                "md_text_forward_lora",
-            )
-            return hidden
-        need = self.lib.md_text_workspace_bytes(C.byref(text), b, t)
-        ws = self._workspace(need)
+        kv = self._kv_struct(rows.slot0)
+        ws = self._workspace(getattr(self.lib, rows.forward_ws_entry)(C.byref(text), *rows.bank_arg(), b, t))
+        # one call site for md_text_forward and its _slots / _shared / _multi_lora (grouped LoRA kernels, csrc/lora_multi.hip) /
+        # _lora (unfused kernels + low-rank pairs: text.py:31-32,55-56; layers.py:129-146) forms
         _lib.check(
-            self.lib.md_text_forward(
-                C.byref(text), x.data_ptr(), hidden.data_ptr(), b, t, pos0.data_ptr(), C.byref(kv),
+            getattr(self.lib, rows.forward_entry)(
+                C.byref(text), *rows.head(), x.data_ptr(), hidden.data_ptr(), b, t, pos0.data_ptr(), *rows.tail(), C.byref(kv),
                 ws.data_ptr(), ws.numel(), self._stream(),
             ),
-            "md_text_forward",
+            rows.forward_entry,
         )
         return hidden
+
+    def _decode_ws_bytes(self, rows: _Rows, b: int) -> int:
+        """The workspace of a decode step over b rows routed by ``rows``."""
+        return getattr(self.lib, rows.step_ws_entry)(C.byref(self.w.text), *rows.bank_arg(), b)
+
+    def _decode_step(self, rows: _Rows, tok_in: torch.Tensor, tok_out: torch.Tensor, pos_buf: torch.Tensor, b: int, suppress_id: int,
+                     logits: torch.Tensor, ws: torch.Tensor, kv: _lib.MdKvCache):
+        """One device-resident decode step over b rows (embed -> decoder -> lm_head -> suppress + argmax; logits [b, V] left
+        in ``logits``): the one call site of md_decode_step and its _slots / _shared / _multi_lora forms."""
+        _lib.check(
+            getattr(self.lib, rows.step_entry)(
+                C.byref(self.w.text), *rows.head(), tok_in.data_ptr(), tok_out.data_ptr(), pos_buf.data_ptr(), b, *rows.tail(),
+                C.byref(kv), suppress_id, logits.data_ptr(), self.config.text.vocab_size, ws.data_ptr(), ws.numel(), self._stream(),
+            ),
+            rows.step_entry,
+        )
 
     def _lm_head(self, hidden: torch.Tensor) -> torch.Tensor:
         """hidden [B,T,D] -> logits of the last token [B,V].  reference: text.py:163-167."""
@@ -614,7 +706,7 @@ class MoondreamModel:
             raise ValueError(f"x must be [1, T, D] (got {tuple(x.shape)})")
         pos0, causal = self._seam_rule(attn_mask, pos_ids, int(x.shape[1]))
         self._select_kernels(1)
-        return self._text_forward(x.to(self._device), pos0, 0, causal=causal, lora=lora)
+        return self._text_forward(x.to(self._device), pos0, _Rows(lora=lora), causal=causal)
 
     def _decode_one_tok(self, x: torch.Tensor, attn_mask: Optional[torch.Tensor], pos_ids: torch.Tensor, lora=None):
         """reference: moondream.py:183-192.  x [1,1,D], attn_mask bool [1,1,ctx] with ones on [0, pos] ->
@@ -894,13 +986,12 @@ class MoondreamModel:
         self._select_kernels(1)
         return self._run_vision_encoder_batch([image])[0]
 
-    def _prefill_images(self, img_emb: torch.Tensor, slot0: int = 0, lora: Optional[PackedLora] = None,
-                        multi: Optional[torch.Tensor] = None) -> int:
-        """[B,729,D] -> image prefix in the KV slabs of slots [slot0, slot0+B); returns pos (730)."""
+    def _prefill_images(self, img_emb: torch.Tensor, rows: Union[int, _Rows] = 0) -> int:
+        """[B,729,D] -> image prefix in the KV slabs of the slots of ``rows``; returns pos (730)."""
         b = img_emb.shape[0]
         bos = self._embed(torch.full((b, 1), self.config.tokenizer.bos_id, dtype=torch.int32))
         x = torch.cat([bos, img_emb], dim=1)
-        self._text_forward(x, 0, slot0, lora=lora, multi=multi)
+        self._text_forward(x, 0, rows)
         return x.shape[1]
 
     def encode_image(self, image: Union[Image.Image, EncodedImage], settings: Optional[dict] = None) -> EncodedImage:
@@ -912,7 +1003,7 @@ class MoondreamModel:
         lora = self._lora(settings)  # the image prefix depends on the variant (moondream.py:241-257)
         with torch.inference_mode():
             self._ensure_batch(1)
-            pos = self._prefill_images(self._run_vision_encoder(image)[None], 0, lora)
+            pos = self._prefill_images(self._run_vision_encoder(image)[None], _Rows(lora=lora))
             caches = [
                 (self._kv_k[l, 0:1, :, :pos, :].clone(), self._kv_v[l, 0:1, :, :pos, :].clone())
                 for l in range(self.config.text.n_layers)
@@ -935,22 +1026,26 @@ class MoondreamModel:
     # --------------------------------------------------------------- sampling
     def _pick(self, logits: torch.Tensor, temperature: float, top_p: float, suppress_id: int = -1,
               generator: Optional[torch.Generator] = None, probs_out: Optional[torch.Tensor] = None,
-              row_perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+              row_perm: Optional[torch.Tensor] = None, uniforms: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """[B,V] -> int32 [B]   (reference: moondream.py:313-318,521-528).  Greedy: argmax, ties to the
         lowest id.  Otherwise temperature + top-p on the device (md_sample_top_p): the reference's
         softmax / _apply_top_p / multinomial semantics with one uniform per sequence from torch's
-        generator (same distribution as torch.multinomial, different random stream)."""
+        generator (same distribution as torch.multinomial, different random stream).  ``uniforms`` (device fp32 [B]): the
+        caller's draws instead; with ``out`` (device int32 [B]) as well nothing is allocated (captured decode steps)."""
         b, v = logits.shape
-        nxt = torch.empty(b, dtype=torch.int32, device=self._device)
+        nxt = out if out is not None else torch.empty(b, dtype=torch.int32, device=self._device)
         if temperature == 0:
             _lib.check(
                 self.lib.md_argmax_bf16(logits.data_ptr(), logits.stride(0), b, v, suppress_id, nxt.data_ptr(), self._stream()),
                 "md_argmax_bf16",
             )
             return nxt
-        u = torch.rand(b, device=self._device, dtype=torch.float32, generator=generator)
-        if row_perm is not None:  # row i draws the uniform of row row_perm[i] (the shared-prefix rows in the copy path's order)
-            u = u[row_perm]
+        u = uniforms
+        if u is None:
+            u = torch.rand(b, device=self._device, dtype=torch.float32, generator=generator)
+            if row_perm is not None:  # row i draws the uniform of row row_perm[i] (the shared-prefix rows in the copy path's order)
+                u = u[row_perm]
         _lib.check(
             self.lib.md_sample_top_p(
                 logits.data_ptr(), logits.stride(0), b, v, suppress_id, float(temperature), float(top_p), u.data_ptr(),
@@ -962,28 +1057,26 @@ class MoondreamModel:
         return nxt
 
     # ---------------------------------------------------------- batched engine
-    def _prefill_prompts(self, prompts: Sequence[Sequence[int]], pos: int, slot0: int = 0, prompt_embs=None,
-                         lora: Optional[PackedLora] = None, multi: Optional[torch.Tensor] = None):
+    def _prefill_prompts(self, prompts: Sequence[Sequence[int]], pos: int, rows: Union[int, _Rows] = 0, prompt_embs=None):
         """Prefill B equal-length prompts at position ``pos``; returns (logits [B,V], hidden [B,T,D], pos+T).
         reference: moondream.py:280-321 (per sequence)."""
         b = len(prompts)
         ids = torch.tensor(prompts, dtype=torch.int32)
         x = self._embed(ids) if prompt_embs is None else prompt_embs
-        hidden = self._text_forward(x, pos, slot0, lora=lora, multi=multi)
+        hidden = self._text_forward(x, pos, rows)
         return self._lm_head(hidden), hidden, pos + ids.shape[1]
 
     def _decode_greedy(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
-                       slot0: int = 0, eos_id: Optional[int] = None, check_every: int = 16,
-                       lora: Optional[PackedLora] = None, allow_b1: bool = True, temperature: float = 0.0, top_p: float = 0.0,
-                       generator: Optional[torch.Generator] = None, shared: Optional[_SharedTable] = None,
-                       row_perm: Optional[torch.Tensor] = None, multi: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       rows: Union[int, _Rows] = 0, eos_id: Optional[int] = None, check_every: int = 16, allow_b1: bool = True,
+                       temperature: float = 0.0, top_p: float = 0.0, generator: Optional[torch.Generator] = None,
+                       row_perm: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``_decode_greedy_impl`` plus the safety net of the persistent single-sequence kernel: its software grid barriers
         need every workgroup resident; if one times out (the GPU was shared with another persistent kernel) the kernel
         raises an error word and finishes with garbage.  That state is fully re-initialised by decoding the same tokens
         again (K / V rows at positions >= ``pos``, the id history, the position buffer), so the call is repeated on the
         batched kernels and the persistent kernel is switched off for this model."""
-        hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, slot0, eos_id, check_every, lora, allow_b1,
-                                        temperature, top_p, generator, shared, row_perm, multi)
+        hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, rows, eos_id, check_every, allow_b1,
+                                        temperature, top_p, generator, row_perm)
         if self._b1_used:
             torch.cuda.current_stream(self._device).synchronize()
             if int(self._b1_sync[64 * 11]) != 0:
@@ -995,15 +1088,13 @@ class MoondreamModel:
                 self._graphs.clear()
                 warnings.warn("md_decode_step_b1: a grid barrier timed out (GPU shared with another persistent kernel?); "
                               "repeating the decode on the batched kernels and disabling the single-sequence kernel", RuntimeWarning)
-                hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, slot0, eos_id, check_every, lora, False)
+                hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, rows, eos_id, check_every, False)
         return hist
 
     def _decode_greedy_impl(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
-                            slot0: int = 0, eos_id: Optional[int] = None, check_every: int = 16,
-                            lora: Optional[PackedLora] = None, allow_b1: bool = True, temperature: float = 0.0,
-                            top_p: float = 0.0, generator: Optional[torch.Generator] = None,
-                            shared: Optional[_SharedTable] = None, row_perm: Optional[torch.Tensor] = None,
-                            multi: Optional[torch.Tensor] = None) -> torch.Tensor:
+                            rows: Union[int, _Rows] = 0, eos_id: Optional[int] = None, check_every: int = 16,
+                            allow_b1: bool = True, temperature: float = 0.0, top_p: float = 0.0,
+                            generator: Optional[torch.Generator] = None, row_perm: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Device-resident decode loop: returns int32 [steps+1, B] (row 0 = ``first``).  ``temperature`` 0: greedy.  Otherwise every
         step draws each sequence's token with the reference's rule (moondream.py:521-528: softmax(logits / T), _apply_top_p,
         multinomial) from the step's own logits on the device (md_sample_top_p), with one uniform per (step, sequence) taken
@@ -1012,14 +1103,14 @@ class MoondreamModel:
         ``pos`` is the position of the next token, one int or one per sequence (sequences whose
         prompts differ in length decode in the same lockstep batch).
         With ``compile()`` the steps are replayed from a captured hipGraph in chunks.
-        ``shared``: the steps are md_decode_step_shared over that table (``slot0`` unused); ``row_perm``: row i draws the
-        uniforms of row row_perm[i], so that sampled rows in another order see the draws of the copy path.
-        ``multi``: per-row LoRA variants of the model's bank (md_decode_step_multi_lora; device int32 [B], -1 = base)."""
+        ``rows``: the routing of every step (``_Rows``); ``row_perm``: row i draws the uniforms of row row_perm[i], so that
+        sampled rows in another order see the draws of the copy path."""
+        rows = _Rows.of(rows)
         b = first.shape[0]
         t = self.config.text
-        assert shared is None or lora is None
-        assert multi is None or (lora is None and shared is None and multi.numel() == b)
-        self._ensure_batch(shared.n_slots if shared is not None else slot0 + b)
+        for tab in (rows.slots, rows.variants):
+            assert tab is None or tab.numel() == b
+        self._ensure_batch(rows.span(b))
         pos_list = [int(pos)] * b if isinstance(pos, int) else [int(p) for p in pos]
         assert len(pos_list) == b
         max_tokens = max(0, min(max_tokens, t.max_context - 1 - max(pos_list)))
@@ -1028,25 +1119,40 @@ class MoondreamModel:
         self._b1_used = False
         if max_tokens == 0:
             return hist
-        logits = self._decode_logits(b)
-        if multi is not None:
-            need = self.lib.md_decode_multi_lora_workspace_bytes(C.byref(self.w.text), C.byref(self._bank.struct), b)
-        else:
-            need = self.lib.md_decode_workspace_bytes(C.byref(self.w.text), b)
-        ws = self._workspace(need, 2)
-        kv = self._kv_struct(0 if shared is not None else slot0)
         pos_base = self._h2d(torch.tensor(pos_list, dtype=torch.int32))
         sample = temperature != 0
         uniforms = (torch.rand(max_tokens, b, device=self._device, dtype=torch.float32, generator=generator) if sample else None)
         if sample and row_perm is not None:
             uniforms = uniforms[:, row_perm].contiguous()
 
-        # one sequence, greedy, no side path: the whole step as ONE persistent launch (csrc/decode_b1.hip) when the library
-        # says this model / cache / device fits its static limits and its grid can be co-resident; anything else decodes on
-        # the batched kernels.  Never from the pipelined engine (allow_b1 = False): a second stream's persistent GEMMs
-        # could keep workgroups of the grid off the chip and its software barriers would time out.
-        b1 = (b == 1 and allow_b1 and not sample and self.single_sequence_kernel and lora is None and shared is None
-              and multi is None and not bool(self.w.text.fp8)
+        def all_done(upto):
+            return eos_id is not None and bool((hist[: upto + 1] == eos_id).any(dim=0).all())
+
+        steps = 0
+        if rows.lora is not None:
+            # LoRA variant: the fused device-resident step has no side path; same loop from its pieces
+            # (embed -> decoder with the low-rank pairs -> lm_head -> suppress + argmax), still without a host sync per token
+            pos_t, pos_h = pos_base.clone(), list(pos_list)
+            while steps < max_tokens:
+                emb = self._embed(hist[steps].reshape(b, 1))
+                h = self._text_forward(emb, pos_h, rows, pos_dev=pos_t)
+                hist[steps + 1] = self._pick(self._lm_head(h), temperature, top_p, suppress_id, generator)
+                pos_t.add_(1)
+                pos_h = [p + 1 for p in pos_h]
+                steps += 1
+                if check_every and steps % check_every == 0 and all_done(steps):
+                    break
+            return hist[: steps + 1]
+
+        logits = self._decode_logits(b)
+        need = self._decode_ws_bytes(rows, b)
+        ws = self._workspace(need, 2)
+        kv = self._kv_struct(rows.slot0)
+        # one sequence, greedy, plain contiguous routing: the whole step as ONE persistent launch (csrc/decode_b1.hip) when the
+        # library says this model / cache / device fits its static limits and its grid can be co-resident; anything else
+        # decodes on the batched kernels.  Never from the pipelined engine (allow_b1 = False): a second stream's persistent
+        # GEMMs could keep workgroups of the grid off the chip and its software barriers would time out.
+        b1 = (b == 1 and allow_b1 and not sample and self.single_sequence_kernel and rows.plain and not bool(self.w.text.fp8)
               and bool(self.lib.md_decode_step_b1_supported(C.byref(self.w.text), C.byref(kv))))
         self._b1_used = b1
         if b1:
@@ -1054,6 +1160,7 @@ class MoondreamModel:
                 self._b1_sync = torch.zeros(4096, dtype=torch.int32, device=self._device)
             need = max(need, self.lib.md_decode_step_b1_workspace_bytes(C.byref(self.w.text)))
             ws = self._workspace(need, 2)
+        step_logits = logits[:b]
 
         def one_step(tok_in, tok_out, pos_buf, u_row=None):
             if b1:
@@ -1066,61 +1173,10 @@ class MoondreamModel:
                     "md_decode_step_b1",
                 )
                 return
-            if multi is not None:
-                _lib.check(
-                    self.lib.md_decode_step_multi_lora(
-                        C.byref(self.w.text), C.byref(self._bank.struct), multi.data_ptr(), tok_in.data_ptr(), tok_out.data_ptr(),
-                        pos_buf.data_ptr(), b, None, 0, C.byref(kv), suppress_id, logits.data_ptr(), t.vocab_size, ws.data_ptr(),
-                        ws.numel(), self._stream(),
-                    ),
-                    "md_decode_step_multi_lora",
-                )
-            elif shared is not None:
-                _lib.check(
-                    self.lib.md_decode_step_shared(
-                        C.byref(self.w.text), tok_in.data_ptr(), tok_out.data_ptr(), pos_buf.data_ptr(), b, *shared.args(),
-                        C.byref(kv), suppress_id, logits.data_ptr(), t.vocab_size, ws.data_ptr(), ws.numel(), self._stream(),
-                    ),
-                    "md_decode_step_shared",
-                )
-            else:
-                _lib.check(
-                    self.lib.md_decode_step(
-                        C.byref(self.w.text), tok_in.data_ptr(), tok_out.data_ptr(), pos_buf.data_ptr(), b, C.byref(kv),
-                        suppress_id, logits.data_ptr(), t.vocab_size, ws.data_ptr(), ws.numel(), self._stream(),
-                    ),
-                    "md_decode_step",
-                )
+            self._decode_step(rows, tok_in, tok_out, pos_buf, b, suppress_id, logits, ws, kv)
             if sample:  # the step left its logits [B, V] in ``logits``: draw from them instead of the argmax it wrote
-                _lib.check(
-                    self.lib.md_sample_top_p(
-                        logits.data_ptr(), logits.stride(0), b, t.vocab_size, suppress_id, float(temperature), float(top_p),
-                        u_row.data_ptr(), tok_out.data_ptr(), None, 0, self._stream(),
-                    ),
-                    "md_sample_top_p",
-                )
+                self._pick(step_logits, temperature, top_p, suppress_id, uniforms=u_row, out=tok_out)
 
-        def all_done(upto):
-            return eos_id is not None and bool((hist[: upto + 1] == eos_id).any(dim=0).all())
-
-        steps = 0
-        if lora is not None:
-            # LoRA variant: the fused device-resident step has no side path; same loop from its pieces
-            # (embed -> decoder with the low-rank pairs -> lm_head -> suppress + argmax), still without a host sync per token
-            pos_t, pos_h = pos_base.clone(), list(pos_list)
-            while steps < max_tokens:
-                emb = self._embed(hist[steps].reshape(b, 1))
-                h = self._text_forward(emb, pos_h, slot0, pos_dev=pos_t, lora=lora)
-                if sample:
-                    hist[steps + 1] = self._pick(self._lm_head(h), temperature, top_p, suppress_id, generator)
-                else:
-                    hist[steps + 1] = self._pick(self._lm_head(h), 0.0, 0.0, suppress_id)
-                pos_t.add_(1)
-                pos_h = [p + 1 for p in pos_h]
-                steps += 1
-                if check_every and steps % check_every == 0 and all_done(steps):
-                    break
-            return hist[: steps + 1]
         if not self.use_graphs:
             pos_t = pos_base.clone()
             while steps < max_tokens:
@@ -1136,43 +1192,50 @@ class MoondreamModel:
             n = min(chunk, max_tokens - steps)
             # a graph is replayed only on the stream (context) it was captured for: the pipelined engine's
             # decode stream and the default stream each keep their own captures
-            key = ("decode", b, slot0, n, suppress_id, ws.data_ptr(), self._kv_k.data_ptr(), logits.data_ptr(),
-                   torch.cuda.current_stream(self._device).cuda_stream, b1, float(temperature), float(top_p),
-                   shared.args() if shared is not None else None,
-                   (multi.data_ptr(), self._bank.generation) if multi is not None else None)
+            key = ("decode", b, n, suppress_id, ws.data_ptr(), self._kv_k.data_ptr(), logits.data_ptr(),
+                   torch.cuda.current_stream(self._device).cuda_stream, b1, float(temperature), float(top_p)) + rows.key()
             entry = self._graphs.get(key)
-            if entry is None:
+            if entry is not None:
+                buf, pos_buf, u_buf = entry[1]
+            else:
                 buf = torch.zeros(n + 1, b, dtype=torch.int32, device=self._device)
                 pos_buf = torch.zeros(b, dtype=torch.int32, device=self._device)
                 u_buf = torch.zeros(n, b, dtype=torch.float32, device=self._device)
-                # eager warm-up on scratch state is not possible (KV side effects), so the
-                # first chunk of a new shape runs eagerly and the graph is captured afterwards
-                buf[0] = hist[steps]
-                pos_buf.copy_(pos_base + steps)
-                if sample:
-                    u_buf.copy_(uniforms[steps : steps + n])
+            buf[0] = hist[steps]
+            pos_buf.copy_(pos_base + steps)
+            if sample:
+                u_buf.copy_(uniforms[steps : steps + n])
+
+            def body():
                 for i in range(n):
                     one_step(buf[i], buf[i + 1], pos_buf, u_buf[i])
-                hist[steps + 1 : steps + n + 1] = buf[1:]
-                torch.cuda.synchronize(self._device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    for i in range(n):
-                        one_step(buf[i], buf[i + 1], pos_buf, u_buf[i])
-                # the capture did not execute; nothing to undo
-                self._graphs[key] = (g, buf, pos_buf, u_buf)
-            else:
-                g, buf, pos_buf, u_buf = entry
-                buf[0] = hist[steps]
-                pos_buf.copy_(pos_base + steps)
-                if sample:
-                    u_buf.copy_(uniforms[steps : steps + n])
-                g.replay()
-                hist[steps + 1 : steps + n + 1] = buf[1:]
+
+            self._replay_or_capture(key, body, (buf, pos_buf, u_buf))
+            hist[steps + 1 : steps + n + 1] = buf[1:]
             steps += n
             if all_done(steps):
                 break
         return hist[: steps + 1]
+
+    def _replay_or_capture(self, key, body, state=None, may_capture=None) -> bool:
+        """Replay the graph stored under ``key``; a key not seen before runs ``body`` eagerly, then captures it and stores
+        (graph, ``state``): the fixed buffers the body addresses stay alive with it.  An eager warm-up on scratch state is not
+        possible (KV side effects), so the first chunk of a new shape IS the eager run and the graph is captured after a
+        device synchronise; the capture does not execute, there is nothing to undo.  ``may_capture`` (asked on a miss
+        only): False runs eagerly without storing.  Returns True when it captured."""
+        entry = self._graphs.get(key)
+        if entry is not None:
+            entry[0].replay()
+            return False
+        body()
+        if may_capture is not None and not may_capture():
+            return False
+        torch.cuda.synchronize(self._device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            body()
+        self._graphs[key] = (g, state)
+        return True
 
     def _check_b1_barriers(self):
         """Call after the tokens of a single-sequence decode have reached the host: the persistent kernel's grid barriers
@@ -1202,9 +1265,32 @@ class MoondreamModel:
             out.append(tok)
         return out
 
-    def _prepare_sequences(self, images, prompts: Sequence[Sequence[int]], mark=None, lora: Optional[PackedLora] = None,
-                           fuse: bool = False, logits_capture: Optional[torch.Tensor] = None, sampler=None,
-                           multi: Optional[torch.Tensor] = None):
+    def _prefill_groups(self, groups: Sequence[Tuple[int, int]], embed, pos: int, rows: _Rows, sampler=None,
+                        logits_capture: Optional[torch.Tensor] = None, row_perm=None):
+        """One decoder pass per group [r0, r1) of equal-length prompts: ``embed(r0, r1)`` [r1-r0, T, D] goes through the decoder
+        at position ``pos`` into the slots of ``rows.sub(r0, r1)``, then lm_head and the pick of the first token (``sampler`` =
+        (temperature, top_p, suppress_id, generator); None: argmax; ``row_perm(r0, r1)``: the draw order of a sampled group).
+        Returns (first int32 [B], hidden_last [B, D], next_pos list); the groups' logits go to ``logits_capture`` [B, V]."""
+        b = groups[-1][1]
+        first = torch.empty(b, dtype=torch.int32, device=self._device)
+        hidden_last = torch.empty(b, self.config.text.dim, dtype=BF16, device=self._device)
+        next_pos = [0] * b
+        for r0, r1 in groups:
+            x = embed(r0, r1)
+            hidden = self._text_forward(x, pos, rows.sub(r0, r1))
+            logits = self._lm_head(hidden)
+            if logits_capture is not None:
+                logits_capture[r0:r1] = logits
+            if sampler is None:
+                first[r0:r1] = self._pick(logits, 0.0, 0.0)
+            else:
+                first[r0:r1] = self._pick(logits, *sampler, row_perm=row_perm(r0, r1) if row_perm is not None else None)
+            hidden_last[r0:r1] = hidden[:, -1, :]
+            next_pos[r0:r1] = [pos + x.shape[1]] * (r1 - r0)
+        return first, hidden_last, next_pos
+
+    def _prepare_sequences(self, images, prompts: Sequence[Sequence[int]], mark=None, rows: Union[int, _Rows] = 0,
+                           fuse: bool = False, logits_capture: Optional[torch.Tensor] = None, sampler=None):
         """Everything before the first generated token, for B (image, prompt-ids) pairs: sequences are
         placed in KV slots in order of prompt length (stable), so that every group of equal-length
         prompts occupies a contiguous slot range; raw images are encoded together and prefilled
@@ -1212,11 +1298,11 @@ class MoondreamModel:
         distinct length.  Returns (order, first int32 [B], hidden_last [B, D], next_pos list) in slot
         order; ``order[slot]`` is the caller's index.  ``sampler`` = (temperature, top_p, suppress_id, generator) draws the first token
         as the reference's _prefill_prompt does (moondream.py:313-318; suppress_id -1 there); None = argmax.  Must run under
-        torch.inference_mode().  ``multi``: the per-row variant table (``_text_forward``), already in slot order."""
+        torch.inference_mode().  ``rows``: the routing of slots 0 .. B-1 (a per-row variant table is already in slot order)."""
         mark = mark or (lambda name: None)
+        rows = _Rows.of(rows)
         b = len(images)
         self._select_kernels(b)
-        mv = (lambda i0, i1: multi[i0:i1]) if multi is not None else (lambda i0, i1: None)
         order = sorted(range(b), key=lambda i: len(prompts[i]))
         images = [images[i] for i in order]
         prompts = [list(prompts[i]) for i in order]
@@ -1229,6 +1315,7 @@ class MoondreamModel:
                 raise ValueError("image must be a PIL Image or EncodedImage")
         mark("start")
         pos = None
+        embed_prompts = lambda g0, g1: self._embed(torch.tensor(prompts[g0:g1], dtype=torch.int32))
         if len(raw_idx) == b and fuse and self.fused_prefill:
             # Every image is raw: image prefix and prompt go through the decoder in ONE pass per group of equal-length
             # prompts ([bos | 729 image embeddings | prompt] at position 0).  The attention kernels evaluate the
@@ -1238,38 +1325,16 @@ class MoondreamModel:
             img_emb = self._run_vision_encoder_batch(images, mark)
             mark("vision")
             bos = self._embed(torch.full((b, 1), self.config.tokenizer.bos_id, dtype=torch.int32))
-            first = torch.empty(b, dtype=torch.int32, device=self._device)
-            hidden_last = torch.empty(b, self.config.text.dim, dtype=BF16, device=self._device)
-            next_pos = [0] * b
-            g0 = 0
-            while g0 < b:
-                g1 = g0
-                while g1 < b and len(prompts[g1]) == len(prompts[g0]):
-                    g1 += 1
-                pe = self._embed(torch.tensor(prompts[g0:g1], dtype=torch.int32))
-                x = torch.cat([bos[g0:g1], img_emb[g0:g1], pe], dim=1)
-                hidden = self._text_forward(x, 0, g0, lora=lora, multi=mv(g0, g1))
-                lg = self._lm_head(hidden)
-                if logits_capture is not None:
-                    logits_capture[g0:g1] = lg
-                first[g0:g1] = self._pick(lg, 0.0, 0.0) if sampler is None else self._pick(lg, *sampler)
-                hidden_last[g0:g1] = hidden[:, -1, :]
-                next_pos[g0:g1] = [x.shape[1]] * (g1 - g0)
-                g0 = g1
+            fused = lambda g0, g1: torch.cat([bos[g0:g1], img_emb[g0:g1], embed_prompts(g0, g1)], dim=1)
+            out = self._prefill_groups(_length_groups(prompts), fused, 0, rows, sampler, logits_capture)
             mark("image_prefill")
             mark("prompt_prefill")
-            return order, first, hidden_last, next_pos
+            return (order, *out)
         if raw_idx:
             img_emb = self._run_vision_encoder_batch([images[i] for i in raw_idx], mark)
             mark("vision")
-            # every run of consecutive raw images is prefilled straight into its own slots
-            j = 0
-            while j < len(raw_idx):
-                k = j
-                while k + 1 < len(raw_idx) and raw_idx[k + 1] == raw_idx[k] + 1:
-                    k += 1
-                pos = self._prefill_images(img_emb[j : k + 1], raw_idx[j], lora, multi=mv(raw_idx[j], raw_idx[k] + 1))
-                j = k + 1
+            for j0, j1 in _runs(raw_idx):  # every run of consecutive raw images is prefilled straight into its own slots
+                pos = self._prefill_images(img_emb[j0:j1], rows.sub(raw_idx[j0], raw_idx[j1 - 1] + 1))
             mark("image_prefill")
         for i, im in enumerate(images):
             if isinstance(im, EncodedImage):
@@ -1277,23 +1342,22 @@ class MoondreamModel:
                     raise ValueError("EncodedImage with a different prefix length than the rest of the batch")
                 self.load_encoded_image(im, i)
                 pos = im.pos
-        first = torch.empty(b, dtype=torch.int32, device=self._device)
-        hidden_last = torch.empty(b, self.config.text.dim, dtype=BF16, device=self._device)
-        next_pos = [0] * b
-        g0 = 0
-        while g0 < b:  # one prefill per distinct prompt length
-            g1 = g0
-            while g1 < b and len(prompts[g1]) == len(prompts[g0]):
-                g1 += 1
-            logits, hidden, p1 = self._prefill_prompts(prompts[g0:g1], pos, g0, lora=lora, multi=mv(g0, g1))
-            if logits_capture is not None:
-                logits_capture[g0:g1] = logits
-            first[g0:g1] = self._pick(logits, 0.0, 0.0) if sampler is None else self._pick(logits, *sampler)
-            hidden_last[g0:g1] = hidden[:, -1, :]
-            next_pos[g0:g1] = [p1] * (g1 - g0)
-            g0 = g1
+        out = self._prefill_groups(_length_groups(prompts), embed_prompts, pos, rows, sampler, logits_capture)  # one per prompt length
         mark("prompt_prefill")
-        return order, first, hidden_last, next_pos
+        return (order, *out)
+
+    def _mark(self, marks: list, name: str):
+        """Phase timing (``collect_timing``): an event on the current stream, named after the phase that ends there."""
+        if self.collect_timing:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(torch.cuda.current_stream(self._device))
+            marks.append((name, e))
+
+    def _phase_times(self, marks: list):
+        """The time between consecutive marks of a call -> ``last_phase_ms``."""
+        if self.collect_timing and len(marks) > 1:
+            torch.cuda.synchronize(self._device)
+            self.last_phase_ms = {marks[i][0]: marks[i - 1][1].elapsed_time(marks[i][1]) for i in range(1, len(marks))}
 
     def _shares_prefix(self, lora: Optional[PackedLora]) -> bool:
         """The shared-prefix path serves the base model over the bf16 cache; a LoRA variant or the fp8 mode's e4m3 KV copy
@@ -1312,8 +1376,9 @@ class MoondreamModel:
         """``_prepare_sequences`` with a SHARED image prefix (moondream_amd/shared_prefix.py): each distinct image (by identity)
         is prefilled or loaded ONCE, into prefix slot k < P; the rows take slots P + r and read the prefix from there.  Raw
         images go through one ViT batch and ``_prefill_images``; EncodedImages are loaded once.  One prompt prefill per
-        distinct length (md_text_forward_shared).  Returns (order, first, hidden_last, next_pos, table, row_perm): the first
-        four as ``_prepare_sequences`` returns them, in this path's row order; ``row_perm`` maps a row to its row in the copy
+        distinct length (md_text_forward_shared).  Returns (order, first, hidden_last, next_pos, rows, row_perm): the first
+        four as ``_prepare_sequences`` returns them, in this path's row order; ``rows`` is the routing over the prefix table
+        (``_Rows``); ``row_perm`` maps a row to its row in the copy
         path's order (sampling draws).  Must run under torch.inference_mode()."""
         mark = mark or (lambda name: None)
         plan = plan_shared_prefix(list(images), [len(p) for p in prompts])
@@ -1332,13 +1397,8 @@ class MoondreamModel:
         if raw:
             img_emb = self._run_vision_encoder_batch([plan.distinct[k] for k in raw], mark)
             mark("vision")
-            j = 0
-            while j < len(raw):  # every run of consecutive prefix slots in one prefill
-                k = j
-                while k + 1 < len(raw) and raw[k + 1] == raw[k] + 1:
-                    k += 1
-                pos = self._prefill_images(img_emb[j : k + 1], raw[j])
-                j = k + 1
+            for j0, j1 in _runs(raw):  # every run of consecutive prefix slots in one prefill
+                pos = self._prefill_images(img_emb[j0:j1], raw[j0])
             mark("image_prefill")
         for k, im in enumerate(plan.distinct):
             if isinstance(im, EncodedImage):
@@ -1352,24 +1412,14 @@ class MoondreamModel:
             buf = torch.empty(3 * max(b, 64), dtype=torch.int32, device=self._device)
             self._shared_buf = buf
         buf[: 3 * b].copy_(self._h2d(torch.tensor(plan.own_slots + plan.prefix_slots + [pos] * b, dtype=torch.int32)))
-        table = _SharedTable(buf[0:b], buf[b : 2 * b], buf[2 * b : 3 * b], plan.n_slots)
+        rows = _Rows(slots=buf[0:b], n_slots=plan.n_slots, prefix_slots=buf[b : 2 * b], prefix_len=buf[2 * b : 3 * b])
         row_perm = torch.tensor(plan.copy_rank, dtype=torch.int64, device=self._device)
-        first = torch.empty(b, dtype=torch.int32, device=self._device)
-        hidden_last = torch.empty(b, self.config.text.dim, dtype=BF16, device=self._device)
-        next_pos = [0] * b
-        for r0, r1 in plan.groups:  # one prefill per distinct prompt length
-            x = self._embed(torch.tensor(prompts[r0:r1], dtype=torch.int32))
-            hidden = self._text_forward(x, pos, shared=table.sub(r0, r1))
-            logits = self._lm_head(hidden)
-            if sampler is None:
-                first[r0:r1] = self._pick(logits, 0.0, 0.0)
-            else:  # the group's draws in the copy path's row order
-                local = row_perm[r0:r1] - min(plan.copy_rank[r0:r1])
-                first[r0:r1] = self._pick(logits, *sampler, row_perm=local)
-            hidden_last[r0:r1] = hidden[:, -1, :]
-            next_pos[r0:r1] = [pos + x.shape[1]] * (r1 - r0)
+        # one prefill per distinct prompt length; a sampled group draws in the copy path's row order
+        first, hidden_last, next_pos = self._prefill_groups(
+            plan.groups, lambda r0, r1: self._embed(torch.tensor(prompts[r0:r1], dtype=torch.int32)), pos, rows, sampler,
+            row_perm=lambda r0, r1: row_perm[r0:r1] - min(plan.copy_rank[r0:r1]))
         mark("prompt_prefill")
-        return plan.order, first, hidden_last, next_pos, table, row_perm
+        return plan.order, first, hidden_last, next_pos, rows, row_perm
 
     def batch_generate_ids(
         self,
@@ -1440,35 +1490,27 @@ class MoondreamModel:
                 multi_rows = [-1 if v is None else self._bank_index(v) for v in variants]
         tk = self.config.tokenizer
         eos = tk.eos_id if eos_id is None else eos_id
-        marks = []
-
-        def mark(name):
-            if self.collect_timing:
-                e = torch.cuda.Event(enable_timing=True)
-                e.record(torch.cuda.current_stream(self._device))
-                marks.append((name, e))
-
+        marks: list = []
+        mark = lambda name: self._mark(marks, name)
         lora = self._lora({"variant": variant})
         with torch.inference_mode():
             sampler = None if temperature == 0 else (float(temperature), float(top_p), -1, generator)
-            shared = row_perm = multi = None
-            if multi_rows is not None:
-                # the slot order of _prepare_sequences (stable by prompt length), so that the table is in slot order too
-                slot_order = sorted(range(b), key=lambda i: len(prompts[i]))
-                multi = self._variant_table([multi_rows[i] for i in slot_order])
-                order, first, _, next_pos = self._prepare_sequences(list(images), prompts, mark, None, fuse=True, sampler=sampler,
-                                                                    multi=multi)
-            elif share_prefix and self._shares_prefix(lora):
-                order, first, _, next_pos, shared, row_perm = self._prepare_sequences_shared(list(images), prompts, mark, sampler)
+            rows, row_perm = _Rows(lora=lora), None
+            if multi_rows is None and share_prefix and self._shares_prefix(lora):
+                order, first, _, next_pos, rows, row_perm = self._prepare_sequences_shared(list(images), prompts, mark, sampler)
             else:
-                if share_prefix:  # the copy path over each distinct image's EncodedImage
+                if multi_rows is not None:
+                    # the slot order of _prepare_sequences (stable by prompt length), so that the table is in slot order too
+                    slot_order = sorted(range(b), key=lambda i: len(prompts[i]))
+                    rows = _Rows(variants=self._variant_table([multi_rows[i] for i in slot_order]), bank=self._bank)
+                elif share_prefix:  # the copy path over each distinct image's EncodedImage
                     images = self._encode_distinct(images, {"variant": variant})
-                order, first, _, next_pos = self._prepare_sequences(list(images), prompts, mark, lora, fuse=True, sampler=sampler)
+                order, first, _, next_pos = self._prepare_sequences(list(images), prompts, mark, rows, fuse=True, sampler=sampler)
             b = len(order)
             stop = None if ignore_eos else eos
             hist = self._decode_greedy(first, next_pos if len(set(next_pos)) > 1 else next_pos[0], max_tokens,
-                                       tk.answer_id, 0, stop, lora=lora, temperature=float(temperature), top_p=float(top_p),
-                                       generator=generator, shared=shared, row_perm=row_perm, multi=multi)
+                                       tk.answer_id, rows, stop, temperature=float(temperature), top_p=float(top_p),
+                                       generator=generator, row_perm=row_perm)
             mark("decode")
             cols = hist.t().tolist()
             if b == 1:
@@ -1476,9 +1518,7 @@ class MoondreamModel:
             results: List[Optional[List[int]]] = [None] * b
             for slot, src in enumerate(order):
                 results[src] = self._truncate(cols[slot], stop, max_tokens)
-        if self.collect_timing and len(marks) > 1:
-            torch.cuda.synchronize(self._device)
-            self.last_phase_ms = {marks[i][0]: marks[i - 1][1].elapsed_time(marks[i][1]) for i in range(1, len(marks))}
+        self._phase_times(marks)
         return results  # type: ignore[return-value]
 
     def batch_generate_ids_continuous(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
@@ -1509,7 +1549,7 @@ class MoondreamModel:
         out = torch.empty(b, t_steps + 1, idx.shape[2], dtype=torch.float32)
         with torch.inference_mode():
             cap = torch.empty(b, t.vocab_size, dtype=BF16, device=self._device)
-            order, _, _, next_pos = self._prepare_sequences(list(images), prompts, None, None, fuse=True, logits_capture=cap)
+            order, _, _, next_pos = self._prepare_sequences(list(images), prompts, fuse=True, logits_capture=cap)
             src = torch.tensor(order, dtype=torch.int64)
             forced_s, idx_s = forced[src].to(self._device), idx[src].to(self._device)  # slot order
             vals = torch.empty(b, t_steps + 1, idx.shape[2], dtype=torch.float32, device=self._device)
@@ -1517,17 +1557,12 @@ class MoondreamModel:
             hist = torch.cat([forced_s.t().contiguous(), torch.zeros(1, b, dtype=torch.int32, device=self._device)], 0)
             scratch = torch.empty(b, dtype=torch.int32, device=self._device)
             logits = self._decode_logits(b)
-            ws = self._workspace(self.lib.md_decode_workspace_bytes(C.byref(self.w.text), b), 2)
+            rows = _Rows()
+            ws = self._workspace(self._decode_ws_bytes(rows, b), 2)
             kv = self._kv_struct(0)
             pos_t = torch.tensor([int(p) for p in next_pos], dtype=torch.int32, device=self._device)
             for j in range(t_steps):
-                _lib.check(
-                    self.lib.md_decode_step(
-                        C.byref(self.w.text), hist[j].data_ptr(), scratch.data_ptr(), pos_t.data_ptr(), b, C.byref(kv),
-                        tk.answer_id, logits.data_ptr(), t.vocab_size, ws.data_ptr(), ws.numel(), self._stream(),
-                    ),
-                    "md_decode_step",
-                )
+                self._decode_step(rows, hist[j], scratch, pos_t, b, tk.answer_id, logits, ws, kv)
                 vals[:, j + 1] = torch.gather(logits[:b].float(), 1, idx_s[:, j + 1])
             out[src] = vals.cpu()
         return out
@@ -1744,7 +1779,7 @@ class MoondreamModel:
                 emb[ids.to(self._device) == self.config.tokenizer.coord_id] = enc["coords"]
                 if enc["sizes"] is not None:
                     emb[ids.to(self._device) == self.config.tokenizer.size_id] = enc["sizes"]
-            hidden = self._text_forward(emb, pos, 0, causal=causal, lora=lora if isinstance(lora, PackedLora) else None)
+            hidden = self._text_forward(emb, pos, _Rows(lora=lora if isinstance(lora, PackedLora) else None), causal=causal)
             logits = self._lm_head(hidden)
             nxt = self._pick(logits, temperature, top_p)
         return logits, hidden, nxt.reshape(1, 1), pos + ids.shape[1]
@@ -1758,6 +1793,7 @@ class MoondreamModel:
         temperature = settings.get("temperature", DEFAULT_TEMPERATURE)
         top_p = settings.get("top_p", DEFAULT_TOP_P)
         lora = self._lora(settings)
+        rows = _Rows(lora=lora)
         eos = eos_id if eos_id is not None else self.config.tokenizer.eos_id
         # decode steps attend to keys [0, pos] only, which both masks allow: the mask matters for the prompt
         _, _, nxt, pos = self._prefill_prompt(prompt_tokens, pos, temperature, top_p, spatial_refs, attn_mask, lora=lora, causal=causal)
@@ -1789,7 +1825,7 @@ class MoondreamModel:
                         return
                     with torch.inference_mode():
                         emb = self._embed(tok.reshape(1, 1))
-                        hidden = self._text_forward(emb, cur_pos, 0, lora=lora)
+                        hidden = self._text_forward(emb, cur_pos, rows)
                         logits = self._lm_head(hidden)
                         cur_pos += 1
                         tok = self._pick(logits, temperature, top_p, self.config.tokenizer.answer_id)  # moondream.py:517
@@ -1892,6 +1928,7 @@ class MoondreamModel:
         temperature = settings.get("temperature", DEFAULT_TEMPERATURE)
         top_p = settings.get("top_p", DEFAULT_TOP_P)
         lora = self._lora(settings)
+        rows = _Rows(lora=lora)
         tk = self.config.tokenizer
         _, hidden, nxt, pos = self._prefill_prompt(prompt_tokens, pos, temperature, top_p, spatial_refs, attn_mask, lora=lora, causal=causal)
         last_hidden = hidden[:, -1:, :].reshape(1, -1)
@@ -1914,7 +1951,7 @@ class MoondreamModel:
                     grounding_chunks[-1].append((bins[0, 0].to(torch.int64) / n_bins).item())
                 else:
                     emb = self._embed(torch.tensor([[tok]]))
-                h = self._text_forward(emb.reshape(1, 1, -1), pos, 0, lora=lora)
+                h = self._text_forward(emb.reshape(1, 1, -1), pos, rows)
                 logits = self._lm_head(h)
                 logits[:, suppress] = float("-inf")  # moondream.py:397-398
                 pos += 1
@@ -2049,11 +2086,10 @@ class MoondreamModel:
         )
         return self._lin(feats, enc)
 
-    def _points_loop(self, hidden: torch.Tensor, first: torch.Tensor, pos: Sequence[int], slot0: int, include_size: bool,
-                     max_objects: int, lora: Optional[PackedLora] = None, run_all: bool = False,
-                     shared: Optional[_SharedTable] = None) -> List[List[dict]]:
+    def _points_loop(self, hidden: torch.Tensor, first: torch.Tensor, pos: Sequence[int], rows: Union[int, _Rows],
+                     include_size: bool, max_objects: int, run_all: bool = False) -> List[List[dict]]:
         """The loop of moondream.py:653-733 for B sequences in lockstep.  hidden [B, D] = last prompt
-        position, first int32 [B] = the token after the prompt, pos[b] = next position."""
+        position, first int32 [B] = the token after the prompt, pos[b] = next position, ``rows`` their routing."""
         b = hidden.shape[0]
         eos = self.config.tokenizer.eos_id
         n_bins = self.config.region.coord_out_dim
@@ -2069,7 +2105,7 @@ class MoondreamModel:
 
         def step(emb):
             nonlocal pos_host, hidden
-            h = self._text_forward(emb.reshape(b, 1, -1), pos_host, slot0, pos_dev=pos_dev, lora=lora, shared=shared)
+            h = self._text_forward(emb.reshape(b, 1, -1), pos_host, rows, pos_dev=pos_dev)
             pos_host = [p + 1 for p in pos_host]
             pos_dev.add_(1)
             hidden = h.reshape(b, -1)
@@ -2129,28 +2165,20 @@ class MoondreamModel:
         lora = self._lora(settings)  # moondream.py:757-761
         max_objects = (settings or {}).get("max_objects", DEFAULT_MAX_OBJECTS)
         prompts = [list(tpl["prefix"]) + list(self.tokenizer.encode(" " + o).ids) + list(tpl["suffix"]) for o in objects]
-        marks = []
-
-        def mark(name):
-            if self.collect_timing:
-                e = torch.cuda.Event(enable_timing=True)
-                e.record(torch.cuda.current_stream(self._device))
-                marks.append((name, e))
-
+        marks: list = []
+        mark = lambda name: self._mark(marks, name)
         with torch.inference_mode():
-            shared = None
+            rows = _Rows(lora=lora)
             if share_prefix and self._shares_prefix(lora):
-                order, first, hidden, next_pos, shared, _ = self._prepare_sequences_shared(list(images), prompts, mark)
+                order, first, hidden, next_pos, rows, _ = self._prepare_sequences_shared(list(images), prompts, mark)
             else:
                 if share_prefix:
                     images = self._encode_distinct(images, settings)
-                order, first, hidden, next_pos = self._prepare_sequences(list(images), prompts, mark, lora)
-            res = self._points_loop(hidden, first, next_pos, 0, include_size, max_objects, lora,
-                                    run_all=bool((settings or {}).get("_run_all_objects", False)), shared=shared)
+                order, first, hidden, next_pos = self._prepare_sequences(list(images), prompts, mark, rows)
+            res = self._points_loop(hidden, first, next_pos, rows, include_size, max_objects,
+                                    run_all=bool((settings or {}).get("_run_all_objects", False)))
             mark("points_loop")
-        if self.collect_timing and len(marks) > 1:
-            torch.cuda.synchronize(self._device)
-            self.last_phase_ms = {marks[i][0]: marks[i - 1][1].elapsed_time(marks[i][1]) for i in range(1, len(marks))}
+        self._phase_times(marks)
         out = [None] * len(order)
         for slot, src in enumerate(order):
             out[src] = res[slot]

@@ -11,6 +11,7 @@ from PIL import Image
 
 from moondream_amd import _lib, synth
 from moondream_amd.config import get_config
+from moondream_amd.moondream import _Rows
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -157,7 +158,7 @@ def test_shrink_and_expand_match_fp32_torch(tiny128, batch, q_len):
 
 # ------------------------------------------------------------------ decoder: mixed vs uniform calls
 def decode_logits(model, x, pos, multi=None, lora=None):
-    h = model._text_forward(x, pos, 0, multi=multi, lora=lora)
+    h = model._text_forward(x, pos, _Rows(variants=multi, bank=model._bank if multi is not None else None, lora=lora))
     return model._lm_head(h)
 
 
