@@ -272,7 +272,7 @@ def hipcc_path() -> str:
 def build_library(force: bool = False, verbose: bool = True) -> str:
     """Compile csrc/*.hip for gfx950 into moondream_amd/libmoondream_hip.so."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("md_common.hpp", "gemm_internal.hpp")] + [os.path.join(REPO, "include", "moondream_hip.h")]
+    deps = srcs + [os.path.join(CSRC, h) for h in ("md_common.hpp", "gemm_internal.hpp", "text_internal.hpp")] + [os.path.join(REPO, "include", "moondream_hip.h")]
     if not force and os.path.exists(LIB_PATH):
         if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps + [os.path.abspath(__file__)]):
             return LIB_PATH

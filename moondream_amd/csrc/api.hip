@@ -3,19 +3,11 @@
 // in this library.  Nothing here allocates or synchronises; every buffer,
 // including the workspace, belongs to the caller.
 #include "gemm_internal.hpp"
+#include "text_internal.hpp"
 #include <climits>
 #include <cstdlib>
 
 #include <algorithm>
-
-md_status md_argmax_advance(const void* logits, int64_t ld, int32_t batch, int32_t vocab,
-                            int32_t suppress_id, int32_t* next, int32_t* pos, hipStream_t stream);
-md_status md_stitch_pool_batched(const void* feats, void* out, int64_t ld_out, int64_t out_img_stride,
-                                 int32_t n_images, int32_t dim, int32_t grid, int32_t margin,
-                                 int32_t tiles_h, int32_t tiles_w, hipStream_t stream);
-
-md_status md_pool_grid_concat(const void* global_feats, const void* grid_feats, int32_t H, int32_t W,
-                              void* out, int64_t ld_out, int32_t dim, int32_t grid, hipStream_t stream);
 
 namespace {
 
@@ -414,53 +406,9 @@ extern "C" size_t md_text_workspace_bytes(const md_text_model* m, int32_t batch,
   return need;
 }
 
-// the slot-table forms of the kernels' host entry points (slots == nullptr: sequence b in slot b)
-md_status md_kv_quantize_f8_layer(const md_kv_cache* kv, int layer, const int32_t* pos0, int pos_fixed, int batch, int n_heads, int n_pos,
-                                  hipStream_t s, const int32_t* slots, int n_slots);
-md_status md_attention_decode_rope_f8_launch(const void* qkv, int64_t ld, void* o, int64_t ldo, const float* freqs, void* k_slab, void* v_slab,
-                                             void* k8_slab, void* v8_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len,
-                                             int32_t batch, int32_t n_heads, int32_t rot_dim, float scale, float k_scale, float v_scale,
-                                             hipStream_t s, const int32_t* slots, int32_t n_slots);
-md_status md_rope_kv_write_slots(void* qkv, int64_t ld, const float* freqs, const int32_t* pos0, void* k_slab, void* v_slab,
-                                 int64_t slab_batch_stride, int32_t ctx, int32_t batch, int32_t q_len, int32_t n_heads,
-                                 int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim, const int32_t* slots, int32_t n_slots,
-                                 hipStream_t stream);
-md_status md_attention_prefill_slots(const md_attn_args* a, const int32_t* slots, hipStream_t stream);
-// lora_multi.hip / elementwise.hip: the pieces of the multi-LoRA path
-md_status lora_bank_ok(const md_lora_bank* bank);
-int32_t md_lora_shrink_cols(const md_lora_bank* bank, int32_t pairs);
-md_status md_reduce_residual_layernorm_add(void* x, int64_t ldx, const float* partial_a, int32_t slices_a, const void* bias_a,
-                                           const float* partial_b, int32_t slices_b, const void* bias_b, int64_t ld_partial,
-                                           int64_t slice_stride, void* y, int64_t ldy, const md_layernorm* ln, int32_t rows,
-                                           int32_t dim, float eps, const void* da, const void* db, int64_t ldd, void* stream);
-md_status md_attention_prefill_shared(const md_attn_args* a, const int32_t* slots, const int32_t* pfx_slots, const int32_t* pfx_len,
-                                      int32_t n_slots, hipStream_t stream);
-md_status md_attention_decode_shared_any(bool fused, const void* q, int64_t ldq, void* o, int64_t ldo, const float* freqs, void* k_slab,
-                                         void* v_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch,
-                                         int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim, float scale,
-                                         const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots, const int32_t* prefix_len,
-                                         hipStream_t stream);
-md_status md_attention_decode_slots(const void* q, int64_t ldq, void* o, int64_t ldo, const void* k_slab, const void* v_slab,
-                                    int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch, int32_t n_heads,
-                                    int32_t n_kv_heads, int32_t head_dim, float scale, const int32_t* slots, int32_t n_slots,
-                                    hipStream_t stream);
-md_status md_attention_decode_rope_slots(const void* qkv, int64_t ld, void* o, int64_t ldo, const float* freqs, void* k_slab,
-                                         void* v_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch,
-                                         int32_t n_heads, int32_t head_dim, int32_t rot_dim, float scale, const int32_t* slots,
-                                         int32_t n_slots, hipStream_t stream);
+namespace {
 
-extern "C" md_status md_text_forward(const md_text_model* m, const void* x_in, void* hidden,
-                                     int32_t batch, int32_t q_len, const int32_t* pos0,
-                                     const md_kv_cache* kv, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-  return md_text_forward_slots(m, x_in, hidden, batch, q_len, pos0, nullptr, 0, kv, workspace, workspace_bytes, stream);
-}
-
-// md_text_forward_multi_lora: the bank and the per-sequence variant table of the rows of this call
-struct LoraCall {
-  const md_lora_bank* bank;
-  const int32_t* variant;
-};
+// md_text_forward_multi_lora: the shrink outputs and the proj / fc2 deltas of the rows of a call
 struct LoraBufs {
   bf16_t *t1, *t2, *d_proj, *d_fc2;  // shrink outputs [M][ld1] / [M][ld2]; proj / fc2 deltas (or outputs) [M][dim]
   int64_t ld1, ld2;
@@ -478,99 +426,322 @@ LoraBufs lora_bufs(const md_text_model* m, const md_lora_bank* bank, size_t M, v
   w.total = a.off;
   return w;
 }
-static md_status text_forward_impl(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
-                                   const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* pfx_slots,
-                                   const int32_t* pfx_len, const md_kv_cache* kv, void* workspace, size_t workspace_bytes,
-                                   void* stream, const LoraCall* lc = nullptr);
 
-extern "C" md_status md_text_forward_slots(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
-                                           const int32_t* pos0, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
-                                           void* workspace, size_t workspace_bytes, void* stream) {
-  return text_forward_impl(m, x_in, hidden, batch, q_len, pos0, slots, n_slots, nullptr, nullptr, kv, workspace, workspace_bytes,
-                           stream);
+inline bf16_t* layer_slab(void* slab, const md_kv_cache* kv, int l) { return (bf16_t*)slab + (int64_t)l * kv->layer_stride; }
+// the e4m3 copy of the cache (fp8 mode) has the same layout at one byte per element
+inline uint8_t* layer_slab8(void* slab8, const md_kv_cache* kv, int l) { return (uint8_t*)slab8 + (int64_t)l * kv->layer_stride; }
+inline bool kv_f8_scaled(const md_kv_cache* kv) { return kv->k8 && kv->v8 && kv->k_scale && kv->v_scale; }
+
+// the prefill attention of block l over its slab: query rows [batch][q_len][ldq] in q, output rows [.][ldo] (text.py:48-51)
+md_attn_args prefill_attn_args(const md_text_model* m, const md_kv_cache* kv, int l, const void* q, int64_t ldq, void* o, int64_t ldo,
+                               int batch, int q_len, const int32_t* pos0, const int32_t* kv_len) {
+  const int hd = m->dim / m->n_heads;
+  md_attn_args a = {};
+  a.q = q;
+  a.q_bs = (int64_t)q_len * ldq;
+  a.q_ts = ldq;
+  a.q_hs = hd;
+  a.k = layer_slab(kv->k, kv, l);
+  a.v = layer_slab(kv->v, kv, l);
+  a.k_bs = a.v_bs = kv->batch_stride;
+  a.k_ts = a.v_ts = hd;
+  a.k_hs = a.v_hs = (int64_t)kv->ctx * hd;
+  a.o = o;
+  a.o_bs = (int64_t)q_len * ldo;
+  a.o_ts = ldo;
+  a.o_hs = hd;
+  a.batch = batch;
+  a.n_heads = m->n_heads;
+  a.n_kv_heads = m->n_kv_heads;
+  a.head_dim = hd;
+  a.q_len = q_len;
+  a.kv_len_all = 0;
+  a.q_pos0 = pos0;
+  a.kv_len = kv_len;
+  a.prefix_len = m->prefix_len;
+  a.scale = 1.0f / sqrtf((float)hd);
+  return a;
 }
 
-// the checks of the shared-prefix entry points that need no device: a table needs the slot table, and the e4m3 KV copy (fp8
-// mode) is not supported with one
-static md_status shared_args_ok(const md_kv_cache* kv, const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
-                                const int32_t* prefix_len) {
-  MD_CHECK_ARG(kv && kv->k8 == nullptr && kv->v8 == nullptr);
-  MD_CHECK_ARG(slots == nullptr || n_slots > 0);  // as md_text_forward_slots
-  MD_CHECK_ARG(prefix_slots == nullptr || (slots != nullptr && prefix_len != nullptr));
+// What the blocks of one forward share: a prefill, or the rows of a decode step that the decode regime takes in one pass.
+struct Fwd {
+  const md_text_model* m;
+  const md_kv_cache* kv;
+  RowMap rows;
+  const int32_t* pos0;
+  int32_t* kv_len;
+  bf16_t* x;  // the hidden rows, updated in place
+  int batch, q_len, M, D, Dp, hd, qkv_w;
+  TextWs w;
+  LoraBufs lw;      // rows.bank != nullptr
+  DecodeAttn dec;   // the decode attention's descriptor but for the block's slabs / scales, leading dimension and fused flag
+  bool tail_fused;  // decode regime: launch-boundary split-K for proj / fc2 + fused block tail
+  // prefill: RoPE + KV write in the epilogue of the fused qkv|fc1 GEMM (MD_EPI_QKV_ROPE), per-row positions / slab offsets
+  // once per forward
+  bool rope_in_gemm;
+  uint64_t slab_bytes;
+  bool rope_done;      // set per block when the fused launch took it
+  bool rope_done_kv8;  // ... and also wrote the e4m3 copy of the rows (fp8 mode)
+  const md_text_f8* f8p;  // FP8 prefill (opt-in, md_text_f8)
+  bool use_f8;
+  float* calib;
+  hipStream_t s;
+};
+
+// per block: the packing of its qkv / fc1 linears and the fp8 weight copies the decode regime may stream instead
+struct BlockIo {
+  bool packed;        // one GEMM writes [qkv | gelu(fc1)]
+  int64_t qld, ffld;  // leading dimensions of the qkv and the fc1 activation
+  const md_text_block_fp8* f8w;
+};
+BlockIo block_io(const Fwd& f, int l) {
+  const md_text_model* m = f.m;
+  const md_text_block& b = m->blocks[l];
+  BlockIo io;
+  io.packed = b.qkv_fc1.w != nullptr;
+  io.qld = io.packed ? b.qkv_fc1.n_pad : f.qkv_w;
+  io.ffld = io.packed ? b.qkv_fc1.n_pad : b.fc1.n_pad;
+  // decode regime with FP8 weight copies attached (opt-in): the same three launches over half the bytes
+  io.f8w = (m->fp8 && m->fp8->blocks && f.tail_fused && io.packed) ? &m->fp8->blocks[l] : nullptr;
+  return io;
+}
+
+md_rope_fuse rope_fuse_args(const Fwd& f, int l) {
+  md_rope_fuse rf;
+  rf.row_cs = f.w.rope_cs;
+  rf.row_kv = f.w.rope_kv;
+  rf.kslab = layer_slab(f.kv->k, f.kv, l);
+  rf.vslab = layer_slab(f.kv->v, f.kv, l);
+  rf.slab_bytes = f.slab_bytes;
+  rf.n_heads = f.m->n_heads;
+  rf.ctx = f.kv->ctx;
+  return rf;
+}
+
+// rope(q), rope(k), cache update (text.py:42-46) and attention over the slab (text.py:48-51) of block l.  fuse_rope (a decode
+// step, MHA): both inside the attention kernel.  att8: the prefill writes proj's e4m3 operand instead of bf16 rows (fp8 mode).
+md_status rope_and_attention(Fwd& f, int l, int64_t qld, bool fuse_rope, uint8_t* att8 = nullptr, float att8_inv_scale = 0.f) {
+  const md_text_model* m = f.m;
+  const md_kv_cache* kv = f.kv;
+  bf16_t *kl = layer_slab(kv->k, kv, l), *vl = layer_slab(kv->v, kv, l);
+  if (!fuse_rope && !f.rope_done)
+    MD_TRY(md_rope_kv_write_slots(f.w.qkv, qld, m->freqs, f.pos0, kl, vl, kv->batch_stride, kv->ctx, f.batch, f.q_len, m->n_heads,
+                                  m->n_kv_heads, f.hd, m->rot_dim, f.rows, f.s));
+  const bool kv8 = kv_f8_scaled(kv) && m->n_kv_heads == m->n_heads && f.hd == 64;
+  if (f.q_len == 1) {
+    DecodeAttn d = f.dec;
+    d.ldq = qld;
+    d.k_slab = kl;
+    d.v_slab = vl;
+    d.fused = fuse_rope;
+    if (kv8) {  // fp8 mode: a fused step attends over the e4m3 copy of the cache and writes the new row into both copies
+      d.k8_slab = layer_slab8(kv->k8, kv, l);
+      d.v8_slab = layer_slab8(kv->v8, kv, l);
+      d.k_scale = kv->k_scale[l];
+      d.v_scale = kv->v_scale[l];
+    }
+    MD_TRY(md_attention_decode_rows(d, f.rows, f.s));
+  } else {
+    md_attn_args a = prefill_attn_args(m, kv, l, f.w.qkv, qld, f.w.att, f.Dp, f.batch, f.q_len, f.pos0, f.kv_len);
+    if (att8 != nullptr) {  // fp8 mode: proj reads e4m3 rows only -- written by the attention epilogue, no bf16 copy, no quantise pass
+      a.o = nullptr;
+      a.o8 = att8;
+      a.o8_bs = (int64_t)f.q_len * f.Dp;
+      a.o8_ts = f.Dp;
+      a.o8_inv_scale = att8_inv_scale;
+    }
+    MD_TRY(md_attention_prefill_rows(&a, f.rows, f.s));
+  }
+  // fp8 mode: the rows this pass wrote (bf16) also go into the e4m3 copy the decode steps read
+  if (kv8 && !fuse_rope && !f.rope_done_kv8) MD_TRY(md_kv_quantize_f8_layer(kv, l, f.pos0, 0, f.batch, m->n_heads, f.q_len, f.rows, f.s));
   return MD_OK;
 }
 
-extern "C" md_status md_text_forward_shared(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
-                                            const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
-                                            const int32_t* prefix_len, const md_kv_cache* kv, void* workspace,
-                                            size_t workspace_bytes, void* stream) {
-  MD_TRY(shared_args_ok(kv, slots, n_slots, prefix_slots, prefix_len));
-  return text_forward_impl(m, x_in, hidden, batch, q_len, pos0, slots, n_slots, prefix_slots, prefix_len, kv, workspace,
-                           workspace_bytes, stream);
+// One block of the FP8 prefill (opt-in, md_text_f8): launches of more than 64 rows with the fused qkv|fc1 packing.
+md_status f8_prefill_block(Fwd& f, int l) {
+  const md_text_model* m = f.m;
+  const md_kv_cache* kv = f.kv;
+  const md_text_block& b = m->blocks[l];
+  const md_text_block_f8& q = f.f8p->blocks[l];
+  const TextWs& w = f.w;
+  const int M = f.M, D = f.D, Dp = f.Dp, qkv_w = f.qkv_w;
+  bf16_t* x = f.x;
+  hipStream_t s = f.s;
+  const int64_t qld = b.qkv_fc1.n_pad;
+  MD_CHECK_ARG(f8_scales_ok(q.s_ln, q.s_att, q.s_ff) && q.qkv_fc1.n_pad == b.qkv_fc1.n_pad && q.qkv_fc1.k_pad == Dp &&
+               q.fc2.k_pad == b.fc1.n_pad && q.proj.k_pad == Dp && b.qkv_fc1.n_pad == qkv_w + b.fc1.n_pad);
+  // fp8 activations: ln(x) / the attention output in the (bf16-sized) h buffer, gelu(fc1) in the fc1 columns' own
+  // (bf16-sized) slots of the fused activation rows
+  uint8_t* h8 = (uint8_t*)w.h;
+  uint8_t* ff8 = (uint8_t*)w.qkv + (size_t)qkv_w * 2;
+  MD_TRY(md_layernorm_f8(x, D, h8, Dp, &b.ln, M, D, Dp, 1e-5f, 1.0f / q.s_ln, s));
+  // [qkv | gelu(fc1) -> e4m3]; with per-row positions at hand the epilogue also rotates q / k and writes k / v to the
+  // slab and to its e4m3 copy (MD_EPI_QKV_ROPE, as the bf16 kernel does): no rope_kv_kernel, no kv-quantise pass
+  f.rope_done = f.rope_done_kv8 = false;
+  if (f.rope_in_gemm) {
+    md_gemm_f8_args g;
+    g.a = h8; g.lda = Dp; g.a_scale = q.s_ln; g.lin = q.qkv_fc1; g.c = w.qkv; g.ldc = qld;
+    g.c8 = ff8; g.ldc8 = qld * 2; g.c8_inv_scale = 1.0f / q.s_ff; g.f8_from_col = qkv_w;
+    g.r = nullptr; g.ldr = 0; g.res_row_mod = 0; g.m = M; g.epilogue = MD_EPI_GELU; g.store_pad_cols = 1; g.gelu_from_col = qkv_w;
+    const md_rope_fuse rf = rope_fuse_args(f, l);
+    md_rope_fuse_f8 rf8 = {nullptr, nullptr, 1.f, 1.f};
+    const bool has8 = kv_f8_scaled(kv);
+    if (has8) rf8 = {layer_slab8(kv->k8, kv, l), layer_slab8(kv->v8, kv, l), kv->k_scale[l], kv->v_scale[l]};
+    const md_status fs = md_gemm_f8_qkv_rope(&g, &rf, &rf8, s);
+    if (fs == MD_OK) {
+      f.rope_done = true;
+      f.rope_done_kv8 = has8;
+    } else if (fs != MD_ERR_UNSUPPORTED) {
+      return fs;
+    }
+  }
+  if (!f.rope_done)
+    MD_TRY(gemm_f8(h8, Dp, q.s_ln, q.qkv_fc1, w.qkv, qld, M, MD_EPI_GELU, nullptr, 0, 0, 1, s, ff8, qld * 2, q.s_ff, qkv_w, qkv_w));
+  if (f.q_len > 1 && Dp == D) {
+    MD_TRY(rope_and_attention(f, l, qld, false, h8, 1.0f / q.s_att));
+  } else {
+    MD_TRY(rope_and_attention(f, l, qld, false));
+    MD_TRY(md_quantize_f8(w.att, Dp, h8, Dp, M, D, Dp, 1.0f / q.s_att, s));
+  }
+  MD_TRY(gemm_f8(h8, Dp, q.s_att, q.proj, x, D, M, MD_EPI_RESIDUAL, x, D, 0, 0, s));
+  return gemm_f8(ff8, qld * 2, q.s_ff, q.fc2, x, D, M, MD_EPI_RESIDUAL, x, D, 0, 0, s);
 }
 
-// reference: text.py:128-160 (text_decoder) with text.py:16-60 (attn).  slots == nullptr: sequence b in slot b (md_text_forward);
-// otherwise every place that addresses a slab -- the RoPE / KV-write epilogue's row offsets, rope_kv_kernel, the prefill and
-// decode attention, the e4m3 copy -- takes slot slots[b], and a decode row whose slot is outside [0, n_slots) is idle.
-// pfx_slots != nullptr (md_text_forward_shared): the prefill and decode attention read keys [0, pfx_len[b]) from slot
-// pfx_slots[b]; every write still goes to slot slots[b].
-static md_status text_forward_impl(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
-                                   const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* pfx_slots,
-                                   const int32_t* pfx_len, const md_kv_cache* kv, void* workspace, size_t workspace_bytes,
-                                   void* stream, const LoraCall* lc) {
-  MD_CHECK_ARG(m && x_in && hidden && pos0 && kv && kv->k && kv->v && workspace && m->blocks);
-  MD_CHECK_ARG(batch > 0 && q_len > 0 && m->dim % m->n_heads == 0);
-  MD_CHECK_ARG(slots == nullptr || n_slots > 0);
-  if (slots == nullptr) n_slots = batch;  // the slots a contiguous call addresses
-  MD_CHECK_ARG(tile_policy_ok(m->tile_policy));
-  TilePolicyScope tile_scope(m->tile_policy);
-  // the e4m3 copy of the KV cache (fp8 mode) keeps the 64-row blocks: its attention kernel is part of an opt-in mode tuned there
-  const bool tall_ok = decode_tall_model(m) && !(kv->k8 && kv->v8);
-  const int block_rows = tall_ok ? 128 : 64;
-  if (q_len == 1 && batch > block_rows) {
-    // A decode step over more sequences than the decode regime takes in one pass: blocks of 64 (128) rows, each through the
-    // decode-regime kernels (weight-streaming GEMMs, launch-boundary split-K, fused block tail).  The weights are
-    // streamed once per block; the big-tile kernels this replaces ran the step ~1.5x slower at 128 rows.
-    for (int b0 = 0; b0 < batch; b0 += block_rows) {
-      const int nb = std::min(block_rows, batch - b0);
-      const void* xb = (const char*)x_in + (int64_t)b0 * m->dim * 2;
-      void* hb = (char*)hidden + (int64_t)b0 * m->dim * 2;
-      LoraCall lb;  // the block's rows take their own entries of the variant table
-      if (lc) lb = LoraCall{lc->bank, lc->variant + b0};
-      if (slots != nullptr) {  // slot table: the slab base stays, the block's rows take their own entries of the table(s)
-        MD_TRY(text_forward_impl(m, xb, hb, nb, 1, pos0 + b0, slots + b0, n_slots, pfx_slots ? pfx_slots + b0 : nullptr,
-                                 pfx_slots ? pfx_len + b0 : nullptr, kv, workspace, workspace_bytes, stream, lc ? &lb : nullptr));
-        continue;
-      }
-      md_kv_cache sub = *kv;
-      sub.k = (char*)kv->k + (int64_t)b0 * kv->batch_stride * 2;
-      sub.v = (char*)kv->v + (int64_t)b0 * kv->batch_stride * 2;
-      // the e4m3 copy of the cache (fp8 mode) has the same slot layout at one byte per element
-      if (kv->k8) sub.k8 = (char*)kv->k8 + (int64_t)b0 * kv->batch_stride;
-      if (kv->v8) sub.v8 = (char*)kv->v8 + (int64_t)b0 * kv->batch_stride;
-      MD_TRY(text_forward_impl(m, xb, hb, nb, 1, pos0 + b0, nullptr, 0, nullptr, nullptr, &sub, workspace, workspace_bytes, stream,
-                               lc ? &lb : nullptr));
-    }
-    return MD_OK;
+// qkv = qkv(l_in), with fc1's half of the packed layer when there is one (text.py:30, layers.py:130-138)
+md_status qkv_linear(Fwd& f, int l, const BlockIo& io) {
+  const md_text_block& b = f.m->blocks[l];
+  const TextWs& w = f.w;
+  if (io.f8w && io.f8w->qkv_fc1.w) {
+    MD_CHECK_ARG(io.f8w->qkv_fc1.n_pad == b.qkv_fc1.n_pad && f.qkv_w % 64 == 0);
+    return md_gemm_fp8w(w.h, f.Dp, &io.f8w->qkv_fc1, w.qkv, io.qld, f.M, MD_EPI_GELU, 1, f.qkv_w, f.s);
   }
-  const int hd = m->dim / m->n_heads;
+  if (!io.packed) return gemm(w.h, f.Dp, b.qkv, w.qkv, f.qkv_w, f.M, MD_EPI_BIAS, nullptr, 0, 0, 0, f.s, w.splitk, w.splitk_bytes);
+  // one GEMM for both consumers of l_in: [qkv | gelu(fc1)]
+  MD_CHECK_ARG(b.qkv_fc1.n_pad == f.qkv_w + b.fc1.n_pad && f.qkv_w % 64 == 0);
+  md_gemm_args g;
+  g.a = w.h; g.lda = f.Dp; g.lin = b.qkv_fc1; g.c = w.qkv; g.ldc = io.qld; g.r = nullptr; g.ldr = 0;
+  g.res_row_mod = 0; g.m = f.M; g.epilogue = MD_EPI_GELU; g.store_pad_cols = 1; g.gelu_from_col = f.qkv_w;
+  if (f.rows.bank) g.epilogue = MD_EPI_BIAS;  // GELU after the fc1 delta, in the expand
+  g.splitk_ws = w.splitk; g.splitk_ws_bytes = w.splitk_bytes; g.tile_policy = t_tile_policy;
+  f.rope_done = false;
+  if (f.rope_in_gemm) {
+    const md_rope_fuse rf = rope_fuse_args(f, l);
+    const md_status fs = md_gemm_qkv_rope(&g, &rf, f.s);
+    if (fs == MD_OK) f.rope_done = true;
+    else if (fs == MD_ERR_UNSUPPORTED) f.rope_in_gemm = false;  // a function of the shape: the same answer for every block
+    else return fs;
+  }
+  return f.rope_done ? MD_OK : md_gemm_bf16(&g, f.s);
+}
+
+// multi-LoRA: fc1 without its GELU (unfused packing), one shrink from l_in for the qkv / proj / fc1 pairs, and one expand
+// that adds the qkv and fc1 deltas and applies GELU to the fc1 columns (text.py:31-32; layers.py:130-137)
+md_status lora_qkv_fc1(Fwd& f, int l, const BlockIo& io) {
+  const md_text_block& b = f.m->blocks[l];
+  const TextWs& w = f.w;
+  const int pairs = MD_LORA_QKV | MD_LORA_PROJ | MD_LORA_FC1;
+  if (!io.packed) MD_TRY(gemm(w.h, f.Dp, b.fc1, w.ff, io.ffld, f.M, MD_EPI_BIAS, nullptr, 0, 0, 1, f.s, w.splitk, w.splitk_bytes));
+  MD_TRY(md_lora_shrink_grouped(f.rows.bank, l, pairs, f.rows.variant, f.batch, f.q_len, w.h, f.Dp, f.D, f.lw.t1, f.lw.ld1, f.s));
+  ExpandSeg sg[2] = {};
+  sg[0].t = sg[1].t = f.lw.t1;
+  sg[0].ldt = sg[1].ldt = f.lw.ld1;
+  sg[0].t_pairs = sg[1].t_pairs = pairs;
+  sg[0].pair = 0; sg[0].out = (bf16_t*)w.qkv; sg[0].ldo = io.qld; sg[0].n = f.qkv_w; sg[0].gelu_from = INT_MAX;
+  sg[1].pair = 2; sg[1].out = (bf16_t*)w.ff; sg[1].ldo = io.ffld; sg[1].n = b.fc1.n; sg[1].gelu_from = 0;
+  return lora_expand_segments(f.rows.bank, l, f.rows.variant, f.batch, f.q_len, sg, 2, f.s);
+}
+
+// multi-LoRA: the fc2 shrink from gelu(fc1), then ONE expand of the proj (from l_in's shrink: text.py:55) and fc2 deltas --
+// as deltas that the fused tail adds, or added to the two linears' outputs off the tail
+md_status lora_pair_deltas(Fwd& f, int l, const BlockIo& io, bool delta) {
+  const LoraBufs& lw = f.lw;
+  MD_TRY(md_lora_shrink_grouped(f.rows.bank, l, MD_LORA_FC2, f.rows.variant, f.batch, f.q_len, f.w.ff, io.ffld, f.m->blocks[l].fc2.k,
+                                lw.t2, lw.ld2, f.s));
+  ExpandSeg sg[2] = {};
+  sg[0].t = lw.t1; sg[0].ldt = lw.ld1; sg[0].t_pairs = MD_LORA_QKV | MD_LORA_PROJ | MD_LORA_FC1; sg[0].pair = 1;
+  sg[0].out = lw.d_proj;
+  sg[1].t = lw.t2; sg[1].ldt = lw.ld2; sg[1].t_pairs = MD_LORA_FC2; sg[1].pair = 3; sg[1].out = lw.d_fc2;
+  for (ExpandSeg& g : sg) {
+    g.ldo = f.D; g.n = f.D; g.gelu_from = INT_MAX; g.delta = delta ? 1 : 0;
+  }
+  return lora_expand_segments(f.rows.bank, l, f.rows.variant, f.batch, f.q_len, sg, 2, f.s);
+}
+
+// x = (x + proj(att)) + fc2(gelu(fc1(l_in)))   (text.py:53,157-158); decode regime: also the next block's ln(x)
+md_status proj_fc2_residual(Fwd& f, int l, const BlockIo& io) {
+  const md_text_model* m = f.m;
+  const md_text_block& b = m->blocks[l];
+  const TextWs& w = f.w;
+  const LoraBufs& lw = f.lw;
+  const int M = f.M, D = f.D, Dp = f.Dp;
+  const int64_t ffld = io.ffld;
+  const bool lora = f.rows.bank != nullptr;
+  bf16_t* x = f.x;
+  hipStream_t s = f.s;
+  if (f.tail_fused) {
+    // decode regime: both linears leave fp32 K-slice partials; ONE tail kernel sums them, applies
+    // bias / residual with the same roundings and writes the next block's ln(x)
+    const md_text_block_fp8* f8 = io.f8w;
+    int sl_a = md_gemm_partial_slices(&b.proj), sl_b = md_gemm_partial_slices(&b.fc2);
+    if (f8 && f8->proj.w && f8->fc2.w) {
+      MD_CHECK_ARG(md_gemm_fp8w_partial_slices(&f8->proj) <= sl_a && md_gemm_fp8w_partial_slices(&f8->fc2) <= sl_b);  // workspace is sized for the bf16 split
+      sl_a = md_gemm_fp8w_partial_slices(&f8->proj);
+      sl_b = md_gemm_fp8w_partial_slices(&f8->fc2);
+      MD_TRY(md_gemm_fp8w_partial_f32_pair(w.att, Dp, &f8->proj, w.part_a, w.ff, ffld, &f8->fc2, w.part_b, M, w.part_ld, w.part_stride, s));
+    } else {
+      MD_TRY(md_gemm_partial_f32_pair(w.att, Dp, &b.proj, w.part_a, w.ff, ffld, &b.fc2, w.part_b, M, w.part_ld, w.part_stride, s));
+    }
+    const bool last = (l + 1 == m->n_layers);
+    void* y = last ? nullptr : w.h;
+    const md_layernorm* ln = last ? nullptr : &m->blocks[l + 1].ln;
+    if (!lora)
+      return md_reduce_residual_layernorm(x, D, w.part_a, sl_a, b.proj.b, w.part_b, sl_b, b.fc2.b, w.part_ld, w.part_stride, y, Dp, ln,
+                                          M, D, 1e-5f, s);
+    MD_TRY(lora_pair_deltas(f, l, io, true));
+    return md_reduce_residual_layernorm_add(x, D, w.part_a, sl_a, b.proj.b, w.part_b, sl_b, b.fc2.b, w.part_ld, w.part_stride, y, Dp,
+                                            ln, M, D, 1e-5f, lw.d_proj, lw.d_fc2, D, s);
+  }
+  if (lora) {
+    // x = bf16(bf16(x + bf16(proj(att) + d_proj)) + bf16(fc2(h) + d_fc2))      (text.py:158)
+    MD_TRY(gemm(w.att, Dp, b.proj, lw.d_proj, D, M, MD_EPI_BIAS, nullptr, 0, 0, 0, s, w.splitk, w.splitk_bytes));
+    MD_TRY(gemm(w.ff, ffld, b.fc2, lw.d_fc2, D, M, MD_EPI_BIAS, nullptr, 0, 0, 0, s, w.splitk, w.splitk_bytes));
+    MD_TRY(lora_pair_deltas(f, l, io, false));
+    MD_TRY(md_add_bf16(x, D, lw.d_proj, D, x, D, M, D, s));
+    return md_add_bf16(x, D, lw.d_fc2, D, x, D, M, D, s);
+  }
+  MD_TRY(gemm(w.att, Dp, b.proj, x, D, M, MD_EPI_RESIDUAL, x, D, 0, 0, s, w.splitk, w.splitk_bytes));
+  return gemm(w.ff, ffld, b.fc2, x, D, M, MD_EPI_RESIDUAL, x, D, 0, 0, s, w.splitk, w.splitk_bytes);
+}
+
+// reference: text.py:128-160 (text_decoder) with text.py:16-60 (attn), for a prefill or for decode rows that the decode regime
+// takes in one pass.  rows.slots == nullptr: sequence b in slot b (md_text_forward); otherwise every place that addresses a
+// slab -- the RoPE / KV-write epilogue's row offsets, rope_kv_kernel, the prefill and decode attention, the e4m3 copy --
+// takes slot slots[b], and a decode row whose slot is outside [0, n_slots) is idle.  rows.pfx_slots != nullptr
+// (md_text_forward_shared): the prefill and decode attention read keys [0, pfx_len[b]) from slot pfx_slots[b]; every write
+// still goes to slot slots[b].
+md_status text_forward_rows(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len, const int32_t* pos0,
+                            const RowMap& rows_in, const md_kv_cache* kv, bool tall_ok, void* workspace, size_t workspace_bytes,
+                            hipStream_t s) {
+  Fwd f = {};
+  f.m = m; f.kv = kv; f.rows = rows_in; f.pos0 = pos0; f.batch = batch; f.q_len = q_len; f.s = s;
+  if (f.rows.slots == nullptr) f.rows.n_slots = batch;  // the slots a contiguous call addresses
+  const bool lora = f.rows.bank != nullptr;
+  const int hd = f.hd = m->dim / m->n_heads;
   if (hd != 64) return MD_ERR_UNSUPPORTED;
-  const TextWs w = text_layout(m, batch, q_len, workspace);
+  const TextWs& w = f.w = text_layout(m, batch, q_len, workspace);
   if (workspace_bytes < w.total) return MD_ERR_WORKSPACE;
   // multi-LoRA: its buffers after the base path's (whose layout stays as it is)
-  LoraBufs lw = {};
-  if (lc) {
-    lw = lora_bufs(m, lc->bank, (size_t)batch * q_len, (char*)workspace + w.total);
-    if (workspace_bytes < w.total + lw.total) return MD_ERR_WORKSPACE;
+  if (lora) {
+    f.lw = lora_bufs(m, f.rows.bank, (size_t)batch * q_len, (char*)workspace + w.total);
+    if (workspace_bytes < w.total + f.lw.total) return MD_ERR_WORKSPACE;
   }
-  hipStream_t s = (hipStream_t)stream;
-  const int D = m->dim, M = batch * q_len;
-  const int qkv_w = (m->n_heads + 2 * m->n_kv_heads) * hd;
-  const int Dp = m->blocks[0].qkv.k_pad;
+  const int D = f.D = m->dim, M = f.M = batch * q_len;
+  const int qkv_w = f.qkv_w = (m->n_heads + 2 * m->n_kv_heads) * hd;
+  const int Dp = f.Dp = m->blocks[0].qkv.k_pad;
   MD_CHECK_ARG(Dp >= D && m->blocks[0].proj.k_pad == Dp && m->blocks[0].fc1.k_pad == Dp);
   MD_TRY(zero_if_padded(w.h, M, Dp, D, s));
   MD_TRY(zero_if_padded(w.att, M, Dp, D, s));
-  bf16_t* x = (bf16_t*)hidden;
+  f.x = (bf16_t*)hidden;
   if (x_in != hidden) {
     if (hipMemcpyAsync(hidden, x_in, (size_t)M * D * 2, hipMemcpyDeviceToDevice, s) != hipSuccess)
       return MD_ERR_LAUNCH;
@@ -578,265 +749,127 @@ static md_status text_forward_impl(const md_text_model* m, const void* x_in, voi
   if (w.splitk_bytes) {
     MD_TRY(zero_fill(w.splitk, 8192, s));  // arrival tickets
   }
-  int32_t* kv_len = (int32_t*)w.pos_kv;
-  hipLaunchKernelGGL(kv_len_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, pos0, kv_len, q_len, batch);
-  const float scale = 1.0f / sqrtf((float)hd);
+  f.kv_len = (int32_t*)w.pos_kv;
+  hipLaunchKernelGGL(kv_len_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, pos0, f.kv_len, q_len, batch);
+  f.dec = DecodeAttn{w.qkv, 0, w.att, Dp, m->freqs, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, kv->batch_stride, kv->ctx, f.kv_len,
+                     batch, m->n_heads, m->n_kv_heads, hd, m->rot_dim, 1.0f / sqrtf((float)hd), false};
   // decode regime (<= 64 rows): launch-boundary split-K for proj / fc2 + fused block tail.
   // A function of the row count only, like the choice of GEMM kernel.  MD_TEXT_TAIL=0: A/B runs.
   static const bool tail_allowed = [] { const char* e = getenv("MD_TEXT_TAIL"); return !(e && e[0] == '0'); }();
   const bool tall = tall_ok && decode_tall_rows(m, M, q_len);   // 65 .. 128 rows of a decode step: one pass (decode_tall_model)
-  const bool tail_fused = tail_allowed && (M <= 64 || tall) && D % 8 == 0 && m->blocks[0].proj.b && m->blocks[0].fc2.b &&
-                          m->blocks[0].proj.n == D && m->blocks[0].fc2.n == D;
+  f.tail_fused = tail_allowed && (M <= 64 || tall) && D % 8 == 0 && m->blocks[0].proj.b && m->blocks[0].fc2.b &&
+                 m->blocks[0].proj.n == D && m->blocks[0].fc2.n == D;
   TilePolicyScope tall_scope(tall ? MD_TILE_DECODE_TALL : t_tile_policy);
 
   // Prefill: RoPE + KV write in the epilogue of the fused qkv|fc1 GEMM (MD_EPI_QKV_ROPE) when the four-wave kernel takes the
   // shape: MHA, head_dim 64, rot_dim 32, slab offsets in 32 bits.  Per-row positions / slab offsets once per forward.
-  const uint64_t slab_bytes = (uint64_t)kv->layer_stride * 2;
-  bool rope_in_gemm = w.rope_cs != nullptr && q_len > 1 && M > 64 && m->n_kv_heads == m->n_heads && hd == 64 && m->rot_dim == 32 &&
-                      m->blocks[0].qkv_fc1.w != nullptr && slab_bytes < 0xfffff000ull && kv->layer_stride >= (int64_t)n_slots * kv->batch_stride &&
-                      lc == nullptr;
-  if (rope_in_gemm)
+  f.slab_bytes = (uint64_t)kv->layer_stride * 2;
+  f.rope_in_gemm = w.rope_cs != nullptr && q_len > 1 && M > 64 && m->n_kv_heads == m->n_heads && hd == 64 && m->rot_dim == 32 &&
+                   m->blocks[0].qkv_fc1.w != nullptr && f.slab_bytes < 0xfffff000ull &&
+                   kv->layer_stride >= (int64_t)f.rows.n_slots * kv->batch_stride && !lora;
+  if (f.rope_in_gemm)
     hipLaunchKernelGGL(rope_rowinfo_kernel, dim3((M + 7) / 8), dim3(256), 0, s, pos0, m->freqs, w.rope_cs, w.rope_kv, q_len, M,
-                       kv->batch_stride, hd, m->rot_dim, slots);
-  bool rope_done = false;  // set per block when the fused launch took it
-  bool rope_done_kv8 = false;  // ... and also wrote the e4m3 copy of the rows (fp8 mode)
+                       kv->batch_stride, hd, m->rot_dim, f.rows.slots);
 
-  // rope(q), rope(k), cache update (text.py:42-46) and attention over the slab (text.py:48-51) of block l
-  auto rope_and_attention = [&](int l, int64_t qld, bool fuse_rope, uint8_t* att8 = nullptr, float att8_inv_scale = 0.f) -> md_status {
-    bf16_t* kl = (bf16_t*)kv->k + (int64_t)l * kv->layer_stride;
-    bf16_t* vl = (bf16_t*)kv->v + (int64_t)l * kv->layer_stride;
-    if (!fuse_rope && !rope_done)
-      MD_TRY(md_rope_kv_write_slots(w.qkv, qld, m->freqs, pos0, kl, vl, kv->batch_stride, kv->ctx, batch,
-                                    q_len, m->n_heads, m->n_kv_heads, hd, m->rot_dim, slots, n_slots, s));
-    // attention over the slab                                   (text.py:48-51)
-    const bool kv8 = kv->k8 && kv->v8 && kv->k_scale && kv->v_scale && m->n_kv_heads == m->n_heads && hd == 64;
-    if (fuse_rope && kv8) {
-      // fp8 mode: the step attends over the e4m3 copy of the cache and writes the new row into both copies
-      MD_TRY(md_attention_decode_rope_f8_launch(w.qkv, qld, w.att, Dp, m->freqs, kl, vl, (uint8_t*)kv->k8 + (int64_t)l * kv->layer_stride,
-                                                (uint8_t*)kv->v8 + (int64_t)l * kv->layer_stride, kv->batch_stride, kv->ctx, kv_len, batch,
-                                                m->n_heads, m->rot_dim, scale, kv->k_scale[l], kv->v_scale[l], s, slots, n_slots));
-    } else if (pfx_slots != nullptr && q_len == 1) {
-      // shared prefix: the grouped decode kernel (FUSED: with RoPE and the new row's K / V write, as below)
-      MD_TRY(md_attention_decode_shared_any(fuse_rope, w.qkv, qld, w.att, Dp, m->freqs, kl, vl, kv->batch_stride, kv->ctx, kv_len,
-                                            batch, m->n_heads, m->n_kv_heads, hd, m->rot_dim, scale, slots, n_slots, pfx_slots,
-                                            pfx_len, s));
-    } else if (fuse_rope) {
-      MD_TRY(md_attention_decode_rope_slots(w.qkv, qld, w.att, Dp, m->freqs, kl, vl, kv->batch_stride, kv->ctx, kv_len,
-                                            batch, m->n_heads, hd, m->rot_dim, scale, slots, n_slots, s));
-    } else if (q_len == 1) {
-      MD_TRY(md_attention_decode_slots(w.qkv, qld, w.att, Dp, kl, vl, kv->batch_stride, kv->ctx, kv_len, batch,
-                                       m->n_heads, m->n_kv_heads, hd, scale, slots, n_slots, s));
-    } else {
-      md_attn_args a = {};
-      a.q = w.qkv;
-      a.q_bs = (int64_t)q_len * qld;
-      a.q_ts = qld;
-      a.q_hs = hd;
-      a.k = kl;
-      a.v = vl;
-      a.k_bs = a.v_bs = kv->batch_stride;
-      a.k_ts = a.v_ts = hd;
-      a.k_hs = a.v_hs = (int64_t)kv->ctx * hd;
-      a.o = w.att;
-      a.o_bs = (int64_t)q_len * Dp;
-      a.o_ts = Dp;
-      a.o_hs = hd;
-      a.batch = batch;
-      a.n_heads = m->n_heads;
-      a.n_kv_heads = m->n_kv_heads;
-      a.head_dim = hd;
-      a.q_len = q_len;
-      a.kv_len_all = 0;
-      a.q_pos0 = pos0;
-      a.kv_len = kv_len;
-      a.prefix_len = m->prefix_len;
-      a.scale = scale;
-      if (att8 != nullptr) {  // fp8 mode: proj reads e4m3 rows only -- written by the attention epilogue, no bf16 copy, no quantise pass
-        a.o = nullptr;
-        a.o8 = att8;
-        a.o8_bs = (int64_t)q_len * Dp;
-        a.o8_ts = Dp;
-        a.o8_inv_scale = att8_inv_scale;
-      }
-      MD_TRY(pfx_slots ? md_attention_prefill_shared(&a, slots, pfx_slots, pfx_len, n_slots, s) : md_attention_prefill_slots(&a, slots, s));
-    }
-    // fp8 mode: the rows this pass wrote (bf16) also go into the e4m3 copy the decode steps read
-    if (kv8 && !fuse_rope && !rope_done_kv8) MD_TRY(md_kv_quantize_f8_layer(kv, l, pos0, 0, batch, m->n_heads, q_len, s, slots, n_slots));
-    return MD_OK;
-  };
-
-  // FP8 prefill (opt-in, md_text_f8): launches of more than 64 rows with the fused qkv|fc1 packing
-  const md_text_f8* f8p = m->f8;
-  float* calib = (f8p && M > 64) ? f8p->calib : nullptr;  // calibration records the PREFILL's activation ranges
-  const bool use_f8 = f8p && !f8p->calib && f8p->blocks && M > 64 && m->blocks[0].qkv_fc1.w != nullptr && qkv_w % 64 == 0;
-  if (lc && (use_f8 || calib)) return MD_ERR_UNSUPPORTED;
+  f.f8p = m->f8;
+  f.calib = (f.f8p && M > 64) ? f.f8p->calib : nullptr;  // calibration records the PREFILL's activation ranges
+  f.use_f8 = f.f8p && !f.f8p->calib && f.f8p->blocks && M > 64 && m->blocks[0].qkv_fc1.w != nullptr && qkv_w % 64 == 0;
+  if (lora && (f.use_f8 || f.calib)) return MD_ERR_UNSUPPORTED;
+  const bool fuse_rope = (q_len == 1) && (m->n_kv_heads == m->n_heads);  // decode step: rope + KV write inside attention
 
   for (int l = 0; l < m->n_layers; ++l) {
     const md_text_block& b = m->blocks[l];
-    if (use_f8) {
-      const md_text_block_f8& q = f8p->blocks[l];
-      const int64_t qld = b.qkv_fc1.n_pad;
-      MD_CHECK_ARG(f8_scales_ok(q.s_ln, q.s_att, q.s_ff) && q.qkv_fc1.n_pad == b.qkv_fc1.n_pad && q.qkv_fc1.k_pad == Dp &&
-                   q.fc2.k_pad == b.fc1.n_pad && q.proj.k_pad == Dp && b.qkv_fc1.n_pad == qkv_w + b.fc1.n_pad);
-      // fp8 activations: ln(x) / the attention output in the (bf16-sized) h buffer, gelu(fc1) in the fc1 columns' own
-      // (bf16-sized) slots of the fused activation rows
-      uint8_t* h8 = (uint8_t*)w.h;
-      uint8_t* ff8 = (uint8_t*)w.qkv + (size_t)qkv_w * 2;
-      MD_TRY(md_layernorm_f8(x, D, h8, Dp, &b.ln, M, D, Dp, 1e-5f, 1.0f / q.s_ln, s));
-      // [qkv | gelu(fc1) -> e4m3]; with per-row positions at hand the epilogue also rotates q / k and writes k / v to the
-      // slab and to its e4m3 copy (MD_EPI_QKV_ROPE, as the bf16 kernel does): no rope_kv_kernel, no kv-quantise pass
-      rope_done = rope_done_kv8 = false;
-      if (rope_in_gemm) {
-        md_gemm_f8_args g;
-        g.a = h8; g.lda = Dp; g.a_scale = q.s_ln; g.lin = q.qkv_fc1; g.c = w.qkv; g.ldc = qld;
-        g.c8 = ff8; g.ldc8 = qld * 2; g.c8_inv_scale = 1.0f / q.s_ff; g.f8_from_col = qkv_w;
-        g.r = nullptr; g.ldr = 0; g.res_row_mod = 0; g.m = M; g.epilogue = MD_EPI_GELU; g.store_pad_cols = 1; g.gelu_from_col = qkv_w;
-        md_rope_fuse rf;
-        rf.row_cs = w.rope_cs; rf.row_kv = w.rope_kv;
-        rf.kslab = (bf16_t*)kv->k + (int64_t)l * kv->layer_stride;
-        rf.vslab = (bf16_t*)kv->v + (int64_t)l * kv->layer_stride;
-        rf.slab_bytes = slab_bytes; rf.n_heads = m->n_heads; rf.ctx = kv->ctx;
-        md_rope_fuse_f8 rf8 = {nullptr, nullptr, 1.f, 1.f};
-        const bool has8 = kv->k8 && kv->v8 && kv->k_scale && kv->v_scale;
-        if (has8) {
-          rf8.k8slab = (uint8_t*)kv->k8 + (int64_t)l * kv->layer_stride;
-          rf8.v8slab = (uint8_t*)kv->v8 + (int64_t)l * kv->layer_stride;
-          rf8.k_scale = kv->k_scale[l];
-          rf8.v_scale = kv->v_scale[l];
-        }
-        const md_status fs = md_gemm_f8_qkv_rope(&g, &rf, &rf8, s);
-        if (fs == MD_OK) {
-          rope_done = true;
-          rope_done_kv8 = has8;
-        } else if (fs != MD_ERR_UNSUPPORTED) {
-          return fs;
-        }
-      }
-      if (!rope_done)
-        MD_TRY(gemm_f8(h8, Dp, q.s_ln, q.qkv_fc1, w.qkv, qld, M, MD_EPI_GELU, nullptr, 0, 0, 1, s, ff8, qld * 2, q.s_ff, qkv_w, qkv_w));
-      if (q_len > 1 && Dp == D) {
-        MD_TRY(rope_and_attention(l, qld, false, h8, 1.0f / q.s_att));
-      } else {
-        MD_TRY(rope_and_attention(l, qld, false));
-        MD_TRY(md_quantize_f8(w.att, Dp, h8, Dp, M, D, Dp, 1.0f / q.s_att, s));
-      }
-      MD_TRY(gemm_f8(h8, Dp, q.s_att, q.proj, x, D, M, MD_EPI_RESIDUAL, x, D, 0, 0, s));
-      MD_TRY(gemm_f8(ff8, qld * 2, q.s_ff, q.fc2, x, D, M, MD_EPI_RESIDUAL, x, D, 0, 0, s));
+    if (f.use_f8) {
+      MD_TRY(f8_prefill_block(f, l));
       continue;
     }
+    const BlockIo io = block_io(f, l);
     // l_in = ln(x)                                            (text.py:145)
     // (decode regime: blocks > 0 get it from the previous block's tail kernel)
-    if (!tail_fused || l == 0) MD_TRY(md_layernorm_bf16(x, D, w.h, Dp, &b.ln, M, D, 1e-5f, s));
-    MD_TRY(calib_site(calib, 3 * l + 0, w.h, Dp, M, D, s));
-    // qkv, rope(q), rope(k), cache update                      (text.py:30-46)
-    const bool fused = b.qkv_fc1.w != nullptr;
-    const int64_t qld = fused ? b.qkv_fc1.n_pad : qkv_w;  // leading dimension of the qkv activation
-    const int64_t ffld = fused ? b.qkv_fc1.n_pad : b.fc1.n_pad;
-    // decode regime with FP8 weight copies attached (opt-in): the same three launches over half the bytes
-    const md_text_block_fp8* f8 = (m->fp8 && m->fp8->blocks && tail_fused && fused) ? &m->fp8->blocks[l] : nullptr;
-    if (lc && f8) return MD_ERR_UNSUPPORTED;
-    if (f8 && f8->qkv_fc1.w) {
-      MD_CHECK_ARG(f8->qkv_fc1.n_pad == b.qkv_fc1.n_pad && qkv_w % 64 == 0);
-      MD_TRY(md_gemm_fp8w(w.h, Dp, &f8->qkv_fc1, w.qkv, qld, M, MD_EPI_GELU, 1, qkv_w, s));
-    } else if (fused) {
-      // one GEMM for both consumers of l_in: [qkv | gelu(fc1)]   (text.py:30 and layers.py:130-138)
-      MD_CHECK_ARG(b.qkv_fc1.n_pad == qkv_w + b.fc1.n_pad && qkv_w % 64 == 0);
-      md_gemm_args g;
-      g.a = w.h; g.lda = Dp; g.lin = b.qkv_fc1; g.c = w.qkv; g.ldc = qld; g.r = nullptr; g.ldr = 0;
-      g.res_row_mod = 0; g.m = M; g.epilogue = MD_EPI_GELU; g.store_pad_cols = 1; g.gelu_from_col = qkv_w;
-      if (lc) g.epilogue = MD_EPI_BIAS;  // GELU after the fc1 delta, in the expand
-      g.splitk_ws = w.splitk; g.splitk_ws_bytes = w.splitk_bytes; g.tile_policy = t_tile_policy;
-      rope_done = false;
-      if (rope_in_gemm) {
-        md_rope_fuse rf;
-        rf.row_cs = w.rope_cs; rf.row_kv = w.rope_kv;
-        rf.kslab = (bf16_t*)kv->k + (int64_t)l * kv->layer_stride;
-        rf.vslab = (bf16_t*)kv->v + (int64_t)l * kv->layer_stride;
-        rf.slab_bytes = slab_bytes; rf.n_heads = m->n_heads; rf.ctx = kv->ctx;
-        const md_status fs = md_gemm_qkv_rope(&g, &rf, s);
-        if (fs == MD_OK) rope_done = true;
-        else if (fs == MD_ERR_UNSUPPORTED) rope_in_gemm = false;  // a function of the shape: the same answer for every block
-        else return fs;
-      }
-      if (!rope_done) MD_TRY(md_gemm_bf16(&g, s));
-    } else {
-      MD_TRY(gemm(w.h, Dp, b.qkv, w.qkv, qkv_w, M, MD_EPI_BIAS, nullptr, 0, 0, 0, s, w.splitk, w.splitk_bytes));
-    }
-    if (lc) {
-      // multi-LoRA: fc1 without its GELU (unfused packing), one shrink from l_in for the qkv / proj / fc1 pairs, and one expand
-      // that adds the qkv and fc1 deltas and applies GELU to the fc1 columns (text.py:31-32; layers.py:130-137)
-      if (!fused) MD_TRY(gemm(w.h, Dp, b.fc1, w.ff, ffld, M, MD_EPI_BIAS, nullptr, 0, 0, 1, s, w.splitk, w.splitk_bytes));
-      MD_TRY(md_lora_shrink_grouped(lc->bank, l, MD_LORA_QKV | MD_LORA_PROJ | MD_LORA_FC1, lc->variant, batch, q_len, w.h, Dp, D,
-                                    lw.t1, lw.ld1, s));
-      ExpandSeg sg[2] = {};
-      sg[0].t = sg[1].t = lw.t1;
-      sg[0].ldt = sg[1].ldt = lw.ld1;
-      sg[0].t_pairs = sg[1].t_pairs = MD_LORA_QKV | MD_LORA_PROJ | MD_LORA_FC1;
-      sg[0].pair = 0; sg[0].out = (bf16_t*)w.qkv; sg[0].ldo = qld; sg[0].n = qkv_w; sg[0].gelu_from = INT_MAX;
-      sg[1].pair = 2; sg[1].out = (bf16_t*)w.ff; sg[1].ldo = ffld; sg[1].n = b.fc1.n; sg[1].gelu_from = 0;
-      MD_TRY(lora_expand_segments(lc->bank, l, lc->variant, batch, q_len, sg, 2, s));
-    }
-    const bool fuse_rope = (q_len == 1) && (m->n_kv_heads == m->n_heads);  // decode step: rope + KV write inside attention
-    MD_TRY(rope_and_attention(l, qld, fuse_rope));
-    MD_TRY(calib_site(calib, 3 * l + 1, w.att, Dp, M, D, s));
-    // x = (x + proj(att)) + fc2(gelu(fc1(l_in)))               (text.py:53,157-158)
-    if (!fused && !lc)
-      MD_TRY(gemm(w.h, Dp, b.fc1, w.ff, ffld, M, MD_EPI_GELU, nullptr, 0, 0, 1, s, w.splitk, w.splitk_bytes));
-    // multi-LoRA: the fc2 shrink from gelu(fc1), then ONE expand of the proj (from l_in's shrink: text.py:55) and fc2 deltas --
-    // as deltas that the fused tail adds, or added to the two linears' outputs off the tail
-    auto lora_pair_deltas = [&](bool delta) -> md_status {
-      MD_TRY(md_lora_shrink_grouped(lc->bank, l, MD_LORA_FC2, lc->variant, batch, q_len, w.ff, ffld, b.fc2.k, lw.t2, lw.ld2, s));
-      ExpandSeg sg[2] = {};
-      sg[0].t = lw.t1; sg[0].ldt = lw.ld1; sg[0].t_pairs = MD_LORA_QKV | MD_LORA_PROJ | MD_LORA_FC1; sg[0].pair = 1;
-      sg[0].out = lw.d_proj;
-      sg[1].t = lw.t2; sg[1].ldt = lw.ld2; sg[1].t_pairs = MD_LORA_FC2; sg[1].pair = 3; sg[1].out = lw.d_fc2;
-      for (ExpandSeg& g : sg) {
-        g.ldo = D; g.n = D; g.gelu_from = INT_MAX; g.delta = delta ? 1 : 0;
-      }
-      return lora_expand_segments(lc->bank, l, lc->variant, batch, q_len, sg, 2, s);
-    };
-    MD_TRY(calib_site(calib, 3 * l + 2, w.ff, ffld, M, b.fc1.n, s));
+    if (!f.tail_fused || l == 0) MD_TRY(md_layernorm_bf16(f.x, D, w.h, Dp, &b.ln, M, D, 1e-5f, s));
+    MD_TRY(calib_site(f.calib, 3 * l + 0, w.h, Dp, M, D, s));
+    // qkv, rope(q), rope(k), cache update, attention           (text.py:30-51)
+    if (lora && io.f8w) return MD_ERR_UNSUPPORTED;
+    MD_TRY(qkv_linear(f, l, io));
+    if (lora) MD_TRY(lora_qkv_fc1(f, l, io));
+    MD_TRY(rope_and_attention(f, l, io.qld, fuse_rope));
+    MD_TRY(calib_site(f.calib, 3 * l + 1, w.att, Dp, M, D, s));
+    // gelu(fc1(l_in)) where the qkv GEMM (or the LoRA expand) has not produced it already     (layers.py:130-138)
+    if (!io.packed && !lora)
+      MD_TRY(gemm(w.h, Dp, b.fc1, w.ff, io.ffld, M, MD_EPI_GELU, nullptr, 0, 0, 1, s, w.splitk, w.splitk_bytes));
+    MD_TRY(calib_site(f.calib, 3 * l + 2, w.ff, io.ffld, M, b.fc1.n, s));
     MD_CHECK_ARG(b.fc2.k_pad == b.fc1.n_pad);
-    if (tail_fused) {
-      // decode regime: both linears leave fp32 K-slice partials; ONE tail kernel sums them, applies
-      // bias / residual with the same roundings and writes the next block's ln(x)
-      const bool f8_tail = f8 && f8->proj.w && f8->fc2.w;
-      int sl_a = md_gemm_partial_slices(&b.proj), sl_b = md_gemm_partial_slices(&b.fc2);
-      if (f8_tail) {
-        MD_CHECK_ARG(md_gemm_fp8w_partial_slices(&f8->proj) <= sl_a && md_gemm_fp8w_partial_slices(&f8->fc2) <= sl_b);  // workspace is sized for the bf16 split
-        sl_a = md_gemm_fp8w_partial_slices(&f8->proj);
-        sl_b = md_gemm_fp8w_partial_slices(&f8->fc2);
-        MD_TRY(md_gemm_fp8w_partial_f32_pair(w.att, Dp, &f8->proj, w.part_a, w.ff, ffld, &f8->fc2, w.part_b, M, w.part_ld,
-                                             w.part_stride, s));
-      } else {
-        MD_TRY(md_gemm_partial_f32_pair(w.att, Dp, &b.proj, w.part_a, w.ff, ffld, &b.fc2, w.part_b, M, w.part_ld,
-                                        w.part_stride, s));
-      }
-      const bool last = (l + 1 == m->n_layers);
-      if (lc) {
-        MD_TRY(lora_pair_deltas(true));
-        MD_TRY(md_reduce_residual_layernorm_add(x, D, w.part_a, sl_a, b.proj.b, w.part_b, sl_b, b.fc2.b, w.part_ld, w.part_stride,
-                                                last ? nullptr : w.h, Dp, last ? nullptr : &m->blocks[l + 1].ln, M, D, 1e-5f,
-                                                lw.d_proj, lw.d_fc2, D, s));
-        continue;
-      }
-      MD_TRY(md_reduce_residual_layernorm(x, D, w.part_a, sl_a, b.proj.b, w.part_b,
-                                          sl_b, b.fc2.b, w.part_ld, w.part_stride,
-                                          last ? nullptr : w.h, Dp, last ? nullptr : &m->blocks[l + 1].ln, M, D,
-                                          1e-5f, s));
-    } else if (lc) {
-      // x = bf16(bf16(x + bf16(proj(att) + d_proj)) + bf16(fc2(h) + d_fc2))      (text.py:158)
-      MD_TRY(gemm(w.att, Dp, b.proj, lw.d_proj, D, M, MD_EPI_BIAS, nullptr, 0, 0, 0, s, w.splitk, w.splitk_bytes));
-      MD_TRY(gemm(w.ff, ffld, b.fc2, lw.d_fc2, D, M, MD_EPI_BIAS, nullptr, 0, 0, 0, s, w.splitk, w.splitk_bytes));
-      MD_TRY(lora_pair_deltas(false));
-      MD_TRY(md_add_bf16(x, D, lw.d_proj, D, x, D, M, D, s));
-      MD_TRY(md_add_bf16(x, D, lw.d_fc2, D, x, D, M, D, s));
-    } else {
-      MD_TRY(gemm(w.att, Dp, b.proj, x, D, M, MD_EPI_RESIDUAL, x, D, 0, 0, s, w.splitk, w.splitk_bytes));
-      MD_TRY(gemm(w.ff, ffld, b.fc2, x, D, M, MD_EPI_RESIDUAL, x, D, 0, 0, s, w.splitk, w.splitk_bytes));
-    }
+    MD_TRY(proj_fc2_residual(f, l, io));
   }
   return MD_OK;
+}
+
+// the slab base moved by b0 slots: the rows [b0, ...) of a contiguous call (no slot table)
+md_kv_cache kv_from_slot(const md_kv_cache* kv, int b0) {
+  md_kv_cache sub = *kv;
+  sub.k = (char*)kv->k + (int64_t)b0 * kv->batch_stride * 2;
+  sub.v = (char*)kv->v + (int64_t)b0 * kv->batch_stride * 2;
+  if (kv->k8) sub.k8 = (char*)kv->k8 + (int64_t)b0 * kv->batch_stride;
+  if (kv->v8) sub.v8 = (char*)kv->v8 + (int64_t)b0 * kv->batch_stride;
+  return sub;
+}
+
+// The decoder over the rows of one call.  A decode step over more sequences than the decode regime takes in one pass runs as
+// blocks of 64 (128: decode_tall_model) rows, each through the decode-regime kernels (weight-streaming GEMMs, launch-boundary
+// split-K, fused block tail).  The weights are streamed once per block; the big-tile kernels this replaces ran the step
+// ~1.5x slower at 128 rows.  With a slot table the slab base stays and the block takes its own entries of every table
+// (RowMap::block); without one the slab base moves.
+md_status text_forward_impl(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len, const int32_t* pos0,
+                            const RowMap& rows, const md_kv_cache* kv, void* workspace, size_t workspace_bytes, void* stream) {
+  MD_CHECK_ARG(m && x_in && hidden && pos0 && kv && kv->k && kv->v && workspace && m->blocks);
+  MD_CHECK_ARG(batch > 0 && q_len > 0 && m->dim % m->n_heads == 0);
+  MD_CHECK_ARG(rows.slots == nullptr || rows.n_slots > 0);
+  MD_CHECK_ARG(tile_policy_ok(m->tile_policy));
+  TilePolicyScope tile_scope(m->tile_policy);
+  hipStream_t s = (hipStream_t)stream;
+  // the e4m3 copy of the KV cache (fp8 mode) keeps the 64-row blocks: its attention kernel is part of an opt-in mode tuned there
+  const bool tall_ok = decode_tall_model(m) && !(kv->k8 && kv->v8);
+  const int block_rows = (q_len == 1) ? (tall_ok ? 128 : 64) : batch;
+  for (int b0 = 0; b0 < batch; b0 += block_rows) {
+    const int nb = std::min(block_rows, batch - b0);
+    const md_kv_cache sub = kv_from_slot(kv, rows.slots ? 0 : b0);
+    MD_TRY(text_forward_rows(m, (const char*)x_in + (int64_t)b0 * m->dim * 2, (char*)hidden + (int64_t)b0 * m->dim * 2, nb, q_len,
+                             pos0 + b0, rows.block(b0), &sub, tall_ok, workspace, workspace_bytes, s));
+  }
+  return MD_OK;
+}
+
+// the checks of the shared-prefix entry points that need no device: a table needs the slot table, and the e4m3 KV copy (fp8
+// mode) is not supported with one
+md_status shared_args_ok(const md_kv_cache* kv, const RowMap& rows) {
+  MD_CHECK_ARG(kv && kv->k8 == nullptr && kv->v8 == nullptr);
+  MD_CHECK_ARG(rows.slots == nullptr || rows.n_slots > 0);  // as md_text_forward_slots
+  MD_CHECK_ARG(rows.pfx_slots == nullptr || (rows.slots != nullptr && rows.pfx_len != nullptr));
+  return MD_OK;
+}
+
+}  // namespace
+
+extern "C" md_status md_text_forward(const md_text_model* m, const void* x_in, void* hidden,
+                                     int32_t batch, int32_t q_len, const int32_t* pos0,
+                                     const md_kv_cache* kv, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  return md_text_forward_slots(m, x_in, hidden, batch, q_len, pos0, nullptr, 0, kv, workspace, workspace_bytes, stream);
+}
+
+extern "C" md_status md_text_forward_slots(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
+                                           const int32_t* pos0, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  return text_forward_impl(m, x_in, hidden, batch, q_len, pos0, RowMap{slots, n_slots}, kv, workspace, workspace_bytes, stream);
+}
+
+extern "C" md_status md_text_forward_shared(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len,
+                                            const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
+                                            const int32_t* prefix_len, const md_kv_cache* kv, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  const RowMap rows{slots, n_slots, prefix_slots, prefix_len};
+  MD_TRY(shared_args_ok(kv, rows));
+  return text_forward_impl(m, x_in, hidden, batch, q_len, pos0, rows, kv, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------- LoRA side path
@@ -912,12 +945,7 @@ extern "C" md_status md_text_forward_lora(const md_text_model* m, const md_text_
       MD_TRY(md_attention_decode(w.qkv, qkv_w, w.att, D, kl, vl, kv->batch_stride, kv->ctx, kv_len, batch, m->n_heads,
                                  m->n_kv_heads, hd, scale, s));
     } else {
-      md_attn_args a = {};
-      a.q = w.qkv; a.q_bs = (int64_t)q_len * qkv_w; a.q_ts = qkv_w; a.q_hs = hd;
-      a.k = kl; a.v = vl; a.k_bs = a.v_bs = kv->batch_stride; a.k_ts = a.v_ts = hd; a.k_hs = a.v_hs = (int64_t)kv->ctx * hd;
-      a.o = w.att; a.o_bs = (int64_t)q_len * D; a.o_ts = D; a.o_hs = hd;
-      a.batch = batch; a.n_heads = m->n_heads; a.n_kv_heads = m->n_kv_heads; a.head_dim = hd; a.q_len = q_len;
-      a.kv_len_all = 0; a.q_pos0 = pos0; a.kv_len = kv_len; a.prefix_len = m->prefix_len; a.scale = scale;
+      const md_attn_args a = prefill_attn_args(m, kv, l, w.qkv, qkv_w, w.att, D, batch, q_len, pos0, kv_len);
       MD_TRY(md_attention_prefill(&a, s));
     }
     MD_TRY(gemm(w.att, D, b.proj, w.d1, D, M, MD_EPI_BIAS, nullptr, 0, 0, 0, s));                        // text.py:53
@@ -971,37 +999,13 @@ extern "C" md_status md_decode_step(const md_text_model* m, const int32_t* token
                               workspace_bytes, stream);
 }
 
+// reference: the generator loop body of moondream.py:512-530, device resident; the rows as in text_forward_impl
 static md_status decode_step_impl(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos, int32_t batch,
-                                  const int32_t* slots, int32_t n_slots, const int32_t* pfx_slots, const int32_t* pfx_len,
-                                  const md_kv_cache* kv, int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
-                                  size_t workspace_bytes, void* stream, const LoraCall* lc = nullptr);
-
-extern "C" md_status md_decode_step_slots(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos,
-                                          int32_t batch, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
-                                          int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
-                                          size_t workspace_bytes, void* stream) {
-  return decode_step_impl(m, tokens, next, pos, batch, slots, n_slots, nullptr, nullptr, kv, suppress_id, logits, ld_logits, workspace,
-                          workspace_bytes, stream);
-}
-
-extern "C" md_status md_decode_step_shared(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos,
-                                           int32_t batch, const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
-                                           const int32_t* prefix_len, const md_kv_cache* kv, int32_t suppress_id, void* logits,
-                                           int64_t ld_logits, void* workspace, size_t workspace_bytes, void* stream) {
-  MD_TRY(shared_args_ok(kv, slots, n_slots, prefix_slots, prefix_len));
-  return decode_step_impl(m, tokens, next, pos, batch, slots, n_slots, prefix_slots, prefix_len, kv, suppress_id, logits, ld_logits,
-                          workspace, workspace_bytes, stream);
-}
-
-// reference: the generator loop body of moondream.py:512-530, device resident; slots as in md_text_forward_slots, the prefix
-// table as in md_text_forward_shared
-static md_status decode_step_impl(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos, int32_t batch,
-                                  const int32_t* slots, int32_t n_slots, const int32_t* pfx_slots, const int32_t* pfx_len,
-                                  const md_kv_cache* kv, int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
-                                  size_t workspace_bytes, void* stream, const LoraCall* lc) {
+                                  const RowMap& rows, const md_kv_cache* kv, int32_t suppress_id, void* logits, int64_t ld_logits,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
   MD_CHECK_ARG(m && tokens && next && pos && kv && logits && workspace && batch > 0);
-  MD_CHECK_ARG(slots == nullptr || n_slots > 0);
-  if (workspace_bytes < (lc ? md_decode_multi_lora_workspace_bytes(m, lc->bank, batch) : md_decode_workspace_bytes(m, batch)))
+  MD_CHECK_ARG(rows.slots == nullptr || rows.n_slots > 0);
+  if (workspace_bytes < (rows.bank ? md_decode_multi_lora_workspace_bytes(m, rows.bank, batch) : md_decode_workspace_bytes(m, batch)))
     return MD_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   Arena a{(char*)workspace, 0};
@@ -1010,7 +1014,7 @@ static md_status decode_step_impl(const md_text_model* m, const int32_t* tokens,
   void* tws = a.take(0);
   const size_t tws_bytes = workspace_bytes - a.off;
   MD_TRY(md_embed_tokens(tokens, m->wte, m->dim, x, m->dim, batch, m->dim, s));
-  MD_TRY(text_forward_impl(m, x, x, batch, 1, pos, slots, n_slots, pfx_slots, pfx_len, kv, tws, tws_bytes, s, lc));
+  MD_TRY(text_forward_impl(m, x, x, batch, 1, pos, rows, kv, tws, tws_bytes, s));
   if (decode_tall_rows(m, batch, 1) && !(kv->k8 && kv->v8)) {
     // the step's lm_head at 65 .. 128 rows: the by-shape config of the same MFMA family as the <= 64-row regime (never the
     // pinned four-wave kernel: a sequence must get the same logits in a step of 128 as in a step of 64)
@@ -1023,14 +1027,30 @@ static md_status decode_step_impl(const md_text_model* m, const int32_t* tokens,
   return md_argmax_advance(logits, ld_logits, batch, m->vocab, suppress_id, next, pos, s);
 }
 
+extern "C" md_status md_decode_step_slots(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos,
+                                          int32_t batch, const int32_t* slots, int32_t n_slots, const md_kv_cache* kv,
+                                          int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  return decode_step_impl(m, tokens, next, pos, batch, RowMap{slots, n_slots}, kv, suppress_id, logits, ld_logits, workspace,
+                          workspace_bytes, stream);
+}
+
+extern "C" md_status md_decode_step_shared(const md_text_model* m, const int32_t* tokens, int32_t* next, int32_t* pos,
+                                           int32_t batch, const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
+                                           const int32_t* prefix_len, const md_kv_cache* kv, int32_t suppress_id, void* logits,
+                                           int64_t ld_logits, void* workspace, size_t workspace_bytes, void* stream) {
+  const RowMap rows{slots, n_slots, prefix_slots, prefix_len};
+  MD_TRY(shared_args_ok(kv, rows));
+  return decode_step_impl(m, tokens, next, pos, batch, rows, kv, suppress_id, logits, ld_logits, workspace, workspace_bytes, stream);
+}
+
 // ------------------------------------------------------------- mixed LoRA variants (csrc/lora_multi.hip)
 // the checks that need no device; the fp8 modes (weight copies, e4m3 KV copy) are not served with a bank
-static md_status multi_lora_args_ok(const md_text_model* m, const md_lora_bank* bank, const int32_t* variant, int32_t batch,
-                                    const md_kv_cache* kv, const int32_t* slots, int32_t n_slots) {
-  MD_CHECK_ARG(m && m->blocks && kv && variant && batch > 0 && batch <= 1024);
-  MD_CHECK_ARG(slots == nullptr || n_slots > 0);
-  MD_TRY(lora_bank_ok(bank));
-  MD_CHECK_ARG(bank->n_layers == m->n_layers);
+static md_status multi_lora_args_ok(const md_text_model* m, const RowMap& rows, int32_t batch, const md_kv_cache* kv) {
+  MD_CHECK_ARG(m && m->blocks && kv && rows.variant && batch > 0 && batch <= 1024);
+  MD_CHECK_ARG(rows.slots == nullptr || rows.n_slots > 0);
+  MD_TRY(lora_bank_ok(rows.bank));
+  MD_CHECK_ARG(rows.bank->n_layers == m->n_layers);
   if (kv->k8 || kv->v8 || (m->fp8 && m->fp8->blocks) || m->f8) return MD_ERR_UNSUPPORTED;
   return MD_OK;
 }
@@ -1055,10 +1075,9 @@ extern "C" md_status md_text_forward_multi_lora(const md_text_model* m, const md
                                                 size_t workspace_bytes, void* stream) {
   if (bank == nullptr)
     return md_text_forward_slots(m, x_in, hidden, batch, q_len, pos0, slots, n_slots, kv, workspace, workspace_bytes, stream);
-  MD_TRY(multi_lora_args_ok(m, bank, variant, batch, kv, slots, n_slots));
-  const LoraCall lc{bank, variant};
-  return text_forward_impl(m, x_in, hidden, batch, q_len, pos0, slots, n_slots, nullptr, nullptr, kv, workspace, workspace_bytes,
-                           stream, &lc);
+  const RowMap rows{slots, n_slots, nullptr, nullptr, bank, variant};
+  MD_TRY(multi_lora_args_ok(m, rows, batch, kv));
+  return text_forward_impl(m, x_in, hidden, batch, q_len, pos0, rows, kv, workspace, workspace_bytes, stream);
 }
 
 extern "C" md_status md_decode_step_multi_lora(const md_text_model* m, const md_lora_bank* bank, const int32_t* variant,
@@ -1069,21 +1088,15 @@ extern "C" md_status md_decode_step_multi_lora(const md_text_model* m, const md_
   if (bank == nullptr)
     return md_decode_step_slots(m, tokens, next, pos, batch, slots, n_slots, kv, suppress_id, logits, ld_logits, workspace,
                                 workspace_bytes, stream);
-  MD_TRY(multi_lora_args_ok(m, bank, variant, batch, kv, slots, n_slots));
-  const LoraCall lc{bank, variant};
-  return decode_step_impl(m, tokens, next, pos, batch, slots, n_slots, nullptr, nullptr, kv, suppress_id, logits, ld_logits,
-                          workspace, workspace_bytes, stream, &lc);
+  const RowMap rows{slots, n_slots, nullptr, nullptr, bank, variant};
+  MD_TRY(multi_lora_args_ok(m, rows, batch, kv));
+  return decode_step_impl(m, tokens, next, pos, batch, rows, kv, suppress_id, logits, ld_logits, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t md_decode_step_b1_workspace_bytes(const md_text_model* m) {
   if (!m || !m->blocks) return 0;
   return align_up(md_decode_b1_workspace_bytes(m));
 }
-
-// decode_b1.hip: embedding lookup, every decoder block, final layer norm, lm_head, suppression, argmax and pos += 1 in ONE launch
-md_status md_decode_b1_step(const md_text_model* m, const int32_t* token, int32_t* next, int32_t* pos, const md_kv_cache* kv,
-                            int32_t suppress_id, void* logits, void* workspace, size_t workspace_bytes, void* sync_state,
-                            hipStream_t s);
 
 extern "C" md_status md_decode_step_b1(const md_text_model* m, const int32_t* token, int32_t* next, int32_t* pos,
                                        const md_kv_cache* kv, int32_t suppress_id, void* logits, int64_t ld_logits,

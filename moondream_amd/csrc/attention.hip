@@ -24,7 +24,7 @@
 //   head_dim 72 is handled by LDS-side zero padding only: 80 for the QK^T
 //   contraction (5 K-steps), 96 (3 x 32 rows of V^T) for PV; HBM layouts stay
 //   dense.
-#include "md_common.hpp"
+#include "text_internal.hpp"
 #include <cstdlib>
 
 // md_gemm_set_tuning("attn_skip_dead", 0..3) / MD_ATTN_SKIP_DEAD: A/B and test hook (every setting gives the same bits)
@@ -1144,33 +1144,11 @@ __global__ __launch_bounds__(1024) void attn_decode_shared_kernel(const bf16_t* 
   }
 }
 
-// the decode attention of md_text_forward_shared (pslots != nullptr; slots required)
-md_status attn_decode_shared_launch(bool fused, const void* q, int64_t ldq, void* o, int64_t ldo, const float* freqs, void* k_slab,
-                                    void* v_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch,
-                                    int32_t n_heads, int32_t n_kv_heads, int32_t rot_dim, float scale, const int32_t* slots,
-                                    int32_t n_slots, const int32_t* pslots, const int32_t* plen, hipStream_t stream) {
-  const dim3 grid(n_heads, (batch + SHG - 1) / SHG);
-  const float sl2 = scale * 1.4426950408889634f;
-  const int kv_group = n_heads / n_kv_heads;
-  const bool nt = n_heads == n_kv_heads && decode_attn_nt();
-#define MD_SHARED_LAUNCH(F, N)                                                                                              \
-  hipLaunchKernelGGL((attn_decode_shared_kernel<F, N>), grid, dim3(1024), 0, stream, (const bf16_t*)q, ldq, (bf16_t*)o, ldo, \
-                     (bf16_t*)k_slab, (bf16_t*)v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads, kv_group, sl2, freqs,  \
-                     rot_dim, slots, n_slots, pslots, plen)
-  if (fused && nt) MD_SHARED_LAUNCH(true, true);
-  else if (fused) MD_SHARED_LAUNCH(true, false);
-  else if (nt) MD_SHARED_LAUNCH(false, true);
-  else MD_SHARED_LAUNCH(false, false);
-#undef MD_SHARED_LAUNCH
-  return md_launch_status();
-}
-
 }  // namespace
 
-// internal (api.hip): md_attention_prefill with the slot table of md_text_forward_slots (slots == nullptr: slot b) and the shared
-// prefix table of md_text_forward_shared (pfx_slots == nullptr: none)
-md_status md_attention_prefill_shared(const md_attn_args* a, const int32_t* slots, const int32_t* pfx_slots, const int32_t* pfx_len,
-                                      int32_t n_slots, hipStream_t stream) {
+// internal (api.hip): md_attention_prefill with the slot table of md_text_forward_slots (rows.slots == nullptr: slot b) and the
+// shared prefix table of md_text_forward_shared (rows.pfx_slots == nullptr: none)
+md_status md_attention_prefill_rows(const md_attn_args* a, const RowMap& rows, hipStream_t stream) {
   MD_CHECK_ARG(a && a->q && a->k && a->v && (a->o || a->o8));
   MD_CHECK_ARG(a->batch > 0 && a->n_heads > 0 && a->n_kv_heads > 0 && a->q_len > 0);
   MD_CHECK_ARG(a->n_heads % a->n_kv_heads == 0);
@@ -1199,21 +1177,19 @@ md_status md_attention_prefill_shared(const md_attn_args* a, const int32_t* slot
   k.kv_len = a->kv_len;
   k.scale_log2 = a->scale * 1.4426950408889634f;
   k.skip_dead = g_attn_skip_dead;
-  k.slots = slots;
-  k.pfx_slots = pfx_slots;
-  k.pfx_len = pfx_len;
-  k.pfx_n_slots = n_slots;
+  const bool shp = rows.pfx_slots != nullptr;
+  k.slots = rows.slots;
+  k.pfx_slots = rows.pfx_slots;
+  k.pfx_len = rows.pfx_len;
+  k.pfx_n_slots = shp ? rows.n_slots : 0;
   k.o8 = (uint8_t*)a->o8;
   k.o8_bs = a->o8_bs;
   k.o8_ts = a->o8_ts;
   k.o8_inv_scale = a->o8_inv_scale;
   k.head_dim = a->head_dim;
-  dim3 grid((a->q_len + 127) / 128, a->n_heads, a->batch);
   k.n_qblk = (a->q_len + 127) / 128;
   k.n_bh = a->batch * a->n_heads;
   k.n_heads = a->n_heads;
-  const dim3 grid1(8 * k.n_qblk * ((k.n_bh + 7) / 8));
-  hipStream_t s = stream;
   // MD_ATTN_VARIANT = reg | dma (default) | pipe for A/B runs
   static const int variant = [] {
     const char* e = getenv("MD_ATTN_VARIANT");
@@ -1221,106 +1197,74 @@ md_status md_attention_prefill_shared(const md_attn_args* a, const int32_t* slot
     if (e && e[0] == 'p') return 2;
     return 1;
   }();
-  // shared prefix: the SHP instantiation of the variant the slot-table call would take (same arithmetic, other addresses)
-  if (pfx_slots != nullptr && variant == 0) {
-    if (a->head_dim == 72)
-      hipLaunchKernelGGL((attn_prefill_kernel<72, true>), grid, dim3(256), 0, s, k);
-    else
-      hipLaunchKernelGGL((attn_prefill_kernel<64, true>), grid, dim3(256), 0, s, k);
-  } else if (pfx_slots != nullptr && variant == 1) {
-    if (a->head_dim == 72)
-      hipLaunchKernelGGL((attn_prefill_dma_kernel<72, false, true>), grid1, dim3(256), 0, s, k);
-    else
-      hipLaunchKernelGGL((attn_prefill_dma_kernel<64, false, true>), grid1, dim3(256), 0, s, k);
-  } else if (pfx_slots != nullptr) {
-    if (a->head_dim == 72)
-      hipLaunchKernelGGL((attn_prefill_dma_kernel<72, true, true>), grid1, dim3(256), 0, s, k);
-    else
-      hipLaunchKernelGGL((attn_prefill_dma_kernel<64, true, true>), grid1, dim3(256), 0, s, k);
-  } else if (variant == 0) {
-    if (a->head_dim == 72)
-      hipLaunchKernelGGL(attn_prefill_kernel<72>, grid, dim3(256), 0, s, k);
-    else
-      hipLaunchKernelGGL(attn_prefill_kernel<64>, grid, dim3(256), 0, s, k);
-  } else if (variant == 1) {
-    if (a->head_dim == 72)
-      hipLaunchKernelGGL((attn_prefill_dma_kernel<72, false>), grid1, dim3(256), 0, s, k);
-    else
-      hipLaunchKernelGGL((attn_prefill_dma_kernel<64, false>), grid1, dim3(256), 0, s, k);
-  } else {
-    if (a->head_dim == 72)
-      hipLaunchKernelGGL((attn_prefill_dma_kernel<72, true>), grid1, dim3(256), 0, s, k);
-    else
-      hipLaunchKernelGGL((attn_prefill_dma_kernel<64, true>), grid1, dim3(256), 0, s, k);
-  }
+  // [variant][head_dim 72][shared prefix]: SHP is the instantiation of the variant the slot-table call would take (same
+  // arithmetic, other addresses)
+  static void (*const kernels[3][2][2])(const AttnK) = {
+      {{attn_prefill_kernel<64>, attn_prefill_kernel<64, true>}, {attn_prefill_kernel<72>, attn_prefill_kernel<72, true>}},
+      {{attn_prefill_dma_kernel<64, false>, attn_prefill_dma_kernel<64, false, true>},
+       {attn_prefill_dma_kernel<72, false>, attn_prefill_dma_kernel<72, false, true>}},
+      {{attn_prefill_dma_kernel<64, true>, attn_prefill_dma_kernel<64, true, true>},
+       {attn_prefill_dma_kernel<72, true>, attn_prefill_dma_kernel<72, true, true>}}};
+  // the register kernel takes a (query block, head, batch) grid, the LDS-DMA kernels the XCD-aware 1-D one
+  const dim3 grid = variant == 0 ? dim3(k.n_qblk, a->n_heads, a->batch) : dim3(8 * k.n_qblk * ((k.n_bh + 7) / 8));
+  hipLaunchKernelGGL(kernels[variant][a->head_dim == 72][shp], grid, dim3(256), 0, stream, k);
   return md_launch_status();
-}
-
-md_status md_attention_prefill_slots(const md_attn_args* a, const int32_t* slots, hipStream_t stream) {
-  return md_attention_prefill_shared(a, slots, nullptr, nullptr, 0, stream);
 }
 
 extern "C" md_status md_attention_prefill(const md_attn_args* a, void* stream) {
-  return md_attention_prefill_slots(a, nullptr, (hipStream_t)stream);
+  return md_attention_prefill_rows(a, RowMap{}, (hipStream_t)stream);
 }
 
-// internal (api.hip): md_attention_decode with the slot table of md_text_forward_slots (slots == nullptr: slot b)
-md_status md_attention_decode_slots(const void* q, int64_t ldq, void* o, int64_t ldo, const void* k_slab, const void* v_slab,
-                                    int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch, int32_t n_heads,
-                                    int32_t n_kv_heads, int32_t head_dim, float scale, const int32_t* slots, int32_t n_slots,
-                                    hipStream_t stream) {
-  MD_CHECK_ARG(q && o && k_slab && v_slab && kv_len);
-  MD_CHECK_ARG(head_dim == 64 && ctx <= DEC_MAX_CTX && batch > 0 && n_heads % n_kv_heads == 0);
-  MD_CHECK_ARG(ldq % 8 == 0 && ldo % 8 == 0 && ldq >= n_heads * 64 && ldo >= n_heads * 64);
-  if (decode_attn_waves(batch, n_heads) == 16)
-    hipLaunchKernelGGL((attn_decode_kernel<false, 16>), dim3(n_heads, batch), dim3(1024), 0, stream,
-                       (const bf16_t*)q, ldq, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                       slab_batch_stride, ctx, kv_len, n_heads, n_heads / n_kv_heads,
-                       scale * 1.4426950408889634f, (const float*)nullptr, 0, slots, n_slots);
-  else if (n_heads == n_kv_heads && decode_attn_nt())
-    hipLaunchKernelGGL((attn_decode_kernel<false, 4, true>), dim3(n_heads, batch), dim3(256), 0, stream,
-                       (const bf16_t*)q, ldq, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                       slab_batch_stride, ctx, kv_len, n_heads, 1, scale * 1.4426950408889634f, (const float*)nullptr, 0,
-                       slots, n_slots);
-  else
-    hipLaunchKernelGGL((attn_decode_kernel<false, 4>), dim3(n_heads, batch), dim3(256), 0, stream,
-                       (const bf16_t*)q, ldq, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                       slab_batch_stride, ctx, kv_len, n_heads, n_heads / n_kv_heads,
-                       scale * 1.4426950408889634f, (const float*)nullptr, 0, slots, n_slots);
+// internal (api.hip) and behind every md_attention_decode* entry point: ONE place for the argument checks, the choice of
+// kernel and each kernel's argument list.
+//   e4m3 copy present, fused and MHA  -> attn_decode_f8_kernel (attention_f8kv.hip)
+//   prefix table present              -> attn_decode_shared_kernel, SHG rows per workgroup
+//   otherwise                         -> attn_decode_kernel, 16 waves for few (row, head) pairs, else 4
+// NT (non-temporal K / V loads) for MHA at 4 waves and in the grouped kernel, unless MD_ATTN_DECODE_NT=0.
+md_status md_attention_decode_rows(const DecodeAttn& d, const RowMap& rows, hipStream_t stream) {
+  MD_CHECK_ARG(d.q && d.o && d.k_slab && d.v_slab && d.kv_len);
+  MD_CHECK_ARG(rows.slots == nullptr || rows.n_slots > 0);
+  MD_CHECK_ARG(rows.pfx_slots == nullptr || (rows.pfx_len != nullptr && rows.slots != nullptr));
+  MD_CHECK_ARG(d.head_dim == 64 && d.ctx <= DEC_MAX_CTX && d.batch > 0 && d.n_heads > 0 && d.n_kv_heads > 0);
+  MD_CHECK_ARG(d.n_heads % d.n_kv_heads == 0 && d.ldq % 8 == 0 && d.ldo % 8 == 0);
+  MD_CHECK_ARG(d.ldq >= (d.fused ? 3 : 1) * d.n_heads * 64 && d.ldo >= d.n_heads * 64);
+  const bool mha = d.n_heads == d.n_kv_heads;
+  if (d.fused) MD_CHECK_ARG(d.freqs && mha && d.rot_dim % 2 == 0 && d.rot_dim > 0 && d.rot_dim <= 64);
+  if (d.k8_slab && d.v8_slab && d.fused) return md_attention_decode_f8_rows(d, rows, stream);
+
+  const bool nt = mha && decode_attn_nt();
+  const float sl2 = d.scale * 1.4426950408889634f;
+  const int kv_group = d.n_heads / d.n_kv_heads;
+  const float* freqs = d.fused ? d.freqs : nullptr;
+  const int rot = d.fused ? d.rot_dim : 0;
+  if (rows.pfx_slots != nullptr) {
+    static const decltype(&attn_decode_shared_kernel<false, false>) kernels[2][2] = {
+        {attn_decode_shared_kernel<false, false>, attn_decode_shared_kernel<false, true>},
+        {attn_decode_shared_kernel<true, false>, attn_decode_shared_kernel<true, true>}};
+    hipLaunchKernelGGL(kernels[d.fused][nt], dim3(d.n_heads, (d.batch + SHG - 1) / SHG), dim3(1024), 0, stream, (const bf16_t*)d.q,
+                       d.ldq, (bf16_t*)d.o, d.ldo, (bf16_t*)d.k_slab, (bf16_t*)d.v_slab, d.slab_batch_stride, d.ctx, d.kv_len, d.batch,
+                       d.n_heads, kv_group, sl2, freqs, rot, rows.slots, rows.n_slots, rows.pfx_slots, rows.pfx_len);
+    return md_launch_status();
+  }
+  // [fused][16 waves | 4 waves NT | 4 waves]
+  static const decltype(&attn_decode_kernel<false, 4>) kernels[2][3] = {
+      {attn_decode_kernel<false, 16>, attn_decode_kernel<false, 4, true>, attn_decode_kernel<false, 4>},
+      {attn_decode_kernel<true, 16>, attn_decode_kernel<true, 4, true>, attn_decode_kernel<true, 4>}};
+  const int cfg = decode_attn_waves(d.batch, d.n_heads) == 16 ? 0 : nt ? 1 : 2;
+  hipLaunchKernelGGL(kernels[d.fused][cfg], dim3(d.n_heads, d.batch), dim3(cfg == 0 ? 1024 : 256), 0, stream, (const bf16_t*)d.q, d.ldq,
+                     (bf16_t*)d.o, d.ldo, (bf16_t*)d.k_slab, (bf16_t*)d.v_slab, d.slab_batch_stride, d.ctx, d.kv_len, d.n_heads, kv_group,
+                     sl2, freqs, rot, rows.slots, rows.n_slots);
   return md_launch_status();
 }
 
+// the kernel-level entry points: each fills the descriptor (a null prefix table is the slot-table launch)
 extern "C" md_status md_attention_decode(const void* q, int64_t ldq, void* o, int64_t ldo,
                                          const void* k_slab, const void* v_slab,
                                          int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len,
                                          int32_t batch, int32_t n_heads, int32_t n_kv_heads,
                                          int32_t head_dim, float scale, void* stream) {
-  return md_attention_decode_slots(q, ldq, o, ldo, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads, n_kv_heads,
-                                   head_dim, scale, nullptr, 0, (hipStream_t)stream);
-}
-
-// internal (api.hip): md_attention_decode_rope with the slot table of md_text_forward_slots (slots == nullptr: slot b)
-md_status md_attention_decode_rope_slots(const void* qkv, int64_t ld, void* o, int64_t ldo, const float* freqs, void* k_slab,
-                                         void* v_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch,
-                                         int32_t n_heads, int32_t head_dim, int32_t rot_dim, float scale, const int32_t* slots,
-                                         int32_t n_slots, hipStream_t stream) {
-  MD_CHECK_ARG(qkv && o && freqs && k_slab && v_slab && kv_len);
-  MD_CHECK_ARG(head_dim == 64 && ctx <= DEC_MAX_CTX && batch > 0 && n_heads > 0);
-  MD_CHECK_ARG(rot_dim % 2 == 0 && rot_dim > 0 && rot_dim <= 64 && ld % 8 == 0 && ldo % 8 == 0);
-  MD_CHECK_ARG(ld >= 3 * n_heads * 64 && ldo >= n_heads * 64);
-  if (decode_attn_waves(batch, n_heads) == 16)
-    hipLaunchKernelGGL((attn_decode_kernel<true, 16>), dim3(n_heads, batch), dim3(1024), 0, stream,
-                       (const bf16_t*)qkv, ld, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                       slab_batch_stride, ctx, kv_len, n_heads, 1, scale * 1.4426950408889634f, freqs, rot_dim, slots, n_slots);
-  else if (decode_attn_nt())
-    hipLaunchKernelGGL((attn_decode_kernel<true, 4, true>), dim3(n_heads, batch), dim3(256), 0, stream,
-                       (const bf16_t*)qkv, ld, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                       slab_batch_stride, ctx, kv_len, n_heads, 1, scale * 1.4426950408889634f, freqs, rot_dim, slots, n_slots);
-  else
-    hipLaunchKernelGGL((attn_decode_kernel<true, 4>), dim3(n_heads, batch), dim3(256), 0, stream,
-                       (const bf16_t*)qkv, ld, (bf16_t*)o, ldo, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                       slab_batch_stride, ctx, kv_len, n_heads, 1, scale * 1.4426950408889634f, freqs, rot_dim, slots, n_slots);
-  return md_launch_status();
+  return md_attention_decode_shared(q, ldq, o, ldo, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads, n_kv_heads,
+                                    head_dim, scale, nullptr, 0, nullptr, nullptr, stream);
 }
 
 extern "C" md_status md_attention_decode_rope(const void* qkv, int64_t ld, void* o, int64_t ldo,
@@ -1328,37 +1272,8 @@ extern "C" md_status md_attention_decode_rope(const void* qkv, int64_t ld, void*
                                               int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len,
                                               int32_t batch, int32_t n_heads, int32_t head_dim,
                                               int32_t rot_dim, float scale, void* stream) {
-  return md_attention_decode_rope_slots(qkv, ld, o, ldo, freqs, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads,
-                                        head_dim, rot_dim, scale, nullptr, 0, (hipStream_t)stream);
-}
-
-// internal (api.hip) and the kernel-level entry points of the shared-prefix decode: prefix_slots == nullptr is the slot-table
-// function (the same launch); otherwise the grouped kernel
-md_status md_attention_decode_shared_any(bool fused, const void* q, int64_t ldq, void* o, int64_t ldo, const float* freqs, void* k_slab,
-                                         void* v_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len, int32_t batch,
-                                         int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim, float scale,
-                                         const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots, const int32_t* prefix_len,
-                                         hipStream_t stream) {
-  MD_CHECK_ARG((slots == nullptr || n_slots > 0) && n_heads > 0 && n_kv_heads > 0);
-  MD_CHECK_ARG(prefix_slots == nullptr || (prefix_len != nullptr && slots != nullptr));
-  if (prefix_slots == nullptr) {
-    if (fused)
-      return md_attention_decode_rope_slots(q, ldq, o, ldo, freqs, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads,
-                                            head_dim, rot_dim, scale, slots, n_slots, stream);
-    return md_attention_decode_slots(q, ldq, o, ldo, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads, n_kv_heads,
-                                     head_dim, scale, slots, n_slots, stream);
-  }
-  MD_CHECK_ARG(q && o && k_slab && v_slab && kv_len);
-  MD_CHECK_ARG(head_dim == 64 && ctx <= DEC_MAX_CTX && batch > 0 && n_heads % n_kv_heads == 0 && ldq % 8 == 0 && ldo % 8 == 0);
-  if (fused) {
-    MD_CHECK_ARG(freqs && n_heads == n_kv_heads && rot_dim % 2 == 0 && rot_dim > 0 && rot_dim <= 64);
-    MD_CHECK_ARG(ldq >= 3 * n_heads * 64 && ldo >= n_heads * 64);
-  } else {
-    MD_CHECK_ARG(ldq >= n_heads * 64 && ldo >= n_heads * 64);
-  }
-  return attn_decode_shared_launch(fused, q, ldq, o, ldo, fused ? freqs : nullptr, k_slab, v_slab, slab_batch_stride, ctx, kv_len,
-                                   batch, n_heads, n_kv_heads, fused ? rot_dim : 0, scale, slots, n_slots, prefix_slots, prefix_len,
-                                   stream);
+  return md_attention_decode_rope_shared(qkv, ld, o, ldo, freqs, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads,
+                                         head_dim, rot_dim, scale, nullptr, 0, nullptr, nullptr, stream);
 }
 
 extern "C" md_status md_attention_decode_shared(const void* q, int64_t ldq, void* o, int64_t ldo, const void* k_slab,
@@ -1366,9 +1281,9 @@ extern "C" md_status md_attention_decode_shared(const void* q, int64_t ldq, void
                                                 int32_t batch, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, float scale,
                                                 const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
                                                 const int32_t* prefix_len, void* stream) {
-  return md_attention_decode_shared_any(false, q, ldq, o, ldo, nullptr, (void*)k_slab, (void*)v_slab, slab_batch_stride, ctx, kv_len,
-                                        batch, n_heads, n_kv_heads, head_dim, 0, scale, slots, n_slots, prefix_slots, prefix_len,
-                                        (hipStream_t)stream);
+  const DecodeAttn d = {q, ldq, o, ldo, nullptr, (void*)k_slab, (void*)v_slab, nullptr, nullptr, 0.f, 0.f, slab_batch_stride, ctx, kv_len,
+                        batch, n_heads, n_kv_heads, head_dim, 0, scale, false};
+  return md_attention_decode_rows(d, RowMap{slots, n_slots, prefix_slots, prefix_len}, (hipStream_t)stream);
 }
 
 extern "C" md_status md_attention_decode_rope_shared(const void* qkv, int64_t ld, void* o, int64_t ldo, const float* freqs,
@@ -1376,6 +1291,7 @@ extern "C" md_status md_attention_decode_rope_shared(const void* qkv, int64_t ld
                                                      const int32_t* kv_len, int32_t batch, int32_t n_heads, int32_t head_dim,
                                                      int32_t rot_dim, float scale, const int32_t* slots, int32_t n_slots,
                                                      const int32_t* prefix_slots, const int32_t* prefix_len, void* stream) {
-  return md_attention_decode_shared_any(true, qkv, ld, o, ldo, freqs, k_slab, v_slab, slab_batch_stride, ctx, kv_len, batch, n_heads,
-                                        n_heads, head_dim, rot_dim, scale, slots, n_slots, prefix_slots, prefix_len, (hipStream_t)stream);
+  const DecodeAttn d = {qkv, ld, o, ldo, freqs, k_slab, v_slab, nullptr, nullptr, 0.f, 0.f, slab_batch_stride, ctx, kv_len,
+                        batch, n_heads, n_heads, head_dim, rot_dim, scale, true};
+  return md_attention_decode_rows(d, RowMap{slots, n_slots, prefix_slots, prefix_len}, (hipStream_t)stream);
 }

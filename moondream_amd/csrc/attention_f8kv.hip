@@ -11,7 +11,7 @@
 // folded into q and the V scale into the output.  The newest key / value enter as what the cache will hold for them
 // (quantised, dequantised), so a step sees the same numbers as every later step.
 // Tolerance-judged like the rest of the fp8 mode; no bit-compatibility with the bf16 kernel is claimed.
-#include "md_common.hpp"
+#include "text_internal.hpp"
 
 #include <algorithm>
 
@@ -217,8 +217,8 @@ __global__ __launch_bounds__(256) void attn_decode_f8_kernel(const bf16_t* __res
 }  // namespace
 
 // internal (api.hip)
-md_status md_kv_quantize_f8_layer(const md_kv_cache* kv, int layer, const int32_t* pos0, int pos_fixed, int batch, int n_heads, int n_pos,
-                                  hipStream_t s, const int32_t* slots, int n_slots) {
+md_status md_kv_quantize_f8_layer(const md_kv_cache* kv, int layer, const int32_t* pos0, int pos_fixed, int batch, int n_heads,
+                                  int n_pos, const RowMap& rows, hipStream_t s) {
   MD_CHECK_ARG(kv && kv->k && kv->v && kv->k8 && kv->v8 && kv->k_scale && kv->v_scale && kv->k_scale[layer] > 0.f && kv->v_scale[layer] > 0.f);
   const int64_t total = (int64_t)batch * n_heads * n_pos * 8;
   if (total <= 0) return MD_OK;
@@ -226,7 +226,7 @@ md_status md_kv_quantize_f8_layer(const md_kv_cache* kv, int layer, const int32_
   const int64_t lo = (int64_t)layer * kv->layer_stride;
   hipLaunchKernelGGL(kv_quantize_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)kv->k + lo, (const bf16_t*)kv->v + lo,
                      (uint8_t*)kv->k8 + lo, (uint8_t*)kv->v8 + lo, 1.0f / kv->k_scale[layer], 1.0f / kv->v_scale[layer], pos0, pos_fixed,
-                     kv->batch_stride, kv->ctx, batch, n_heads, n_pos, slots, n_slots);
+                     kv->batch_stride, kv->ctx, batch, n_heads, n_pos, rows.slots, rows.n_slots);
   return md_launch_status();
 }
 
@@ -234,20 +234,17 @@ extern "C" md_status md_kv_quantize_f8(const md_kv_cache* kv, int32_t n_layers, 
                                        int32_t pos_fixed, int32_t n_pos, void* stream) {
   MD_CHECK_ARG(kv && n_layers > 0 && batch > 0 && n_heads > 0 && n_pos > 0 && pos_fixed >= 0);
   for (int l = 0; l < n_layers; ++l)
-    MD_TRY(md_kv_quantize_f8_layer(kv, l, pos0, pos_fixed, batch, n_heads, n_pos, (hipStream_t)stream, nullptr, 0));
+    MD_TRY(md_kv_quantize_f8_layer(kv, l, pos0, pos_fixed, batch, n_heads, n_pos, RowMap{}, (hipStream_t)stream));
   return MD_OK;
 }
 
-md_status md_attention_decode_rope_f8_launch(const void* qkv, int64_t ld, void* o, int64_t ldo, const float* freqs, void* k_slab, void* v_slab,
-                                             void* k8_slab, void* v8_slab, int64_t slab_batch_stride, int32_t ctx, const int32_t* kv_len,
-                                             int32_t batch, int32_t n_heads, int32_t rot_dim, float scale, float k_scale, float v_scale,
-                                             hipStream_t s, const int32_t* slots, int32_t n_slots) {
-  MD_CHECK_ARG(qkv && o && freqs && k_slab && v_slab && k8_slab && v8_slab && kv_len);
-  MD_CHECK_ARG(ctx <= F8_MAX_CTX && batch > 0 && n_heads > 0 && rot_dim % 2 == 0 && rot_dim > 0 && rot_dim <= 64);
-  MD_CHECK_ARG(ld % 8 == 0 && ldo % 8 == 0 && ld >= 3 * n_heads * 64 && ldo >= n_heads * 64 && k_scale > 0.f && v_scale > 0.f);
-  hipLaunchKernelGGL(attn_decode_f8_kernel, dim3(n_heads, batch), dim3(256), 0, s, (const bf16_t*)qkv, ld, (bf16_t*)o, ldo, freqs,
-                     (bf16_t*)k_slab, (bf16_t*)v_slab, (uint8_t*)k8_slab, (uint8_t*)v8_slab, slab_batch_stride, ctx, kv_len, n_heads,
-                     scale * 1.4426950408889634f, rot_dim, k_scale, v_scale, slots, n_slots);
+// internal (md_attention_decode_rows picks it): the fused MHA step over the e4m3 copy; the checks that are this kernel's own
+md_status md_attention_decode_f8_rows(const DecodeAttn& d, const RowMap& rows, hipStream_t s) {
+  MD_CHECK_ARG(d.k8_slab && d.v8_slab && d.ctx <= F8_MAX_CTX && d.k_scale > 0.f && d.v_scale > 0.f);
+  hipLaunchKernelGGL(attn_decode_f8_kernel, dim3(d.n_heads, d.batch), dim3(256), 0, s, (const bf16_t*)d.q, d.ldq, (bf16_t*)d.o, d.ldo,
+                     d.freqs, (bf16_t*)d.k_slab, (bf16_t*)d.v_slab, (uint8_t*)d.k8_slab, (uint8_t*)d.v8_slab, d.slab_batch_stride,
+                     d.ctx, d.kv_len, d.n_heads, d.scale * 1.4426950408889634f, d.rot_dim, d.k_scale, d.v_scale, rows.slots,
+                     rows.n_slots);
   return md_launch_status();
 }
 
@@ -255,6 +252,8 @@ extern "C" md_status md_attention_decode_rope_f8(const void* qkv, int64_t ld, vo
                                                  void* v_slab, void* k8_slab, void* v8_slab, int64_t slab_batch_stride, int32_t ctx,
                                                  const int32_t* kv_len, int32_t batch, int32_t n_heads, int32_t rot_dim, float scale,
                                                  float k_scale, float v_scale, void* stream) {
-  return md_attention_decode_rope_f8_launch(qkv, ld, o, ldo, freqs, k_slab, v_slab, k8_slab, v8_slab, slab_batch_stride, ctx, kv_len, batch,
-                                            n_heads, rot_dim, scale, k_scale, v_scale, (hipStream_t)stream, nullptr, 0);
+  MD_CHECK_ARG(k8_slab && v8_slab);  // without the copy the dispatcher would take the bf16 kernel
+  const DecodeAttn d = {qkv, ld, o, ldo, freqs, k_slab, v_slab, k8_slab, v8_slab, k_scale, v_scale, slab_batch_stride, ctx, kv_len,
+                        batch, n_heads, n_heads, 64, rot_dim, scale, true};
+  return md_attention_decode_rows(d, RowMap{}, (hipStream_t)stream);
 }

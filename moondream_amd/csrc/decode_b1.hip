@@ -22,7 +22,7 @@
 // Numerics: fp32 dot products in a different association than the MFMA kernels (lane-strided partial sums + a wave
 // butterfly), softmax with per-slice maxima (flash-decoding) -- within the same tolerance of the reference as the
 // batched path, not bit-identical to it.  Weights: the SAME packed row-major bf16 matrices as every other kernel.
-#include "md_common.hpp"
+#include "text_internal.hpp"
 
 #include <cstdlib>
 

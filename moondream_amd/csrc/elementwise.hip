@@ -2,7 +2,7 @@
 // + KV-slab write, token embedding gather, greedy argmax, crop stitch + pool.
 // All of them move 16 bytes per lane per access (8 bf16) and do their
 // arithmetic in fp32 with exactly one rounding to bf16 per reference op.
-#include "md_common.hpp"
+#include "text_internal.hpp"
 
 #include <algorithm>
 
@@ -557,18 +557,17 @@ extern "C" md_status md_patchify_bf16(const void* crops, void* out, int64_t ld_o
   return md_launch_status();
 }
 
-// internal (api.hip): md_rope_kv_write with the slot table of md_text_forward_slots (slots == nullptr: slot b)
+// internal (api.hip): md_rope_kv_write with the slot table of md_text_forward_slots (rows.slots == nullptr: slot b)
 md_status md_rope_kv_write_slots(void* qkv, int64_t ld, const float* freqs, const int32_t* pos0, void* k_slab, void* v_slab,
                                  int64_t slab_batch_stride, int32_t ctx, int32_t batch, int32_t q_len, int32_t n_heads,
-                                 int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim, const int32_t* slots, int32_t n_slots,
-                                 hipStream_t stream) {
+                                 int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim, const RowMap& rows, hipStream_t stream) {
   MD_CHECK_ARG(qkv && freqs && pos0 && k_slab && v_slab && batch > 0 && q_len > 0);
   MD_CHECK_ARG(head_dim % 8 == 0 && rot_dim % 8 == 0 && rot_dim <= head_dim && ld % 8 == 0);
   MD_CHECK_ARG((n_heads + n_kv_heads) * (rot_dim / 2) <= 1024);
   MD_CHECK_ARG(ld >= (int64_t)(n_heads + 2 * n_kv_heads) * head_dim);
   hipLaunchKernelGGL(rope_kv_kernel, dim3(batch * q_len), dim3(256), 0, stream,
                      (bf16_t*)qkv, ld, freqs, pos0, (bf16_t*)k_slab, (bf16_t*)v_slab,
-                     slab_batch_stride, ctx, q_len, n_heads, n_kv_heads, head_dim, rot_dim, slots, n_slots);
+                     slab_batch_stride, ctx, q_len, n_heads, n_kv_heads, head_dim, rot_dim, rows.slots, rows.n_slots);
   return md_launch_status();
 }
 
@@ -578,7 +577,7 @@ extern "C" md_status md_rope_kv_write(void* qkv, int64_t ld, const float* freqs,
                                       int32_t n_kv_heads, int32_t head_dim, int32_t rot_dim,
                                       void* stream) {
   return md_rope_kv_write_slots(qkv, ld, freqs, pos0, k_slab, v_slab, slab_batch_stride, ctx, batch, q_len, n_heads, n_kv_heads,
-                                head_dim, rot_dim, nullptr, 0, (hipStream_t)stream);
+                                head_dim, rot_dim, RowMap{}, (hipStream_t)stream);
 }
 
 extern "C" md_status md_add_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo,

@@ -22,6 +22,7 @@
 // Operand maps of v_mfma_f32_16x16x32_bf16: lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j]
 // [col l & 15]; the accumulator has col = l & 15, row = 4 (l >> 4) + j.
 #include "gemm_internal.hpp"
+#include "text_internal.hpp"
 
 #include <climits>
 #include <cstdlib>

@@ -309,6 +309,64 @@ def test_decode_step_entry_point_rows_equal_uniform_steps(tiny128, batch):
         assert torch.equal(a, b) and torch.equal(an, bn)
 
 
+def test_block_split_of_a_mixed_step_equals_per_block_steps():
+    """md_decode_step_multi_lora over 130 rows -- the smallest step that enters the block split of the C layer (blocks of 64 or
+    128 rows) and leaves a ragged last block -- with a permuted slot table, one idle row and a table mixing base rows with two
+    variants, against three calls over rows [0, 64), [64, 128), [128, 130) with the sub-tables: next, pos, the logits and the
+    K / V slabs are bit-equal.  What the split must get right is the advance of every per-row table at once."""
+    rows = 130
+    cfg, sd, model = build("tiny", 7, max_batch=rows)
+    for name, seed, rank in (("a", 1, 8), ("b", 2, 64)):
+        model.register_variant(name, synth.synthetic_lora(cfg, seed=seed, rank=rank, device="cuda"))
+        model._bank_index(name)
+    bank, t, lib = model._bank, cfg.text, model.lib
+    rng = np.random.default_rng(rows)
+    slot_list = [int(v) for v in rng.permutation(rows)]
+    idle = 70  # in the second block of 64, and not a block's first row
+    slot_list[idle] = -1
+    table = [(-1, 0, 1)[i % 3] for i in rng.permutation(rows)]
+    # every block mixes the three kinds of row, and no block's sub-table equals the first block's: a table that does not
+    # advance with the block changes the result
+    assert {-1, 0, 1} == set(table[:64]) == set(table[64:128]) and table[64:128] != table[:64] and table[128:] != table[:2]
+    tokens, pos0 = dev(rng.integers(10, t.vocab_size, rows)), dev(rng.integers(1, 40, rows))
+    slots, variant = dev(slot_list), dev(table)
+    g = torch.Generator(device="cuda").manual_seed(rows)
+    k0 = torch.randn(model._kv_k.shape, generator=g, device="cuda").to(BF16)
+    v0 = torch.randn(model._kv_v.shape, generator=g, device="cuda").to(BF16)
+    ws = torch.empty(lib.md_decode_multi_lora_workspace_bytes(C.byref(model.w.text), C.byref(bank.struct), rows), dtype=torch.uint8,
+                     device="cuda")
+    kv = model._kv_struct(0)
+
+    def run(blocks):
+        model._kv_k.copy_(k0)
+        model._kv_v.copy_(v0)
+        logits = torch.zeros(rows, t.vocab_size, dtype=BF16, device="cuda")
+        nxt = torch.full((rows,), -7, dtype=torch.int32, device="cuda")
+        pos = pos0.clone()
+        for r0, r1 in blocks:
+            _lib.check(lib.md_decode_step_multi_lora(C.byref(model.w.text), C.byref(bank.struct), variant[r0:].data_ptr(),
+                                                     tokens[r0:].data_ptr(), nxt[r0:].data_ptr(), pos[r0:].data_ptr(), r1 - r0,
+                                                     slots[r0:].data_ptr(), rows, C.byref(kv), cfg.tokenizer.answer_id,
+                                                     logits[r0:].data_ptr(), t.vocab_size, ws.data_ptr(), ws.numel(), stream()),
+                       "md_decode_step_multi_lora")
+        torch.cuda.synchronize()
+        return logits, nxt, pos, model._kv_k.clone(), model._kv_v.clone()
+
+    with torch.inference_mode():
+        one = run([(0, rows)])
+        three = run([(0, 64), (64, 128), (128, rows)])
+    for name, a, b in zip(("logits", "next", "pos", "K", "V"), one, three):
+        assert torch.equal(a, b), name
+    logits, nxt, pos, k1, v1 = one
+    assert torch.equal(pos, pos0 + 1)
+    # the step wrote exactly one K / V row per live row: position pos0 of its own slot
+    live = [i for i in range(rows) if i != idle]
+    changed = (k1 != k0).any(dim=-1).any(dim=0).any(dim=1)  # [slot][position]
+    want = torch.zeros_like(changed)
+    want[slots[live].long(), pos0[live].long()] = True
+    assert torch.equal(changed, want)
+
+
 def test_reregistered_variant_replaces_the_bank_copy(tiny128):
     cfg, model, variants = tiny128
     model.register_variant("rr", synth.synthetic_lora(cfg, seed=11, rank=8, device="cuda"))
