@@ -123,10 +123,14 @@ typedef struct {
  *                     the 64-row configs -- a sequence gets the same bits in a decode step of 128 as in one of 64; layers of
  *                     >= 16384 output columns (lm_head) take the by-shape config (same MFMA family, same K order).  Other row
  *                     counts: as MD_TILE_BY_SHAPE.
+ *   MD_TILE_PINNED_ANY_ROWS  MD_TILE_PINNED for launches of <= 64 rows as well: the 256x256 kernel with the rows past m dropped
+ *                     by its range checks, not the split-K weight-streaming configs.  For recomputing a few rows of a pinned
+ *                     launch with the bits that launch gives them (md_text_forward_trim's last block); slower than the
+ *                     decode regime for anything else.
  * md_vit_model.tile_policy / md_text_model.tile_policy apply it to every GEMM of md_vit_encode / md_vision_project* /
  * md_text_forward* / md_lm_head / md_decode_step made with that struct.  Launches of <= 64 rows (the decode regime) are
- * not affected: they always take the split-K weight-streaming configs. */
-enum { MD_TILE_BY_SHAPE = 0, MD_TILE_PINNED = 1, MD_TILE_DECODE_TALL = 2 };
+ * not affected: they always take the split-K weight-streaming configs, except under MD_TILE_PINNED_ANY_ROWS. */
+enum { MD_TILE_BY_SHAPE = 0, MD_TILE_PINNED = 1, MD_TILE_DECODE_TALL = 2, MD_TILE_PINNED_ANY_ROWS = 3 };
 
 md_status md_gemm_bf16(const md_gemm_args* args, void* stream);
 size_t md_gemm_workspace_bytes(const md_linear* lin, int32_t m, int32_t store_pad_cols);
@@ -624,6 +628,30 @@ md_status md_text_forward_shared(const md_text_model* m, const void* x, void* hi
                                  const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
                                  const int32_t* prefix_len, const md_kv_cache* kv, void* workspace, size_t workspace_bytes,
                                  void* stream);
+
+/* The decoder for a caller that does not keep every hidden row.  hidden_mode:
+ *   MD_HIDDEN_ALL   every row in hidden [batch*q_len][dim]: md_text_forward_shared (hidden_last is not read);
+ *   MD_HIDDEN_LAST  the last row of every sequence in hidden_last bf16 [batch][dim] (16-byte aligned) -- what lm_head and
+ *                   the first decode step read after a prefill;
+ *   MD_HIDDEN_NONE  no hidden row (hidden_last may be NULL): the K / V rows of the slab are the result (an image prefill).
+ * In the last two modes hidden [batch*q_len][dim] is working memory whose contents are unspecified afterwards (x may still
+ * alias it).  slots / prefix_slots / prefix_len as in md_text_forward_shared, each may be NULL (slots == NULL: sequence b in
+ * slot b, md_text_forward).
+ * What it saves: in the LAST block the decode steps read only K and V of every row, so ln(x) and the [q | k | v] columns of
+ * the packed qkv|fc1 layer run over all rows (K / V leave from the RoPE epilogue as ever) and everything else -- the fc1
+ * columns, attention, proj, fc2, the residual adds -- runs for the kept rows only: the query block of 128 rows that holds
+ * the sequences' last rows, then the `batch` last rows gathered into compact buffers, through the same 256x256 kernel
+ * (MD_TILE_PINNED_ANY_ROWS).
+ * Bits: hidden_last and every K / V row written equal md_text_forward*'s.  The trim applies where that can be promised:
+ * q_len > 1, batch * q_len > 64, the packed qkv|fc1 layer, tile_policy MD_TILE_PINNED, no fp8 prefill / calibration
+ * (m->f8), no e4m3 copy of the cache; everywhere else the call runs the full computation and copies the last rows out, so
+ * a caller never branches.  hidden_mode outside the three values, MD_HIDDEN_LAST with hidden_last NULL or misaligned:
+ * MD_ERR_INVALID_ARG.  Workspace: md_text_workspace_bytes(m, batch, q_len). */
+enum { MD_HIDDEN_ALL = 0, MD_HIDDEN_LAST = 1, MD_HIDDEN_NONE = 2 };
+md_status md_text_forward_trim(const md_text_model* m, const void* x, void* hidden, void* hidden_last, int32_t hidden_mode,
+                               int32_t batch, int32_t q_len, const int32_t* pos0, const int32_t* slots, int32_t n_slots,
+                               const int32_t* prefix_slots, const int32_t* prefix_len, const md_kv_cache* kv, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* LoRA "variant" side path (reference: lora.py:54-79 -> text.py:31-32,55-56 and layers.py:129-146 with lora != None).
  * delta(x) = (x A^T) B^T with A [r][k] and B [n][r] packed as bias-free md_linear (r zero-padded to 64); a pair with

@@ -22,6 +22,8 @@ MD_OK = 0
 ABI_VERSION = 5  # include/moondream_hip.h MD_ABI_VERSION
 MD_EPI_BIAS, MD_EPI_GELU, MD_EPI_RESIDUAL = 0, 1, 2
 MD_TILE_BY_SHAPE, MD_TILE_PINNED, MD_TILE_DECODE_TALL = 0, 1, 2  # md_gemm_args / md_vit_model / md_text_model .tile_policy (ABI 5; 2: round 6)
+MD_TILE_PINNED_ANY_ROWS = 3  # <= 64 rows on the pinned config too (md_text_forward_trim's last block)
+MD_HIDDEN_ALL, MD_HIDDEN_LAST, MD_HIDDEN_NONE = 0, 1, 2  # md_text_forward_trim: the hidden rows the caller keeps
 MD_CROPS_U8_HWC, MD_CROPS_BF16_CHW = 0, 1
 
 c_void_p, c_int32, c_int64, c_size_t, c_float = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float
@@ -222,6 +224,8 @@ SIGNATURES = {
                                         P(MdKvCache), c_void_p, c_size_t, c_void_p]),
     "md_text_forward_shared": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                          c_void_p, c_void_p, P(MdKvCache), c_void_p, c_size_t, c_void_p]),
+    "md_text_forward_trim": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                       c_int32, c_void_p, c_void_p, P(MdKvCache), c_void_p, c_size_t, c_void_p]),
     "md_text_lora_workspace_bytes": (c_size_t, [P(MdTextModel), c_int32, c_int32]),
     "md_text_forward_lora": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, P(MdKvCache),
                                        c_void_p, c_size_t, c_void_p]),

@@ -386,9 +386,9 @@ class ContinuousEngine:
 
         return torch.rand(n, dtype=torch.float32, generator=self._generator(r))
 
-    def _forward_slots(self, x, pos0: int, slots: List[int], variants: Optional[List[int]] = None):
-        """x [k, T, D] -> hidden [k, T, D]; K / V rows written into ``slots``.  ``variants`` with a LoRA row: those per-row
-        bank indices travel with the call."""
+    def _forward_slots(self, x, pos0: int, slots: List[int], variants: Optional[List[int]] = None, keep: str = "last"):
+        """x [k, T, D] -> the last hidden row of every sequence [k, 1, D] (``keep`` "none": nothing, an image prefill); K / V
+        rows written into ``slots``.  ``variants`` with a LoRA row: those per-row bank indices travel with the call."""
         import torch
 
         m = self.model
@@ -396,12 +396,12 @@ class ContinuousEngine:
         var_d = None
         if variants is not None and any(v >= 0 for v in variants):
             var_d = m._h2d(torch.tensor(variants, dtype=torch.int32))
-        hidden = m._text_forward(x, int(pos0), self._rows(slots_d, var_d))
+        hidden = m._text_forward(x, int(pos0), self._rows(slots_d, var_d), keep=keep)
         self.stats.prefill_passes += 1
         return hidden
 
     def _first_tokens(self, hidden, reqs: List[Request]):
-        """hidden [k, T, D] of a prefill -> the first token of each request from its last row, as _prepare_sequences picks it (argmax, or
+        """hidden [k, 1, D], the last rows of a prefill -> the first token of each request from its last row, as _prepare_sequences picks it (argmax, or
         md_sample_top_p with the request's first uniform; no suppression).  lm_head in launches of <= 64 rows: the
         decode-regime kernels, whatever the admission size."""
         import torch
@@ -453,7 +453,7 @@ class ContinuousEngine:
             if raw:
                 bos = m._embed(torch.full((len(raw), 1), tk.bos_id, dtype=torch.int32))
                 x = torch.cat([bos, img_emb], dim=1)
-                self._forward_slots(x, 0, [reqs[i].slot for i in raw], [reqs[i].variant for i in raw])
+                self._forward_slots(x, 0, [reqs[i].slot for i in raw], [reqs[i].variant for i in raw], keep="none")
                 for i in raw:
                     prefix[i] = x.shape[1]
             for i, r in enumerate(reqs):

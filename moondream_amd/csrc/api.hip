@@ -35,7 +35,9 @@ struct TilePolicyScope {
   TilePolicyScope(const TilePolicyScope&) = delete;
   TilePolicyScope& operator=(const TilePolicyScope&) = delete;
 };
-inline bool tile_policy_ok(int p) { return p == MD_TILE_BY_SHAPE || p == MD_TILE_PINNED || p == MD_TILE_DECODE_TALL; }
+inline bool tile_policy_ok(int p) {
+  return p == MD_TILE_BY_SHAPE || p == MD_TILE_PINNED || p == MD_TILE_DECODE_TALL || p == MD_TILE_PINNED_ANY_ROWS;
+}
 
 // Round 6: a decode step (q_len 1) of 65 .. 128 sequences as ONE pass over the weights -- the fused qkv|fc1 GEMM on the 128 x 64
 // weight-streaming tile, proj / fc2 as K-slice partials of 128 rows + the fused tail, lm_head on its by-shape config -- instead of
@@ -139,6 +141,9 @@ struct TextWs {
   // decode regime: fp32 partial products of proj / fc2 (launch-boundary split-K)
   float *part_a, *part_b;
   int64_t part_ld, part_stride;
+  // prefill: the last row of every sequence, compact, for the last block of a call that keeps only those (MD_HIDDEN_LAST):
+  // ln(x) [batch][Dp], the attention output [batch][Dp], gelu(fc1) [batch][fc1.n_pad]
+  void *last_h, *last_att, *last_ff;
   size_t total;
 };
 
@@ -184,6 +189,13 @@ TextWs text_layout(const md_text_model* m, int batch, int q_len, void* base) {
     w.part_a = (float*)a.take((size_t)md_gemm_partial_slices(&b0.proj) * w.part_stride * 4);
     w.part_b = (float*)a.take((size_t)md_gemm_partial_slices(&b0.fc2) * w.part_stride * 4);
   }
+  // (behind everything else: the other buffers stay where they were)
+  w.last_h = w.last_att = w.last_ff = nullptr;
+  if (M > 64 && q_len > 1 && m->blocks[0].qkv_fc1.w) {
+    w.last_h = a.take((size_t)batch * m->blocks[0].qkv.k_pad * 2);
+    w.last_att = a.take((size_t)batch * m->blocks[0].proj.k_pad * 2);
+    w.last_ff = a.take((size_t)batch * m->blocks[0].fc1.n_pad * 2);
+  }
   w.total = a.off;
   return w;
 }
@@ -199,6 +211,30 @@ __global__ __launch_bounds__(256) void rope_rowinfo_kernel(const int32_t* __rest
   const int64_t sb = slots ? slots[b] : b;  // slot table of md_text_forward_slots (prefill: every slot valid)
   if (l < half2) row_cs[(int64_t)m * half2 + l] = freqs[(int64_t)pos * half2 + l];
   if (l == 0) row_kv[m] = (uint32_t)((sb * slab_bs + (int64_t)pos * hd) * 2);
+}
+
+// dst[b] = src[b * q_len + q_len - 1] for up to three row-major bf16 matrices (blockIdx.y), rows as 16-byte chunks: the
+// last row of every sequence, compact
+struct LastRows {
+  const bf16_t* src;
+  int64_t lds;
+  bf16_t* dst;
+  int64_t ldd;
+  int chunks;
+};
+__global__ __launch_bounds__(256) void gather_last_rows_kernel(LastRows s0, LastRows s1, LastRows s2, int q_len) {
+  const LastRows g = blockIdx.y == 0 ? s0 : blockIdx.y == 1 ? s1 : s2;
+  const int64_t b = blockIdx.x, row = b * q_len + q_len - 1;
+  const u32x4* src = (const u32x4*)(g.src + row * g.lds);
+  u32x4* dst = (u32x4*)(g.dst + b * g.ldd);
+  for (int i = threadIdx.x; i < g.chunks; i += 256) dst[i] = src[i];
+}
+md_status gather_last_rows(const LastRows* segs, int n_seg, int batch, int q_len, hipStream_t s) {
+  for (int i = 0; i < n_seg; ++i)
+    MD_CHECK_ARG((((uintptr_t)segs[i].src | (uintptr_t)segs[i].dst) & 15) == 0 && segs[i].lds % 8 == 0 && segs[i].ldd % 8 == 0);
+  hipLaunchKernelGGL(gather_last_rows_kernel, dim3(batch, n_seg), dim3(256), 0, s, segs[0], segs[n_seg > 1 ? 1 : 0],
+                     segs[n_seg > 2 ? 2 : 0], q_len);
+  return md_launch_status();
 }
 
 __global__ void kv_len_kernel(const int32_t* pos0, int32_t* kv_len, int q_len, int n) {
@@ -520,7 +556,9 @@ md_rope_fuse rope_fuse_args(const Fwd& f, int l) {
 
 // rope(q), rope(k), cache update (text.py:42-46) and attention over the slab (text.py:48-51) of block l.  fuse_rope (a decode
 // step, MHA): both inside the attention kernel.  att8: the prefill writes proj's e4m3 operand instead of bf16 rows (fp8 mode).
-md_status rope_and_attention(Fwd& f, int l, int64_t qld, bool fuse_rope, uint8_t* att8 = nullptr, float att8_inv_scale = 0.f) {
+// last_q_block (prefill): only the 128-row query block that holds every sequence's last row -- the rows the caller keeps.
+md_status rope_and_attention(Fwd& f, int l, int64_t qld, bool fuse_rope, uint8_t* att8 = nullptr, float att8_inv_scale = 0.f,
+                             bool last_q_block = false) {
   const md_text_model* m = f.m;
   const md_kv_cache* kv = f.kv;
   bf16_t *kl = layer_slab(kv->k, kv, l), *vl = layer_slab(kv->v, kv, l);
@@ -550,7 +588,8 @@ md_status rope_and_attention(Fwd& f, int l, int64_t qld, bool fuse_rope, uint8_t
       a.o8_ts = f.Dp;
       a.o8_inv_scale = att8_inv_scale;
     }
-    MD_TRY(md_attention_prefill_rows(&a, f.rows, f.s));
+    const int n_qblk = (f.q_len + 127) / 128;
+    MD_TRY(md_attention_prefill_rows(&a, f.rows, f.s, last_q_block ? n_qblk - 1 : 0, last_q_block ? 1 : n_qblk));
   }
   // fp8 mode: the rows this pass wrote (bf16) also go into the e4m3 copy the decode steps read
   if (kv8 && !fuse_rope && !f.rope_done_kv8) MD_TRY(md_kv_quantize_f8_layer(kv, l, f.pos0, 0, f.batch, m->n_heads, f.q_len, f.rows, f.s));
@@ -608,7 +647,9 @@ md_status f8_prefill_block(Fwd& f, int l) {
 }
 
 // qkv = qkv(l_in), with fc1's half of the packed layer when there is one (text.py:30, layers.py:130-138)
-md_status qkv_linear(Fwd& f, int l, const BlockIo& io) {
+// qkv_only (packed layer): the [q | k | v] columns alone -- b.qkv is the view of the packed layer's first rows -- into the same
+// activation rows, through the same kernel and epilogue
+md_status qkv_linear(Fwd& f, int l, const BlockIo& io, bool qkv_only = false) {
   const md_text_block& b = f.m->blocks[l];
   const TextWs& w = f.w;
   if (io.f8w && io.f8w->qkv_fc1.w) {
@@ -619,7 +660,7 @@ md_status qkv_linear(Fwd& f, int l, const BlockIo& io) {
   // one GEMM for both consumers of l_in: [qkv | gelu(fc1)]
   MD_CHECK_ARG(b.qkv_fc1.n_pad == f.qkv_w + b.fc1.n_pad && f.qkv_w % 64 == 0);
   md_gemm_args g;
-  g.a = w.h; g.lda = f.Dp; g.lin = b.qkv_fc1; g.c = w.qkv; g.ldc = io.qld; g.r = nullptr; g.ldr = 0;
+  g.a = w.h; g.lda = f.Dp; g.lin = qkv_only ? b.qkv : b.qkv_fc1; g.c = w.qkv; g.ldc = io.qld; g.r = nullptr; g.ldr = 0;
   g.res_row_mod = 0; g.m = f.M; g.epilogue = MD_EPI_GELU; g.store_pad_cols = 1; g.gelu_from_col = f.qkv_w;
   if (f.rows.bank) g.epilogue = MD_EPI_BIAS;  // GELU after the fc1 delta, in the expand
   g.splitk_ws = w.splitk; g.splitk_ws_bytes = w.splitk_bytes; g.tile_policy = t_tile_policy;
@@ -713,15 +754,66 @@ md_status proj_fc2_residual(Fwd& f, int l, const BlockIo& io) {
   return gemm(w.ff, ffld, b.fc2, x, D, M, MD_EPI_RESIDUAL, x, D, 0, 0, s, w.splitk, w.splitk_bytes);
 }
 
+// Whether the last block of this forward may skip what only the rows the caller does not keep would read (hidden_mode !=
+// MD_HIDDEN_ALL): where the kept rows are promised the bits of the full computation -- a prefill of more than 64 rows on the
+// pinned four-wave tile, the packed [qkv | fc1] layer with qkv / fc1 as row-range views of it, no adapters, no fp8 prefill, no
+// calibration, no e4m3 copy of the cache.
+bool last_block_trim_ok(const Fwd& f) {
+  const md_text_model* m = f.m;
+  const md_text_block& b = m->blocks[m->n_layers - 1];
+  return f.q_len > 1 && f.M > 64 && t_tile_policy == MD_TILE_PINNED && f.rows.bank == nullptr && !f.use_f8 && !f.calib &&
+         !(f.kv->k8 || f.kv->v8) && f.w.last_h != nullptr && b.qkv_fc1.w != nullptr && b.qkv.w == b.qkv_fc1.w &&
+         b.qkv.b == b.qkv_fc1.b && b.qkv.n == f.qkv_w && b.qkv.n_pad == f.qkv_w && b.qkv.k_pad == b.qkv_fc1.k_pad &&
+         b.fc1.w == (const char*)b.qkv_fc1.w + (int64_t)f.qkv_w * b.qkv_fc1.k_pad * 2 && b.qkv_fc1.b != nullptr &&
+         b.fc1.b == (const char*)b.qkv_fc1.b + (int64_t)f.qkv_w * 2 && b.qkv_fc1.n_pad == f.qkv_w + b.fc1.n_pad &&
+         b.fc1.k_pad == b.qkv_fc1.k_pad && b.fc2.k_pad == b.fc1.n_pad && b.proj.n == f.D && b.fc2.n == f.D && f.qkv_w % 64 == 0;
+}
+
+// The last block of a prefill whose caller keeps the last row of every sequence (MD_HIDDEN_LAST) or no hidden row at all
+// (MD_HIDDEN_NONE).  The decode steps read K and V of every row, so ln(x) and the [q | k | v] columns of the packed layer run
+// over all rows (K / V leave from the epilogue as ever); q of the other rows, their attention, proj, fc1 + GELU, fc2 and the
+// residual adds feed nothing.  The kept rows go through the kernels the full block runs, in the positions it gives them where
+// a position matters (the attention's query block), so they get its bits.
+md_status trimmed_last_block(Fwd& f, int l, int hidden_mode, bf16_t* hidden_last) {
+  const md_text_block& b = f.m->blocks[l];
+  const TextWs& w = f.w;
+  const int D = f.D, Dp = f.Dp, B = f.batch;
+  hipStream_t s = f.s;
+  const BlockIo io = block_io(f, l);
+  MD_TRY(md_layernorm_bf16(f.x, D, w.h, Dp, &b.ln, f.M, D, 1e-5f, s));
+  MD_TRY(qkv_linear(f, l, io, true));
+  if (hidden_mode == MD_HIDDEN_NONE) {
+    if (!f.rope_done)  // no RoPE epilogue for this shape: the rows' K / V still have to reach the slab
+      MD_TRY(md_rope_kv_write_slots(w.qkv, io.qld, f.m->freqs, f.pos0, layer_slab(f.kv->k, f.kv, l), layer_slab(f.kv->v, f.kv, l),
+                                    f.kv->batch_stride, f.kv->ctx, B, f.q_len, f.m->n_heads, f.m->n_kv_heads, f.hd, f.m->rot_dim,
+                                    f.rows, s));
+    return MD_OK;
+  }
+  MD_TRY(rope_and_attention(f, l, io.qld, false, nullptr, 0.f, true));
+  const LastRows segs[3] = {{(const bf16_t*)w.h, Dp, (bf16_t*)w.last_h, Dp, Dp / 8},
+                            {(const bf16_t*)w.att, Dp, (bf16_t*)w.last_att, Dp, Dp / 8},
+                            {f.x, D, hidden_last, D, D / 8}};
+  MD_TRY(gather_last_rows(segs, 3, B, f.q_len, s));
+  // <= 64 rows would take the split-K weight-streaming configs (another K association): these launches ask for the layer's
+  // pinned config whatever their row count
+  TilePolicyScope any_rows(MD_TILE_PINNED_ANY_ROWS);
+  const int64_t ffld = b.fc1.n_pad;
+  MD_TRY(gemm(w.last_h, Dp, b.fc1, w.last_ff, ffld, B, MD_EPI_GELU, nullptr, 0, 0, 1, s));
+  MD_TRY(gemm(w.last_att, Dp, b.proj, hidden_last, D, B, MD_EPI_RESIDUAL, hidden_last, D, 0, 0, s));
+  return gemm(w.last_ff, ffld, b.fc2, hidden_last, D, B, MD_EPI_RESIDUAL, hidden_last, D, 0, 0, s);
+}
+
 // reference: text.py:128-160 (text_decoder) with text.py:16-60 (attn), for a prefill or for decode rows that the decode regime
 // takes in one pass.  rows.slots == nullptr: sequence b in slot b (md_text_forward); otherwise every place that addresses a
 // slab -- the RoPE / KV-write epilogue's row offsets, rope_kv_kernel, the prefill and decode attention, the e4m3 copy --
 // takes slot slots[b], and a decode row whose slot is outside [0, n_slots) is idle.  rows.pfx_slots != nullptr
 // (md_text_forward_shared): the prefill and decode attention read keys [0, pfx_len[b]) from slot pfx_slots[b]; every write
-// still goes to slot slots[b].
+// still goes to slot slots[b].  hidden_mode (MD_HIDDEN_*): which rows of the result the caller keeps -- all of them in `hidden`,
+// the last row of every sequence in hidden_last [batch][dim], or none; in the last two `hidden` is working memory, and the last
+// block skips the work only the other rows would read where last_block_trim_ok() holds (elsewhere: the full computation).
 md_status text_forward_rows(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len, const int32_t* pos0,
                             const RowMap& rows_in, const md_kv_cache* kv, bool tall_ok, void* workspace, size_t workspace_bytes,
-                            hipStream_t s) {
+                            hipStream_t s, int hidden_mode = MD_HIDDEN_ALL, void* hidden_last = nullptr) {
   Fwd f = {};
   f.m = m; f.kv = kv; f.rows = rows_in; f.pos0 = pos0; f.batch = batch; f.q_len = q_len; f.s = s;
   if (f.rows.slots == nullptr) f.rows.n_slots = batch;  // the slots a contiguous call addresses
@@ -776,9 +868,11 @@ md_status text_forward_rows(const md_text_model* m, const void* x_in, void* hidd
   f.use_f8 = f.f8p && !f.f8p->calib && f.f8p->blocks && M > 64 && m->blocks[0].qkv_fc1.w != nullptr && qkv_w % 64 == 0;
   if (lora && (f.use_f8 || f.calib)) return MD_ERR_UNSUPPORTED;
   const bool fuse_rope = (q_len == 1) && (m->n_kv_heads == m->n_heads);  // decode step: rope + KV write inside attention
+  const bool trim = hidden_mode != MD_HIDDEN_ALL && m->n_layers > 0 && last_block_trim_ok(f);
 
   for (int l = 0; l < m->n_layers; ++l) {
     const md_text_block& b = m->blocks[l];
+    if (trim && l == m->n_layers - 1) return trimmed_last_block(f, l, hidden_mode, (bf16_t*)hidden_last);
     if (f.use_f8) {
       MD_TRY(f8_prefill_block(f, l));
       continue;
@@ -801,6 +895,10 @@ md_status text_forward_rows(const md_text_model* m, const void* x_in, void* hidd
     MD_CHECK_ARG(b.fc2.k_pad == b.fc1.n_pad);
     MD_TRY(proj_fc2_residual(f, l, io));
   }
+  if (hidden_mode == MD_HIDDEN_LAST) {
+    const LastRows seg = {f.x, D, (bf16_t*)hidden_last, D, D / 8};  // (D = n_heads * 64)
+    return gather_last_rows(&seg, 1, batch, q_len, s);
+  }
   return MD_OK;
 }
 
@@ -820,8 +918,11 @@ md_kv_cache kv_from_slot(const md_kv_cache* kv, int b0) {
 // ~1.5x slower at 128 rows.  With a slot table the slab base stays and the block takes its own entries of every table
 // (RowMap::block); without one the slab base moves.
 md_status text_forward_impl(const md_text_model* m, const void* x_in, void* hidden, int32_t batch, int32_t q_len, const int32_t* pos0,
-                            const RowMap& rows, const md_kv_cache* kv, void* workspace, size_t workspace_bytes, void* stream) {
+                            const RowMap& rows, const md_kv_cache* kv, void* workspace, size_t workspace_bytes, void* stream,
+                            int hidden_mode = MD_HIDDEN_ALL, void* hidden_last = nullptr) {
   MD_CHECK_ARG(m && x_in && hidden && pos0 && kv && kv->k && kv->v && workspace && m->blocks);
+  MD_CHECK_ARG(hidden_mode == MD_HIDDEN_ALL || hidden_mode == MD_HIDDEN_LAST || hidden_mode == MD_HIDDEN_NONE);
+  MD_CHECK_ARG(hidden_mode != MD_HIDDEN_LAST || (hidden_last != nullptr && ((uintptr_t)hidden_last & 15) == 0));
   MD_CHECK_ARG(batch > 0 && q_len > 0 && m->dim % m->n_heads == 0);
   MD_CHECK_ARG(rows.slots == nullptr || rows.n_slots > 0);
   MD_CHECK_ARG(tile_policy_ok(m->tile_policy));
@@ -834,7 +935,8 @@ md_status text_forward_impl(const md_text_model* m, const void* x_in, void* hidd
     const int nb = std::min(block_rows, batch - b0);
     const md_kv_cache sub = kv_from_slot(kv, rows.slots ? 0 : b0);
     MD_TRY(text_forward_rows(m, (const char*)x_in + (int64_t)b0 * m->dim * 2, (char*)hidden + (int64_t)b0 * m->dim * 2, nb, q_len,
-                             pos0 + b0, rows.block(b0), &sub, tall_ok, workspace, workspace_bytes, s));
+                             pos0 + b0, rows.block(b0), &sub, tall_ok, workspace, workspace_bytes, s, hidden_mode,
+                             hidden_last ? (char*)hidden_last + (int64_t)b0 * m->dim * 2 : nullptr));
   }
   return MD_OK;
 }
@@ -870,6 +972,17 @@ extern "C" md_status md_text_forward_shared(const md_text_model* m, const void* 
   const RowMap rows{slots, n_slots, prefix_slots, prefix_len};
   MD_TRY(shared_args_ok(kv, rows));
   return text_forward_impl(m, x_in, hidden, batch, q_len, pos0, rows, kv, workspace, workspace_bytes, stream);
+}
+
+extern "C" md_status md_text_forward_trim(const md_text_model* m, const void* x_in, void* hidden, void* hidden_last,
+                                          int32_t hidden_mode, int32_t batch, int32_t q_len, const int32_t* pos0,
+                                          const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
+                                          const int32_t* prefix_len, const md_kv_cache* kv, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  const RowMap rows{slots, n_slots, prefix_slots, prefix_len};
+  if (prefix_slots != nullptr) MD_TRY(shared_args_ok(kv, rows));
+  return text_forward_impl(m, x_in, hidden, batch, q_len, pos0, rows, kv, workspace, workspace_bytes, stream, hidden_mode,
+                           hidden_last);
 }
 
 // ------------------------------------------------------------- LoRA side path

@@ -44,6 +44,7 @@ struct AttnK {
   const int32_t* kv_len;
   float scale_log2;  // scale * log2(e)
   int n_qblk, n_bh, n_heads;  // XCD-aware 1-D grid of the LDS-DMA kernels
+  int q_blk0;                 // first 128-row query block of the launch (n_qblk = the blocks it runs)
   uint8_t* o8;                // opt-in FP8 mode: the output row as e4m3 bytes as well (md_attn_args.o8), or nullptr
   int64_t o8_bs, o8_ts;
   float o8_inv_scale;
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const AttnK p) {
   const int q_pos0 = p.q_pos0 ? p.q_pos0[b] : 0;
   const int kv_len = p.kv_len ? p.kv_len[b] : p.kv_len_all;
 
-  const int q_blk0 = blockIdx.x * 128;
+  const int q_blk0 = (p.q_blk0 + blockIdx.x) * 128;
   const int q_row0 = q_blk0 + wave * 32;
   const int q_row = min(q_row0 + l31, p.q_len - 1);  // clamp: padding rows replay a valid row
   const int qpos = q_pos0 + q_row;
@@ -375,7 +376,7 @@ __global__ __launch_bounds__(256) void attn_prefill_dma_kernel(const AttnK p) {
   const int q_pos0 = p.q_pos0 ? p.q_pos0[b] : 0;
   const int kv_len = p.kv_len ? p.kv_len[b] : p.kv_len_all;
 
-  const int q_blk0 = (slot % p.n_qblk) * 128;
+  const int q_blk0 = (p.q_blk0 + slot % p.n_qblk) * 128;
   const int q_row0 = q_blk0 + wave * 32;
   const int q_row = min(q_row0 + l31, p.q_len - 1);
   const int qpos = q_pos0 + q_row;
@@ -1148,7 +1149,7 @@ __global__ __launch_bounds__(1024) void attn_decode_shared_kernel(const bf16_t* 
 
 // internal (api.hip): md_attention_prefill with the slot table of md_text_forward_slots (rows.slots == nullptr: slot b) and the
 // shared prefix table of md_text_forward_shared (rows.pfx_slots == nullptr: none)
-md_status md_attention_prefill_rows(const md_attn_args* a, const RowMap& rows, hipStream_t stream) {
+md_status md_attention_prefill_rows(const md_attn_args* a, const RowMap& rows, hipStream_t stream, int q_blk0, int n_q_blks) {
   MD_CHECK_ARG(a && a->q && a->k && a->v && (a->o || a->o8));
   MD_CHECK_ARG(a->batch > 0 && a->n_heads > 0 && a->n_kv_heads > 0 && a->q_len > 0);
   MD_CHECK_ARG(a->n_heads % a->n_kv_heads == 0);
@@ -1187,7 +1188,11 @@ md_status md_attention_prefill_rows(const md_attn_args* a, const RowMap& rows, h
   k.o8_ts = a->o8_ts;
   k.o8_inv_scale = a->o8_inv_scale;
   k.head_dim = a->head_dim;
-  k.n_qblk = (a->q_len + 127) / 128;
+  const int all_qblk = (a->q_len + 127) / 128;
+  if (n_q_blks < 0) n_q_blks = all_qblk - q_blk0;
+  MD_CHECK_ARG(q_blk0 >= 0 && n_q_blks > 0 && q_blk0 + n_q_blks <= all_qblk);
+  k.q_blk0 = q_blk0;
+  k.n_qblk = n_q_blks;
   k.n_bh = a->batch * a->n_heads;
   k.n_heads = a->n_heads;
   // MD_ATTN_VARIANT = reg | dma (default) | pipe for A/B runs

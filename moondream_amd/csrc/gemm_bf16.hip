@@ -740,6 +740,9 @@ int pick_tile(int M, int n_store, int K, int policy) {
   // the 256x256 kernel (16x16x32 MFMAs; the small-shape configs below multiply with 32x32x16: equal to fp32 rounding, not
   // bitwise), so that a sequence gets the same bits alone and in a batch
   if (policy == MD_TILE_PINNED && M > 64) return knobs().w4 ? 20 : 11;
+  // MD_TILE_PINNED_ANY_ROWS: the same config at <= 64 rows too -- a few rows of a pinned launch recomputed on their own get the
+  // bits the whole launch gives them (the kernels drop rows past m by range check)
+  if (policy == MD_TILE_PINNED_ANY_ROWS) return knobs().w4 ? 20 : 11;
   // MD_TILE_DECODE_TALL: 65 .. 128 rows of a decode step -- the 128 x 64 weight-streaming tile (21), except for the widest layers
   // (lm_head: 800 column panels keep every CU busy with the 128 x 128 two-stage config, measured 57 vs 73 us); every config
   // involved multiplies with 32x32x16 in the same K order as the 64-row decode configs
@@ -824,14 +827,16 @@ md_status gemm_dispatch(const md_gemm_args* a, void* stream, const md_rope_fuse*
   k.partial_ld = k.partial_slice_stride = 0;
   k.nt = knobs().nt;  // decode regime: non-temporal weight stream (kernel-level +2..10 %, nothing end to end)
   hipStream_t s = (hipStream_t)stream;
-  MD_CHECK_ARG(a->tile_policy == MD_TILE_BY_SHAPE || a->tile_policy == MD_TILE_PINNED || a->tile_policy == MD_TILE_DECODE_TALL);
+  MD_CHECK_ARG(a->tile_policy == MD_TILE_BY_SHAPE || a->tile_policy == MD_TILE_PINNED || a->tile_policy == MD_TILE_DECODE_TALL ||
+               a->tile_policy == MD_TILE_PINNED_ANY_ROWS);
+  const bool pinned = a->tile_policy == MD_TILE_PINNED || a->tile_policy == MD_TILE_PINNED_ANY_ROWS;
   int tile = pick_tile(k.M, k.n_store, k.K, a->tile_policy);
   k.slices = 1;
   k.slabs = nullptr;
   k.tickets = nullptr;
   const bool forced = knobs().tile >= 0;
   if (tile == 20 && !md_gemm_w4_takes(k, a->epilogue)) {
-    if (a->tile_policy != MD_TILE_PINNED) {
+    if (!pinned) {
       tile = 11;
     } else {
       // MD_TILE_PINNED promises that the tile config is a function of the layer alone; the four-wave kernel's 32-bit offsets
@@ -881,7 +886,7 @@ md_status gemm_dispatch(const md_gemm_args* a, void* stream, const md_rope_fuse*
     if (knobs().persist && tiles > 256) tile = 15;
   }
   const bool tall = (tile == 21 && a->m > 64 && a->m <= 128 && !forced);  // MD_TILE_DECODE_TALL: the 128-row weight-streaming tile
-  if ((a->m <= 64 || tall) && !forced) {
+  if ((a->m <= 64 || tall) && !forced && a->tile_policy != MD_TILE_PINNED_ANY_ROWS) {
     if (!tall) tile = decode_cfg();
     // in-launch split-K exactly where the 64-row regime splits (a function of the layer shape): the same slices, the same
     // slab summation order -- a row gets the same bits in a 128-row launch as in a 64-row one

@@ -47,7 +47,9 @@ struct DecodeAttn {
 
 // attention.hip
 md_status md_attention_decode_rows(const DecodeAttn& d, const RowMap& rows, hipStream_t stream);
-md_status md_attention_prefill_rows(const md_attn_args* a, const RowMap& rows, hipStream_t stream);
+// q_blk0, n_q_blks: the 128-row query blocks [q_blk0, q_blk0 + n_q_blks) only (n_q_blks < 0: all of them); a row of a block that
+// runs sits in the workgroup and wave it has in the full launch
+md_status md_attention_prefill_rows(const md_attn_args* a, const RowMap& rows, hipStream_t stream, int q_blk0 = 0, int n_q_blks = -1);
 // attention_f8kv.hip
 md_status md_attention_decode_f8_rows(const DecodeAttn& d, const RowMap& rows, hipStream_t stream);
 md_status md_kv_quantize_f8_layer(const md_kv_cache* kv, int layer, const int32_t* pos0, int pos_fixed, int batch, int n_heads,

@@ -270,6 +270,9 @@ class MoondreamModel:
         # all decoder blocks; False = the batched kernels at one row (bit-identical to a row of a batch)
         self.single_sequence_kernel = True
         self.strict_batch_invariance = False  # see set_strict_batch_invariance
+        # prefills whose caller keeps only the last row of each sequence (or none) skip the last block's work on the other rows
+        # (md_text_forward_trim; same bits).  False: the all-rows entry points and a slice -- A/B and tests.
+        self.prefill_trim = True
         self._tile_policy = _lib.MD_TILE_BY_SHAPE  # of the call in flight: _select_kernels
         self._b1_sync = None  # barrier state of that kernel: zeroed once, then owned by it
         self._b1_used = False
@@ -594,8 +597,12 @@ class MoondreamModel:
         return st
 
     def _text_forward(self, x: torch.Tensor, pos0: Union[int, Sequence[int]], rows: Union[int, _Rows] = 0, causal: bool = False,
-                      pos_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      pos_dev: Optional[torch.Tensor] = None, keep: str = "all") -> Optional[torch.Tensor]:
         """x [B,T,D] embeddings -> hidden [B,T,D]; K,V written at pos0[b]..pos0[b]+T-1.
+        ``keep``: the hidden rows the caller reads -- "all", "last" (returns [B,1,D], the last row of every sequence: what
+        lm_head and the first decode step take from a prefill) or "none" (returns None: the K / V rows are the result).  The
+        last two go to md_text_forward_trim, which skips the last block's work on the other rows (``prefill_trim`` off, or
+        a LoRA routing: the all-rows entry point and a slice -- the same bits).
         ``pos0`` is host data (one int for the whole batch or one per sequence): the slab has
         max_context slots per head and the kernels do not bounds-check, so the check is here
         (the reference fails at this point too: its index_put / mask indexing raises).
@@ -612,8 +619,8 @@ class MoondreamModel:
             outs = []
             for i0 in range(0, b, per):
                 p0 = pos0 if isinstance(pos0, int) else list(pos0)[i0 : i0 + per]
-                outs.append(self._text_forward(x[i0 : i0 + per], p0, rows.sub(i0, min(b, i0 + per)), causal=causal))
-            return torch.cat(outs, dim=0)
+                outs.append(self._text_forward(x[i0 : i0 + per], p0, rows.sub(i0, min(b, i0 + per)), causal=causal, keep=keep))
+            return None if keep == "none" else torch.cat(outs, dim=0)
         hi = pos0 if isinstance(pos0, int) else max(int(p) for p in pos0)
         lo = pos0 if isinstance(pos0, int) else min(int(p) for p in pos0)
         if lo < 0 or hi + t > self.config.text.max_context:
@@ -638,6 +645,19 @@ class MoondreamModel:
         hidden = torch.empty_like(x)
         kv = self._kv_struct(rows.slot0)
         ws = self._workspace(getattr(self.lib, rows.forward_ws_entry)(C.byref(text), *rows.bank_arg(), b, t))
+        assert keep in ("all", "last", "none")
+        if keep != "all" and self.prefill_trim and rows.kind in ("", "_slots", "_shared"):
+            last = torch.empty(b, 1, d, dtype=x.dtype, device=x.device) if keep == "last" else None
+            tables = [tab.data_ptr() if tab is not None else None for tab in (rows.slots, rows.prefix_slots, rows.prefix_len)]
+            _lib.check(
+                self.lib.md_text_forward_trim(
+                    C.byref(text), x.data_ptr(), hidden.data_ptr(), last.data_ptr() if last is not None else None,
+                    _lib.MD_HIDDEN_LAST if keep == "last" else _lib.MD_HIDDEN_NONE, b, t, pos0.data_ptr(), tables[0], rows.n_slots,
+                    tables[1], tables[2], C.byref(kv), ws.data_ptr(), ws.numel(), self._stream(),
+                ),
+                "md_text_forward_trim",
+            )
+            return last
         # one call site for md_text_forward and its _slots / _shared / _multi_lora (grouped LoRA kernels, csrc/lora_multi.hip) /
         # _lora (unfused kernels + low-rank pairs: text.py:31-32,55-56; layers.py:129-146) forms
         _lib.check(
@@ -647,7 +667,9 @@ class MoondreamModel:
             ),
             rows.forward_entry,
         )
-        return hidden
+        if keep == "last":
+            return hidden[:, -1:, :].contiguous()
+        return hidden if keep == "all" else None
 
     def _decode_ws_bytes(self, rows: _Rows, b: int) -> int:
         """The workspace of a decode step over b rows routed by ``rows``."""
@@ -991,7 +1013,7 @@ class MoondreamModel:
         b = img_emb.shape[0]
         bos = self._embed(torch.full((b, 1), self.config.tokenizer.bos_id, dtype=torch.int32))
         x = torch.cat([bos, img_emb], dim=1)
-        self._text_forward(x, 0, rows)
+        self._text_forward(x, 0, rows, keep="none")
         return x.shape[1]
 
     def encode_image(self, image: Union[Image.Image, EncodedImage], settings: Optional[dict] = None) -> EncodedImage:
@@ -1057,13 +1079,15 @@ class MoondreamModel:
         return nxt
 
     # ---------------------------------------------------------- batched engine
-    def _prefill_prompts(self, prompts: Sequence[Sequence[int]], pos: int, rows: Union[int, _Rows] = 0, prompt_embs=None):
+    def _prefill_prompts(self, prompts: Sequence[Sequence[int]], pos: int, rows: Union[int, _Rows] = 0, prompt_embs=None,
+                         last_only: bool = False):
         """Prefill B equal-length prompts at position ``pos``; returns (logits [B,V], hidden [B,T,D], pos+T).
+        ``last_only``: for a caller that reads the logits alone -- hidden is [B,1,D], the last row of every sequence.
         reference: moondream.py:280-321 (per sequence)."""
         b = len(prompts)
         ids = torch.tensor(prompts, dtype=torch.int32)
         x = self._embed(ids) if prompt_embs is None else prompt_embs
-        hidden = self._text_forward(x, pos, rows)
+        hidden = self._text_forward(x, pos, rows, keep="last" if last_only else "all")
         return self._lm_head(hidden), hidden, pos + ids.shape[1]
 
     def _decode_greedy(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
@@ -1277,7 +1301,7 @@ class MoondreamModel:
         next_pos = [0] * b
         for r0, r1 in groups:
             x = embed(r0, r1)
-            hidden = self._text_forward(x, pos, rows.sub(r0, r1))
+            hidden = self._text_forward(x, pos, rows.sub(r0, r1), keep="last")  # [r1-r0, 1, D]
             logits = self._lm_head(hidden)
             if logits_capture is not None:
                 logits_capture[r0:r1] = logits
@@ -1650,11 +1674,11 @@ class MoondreamModel:
                             x = self._prefill_arena(nb, 1 + n_img + n_pr, tk.bos_id)
                             x[:, 1 : 1 + n_img].copy_(img_emb)
                             x[:, 1 + n_img :].copy_(self._embed(torch.tensor(prompts, dtype=torch.int32)))
-                            logits = self._lm_head(self._text_forward(x, 0, slot0))
+                            logits = self._lm_head(self._text_forward(x, 0, slot0, keep="last"))
                             p1 = x.shape[1]
                         else:
                             pos = self._prefill_images(img_emb, slot0)
-                            logits, _, p1 = self._prefill_prompts(prompts, pos, slot0)
+                            logits, _, p1 = self._prefill_prompts(prompts, pos, slot0, last_only=True)
                         firsts.append(self._pick(logits, 0.0, 0.0))
                     p1s.append(p1)
                     sizes.append(nb)
