@@ -249,8 +249,21 @@ md_status md_amax_bf16(const void* x, int64_t ldx, int32_t rows, int32_t cols, f
  * knobs at run time (the same knobs are read once from MD_GEMM_* / MD_DECODE_* environment
  * variables at first use).  PROCESS-WIDE and not thread-safe: for sweeps and A/B tests only; nothing that decides the
  * bits of a product call lives here (that is md_gemm_args.tile_policy, per call).  The complete key list:
- *   "tile"          -1 = automatic; 20 = four-wave 256x256, 11 / 15 = the eight-wave 256x256 baselines, 1 = 256x128,
- *                   2 = 128x128, 16 / 10 / 3 = decode-regime configs (forces the config for every launch)
+ *   "tile"          -1 = automatic; otherwise the id of a tile config, forced for every launch (the table of
+ *                   csrc/gemm_bf16.hip, one row per id; an id it does not have runs 2):
+ *                      1  256x128, eight waves, two-stage ring
+ *                      2  128x128, four waves, two-stage ring (what an unknown id runs, too)
+ *                      3  decode regime: 64x128 tiles, two waves, 4-deep ring
+ *                     10  decode regime: 64x64 tiles, two waves, no helper waves
+ *                     11  eight-wave 256x256 baseline of 20: alternating wave groups, 2 slices ahead
+ *                     15  11 with a persistent tile loop
+ *                     16  decode regime (default): 64x64 tiles, two compute waves + two DMA-only helper waves
+ *                     17  decode regime: 64x64 tiles, FOUR compute waves + helpers, 128-wide K slices where the layer allows
+ *                     18  17's four compute waves on 64-wide K slices
+ *                     19  16's two compute waves on 128-wide K slices where the layer allows
+ *                     20  four-wave 256x256 (16x16x32 MFMAs), persistent: the default for large launches
+ *                     21  decode regime at 65 .. 128 rows (MD_TILE_DECODE_TALL): 128x64 tiles, four compute waves x 32 rows + helpers
+ *                   Every id but 20 multiplies with 32x32x16 MFMAs.
  *   "small_m_rule"  tile rule of MD_TILE_BY_SHAPE launches: 1 (default) = round 5's (the 128x128 config for up to 512 tiles
  *                   of 128x128), 0 = round 2's (the cost model above 128 such tiles), n > 1 = n tiles instead of 512; same
  *                   bits either way
@@ -259,7 +272,7 @@ md_status md_amax_bf16(const void* x, int64_t ldx, int32_t rows, int32_t cols, f
  *   "persist"       0: eight-wave kernels without their persistent tile loop
  *   "group_m"       row panels per tile-order group (0 = by shape)
  *   "decode_nt"     1: decode-regime weights streamed non-temporally
- *   "decode_cfg"    16 (default) / 10 / 3: decode-regime tile config
+ *   "decode_cfg"    16 (default) / 17 / 18 / 19 / 10 / 3: the decode-regime tile config of launches of <= 64 rows
  *   "decode_slices" K slices per decode-regime tile (0 = by shape)
  *   "rope_fuse"     0: prefill RoPE + KV write as their own kernel instead of the qkv GEMM's epilogue
  *   "attn_skip_dead"  (not a GEMM key; the library's one tuning entry point) exact work skipping of md_attention_prefill:

@@ -29,8 +29,10 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -46,6 +48,63 @@ struct ProfRec {
 bool g_prof_on = false;
 std::vector<ProfRec> g_prof;
 
+// The tile configs, one row per id.  The ids are public (md_gemm_set_tuning "tile" / "decode_cfg", MD_GEMM_TILE,
+// MD_DECODE_CFG, tools/, tests/) and never renumbered; include/moondream_hip.h repeats the descriptions.  A new config is a
+// new row here: launch_row instantiates its kernel, and the decode-regime selector, the split-K geometry and the
+// MD_DECODE_CFG parser read its columns.
+struct TileCfg {
+  int id;
+  int BM, BN, WM, WN, STAGES, BKT, PP, XW;  // launch_cfg's template arguments
+  bool four_wave;   // gemm_w4.hip's kernel (16x16x32 MFMAs, its own launcher); every other row multiplies with 32x32x16
+  bool decode;      // decode-regime (weight-streaming) config: the only rows that may run with SPLITK
+  int k64;          // rows with 128-wide K slices: the id with the same waves on 64-wide ones (fit_k_slices); 0 = none
+  const char* env;  // MD_DECODE_CFG value that selects the row (a prefix match), or nullptr
+  const char* what;
+};
+constexpr TileCfg TILES[] = {
+    // id  BM   BN  WM WN ST BKT PP XW  4-wave decode k64 env
+    {1, 256, 128, 4, 2, 2, 64, 0, 0, false, false, 0, nullptr, "256x128, eight waves, two-stage ring"},
+    {2, 128, 128, 2, 2, 2, 64, 0, 0, false, false, 0, nullptr, "128x128, four waves, two-stage ring (what an unknown id runs, too)"},
+    {3, 64, 128, 1, 2, 4, 64, 0, 0, false, true, 0, "d", "decode regime: 64x128 tiles, two waves, 4-deep ring"},
+    // twice the tiles of 64x128 -> the wide fused layer needs no split-K, the N = 2048 layers get 16 KiB slabs
+    {10, 64, 64, 2, 1, 4, 64, 0, 0, false, true, 0, "6", "decode regime: 64x64 tiles, two waves, no helper waves"},
+    // the eight-wave 256x256 kernels the four-wave one replaced, kept as its A/B baseline (MD_GEMM_W4=0)
+    {11, 256, 256, 2, 4, 4, 32, 2, 0, false, false, 0, nullptr, "eight-wave 256x256 baseline of 20: alternating wave groups, 2 slices ahead"},
+    {15, 256, 256, 2, 4, 4, 32, 3, 0, false, false, 0, nullptr, "11 with a persistent tile loop"},
+    {16, 64, 64, 2, 1, 4, 64, 0, 2, false, true, 0, "16", "decode regime (default): 64x64 tiles, two compute waves + two DMA-only helper waves"},
+    // round 5: 2 x 2 wave tiles of 32 x 32 (one MFMA and two fragment reads per wave and K step instead of two and three on two
+    // of the four SIMDs).  Same K order per output element as 16 / 10: bit-identical results.  18 and 19 are its two
+    // ingredients on their own (A/B).
+    {17, 64, 64, 2, 2, 4, 128, 0, 2, false, true, 18, "17", "decode regime: 64x64 tiles, FOUR compute waves + helpers, 128-wide K slices where the layer allows"},
+    {18, 64, 64, 2, 2, 4, 64, 0, 2, false, true, 0, "18", "17's four compute waves on 64-wide K slices"},
+    {19, 64, 64, 2, 1, 4, 128, 0, 2, false, true, 16, "19", "16's two compute waves on 128-wide K slices where the layer allows"},
+    {20, 256, 256, 2, 2, 2, 64, 0, 0, true, false, 0, nullptr, "four-wave 256x256 (16x16x32 MFMAs), persistent: the default for large launches"},
+    // round 6: one weight panel per 128 rows instead of one per 64.  Same K order per output element as 16.
+    {21, 128, 64, 4, 1, 4, 64, 0, 2, false, true, 0, nullptr, "decode regime at 65 .. 128 rows (MD_TILE_DECODE_TALL): 128x64 tiles, four compute waves x 32 rows + helpers"},
+};
+constexpr int N_TILES = sizeof(TILES) / sizeof(TILES[0]);
+constexpr int tile_index(int id) {
+  for (int i = 0; i < N_TILES; ++i)
+    if (TILES[i].id == id) return i;
+  return -1;
+}
+constexpr const TileCfg& tile_row(int id) { return TILES[tile_index(id)]; }  // an id of the table
+const TileCfg* find_tile(int id) { return tile_index(id) < 0 ? nullptr : &TILES[tile_index(id)]; }
+constexpr bool tiles_ok() {
+  for (int i = 0; i < N_TILES; ++i) {
+    const TileCfg& t = TILES[i];
+    if (tile_index(t.id) != i) return false;  // ids are unique
+    if (t.k64 != 0) {
+      const TileCfg& n = tile_row(t.k64);
+      if (t.BKT != 128 || n.BKT != 64 || n.BM != t.BM || n.BN != t.BN || n.WM != t.WM || n.WN != t.WN || n.STAGES != t.STAGES || n.XW != t.XW)
+        return false;
+    }
+  }
+  return true;
+}
+static_assert(tiles_ok(), "tile table");
+constexpr int TILE_FALLBACK = 2, TILE_TALL = 21;
+
 // Experiment knobs, read ONCE (A/B runs; the product path never sets them).
 struct Knobs {
   int tile = -1;       // MD_GEMM_TILE: force a tile config
@@ -53,7 +112,7 @@ struct Knobs {
   int w4 = 1;          // MD_GEMM_W4=0: the eight-wave 256x256 kernels instead of the four-wave one
   int persist = 1;     // MD_GEMM_PERSIST=0 (eight-wave kernels only)
   int nt = 0;          // MD_DECODE_NT=1: stream decode-regime weights non-temporally
-  int decode_cfg = 16; // MD_DECODE_CFG: d / 6 = alternatives to the 64x64 + helper-waves config
+  int decode_cfg = 16; // MD_DECODE_CFG: the TileCfg::env code of a decode-regime row
   int decode_slices = 0;  // MD_DECODE_SLICES
   int rope_fuse = 1;      // MD_ROPE_FUSE=0: prefill RoPE + KV write as their own kernel again (A/B, tests)
   int small_m_rule = 1;   // MD_SMALL_M_RULE=0: round 2's single-image tile rule (cost model for everything above 128 tiles of 128 x 128)
@@ -67,11 +126,9 @@ struct Knobs {
     decode_slices = geti("MD_DECODE_SLICES", 0);
     rope_fuse = geti("MD_ROPE_FUSE", 1);
     small_m_rule = geti("MD_SMALL_M_RULE", 1);
-    if (const char* dc = getenv("MD_DECODE_CFG")) {
-      if (dc[0] == 'd') decode_cfg = 3;
-      else if (dc[0] == '6') decode_cfg = 10;
-      else if (dc[0] == '1' && dc[1] >= '6' && dc[1] <= '9') decode_cfg = 10 + (dc[1] - '0');  // "16" .. "19"
-    }
+    if (const char* dc = getenv("MD_DECODE_CFG"))
+      for (const TileCfg& t : TILES)
+        if (t.env && strncmp(dc, t.env, strlen(t.env)) == 0) decode_cfg = t.id;
   }
 };
 Knobs& knobs() {
@@ -654,66 +711,87 @@ md_status launch_cfg(const GemmK& k, hipStream_t stream) {
   return md_launch_status();
 }
 
-constexpr int DEC_STAGES = 4;  // decode-regime ring: 3 x 24 KiB slices in flight per workgroup
+// The one place a table row becomes a kernel: launch_cfg with the row's columns, SPLITK where the launch splits K (in-launch
+// slices, or launch-boundary partials, which the kernels store on their SPLITK path only).
+template <int I, int EPI>
+md_status launch_row(const GemmK& k, hipStream_t stream) {
+  constexpr TileCfg t = TILES[I];
+  if constexpr (t.four_wave) {
+    return md_gemm_w4_launch(k, EPI, stream);
+  } else {
+    if constexpr (t.decode)
+      if (k.slices > 1 || k.partial != nullptr)
+        return launch_cfg<t.BM, t.BN, t.WM, t.WN, EPI, true, t.STAGES, t.BKT, t.PP, t.XW>(k, stream);
+    return launch_cfg<t.BM, t.BN, t.WM, t.WN, EPI, false, t.STAGES, t.BKT, t.PP, t.XW>(k, stream);
+  }
+}
+template <int EPI, int... I>
+md_status launch_id(const GemmK& k, int id, hipStream_t stream, std::integer_sequence<int, I...>) {
+  md_status st = MD_OK;
+  const bool known = ((TILES[I].id == id && ((st = launch_row<I, EPI>(k, stream)), true)) || ...);
+  return known ? st : launch_row<tile_index(TILE_FALLBACK), EPI>(k, stream);
+}
+template <int EPI>
+md_status launch_id(const GemmK& k, int id, hipStream_t stream) {
+  return launch_id<EPI>(k, id, stream, std::make_integer_sequence<int, N_TILES>{});
+}
+
+// Decode regime (m <= 64, and 65 .. 128 rows under MD_TILE_DECODE_TALL): the layer is a weight stream, and K is split over
+// S workgroups per tile so that ~256+ workgroups pull from HBM.  Three entry points launch these configs, and they differ on
+// purpose:
+enum Entry { IN_LAUNCH = 0, PARTIAL_ONE = 1, PARTIAL_PAIR = 2 };  // md_gemm_bf16 / md_gemm_partial_f32 / md_gemm_partial_f32_pair
+struct EntryRule {
+  bool wide_k;      // a row's 128-wide K slices may run
+  int not_64x64;    // what runs when decode_cfg names no 64x64 row (id 3 above all); 0 = the id as named
+  int tall_stages;  // ring depth of the 128x64 tile where it is not the row's own (0); MD_TALL_PAIR_STAGES overrides it (A/B)
+};
+constexpr EntryRule ENTRY_RULES[3] = {
+    {true, 0, 0},
+    // the partial entry points slice K by md_gemm_partial_slices, whatever the config: 64-wide slices always (64 KiB of ring =
+    // TWO workgroups per CU, and the pair makes 512), and a 64x128 config runs as 64x64 without helpers
+    {false, 10, 0},
+    // the tall pair on 3 stages = 72 KiB of ring: TWO workgroups per CU, all 512 of the pair resident at once (18.6 us against
+    // 20.3 with 4 stages)
+    {false, 10, 3},
+};
+constexpr size_t TICKET_BYTES = 8192;
+
+int decode_cfg() { return knobs().decode_cfg; }
+// the 64x64 row decode_cfg names, or nullptr
+const TileCfg* row_64x64(int cfg) {
+  const TileCfg* t = find_tile(cfg);
+  return t && t->decode && t->BM == 64 && t->BN == 64 ? t : nullptr;
+}
+
+struct DecodeRun {
+  int id;      // the table row that runs (an id the table does not have: launch_id's fallback)
+  int stages;  // its ring depth
+};
+DecodeRun select_decode(int cfg, bool tall, Entry e) {
+  const EntryRule& r = ENTRY_RULES[e];
+  if (tall) {
+    static const char* const env = getenv("MD_TALL_PAIR_STAGES");
+    return {TILE_TALL, !r.tall_stages ? tile_row(TILE_TALL).STAGES : env ? atoi(env) : r.tall_stages};
+  }
+  const TileCfg* t = row_64x64(cfg);
+  const int id = !t ? (r.not_64x64 ? r.not_64x64 : cfg) : (!r.wide_k && t->k64) ? t->k64 : cfg;
+  return {id, find_tile(id) ? find_tile(id)->STAGES : 0};
+}
+
+// 128-wide K slices only where K and every K-slice range are a multiple of 128; elsewhere the same waves on 64-wide slices
+int fit_k_slices(int id, const GemmK& k) {
+  const TileCfg* t = find_tile(id);
+  if (!t || t->k64 == 0) return id;
+  return k.K % 128 == 0 && (k.slices <= 1 || (k.K / 64) % (2 * k.slices) == 0) ? id : t->k64;
+}
 
 template <int EPI>
 md_status launch_epi(const GemmK& k, int tile, hipStream_t stream) {
-  switch (tile) {
-    case 20: return md_gemm_w4_launch(k, EPI, stream);                              // 256x256, four waves (gemm_w4.hip)
-    case 1: return launch_cfg<256, 128, 4, 2, EPI>(k, stream);
-    case 3: return k.slices > 1 ? launch_cfg<64, 128, 1, 2, EPI, true, DEC_STAGES>(k, stream)
-                                : launch_cfg<64, 128, 1, 2, EPI, false, DEC_STAGES>(k, stream);
-    // decode regime, 64x64 tiles: twice the tiles of 64x128 -> the wide fused layer needs no
-    // split-K, the N = 2048 layers get 16 KiB slabs
-    case 10: return k.slices > 1 ? launch_cfg<64, 64, 2, 1, EPI, true, 4>(k, stream)
-                                 : launch_cfg<64, 64, 2, 1, EPI, false, 4>(k, stream);
-    // the eight-wave 256x256 kernels the four-wave one replaced, kept as its A/B baseline (MD_GEMM_W4=0)
-    case 11: return launch_cfg<256, 256, 2, 4, EPI, false, 4, 32, 2>(k, stream);  // alternating wave groups, 2 slices ahead
-    case 15: return launch_cfg<256, 256, 2, 4, EPI, false, 4, 32, 3>(k, stream);  // alternating + persistent tile loop
-    // decode regime, 64x64 tiles + two DMA-only helper waves (4 waves issue the stream)
-    case 16: return k.slices > 1 ? launch_cfg<64, 64, 2, 1, EPI, true, 4, 64, 0, 2>(k, stream)
-                                 : launch_cfg<64, 64, 2, 1, EPI, false, 4, 64, 0, 2>(k, stream);
-    // round 5: FOUR compute waves (2 x 2 wave tiles of 32 x 32: one MFMA and two fragment reads per wave and K step instead of two and
-    // three on two of the four SIMDs) + the two DMA-only helpers, and 128-wide K slices where the layer allows it (K and every
-    // K-slice range a multiple of 128).  Same K order per output element as 16 / 10: bit-identical results.
-    case 17:
-      if (k.K % 128 == 0 && (k.slices <= 1 || (k.K / 64) % (2 * k.slices) == 0))
-        return k.slices > 1 ? launch_cfg<64, 64, 2, 2, EPI, true, 4, 128, 0, 2>(k, stream)
-                            : launch_cfg<64, 64, 2, 2, EPI, false, 4, 128, 0, 2>(k, stream);
-      return k.slices > 1 ? launch_cfg<64, 64, 2, 2, EPI, true, 4, 64, 0, 2>(k, stream)
-                          : launch_cfg<64, 64, 2, 2, EPI, false, 4, 64, 0, 2>(k, stream);
-    // the two ingredients of 17 on their own (A/B): 18 = four compute waves, 64-wide slices; 19 = two compute waves, 128-wide slices
-    case 18: return k.slices > 1 ? launch_cfg<64, 64, 2, 2, EPI, true, 4, 64, 0, 2>(k, stream)
-                                 : launch_cfg<64, 64, 2, 2, EPI, false, 4, 64, 0, 2>(k, stream);
-    case 19:
-      if (k.K % 128 == 0 && (k.slices <= 1 || (k.K / 64) % (2 * k.slices) == 0))
-        return k.slices > 1 ? launch_cfg<64, 64, 2, 1, EPI, true, 4, 128, 0, 2>(k, stream)
-                            : launch_cfg<64, 64, 2, 1, EPI, false, 4, 128, 0, 2>(k, stream);
-      return k.slices > 1 ? launch_cfg<64, 64, 2, 1, EPI, true, 4, 64, 0, 2>(k, stream)
-                          : launch_cfg<64, 64, 2, 1, EPI, false, 4, 64, 0, 2>(k, stream);
-    // round 6 (probe): the decode-regime config with a 128-row tile -- four compute waves x 32 rows + the two DMA helpers; one
-    // weight panel per 128 rows instead of one per 64.  Same K order per output element as 16.
-    case 21: return k.slices > 1 ? launch_cfg<128, 64, 4, 1, EPI, true, 4, 64, 0, 2>(k, stream)
-                                 : launch_cfg<128, 64, 4, 1, EPI, false, 4, 64, 0, 2>(k, stream);
-    default: return launch_cfg<128, 128, 2, 2, EPI>(k, stream);
-  }
+  const TileCfg* t = find_tile(tile);
+  if (t && t->decode) tile = fit_k_slices(select_decode(tile, t->BM > 64, IN_LAUNCH).id, k);
+  return launch_id<EPI>(k, tile, stream);
 }
 
-// Decode regime (m <= 64): the layer is a weight stream.  64 x 128 tiles keep the
-// activation traffic at half the weight traffic through the per-CU load path; K is
-// split over S workgroups per tile so that ~256+ workgroups pull from HBM.  S is a
-// function of (n, k) only.
-constexpr size_t TICKET_BYTES = 8192;
-
-// decode-regime config: 16 = 64x64 tiles + helper waves (default), 10 = 64x64 without helpers, 3 = 64x128 / 4-deep ring
-int decode_cfg() { return knobs().decode_cfg; }
-bool decode_is64(int cfg) { return cfg == 10 || cfg == 16 || cfg == 17 || cfg == 18 || cfg == 19; }
-int decode_bn() { return decode_is64(decode_cfg()) ? 64 : 128; }
-int decode_slab_floats() { return decode_is64(decode_cfg()) ? 64 * 64 : 128 * 2 * 2 * 16; }  // CT * MI * NI * 16 = the tile's outputs
-
-// bn: width of the tile that runs -- decode_bn() for the <= 64-row configs, TALL_BN for the 128 x 64 tile
-constexpr int TALL_BN = 64;
-constexpr int TALL_SLAB_FLOATS = 128 * TALL_BN;
 int decode_slices(int n_store, int k_pad, int bn) {
   const int DEC_BN = bn;
   const int tiles = (n_store + DEC_BN - 1) / DEC_BN, nk = k_pad / BK;
@@ -726,6 +804,27 @@ int decode_slices(int n_store, int k_pad, int bn) {
   int s = 1;
   while (s < 8 && tiles * s < 192 && s * 2 <= nk / 2) s *= 2;
   return s;
+}
+
+// In-launch split-K of a decode-regime layer under the current knobs, counted in the tiles that RUN: the decode_cfg row at
+// <= 64 rows (anything that is no 64x64 row counts as 64x128), the 128x64 tile when tall -- which is 64 wide whatever the
+// decode_cfg knob says (counting a tall launch in 128-wide tiles under decode_cfg = 3 once gave it half the slab and ticket
+// space its tiles index).
+struct SplitK {
+  int bn, slices, tiles;
+  int slab_floats;  // one tile's outputs
+  size_t ws_bytes;  // tickets + slabs
+};
+SplitK splitk_geometry(int n_store, int k_pad, bool tall) {
+  const TileCfg* t64 = row_64x64(decode_cfg());
+  const TileCfg& t = tall ? tile_row(TILE_TALL) : t64 ? *t64 : tile_row(3);
+  SplitK g;
+  g.bn = t.BN;
+  g.slices = decode_slices(n_store, k_pad, g.bn);
+  g.tiles = (n_store + g.bn - 1) / g.bn;
+  g.slab_floats = t.BM * t.BN;
+  g.ws_bytes = TICKET_BYTES + (size_t)g.tiles * g.slices * g.slab_floats * sizeof(float);
+  return g;
 }
 
 // Tile choice: every CU works through ceil(tiles / 256) tiles, a tile costs its area
@@ -783,19 +882,45 @@ int pick_tile(int M, int n_store, int K, int policy) {
   return best;
 }
 
-}  // namespace
+struct ProfScope {  // HIP-event bracket of one launch for md_profile_gemm
+  ProfRec rec;
+  bool on = false;
+  hipStream_t s = nullptr;
+  md_status begin(int kind, double work, double rd, double wr, hipStream_t stream) {
+    on = g_prof_on;
+    s = stream;
+    if (!on) return MD_OK;
+    if (hipEventCreate(&rec.start) != hipSuccess || hipEventCreate(&rec.stop) != hipSuccess) return MD_ERR_LAUNCH;
+    rec.kind = kind;
+    rec.work = work;
+    rec.rd = rd;
+    rec.wr = wr;
+    (void)hipEventRecord(rec.start, s);
+    return MD_OK;
+  }
+  void end() {
+    if (!on) return;
+    (void)hipEventRecord(rec.stop, s);
+    g_prof.push_back(rec);
+  }
+};
 
-namespace {
-md_status gemm_dispatch(const md_gemm_args* a, void* stream, const md_rope_fuse* rf);
+// What every entry point fills the same way: operands, leading dimensions, sizes, the weight-stream policy
+GemmK gemm_operands(const void* a, int64_t lda, const md_linear& lin, int m, int n_store) {
+  GemmK k;
+  k.A = (const bf16_t*)a;
+  k.W = (const bf16_t*)lin.w;
+  k.lda = lda;
+  k.ldw = lin.k_pad;
+  k.M = m;
+  k.n_pad = lin.n_pad;
+  k.n_store = n_store;
+  k.K = lin.k_pad;
+  k.nt = knobs().nt;  // decode regime: non-temporal weight stream (kernel-level +2..10 %, nothing end to end)
+  return k;
 }
-extern "C" md_status md_gemm_bf16(const md_gemm_args* a, void* stream) { return gemm_dispatch(a, stream, nullptr); }
-md_status md_gemm_qkv_rope(const md_gemm_args* a, const md_rope_fuse* rf, hipStream_t stream) {
-  MD_CHECK_ARG(rf && rf->row_cs && rf->row_kv && rf->kslab && rf->vslab && rf->n_heads > 0 && rf->ctx > 0);
-  if (!knobs().rope_fuse) return MD_ERR_UNSUPPORTED;
-  return gemm_dispatch(a, (void*)stream, rf);
-}
-namespace {
-md_status gemm_dispatch(const md_gemm_args* a, void* stream, const md_rope_fuse* rf) {
+
+md_status validate_gemm(const md_gemm_args* a) {
   MD_CHECK_ARG(a && a->a && a->c && a->lin.w);
   MD_CHECK_ARG(a->m > 0 && a->lin.n > 0 && a->lin.k > 0);
   MD_CHECK_ARG(a->lin.k_pad % BK == 0 && a->lin.k_pad >= a->lin.k);
@@ -804,133 +929,150 @@ md_status gemm_dispatch(const md_gemm_args* a, void* stream, const md_rope_fuse*
   MD_CHECK_ARG(a->gelu_from_col >= 0 && a->gelu_from_col % 8 == 0);
   MD_CHECK_ARG(a->lda >= a->lin.k_pad && a->lda % 8 == 0 && a->ldc % 8 == 0);
   MD_CHECK_ARG(((uintptr_t)a->a & 15) == 0 && ((uintptr_t)a->c & 15) == 0 && ((uintptr_t)a->lin.w & 15) == 0);
-  GemmK k;
-  k.A = (const bf16_t*)a->a;
-  k.W = (const bf16_t*)a->lin.w;
-  k.bias = (const bf16_t*)a->lin.b;
-  k.R = (const bf16_t*)a->r;
-  k.C = (bf16_t*)a->c;
-  k.lda = a->lda;
-  k.ldw = a->lin.k_pad;
-  k.ldc = a->ldc;
-  k.ldr = a->ldr;
-  k.M = a->m;
-  k.n_pad = a->lin.n_pad;
-  k.n_store = a->store_pad_cols ? a->lin.n_pad : a->lin.n;
-  MD_CHECK_ARG(a->ldc >= k.n_store);
-  k.K = a->lin.k_pad;
-  k.res_row_mod = a->res_row_mod;
-  k.tiles_m = k.tiles_n = 0;
-  k.group_m = knobs().group_m > 0 ? knobs().group_m : knobs().group_m < 0 ? md_gemm_auto_group_m(k.n_store) : md_gemm_auto_group_m_w4(k.n_store, k.K);
-  k.gelu_from = a->gelu_from_col;
-  k.partial = nullptr;
-  k.partial_ld = k.partial_slice_stride = 0;
-  k.nt = knobs().nt;  // decode regime: non-temporal weight stream (kernel-level +2..10 %, nothing end to end)
-  hipStream_t s = (hipStream_t)stream;
+  MD_CHECK_ARG(a->ldc >= (a->store_pad_cols ? a->lin.n_pad : a->lin.n));
   MD_CHECK_ARG(a->tile_policy == MD_TILE_BY_SHAPE || a->tile_policy == MD_TILE_PINNED || a->tile_policy == MD_TILE_DECODE_TALL ||
                a->tile_policy == MD_TILE_PINNED_ANY_ROWS);
-  const bool pinned = a->tile_policy == MD_TILE_PINNED || a->tile_policy == MD_TILE_PINNED_ANY_ROWS;
-  int tile = pick_tile(k.M, k.n_store, k.K, a->tile_policy);
-  k.slices = 1;
-  k.slabs = nullptr;
-  k.tickets = nullptr;
+  return MD_OK;
+}
+
+GemmK build_gemm(const md_gemm_args& a) {
+  GemmK k = gemm_operands(a.a, a.lda, a.lin, a.m, a.store_pad_cols ? a.lin.n_pad : a.lin.n);
+  k.bias = (const bf16_t*)a.lin.b;
+  k.R = (const bf16_t*)a.r;
+  k.C = (bf16_t*)a.c;
+  k.ldc = a.ldc;
+  k.ldr = a.ldr;
+  k.res_row_mod = a.res_row_mod;
+  k.group_m = knobs().group_m > 0 ? knobs().group_m : knobs().group_m < 0 ? md_gemm_auto_group_m(k.n_store) : md_gemm_auto_group_m_w4(k.n_store, k.K);
+  k.gelu_from = a.gelu_from_col;
+  return k;
+}
+
+// What a valid launch will do -- a function of the arguments' values and the knobs alone (no operand is read, nothing is
+// launched).
+struct GemmPlan {
+  md_status status = MD_OK;  // MD_ERR_UNSUPPORTED: a pinned launch that cannot be cut, a RoPE epilogue the four-wave kernel does not take
+  int tile = TILE_FALLBACK;
+  int64_t row_block = 0;     // > 0: a pinned launch cut into blocks of this many rows (launch_row_blocks)
+  bool rope = false;         // RoPE + KV write in the epilogue
+  int slices = 1;            // > 1: in-launch split-K over the caller's workspace
+};
+GemmPlan plan_gemm(const md_gemm_args& a, const GemmK& k, const md_rope_fuse* rf) {
+  GemmPlan p;
+  const auto refuse = [&p](md_status st) { p.status = st; return p; };
+  const bool pinned = a.tile_policy == MD_TILE_PINNED || a.tile_policy == MD_TILE_PINNED_ANY_ROWS;
   const bool forced = knobs().tile >= 0;
-  if (tile == 20 && !md_gemm_w4_takes(k, a->epilogue)) {
+  p.tile = pick_tile(k.M, k.n_store, k.K, a.tile_policy);
+  if (p.tile == 20 && !md_gemm_w4_takes(k, a.epilogue)) {
     if (!pinned) {
-      tile = 11;
+      p.tile = 11;
     } else {
       // MD_TILE_PINNED promises that the tile config is a function of the layer alone; the four-wave kernel's 32-bit offsets
       // bound the ROWS of a launch (M * lda * 2 < 4 GiB, (M + 256) * ldc * 2 < 0xfffff000: ~150 k rows of the 2B fused qkv|fc1
       // layer).  Falling back to the 32x32x16 family here would give a very large batch other bits than the same sequence
       // alone (advisor, round 5): the launch is cut into row blocks the kernel accepts -- rows are independent, so the bits
       // are those of one launch -- and what cannot be cut (a broadcast residual, the RoPE epilogue) is refused loudly.
-      if (rf != nullptr || (a->epilogue == MD_EPI_RESIDUAL && a->res_row_mod != 0) || k.K % 64 != 0 ||
+      if (rf != nullptr || (a.epilogue == MD_EPI_RESIDUAL && a.res_row_mod != 0) || k.K % 64 != 0 ||
           (uint64_t)k.n_pad * (uint64_t)k.ldw * 2 >= (1ull << 32))
-        return MD_ERR_UNSUPPORTED;
+        return refuse(MD_ERR_UNSUPPORTED);
       uint64_t rows = (1ull << 32) / ((uint64_t)k.lda * 2) - 1;
       rows = std::min<uint64_t>(rows, 0xfffff000ull / ((uint64_t)k.ldc * 2) - 257);
-      if (a->epilogue == MD_EPI_RESIDUAL) rows = std::min<uint64_t>(rows, 0xfffff000ull / ((uint64_t)k.ldr * 2) - 257);
+      if (a.epilogue == MD_EPI_RESIDUAL) rows = std::min<uint64_t>(rows, 0xfffff000ull / ((uint64_t)k.ldr * 2) - 257);
       rows = rows / 256 * 256;
-      if (rows < 256 || rows >= (uint64_t)a->m) return MD_ERR_UNSUPPORTED;
-      for (int64_t r0 = 0; r0 < a->m; r0 += (int64_t)rows) {
-        md_gemm_args blk = *a;
-        blk.m = (int32_t)std::min<int64_t>((int64_t)rows, a->m - r0);
-        blk.a = (const char*)a->a + r0 * a->lda * 2;
-        blk.c = (char*)a->c + r0 * a->ldc * 2;
-        if (a->r) blk.r = (const char*)a->r + r0 * a->ldr * 2;
-        if (blk.m <= 64) blk.splitk_ws = nullptr;  // a short last block: no in-launch split-K (another K association)
-        const md_status st = gemm_dispatch(&blk, stream, nullptr);
-        if (st != MD_OK) return st;
-      }
-      return MD_OK;
+      if (rows < 256 || rows >= (uint64_t)a.m) return refuse(MD_ERR_UNSUPPORTED);
+      p.row_block = (int64_t)rows;
+      return p;
     }
   }
   if (rf != nullptr) {
     // RoPE + KV write in the epilogue: four-wave kernel only, [q | k | v] sections of n_heads x 64 columns ending where the
     // GELU columns start, slab offsets in 32 bits
     const int D = rf->n_heads * 64;
-    if (tile != 20 || a->epilogue != MD_EPI_GELU || a->gelu_from_col != 3 * D || D % 128 != 0 || a->m <= 64 ||
+    if (p.tile != 20 || a.epilogue != MD_EPI_GELU || a.gelu_from_col != 3 * D || D % 128 != 0 || a.m <= 64 ||
         rf->slab_bytes >= 0xfffff000ull)
-      return MD_ERR_UNSUPPORTED;
+      return refuse(MD_ERR_UNSUPPORTED);
+    p.rope = true;
+  }
+  if (p.tile == 11 && a.epilogue != MD_EPI_RESIDUAL && !forced) {
+    // eight-wave baseline: bias / GELU layers with more tiles than CUs run its persistent tile loop
+    const long tiles = (long)((k.M + 255) / 256) * ((k.n_store + 255) / 256);
+    if (knobs().persist && tiles > 256) p.tile = 15;
+  }
+  const bool tall = (p.tile == TILE_TALL && a.m > 64 && a.m <= 128 && !forced);  // MD_TILE_DECODE_TALL: the 128-row weight-streaming tile
+  if ((a.m <= 64 || tall) && !forced && a.tile_policy != MD_TILE_PINNED_ANY_ROWS) {
+    if (!tall) p.tile = decode_cfg();
+    // in-launch split-K exactly where the 64-row regime splits (a function of the layer shape): the same slices, the same
+    // slab summation order -- a row gets the same bits in a 128-row launch as in a 64-row one
+    const SplitK g = splitk_geometry(k.n_store, k.K, tall);
+    if (g.slices > 1 && a.splitk_ws != nullptr && a.splitk_ws_bytes >= g.ws_bytes && (size_t)g.tiles * 4 <= TICKET_BYTES)
+      p.slices = g.slices;
+  }
+  return p;
+}
+
+md_status gemm_dispatch(const md_gemm_args* a, void* stream, const md_rope_fuse* rf);
+// A pinned launch beyond the four-wave kernel's 32-bit offsets, as launches of row blocks it accepts
+md_status launch_row_blocks(const md_gemm_args* a, int64_t rows, void* stream) {
+  for (int64_t r0 = 0; r0 < a->m; r0 += rows) {
+    md_gemm_args blk = *a;
+    blk.m = (int32_t)std::min<int64_t>(rows, a->m - r0);
+    blk.a = (const char*)a->a + r0 * a->lda * 2;
+    blk.c = (char*)a->c + r0 * a->ldc * 2;
+    if (a->r) blk.r = (const char*)a->r + r0 * a->ldr * 2;
+    if (blk.m <= 64) blk.splitk_ws = nullptr;  // a short last block: no in-launch split-K (another K association)
+    MD_TRY(gemm_dispatch(&blk, stream, nullptr));
+  }
+  return MD_OK;
+}
+
+md_status gemm_dispatch(const md_gemm_args* a, void* stream, const md_rope_fuse* rf) {
+  MD_TRY(validate_gemm(a));
+  GemmK k = build_gemm(*a);
+  const GemmPlan p = plan_gemm(*a, k, rf);
+  if (p.status != MD_OK) return p.status;
+  if (p.row_block > 0) return launch_row_blocks(a, p.row_block, stream);
+  if (p.rope) {
     k.rope_cs = rf->row_cs;
     k.rope_kv = rf->row_kv;
     k.kslab = (bf16_t*)rf->kslab;
     k.vslab = (bf16_t*)rf->vslab;
     k.slab_bytes = (uint32_t)rf->slab_bytes;
-    k.rope_d = D;
+    k.rope_d = rf->n_heads * 64;
     k.rope_ctx = rf->ctx;
   }
-  if (tile == 11 && a->epilogue != MD_EPI_RESIDUAL && !forced) {
-    // eight-wave baseline: bias / GELU layers with more tiles than CUs run its persistent tile loop
-    const long tiles = (long)((k.M + 255) / 256) * ((k.n_store + 255) / 256);
-    if (knobs().persist && tiles > 256) tile = 15;
-  }
-  const bool tall = (tile == 21 && a->m > 64 && a->m <= 128 && !forced);  // MD_TILE_DECODE_TALL: the 128-row weight-streaming tile
-  if ((a->m <= 64 || tall) && !forced && a->tile_policy != MD_TILE_PINNED_ANY_ROWS) {
-    if (!tall) tile = decode_cfg();
-    // in-launch split-K exactly where the 64-row regime splits (a function of the layer shape): the same slices, the same
-    // slab summation order -- a row gets the same bits in a 128-row launch as in a 64-row one
-    // (the tall tile is 64 wide whatever the decode_cfg knob says: slices, tickets and slabs are counted in the tiles that RUN --
-    // under decode_cfg = 3 the 64-row configs are 128 wide, and counting the tall launch in those gave it half the slab and ticket
-    // space its 64-wide tiles index)
-    const int bn = tall ? TALL_BN : decode_bn();
-    const int sl = decode_slices(k.n_store, k.K, bn);
-    const size_t tiles = (k.n_store + bn - 1) / bn;
-    const size_t need = TICKET_BYTES + tiles * sl * (tall ? TALL_SLAB_FLOATS : decode_slab_floats()) * sizeof(float);
-    if (sl > 1 && a->splitk_ws != nullptr && a->splitk_ws_bytes >= need && tiles * 4 <= TICKET_BYTES) {
-      k.slices = sl;
-      k.tickets = (unsigned*)a->splitk_ws;
-      k.slabs = (float*)((char*)a->splitk_ws + TICKET_BYTES);
-    }
+  if (p.slices > 1) {
+    k.slices = p.slices;
+    k.tickets = (unsigned*)a->splitk_ws;
+    k.slabs = (float*)((char*)a->splitk_ws + TICKET_BYTES);
   }
   if (a->epilogue == MD_EPI_RESIDUAL)
     MD_CHECK_ARG(a->r != nullptr && a->ldr % 8 == 0 && ((uintptr_t)a->r & 15) == 0);
-  ProfRec rec;
-  const bool prof = g_prof_on;
-  if (prof) {
-    if (hipEventCreate(&rec.start) != hipSuccess || hipEventCreate(&rec.stop) != hipSuccess) return MD_ERR_LAUNCH;
-    rec.kind = (a->m <= 64 || (a->tile_policy == MD_TILE_DECODE_TALL && a->m <= 128)) ? 1 : 0;   // a weight stream
-    rec.work = rec.kind ? 2.0 * (double)a->lin.n * (double)a->lin.k           // bf16 weight bytes, logical n, k
-                        : 2.0 * a->m * (double)a->lin.n * (double)a->lin.k;  // algorithmic flops
-    rec.rd = 2.0 * ((double)a->m * a->lin.k_pad + (double)a->lin.n_pad * a->lin.k_pad +
-                    (a->epilogue == MD_EPI_RESIDUAL ? (double)(a->res_row_mod ? a->res_row_mod : a->m) * k.n_store : 0.0));
-    rec.wr = 2.0 * (double)a->m * k.n_store;
-    (void)hipEventRecord(rec.start, s);
-  }
+  hipStream_t s = (hipStream_t)stream;
+  const int kind = (a->m <= 64 || (a->tile_policy == MD_TILE_DECODE_TALL && a->m <= 128)) ? 1 : 0;  // a weight stream
+  const double work = kind ? 2.0 * (double)a->lin.n * (double)a->lin.k           // bf16 weight bytes, logical n, k
+                           : 2.0 * a->m * (double)a->lin.n * (double)a->lin.k;  // algorithmic flops
+  const double rd = 2.0 * ((double)a->m * a->lin.k_pad + (double)a->lin.n_pad * a->lin.k_pad +
+                           (a->epilogue == MD_EPI_RESIDUAL ? (double)(a->res_row_mod ? a->res_row_mod : a->m) * k.n_store : 0.0));
+  ProfScope prof;
+  MD_TRY(prof.begin(kind, work, rd, 2.0 * (double)a->m * k.n_store, s));
   md_status st;
   switch (a->epilogue) {
-    case MD_EPI_BIAS: st = launch_epi<MD_EPI_BIAS>(k, tile, s); break;
-    case MD_EPI_GELU: st = rf ? md_gemm_w4_launch(k, MD_EPI_QKV_ROPE, s) : launch_epi<MD_EPI_GELU>(k, tile, s); break;
-    case MD_EPI_RESIDUAL: st = launch_epi<MD_EPI_RESIDUAL>(k, tile, s); break;
+    case MD_EPI_BIAS: st = launch_epi<MD_EPI_BIAS>(k, p.tile, s); break;
+    case MD_EPI_GELU: st = p.rope ? md_gemm_w4_launch(k, MD_EPI_QKV_ROPE, s) : launch_epi<MD_EPI_GELU>(k, p.tile, s); break;
+    case MD_EPI_RESIDUAL: st = launch_epi<MD_EPI_RESIDUAL>(k, p.tile, s); break;
     default: st = MD_ERR_INVALID_ARG;
   }
-  if (prof) {
-    (void)hipEventRecord(rec.stop, s);
-    g_prof.push_back(rec);
-  }
+  prof.end();
   return st;
 }
 }  // namespace
+
+extern "C" md_status md_gemm_bf16(const md_gemm_args* a, void* stream) { return gemm_dispatch(a, stream, nullptr); }
+md_status md_gemm_qkv_rope(const md_gemm_args* a, const md_rope_fuse* rf, hipStream_t stream) {
+  MD_CHECK_ARG(rf && rf->row_cs && rf->row_kv && rf->kslab && rf->vslab && rf->n_heads > 0 && rf->ctx > 0);
+  if (!knobs().rope_fuse) return MD_ERR_UNSUPPORTED;
+  return gemm_dispatch(a, (void*)stream, rf);
+}
 
 // Launch-boundary split-K (decode regime, m <= 64): S = md_gemm_partial_slices() workgroups per
 // 64-column tile, each over a contiguous range of K, store fp32 partial products
@@ -952,74 +1094,56 @@ md_status fill_partial(GemmK& k, const void* a, int64_t lda, const md_linear* li
   MD_CHECK_ARG(lda >= lin->k_pad && lda % 8 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)lin->w & 15) == 0);
   MD_CHECK_ARG(ld_partial >= lin->n && ld_partial % 4 == 0 && ((uintptr_t)partial & 15) == 0);
   MD_CHECK_ARG(slice_stride >= (int64_t)m * ld_partial && slice_stride % 4 == 0);
-  k.A = (const bf16_t*)a;
-  k.W = (const bf16_t*)lin->w;
-  k.bias = nullptr;
-  k.R = nullptr;
-  k.C = nullptr;
-  k.lda = lda;
-  k.ldw = lin->k_pad;
-  k.ldc = k.ldr = 0;
-  k.M = m;
-  k.n_pad = lin->n_pad;
-  k.n_store = lin->n;
-  k.K = lin->k_pad;
-  k.res_row_mod = 0;
+  k = gemm_operands(a, lda, *lin, m, lin->n);
   k.tiles_m = 1;
   k.tiles_n = (lin->n + 63) / 64;
   k.group_m = 8;
-  k.gelu_from = 0;
-  k.nt = knobs().nt;
   k.slices = md_gemm_partial_slices(lin);
-  k.slabs = nullptr;
-  k.tickets = nullptr;
   k.partial = partial;
   k.partial_ld = ld_partial;
   k.partial_slice_stride = slice_stride;
   return MD_OK;
 }
-
-struct ProfScope {  // HIP-event bracket of one launch for md_profile_gemm (kind 1: weight bytes streamed)
-  ProfRec rec;
-  bool on;
-  hipStream_t s;
-  md_status begin(double work, hipStream_t stream) {
-    on = g_prof_on;
-    s = stream;
-    if (!on) return MD_OK;
-    if (hipEventCreate(&rec.start) != hipSuccess || hipEventCreate(&rec.stop) != hipSuccess) return MD_ERR_LAUNCH;
-    rec.kind = 1;
-    rec.work = work;
-    rec.rd = work;
-    rec.wr = 0;
-    (void)hipEventRecord(rec.start, s);
-    return MD_OK;
-  }
-  void end() {
-    if (!on) return;
-    (void)hipEventRecord(rec.stop, s);
-    g_prof.push_back(rec);
-  }
-};
 }  // namespace
 
 extern "C" md_status md_gemm_partial_f32(const void* a, int64_t lda, const md_linear* lin, int32_t m,
                                          float* partial, int64_t ld_partial, int64_t slice_stride,
                                          void* stream) {
   GemmK k;
-  const md_status chk = fill_partial(k, a, lda, lin, m, partial, ld_partial, slice_stride);
-  if (chk != MD_OK) return chk;
+  MD_TRY(fill_partial(k, a, lda, lin, m, partial, ld_partial, slice_stride));
   hipStream_t s = (hipStream_t)stream;
+  const double bytes = 2.0 * (double)lin->n * (double)lin->k;  // kind 1: weight bytes streamed
   ProfScope prof;
-  if (prof.begin(2.0 * (double)lin->n * (double)lin->k, s) != MD_OK) return MD_ERR_LAUNCH;
-  const int cfg = decode_cfg();
-  const md_status st = m > 64 ? launch_cfg<128, 64, 4, 1, MD_EPI_BIAS, true, 4, 64, 0, 2>(k, s)
-                       : (cfg == 17 || cfg == 18) ? launch_cfg<64, 64, 2, 2, MD_EPI_BIAS, true, 4, 64, 0, 2>(k, s)
-                       : (cfg == 16 || cfg == 19) ? launch_cfg<64, 64, 2, 1, MD_EPI_BIAS, true, 4, 64, 0, 2>(k, s)
-                                                  : launch_cfg<64, 64, 2, 1, MD_EPI_BIAS, true, 4>(k, s);
+  MD_TRY(prof.begin(1, bytes, bytes, 0, s));
+  const md_status st = launch_id<MD_EPI_BIAS>(k, select_decode(decode_cfg(), m > 64, PARTIAL_ONE).id, s);
   prof.end();
   return st;
 }
+
+namespace {
+using PairFn = void (*)(const GemmPair);
+// The rows select_decode can name for the pair: the tall tile and every 64x64 decode row on 64-wide slices -- these, and
+// only these, have a gemm_pair_kernel (the tall one also on the pair rule's ring depth)
+constexpr bool pair_runs(const TileCfg& t) { return t.id == TILE_TALL || (t.decode && t.BM == 64 && t.BN == 64 && t.k64 == 0); }
+template <int I>
+PairFn pair_kernel(int stages) {
+  constexpr TileCfg t = TILES[I];
+  if constexpr (!pair_runs(t)) {
+    return nullptr;
+  } else {
+    constexpr int S3 = ENTRY_RULES[PARTIAL_PAIR].tall_stages;
+    if constexpr (t.id == TILE_TALL)
+      if (stages == S3) return gemm_pair_kernel<t.BM, t.BN, t.WM, t.WN, MD_EPI_BIAS, true, S3, t.BKT, t.PP, t.XW>;
+    return gemm_pair_kernel<t.BM, t.BN, t.WM, t.WN, MD_EPI_BIAS, true, t.STAGES, t.BKT, t.PP, t.XW>;
+  }
+}
+template <int... I>
+PairFn pair_kernel(int id, int stages, std::integer_sequence<int, I...>) {
+  PairFn fn = nullptr;
+  (void)((TILES[I].id == id && ((fn = pair_kernel<I>(stages)), true)) || ...);
+  return fn;
+}
+}  // namespace
 
 // Both partial-product GEMMs of a decode block (proj over the attention output, fc2 over
 // gelu(fc1)) in ONE launch: they are independent, and a launch costs as much as the stream.
@@ -1027,44 +1151,31 @@ extern "C" md_status md_gemm_partial_f32_pair(const void* a0, int64_t lda0, cons
                                               const void* a1, int64_t lda1, const md_linear* lin1, float* partial1,
                                               int32_t m, int64_t ld_partial, int64_t slice_stride, void* stream) {
   GemmPair pair;
-  md_status chk = fill_partial(pair.g[0], a0, lda0, lin0, m, partial0, ld_partial, slice_stride);
-  if (chk != MD_OK) return chk;
-  chk = fill_partial(pair.g[1], a1, lda1, lin1, m, partial1, ld_partial, slice_stride);
-  if (chk != MD_OK) return chk;
+  MD_TRY(fill_partial(pair.g[0], a0, lda0, lin0, m, partial0, ld_partial, slice_stride));
+  MD_TRY(fill_partial(pair.g[1], a1, lda1, lin1, m, partial1, ld_partial, slice_stride));
   hipStream_t s = (hipStream_t)stream;
-  constexpr int lds = 4 * (64 + 64) * 64 * 2;
-  // (64-wide slices here whatever the config: 64 KiB of ring = TWO workgroups per CU, and the pair makes 512)
-  const int cfg = decode_cfg();
-  const bool four = cfg == 17 || cfg == 18, helpers = four || cfg == 16 || cfg == 19;
-  // 65 .. 128 rows (round 6): one 128 x 64 tile per weight panel -- four compute waves x 32 rows + the two DMA helpers, 96 KiB
-  // of ring (one workgroup per CU); the same K slices and the same K order per output element as the 64-row configs
-  const bool tall = m > 64;
-  const int NT = tall ? 384 : four ? 384 : helpers ? 256 : 128;
-  static const int tall_stages = [] { const char* e = getenv("MD_TALL_PAIR_STAGES"); return e ? atoi(e) : 3; }();   // 3 stages = 72 KiB of ring: TWO workgroups per CU, all 512 of the pair resident at once (18.6 us against 20.3 with 4 stages; MD_TALL_PAIR_STAGES=4: A/B)
-  const int lds_used = tall ? tall_stages * (128 + 64) * 64 * 2 : lds;
-  auto fn = tall ? (tall_stages == 3 ? gemm_pair_kernel<128, 64, 4, 1, MD_EPI_BIAS, true, 3, 64, 0, 2>
-                                     : gemm_pair_kernel<128, 64, 4, 1, MD_EPI_BIAS, true, 4, 64, 0, 2>)
-            : four ? gemm_pair_kernel<64, 64, 2, 2, MD_EPI_BIAS, true, 4, 64, 0, 2>
-            : helpers ? gemm_pair_kernel<64, 64, 2, 1, MD_EPI_BIAS, true, 4, 64, 0, 2>
-                      : gemm_pair_kernel<64, 64, 2, 1, MD_EPI_BIAS, true, 4>;
-  MD_TRY(md_ensure_dynamic_lds((const void*)fn, lds_used));
+  // 65 .. 128 rows (round 6): one 128 x 64 tile per weight panel, the same K slices and the same K order per output element as
+  // the 64-row configs.  (A ring depth other than the rule's runs the row's own kernel, in the LDS the depth asks for.)
+  const DecodeRun run = select_decode(decode_cfg(), m > 64, PARTIAL_PAIR);
+  const TileCfg& t = tile_row(run.id);
+  const PairFn fn = pair_kernel(run.id, run.stages, std::make_integer_sequence<int, N_TILES>{});
+  if (fn == nullptr) return MD_ERR_UNSUPPORTED;
+  const int NT = (t.WM * t.WN + t.XW) * 64, lds = run.stages * (t.BM + t.BN) * t.BKT * 2;
+  MD_TRY(md_ensure_dynamic_lds((const void*)fn, lds));
+  const double bytes = 2.0 * ((double)lin0->n * lin0->k + (double)lin1->n * lin1->k);
   ProfScope prof;
-  if (prof.begin(2.0 * ((double)lin0->n * lin0->k + (double)lin1->n * lin1->k), s) != MD_OK) return MD_ERR_LAUNCH;
+  MD_TRY(prof.begin(1, bytes, bytes, 0, s));
   const int gx = std::max(pair.g[0].tiles_m * pair.g[0].tiles_n, pair.g[1].tiles_m * pair.g[1].tiles_n);
   const int gy = std::max(pair.g[0].slices, pair.g[1].slices);
-  hipLaunchKernelGGL(fn, dim3(gx, gy, 2), dim3(NT), lds_used, s, pair);
+  hipLaunchKernelGGL(fn, dim3(gx, gy, 2), dim3(NT), lds, s, pair);
   prof.end();
   return md_launch_status();
 }
 
 extern "C" size_t md_gemm_workspace_bytes(const md_linear* lin, int32_t m, int32_t store_pad_cols) {
   if (!lin || m > 128) return 0;   // (65 .. 128 rows: what a MD_TILE_DECODE_TALL launch needs; other policies ignore the workspace there)
-  const int n_store = store_pad_cols ? lin->n_pad : lin->n;
-  const int bn = m > 64 ? TALL_BN : decode_bn();  // the tile that runs (gemm_dispatch)
-  const int sl = decode_slices(n_store, lin->k_pad, bn);
-  if (sl == 1) return 0;
-  const size_t tiles = (n_store + bn - 1) / bn;
-  return TICKET_BYTES + tiles * sl * (m > 64 ? TALL_SLAB_FLOATS : decode_slab_floats()) * sizeof(float);
+  const SplitK g = splitk_geometry(store_pad_cols ? lin->n_pad : lin->n, lin->k_pad, m > 64);
+  return g.slices == 1 ? 0 : g.ws_bytes;
 }
 
 bool md_gemm_knob_rope_fuse() { return knobs().rope_fuse != 0; }

@@ -3,27 +3,28 @@
 #include "md_common.hpp"
 
 // One launch of  C = epilogue(A . W^T + b)  as the kernels see it.
+// Every field has a default, so a filler names only what its launch uses (same layout as before: passed to kernels by value).
 struct GemmK {
-  const bf16_t* A;
-  const bf16_t* W;
-  const bf16_t* bias;
-  const bf16_t* R;
-  bf16_t* C;
-  int64_t lda, ldw, ldc, ldr;
-  int M, n_store, n_pad, K;
-  int tiles_m, tiles_n;
-  int res_row_mod;
-  int group_m;    // tile-order grouping (row panels per group)
-  int gelu_from;  // EPI_GELU: columns >= gelu_from get the GELU
-  int nt;         // decode regime: stream the weights with the non-temporal policy
+  const bf16_t* A = nullptr;
+  const bf16_t* W = nullptr;
+  const bf16_t* bias = nullptr;
+  const bf16_t* R = nullptr;
+  bf16_t* C = nullptr;
+  int64_t lda = 0, ldw = 0, ldc = 0, ldr = 0;
+  int M = 0, n_store = 0, n_pad = 0, K = 0;
+  int tiles_m = 0, tiles_n = 0;  // filled by the launchers
+  int res_row_mod = 0;
+  int group_m = 0;    // tile-order grouping (row panels per group)
+  int gelu_from = 0;  // EPI_GELU: columns >= gelu_from get the GELU
+  int nt = 0;         // decode regime: stream the weights with the non-temporal policy
   // launch-boundary split-K: every K slice stores its fp32 partial tile [slice][m][ldp] and exits;
   // the consumer kernel sums the slices (md_reduce_residual_layernorm)
-  float* partial;
-  int64_t partial_ld, partial_slice_stride;
+  float* partial = nullptr;
+  int64_t partial_ld = 0, partial_slice_stride = 0;
   // split-K (decode regime only): K slices per output tile, fp32 slabs, arrival tickets
-  int slices;
-  float* slabs;
-  unsigned* tickets;
+  int slices = 1;
+  float* slabs = nullptr;
+  unsigned* tickets = nullptr;
   // MD_EPI_QKV_ROPE (four-wave kernel only): the decoder prefill's fused [q | k | v | gelu(fc1)] layer with the partial RoPE
   // (rope.py:20-48) and the KV-cache update (text.py:45-46, moondream.py:74-78) applied in the epilogue
   const float* rope_cs = nullptr;      // fp32 [M][32]: (cos, sin) of the row's position for the 16 rotated pairs

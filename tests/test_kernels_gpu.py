@@ -129,6 +129,28 @@ def test_gemm_tile_configs_agree_bitwise(lib, force_tile):
         assert torch.equal(gemm(lib, a, lin), first), f"tile 20 rep {rep}"
 
 
+@pytest.mark.parametrize("k", [192, 256])
+def test_every_tile_id_forced_agrees_bitwise(lib, force_tile, k):
+    """Every decode-regime id of the tile table and id 1, forced through "tile", against forced id 2: bit for bit, bias and
+    residual epilogues (the other tests force only 2 and 16 at more than 64 rows; 11 / 15 are covered by BIG_TILES).  70 rows
+    are ragged across a 64-row and a 128-row tile, 200 columns across every tile width; k = 192 is a multiple of 64 but not of
+    128 (ids 17 and 19 fall back to their 64-wide slices), k = 256 takes their 128-wide ones.  (20, the four-wave kernel, is
+    another MFMA family: test_gemm_tile_configs_agree_bitwise.)"""
+    m, n = 70, 200
+    a, w, b = randn(m, k, seed=71), randn(n, k, scale=1 / math.sqrt(k), seed=72), randn(n, scale=0.1, seed=73)
+    r = randn(m, n, seed=74)
+    lin = PackedLinear(w, b, "cuda")
+    force_tile(2)
+    want = {epi: gemm(lib, a, lin, epi=epi, r=r if epi == _lib.MD_EPI_RESIDUAL else None)
+            for epi in (_lib.MD_EPI_BIAS, _lib.MD_EPI_RESIDUAL)}
+    compare(f"tile 2 k={k}", want[_lib.MD_EPI_BIAS], ref_linear(a, w, b), 3e-3, 2e-2)
+    for tile in (1, 3, 10, 16, 17, 18, 19, 21):
+        force_tile(tile)
+        for epi, ref in want.items():
+            got = gemm(lib, a, lin, epi=epi, r=r if epi == _lib.MD_EPI_RESIDUAL else None)
+            assert torch.equal(got, ref), f"tile {tile} k={k} epi={epi}"
+
+
 def test_tile_policy_is_a_per_call_field(lib, force_tile):
     """ABI 5: md_gemm_args.tile_policy.  MD_TILE_PINNED makes the tile config of a > 64-row launch a function of the layer alone --
     the 256 x 256 kernel whatever the row count -- so a row gets the same bits in a 100-row and in a 5000-row launch; MD_TILE_BY_SHAPE
