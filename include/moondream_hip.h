@@ -279,8 +279,6 @@ md_status md_amax_bf16(const void* x, int64_t ldx, int32_t rows, int32_t cols, f
  *                   bit 0 = the second 32-key half of a last key tile with no live key in it, bit 1 = waves with no live
  *                   query row; default 3, 0 = round 4's kernel; same bits whatever the value
  *   "w4_grid"       workgroups of the four-wave kernel's persistent grid (0 = one per CU)
- *   "w4_variant"    main-loop schedule variant of the four-wave kernel (0 = shipped; others: tools/sweep_w4_variants.py)
- *   "w4_dbg_*"      in-kernel cycle stamps of the four-wave kernel (tools/w4_probe.py)
  * Every tile config of one MFMA family accumulates K in the same order, so within a family outputs do not depend on
  * these.  Unknown key: MD_ERR_INVALID_ARG. */
 md_status md_gemm_set_tuning(const char* key, int32_t value);
@@ -635,7 +633,6 @@ md_status md_text_forward_slots(const md_text_model* m, const void* x, void* hid
  * [0, prefix_len[b]) of the prefix slot have been copied.  The decode attention groups rows: one K / V load of a prefix row
  * serves every row of a group sharing its prefix slot.
  * kv->k8 / kv->v8 (the e4m3 copy of the fp8 mode) set, NULL kv, slots with n_slots <= 0: MD_ERR_INVALID_ARG.
- * The prefill attention takes the shared-prefix instantiation of whichever variant MD_ATTN_VARIANT selects.
  * Workspace: md_text_workspace_bytes(m, batch, q_len). */
 md_status md_text_forward_shared(const md_text_model* m, const void* x, void* hidden, int32_t batch, int32_t q_len,
                                  const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,

@@ -1,7 +1,7 @@
 // Softmax attention kernels.
 //
-//  attn_prefill_kernel<HD>  tiled (flash-style) attention for a block of query
-//     rows on the matrix cores: the ViT encoder (729 x 729, head_dim 72, no
+//  attn_prefill_dma_kernel<HD, SHP>  tiled (flash-style) attention for a block of
+//     query rows on the matrix cores: the ViT encoder (729 x 729, head_dim 72, no
 //     mask; reference layers.py:163) and the decoder prefill against the KV
 //     slab with the prefix-LM visibility rule (reference text.py:48-50, mask of
 //     moondream.py:138-146).
@@ -21,9 +21,9 @@
 //   K-slot -> key permutation this implies (slot (hi, j) <-> key 16u + 4hi +
 //   (j&3) + 8(j>>2)) is applied to the V^T operand's LDS addresses instead of
 //   shuffling P between lanes.
-//   head_dim 72 is handled by LDS-side zero padding only: 80 for the QK^T
-//   contraction (5 K-steps), 96 (3 x 32 rows of V^T) for PV; HBM layouts stay
-//   dense.
+//   head_dim 72 is handled on the LDS / register side only: 80 for the QK^T
+//   contraction (5 K-steps, the Q fragments zero padded), 96 (3 x 32 rows of V^T)
+//   for PV; HBM layouts stay dense.
 #include "text_internal.hpp"
 #include <cstdlib>
 
@@ -43,33 +43,19 @@ struct AttnK {
   const int32_t* q_pos0;
   const int32_t* kv_len;
   float scale_log2;  // scale * log2(e)
-  int n_qblk, n_bh, n_heads;  // XCD-aware 1-D grid of the LDS-DMA kernels
+  int n_qblk, n_bh, n_heads;  // XCD-aware 1-D grid of the prefill kernel
   int q_blk0;                 // first 128-row query block of the launch (n_qblk = the blocks it runs)
   uint8_t* o8;                // opt-in FP8 mode: the output row as e4m3 bytes as well (md_attn_args.o8), or nullptr
   int64_t o8_bs, o8_ts;
   float o8_inv_scale;
   int head_dim;
   const int32_t* slots;  // md_text_forward_slots: sequence b's K / V rows are those of slot slots[b] (nullptr: slot b); q / o stay row-indexed
-  int skip_dead;  // LDS-DMA prefill kernel, exact work skipping: bit 0 = the second 32-key half of a last tile with no live key in it, bit 1 = waves with no live query row
+  int skip_dead;  // prefill kernel, exact work skipping: bit 0 = the second 32-key half of a last tile with no live key in it, bit 1 = waves with no live query row
   // md_text_forward_shared: keys [0, pfx_len[b]) of sequence b are read from slot pfx_slots[b] (when in [0, pfx_n_slots)), the
   // rest from its own slot -- addresses only (nullptr: no shared prefix)
   const int32_t* pfx_slots;
   const int32_t* pfx_len;
   int pfx_n_slots;
-};
-
-template <int HD>
-struct Cfg {
-  static constexpr int HDP = (HD + 15) / 16 * 16;  // QK^T contraction length (zero padded)
-  static constexpr int KSTEPS = HDP / 16;
-  static constexpr int ND = (HD + 31) / 32;        // 32-row blocks of V^T / O^T
-  static constexpr int KSTR = HDP + 8;             // K tile row stride (elements): 16-B slots rotate by 11 (HD 72) / 9 (HD 64) per row -> conflict-free b128
-  static constexpr int VSTR = 68;                  // V^T row stride: 8-B slots rotate by 17 per row
-  static constexpr int CPR = HD / 8;               // 16-byte chunks per global row
-  static constexpr int K_BYTES = 64 * KSTR * 2;
-  static constexpr int V_BYTES = ND * 32 * VSTR * 2;
-  static constexpr int O_BYTES = 4 * 32 * KSTR * 2;
-  static constexpr int LDS = (K_BYTES + V_BYTES) > O_BYTES ? (K_BYTES + V_BYTES) : O_BYTES;
 };
 
 // md_text_forward_shared: the shared prefix of sequence b (own slot kvb) as a key count and the element offsets from the own
@@ -83,241 +69,8 @@ __device__ __forceinline__ void shared_prefix_delta(const AttnK& p, int b, int64
   pdv = ((int64_t)ps - kvb) * p.v_bs;
 }
 
-// SHP: the shared-prefix addressing of md_text_forward_shared (per key row); the other instantiations compile without it
-template <int HD, bool SHP = false>
-__global__ __launch_bounds__(256) void attn_prefill_kernel(const AttnK p) {
-  using C = Cfg<HD>;
-  __shared__ __attribute__((aligned(16))) char smem[C::LDS];
-  char* Ks = smem;
-  char* Vt = smem + C::K_BYTES;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int hi = lane >> 5, l31 = lane & 31;
-  const int b = blockIdx.z, h = blockIdx.y, hk = h / p.kv_group;
-  const int q_pos0 = p.q_pos0 ? p.q_pos0[b] : 0;
-  const int kv_len = p.kv_len ? p.kv_len[b] : p.kv_len_all;
-
-  const int q_blk0 = (p.q_blk0 + blockIdx.x) * 128;
-  const int q_row0 = q_blk0 + wave * 32;
-  const int q_row = min(q_row0 + l31, p.q_len - 1);  // clamp: padding rows replay a valid row
-  const int qpos = q_pos0 + q_row;
-
-  // keys any row of this workgroup may see
-  const int blk_qpos_hi = q_pos0 + min(q_blk0 + 127, p.q_len - 1);
-  const int blk_vis = (blk_qpos_hi < p.prefix) ? max(blk_qpos_hi + 1, p.prefix) : blk_qpos_hi + 1;
-  const int kv_end = min(kv_len, blk_vis);
-  // per-wave bounds for skipping the mask arithmetic on fully visible tiles
-  const int w_qpos_lo = q_pos0 + min(q_row0, p.q_len - 1);
-  const int w_qpos_hi = q_pos0 + min(q_row0 + 31, p.q_len - 1);
-
-  // ---- Q fragments (B operand: column = query row, K-slot = 8 hi + j) ------
-  bf16x8 qf[C::KSTEPS];
-  {
-    const bf16_t* qrow = p.q + (int64_t)b * p.q_bs + (int64_t)q_row * p.q_ts + (int64_t)h * p.q_hs;
-#pragma unroll
-    for (int s = 0; s < C::KSTEPS; ++s) {
-      const int col = 16 * s + 8 * hi;
-      bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-      qf[s] = (col < HD) ? *(const bf16x8*)(qrow + col) : z;
-    }
-  }
-
-  // zero the LDS padding that tile loads never touch
-  if (C::HDP > HD) {
-    for (int r = tid; r < 64; r += 256) *(u32x4*)(Ks + r * C::KSTR * 2 + HD * 2) = u32x4{0, 0, 0, 0};
-  }
-  for (int i = tid; i < (C::ND * 32 - HD) * (C::VSTR / 2); i += 256)
-    *(uint32_t*)(Vt + HD * C::VSTR * 2 + i * 4) = 0u;
-
-  f32x16 oacc[C::ND];
-#pragma unroll
-  for (int d = 0; d < C::ND; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f;
-
-  const int64_t kvb = p.slots ? p.slots[b] : b;
-  const bf16_t* kbase = p.k + kvb * p.k_bs + (int64_t)hk * p.k_hs;
-  const bf16_t* vbase = p.v + kvb * p.v_bs + (int64_t)hk * p.v_hs;
-  int plen = 0;           // SHP: keys below plen come from the shared prefix slot, at kbase / vbase + pdk / pdv
-  int64_t pdk = 0, pdv = 0;
-  if constexpr (SHP) shared_prefix_delta(p, b, kvb, plen, pdk, pdv);
-
-  // ---- K/V staging, split (cdna guide T14): the global loads of tile t+1 are issued
-  // before tile t is computed and written to LDS after it, so their latency hides
-  // under the MFMA/softmax work.  A thread owns (key-row PAIR, 16-byte chunk) items:
-  // K goes to LDS row-major, V transposed -- two adjacent keys of one feature pack
-  // into a single 4-byte LDS store.
-  constexpr int ITEMS = 32 * C::CPR, NIT = (ITEMS + 255) / 256;
-  u32x4 kreg[NIT][2], vreg[NIT][2];
-  auto stage_load = [&](int kv0) {
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {
-      const int it = min(tid + 256 * u, ITEMS - 1);  // surplus threads replay the last item (never written)
-      const int rp = it / C::CPR, ch = it % C::CPR;
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        // rows past kv_len replay the last valid row: their scores are masked to -inf
-        // below, so P is exactly 0 and the (finite) V values never contribute
-        const int j = min(kv0 + 2 * rp + e, kv_len - 1);
-        kreg[u][e] = *(const u32x4*)(kbase + ((SHP && j < plen) ? pdk : 0) + (int64_t)j * p.k_ts + ch * 8);
-        vreg[u][e] = *(const u32x4*)(vbase + ((SHP && j < plen) ? pdv : 0) + (int64_t)j * p.v_ts + ch * 8);
-      }
-    }
-  };
-  auto stage_write = [&]() {
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {
-      const int it = tid + 256 * u;
-      if (it < ITEMS) {
-        const int rp = it / C::CPR, ch = it % C::CPR;
-        *(u32x4*)(Ks + (2 * rp) * C::KSTR * 2 + ch * 16) = kreg[u][0];
-        *(u32x4*)(Ks + (2 * rp + 1) * C::KSTR * 2 + ch * 16) = kreg[u][1];
-        char* vt = Vt + (ch * 8) * C::VSTR * 2 + rp * 4;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          const uint32_t a = vreg[u][0][w], bq = vreg[u][1][w];
-          *(uint32_t*)(vt + (2 * w) * C::VSTR * 2) = (a & 0xffffu) | (bq << 16);
-          *(uint32_t*)(vt + (2 * w + 1) * C::VSTR * 2) = (a >> 16) | (bq & 0xffff0000u);
-        }
-      }
-    }
-  };
-
-  if (kv_end > 0) {
-    stage_load(0);
-    stage_write();
-  }
-  for (int kv0 = 0; kv0 < kv_end; kv0 += 64) {
-    __syncthreads();  // tile kv0 is in LDS
-    const bool more = kv0 + 64 < kv_end;
-    if (more) stage_load(kv0 + 64);
-
-    // ---- S^T = K Q^T : two 32-key blocks ------------------------------------
-    f32x16 sacc[2];
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[sub][r] = 0.f;
-#pragma unroll
-      for (int s = 0; s < C::KSTEPS; ++s) {
-        const bf16x8 kf = *(const bf16x8*)(Ks + (32 * sub + l31) * C::KSTR * 2 + (16 * s + 8 * hi) * 2);
-        sacc[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[s], sacc[sub], 0, 0, 0);
-      }
-    }
-
-    // ---- mask, online softmax (per lane = per query row) --------------------
-    // Scores stay raw; the softmax scale is folded into the exp2 argument as one FMA:
-    // p = 2^(s*c - m*c), c = scale*log2(e) > 0 (so the row max can be taken on raw s).
-    const bool full_vis = (kv0 + 63 <= w_qpos_lo) || (w_qpos_hi < p.prefix && kv0 + 64 <= p.prefix);
-    const bool need_mask = !(full_vis && kv0 + 64 <= kv_len);
-    float mx = -INFINITY;
-    if (need_mask) {
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int j = kv0 + 32 * sub + 8 * (r >> 2) + 4 * hi + (r & 3);
-          const bool ok = (j < kv_len) && (j <= qpos || (qpos < p.prefix && j < p.prefix));
-          sacc[sub][r] = ok ? sacc[sub][r] : -INFINITY;
-        }
-    }
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[sub][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    // Deferred rescale: the running reference m_run only moves when some row's max
-    // has grown by more than 2^RESCALE_THR in the exp2 domain (wave-uniform branch).
-    // Until then P = 2^((s - m_run) c) <= 2^RESCALE_THR, which bf16 P and the fp32
-    // accumulators hold without loss; O, l and P always share one reference, so the
-    // result is the same softmax.  Saves the 48-register accumulator rescale (and
-    // its AGPR round trip) on almost every tile.
-    constexpr float RESCALE_THR = 6.0f;
-    if (__any((mx - m_run) * p.scale_log2 > RESCALE_THR)) {
-      const float m_new = fmaxf(m_run, mx);  // finite from the first tile on: key 0 is visible to every query
-      // (a row with no visible key yet keeps alpha = 1: it has nothing accumulated)
-      const float alpha = (m_new == -INFINITY) ? 1.f : __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);
-      m_run = m_new;
-      l_run *= alpha;
-#pragma unroll
-      for (int d = 0; d < C::ND; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-    }
-    const float mc = (m_run == -INFINITY) ? 0.f : -m_run * p.scale_log2;
-    float psum = 0.f;
-    bf16x8 pf[2][2];
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        u32x4 w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float p0 = __builtin_amdgcn_exp2f(fmaf(sacc[sub][8 * u + 2 * e], p.scale_log2, mc));
-          const float p1 = __builtin_amdgcn_exp2f(fmaf(sacc[sub][8 * u + 2 * e + 1], p.scale_log2, mc));
-          psum += p0 + p1;
-          w[e] = pack_bf16x2(p0, p1);
-        }
-        pf[sub][u] = __builtin_bit_cast(bf16x8, w);
-      }
-    l_run += psum;
-
-    // ---- O^T += V^T P^T ------------------------------------------------------
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int kcol = 32 * sub + 16 * u + 4 * hi;
-#pragma unroll
-        for (int d = 0; d < C::ND; ++d) {
-          const char* vrow = Vt + (32 * d + l31) * C::VSTR * 2 + kcol * 2;
-          const u32x2 lo = *(const u32x2*)(vrow);
-          const u32x2 hi8 = *(const u32x2*)(vrow + 16);
-          const u32x4 vv = {lo[0], lo[1], hi8[0], hi8[1]};
-          oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vv), pf[sub][u],
-                                                            oacc[d], 0, 0, 0);
-        }
-      }
-    if (more) {
-      __syncthreads();  // every wave is done reading tile kv0
-      stage_write();
-    }
-  }
-
-  // ---- finalize: O / l, transpose through LDS, coalesced row stores ---------
-  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-  __syncthreads();
-  char* ot = smem + wave * 32 * C::KSTR * 2;
-#pragma unroll
-  for (int d = 0; d < C::ND; ++d)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int col = 32 * d + 8 * g + 4 * hi;
-      if (col < HD) {
-        u32x2 w;
-        w[0] = pack_bf16x2(oacc[d][4 * g + 0] * inv, oacc[d][4 * g + 1] * inv);
-        w[1] = pack_bf16x2(oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv);
-        *(u32x2*)(ot + l31 * C::KSTR * 2 + col * 2) = w;
-      }
-    }
-  bf16_t* obase = p.o + (int64_t)b * p.o_bs + (int64_t)h * p.o_hs;
-  uint8_t* o8base = p.o8 + (int64_t)b * p.o8_bs + (int64_t)h * HD;
-  for (int idx = lane; idx < 32 * C::CPR; idx += 64) {
-    const int row = idx / C::CPR, ch = idx % C::CPR;
-    if (q_row0 + row < p.q_len) {
-      const u32x4 v = *(const u32x4*)(ot + row * C::KSTR * 2 + ch * 16);
-      if (p.o != nullptr) *(u32x4*)(obase + (int64_t)(q_row0 + row) * p.o_ts + ch * 8) = v;
-      if (p.o8 != nullptr) *(u32x2*)(o8base + (int64_t)(q_row0 + row) * p.o8_ts + ch * 8) = quant8(v, p.o8_inv_scale);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------
-// prefill, LDS-DMA staged (default): same math and fragment layouts as
-// attn_prefill_kernel above, different plumbing --
+// prefill: the math and fragment layouts of the header comment; the plumbing --
 //   * K and V tiles go global -> LDS by LDS-DMA (no staging registers, no VALU), both
 //     ROW-major, double buffered: one barrier per 64-key tile, the DMA of tile t+1
 //     runs under the MFMA/softmax work of tile t;
@@ -353,12 +106,8 @@ struct CfgD {
   static_assert((64 * KCH - 512) % 64 == 0 && K_LAST_WAVES >= 1 && K_LAST_WAVES <= 4, "K piece split");
 };
 
-// PIPE: the K stream runs one tile ahead of the V stream and S(t+1) = K(t+1) Q^T is issued
-// in the same basic block as the exp2 / pack work of tile t and the P V MFMAs of tile t, so
-// one wave keeps the matrix pipe and the VALU busy at the same time (22 MFMAs x 32 cycles
-// against ~110 VALU instructions per tile) instead of alternating between them.
-// SHP: the shared-prefix addressing of md_text_forward_shared; the other instantiations compile without it
-template <int HD, bool PIPE, bool SHP = false>
+// SHP: the shared-prefix addressing of md_text_forward_shared (per key row); the other instantiations compile without it
+template <int HD, bool SHP = false>
 __global__ __launch_bounds__(256) void attn_prefill_dma_kernel(const AttnK p) {
   using C = CfgD<HD>;
   __shared__ __attribute__((aligned(16))) char smem[C::LDS];
@@ -515,11 +264,6 @@ __global__ __launch_bounds__(256) void attn_prefill_dma_kernel(const AttnK p) {
   if (kv_end > 0) {
     issue_k(0, 0);
     issue_v(0, 0);
-    if (PIPE) {
-      if (64 < kv_end) issue_k(64, 1);
-      tile_barrier();
-      compute_s(sacc, smem, true);
-    }
   }
   const bool wave_live = !(p.skip_dead & 2) || q_row0 < p.q_len;  // wave-uniform
   int buf = 0;
@@ -527,25 +271,25 @@ __global__ __launch_bounds__(256) void attn_prefill_dma_kernel(const AttnK p) {
     // own DMA of the previous iteration landed (vmcnt 0), everybody's is visible, and the
     // buffers refilled below are no longer read by any wave
     tile_barrier();
-    if (PIPE) {
-      if (kv0 + 128 < kv_end) issue_k(kv0 + 128, buf);      // K(t+2) over K(t), consumed one iteration ago
-      if (kv0 + 64 < kv_end) issue_v(kv0 + 64, buf ^ 1);    // V(t+1) over V(t-1)
-    } else if (kv0 + 64 < kv_end) {
-      issue_k(kv0 + 64, buf ^ 1);
-      issue_v(kv0 + 64, buf ^ 1);
+    const bool more = kv0 + 64 < kv_end;
+    const int nbuf = buf ^ 1;  // outside the branch, behind the comparison: the order hipcc emits the measured loop from (profiles/retire_ab_variants_isa.txt)
+    if (more) {
+      issue_k(kv0 + 64, nbuf);
+      issue_v(kv0 + 64, nbuf);
     }
     const char* Ks = smem + buf * C::BUF;
     const char* Vs = Ks + C::K_BYTES;
-    const char* Kn = smem + (buf ^ 1) * C::BUF;  // PIPE: K(t+1) (stale but finite data after the last tile; result unused)
 
-    // (PIPE keeps the full computation: its S runs one tile ahead)
-    const bool both = PIPE || !(p.skip_dead & 1) || kv0 + 32 < kv_end;  // (kv_end <= kv_len: keys past it are visible to no row of this block)
+    const bool both = !(p.skip_dead & 1) || kv0 + 32 < kv_end;  // (kv_end <= kv_len: keys past it are visible to no row of this block)
     // A wave whose 32 query rows all lie past q_len (the fourth wave of the last query block: 729 / 735 rows = 5 blocks of 128 +
     // 89 / 95 rows) stores nothing: it keeps its share of the LDS-DMA stream and the barriers and skips the arithmetic, which
     // leaves its SIMD to the other workgroups' waves.
-    if (!PIPE && !wave_live) continue;
-    if (!PIPE) compute_s(sacc, Ks, both);
+    if (!wave_live) continue;
+    compute_s(sacc, Ks, both);
 
+    // ---- mask, online softmax (per lane = per query row) --------------------
+    // Scores stay raw; the softmax scale is folded into the exp2 argument as one FMA:
+    // p = 2^(s*c - m*c), c = scale*log2(e) > 0 (so the row max can be taken on raw s).
     const bool full_vis = (kv0 + 63 <= w_qpos_lo) || (w_qpos_hi < p.prefix && kv0 + 64 <= p.prefix);
     const bool need_mask = !(full_vis && kv0 + 64 <= kv_len);
     float mx = -INFINITY;
@@ -564,9 +308,16 @@ __global__ __launch_bounds__(256) void attn_prefill_dma_kernel(const AttnK p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[sub][r]);
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    constexpr float RESCALE_THR = 6.0f;  // deferred rescale, see attn_prefill_kernel
+    // Deferred rescale: the running reference m_run only moves when some row's max
+    // has grown by more than 2^RESCALE_THR in the exp2 domain (wave-uniform branch).
+    // Until then P = 2^((s - m_run) c) <= 2^RESCALE_THR, which bf16 P and the fp32
+    // accumulators hold without loss; O, l and P always share one reference, so the
+    // result is the same softmax.  Saves the 48-register accumulator rescale on almost
+    // every tile.
+    constexpr float RESCALE_THR = 6.0f;
     if (__any((mx - m_run) * p.scale_log2 > RESCALE_THR)) {
-      const float m_new = fmaxf(m_run, mx);
+      const float m_new = fmaxf(m_run, mx);  // finite from the first tile on: key 0 is visible to every query
+      // (a row with no visible key yet keeps alpha = 1: it has nothing accumulated)
       const float alpha = (m_new == -INFINITY) ? 1.f : __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);
       m_run = m_new;
       l_run *= alpha;
@@ -578,8 +329,6 @@ __global__ __launch_bounds__(256) void attn_prefill_dma_kernel(const AttnK p) {
     const float mc = (m_run == -INFINITY) ? 0.f : -m_run * p.scale_log2;
     float psum = 0.f;
     bf16x8 pf[2][2];
-    f32x16 snext[2];
-    if (PIPE) compute_s(snext, Kn, true);  // independent of everything below: the scheduler interleaves it
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
       if (sub == 1 && !both) break;
@@ -614,10 +363,6 @@ __global__ __launch_bounds__(256) void attn_prefill_dma_kernel(const AttnK p) {
           oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vv, pf[sub][u], oacc[d], 0, 0, 0);
         }
       }
-    }
-    if (PIPE) {
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub) sacc[sub] = snext[sub];
     }
   }
 
@@ -1195,24 +940,11 @@ md_status md_attention_prefill_rows(const md_attn_args* a, const RowMap& rows, h
   k.n_qblk = n_q_blks;
   k.n_bh = a->batch * a->n_heads;
   k.n_heads = a->n_heads;
-  // MD_ATTN_VARIANT = reg | dma (default) | pipe for A/B runs
-  static const int variant = [] {
-    const char* e = getenv("MD_ATTN_VARIANT");
-    if (e && e[0] == 'r') return 0;
-    if (e && e[0] == 'p') return 2;
-    return 1;
-  }();
-  // [variant][head_dim 72][shared prefix]: SHP is the instantiation of the variant the slot-table call would take (same
-  // arithmetic, other addresses)
-  static void (*const kernels[3][2][2])(const AttnK) = {
-      {{attn_prefill_kernel<64>, attn_prefill_kernel<64, true>}, {attn_prefill_kernel<72>, attn_prefill_kernel<72, true>}},
-      {{attn_prefill_dma_kernel<64, false>, attn_prefill_dma_kernel<64, false, true>},
-       {attn_prefill_dma_kernel<72, false>, attn_prefill_dma_kernel<72, false, true>}},
-      {{attn_prefill_dma_kernel<64, true>, attn_prefill_dma_kernel<64, true, true>},
-       {attn_prefill_dma_kernel<72, true>, attn_prefill_dma_kernel<72, true, true>}}};
-  // the register kernel takes a (query block, head, batch) grid, the LDS-DMA kernels the XCD-aware 1-D one
-  const dim3 grid = variant == 0 ? dim3(k.n_qblk, a->n_heads, a->batch) : dim3(8 * k.n_qblk * ((k.n_bh + 7) / 8));
-  hipLaunchKernelGGL(kernels[variant][a->head_dim == 72][shp], grid, dim3(256), 0, stream, k);
+  // [head_dim 72][shared prefix]: SHP is the instantiation a call with a shared prefix table takes (same arithmetic, other
+  // addresses); the grid is the XCD-aware 1-D one the kernel decodes
+  static void (*const kernels[2][2])(const AttnK) = {{attn_prefill_dma_kernel<64>, attn_prefill_dma_kernel<64, true>},
+                                                     {attn_prefill_dma_kernel<72>, attn_prefill_dma_kernel<72, true>}};
+  hipLaunchKernelGGL(kernels[a->head_dim == 72][shp], dim3(8 * k.n_qblk * ((k.n_bh + 7) / 8)), dim3(256), 0, stream, k);
   return md_launch_status();
 }
 

@@ -64,8 +64,6 @@ md_status md_gemm_f8_qkv_rope(const md_gemm_f8_args* a, const md_rope_fuse* rf, 
 md_status md_gemm_w4_launch(const GemmK& k, int epi, hipStream_t stream);
 bool md_gemm_w4_takes(const GemmK& k, int epi);  // shape limits of the four-wave kernel for this launch
 void md_gemm_w4_set_grid(int v);     // persistent workgroups per launch of the four-wave kernel (0 = one per CU)
-void md_gemm_w4_set_debug(int half, uint32_t v);  // measurement builds: device buffer for in-kernel stamps
-void md_gemm_w4_set_variant(int v);  // measurement hook: schedule / ablation variant of the bias-epilogue kernel
 void md_attention_set_skip_dead(int v);  // attention.hip: exact work skipping of the prefill kernel (bit 0: dead half of the last key tile, bit 1: waves without a live query row)
 
 // one output segment of a grouped LoRA expand launch (lora_multi.hip; the multi-LoRA path of api.hip)

@@ -43,7 +43,6 @@
 #include "gemm_internal.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -90,15 +89,6 @@ __device__ __forceinline__ void wait_lgkm() {
   asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(N) : "memory");
 }
 #define MD_PIN() __builtin_amdgcn_sched_barrier(0)
-// ablation builds: keep a value opaque / alive without emitting an instruction
-template <class T>
-__device__ __forceinline__ void opaque(T& v) {
-  asm volatile("" : "+v"(v));
-}
-template <class T>
-__device__ __forceinline__ void keep_alive(const T& v) {
-  asm volatile("" ::"v"(v));
-}
 
 // The 64 accumulator blocks of a wave (256 registers) live in a[0:255], OWNED BY INLINE ASM: block X is
 // a[4X : 4X+3].  As compiler-visible values they made the register allocator shuffle and spill around every
@@ -136,17 +126,16 @@ __device__ __forceinline__ float acc_read() {
 //                65, 68, .., 110
 //   gap 64       lgkmcnt(0), vmcnt(0), s_barrier (see the head of the file)
 //   LDS-DMA      the 16 pieces of the pair AFTER the next one, into the buffer the barrier released, at the stream positions
-//                dma_pos() names (64 .. 127 = the rest of this pair, 128 .. = the first gaps of the next pair).  MODE picks
-//                the placement.
+//                dma_pos() names (64 .. 127 = the rest of this pair, 128 .. = the first gaps of the next pair): every sixth
+//                gap from the barrier on.
 constexpr int kReadOrder[16] = {0, 8, 1, 2, 3, 4, 5, 6, 7, 9, 10, 11, 12, 13, 14, 15};
 constexpr int kFirstUse[16] = {0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 16, 24, 32, 40, 48, 56};  // by read position k
 constexpr int kAdvanceGap = 50;                 // the load cursor moves on here: after the last wrapped piece, before gap 64
 constexpr int kBiasGap = 52;                    // first pair of a tile: the tile's bias slice is requested here
-constexpr int dma_pos(int mode, int q) { return mode == 1 ? 66 + 4 * q : mode == 2 ? 64 + 6 * q : mode == 3 ? 66 + 2 * q : 67 + 3 * q; }
+constexpr int dma_pos(int q) { return 64 + 6 * q; }
 constexpr bool modes_ok() {
-  for (int m = 1; m <= 4; ++m)
-    for (int q = 0; q < 16; ++q)
-      if (dma_pos(m, q) < 64 || dma_pos(m, q) - 128 >= kAdvanceGap || (q > 0 && dma_pos(m, q) <= dma_pos(m, q - 1))) return false;
+  for (int q = 0; q < 16; ++q)
+    if (dma_pos(q) < 64 || dma_pos(q) - 128 >= kAdvanceGap || (q > 0 && dma_pos(q) <= dma_pos(q - 1))) return false;
   return true;
 }
 static_assert(modes_ok(), "pieces are issued in order, from gap 64 on, and the wrapped ones before the cursor advances");
@@ -175,9 +164,7 @@ constexpr int frag_wait(int m) {
   return w > 15 ? 15 : w;  // lgkmcnt is a 4-bit counter; a smaller count only waits for more
 }
 
-// ABL: measurement builds (bit 1: no operand DMA, 2: no barrier, 3: no fragment reads, 4: no epilogue stores, 5: no
-// epilogue, 6: shader-clock stamps around the waits of gap 64 and the epilogue, 8: every operand load from one L2-resident MiB); results are garbage with bits 1-5 set.
-template <int EPI, int ABL = 0, int MODE = 1>
+template <int EPI>
 __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmK p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -259,9 +246,8 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmK p) {
     constexpr bool SETM0 = decltype(setm0_c)::value || (J & 3) == 0;
     constexpr int BLOCK = (J < 8 ? 0 : W_OFF) + ((J & 7) >> 2) * 4096, IMM = (J & 3) * 1024;
     // (operands copied to locals first: clang does not capture variables that appear only as asm operands of a generic lambda)
-    const uint32_t base = dma_lds + buf, vo = (ABL & 256) ? ((voff[J] & 0xfffffu) | 4096u) : voff[J], so = (ABL & 256) ? (ld_soff & 0xfffu) : ld_soff;  // base, so: wave-uniform (ABL & 256: every load from one L2-resident MiB)
+    const uint32_t base = dma_lds + buf, vo = voff[J], so = ld_soff;  // base, so: wave-uniform
     const u32x4 rs = J < 8 ? rs_a : rs_w;
-    if constexpr (ABL & 2) return;
     if constexpr (SETM0)
       asm volatile("s_add_u32 m0, %0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen offset:%5 lds" ::"s"(base), "i"(BLOCK), "v"(vo), "s"(rs), "s"(so), "i"(IMM) : "memory", "scc");
     else
@@ -277,15 +263,9 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmK p) {
     db[st] = lds_base + W_OFF + (wn * 128 + l15) * 128 + (((4 * st + g4) ^ swz8) * 16);
   }
   bf16x8 fa[2][8], fb[2][8];  // [fragment set = K step parity][16-row block]
-  if constexpr (ABL & 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) fa[0][j] = fa[1][j] = fb[0][j] = fb[1][j] = bf16x8{0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80};
-  }
   auto read_frag = [&](auto set_c, auto f_c, uint32_t a_addr, uint32_t b_addr) {
     constexpr int SET = decltype(set_c)::value, F = decltype(f_c)::value;
-    if constexpr (ABL & 8) {
-      if constexpr (F < 8) opaque(fb[SET][F]); else opaque(fa[SET][F - 8]);
-    } else if constexpr (F < 8)
+    if constexpr (F < 8)
       ds_read_b128<F * 2048>(fb[SET][F], b_addr);
     else
       ds_read_b128<(F - 8) * 2048>(fa[SET][F - 8], a_addr);
@@ -319,16 +299,11 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmK p) {
   static_for<0, 16>([&](auto j) { dma_piece(j, pair_cur, std::false_type{}); });
   advance_load_cursor();
   static_for<0, 16>([&](auto j) {
-    if constexpr (dma_pos(MODE, decltype(j)::value) < 128) dma_piece(j, pair_wr, std::false_type{});
+    if constexpr (dma_pos(decltype(j)::value) < 128) dma_piece(j, pair_wr, std::false_type{});
   });
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   read_first_frags();
-
-  // measurement build (ABL & 64): shader-clock stamps around the waits of gap 64 (s_memtime is counted by lgkmcnt: only here,
-  // where the counter is drained anyway)
-  uint32_t st_lgkm = 0, st_vm = 0, st_bar = 0, st_n = 0, st_vm_first = 0;
-  uint64_t st_first = 0, st_last = 0, st_epi = 0;
 
   // One pair = 128 MFMAs = 128 gaps.  pair_cur = the buffer being multiplied, pair_wr = the other one: it receives the late
   // pieces of the NEXT pair in the first gaps, is published by the barrier in gap 64 and read from gap 65 on; from gap 64 on
@@ -341,25 +316,13 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmK p) {
     static_for<0, 128>([&](auto xc) {
       constexpr int X = decltype(xc)::value, H = X / 64, M = X % 64, I = M / 8, J = (I & 1) ? 7 - M % 8 : M % 8;
       if constexpr (X == 64) {
-        uint64_t t0 = 0;
-        if constexpr (ABL & 64) t0 = __builtin_readcyclecounter();
-        if constexpr (!(ABL & 8)) wait_lgkm<0>();
-        if constexpr (ABL & 64) { const uint64_t t = __builtin_readcyclecounter(); st_lgkm += (uint32_t)(t - t0); t0 = t; }
+        wait_lgkm<0>();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr (ABL & 64) { const uint64_t t = __builtin_readcyclecounter(); st_vm += (uint32_t)(t - t0); if constexpr (FIRST) st_vm_first += (uint32_t)(t - t0); t0 = t; }
-        if constexpr (!(ABL & 4)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if constexpr (ABL & 64) {
-          const uint64_t t = __builtin_readcyclecounter();
-          st_bar += (uint32_t)(t - t0);
-          if (st_n == 0) st_first = t;
-          st_last = t;
-          ++st_n;
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
       }
       // counted wait: the fragments this MFMA is the first to use have landed, younger reads stay in flight
-      if constexpr (H == 0 && frag_wait(M) >= 0 && !(ABL & 8)) wait_lgkm<frag_wait(M)>();
+      if constexpr (H == 0 && frag_wait(M) >= 0) wait_lgkm<frag_wait(M)>();
       // (the first-use table assumes ascending j in row i = 0 and that block (i, *) first needs activation fragment i: both hold
       // for the serpentine order)
       mfma_acc<8 * I + J, FIRST && H == 0>(fb[H][J], fa[H][I]);
@@ -372,9 +335,9 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmK p) {
       }
       static_for<0, 16>([&](auto qc) {
         constexpr int Q = decltype(qc)::value;
-        if constexpr (dma_pos(MODE, Q) == X) dma_piece(qc, buf_cur, std::false_type{});  // pair p + 2 -> the buffer released in gap 64
+        if constexpr (dma_pos(Q) == X) dma_piece(qc, buf_cur, std::false_type{});  // pair p + 2 -> the buffer released in gap 64
         // late pieces of pair p + 1 (the first of them is the body's first DMA instruction: it writes M0 whatever its place in a block)
-        if constexpr (dma_pos(MODE, Q) - 128 == X) dma_piece(qc, buf_nxt, std::integral_constant<bool, (Q == 0 || dma_pos(MODE, Q - 1) < 128)>{});
+        if constexpr (dma_pos(Q) - 128 == X) dma_piece(qc, buf_nxt, std::integral_constant<bool, (Q == 0 || dma_pos(Q - 1) < 128)>{});
       });
       if constexpr (FIRST && X == kBiasGap) dma_bias();  // the slot's previous contents went to registers in the last epilogue
       if constexpr (X == kAdvanceGap) advance_load_cursor();
@@ -397,12 +360,9 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmK p) {
     for (int u = 1; u < npair; ++u) pair_body(std::false_type{});
     wait_lgkm<0>();
     MD_PIN();
-    uint64_t te0 = 0;
-    if constexpr (ABL & 64) { te0 = __builtin_readcyclecounter(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
     // ---- epilogue of tile vtile (the next tile's first pairs are already in the ring / in flight) ----------------------
     // block X = 8 i + j, register r: row m = 16 i + l15, col n = 16 j + 4 g4 + r   within the wave's quarter
-    if constexpr (!(ABL & 32)) {
     // This lane's 32 bias values (column 16 j + 4 g4 + r), unpacked ONCE per tile from the wave's slot.  (npair == 1: the slot's
     // DMA was waited for by gap 64's vmcnt(0) like every other piece.)
     md_f32x2 bias_f[8][2];
@@ -564,11 +524,10 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmK p) {
           if constexpr (SLAB) {
             // slab: [head][position][64] bf16 per slot
             const uint32_t head_off = (uint32_t)(head0 + jp) * (uint32_t)p.rope_ctx * 128u;
-            if constexpr (!(ABL & 16)) __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_s, kv_off[ip][q], head_off, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_s, kv_off[ip][q], head_off, 0);
           } else {
             const uint32_t off = store_off(ip, q, jp);
-            if constexpr (!(ABL & 16)) __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_c, off, 0, 0);
-            else keep_alive(v);
+            __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_c, off, 0, 0);
           }
         }
         MD_PIN();
@@ -585,34 +544,20 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmK p) {
     } else {
       lds_epilogue(I0{});
     }
-    }
     // the next tile's first fragments again (the copy read before the epilogue was not kept: 64
     // registers the epilogue does not have to carry); its first pair was published by the last barrier above
     read_first_frags();
-    if constexpr (ABL & 64) { st_epi += __builtin_readcyclecounter() - te0; asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA of the run-on stream in flight at the end of the wave
-  if constexpr (ABL & 64) {
-    if (lane == 0 && p.slabs != nullptr) {
-      float* o = p.slabs + (blockIdx.x * 4 + wave) * 8;
-      o[0] = (float)st_n; o[1] = (float)(st_last - st_first); o[2] = (float)st_lgkm; o[3] = (float)st_vm; o[4] = (float)st_bar; o[5] = (float)st_epi; o[6] = (float)st_vm_first;
-    }
-  }
 }
 
 int g_w4_grid = 0;     // md_gemm_set_tuning "w4_grid": persistent workgroups per launch (0 = one per CU); a multiple of 8
-// md_gemm_set_tuning "w4_variant" (MD_W4_VARIANT): low 4 bits = placement of the LDS-DMA pieces (MODE, 0 = the default;
-// the others exist for the bias epilogue only), the rest 16 * ABL (measurement builds, bias epilogue only)
-int g_w4_variant = [] { const char* e = getenv("MD_W4_VARIANT"); return (e && *e) ? atoi(e) : 0; }();
-uint64_t g_w4_debug = 0;  // measurement builds: device buffer for the in-kernel stamps (md_gemm_set_tuning "w4_dbg_lo" / "w4_dbg_hi")
-constexpr int kDefaultMode = 2;
 
-template <int EPI, int ABL = 0, int MODE = kDefaultMode>
+template <int EPI>
 md_status launch(const GemmK& k, hipStream_t stream) {
-  auto fn = gemm_w4_kernel<EPI, ABL, MODE>;
+  auto fn = gemm_w4_kernel<EPI>;
   MD_TRY(md_ensure_dynamic_lds((const void*)fn, LDS_BYTES));
   GemmK kk = k;
-  if constexpr (ABL & 64) kk.slabs = (float*)(uintptr_t)g_w4_debug;
   kk.tiles_m = (k.M + BM - 1) / BM;
   kk.tiles_n = (k.n_store + BN - 1) / BN;
   const int nwg = kk.tiles_m * kk.tiles_n;
@@ -630,8 +575,6 @@ md_status launch(const GemmK& k, hipStream_t stream) {
 
 }  // namespace
 
-void md_gemm_w4_set_variant(int v) { g_w4_variant = v; }
-void md_gemm_w4_set_debug(int half, uint32_t v) { g_w4_debug = half ? ((g_w4_debug & 0xffffffffull) | ((uint64_t)v << 32)) : ((g_w4_debug & ~0xffffffffull) | v); }
 void md_gemm_w4_set_grid(int v) { g_w4_grid = v > 0 ? std::max(8, v / 8 * 8) : 0; }
 
 bool md_gemm_w4_takes(const GemmK& k, int epi) {
@@ -652,36 +595,6 @@ bool md_gemm_w4_takes(const GemmK& k, int epi) {
 md_status md_gemm_w4_launch(const GemmK& k, int epi, hipStream_t stream) {
   if (k.K % 64 != 0 || k.M <= 0) return MD_ERR_INVALID_ARG;
   if (!md_gemm_w4_takes(k, epi)) return MD_ERR_UNSUPPORTED;
-  const int mode = g_w4_variant & 15, abl = g_w4_variant >> 4;  // (measurement codes: MODE + 16 * ABL)
-#ifdef MD_W4_ABLATIONS  // measurement builds only (MD_W4_ABLATIONS=1 python -c "import __graft_entry__ as g; g.build()")
-  if (epi == MD_EPI_BIAS && abl != 0) {
-    switch (256 * (mode == 0 ? kDefaultMode : mode) + abl) {
-      case 256 * 2 + 2: return launch<MD_EPI_BIAS, 2, 2>(k, stream);
-      case 256 * 2 + 4: return launch<MD_EPI_BIAS, 4, 2>(k, stream);
-      case 256 * 2 + 8: return launch<MD_EPI_BIAS, 8, 2>(k, stream);
-      case 256 * 2 + 14: return launch<MD_EPI_BIAS, 14, 2>(k, stream);
-      case 256 * 2 + 16: return launch<MD_EPI_BIAS, 16, 2>(k, stream);
-      case 256 * 2 + 32: return launch<MD_EPI_BIAS, 32, 2>(k, stream);
-      case 256 * 2 + 46: return launch<MD_EPI_BIAS, 46, 2>(k, stream);
-      case 256 * 2 + 64: return launch<MD_EPI_BIAS, 64, 2>(k, stream);
-      case 256 * 2 + 80: return launch<MD_EPI_BIAS, 80, 2>(k, stream);
-      case 256 * 2 + 256: return launch<MD_EPI_BIAS, 256, 2>(k, stream);
-      case 256 * 2 + 272: return launch<MD_EPI_BIAS, 272, 2>(k, stream);
-      case 256 * 2 + 320: return launch<MD_EPI_BIAS, 320, 2>(k, stream);
-      default: return MD_ERR_INVALID_ARG;
-    }
-  }
-#endif
-  if (abl != 0) return MD_ERR_INVALID_ARG;
-  if (mode != 0 && mode != kDefaultMode) {
-    if (epi != MD_EPI_BIAS) return MD_ERR_INVALID_ARG;
-    switch (mode) {
-      case 1: return launch<MD_EPI_BIAS, 0, 1>(k, stream);
-      case 3: return launch<MD_EPI_BIAS, 0, 3>(k, stream);
-      case 4: return launch<MD_EPI_BIAS, 0, 4>(k, stream);
-      default: return MD_ERR_INVALID_ARG;
-    }
-  }
   switch (epi) {
     case MD_EPI_BIAS: return launch<MD_EPI_BIAS>(k, stream);
     case MD_EPI_GELU: return launch<MD_EPI_GELU>(k, stream);

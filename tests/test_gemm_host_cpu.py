@@ -82,6 +82,26 @@ def test_workspace_bytes_and_partial_slices_are_what_they_were(cfg, slices):
     assert lib.md_gemm_partial_slices(None) == 0
 
 
+# every key md_gemm_set_tuning takes, with the value the library starts from (Knobs' initialisers, g_attn_skip_dead, g_w4_grid)
+TUNING_DEFAULTS = dict(tile=-1, w4=1, w4_grid=0, decode_cfg=16, decode_slices=0, rope_fuse=1, group_m=0, persist=1, decode_nt=0,
+                       small_m_rule=1, attn_skip_dead=3)
+# keys of the measurement variants that were retired with their kernels: unknown keys now
+RETIRED_TUNING_KEYS = ["w4_variant", "w4_dbg_lo", "w4_dbg_hi"]
+
+
+def test_tuning_keys_the_kept_ones_and_the_retired_ones():
+    lib = _lib.load()
+    try:
+        for key in RETIRED_TUNING_KEYS:
+            assert lib.md_gemm_set_tuning(key.encode(), 0) == ERR_ARG, key
+        for key, default in TUNING_DEFAULTS.items():
+            assert lib.md_gemm_set_tuning(key.encode(), default) == OK, key
+    finally:  # (there is no getter: the defaults are what the other tests of this process expect)
+        for key, default in TUNING_DEFAULTS.items():
+            lib.md_gemm_set_tuning(key.encode(), default)
+    assert lib.md_gemm_set_tuning(None, 0) == ERR_ARG
+
+
 def gemm_args(**kw):
     """A launch every host check accepts: 100 rows of the (2048, 2048) layer."""
     f = dict(a=P, lda=2048, n=2048, k=2048, n_pad=2048, k_pad=2048, w=P, c=P, ldc=2048, r=None, ldr=0, res_row_mod=0, m=100,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Decode-step attention (RoPE + cache update fused, B = 64 x 32 heads, contexts 736..767) as the decode graph runs it:
 a hipGraph of 48 launches over alternating caches, replayed; us per launch and TB/s of K / V bytes.
-MD_ATTN_DECODE_VAR / MD_ATTN_DECODE_NT select kernel variants (one per process)."""
+MD_ATTN_DECODE_NT selects the kernel variant (one per process)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -35,4 +35,4 @@ for rep in range(5):
     e1.record(); torch.cuda.synchronize()
     best = min(best, e0.elapsed_time(e1) / (4 * 48) * 1e3)
 nbytes = float(lens.sum().item()) * h * hd * 2 * 2
-print(f"var={os.environ.get('MD_ATTN_DECODE_VAR','0')} nt={os.environ.get('MD_ATTN_DECODE_NT','1')}: {best:6.1f} us per launch (graph replay, launch gaps included)  {nbytes / best / 1e6:5.2f} TB/s")
+print(f"nt={os.environ.get('MD_ATTN_DECODE_NT','1')}: {best:6.1f} us per launch (graph replay, launch gaps included)  {nbytes / best / 1e6:5.2f} TB/s")
