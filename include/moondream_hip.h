@@ -593,6 +593,19 @@ md_status md_attention_decode_rope_f8(const void* qkv, int64_t ld, void* o, int6
                                       const int32_t* kv_len, int32_t batch, int32_t n_heads, int32_t rot_dim, float scale,
                                       float k_scale, float v_scale, void* stream);
 
+/* md_attention_decode_rope_f8 with the slot table of md_text_forward_slots and the shared-prefix table of
+ * md_text_forward_shared (slots, n_slots, prefix_slots, prefix_len: see there), so that tests reach the grouped e4m3
+ * kernel directly: row b reads keys [0, prefix_len[b]) from slot prefix_slots[b] of the e4m3 slabs, the rest from its own
+ * slot, and writes the new row (both copies) to its own slot only.  Every output bit and slab byte of a live row equals
+ * what the call without a prefix table gives over a slot that holds a copy of the prefix.  prefix_slots == NULL: the
+ * slot-table launch of md_attention_decode_rope_f8's kernel.  A prefix slot's e4m3 bytes are its WRITER's job: an image
+ * prefill into the slot through md_text_forward* quantises them, anything else calls md_kv_quantize_f8. */
+md_status md_attention_decode_rope_f8_shared(const void* qkv, int64_t ld, void* o, int64_t ldo, const float* freqs, void* k_slab,
+                                             void* v_slab, void* k8_slab, void* v8_slab, int64_t slab_batch_stride, int32_t ctx,
+                                             const int32_t* kv_len, int32_t batch, int32_t n_heads, int32_t rot_dim, float scale,
+                                             float k_scale, float v_scale, const int32_t* slots, int32_t n_slots,
+                                             const int32_t* prefix_slots, const int32_t* prefix_len, void* stream);
+
 /* (Re)build the e4m3 copy from the bf16 slabs for positions pos .. pos + n_pos - 1 of `batch` slots, every layer and
  * head (pos = pos0[b], device int32, or pos_fixed when pos0 is NULL): after bf16 rows were written by something other
  * than md_text_forward (load_encoded_image's copy). */
@@ -632,7 +645,12 @@ md_status md_text_forward_slots(const md_text_model* m, const void* x, void* hid
  * Bits: every output of a row (hidden, the K / V rows written) equals md_text_forward_slots' over a slot into which keys
  * [0, prefix_len[b]) of the prefix slot have been copied.  The decode attention groups rows: one K / V load of a prefix row
  * serves every row of a group sharing its prefix slot.
- * kv->k8 / kv->v8 (the e4m3 copy of the fp8 mode) set, NULL kv, slots with n_slots <= 0: MD_ERR_INVALID_ARG.
+ * The e4m3 copy of the fp8 mode (kv->k8 / v8 with k_scale / v_scale; MHA, head_dim 64): the prompt prefill attends over the
+ * bf16 slabs and quantises its rows into the rows' own slots; a decode step attends over the e4m3 copy with the same
+ * addressing rule and grouping (csrc/attention_f8kv.hip), and the bit statement above holds for all four slabs.  The e4m3
+ * bytes of a prefix slot are its writer's job: an image prefill into the slot quantises them, md_kv_quantize_f8 after any
+ * other write (load_encoded_image's copy).
+ * kv->k8 / kv->v8 without both scale arrays, NULL kv, slots with n_slots <= 0: MD_ERR_INVALID_ARG.
  * Workspace: md_text_workspace_bytes(m, batch, q_len). */
 md_status md_text_forward_shared(const md_text_model* m, const void* x, void* hidden, int32_t batch, int32_t q_len,
                                  const int32_t* pos0, const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,

@@ -941,10 +941,13 @@ md_status text_forward_impl(const md_text_model* m, const void* x_in, void* hidd
   return MD_OK;
 }
 
-// the checks of the shared-prefix entry points that need no device: a table needs the slot table, and the e4m3 KV copy (fp8
-// mode) is not supported with one
+// the checks of the shared-prefix entry points that need no device: a table needs the slot table, and an e4m3 KV copy (fp8
+// mode) must be complete -- both slabs and both scale arrays.  Whether the decode steps then read it is text_forward_rows'
+// rule (kv_f8_scaled, MHA, head_dim 64): the grouped e4m3 kernel, otherwise the grouped bf16 one.  The prompt prefill reads the
+// bf16 slabs and quantises its rows into the rows' own slots; a prefix slot's e4m3 bytes are its writer's job (an image
+// prefill into the slot quantises them; md_kv_quantize_f8 after any other write).
 md_status shared_args_ok(const md_kv_cache* kv, const RowMap& rows) {
-  MD_CHECK_ARG(kv && kv->k8 == nullptr && kv->v8 == nullptr);
+  MD_CHECK_ARG(kv && ((kv->k8 == nullptr && kv->v8 == nullptr) || kv_f8_scaled(kv)));
   MD_CHECK_ARG(rows.slots == nullptr || rows.n_slots > 0);  // as md_text_forward_slots
   MD_CHECK_ARG(rows.pfx_slots == nullptr || (rows.slots != nullptr && rows.pfx_len != nullptr));
   return MD_OK;

@@ -954,7 +954,8 @@ extern "C" md_status md_attention_prefill(const md_attn_args* a, void* stream) {
 
 // internal (api.hip) and behind every md_attention_decode* entry point: ONE place for the argument checks, the choice of
 // kernel and each kernel's argument list.
-//   e4m3 copy present, fused and MHA  -> attn_decode_f8_kernel (attention_f8kv.hip)
+//   e4m3 copy present, fused and MHA  -> attn_decode_f8_kernel (attention_f8kv.hip); with a prefix table its grouped
+//                                        launch shape attn_decode_f8_shared_kernel
 //   prefix table present              -> attn_decode_shared_kernel, SHG rows per workgroup
 //   otherwise                         -> attn_decode_kernel, 16 waves for few (row, head) pairs, else 4
 // NT (non-temporal K / V loads) for MHA at 4 waves and in the grouped kernel, unless MD_ATTN_DECODE_NT=0.
@@ -967,7 +968,8 @@ md_status md_attention_decode_rows(const DecodeAttn& d, const RowMap& rows, hipS
   MD_CHECK_ARG(d.ldq >= (d.fused ? 3 : 1) * d.n_heads * 64 && d.ldo >= d.n_heads * 64);
   const bool mha = d.n_heads == d.n_kv_heads;
   if (d.fused) MD_CHECK_ARG(d.freqs && mha && d.rot_dim % 2 == 0 && d.rot_dim > 0 && d.rot_dim <= 64);
-  if (d.k8_slab && d.v8_slab && d.fused) return md_attention_decode_f8_rows(d, rows, stream);
+  if (d.k8_slab && d.v8_slab && d.fused)
+    return rows.pfx_slots != nullptr ? md_attention_decode_f8_shared_rows(d, rows, stream) : md_attention_decode_f8_rows(d, rows, stream);
 
   const bool nt = mha && decode_attn_nt();
   const float sl2 = d.scale * 1.4426950408889634f;

@@ -52,6 +52,7 @@ md_status md_attention_decode_rows(const DecodeAttn& d, const RowMap& rows, hipS
 md_status md_attention_prefill_rows(const md_attn_args* a, const RowMap& rows, hipStream_t stream, int q_blk0 = 0, int n_q_blks = -1);
 // attention_f8kv.hip
 md_status md_attention_decode_f8_rows(const DecodeAttn& d, const RowMap& rows, hipStream_t stream);
+md_status md_attention_decode_f8_shared_rows(const DecodeAttn& d, const RowMap& rows, hipStream_t stream);  // rows with a prefix table
 md_status md_kv_quantize_f8_layer(const md_kv_cache* kv, int layer, const int32_t* pos0, int pos_fixed, int batch, int n_heads,
                                   int n_pos, const RowMap& rows, hipStream_t stream);
 // elementwise.hip

@@ -1217,7 +1217,9 @@ class MoondreamModel:
             # a graph is replayed only on the stream (context) it was captured for: the pipelined engine's
             # decode stream and the default stream each keep their own captures
             key = ("decode", b, n, suppress_id, ws.data_ptr(), self._kv_k.data_ptr(), logits.data_ptr(),
-                   torch.cuda.current_stream(self._device).cuda_stream, b1, float(temperature), float(top_p)) + rows.key()
+                   torch.cuda.current_stream(self._device).cuda_stream, b1, float(temperature), float(top_p),
+                   # the e4m3 copy decides the attention kernel a step bakes in (enable_fp8 also clears the graphs)
+                   self._kv_k8.data_ptr() if self._kv8_scales is not None and self._kv_k8 is not None else 0) + rows.key()
             entry = self._graphs.get(key)
             if entry is not None:
                 buf, pos_buf, u_buf = entry[1]
@@ -1384,9 +1386,9 @@ class MoondreamModel:
             self.last_phase_ms = {marks[i][0]: marks[i - 1][1].elapsed_time(marks[i][1]) for i in range(1, len(marks))}
 
     def _shares_prefix(self, lora: Optional[PackedLora]) -> bool:
-        """The shared-prefix path serves the base model over the bf16 cache; a LoRA variant or the fp8 mode's e4m3 KV copy
+        """The shared-prefix path serves the base model, over the bf16 cache or (fp8 mode) its e4m3 copy; a LoRA variant
         takes the copy path (same results)."""
-        return lora is None and self._kv8_scales is None
+        return lora is None
 
     def _encode_distinct(self, images, settings: Optional[dict]) -> List[EncodedImage]:
         """Each distinct image object encoded once (``encode_image``), repeated per row: the copy path's input."""
@@ -1399,7 +1401,9 @@ class MoondreamModel:
     def _prepare_sequences_shared(self, images, prompts: Sequence[Sequence[int]], mark=None, sampler=None):
         """``_prepare_sequences`` with a SHARED image prefix (moondream_amd/shared_prefix.py): each distinct image (by identity)
         is prefilled or loaded ONCE, into prefix slot k < P; the rows take slots P + r and read the prefix from there.  Raw
-        images go through one ViT batch and ``_prefill_images``; EncodedImages are loaded once.  One prompt prefill per
+        images go through one ViT batch and ``_prefill_images``; EncodedImages are loaded once.  In the fp8 KV mode both of these
+        also write the prefix slot's e4m3 rows (the prefill quantises, ``load_encoded_image`` calls md_kv_quantize_f8), once per
+        image; the prompt prefill quantises its rows into the rows' own slots.  One prompt prefill per
         distinct length (md_text_forward_shared).  Returns (order, first, hidden_last, next_pos, rows, row_perm): the first
         four as ``_prepare_sequences`` returns them, in this path's row order; ``rows`` is the routing over the prefix table
         (``_Rows``); ``row_perm`` maps a row to its row in the copy
@@ -1464,8 +1468,9 @@ class MoondreamModel:
         ``share_prefix``: rows whose image is the same object (the same ``EncodedImage``, or the same PIL image by identity)
         read ONE copy of its KV prefix -- the image is encoded / loaded once, and the decode attention loads each prefix row
         once for a group of rows (md_decode_step_shared).  The ids are those of the same call with every image replaced by
-        its ``EncodedImage`` (the copy path), greedy or sampled with the same ``generator`` seed.  A LoRA ``variant`` or the
-        fp8 KV mode takes the copy path.
+        its ``EncodedImage`` (the copy path), greedy or sampled with the same ``generator`` seed, in the bf16 mode and in the
+        fp8 KV mode (the decode steps then read one e4m3 prefix per image: csrc/attention_f8kv.hip).  A LoRA ``variant``
+        takes the copy path.
 
         ``temperature`` > 0 (round 6): every sequence SAMPLES each of its tokens -- the first from the prompt pass's logits,
         the rest inside the lockstep loop -- with the reference's rule (softmax(logits / T), ``_apply_top_p``, multinomial:
@@ -2219,8 +2224,8 @@ class MoondreamModel:
     def query_many(self, image, questions: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
         """Many questions about ONE image (reference pattern: encode_image once, then query per question,
         moondream.py:230-268,620-623), answered in one batch that reads a single copy of the image's KV prefix.  Element i ==
-        ``{"answer": batch_query([encode_image(image)] * N, questions)[i]}``.  A LoRA ``variant`` (settings) or the fp8 KV mode
-        takes the copy path, with the same results."""
+        ``{"answer": batch_query([encode_image(image)] * N, questions)[i]}``, in the bf16 mode and in the fp8 KV mode.  A LoRA
+        ``variant`` (settings) takes the copy path, with the same results."""
         prompts = self._query_prompts(questions)
         enc = self.encode_image(image, settings)
         ids = self.batch_generate_ids([enc] * len(prompts), prompts, share_prefix=True, **self._sampling_kwargs(settings))
@@ -2228,13 +2233,13 @@ class MoondreamModel:
 
     def detect_many(self, image, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
         """``detect`` of many objects in ONE image over a single copy of its KV prefix.  Element i ==
-        ``batch_detect([encode_image(image)] * N, objects)[i]``.  LoRA variant / fp8 KV mode: the copy path, same results."""
+        ``batch_detect([encode_image(image)] * N, objects)[i]`` (fp8 KV mode included).  LoRA variant: the copy path, same results."""
         enc = self.encode_image(image, settings)
         return [{"objects": o} for o in self._batch_detect_like([enc] * len(objects), objects, "detect", True, settings, True)]
 
     def point_many(self, image, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
         """``point`` for many objects in ONE image over a single copy of its KV prefix.  Element i ==
-        ``batch_point([encode_image(image)] * N, objects)[i]``.  LoRA variant / fp8 KV mode: the copy path, same results."""
+        ``batch_point([encode_image(image)] * N, objects)[i]`` (fp8 KV mode included).  LoRA variant: the copy path, same results."""
         enc = self.encode_image(image, settings)
         return [{"points": o} for o in self._batch_detect_like([enc] * len(objects), objects, "point", False, settings, True)]
 

@@ -10,6 +10,8 @@ The paths are interleaved across repeats; the median is reported.  copy and shar
 
   python tools/bench_shared_prefix.py [--repeats 5]
   python tools/bench_shared_prefix.py --profile 4   # (1, 64) copy / shared only, for a rocprofv3 --kernel-trace --stats run
+  python tools/bench_shared_prefix.py --fp8 > profiles/shared_prefix_f8_bench.json
+      # the same legs in the fp8 KV mode: enable_fp8(kv_cache=True) calibrated on the tool's own images, before they are encoded
 """
 import argparse
 import json
@@ -31,6 +33,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--profile", type=int, default=0, help="only (1, 64) copy then shared, N timed calls each")
+    ap.add_argument("--fp8", action="store_true", help="every leg in the fp8 mode with the e4m3 copy of the KV cache")
     args = ap.parse_args()
 
     import torch
@@ -44,6 +47,9 @@ def main():
     model = MoondreamModel(cfg, sd, device="cuda", tokenizer=IdTokenizer(), max_batch=132)
     model.compile()
     images = [synth.synthetic_image(i, args.seed) for i in range(4)]
+    if args.fp8:
+        info = model.enable_fp8(images, synth.synthetic_vqa_prompt(cfg, 0, args.seed), kv_cache=True)
+        assert info["kv_cache_fp8"], "this model has no e4m3 KV mode (MHA, head_dim 64, context <= 2048)"
     encs = [model.encode_image(im) for im in images]
     prompts_all = [synth.synthetic_vqa_prompt(cfg, i, args.seed) for i in range(128)]
 
@@ -74,11 +80,11 @@ def main():
                 run(path, 1, 64)  # warm-up: graph captures
                 for _ in range(args.profile):
                     timed(path, 1, 64)
-            print(json.dumps({"profile_calls": args.profile, "decode_steps_per_call": TOKENS - 1, "rows": 64}))
+            print(json.dumps({"profile_calls": args.profile, "decode_steps_per_call": TOKENS - 1, "rows": 64, "fp8_kv": args.fp8}))
             return
         paths = ("raw", "copy", "shared", "shared_raw")
         result = {"metric": "shared_prefix_answers_per_s", "model": args.model, "tokens": TOKENS, "repeats": args.repeats,
-                  "prompt_len": len(prompts_all[0])}
+                  "prompt_len": len(prompts_all[0]), "fp8_kv": args.fp8}
         for n_img, per in CONFIGS:
             n = n_img * per
             ids = {p: run(p, n_img, per) for p in paths}  # warm-up
