@@ -12,7 +12,7 @@ import torch
 
 from moondream_amd import _lib
 from moondream_amd.weights import PackedLinear, PackedLayerNorm, rope_table, reference_pixel_lut
-from util import compare, compare_elementwise, quantize_int4
+from util import compare, compare_attention_elementwise, compare_elementwise, quantize_int4
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -791,6 +791,8 @@ def test_attention_no_mask(lib, hd, t):
     o = run_prefill(lib, q, k, v, t, t, prefix=t)
     ref = ref_attention(q.permute(0, 2, 1, 3), k, v, None, 1 / math.sqrt(hd)).permute(0, 2, 1, 3)
     compare(f"attn hd{hd} t{t}", o, ref, 6e-3, 4e-2)
+    # and every element against the exact attention (derived bound; permute: [B, T, H, d] -> [B, H, T, d])
+    compare_attention_elementwise(f"attn hd{hd} t{t}", o.permute(0, 2, 1, 3), q.permute(0, 2, 1, 3), k, v, None, 1 / math.sqrt(hd))
 
 
 @pytest.mark.parametrize("hd,t", [(72, 729), (64, 730), (64, 77)])
@@ -840,6 +842,7 @@ def test_attention_spiky_scores_force_rescale(lib):
     o = run_prefill(lib, q, k, v, t, t, prefix=t)
     ref = ref_attention(q.permute(0, 2, 1, 3), k, v, None, 1 / math.sqrt(hd)).permute(0, 2, 1, 3)
     compare("attn spiky", o, ref, 6e-3, 4e-2)
+    compare_attention_elementwise("attn spiky", o.permute(0, 2, 1, 3), q.permute(0, 2, 1, 3), k, v, None, 1 / math.sqrt(hd))
 
 
 @pytest.mark.parametrize("q_len,pos", [(730, 0), (5, 730), (32, 730), (1, 735), (200, 650)])
@@ -859,6 +862,8 @@ def test_attention_prefix_lm_against_slab(lib, q_len, pos):
         allowed = prefix_lm_allowed(torch.arange(p0, p0 + q_len), p0 + q_len, prefix).cuda()
         ref = ref_attention(q[bi].permute(1, 0, 2), k[bi, :, : p0 + q_len], v[bi, :, : p0 + q_len], allowed, 1 / 8.0)
         compare(f"prefix-lm q{q_len} pos{p0}", o[bi], ref.permute(1, 0, 2), 6e-3, 4e-2)
+        compare_attention_elementwise(f"prefix-lm q{q_len} pos{p0}", o[bi].permute(1, 0, 2), q[bi].permute(1, 0, 2), k[bi, :, : p0 + q_len],
+                                      v[bi, :, : p0 + q_len], allowed, 1 / 8.0)
 
 
 def test_attention_decode(lib):
@@ -875,6 +880,7 @@ def test_attention_decode(lib):
         qq = q[bi, : h * hd].view(h, 1, hd)
         ref = ref_attention(qq, k[bi, :, :n], v[bi, :, :n], None, 0.125)
         compare(f"decode attn len{n}", o[bi].view(h, 1, hd), ref, 6e-3, 4e-2)
+        compare_attention_elementwise(f"decode attn len{n}", o[bi].view(h, 1, hd), qq, k[bi, :, :n], v[bi, :, :n], None, 0.125)
 
 
 def test_decode_attention_with_fused_rope_equals_two_kernels(lib):
@@ -1269,3 +1275,4 @@ def test_decode_attention_over_e4m3_kv_cache(lib):
         pr = torch.exp(s - s.amax(dim=1, keepdim=True))
         want = (torch.einsum("hn,hnd->hd", pr.to(BF16).float(), vd) / pr.sum(dim=1, keepdim=True)).to(BF16)
         compare(f"decode attention over the e4m3 cache, len {n}", o[bi].view(h, hd), want, 6e-3, 4e-2)
+        compare_attention_elementwise(f"decode attention over the e4m3 cache, len {n}", o[bi].view(h, 1, hd), q.unsqueeze(1), kd, vd, None, 0.125)

@@ -2,13 +2,18 @@
 walked in 64-wide K chunks (the kernels' slice width) in several orders and split-K associations passes with zero violations,
 and every localised error of the kind a ragged tile makes -- a K slice lost in one row, the bias lost in one column, two
 8-column store groups swapped, the rows of the second 64-row half shifted by one -- is rejected, with every violation inside the
-mutated region."""
+mutated region.
+
+The same for the per-element attention bound of util.compare_attention_elementwise, on the probe inputs of
+tests/test_attention_exact_gpu.py: a float32 model of the kernels (64-key tiles, online softmax, bf16 probabilities) is inside
+it, and the model with ONE key wrongly admitted or wrongly dropped is outside it in every row the probe aims at that key."""
 import math
 
 import pytest
 import torch
 
-from util import compare_elementwise, elementwise_excess
+from test_attention_exact_gpu import DEC_CTX, PROBES, prefill_geometry, visibility
+from util import attention_excess, compare_attention_elementwise, compare_elementwise, elementwise_excess
 
 BF16 = torch.bfloat16
 SHAPES = [(128, 2048, 3584), (100, 8192, 2048), (65, 704, 256), (97, 1024, 1000)]
@@ -140,3 +145,106 @@ def test_non_finite_and_fp32_partials():
         compare_elementwise("nan", got, a, w, b, rounded=True)
     with pytest.raises(AssertionError):
         compare_elementwise("bf16 result held to the fp32 bound", finish(acc, b), a, w, b, rounded=False)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# attention: util.compare_attention_elementwise on the probes of test_attention_exact_gpu.py
+# ---------------------------------------------------------------------------------------------------------------------
+def attention_model_f32(q, k, v, allowed, scale, tile=64):
+    """The kernels' arithmetic in float32 for one sequence: q [H, rows, d], k / v [H, keys, d], allowed [rows, keys].  Keys in tiles
+    of 64, raw scores, online softmax in the exp2 domain with the scale folded into one constant, probabilities rounded to bf16
+    for P V while the row sum adds their fp32 values, one division and one bf16 rounding at the end."""
+    c = torch.tensor(scale, dtype=torch.float32) * torch.tensor(1.4426950408889634, dtype=torch.float32)
+    qf, kf, vf = q.float(), k.float(), v.float()
+    h, rows, _ = qf.shape
+    m = torch.full((h, rows), float("-inf"))
+    l = torch.zeros(h, rows)
+    o = torch.zeros(h, rows, vf.shape[-1])
+    for k0 in range(0, kf.shape[1], tile):
+        live = allowed[:, k0 : k0 + tile]
+        if not bool(live.any()):
+            continue
+        s = (qf @ kf[:, k0 : k0 + tile].transpose(-1, -2)).masked_fill(~live, float("-inf"))
+        m_new = torch.maximum(m, s.amax(-1))
+        ref = torch.where(torch.isinf(m_new), torch.zeros_like(m_new), m_new)
+        alpha = torch.where(torch.isinf(m), torch.zeros_like(m), torch.exp2((m - ref) * c))
+        p = torch.exp2(s * c - (ref * c).unsqueeze(-1))
+        l = l * alpha + p.sum(-1)
+        o = o * alpha.unsqueeze(-1) + p.to(BF16).float() @ vf[:, k0 : k0 + tile]
+        m = m_new
+    return (o / l.unsqueeze(-1)).to(BF16)
+
+
+# (prefix, q_len, ctx, pos0 per sequence, no mask, head_dim): causal over two query blocks, a prefix inside a wave, a continuation
+# across the prefix end, no mask with head_dim 72, and decode rows at both ends of the length list
+ATTN_GEOMETRY = [(0, 129, 256, (0, 3), False, 64), (70, 200, 256, (0, 3), False, 64), (730, 33, 768, (731, 728), False, 64),
+                 (732, 729, 729, (0, 3), True, 72)]
+
+
+def attention_cases():
+    for prefix, q_len, ctx, pos0, no_mask, hd in ATTN_GEOMETRY:
+        kv_lens, vis = prefill_geometry(prefix, q_len, ctx, pos0, no_mask)
+        yield f"prefix{prefix} q{q_len} ctx{ctx} hd{hd}", vis, kv_lens, ctx, hd
+    lens = [1, 2, 33, 256, 729, 2047, 2048]
+    yield "decode rows", [visibility(n - 1, 1, n, 0, DEC_CTX) for n in lens], lens, DEC_CTX, 64
+
+
+ATTN_CASES = list(attention_cases())
+
+
+@pytest.mark.parametrize("probe", list(PROBES))
+@pytest.mark.parametrize("case", ATTN_CASES, ids=lambda c: c[0])
+def test_attention_bound_accepts_the_float32_kernel_model(case, probe):
+    name, vis, kv_lens, ctx, hd = case
+    scale = 1.0 / math.sqrt(hd)
+    q, k, v, _ = PROBES[probe](vis, 4, 4, hd, ctx, kv_lens, scale, seed=7)
+    for bi, (allowed, _) in enumerate(vis):
+        got = attention_model_f32(q[bi], k[bi], v[bi], allowed, scale)
+        ex = compare_attention_elementwise(f"model {name} {probe} seq {bi}", got, q[bi], k[bi], v[bi], allowed.unsqueeze(0), scale)
+        assert int((ex > 0).sum()) == 0
+
+
+@pytest.mark.parametrize("case", ATTN_CASES, ids=lambda c: c[0])
+def test_one_key_mask_errors_are_rejected_in_every_row_the_spikes_aim_at(case):
+    """Head 0's rows aim at their last visible key: the model that DROPS it is outside the bound in each of them.  Head 1's rows
+    aim at their first hidden key: the model that ADMITS it is outside the bound in each of them."""
+    name, vis, kv_lens, ctx, hd = case
+    scale = 1.0 / math.sqrt(hd)
+    q, k, v, targets = PROBES["spikes"](vis, 4, 4, hd, ctx, kv_lens, scale, seed=7)
+    checked = {"dropped": 0, "admitted": 0}
+    for bi, (allowed, _) in enumerate(vis):
+        rows = torch.arange(allowed.shape[0])
+        n_vis = allowed.sum(1)
+        for what, head in (("dropped", 0), ("admitted", 1)):
+            t = targets[bi, head]
+            # the row owns a spike at exactly the key the mutation flips (a row with one visible key cannot lose it: no softmax left)
+            owns = (t == n_vis - 1) & (n_vis > 1) if what == "dropped" else (t == n_vis) & (t >= 0)
+            if not bool(owns.any()):
+                continue
+            mutated = allowed.clone()
+            mutated[rows[owns], t[owns]] = what == "admitted"
+            got = attention_model_f32(q[bi], k[bi], v[bi], mutated, scale)
+            with pytest.raises(AssertionError, match="exceed the per-element bound"):
+                compare_attention_elementwise(f"{what} {name} seq {bi}", got, q[bi], k[bi], v[bi], allowed.unsqueeze(0), scale)
+            bad = (attention_excess(got, q[bi], k[bi], v[bi], allowed.unsqueeze(0), scale) > 0).any(-1)  # [H, rows]
+            assert bool(bad[head][owns].all()), f"{what} {name} seq {bi}: rows {rows[owns][~bad[head][owns]].tolist()} of head {head} pass"
+            assert not bool(bad[:, ~owns].any()), f"{what} {name} seq {bi}: violations outside the mutated rows"
+            checked[what] += int(owns.sum())
+    print(f"{name}: {checked}")
+    assert checked["dropped"] > 0 and (checked["admitted"] > 0 or all(int(a.sum(1).min()) == ctx for a, _ in vis))
+
+
+@pytest.mark.parametrize("n", [33, 729, 2048])
+def test_uniform_probe_flags_one_dropped_key(n):
+    """q = 0, integer V: one key lost anywhere among n moves most features by more than one bf16 rounding plus the fp32 sums."""
+    vis = [visibility(n - 1, 1, n, 0, DEC_CTX)]
+    q, k, v, _ = PROBES["uniform"](vis, 4, 4, 64, DEC_CTX, [n], 0.125, seed=11)
+    allowed = vis[0][0]
+    for lost in (0, n // 2, n - 1):
+        mutated = allowed.clone()
+        mutated[0, lost] = False
+        got = attention_model_f32(q[0], k[0], v[0], mutated, 0.125)
+        bad = attention_excess(got, q[0], k[0], v[0], allowed.unsqueeze(0), 0.125) > 0  # [H, 1, 64]
+        print(f"n {n}, key {lost} lost: {bad.sum(-1).flatten().tolist()} of 64 features flagged per head")
+        assert bool(bad.any(-1).all())
+        assert int(bad.sum()) > bad.numel() // 2
