@@ -12,7 +12,7 @@ import torch
 
 from moondream_amd import _lib
 from moondream_amd.weights import PackedLinear, PackedLayerNorm, rope_table, reference_pixel_lut
-from util import compare, compare_attention_elementwise, compare_elementwise, quantize_int4
+from util import compare, compare_attention_elementwise, compare_elementwise, compare_f8_elementwise, gemm_f8_exact, quantize_int4
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -1160,6 +1160,9 @@ def test_gemm_f8_bias_exact_against_dequantised_operands(lib, m, k, n):
     compare(f"gemm_f8 bias {m}x{k}x{n} vs dequantised fp32", got, want, 2e-3, 1.5e-2)
     # and the quantisation itself costs what e4m3 operands cost (3 mantissa bits each): a few percent against bf16
     compare(f"gemm_f8 bias {m}x{k}x{n} vs the bf16 layer", got, ref_linear(x, lin.w[:n, :k], lin.b[:n]), 8e-2)
+    # every element against the float64 value of the e4m3 codes (util.compare_f8_elementwise)
+    exact, mag = gemm_f8_exact(a8, a_scale, lin8.q[:n], lin8.scale[:n], lin.b[:n])
+    compare_f8_elementwise(f"gemm_f8 bias {m}x{k}x{n} per element", got, exact, mag, lin.k_pad)
 
 
 def test_gemm_f8_identity_detects_transposes(lib):
@@ -1190,11 +1193,17 @@ def test_gemm_f8_gelu_residual_and_fp8_output(lib):
     compare("gemm_f8 fp8 part (dequantised)", g8 * out_scale, w8 * out_scale, 2e-2)  # a bf16 1-ulp flip upstream can move an fp8 code
     assert float((g8 != w8).float().mean()) < 0.02
     assert torch.equal(got8[:, n - 1152 :], torch.zeros_like(got8[:, n - 1152 :]))  # K padding of the consumer: 0x00
+    # every element: the bf16 columns against the float64 value, every e4m3 code between the codes of its interval's ends
+    exact, mag = gemm_f8_exact(a8, a_scale, lin8.q, lin8.scale, lin.b)
+    compare_f8_elementwise("gemm_f8 bf16 | GELU e4m3 per element", got[:, :1152], exact, mag, lin.k_pad, gelu_from=1152, got8=got8,
+                           f8_from=1152, c8_inv_scale=1.0 / out_scale)
     # residual epilogue, rows of the second operand taken modulo 729 (the ViT's position embedding form)
     r = randn(729, lin.n_pad, seed=53)
     got_r, _ = gemm_f8(lib, a8, a_scale, lin8, m, epi=2, r=r, res_row_mod=729)
     want_r = (r[torch.arange(m, device="cuda") % 729][:, :n].float() + pre[:, :n].float()).to(BF16)
     compare("gemm_f8 residual", got_r, want_r, 2e-3, 1.5e-2)
+    compare_f8_elementwise("gemm_f8 residual per element", got_r, exact[:, :n], mag[:, :n], lin.k_pad,
+                           residual=r[torch.arange(m, device="cuda") % 729][:, :n])
 
 
 def test_quantize_layernorm_amax_f8(lib):

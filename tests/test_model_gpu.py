@@ -193,6 +193,72 @@ def test_fp8_mode_rope_kv_write_in_gemm_epilogue_is_bit_identical(tiny):
         assert torch.equal(a, b), name
 
 
+def test_fp8_mode_rope_kv_write_in_gemm_epilogue_past_a_workgroups_first_tile(tiny):
+    """The fused epilogue of gemm_f8_kernel<MD_EPI_QKV_ROPE> in a workgroup's SECOND tile: 16 sequences of 735 rows are
+    46 x 6 = 276 tiles of the [q | k | v | fc1] layer, more than the device has CUs, so the persistent loop re-enters the RoPE /
+    KV-write epilogue with the next tile's operands already in flight.  Differing start positions per sequence; fused against
+    the three-kernel path bit for bit, as above."""
+    g, cfg, sd, model = tiny
+    t = cfg.text
+    nseq, rows = 16, 735
+    tiles = ((nseq * rows + 255) // 256) * ((3 * t.dim + t.ff_dim + 255) // 256)
+    cu = torch.cuda.get_device_properties(0).multi_processor_count
+    print(f"[q | k | v | fc1] at {nseq} x {rows} rows: {tiles} tiles, {cu} CUs")
+    assert tiles == 276 and tiles > cu
+    gen = torch.Generator().manual_seed(13)
+    x = (torch.randn(nseq, rows, t.dim, generator=gen) * 0.7).to(BF16).cuda()
+    pos0 = [(5 * i) % 7 for i in range(nseq)]
+    hi = rows + max(pos0)
+    model._ensure_batch(2 + nseq)
+    model.enable_fp8([golden_image(g, i) for i in range(3)], kv_cache=True)
+    outs = []
+    try:
+        for fuse in (0, 1):
+            model.lib.md_gemm_set_tuning(b"rope_fuse", fuse)
+            with torch.inference_mode():
+                for buf in (model._kv_k, model._kv_v, model._kv_k8, model._kv_v8):
+                    buf[:, 2 : 2 + nseq].zero_()
+                h = model._text_forward(x, pos0, 2)
+                torch.cuda.synchronize()
+                outs.append((h.clone(),) + tuple(buf[:, 2 : 2 + nseq, :, :hi].clone() for buf in (model._kv_k, model._kv_v, model._kv_k8, model._kv_v8)))
+    finally:
+        model.lib.md_gemm_set_tuning(b"rope_fuse", 1)
+        model.enable_fp8(on=False)
+    assert float(outs[0][1].float().abs().sum()) > 0 and int((outs[0][3] != 0).sum()) > 0
+    for a, b, name in zip(outs[0], outs[1], ("hidden", "K slab", "V slab", "e4m3 K slab", "e4m3 V slab")):
+        assert torch.equal(a, b), name
+
+
+def test_rope_kv_write_in_gemm_epilogue_past_a_workgroups_first_tile(tiny):
+    """The four-wave bf16 kernel (tile 20) with its persistent grid cut to 8 workgroups: each of them walks eleven or twelve of
+    the 90 tiles of the five-sequence prefill through the fused RoPE / KV-write epilogue.  Fused against rope_kv_kernel bit for
+    bit, as test_rope_kv_write_in_gemm_epilogue_is_bit_identical does inside the first tile."""
+    g, cfg, sd, model = tiny
+    t = cfg.text
+    gen = torch.Generator().manual_seed(11)
+    x = (torch.randn(5, 735, t.dim, generator=gen) * 0.7).to(BF16).cuda()
+    model._ensure_batch(8)
+    outs = []
+    try:
+        model.lib.md_gemm_set_tuning(b"tile", 20)
+        model.lib.md_gemm_set_tuning(b"w4_grid", 8)
+        for fuse in (0, 1):
+            model.lib.md_gemm_set_tuning(b"rope_fuse", fuse)
+            with torch.inference_mode():
+                model._kv_k[:, 2:7].zero_()
+                model._kv_v[:, 2:7].zero_()
+                h = model._text_forward(x, [0, 3, 0, 1, 0], 2)
+                torch.cuda.synchronize()
+                outs.append((h.clone(), model._kv_k[:, 2:7, :, :740].clone(), model._kv_v[:, 2:7, :, :740].clone()))
+    finally:
+        model.lib.md_gemm_set_tuning(b"w4_grid", 0)
+        model.lib.md_gemm_set_tuning(b"tile", -1)
+        model.lib.md_gemm_set_tuning(b"rope_fuse", 1)
+    assert float(outs[0][1].float().abs().sum()) > 0
+    for a, b, name in zip(outs[0], outs[1], ("hidden", "K slab", "V slab")):
+        assert torch.equal(a, b), name
+
+
 def test_dedup_identical_crops_is_bit_identical(tiny):
     """An image that fits one crop has a local crop equal to its global crop; with dedup_identical_crops the encoder
     runs once per distinct crop.  The projected embeddings must be the same bits as with both crops encoded, in a batch

@@ -6,14 +6,21 @@ mutated region.
 
 The same for the per-element attention bound of util.compare_attention_elementwise, on the probe inputs of
 tests/test_attention_exact_gpu.py: a float32 model of the kernels (64-key tiles, online softmax, bf16 probabilities) is inside
-it, and the model with ONE key wrongly admitted or wrongly dropped is outside it in every row the probe aims at that key."""
+it, and the model with ONE key wrongly admitted or wrongly dropped is outside it in every row the probe aims at that key.
+
+And for the fp8 tile GEMM's references, util.gemm_f8_exact and util.compare_f8_elementwise: a float32 model of gemm_f8_kernel's
+arithmetic (64-wide K slices, the fp32 scale, the FMA with the bias, bf16 rounding, the GELU in its sigmoid form, the residual's
+second rounding, e4m3 rounding) is inside the intervals, and one dropped K element, one column that reads its neighbour's
+wscale and one bias taken from the next column are outside them, in the affected elements only."""
 import math
 
+import numpy as np
 import pytest
 import torch
 
 from test_attention_exact_gpu import DEC_CTX, PROBES, prefill_geometry, visibility
-from util import attention_excess, compare_attention_elementwise, compare_elementwise, elementwise_excess
+from util import (attention_excess, compare_attention_elementwise, compare_elementwise, compare_f8_elementwise, elementwise_excess,
+                  f8_excess, gemm_f8_exact, round_to_bf16)
 
 BF16 = torch.bfloat16
 SHAPES = [(128, 2048, 3584), (100, 8192, 2048), (65, 704, 256), (97, 1024, 1000)]
@@ -248,3 +255,175 @@ def test_uniform_probe_flags_one_dropped_key(n):
         print(f"n {n}, key {lost} lost: {bad.sum(-1).flatten().tolist()} of 64 features flagged per head")
         assert bool(bad.any(-1).all())
         assert int(bad.sum()) > bad.numel() // 2
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# md_gemm_f8: gemm_f8_exact / compare_f8_elementwise
+# ---------------------------------------------------------------------------------------------------------------------
+F8 = torch.float8_e4m3fn
+F8_SHAPES = [(64, 64, 192), (130, 588, 320), (40, 4304, 192)]
+
+
+def f8_operands(m, k, n, seed=0):
+    """e4m3 operands drawn as the kernel tests draw them: per-tensor activation scale, per-channel weight scales, K zero padded."""
+    g = torch.Generator(device="cpu").manual_seed(2000 + m + k + n + seed)
+    k_pad = (k + 63) // 64 * 64
+    x = torch.randn(m, k, generator=g).to(BF16).float()
+    w = (torch.randn(n, k, generator=g) / math.sqrt(k)).to(BF16).float()
+    bias = (torch.randn(n, generator=g) * 0.1).to(BF16)
+    a_scale = float(x.abs().max()) / 448.0
+    wscale = (w.abs().amax(dim=1) / 448.0).float()
+    a8 = torch.zeros(m, k_pad, dtype=torch.uint8)
+    w8 = torch.zeros(n, k_pad, dtype=torch.uint8)
+    a8[:, :k] = (x / a_scale).clamp(-448, 448).to(F8).view(torch.uint8)
+    w8[:, :k] = (w / wscale[:, None]).clamp(-448, 448).to(F8).view(torch.uint8)
+    return a8, a_scale, w8, wscale, bias
+
+
+def f8_model(a8, a_scale, w8, wscale, bias, *, drop=None, scale_from=None, bias_from=None):
+    """bf16(fma(acc, sc, bias)) in float32 the way gemm_f8_kernel does it, one 64-wide K slice after the other.  Mutations:
+    ``drop`` = (row, kk): that A element reads as zero; ``scale_from`` / ``bias_from`` = (col, src): column col takes
+    wscale / bias of column src."""
+    af, wf = a8.view(F8).float(), w8.view(F8).float()
+    if drop is not None:
+        af[drop[0], drop[1]] = 0.0
+    acc = torch.zeros(af.shape[0], wf.shape[0], dtype=torch.float32)
+    for c in range(af.shape[1] // CHUNK):
+        acc = acc + af[:, c * CHUNK : (c + 1) * CHUNK] @ wf[:, c * CHUNK : (c + 1) * CHUNK].t()
+    sc = wscale * torch.tensor(np.float32(a_scale))
+    b = bias.float().clone()
+    if scale_from is not None:
+        sc[scale_from[0]] = sc[scale_from[1]]
+    if bias_from is not None:
+        b[bias_from[0]] = b[bias_from[1]]
+    return (acc * sc + b).to(BF16)
+
+
+def gelu_model(pre):
+    """gelu_tanh_f32x2 in float32: constants folded in float32, x / (1 + 2^z)."""
+    ka = np.float32(-2.0) * np.float32(1.4426950408889634) * np.float32(0.7978845608028654)
+    kb = ka * np.float32(0.044715)
+    x = pre.float()
+    z = x * (float(kb) * (x * x) + float(ka))
+    return (x * (1.0 / (1.0 + torch.exp2(z)))).to(BF16)
+
+
+def quant_model(v, inv):
+    return (v.float() * torch.tensor(np.float32(inv))).clamp(-448.0, 448.0).to(F8).view(torch.uint8)
+
+
+def test_round_to_bf16_is_round_to_nearest_even():
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(20000, generator=g) * torch.exp2(torch.randint(-20, 20, (20000,), generator=g).float())
+    assert torch.equal(round_to_bf16(x.double()), x.to(BF16).double())
+    ties = torch.tensor([1.00390625, 1.01171875, -2.0078125, 255.5, 0.0], dtype=torch.float64)
+    assert round_to_bf16(ties).tolist() == [1.0, 1.015625, -2.0, 256.0, 0.0]
+
+
+@pytest.mark.parametrize("m,k,n", F8_SHAPES)
+def test_f8_bound_accepts_the_float32_kernel_model_in_every_epilogue(m, k, n):
+    a8, a_scale, w8, wscale, bias = f8_operands(m, k, n)
+    k_pad = a8.shape[1]
+    exact, mag = gemm_f8_exact(a8, a_scale, w8, wscale, bias)
+    assert exact.dtype == torch.float64 and bool((mag >= exact.abs()).all())
+    pre = f8_model(a8, a_scale, w8, wscale, bias)
+    compare_f8_elementwise(f"model bias {m}x{k}x{n}", pre, exact, mag, k_pad)
+    # residual: the second rounding
+    r = torch.randn(m, n, generator=torch.Generator().manual_seed(7)).to(BF16)
+    compare_f8_elementwise(f"model residual {m}x{k}x{n}", (r.float() + pre.float()).to(BF16), exact, mag, k_pad, residual=r)
+    # GELU from a 64-column boundary on, with an fp8 tail from the next one
+    gf, ff = 64, 128
+    out = pre.clone()
+    out[:, gf:] = gelu_model(pre[:, gf:])
+    inv = 448.0 / float(out[:, ff:].float().abs().max())
+    compare_f8_elementwise(f"model gelu + e4m3 {m}x{k}x{n}", out[:, :ff], exact, mag, k_pad, gelu_from=gf,
+                           got8=quant_model(out[:, ff:], inv), f8_from=ff, c8_inv_scale=inv)
+    # all-fp8 output, no bias
+    exact0, mag0 = gemm_f8_exact(a8, a_scale, w8, wscale, None)
+    pre0 = f8_model(a8, a_scale, w8, wscale, torch.zeros_like(bias))
+    inv0 = 448.0 / float(pre0.float().abs().max())
+    compare_f8_elementwise(f"model all-e4m3 {m}x{k}x{n}", None, exact0, mag0, k_pad, got8=quant_model(pre0, inv0), f8_from=0, c8_inv_scale=inv0)
+
+
+def f8_rejected(name, got, exact, mag, k_pad, region, least, **kw):
+    """compare_f8_elementwise must refuse ``got``, with every violation inside ``region`` and at least ``least`` of them."""
+    with pytest.raises(AssertionError, match="exceed the per-element bound"):
+        compare_f8_elementwise(name, got, exact, mag, k_pad, **kw)
+    bad = f8_excess(got, exact, mag, k_pad, **kw)[0] > 0
+    assert not bool((bad & ~region).any()), f"{name}: violations outside the mutated region"
+    print(f"{name}: {int(bad.sum())} of {int(region.sum())} mutated elements violate")
+    assert int(bad.sum()) >= least, f"{name}: {int(bad.sum())} < {least}"
+
+
+@pytest.mark.parametrize("m,k,n", F8_SHAPES)
+def test_f8_bound_rejects_a_dropped_k_element_a_neighbours_scale_and_a_shifted_bias(m, k, n):
+    """Each mutation changes one row or one column.  How many of its elements must leave the bound, at K <= 640: the
+    neighbour's wscale moves the column's products by the ratio of two channel maxima (the columns are chosen at least 3 %
+    apart, eight bf16 half-spacings) and the next column's bias moves it by at least 0.05 against values of order one, so at
+    least 90 % of the column in both; a dropped element -- the row's largest activation code -- moves an output by |a w|,
+    which is below the output's half-spacing where the weight code is small: at least a quarter of the row.  At K = 4352 the
+    accumulate term alone, 5.74 K u mag = 3e-3 mag with mag some 60 times a typical |value|, is a fifth of the value: there
+    each mutation must still be refused, by at least one element, and never outside its region."""
+    a8, a_scale, w8, wscale, bias = f8_operands(m, k, n)
+    k_pad = a8.shape[1]
+    exact, mag = gemm_f8_exact(a8, a_scale, w8, wscale, bias)
+    row = m - 1
+    kk = int(a8.view(F8).float()[row].abs().argmax())
+    region = torch.zeros(m, n, dtype=torch.bool)
+    region[row] = True
+    f8_rejected(f"dropped K element {m}x{k}x{n}", f8_model(a8, a_scale, w8, wscale, bias, drop=(row, kk)), exact, mag, k_pad, region,
+                n // 4 if k <= 640 else 1)
+    ratio = (wscale[1:] / wscale[:-1] - 1).abs()
+    col = int(ratio.argmax())
+    assert float(ratio[col]) >= 0.03
+    region = torch.zeros(m, n, dtype=torch.bool)
+    region[:, col] = True
+    f8_rejected(f"neighbour's wscale {m}x{k}x{n}", f8_model(a8, a_scale, w8, wscale, bias, scale_from=(col, col + 1)), exact, mag, k_pad,
+                region, int(0.9 * m) if k <= 640 else 1)
+    step = (bias.float()[1:] - bias.float()[:-1]).abs()
+    col = int(step.argmax())
+    assert float(step[col]) >= 0.05
+    region = torch.zeros(m, n, dtype=torch.bool)
+    region[:, col] = True
+    f8_rejected(f"bias of the next column {m}x{k}x{n}", f8_model(a8, a_scale, w8, wscale, bias, bias_from=(col, col + 1)), exact, mag,
+                k_pad, region, int(0.9 * m) if k <= 640 else 1)
+
+
+def test_f8_exact_probe_form_and_code_interval_have_no_tolerance():
+    """exact_acc: one bf16 step off is refused; the e4m3 interval refuses a code one step outside and a NaN code."""
+    a8, a_scale, w8, wscale, bias = f8_operands(64, 64, 128)
+    exact, mag = gemm_f8_exact(a8, a_scale, w8, wscale, bias)
+    pre = round_to_bf16(exact).to(BF16)
+    compare_f8_elementwise("rounded exact", pre, exact, mag, 64, exact_acc=True)
+    off = pre.clone()
+    off.view(torch.int16)[3, 5] += 1
+    with pytest.raises(AssertionError, match="1 of"):
+        compare_f8_elementwise("one bf16 step", off, exact, mag, 64, exact_acc=True)
+    codes = quant_model(pre, 8.0)
+    compare_f8_elementwise("codes", None, exact, mag, 64, exact_acc=True, got8=codes, f8_from=0, c8_inv_scale=8.0)
+    for value in (int(codes[2, 9]) ^ 1, 0x7F):
+        wrong = codes.clone()
+        wrong[2, 9] = value
+        with pytest.raises(AssertionError, match="1 of"):
+            compare_f8_elementwise("one code", None, exact, mag, 64, exact_acc=True, got8=wrong, f8_from=0, c8_inv_scale=8.0)
+
+
+def test_exact_probe_arithmetic_is_exact_in_fp32_for_every_shape_of_the_gpu_list():
+    """The headroom argument of tests/test_gemm_f8_exact_gpu.py, and on its smallest K the claim itself: the float32 model
+    equals the rounded float64 value bit for bit in any slice order."""
+    import test_gemm_f8_exact_gpu as T
+
+    for case in T.EXACT_CASES:
+        k_pad = T.pad64(case.k)
+        T.probe_headroom(k_pad, T.probe_a_scale(k_pad))
+    assert {T.pad64(c.k) for c in T.EXACT_CASES} >= {64, 128, 192, 256, 320, 640, 4352}
+    old, T.DEV = T.DEV, "cpu"
+    try:
+        for k in (64, 588, 4304):
+            a8, a_scale, w8, wscale, bias = T.probe_operands(70, 130, k, True)
+            exact, mag = gemm_f8_exact(a8, a_scale, w8, wscale, bias)
+            got = f8_model(a8, a_scale, w8, wscale, bias)
+            assert torch.equal(got, exact.to(BF16)) and torch.equal(got.double(), round_to_bf16(exact))
+            compare_f8_elementwise(f"probe model k={k}", got, exact, mag, T.pad64(k), exact_acc=True)
+    finally:
+        T.DEV = old

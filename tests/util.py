@@ -1,4 +1,6 @@
 """Shared helpers for the parity tests."""
+import math
+
 import numpy as np
 import torch
 
@@ -74,6 +76,228 @@ def compare_elementwise(name, got: torch.Tensor, a: torch.Tensor, w: torch.Tenso
     print(msg if n_bad else f"{name}: all {excess.numel()} elements within the per-element bound (closest ({row}, {col}): {float(-excess[row, col]):.3e} to spare)")
     assert n_bad == 0, msg
     return excess
+
+
+def _e4m3_values(t: torch.Tensor) -> torch.Tensor:
+    """e4m3fn codes (uint8, or a float8 tensor) as float64 values."""
+    if t.dtype == torch.uint8:
+        t = t.view(torch.float8_e4m3fn)
+    return t.float().double()
+
+
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """2^e as float64 for integer e in the normal range, assembled from its bits: a device's ldexp may go through pow and be
+    an ulp off, which would move a tie."""
+    return ((e.to(torch.int64) + 1023) << 52).view(torch.float64)
+
+
+def bf16_spacing(x: torch.Tensor) -> torch.Tensor:
+    """The spacing of bf16 at |x| (float64 in, float64 out, an exact power of two; the subnormal spacing below 2^-126)."""
+    _, e = torch.frexp(x)                                    # x = f * 2^e, f in [0.5, 1): the bf16 spacing at x is 2^(e - 8)
+    return _pow2(e.clamp_min(-125) - 8)
+
+
+def round_to_bf16(x: torch.Tensor) -> torch.Tensor:
+    """float64 -> the nearest bf16 value, ties to even, as float64 (no detour through float32: no double rounding)."""
+    s = bf16_spacing(x)
+    return torch.round(x / s) * s                            # x / s is exact; torch.round rounds halves to even
+
+
+def gemm_f8_exact(a8: torch.Tensor, a_scale: float, w8: torch.Tensor, wscale: torch.Tensor, bias, row_chunk: int = 8192):
+    """md_gemm_f8 before its epilogue, in float64 from the e4m3 codes with NO intermediate rounding:
+    ``exact = a_scale * wscale[n] * (A8 . W8^T) + bias`` and ``mag``, the same expression over absolute values.
+    a8 [m, K] and w8 [n, K] are e4m3fn codes (uint8 or float8; a8 may be a strided view), wscale [n] fp32, bias [n] bf16 or
+    None; a_scale is taken as the float the C ABI hands the kernel.  Evaluated on a8's device in chunks of rows."""
+    dev = a8.device
+    w64 = _e4m3_values(w8.to(dev))
+    s64 = wscale.detach().to(dev).double() * float(np.float32(a_scale))
+    b64 = torch.zeros(w64.shape[0], dtype=torch.float64, device=dev) if bias is None else bias.detach().to(dev).double()
+    assert a8.dim() == 2 and w64.dim() == 2 and a8.shape[1] == w64.shape[1] and s64.shape == b64.shape == (w64.shape[0],)
+    m, n = a8.shape[0], w64.shape[0]
+    exact = torch.empty(m, n, dtype=torch.float64, device=dev)
+    mag = torch.empty_like(exact)
+    wt, wt_abs = w64.t().contiguous(), w64.abs().t().contiguous()
+    for r0 in range(0, m, row_chunk):
+        a64 = _e4m3_values(a8[r0 : r0 + row_chunk])
+        exact[r0 : r0 + row_chunk] = (a64 @ wt) * s64 + b64
+        mag[r0 : r0 + row_chunk] = (a64.abs() @ wt_abs) * s64.abs() + b64.abs()
+    return exact, mag
+
+
+# The charge per K accumulate step of compare_f8_elementwise: twice the largest error MEASURED for the fp8 matrix instruction
+# (2.8696 * 2^-23 of mag per step; see the docstring and profiles/gemm_f8_exact_tests_gpu.txt), not the 2^-23 of an fp32 accumulator.
+F8_MFMA_MEASURED_U = 2.8696 * 2.0 ** -23
+F8_ACCUM_U = 2.0 * F8_MFMA_MEASURED_U
+_GELU_A = -2.0 * math.log2(math.e) * math.sqrt(2.0 / math.pi)
+_GELU_B = _GELU_A * 0.044715
+_GELU_DIP = (-0.80, -0.70)   # brackets the minimiser of the tanh-GELU (x = -0.7525...)
+
+
+def _gelu64(p: torch.Tensor):
+    """tanh-GELU in float64 in the algebraically equal form x / (1 + 2^z), z = x (A + B x^2), that does not cancel for x << 0,
+    and the error bound of gelu_tanh_f32x2 at p (see compare_f8_elementwise)."""
+    z = p * (_GELU_A + _GELU_B * p * p)
+    s = 1.0 / (1.0 + torch.exp2(z))
+    y = p * s
+    rel = ((1.0 - s) * (4.0 * math.log(2.0) * z.abs() + 1.0) + 2.0) * 2.0 ** -23
+    return y, rel * y.abs() + p.abs() * 2.0 ** -120
+
+
+def _gelu_floor() -> float:
+    xs = torch.linspace(_GELU_DIP[0], _GELU_DIP[1], 100001, dtype=torch.float64)
+    ys = _gelu64(xs)[0]
+    i = int(torch.argmin(ys))
+    assert 0 < i < xs.numel() - 1, "the bracket does not hold the minimiser"
+    return float(ys[i]) - 1e-12   # a grid of step 1e-6 misses the minimum by <= 0.5 * max|gelu''| * (0.5e-6)^2 < 1e-12
+
+
+_GELU_FLOOR = _gelu_floor()
+
+
+def f8_output_interval(exact, mag, k, *, exact_acc=False, accum_u=F8_ACCUM_U, residual=None, gelu_from=None):
+    """The closed interval [lo, hi] of bf16 values (as float64) md_gemm_f8 may store for every element; see
+    compare_f8_elementwise.  ``residual`` [m, n]: the rows the kernel adds (already gathered); ``gelu_from``: first GELU column."""
+    e32 = torch.zeros_like(mag) if exact_acc else (k * accum_u + 2 * 2.0 ** -23) * mag
+    lo, hi = round_to_bf16(exact - e32), round_to_bf16(exact + e32)
+    if residual is not None:
+        r32 = residual.detach().to(exact.device).float()
+        assert r32.shape == exact.shape
+        lo, hi = ((r32 + p.float()).to(torch.bfloat16).double() for p in (lo, hi))
+    if gelu_from is not None and gelu_from < exact.shape[1]:
+        p_lo, p_hi = lo[:, gelu_from:], hi[:, gelu_from:]
+        (y_lo, g_lo), (y_hi, g_hi) = _gelu64(p_lo), _gelu64(p_hi)
+        ymin, ymax = torch.minimum(y_lo - g_lo, y_hi - g_hi), torch.maximum(y_lo + g_lo, y_hi + g_hi)
+        dip = (p_lo < _GELU_DIP[1]) & (p_hi > _GELU_DIP[0])
+        ymin = torch.where(dip, torch.clamp_max(ymin, _GELU_FLOOR - torch.maximum(g_lo, g_hi)), ymin)
+        w = 2.0 ** -50                                       # this reference's own float64 evaluation (exp2, a division, products)
+        lo, hi = lo.clone(), hi.clone()
+        lo[:, gelu_from:] = round_to_bf16(ymin - w * ymin.abs())
+        hi[:, gelu_from:] = round_to_bf16(ymax + w * ymax.abs())
+    return lo, hi
+
+
+def f8_code_interval(lo, hi, c8_inv_scale: float):
+    """The e4m3 values (float64) of the two ends of a bf16 interval as the epilogue quantises them:
+    e4m3(clamp(fp32(v * c8_inv_scale), +-448)), round to nearest even -- monotone in v."""
+    s = torch.tensor(float(np.float32(c8_inv_scale)), dtype=torch.float32, device=lo.device)
+    q = lambda v: (v.float() * s).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float().double()
+    return q(lo), q(hi)
+
+
+def f8_excess(got, exact, mag, k, *, got8=None, f8_from=None, c8_inv_scale=1.0, **kw):
+    """Distance of every element from its allowed interval (float64, > 0 = violation, non-finite = +inf): one tensor for the
+    bf16 columns [0, f8_from) of ``got`` (None when there are none) and one for the e4m3 columns of ``got8`` (uint8 codes of
+    columns f8_from .. n - 1; None without an fp8 output).  ``kw``: the arguments of f8_output_interval."""
+    lo, hi = f8_output_interval(exact, mag, k, **kw)
+    n = exact.shape[1]
+    n_bf = n if got8 is None else int(f8_from)
+    out = [None, None]
+    if n_bf > 0:
+        assert got is not None and tuple(got.shape) == (exact.shape[0], n_bf), f"bf16 part {tuple(got.shape)} vs {(exact.shape[0], n_bf)}"
+        g = got.detach().double()
+        ex = torch.maximum(lo[:, :n_bf] - g, g - hi[:, :n_bf])
+        out[0] = torch.where(torch.isfinite(g), ex, torch.full_like(ex, float("inf")))
+    if got8 is not None:
+        assert tuple(got8.shape) == (exact.shape[0], n - n_bf), f"fp8 part {tuple(got8.shape)} vs {(exact.shape[0], n - n_bf)}"
+        q_lo, q_hi = f8_code_interval(lo[:, n_bf:], hi[:, n_bf:], c8_inv_scale)
+        g8 = _e4m3_values(got8.detach())
+        ex8 = torch.maximum(q_lo - g8, g8 - q_hi)
+        out[1] = torch.where(torch.isfinite(g8), ex8, torch.full_like(ex8, float("inf")))
+    return out
+
+
+def compare_f8_elementwise(name, got, exact, mag, k, *, got8=None, f8_from=None, c8_inv_scale=1.0, exact_acc=False,
+                           accum_u=F8_ACCUM_U, residual=None, gelu_from=None):
+    """Per-element bound for md_gemm_f8 (csrc/gemm_f8.hip), derived and not measured, with ``exact`` and ``mag`` of
+    gemm_f8_exact and K = ``k`` (k_pad).  EVERY stored element must lie in an interval that follows the kernel's own
+    operations; no element is excluded and there is no slack factor.  u = 2^-23.
+
+    Pre-activation.  The kernel stores pre = bf16(fma(acc, sc, bias)), sc = fp32(wscale[n] * a_scale).  Its fp32 value x
+    satisfies |x - exact| <= e32 = (K + 2) u mag in the fp32 model:
+      * K u mag: the K accumulate steps of acc, each charged u of the running magnitude (<= mag), which covers a truncating as
+        well as a round-to-nearest accumulator in any order.  The products need no term: e4m3 x e4m3 is 4 x 4 significand
+        bits, exact in fp32.
+        MEASURED, and this term alone widened: v_mfma_f32_32x32x64_f8f6f4 does not meet that model.  The exact probe of
+        tests/test_gemm_f8_exact_gpu.py (integer operands, every fp32 step exact) passes bit for bit at every shape, yet with
+        random operands K u mag was exceeded at K = 64 (13 of 96000 elements at 300 x 320 x 64, by up to one bf16 step),
+        and only at K = 64, where no other term can hide it.  The instruction was therefore measured on its own at the
+        smallest problem the kernel accepts -- one 256 x 256 tile, K = 64 (one instruction per output block), unit scales,
+        no bias, 48 random operand draws -- against the float64 value: the largest (|got - exact| - half a bf16 spacing) /
+        (K u mag) is 2.8696 (between 1.31 and 2.87 per draw; 2e-4 of the elements are above 1).  Sixty-four exact products summed
+        with an error near 2^-15.5 of their magnitudes says the instruction aligns the products of a K block to a common
+        exponent and drops the bits below a fixed width before it adds them.  The term is charged TWICE the measured value,
+        so that another operand draw does not trip it: ``accum_u`` = F8_ACCUM_U = 2 * 2.8696 u = 5.74 u per step, i.e.
+        e32 = (5.74 K + 2) u mag.  No figure comes from the kernel's output at a shape under test.
+        What that costs: the K term grows with K while half a bf16 spacing does not.  At K = 4352 it is 5.74 K u mag = 3e-3
+        mag, and mag is some 60 times a typical |value| of random operands: a fifth of the value.  With random operands the
+        per-element check is therefore sharp at short K (at K = 64 it sees one bf16 step) and WEAK at long K, where it still
+        finds a wrong scale or a lost slice only in the elements they move most (tests/test_util_cpu.py: "at least one
+        element" at K = 4352).  Long K is guarded by the exact probe (``exact_acc``), which has no such term: do not rely
+        on the random bound there.
+      * u mag: the rounding of wscale[n] * a_scale to fp32, 2^-24.
+      * u mag: the one rounding of the FMA with the bias, 2^-24 of a result of at most mag.
+        The two roundings are charged u rather than 2^-24 each: the spare u pays for their products with the K-step term
+        (K u * u apiece).  The count is K + 2, as compare_elementwise's is K + 1 for a GEMM without the scale.
+    Rounding to nearest is monotone, so pre lies in [bf16(exact - e32), bf16(exact + e32)].  That is the bound
+        |pre - exact| <= 0.5 ulp_bf16(max(|pre|, |exact|)) + (K accum_u + 2 u) mag
+    in its sharpest form (every value of the interval satisfies it; the closest element is printed in this form).
+    ``exact_acc``: e32 = 0 -- for operands whose products, partial sums and scaled FMA are exact in fp32 (small integers,
+    power-of-two scales): pre must equal bf16(exact) bit for bit.
+
+    Residual epilogue.  The kernel adds bf16(r) to the ROUNDED pre in fp32 and rounds once more: out = bf16(fp32(r + pre)),
+    monotone in pre, evaluated with those rounding points at both ends of the interval.
+
+    GELU epilogue (columns >= gelu_from), gelu_tanh_f32x2 on the rounded pre p (exact in fp32):
+        y = p / (1 + 2^z),  z = p (A + B p^2),  A = -2 log2(e) sqrt(2 / pi),  B = 0.044715 A      (= 0.5 p (1 + tanh(..)))
+      * z: the literals behind the fp32 constants are rounded (log2 e, sqrt(2 / pi), 0.044715: 3) and multiplied (-2 is a
+        power of two: 2 products) -> B is off by at most 5 * 2^-24; the three polynomial operations p p (exact for a bf16 p,
+        charged anyway: it pays for the second-order terms), the FMA and the product with p add 2^-24 each.  A and B p^2 have
+        one sign, so nothing cancels: |dz| <= 8 * 2^-24 |z| = 4 u |z|.
+      * v_exp_f32 is accurate to 1 ulp: 2^z (1 + e), |e| <= u, the same as an error of log2(1 + e) <= u / ln 2 in z.
+      * s(z) = 1 / (1 + 2^z) has ds / dz = -ln 2 s (1 - s): a relative error of s of ln 2 (1 - s) |dz|
+        <= (1 - s)(4 ln 2 |z| + 1) u.  It is bounded: (1 - s) |z| s has the maximum 0.224 / ln 2, so the ABSOLUTE error of
+        y = p s from z never exceeds 1.2 u |p| however large |z| grows; the bound charges the sharper relative form.
+      * 1 + 2^z (2^-24), v_rcp_f32 (1 ulp = u) and the product with p (2^-24): 2 u.
+        |y_kernel - y| <= G(p) = ((1 - s)(4 ln 2 |z| + 1) + 2) u |y| + 2^-120 |p|,
+      the last term for 2^z overflowing or flushing beyond 2^+-126, where y is below 2^-126 |p| or equals p.
+    p may be any bf16 value of its interval [p_lo, p_hi]; y -+ G is monotone wherever y is (G is 1e-6 of |y|), so the image
+    is spanned by the two ends, and by the global minimum of the tanh-GELU (-0.17 at x = -0.7525) where the interval reaches
+    the bracket [-0.80, -0.70] around it.  The image, widened by 2^-50 for this reference's own float64 arithmetic, is
+    rounded to bf16 at both ends: out lies in [bf16(ymin), bf16(ymax)].
+
+    fp8 output (``got8``: the e4m3 codes of columns f8_from .. n - 1).  code = e4m3(clamp(fp32(v * c8_inv_scale), +-448))
+    is monotone in the bf16 value v: every code must lie between the codes of the two ends of v's interval (compared as
+    values, so +0 and -0 agree).  There is no cap on a share of differing codes: none may differ beyond that.
+
+    Returns the excess tensors of f8_excess."""
+    kw = dict(exact_acc=exact_acc, accum_u=accum_u, residual=residual, gelu_from=gelu_from)
+    ex, ex8 = f8_excess(got, exact, mag, k, got8=got8, f8_from=f8_from, c8_inv_scale=c8_inv_scale, **kw)
+    total = n_bad = 0
+    notes = []
+    for part, e in (("bf16", ex), ("e4m3", ex8)):
+        if e is None:
+            continue
+        total += e.numel()
+        bad = int((e > 0).sum())
+        n_bad += bad
+        if bad:
+            row, col = divmod(int(torch.argmax(e)), e.shape[1])
+            notes.append(f"{bad} {part} elements outside, worst ({row}, {col}) by {float(e[row, col]):.3e}")
+        else:
+            notes.append(f"{part}: {float((e == 0).double().mean()):.3f} of {e.numel()} on an end of their interval")
+    if ex is not None and residual is None and not exact_acc:
+        # the plain columns in the |pre - exact| form, for the record: how much the closest element has to spare
+        n_plain = ex.shape[1] if gelu_from is None else min(ex.shape[1], gelu_from)
+        if n_plain > 0:
+            g, x, mg = got[:, :n_plain].detach().double(), exact[:, :n_plain], mag[:, :n_plain]
+            half = 0.5 * bf16_spacing(torch.maximum(g.abs(), x.abs()))
+            spare = half + (k * accum_u + 2 * 2.0 ** -23) * mg - (g - x).abs()
+            row, col = divmod(int(torch.argmin(spare)), n_plain)
+            notes.append(f"closest ({row}, {col}): {float(spare[row, col]):.3e} to spare")
+    msg = f"{name}: {n_bad} of {total} elements exceed the per-element bound; " + "; ".join(notes)
+    print(msg if n_bad else f"{name}: all {total} elements within the per-element bound; " + "; ".join(notes))
+    assert n_bad == 0, msg
+    return ex, ex8
 
 
 def attention_exact(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, allowed, scale: float):
