@@ -426,6 +426,20 @@ md_status md_sample_top_p(const void* logits, int64_t ld, int32_t batch, int32_t
                           float temperature, float top_p, const float* uniforms, int32_t* next,
                           void* probs_out, int64_t ld_probs, void* stream);
 
+/* md_sample_top_p with per-row settings: temperature, top_p and uniforms are device fp32 [batch].  One workgroup per
+ * row reads temperature[b] once and takes one of three paths:
+ *   temperature[b] > 0:  the row is sampled exactly as md_sample_top_p samples it with the scalars
+ *     (temperature[b], top_p[b]) and uniforms[b] -- the same next[b] and the same probs_out row, bit for bit (both
+ *     kernels run one device function);
+ *   temperature[b] == 0: greedy, next[b] = what md_argmax_bf16 gives the row (suppress_id as -inf, ties -> lowest id);
+ *     top_p[b] and uniforms[b] are not read, the probs_out row is not written;
+ *   temperature[b] < 0:  idle, next[b] and the probs_out row keep their contents and the row's logits are not read.
+ * The greedy path uses plain loads: unlike md_argmax_bf16 there is no vocab % 8 / ld % 8 requirement.  The values in the
+ * arrays are the caller's contract (finite, 0 < top_p <= 1); no host sync, no allocation: capturable. */
+md_status md_sample_rows(const void* logits, int64_t ld, int32_t batch, int32_t vocab, int32_t suppress_id,
+                         const float* temperature, const float* top_p, const float* uniforms,
+                         int32_t* next, void* probs_out, int64_t ld_probs, void* stream);
+
 /* Region head, device resident (reference: region.py:12-71 inside the loop of moondream.py:653-733).
  * md_fourier_features: out[r] = [cos(f) | sin(f)], f = bf16(bf16(2 pi x[r, :in_dim]) . w[in_dim][half])
  *   (region.py:12-29; in_dim 1 for coordinates, 2 for sizes) -- the input of coord_encoder /

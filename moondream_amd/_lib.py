@@ -209,6 +209,8 @@ SIGNATURES = {
     "md_argmax_bf16": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "md_sample_top_p": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p,
                                   c_void_p, c_int64, c_void_p]),
+    "md_sample_rows": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_int64, c_void_p]),
     "md_fourier_features": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     "md_region_pick_encode": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                         c_void_p, c_int64, c_void_p, c_int64, c_void_p]),

@@ -18,6 +18,7 @@ retirement.  ``ContinuousEngine`` drives it with the library.
 """
 from __future__ import annotations
 
+import math
 from collections import deque
 from dataclasses import dataclass, field
 from typing import Callable, Deque, Dict, Iterator, List, Optional, Sequence, Tuple, Union
@@ -65,6 +66,8 @@ class Request:
     done: bool = False
     generator: object = None
     variant: int = -1  # index in the model's LoRA bank (md_lora_bank); -1: the base model
+    temperature: float = 0.0  # 0: greedy (the request draws nothing from its generator)
+    top_p: float = DEFAULT_TOP_P
 
     @property
     def remaining(self) -> int:
@@ -238,9 +241,12 @@ class ContinuousEngine:
 
     ``max_live`` KV slots are allocated once, before the first admission, and never grown during a run.  With
     ``model.compile()`` decode chunks are replayed from hipGraphs keyed by the padded row count (at most MAX_GRAPHS per
-    model and stream); the token, position, slot-table and uniform buffers of a bucket keep their addresses and are
-    refreshed before each replay.  ``temperature`` > 0 samples with md_sample_top_p; each request draws its uniforms from its
-    own generator (``seed``), so its tokens do not depend on which other requests share its steps."""
+    model and stream); the token, position, slot-table, uniform and row-settings buffers of a bucket keep their addresses
+    and are refreshed before each replay.  ``temperature`` / ``top_p`` are the defaults of a request that names none
+    (``submit(..., temperature=, top_p=)``): every row of a decode step carries its own pair (md_sample_rows: temperature > 0
+    samples, 0 takes the argmax, padding rows are idle), so greedy and sampled requests of any settings share steps and
+    captured chunks.  Each sampled request draws its uniforms from its own generator (``seed``): its tokens depend neither
+    on which other requests share its steps nor on their settings."""
 
     def __init__(self, model, max_live: int = 64, chunk: int = 16, temperature: float = 0.0, top_p: float = DEFAULT_TOP_P,
                  admit_threshold: Optional[int] = None):
@@ -260,13 +266,20 @@ class ContinuousEngine:
 
     # ---- submission
     def submit(self, image, prompt_ids: Sequence[int], max_tokens: int = DEFAULT_MAX_TOKENS, eos_id: Optional[int] = None,
-               seed: Optional[int] = None, ignore_eos: bool = False, variant: Optional[str] = None) -> int:
+               seed: Optional[int] = None, ignore_eos: bool = False, variant: Optional[str] = None,
+               temperature: Optional[float] = None, top_p: Optional[float] = None) -> int:
         """Queue one request; ``image`` is a PIL image or an EncodedImage.  ``eos_id`` None: the tokenizer's EOS
-        (``ignore_eos``: none).  Returns its id."""
+        (``ignore_eos``: none).  ``temperature`` / ``top_p`` None: the engine's.  Returns its id."""
         from PIL import Image
 
         from .moondream import EncodedImage
 
+        temp = self.temperature if temperature is None else float(temperature)
+        tp = self.top_p if top_p is None else float(top_p)
+        if not (math.isfinite(temp) and temp >= 0):
+            raise ValueError(f"temperature must be finite and >= 0 (0: greedy), not {temp}")
+        if not (math.isfinite(tp) and 0 < tp <= 1):
+            raise ValueError(f"top_p must be in (0, 1], not {tp}")
         if not isinstance(image, (Image.Image, EncodedImage)):
             raise ValueError("image must be a PIL Image or EncodedImage")
         prompt = [int(p) for p in prompt_ids]
@@ -280,7 +293,7 @@ class ContinuousEngine:
         vidx = -1 if variant is None else self._variant_index(variant)
         rid = self._next_rid
         self._next_rid += 1
-        self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed, variant=vidx))
+        self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed, variant=vidx, temperature=temp, top_p=tp))
         return rid
 
     def _variant_index(self, variant: str) -> int:
@@ -355,8 +368,10 @@ class ContinuousEngine:
 
     def generate(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                  eos_id: Optional[int] = None, ignore_eos: bool = False, seeds: Optional[Sequence[Optional[int]]] = None,
-                 variant: Optional[str] = None) -> List[List[int]]:
-        """Ids for (images[i], prompts[i]) in input order; ``max_tokens`` one int or one per request."""
+                 variant: Optional[str] = None, temperature: Union[None, float, Sequence[float]] = None,
+                 top_p: Union[None, float, Sequence[float]] = None) -> List[List[int]]:
+        """Ids for (images[i], prompts[i]) in input order; ``max_tokens`` one int or one per request, ``temperature`` and
+        ``top_p`` one float or one per request (None: the engine's)."""
         n = len(images)
         if len(prompts) != n:
             raise ValueError("images and prompts differ in length")
@@ -364,7 +379,17 @@ class ContinuousEngine:
         if len(mt) != n:
             raise ValueError("one max_tokens per request")
         seeds = list(seeds) if seeds is not None else [None] * n
-        rids = [self.submit(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant) for i in range(n)]
+
+        def per_request(x, name):
+            if x is None or isinstance(x, (int, float, np.integer, np.floating)):
+                return [x] * n
+            x = list(x)
+            if len(x) != n:
+                raise ValueError(f"one {name} per request")
+            return x
+
+        temps, tps = per_request(temperature, "temperature"), per_request(top_p, "top_p")
+        rids = [self.submit(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant, temps[i], tps[i]) for i in range(n)]
         got = dict(self.run())
         return [got[r] for r in rids]
 
@@ -402,8 +427,8 @@ class ContinuousEngine:
 
     def _first_tokens(self, hidden, reqs: List[Request]):
         """hidden [k, 1, D], the last rows of a prefill -> the first token of each request from its last row, as _prepare_sequences picks it (argmax, or
-        md_sample_top_p with the request's first uniform; no suppression).  lm_head in launches of <= 64 rows: the
-        decode-regime kernels, whatever the admission size."""
+        top-p sampling with the request's own settings and first uniform: md_sample_rows over the group; no suppression).
+        lm_head in launches of <= 64 rows: the decode-regime kernels, whatever the admission size."""
         import torch
 
         m = self.model
@@ -411,8 +436,19 @@ class ContinuousEngine:
         for i0 in range(0, len(reqs), 64):
             part = reqs[i0 : i0 + 64]
             lg = m._lm_head(hidden[i0 : i0 + len(part)])
-            u = None if self.temperature == 0 else m._h2d(torch.cat([self._uniforms(r, 1) for r in part]))
-            out.append(m._pick(lg, self.temperature, self.top_p, uniforms=u))
+            if all(r.temperature == 0 for r in part):
+                out.append(m._pick(lg, 0.0, 0.0))
+                continue
+            # one H2D copy of [temperature | top_p | uniform] rows; a greedy request draws nothing
+            k = len(part)
+            st = torch.zeros(3, k, dtype=torch.float32)
+            st[0] = torch.tensor([r.temperature for r in part], dtype=torch.float32)
+            st[1] = torch.tensor([r.top_p for r in part], dtype=torch.float32)
+            for j, r in enumerate(part):
+                if r.temperature != 0:
+                    st[2, j] = self._uniforms(r, 1)[0]
+            st_d = m._h2d(st)
+            out.append(m._pick_rows(lg, st_d[0], st_d[1], -1, st_d[2]))
         return torch.cat(out)
 
     def _admit(self, reqs: List[Request]) -> List[Tuple[int, int]]:
@@ -474,8 +510,9 @@ class ContinuousEngine:
 
     def _buffers(self, bucket: int):
         """Fixed-address buffers of a (chunk, bucket): int32 device state [slots (chunk x bucket) | pos (bucket) | tokens ((chunk + 1) x
-        bucket) | row variants (bucket)] with its pinned host staging (one H2D copy of everything a chunk reads), and fp32 uniforms
-        [chunk x bucket].  The row-variant table sits next to the slot table; only chunks with a LoRA row read it."""
+        bucket) | row variants (bucket)] with its pinned host staging (one H2D copy of everything a chunk reads), and fp32
+        [uniforms (chunk x bucket) | temperature (bucket) | top_p (bucket)] with its own, one more copy that only chunks with a
+        sampling row make.  The row-variant table sits next to the slot table; only chunks with a LoRA row read it."""
         import torch
 
         bufs = self.model.__dict__.setdefault("_continuous_bufs", {})  # on the model: engines of one model share captured chunks
@@ -487,8 +524,8 @@ class ContinuousEngine:
             dev = torch.zeros(n_in + c * bucket + bucket, dtype=torch.int32, device=self.model.device)
             with torch.inference_mode(False):
                 host = torch.zeros(n_in + bucket, dtype=torch.int32, pin_memory=True)
-                u_host = torch.zeros(c * bucket, dtype=torch.float32, pin_memory=True)
-            u_dev = torch.zeros(c * bucket, dtype=torch.float32, device=self.model.device)
+                u_host = torch.zeros(c * bucket + 2 * bucket, dtype=torch.float32, pin_memory=True)
+            u_dev = torch.zeros(c * bucket + 2 * bucket, dtype=torch.float32, device=self.model.device)
             b = bufs[key] = (dev, host, u_dev, u_host, n_in)
         return b
 
@@ -515,15 +552,21 @@ class ContinuousEngine:
             hs[n_in:] = -1
             hs[n_in : n_in + len(row_var)] = row_var
             var_d.copy_(host[n_in:], non_blocking=True)
-        sample = self.temperature != 0
+        sample = any(r.temperature != 0 for r in plan.rows)
         if sample:
-            uh = u_host.numpy().reshape(c, B)
+            fh = u_host.numpy()
+            uh, th, ph = fh[: c * B].reshape(c, B), fh[c * B : c * B + B], fh[c * B + B :]
             uh[:] = 0.5
+            th[:] = -1.0  # rows past the plan's are idle: md_sample_rows leaves them alone
+            ph[:] = 1.0
             for r_idx, r in enumerate(plan.rows):
-                k = min(n, r.remaining)
-                uh[:k, r_idx] = self._uniforms(r, k).numpy()
+                th[r_idx], ph[r_idx] = r.temperature, r.top_p
+                if r.temperature != 0:  # a greedy request draws nothing from its generator
+                    k = min(n, r.remaining)
+                    uh[:k, r_idx] = self._uniforms(r, k).numpy()
             u_dev.copy_(u_host, non_blocking=True)
-        u2 = u_dev.view(c, B)
+        u2 = u_dev[: c * B].view(c, B)
+        temp_d, top_p_d = u_dev[c * B : c * B + B], u_dev[c * B + B :]
         logits = m._decode_logits(B)
         ws = m._workspace(self._decode_ws_bytes(B), 2)
         kv = m._kv_struct(0)
@@ -536,16 +579,18 @@ class ContinuousEngine:
         def body():
             for i in range(n):
                 m._decode_step(step_rows(i), hist[i], hist[i + 1], pos_d, B, answer_id, logits, ws, kv)
-                if sample:  # the step left its logits in ``logits``: draw from them instead of the argmax it wrote
-                    m._pick(step_logits, self.temperature, self.top_p, answer_id, uniforms=u2[i], out=hist[i + 1])
+                if sample:  # the step left its logits in ``logits``: every sampling row draws from them instead of the argmax it
+                    # wrote (a greedy row takes the same argmax again; an idle row keeps it)
+                    m._pick_rows(step_logits, temp_d, top_p_d, answer_id, u2[i], out=hist[i + 1])
 
         if not m.use_graphs:
             body()
         else:
             stream = torch.cuda.current_stream(m.device).cuda_stream
-            # (the bank's generation in the routing's key part: its ranks are launch shapes of the capture)
-            key = ("continuous", stream, B, n, dev.data_ptr(), ws.data_ptr(), m._kv_k.data_ptr(), logits.data_ptr(), self.temperature,
-                   self.top_p) + step_rows(0).key()
+            # (the bank's generation in the routing's key part: its ranks are launch shapes of the capture.  Of the sampling
+            # settings only "this chunk has a sampling launch": the values are device data, in the allocation of the uniforms)
+            key = ("continuous", stream, B, n, dev.data_ptr(), ws.data_ptr(), m._kv_k.data_ptr(), logits.data_ptr(), sample,
+                   u_dev.data_ptr()) + step_rows(0).key()
 
             def below_cap():
                 return sum(1 for k in m._graphs if isinstance(k, tuple) and k and k[0] == "continuous" and k[1] == stream) < MAX_GRAPHS

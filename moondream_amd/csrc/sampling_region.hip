@@ -115,18 +115,18 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   return t;
 }
 
-__global__ __launch_bounds__(SAMPLE_THREADS) void sample_top_p_kernel(const bf16_t* __restrict__ logits, int64_t ld, int vocab,
-                                                                      int suppress, float temperature, float top_p,
-                                                                      const float* __restrict__ uniforms,
-                                                                      int32_t* __restrict__ next,
-                                                                      bf16_t* __restrict__ probs_out, int64_t ldp) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+constexpr int SAMPLE_LDS = HIST_BINS * 4 + 16 * 4 + SAMPLE_THREADS * 4 + 16 * 4;  // histogram, wave partials, block scan, results
+
+// One row, one workgroup of SAMPLE_THREADS: lr the row's logits, u its uniform, next its token, pr its row of probs_out (or
+// nullptr).  The body of both sampling kernels; smem is the workgroup's SAMPLE_LDS bytes.
+__device__ __forceinline__ void sample_top_p_row(char* smem, const bf16_t* __restrict__ lr, int vocab, int suppress,
+                                                 float temperature, float top_p, const float* __restrict__ u,
+                                                 int32_t* __restrict__ next, bf16_t* __restrict__ pr) {
   unsigned* hist = (unsigned*)smem;                    // [HIST_BINS] counts per bf16 bit pattern
   float* red = (float*)(smem + HIST_BINS * 4);         // [16]
   float* scan = red + 16;                              // [SAMPLE_THREADS] block scans
   int* shared_i = (int*)(scan + SAMPLE_THREADS);       // [8] boundary pattern, survivors in it, drawn token, ...
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const bf16_t* lr = logits + (int64_t)b * ld;
+  const int tid = threadIdx.x;
   const float inv_t = temperature;  // division, not a reciprocal multiply: the reference divides
 
   // ---- z = bf16(logit / T), softmax statistics
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_top_p_kernel(const bf16
       bool keep = pat > bpat;
       if (pat == bpat) keep = (e++ < n_boundary);
       const bf16_t q = keep ? f2bf(bf2f((bf16_t)pat) / denom) : (bf16_t)0;
-      if (probs_out) probs_out[(int64_t)b * ldp + i] = q;
+      if (pr) pr[i] = q;
       cm += bf2f(q);
     }
   }
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_top_p_kernel(const bf16
     __syncthreads();
   }
   const float all = scan[SAMPLE_THREADS - 1];
-  const float target = uniforms[b] * all;
+  const float target = *u * all;
   const float lo = scan[tid] - cm;
   int last = -1;
   {
@@ -286,7 +286,79 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_top_p_kernel(const bf16
   }
   if (last >= 0) atomicMax(&shared_i[4], last);
   __syncthreads();
-  if (tid == 0) next[b] = shared_i[3] >= 0 ? shared_i[3] : (shared_i[4] > 0 ? shared_i[4] : 0);
+  if (tid == 0) *next = shared_i[3] >= 0 ? shared_i[3] : (shared_i[4] > 0 ? shared_i[4] : 0);
+}
+
+// greedy row: argmax with lr[suppress] as -inf, ties -> lowest id, an all-NaN row -> 0 (argmax_kernel's rule, elementwise.hip).
+// Plain 2-byte loads: no alignment demand on vocab or the row stride.
+__device__ __forceinline__ void argmax_row(char* smem, const bf16_t* __restrict__ lr, int vocab, int suppress,
+                                           int32_t* __restrict__ next) {
+  float* sv = (float*)smem;  // [16] wave partials
+  int* si = (int*)(sv + 16);
+  const int tid = threadIdx.x;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = tid; i < vocab; i += SAMPLE_THREADS) {  // ascending ids per thread: a later equal value never replaces
+    const float v = (i == suppress) ? -INFINITY : bf2f(lr[i]);
+    if (v > best || (v == best && i < bi)) {
+      best = v;
+      bi = i;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > best || (ov == best && oi < bi)) {
+      best = ov;
+      bi = oi;
+    }
+  }
+  if ((tid & 63) == 0) {
+    sv[tid >> 6] = best;
+    si[tid >> 6] = bi;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < SAMPLE_THREADS / 64; ++w)
+      if (sv[w] > best || (sv[w] == best && si[w] < bi)) {
+        best = sv[w];
+        bi = si[w];
+      }
+    *next = (bi >= vocab) ? 0 : bi;
+  }
+}
+
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_top_p_kernel(const bf16_t* __restrict__ logits, int64_t ld, int vocab,
+                                                                      int suppress, float temperature, float top_p,
+                                                                      const float* __restrict__ uniforms,
+                                                                      int32_t* __restrict__ next,
+                                                                      bf16_t* __restrict__ probs_out, int64_t ldp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int b = blockIdx.x;
+  sample_top_p_row(smem, logits + (int64_t)b * ld, vocab, suppress, temperature, top_p, uniforms + b, next + b,
+                   probs_out ? probs_out + (int64_t)b * ldp : nullptr);
+}
+
+// per-row settings: temperature[b] > 0 samples the row with (temperature[b], top_p[b], uniforms[b]), == 0 takes its argmax,
+// < 0 leaves the row alone.  One load decides for the whole workgroup, before any barrier.
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const bf16_t* __restrict__ logits, int64_t ld, int vocab,
+                                                                     int suppress, const float* __restrict__ temperature,
+                                                                     const float* __restrict__ top_p,
+                                                                     const float* __restrict__ uniforms,
+                                                                     int32_t* __restrict__ next,
+                                                                     bf16_t* __restrict__ probs_out, int64_t ldp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int b = blockIdx.x;
+  const float t = temperature[b];
+  if (t < 0.f) return;  // idle: next[b], the probs_out row and the row's logits stay untouched
+  const bf16_t* lr = logits + (int64_t)b * ld;
+  if (t == 0.f) {
+    argmax_row(smem, lr, vocab, suppress, next + b);
+    return;
+  }
+  sample_top_p_row(smem, lr, vocab, suppress, t, top_p[b], uniforms + b, next + b,
+                   probs_out ? probs_out + (int64_t)b * ldp : nullptr);
 }
 
 }  // namespace
@@ -314,9 +386,19 @@ extern "C" md_status md_sample_top_p(const void* logits, int64_t ld, int32_t bat
                                      void* probs_out, int64_t ld_probs, void* stream) {
   MD_CHECK_ARG(logits && uniforms && next && batch > 0 && vocab > 0 && ld >= vocab && temperature > 0.f);
   MD_CHECK_ARG(probs_out == nullptr || ld_probs >= vocab);
-  constexpr int lds = HIST_BINS * 4 + 16 * 4 + SAMPLE_THREADS * 4 + 16 * 4;
-  MD_TRY(md_ensure_dynamic_lds((const void*)sample_top_p_kernel, lds));
-  hipLaunchKernelGGL(sample_top_p_kernel, dim3(batch), dim3(SAMPLE_THREADS), lds, (hipStream_t)stream, (const bf16_t*)logits, ld,
-                     vocab, suppress_id, temperature, top_p, uniforms, next, (bf16_t*)probs_out, ld_probs);
+  MD_TRY(md_ensure_dynamic_lds((const void*)sample_top_p_kernel, SAMPLE_LDS));
+  hipLaunchKernelGGL(sample_top_p_kernel, dim3(batch), dim3(SAMPLE_THREADS), SAMPLE_LDS, (hipStream_t)stream, (const bf16_t*)logits,
+                     ld, vocab, suppress_id, temperature, top_p, uniforms, next, (bf16_t*)probs_out, ld_probs);
+  return md_launch_status();
+}
+
+extern "C" md_status md_sample_rows(const void* logits, int64_t ld, int32_t batch, int32_t vocab, int32_t suppress_id,
+                                    const float* temperature, const float* top_p, const float* uniforms, int32_t* next,
+                                    void* probs_out, int64_t ld_probs, void* stream) {
+  MD_CHECK_ARG(logits && temperature && top_p && uniforms && next && batch > 0 && vocab > 0 && ld >= vocab);
+  MD_CHECK_ARG(probs_out == nullptr || ld_probs >= vocab);
+  MD_TRY(md_ensure_dynamic_lds((const void*)sample_rows_kernel, SAMPLE_LDS));
+  hipLaunchKernelGGL(sample_rows_kernel, dim3(batch), dim3(SAMPLE_THREADS), SAMPLE_LDS, (hipStream_t)stream, (const bf16_t*)logits,
+                     ld, vocab, suppress_id, temperature, top_p, uniforms, next, (bf16_t*)probs_out, ld_probs);
   return md_launch_status();
 }

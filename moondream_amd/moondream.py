@@ -1078,6 +1078,23 @@ class MoondreamModel:
         )
         return nxt
 
+    def _pick_rows(self, logits: torch.Tensor, temperature_dev: torch.Tensor, top_p_dev: torch.Tensor, suppress_id: int,
+                   uniforms: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``_pick`` with every row's own settings (md_sample_rows): ``temperature_dev``, ``top_p_dev`` and ``uniforms`` are
+        device fp32 [B].  A row of temperature > 0 is drawn as ``_pick`` draws it with those scalars and that uniform, a row
+        of temperature 0 takes its argmax, a row of temperature < 0 keeps what ``out`` holds.  With ``out`` (device int32 [B])
+        nothing is allocated (captured decode steps)."""
+        b, v = logits.shape
+        for t in (temperature_dev, top_p_dev, uniforms):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == b and t.device == logits.device
+        nxt = out if out is not None else torch.empty(b, dtype=torch.int32, device=self._device)
+        _lib.check(
+            self.lib.md_sample_rows(logits.data_ptr(), logits.stride(0), b, v, suppress_id, temperature_dev.data_ptr(),
+                                    top_p_dev.data_ptr(), uniforms.data_ptr(), nxt.data_ptr(), None, 0, self._stream()),
+            "md_sample_rows",
+        )
+        return nxt
+
     # ---------------------------------------------------------- batched engine
     def _prefill_prompts(self, prompts: Sequence[Sequence[int]], pos: int, rows: Union[int, _Rows] = 0, prompt_embs=None,
                          last_only: bool = False):
@@ -1552,14 +1569,16 @@ class MoondreamModel:
 
     def batch_generate_ids_continuous(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                                       eos_id: Optional[int] = None, ignore_eos: bool = False, max_live: int = 64, chunk: int = 16,
-                                      temperature: float = 0.0, top_p: float = DEFAULT_TOP_P, seeds=None,
+                                      temperature: Union[float, Sequence[float]] = 0.0,
+                                      top_p: Union[float, Sequence[float]] = DEFAULT_TOP_P, seeds=None,
                                       variant: Optional[str] = None) -> List[List[int]]:
         """``batch_generate_ids`` with continuous batching (moondream_amd/continuous.py): per-request ``max_tokens`` and EOS
-        exit, freed KV slots refilled from the queue mid-decode; same greedy ids as the lockstep path."""
+        exit, freed KV slots refilled from the queue mid-decode; same greedy ids as the lockstep path.  ``temperature`` and
+        ``top_p``: one float, or one per request (greedy and sampled requests share the decode steps)."""
         from .continuous import ContinuousEngine
 
-        return ContinuousEngine(self, max_live, chunk, temperature, top_p).generate(images, prompts, max_tokens, eos_id, ignore_eos,
-                                                                                   seeds, variant)
+        return ContinuousEngine(self, max_live, chunk).generate(images, prompts, max_tokens, eos_id, ignore_eos, seeds, variant,
+                                                                 temperature, top_p)
 
     def teacher_forced_logits(self, images, prompts: Sequence[Sequence[int]], forced_ids, gather_idx) -> torch.Tensor:
         """Parity instrument (tests / bench.py): the logits of every greedy decision when each sequence is FORCED to follow

@@ -13,7 +13,13 @@ images/s = median of ``--repeats`` timed runs after one warm-up run; decode-phas
 (A: the lockstep loop's own phase marks; B / C: the decode chunks, each bracketed by a device sync); row-steps: padded =
 rows launched x steps, live = rows doing useful work (a request of n tokens needs n - 1 decode steps after its prefill).
 
-    python tools/bench_continuous.py [--n 256] [--repeats 5] [--model 2b]
+Sampling: ``--temperature T --top-p P`` builds the engines with those engine-wide settings; ``--mixed-sampling`` gives a
+quarter of the requests each of four settings per request, (0, -) greedy, (0.5, 0.3), (1.0, 0.8) and (4.0, 0.999), in one
+engine.  Request i is seeded with i.  Sampled ids are not the lockstep leg's, so with either switch choose the engine legs
+(``--legs B_continuous64``); ``ids_equal_A`` then compares with the first leg run.
+
+    python tools/bench_continuous.py [--n 256] [--repeats 5] [--model 2b] [--legs A_lockstep64,B_continuous64]
+                                     [--workloads ragged] [--temperature 0.5 --top-p 0.3 | --mixed-sampling]
 """
 import argparse
 import json
@@ -37,6 +43,11 @@ def main():
     ap.add_argument("--len-seed", type=int, default=0)
     ap.add_argument("--group", type=int, default=64, help="lockstep group size of (A)")
     ap.add_argument("--chunk", type=int, default=16)
+    ap.add_argument("--legs", default="A_lockstep64,B_continuous64,C_continuous128")
+    ap.add_argument("--workloads", default="ragged,uniform32")
+    ap.add_argument("--temperature", type=float, default=0.0, help="engine-wide sampling temperature of the engine legs")
+    ap.add_argument("--top-p", type=float, default=0.3)
+    ap.add_argument("--mixed-sampling", action="store_true", help="four per-request settings, one of them greedy")
     args = ap.parse_args()
 
     import torch
@@ -76,7 +87,7 @@ def main():
         return out, {"decode_ms": decode_ms, "padded_row_steps": padded, "live_row_steps": sum(n - 1 for n in mt)}
 
     def run_engine(max_live, mt, instrument=False):
-        eng = ContinuousEngine(model, max_live=max_live, chunk=args.chunk)
+        eng = ContinuousEngine(model, max_live=max_live, chunk=args.chunk, temperature=args.temperature, top_p=args.top_p)
         decode_ms = [0.0]
         if instrument:
             step = eng._step
@@ -89,17 +100,25 @@ def main():
                 return r
 
             eng._step = timed
-        out = eng.generate(images, prompts, max_tokens=mt, ignore_eos=True)
+        out = eng.generate(images, prompts, max_tokens=mt, ignore_eos=True, seeds=list(range(args.n)), **per_request)
         torch.cuda.synchronize()
         s = eng.stats
         return out, {"decode_ms": decode_ms[0], "padded_row_steps": s.padded_row_steps, "live_row_steps": s.live_row_steps,
                      "decode_steps": s.decode_steps, "admissions": s.admissions, "prefill_passes": s.prefill_passes,
                      "graph_captures": s.graph_captures}
 
+    per_request = {}
+    if args.mixed_sampling:
+        four = [(0.0, 0.3), (0.5, 0.3), (1.0, 0.8), (4.0, 0.999)]
+        per_request = {"temperature": [four[i % 4][0] for i in range(args.n)], "top_p": [four[i % 4][1] for i in range(args.n)]}
     legs = {"A_lockstep64": run_lockstep, "B_continuous64": lambda mt, instrument=False: run_engine(64, mt, instrument),
             "C_continuous128": lambda mt, instrument=False: run_engine(128, mt, instrument)}
+    legs = {k: legs[k] for k in args.legs.split(",")}
+    workloads = {k: workloads[k] for k in args.workloads.split(",")}
+    sampling = "mixed per request" if args.mixed_sampling else (
+        "greedy" if args.temperature == 0 else "engine-wide T=%g top_p=%g" % (args.temperature, args.top_p))
     result = {"metric": "continuous_batching_images_per_s", "model": args.model, "n": args.n, "repeats": args.repeats,
-              "chunk": args.chunk, "lengths": "uniform 4..64 (seed %d)" % args.len_seed}
+              "chunk": args.chunk, "lengths": "uniform 4..64 (seed %d)" % args.len_seed, "sampling": sampling}
     with torch.inference_mode():
         for wname, mt in workloads.items():
             res, ref_ids = {}, None
@@ -118,9 +137,11 @@ def main():
                 res[lname] = {"images_per_s": round(args.n / med, 2), "run_s_median": round(med, 4),
                               "run_s_all": [round(t, 4) for t in times], "ids_equal_A": ids == ref_ids,
                               **{k: (round(v, 2) if isinstance(v, float) else v) for k, v in info.items()}}
-            a = res["A_lockstep64"]["images_per_s"]
-            for lname in ("B_continuous64", "C_continuous128"):
-                res[lname]["speedup_vs_A"] = round(res[lname]["images_per_s"] / a, 4)
+            if "A_lockstep64" in res:
+                a = res["A_lockstep64"]["images_per_s"]
+                for lname in res:
+                    if lname != "A_lockstep64":
+                        res[lname]["speedup_vs_A"] = round(res[lname]["images_per_s"] / a, 4)
             result[wname] = res
     print(json.dumps(result))
 
