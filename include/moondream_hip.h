@@ -440,6 +440,25 @@ md_status md_sample_rows(const void* logits, int64_t ld, int32_t batch, int32_t 
                          const float* temperature, const float* top_p, const float* uniforms,
                          int32_t* next, void* probs_out, int64_t ld_probs, void* stream);
 
+/* Log-probability and rank of ONE GIVEN token per row: targets[r] in row r of logits (bf16 [rows][ld]).  One workgroup per row.
+ *   Live tokens: v is live unless v == suppress_id, suppress_id >= 0 and row r is suppressed; row r is suppressed when
+ *     suppress_rows == NULL or suppress_rows[r] != 0 (int32 [rows]).  The rule of md_argmax_bf16 / md_sample_* (moondream.py:517),
+ *     per row here because a scoring launch mixes a sequence's first decision (not suppressed) with its later ones.
+ *   t = targets[r];  m = max over live v of float(logit[v]);  s = sum over live v of exp(float(logit[v]) - m) in fp32
+ *     (a -inf logit adds 0);  logprob[r] = (float(logit[t]) - m) - log(s).
+ *   This is the model's OWN distribution at temperature 1, untruncated, with the suppression generation applies -- NOT the
+ *     tempered / top-p-renormalised distribution a sampled token was drawn from.
+ *   rank (optional, NULL to skip): rank[r] = #{live v: logit[v] > logit[t]} + #{live v < t: logit[v] == logit[t]} -- exact, and
+ *     0 exactly when t is what md_argmax_bf16 returns for the row (ties go to the lowest id).
+ *   t outside [0, vocab) (idle / padding rows): logprob[r] = NaN, rank[r] = -1, the logits row is not read.
+ *   t the suppressed token of a suppressed row: logprob[r] = -inf, rank[r] = -1.
+ * Two passes (max, then sum) in a summation order that depends on vocab alone (csrc/sampling_region.hip).  Plain loads: no
+ * vocab % 8 / ld % 8 requirement.  No host sync, no allocation: capturable.  rows == 0: MD_OK, nothing launched.
+ * MD_ERR_INVALID_ARG: NULL logits / targets / logprob, rows < 0, vocab <= 0, ld < vocab. */
+md_status md_token_logprobs(const void* logits, int64_t ld, int32_t rows, int32_t vocab, int32_t suppress_id,
+                            const int32_t* suppress_rows, const int32_t* targets, float* logprob, int32_t* rank,
+                            void* stream);
+
 /* Region head, device resident (reference: region.py:12-71 inside the loop of moondream.py:653-733).
  * md_fourier_features: out[r] = [cos(f) | sin(f)], f = bf16(bf16(2 pi x[r, :in_dim]) . w[in_dim][half])
  *   (region.py:12-29; in_dim 1 for coordinates, 2 for sizes) -- the input of coord_encoder /

@@ -68,6 +68,8 @@ class Request:
     variant: int = -1  # index in the model's LoRA bank (md_lora_bank); -1: the base model
     temperature: float = 0.0  # 0: greedy (the request draws nothing from its generator)
     top_p: float = DEFAULT_TOP_P
+    logprobs: List[float] = field(default_factory=list)  # of ``ids``, entry for entry (an engine with logprobs=True)
+    ranks: List[int] = field(default_factory=list)
 
     @property
     def remaining(self) -> int:
@@ -141,9 +143,10 @@ class SlotScheduler:
         self.stats.admissions += 1
         return out
 
-    def start(self, req: Request, first: int, pos: int) -> bool:
-        """The prefill of ``req`` picked ``first`` with the next token at position ``pos``.  Returns True if the request is
-        already finished (it then no longer holds its slot)."""
+    def start(self, req: Request, first: int, pos: int, logprob: Optional[float] = None, rank: Optional[int] = None) -> bool:
+        """The prefill of ``req`` picked ``first`` with the next token at position ``pos`` (``logprob`` / ``rank``: its values,
+        kept beside it).  Returns True if the request is already finished (it then no longer holds its slot)."""
+        req.logprobs, req.ranks = [], []
         req.pos = int(pos)
         req.steps = 0
         req.step_limit = max(0, min(req.max_tokens - 1, self.max_context - 1 - req.pos))
@@ -152,6 +155,8 @@ class SlotScheduler:
             req.ids = []
             return self._retire(req)
         req.ids = [int(first)]
+        if logprob is not None:
+            req.logprobs, req.ranks = [float(logprob)], [int(rank)]
         if req.step_limit == 0:
             return self._retire(req)
         self.live.append(req)
@@ -188,8 +193,10 @@ class SlotScheduler:
             pos[i] = r.pos
         return ChunkPlan(rows, bucket, n, slots, tokens, pos)
 
-    def commit(self, plan: ChunkPlan, out: np.ndarray) -> List[Request]:
-        """``out[i][r]``: the token row r produced in step i.  Advances every row, retires the finished ones (their slots
+    def commit(self, plan: ChunkPlan, out: np.ndarray, logprobs: Optional[np.ndarray] = None,
+               ranks: Optional[np.ndarray] = None) -> List[Request]:
+        """``out[i][r]``: the token row r produced in step i (``logprobs[i][r]`` / ``ranks[i][r]``: its values, appended in step
+        with the ids; idle and padding rows are never read).  Advances every row, retires the finished ones (their slots
         return to the pool) and returns them in row order."""
         self.stats.decode_steps += plan.n
         self.stats.padded_row_steps += plan.n * plan.bucket
@@ -206,6 +213,9 @@ class SlotScheduler:
                     fin = True
                     break
                 r.ids.append(tok)
+                if logprobs is not None:
+                    r.logprobs.append(float(logprobs[i][r_idx]))
+                    r.ranks.append(int(ranks[i][r_idx]))
                 if r.steps >= r.step_limit:
                     fin = True
                     break
@@ -217,17 +227,19 @@ class SlotScheduler:
     def run(self, admit: Callable[[List[Request]], Sequence[Tuple[int, int]]],
             step: Callable[[ChunkPlan], np.ndarray]) -> Iterator[Request]:
         """Drive the schedule: ``admit(requests)`` prefills them and returns (first token, next position) per request,
-        ``step(plan)`` runs a chunk and returns its tokens [n, bucket].  Yields requests in completion order."""
+        ``step(plan)`` runs a chunk and returns its tokens [n, bucket].  With log-probabilities: (first token, next position,
+        logprob, rank) and (tokens, logprobs, ranks).  Yields requests in completion order."""
         while self.pending():
             adm = self.take_admissions()
             if adm:
-                for r, (first, pos) in zip(adm, admit(adm)):
-                    if self.start(r, first, pos):
+                for r, started in zip(adm, admit(adm)):
+                    if self.start(r, *started):
                         yield r
             plan = self.plan()
             if plan is None:
                 continue
-            yield from self.commit(plan, step(plan))
+            res = step(plan)
+            yield from (self.commit(plan, *res) if isinstance(res, tuple) else self.commit(plan, res))
 
 
 class ContinuousEngine:
@@ -246,11 +258,19 @@ class ContinuousEngine:
     (``submit(..., temperature=, top_p=)``): every row of a decode step carries its own pair (md_sample_rows: temperature > 0
     samples, 0 takes the argmax, padding rows are idle), so greedy and sampled requests of any settings share steps and
     captured chunks.  Each sampled request draws its uniforms from its own generator (``seed``): its tokens depend neither
-    on which other requests share its steps nor on their settings."""
+    on which other requests share its steps nor on their settings.
+
+    ``logprobs`` (engine-wide, part of the chunk graph key): every step of a chunk also reduces each row's logits to the
+    log-probability and rank of the token the row picked (md_token_logprobs with targets = the step's tokens, inside the
+    captured chunk), and every ``Request`` carries ``logprobs`` / ``ranks`` beside its ids: ``run(with_logprobs=True)``.  They
+    are the values of ``MoondreamModel.batch_generate_ids(..., return_logprobs=True)`` -- the model's own distribution at
+    temperature 1, untruncated, whatever the request's sampling settings -- bit for bit.  Off: the launches and graphs of
+    an engine without the flag."""
 
     def __init__(self, model, max_live: int = 64, chunk: int = 16, temperature: float = 0.0, top_p: float = DEFAULT_TOP_P,
-                 admit_threshold: Optional[int] = None):
+                 admit_threshold: Optional[int] = None, logprobs: bool = False):
         self.model = model
+        self.logprobs = bool(logprobs)
         self.max_live = int(max_live)
         self.chunk = int(chunk)
         self.temperature = float(temperature)
@@ -325,16 +345,19 @@ class ContinuousEngine:
         return self.submit(image, prompt, **kw)
 
     # ---- running
-    def run(self) -> Iterator[Tuple[int, List[int]]]:
-        """Generate every queued request; yields (rid, ids) in completion order.  Requests submitted while this runs are
-        admitted too.  ``stats`` counts this run."""
+    def run(self, with_logprobs: bool = False) -> Iterator[tuple]:
+        """Generate every queued request; yields (rid, ids) in completion order -- with ``with_logprobs`` (an engine made with
+        ``logprobs=True``) (rid, ids, logprobs, ranks).  Requests submitted while this runs are admitted too.  ``stats``
+        counts this run."""
         import torch
 
+        if with_logprobs and not self.logprobs:
+            raise ValueError("run(with_logprobs=True) needs ContinuousEngine(..., logprobs=True)")
         self.sched.stats = EngineStats()
         with torch.inference_mode():
             self._prepare_run()
             for r in self.sched.run(self._admit, self._step):
-                yield r.rid, list(r.ids)
+                yield (r.rid, list(r.ids), list(r.logprobs), list(r.ranks)) if with_logprobs else (r.rid, list(r.ids))
 
     def _prepare_run(self) -> None:
         """Size the KV slab (once, before the first admission: never grown during a run) and the decode buffers of the
@@ -369,9 +392,12 @@ class ContinuousEngine:
     def generate(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                  eos_id: Optional[int] = None, ignore_eos: bool = False, seeds: Optional[Sequence[Optional[int]]] = None,
                  variant: Optional[str] = None, temperature: Union[None, float, Sequence[float]] = None,
-                 top_p: Union[None, float, Sequence[float]] = None) -> List[List[int]]:
+                 top_p: Union[None, float, Sequence[float]] = None, return_logprobs: bool = False):
         """Ids for (images[i], prompts[i]) in input order; ``max_tokens`` one int or one per request, ``temperature`` and
-        ``top_p`` one float or one per request (None: the engine's)."""
+        ``top_p`` one float or one per request (None: the engine's).  ``return_logprobs`` (an engine made with
+        ``logprobs=True``): (ids, logprobs, ranks), each in input order."""
+        if return_logprobs and not self.logprobs:
+            raise ValueError("generate(return_logprobs=True) needs ContinuousEngine(..., logprobs=True)")
         n = len(images)
         if len(prompts) != n:
             raise ValueError("images and prompts differ in length")
@@ -390,6 +416,9 @@ class ContinuousEngine:
 
         temps, tps = per_request(temperature, "temperature"), per_request(top_p, "top_p")
         rids = [self.submit(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant, temps[i], tps[i]) for i in range(n)]
+        if return_logprobs:
+            got3 = {rid: rest for rid, *rest in self.run(with_logprobs=True)}
+            return tuple([got3[r][k] for r in rids] for k in range(3))
         got = dict(self.run())
         return [got[r] for r in rids]
 
@@ -428,16 +457,27 @@ class ContinuousEngine:
     def _first_tokens(self, hidden, reqs: List[Request]):
         """hidden [k, 1, D], the last rows of a prefill -> the first token of each request from its last row, as _prepare_sequences picks it (argmax, or
         top-p sampling with the request's own settings and first uniform: md_sample_rows over the group; no suppression).
-        lm_head in launches of <= 64 rows: the decode-regime kernels, whatever the admission size."""
+        lm_head in launches of <= 64 rows: the decode-regime kernels, whatever the admission size.  Returns one tuple per
+        request: (token,), or with ``logprobs`` (token, logprob, rank) of the same logits, unsuppressed like the pick."""
         import torch
 
         m = self.model
-        out = []
+        out, lps, rks = [], [], []
+
+        def score(lg, picked):
+            if self.logprobs:
+                lp = torch.empty(lg.shape[0], dtype=torch.float32, device=m.device)
+                rk = torch.empty(lg.shape[0], dtype=torch.int32, device=m.device)
+                m._token_logprobs(lg, picked, -1, lp, rk)
+                lps.append(lp)
+                rks.append(rk)
+            out.append(picked)
+
         for i0 in range(0, len(reqs), 64):
             part = reqs[i0 : i0 + 64]
             lg = m._lm_head(hidden[i0 : i0 + len(part)])
             if all(r.temperature == 0 for r in part):
-                out.append(m._pick(lg, 0.0, 0.0))
+                score(lg, m._pick(lg, 0.0, 0.0))
                 continue
             # one H2D copy of [temperature | top_p | uniform] rows; a greedy request draws nothing
             k = len(part)
@@ -448,8 +488,11 @@ class ContinuousEngine:
                 if r.temperature != 0:
                     st[2, j] = self._uniforms(r, 1)[0]
             st_d = m._h2d(st)
-            out.append(m._pick_rows(lg, st_d[0], st_d[1], -1, st_d[2]))
-        return torch.cat(out)
+            score(lg, m._pick_rows(lg, st_d[0], st_d[1], -1, st_d[2]))
+        first = torch.cat(out).tolist()
+        if not self.logprobs:
+            return [(f,) for f in first]
+        return list(zip(first, torch.cat(lps).tolist(), torch.cat(rks).tolist()))
 
     def _admit(self, reqs: List[Request]) -> List[Tuple[int, int]]:
         """ViT over the admitted raw images as one batch, then the prefill into their slots with the choices of
@@ -465,7 +508,7 @@ class ContinuousEngine:
         raw = [i for i, r in enumerate(reqs) if isinstance(r.image, Image.Image)]
         img_emb = m._run_vision_encoder_batch([reqs[i].image for i in raw]) if raw else None
         emb_of = {i: j for j, i in enumerate(raw)}
-        firsts: Dict[int, int] = {}
+        firsts: Dict[int, tuple] = {}
         pos_of: Dict[int, int] = {}
 
         def groups(keyf):
@@ -481,9 +524,9 @@ class ContinuousEngine:
                 pe = m._embed(torch.tensor([reqs[i].prompt for i in idx], dtype=torch.int32))
                 x = torch.cat([bos, img_emb[[emb_of[i] for i in idx]], pe], dim=1)
                 hidden = self._forward_slots(x, 0, [reqs[i].slot for i in idx], [reqs[i].variant for i in idx])
-                first = self._first_tokens(hidden, [reqs[i] for i in idx]).tolist()
+                first = self._first_tokens(hidden, [reqs[i] for i in idx])
                 for i, f in zip(idx, first):
-                    firsts[i], pos_of[i] = int(f), x.shape[1]
+                    firsts[i], pos_of[i] = f, x.shape[1]
         else:
             prefix: Dict[int, int] = {}
             if raw:
@@ -503,10 +546,11 @@ class ContinuousEngine:
                     sub = idx[j0 : j0 + per]
                     pe = m._embed(torch.tensor([reqs[i].prompt for i in sub], dtype=torch.int32))
                     hidden = self._forward_slots(pe, prefix[sub[0]], [reqs[i].slot for i in sub], [reqs[i].variant for i in sub])
-                    first = self._first_tokens(hidden, [reqs[i] for i in sub]).tolist()
+                    first = self._first_tokens(hidden, [reqs[i] for i in sub])
                     for i, f in zip(sub, first):
-                        firsts[i], pos_of[i] = int(f), prefix[i] + t
-        return [(firsts[i], pos_of[i]) for i in range(len(reqs))]
+                        firsts[i], pos_of[i] = f, prefix[i] + t
+        # (first token, next position) per request; with ``logprobs`` also the first token's (logprob, rank)
+        return [(int(firsts[i][0]), pos_of[i]) + tuple(firsts[i][1:]) for i in range(len(reqs))]
 
     def _buffers(self, bucket: int):
         """Fixed-address buffers of a (chunk, bucket): int32 device state [slots (chunk x bucket) | pos (bucket) | tokens ((chunk + 1) x
@@ -527,6 +571,18 @@ class ContinuousEngine:
                 u_host = torch.zeros(c * bucket + 2 * bucket, dtype=torch.float32, pin_memory=True)
             u_dev = torch.zeros(c * bucket + 2 * bucket, dtype=torch.float32, device=self.model.device)
             b = bufs[key] = (dev, host, u_dev, u_host, n_in)
+        return b
+
+    def _logprob_buffers(self, bucket: int):
+        """Fixed-address int32 device words [2, chunk, bucket] of a (chunk, bucket): plane 0 the fp32 log-probabilities of a
+        chunk's tokens (as raw words), plane 1 their ranks -- one D2H copy of both.  Only an engine with ``logprobs`` has them."""
+        import torch
+
+        bufs = self.model.__dict__.setdefault("_continuous_logprob_bufs", {})
+        key = (self.chunk, bucket)
+        b = bufs.get(key)
+        if b is None:
+            b = bufs[key] = torch.zeros(2, self.chunk, bucket, dtype=torch.int32, device=self.model.device)
         return b
 
     def _step(self, plan: ChunkPlan) -> np.ndarray:
@@ -572,6 +628,10 @@ class ContinuousEngine:
         kv = m._kv_struct(0)
         answer_id = m.config.tokenizer.answer_id
         step_logits = logits[:B]
+        with_lp = self.logprobs
+        if with_lp:
+            lp_words = self._logprob_buffers(B)
+            lp_d, rk_d = lp_words[0].view(torch.float32), lp_words[1]
 
         def step_rows(i):  # step i's row of the slot table; a LoRA row in the chunk: the chunk's row-variant table with it
             return self._rows(slots_d[i], var_d if lora else None)
@@ -582,6 +642,8 @@ class ContinuousEngine:
                 if sample:  # the step left its logits in ``logits``: every sampling row draws from them instead of the argmax it
                     # wrote (a greedy row takes the same argmax again; an idle row keeps it)
                     m._pick_rows(step_logits, temp_d, top_p_d, answer_id, u2[i], out=hist[i + 1])
+                if with_lp:  # targets = the step's tokens; an idle or padding row's value is never read (SlotScheduler.commit)
+                    m._token_logprobs(step_logits, hist[i + 1], answer_id, lp_d[i], rk_d[i])
 
         if not m.use_graphs:
             body()
@@ -591,10 +653,16 @@ class ContinuousEngine:
             # settings only "this chunk has a sampling launch": the values are device data, in the allocation of the uniforms)
             key = ("continuous", stream, B, n, dev.data_ptr(), ws.data_ptr(), m._kv_k.data_ptr(), logits.data_ptr(), sample,
                    u_dev.data_ptr()) + step_rows(0).key()
+            if with_lp:  # a chunk with the logprob launches is another graph; without them key and graph are unchanged
+                key += ("logprobs", lp_words.data_ptr())
 
             def below_cap():
                 return sum(1 for k in m._graphs if isinstance(k, tuple) and k and k[0] == "continuous" and k[1] == stream) < MAX_GRAPHS
 
             if m._replay_or_capture(key, body, may_capture=below_cap):
                 self.stats.graph_captures += 1
-        return hist[1 : n + 1].cpu().numpy()  # the chunk's one D2H copy (the lockstep loop syncs here too)
+        out = hist[1 : n + 1].cpu().numpy()  # the chunk's D2H copy of the ids (the lockstep loop syncs here too)
+        if not with_lp:
+            return out
+        words = lp_words[:, :n].cpu().numpy()  # ... and one more of both planes
+        return out, words[0].view(np.float32), words[1]

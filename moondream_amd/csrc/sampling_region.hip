@@ -361,6 +361,91 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const bf16_
                    probs_out ? probs_out + (int64_t)b * ldp : nullptr);
 }
 
+// ---------------------------------------------------------------------------
+// log-probability and rank of one given token per row (md_token_logprobs): the model's own distribution at temperature 1,
+// untruncated, over the LIVE tokens of the row (all but the suppressed id of a suppressed row).
+// TWO-PASS form: pass 1 takes the maximum m of the live logits (and the integer rank counts), pass 2 sums exp(x - m).
+// Summation order, a function of vocab alone (never of the row count or the row):
+//   1. thread tid adds its strided share exp(x[tid + k * 1024] - m), k = 0, 1, .. ascending, sequentially in fp32
+//      (n_t = ceil(vocab / 1024) terms: 50 at vocab 51200);
+//   2. a 6-level xor butterfly over the wave's 64 lanes (offsets 32, 16, .., 1);
+//   3. a 4-level xor butterfly over the 16 wave partials (offsets 8, 4, 2, 1).
+// So every term passes through at most (n_t - 1) + log2(1024) additions.  A -inf logit adds exp(-inf) = 0.  The rank is
+// a sum of integers: exact, whatever the order.  Plain 2-byte loads: no alignment demand on vocab or the row stride.
+constexpr int LOGPROB_THREADS = 1024;
+
+__global__ __launch_bounds__(LOGPROB_THREADS) void token_logprobs_kernel(const bf16_t* __restrict__ logits, int64_t ld, int vocab,
+                                                                         int suppress_id, const int32_t* __restrict__ suppress_rows,
+                                                                         const int32_t* __restrict__ targets,
+                                                                         float* __restrict__ logprob, int32_t* __restrict__ rank) {
+  __shared__ float red_max[LOGPROB_THREADS / 64];
+  __shared__ float red_sum[LOGPROB_THREADS / 64];
+  __shared__ int red_cnt[LOGPROB_THREADS / 64];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  // every exit below is taken by the whole workgroup (t and sup are per row), before any barrier
+  const int t = targets[r];
+  if (t < 0 || t >= vocab) {  // an idle / padding row: the logits row is not read
+    if (tid == 0) {
+      logprob[r] = __builtin_nanf("");
+      if (rank) rank[r] = -1;
+    }
+    return;
+  }
+  const int sup = (suppress_id >= 0 && (suppress_rows == nullptr || suppress_rows[r] != 0)) ? suppress_id : -1;
+  if (t == sup) {
+    if (tid == 0) {
+      logprob[r] = -INFINITY;
+      if (rank) rank[r] = -1;
+    }
+    return;
+  }
+  const bf16_t* lr = logits + (int64_t)r * ld;
+  const float xt = bf2f(lr[t]);
+
+  // ---- pass 1: maximum of the live logits; tokens that come before t in md_argmax_bf16's order (greater, or equal with a lower id)
+  float mx = -INFINITY;
+  int cnt = 0;
+  for (int i = tid; i < vocab; i += LOGPROB_THREADS) {
+    if (i == sup) continue;
+    const float x = bf2f(lr[i]);
+    mx = fmaxf(mx, x);
+    cnt += (x > xt || (x == xt && i < t)) ? 1 : 0;
+  }
+  mx = wave_max(mx);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if ((tid & 63) == 0) {
+    red_max[tid >> 6] = mx;
+    red_cnt[tid >> 6] = cnt;
+  }
+  __syncthreads();
+  mx = red_max[tid & 15];  // every 16 consecutive lanes hold the 16 wave partials
+  cnt = red_cnt[tid & 15];
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) {
+    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    cnt += __shfl_xor(cnt, o, 64);
+  }
+
+  // ---- pass 2: s = sum over live v of exp(x[v] - m), in the order documented above
+  float s = 0.f;
+  for (int i = tid; i < vocab; i += LOGPROB_THREADS) {
+    if (i == sup) continue;
+    s += expf(bf2f(lr[i]) - mx);
+  }
+  s = wave_sum(s);
+  if ((tid & 63) == 0) red_sum[tid >> 6] = s;
+  __syncthreads();
+  s = red_sum[tid & 15];
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+
+  if (tid == 0) {
+    logprob[r] = (xt - mx) - logf(s);
+    if (rank) rank[r] = cnt;
+  }
+}
+
 }  // namespace
 
 extern "C" md_status md_fourier_features(const void* x, int64_t ldx, int32_t rows, int32_t in_dim, const void* w,
@@ -400,5 +485,15 @@ extern "C" md_status md_sample_rows(const void* logits, int64_t ld, int32_t batc
   MD_TRY(md_ensure_dynamic_lds((const void*)sample_rows_kernel, SAMPLE_LDS));
   hipLaunchKernelGGL(sample_rows_kernel, dim3(batch), dim3(SAMPLE_THREADS), SAMPLE_LDS, (hipStream_t)stream, (const bf16_t*)logits,
                      ld, vocab, suppress_id, temperature, top_p, uniforms, next, (bf16_t*)probs_out, ld_probs);
+  return md_launch_status();
+}
+
+extern "C" md_status md_token_logprobs(const void* logits, int64_t ld, int32_t rows, int32_t vocab, int32_t suppress_id,
+                                       const int32_t* suppress_rows, const int32_t* targets, float* logprob, int32_t* rank,
+                                       void* stream) {
+  MD_CHECK_ARG(logits && targets && logprob && rows >= 0 && vocab > 0 && ld >= vocab);
+  if (rows == 0) return MD_OK;
+  hipLaunchKernelGGL(token_logprobs_kernel, dim3(rows), dim3(LOGPROB_THREADS), 0, (hipStream_t)stream, (const bf16_t*)logits, ld,
+                     vocab, suppress_id, suppress_rows, targets, logprob, rank);
   return md_launch_status();
 }

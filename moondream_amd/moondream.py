@@ -18,8 +18,8 @@ constructor raises.
 from __future__ import annotations
 
 import ctypes as C
-import os
 import math
+import os
 from dataclasses import dataclass, replace
 from typing import Any, Dict, Iterable, List, Literal, Optional, Sequence, Tuple, Union
 
@@ -687,15 +687,16 @@ class MoondreamModel:
             rows.step_entry,
         )
 
-    def _lm_head(self, hidden: torch.Tensor) -> torch.Tensor:
-        """hidden [B,T,D] -> logits of the last token [B,V].  reference: text.py:163-167."""
+    def _lm_head(self, hidden: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """hidden [B,T,D] -> logits of the last token [B,V] (into ``out`` when given).  reference: text.py:163-167."""
         b, t, d = hidden.shape
-        logits = torch.empty(b, self.config.text.vocab_size, dtype=BF16, device=self._device)
+        logits = out if out is not None else torch.empty(b, self.config.text.vocab_size, dtype=BF16, device=self._device)
+        assert logits.shape == (b, self.config.text.vocab_size) and logits.dtype == BF16 and logits.stride(1) == 1
         need = self.lib.md_lm_head_workspace_bytes(C.byref(self.w.text), b)
         ws = self._workspace(need, 1)
         _lib.check(
             self.lib.md_lm_head(
-                C.byref(self.w.text), hidden.contiguous().data_ptr(), b, t, logits.data_ptr(), logits.shape[1],
+                C.byref(self.w.text), hidden.contiguous().data_ptr(), b, t, logits.data_ptr(), logits.stride(0),
                 ws.data_ptr(), ws.numel(), self._stream(),
             ),
             "md_lm_head",
@@ -1095,6 +1096,24 @@ class MoondreamModel:
         )
         return nxt
 
+    def _token_logprobs(self, logits: torch.Tensor, targets: torch.Tensor, suppress_id: int, logprob: torch.Tensor,
+                        rank: torch.Tensor, suppress_rows: Optional[torch.Tensor] = None):
+        """``logprob[r]`` (device fp32 [R]) and ``rank[r]`` (device int32 [R]) of token ``targets[r]`` (device int32 [R]) in row
+        r of ``logits`` [R, V]: md_token_logprobs.  The log-probability is the model's own distribution at temperature 1,
+        untruncated, with ``suppress_id`` left out in the rows ``suppress_rows`` marks (None: all of them; -1: in none) --
+        not the tempered / top-p-renormalised distribution a sampled token was drawn from.  Rank 0: the row's argmax.
+        Nothing is allocated and nothing synchronises: capturable."""
+        r, v = logits.shape
+        for t in (targets, logprob, rank) + ((suppress_rows,) if suppress_rows is not None else ()):
+            assert t.is_contiguous() and t.numel() == r and t.device == logits.device
+        assert targets.dtype == torch.int32 and rank.dtype == torch.int32 and logprob.dtype == torch.float32
+        _lib.check(
+            self.lib.md_token_logprobs(logits.data_ptr(), logits.stride(0), r, v, suppress_id,
+                                       suppress_rows.data_ptr() if suppress_rows is not None else None, targets.data_ptr(),
+                                       logprob.data_ptr(), rank.data_ptr(), self._stream()),
+            "md_token_logprobs",
+        )
+
     # ---------------------------------------------------------- batched engine
     def _prefill_prompts(self, prompts: Sequence[Sequence[int]], pos: int, rows: Union[int, _Rows] = 0, prompt_embs=None,
                          last_only: bool = False):
@@ -1110,14 +1129,14 @@ class MoondreamModel:
     def _decode_greedy(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
                        rows: Union[int, _Rows] = 0, eos_id: Optional[int] = None, check_every: int = 16, allow_b1: bool = True,
                        temperature: float = 0.0, top_p: float = 0.0, generator: Optional[torch.Generator] = None,
-                       row_perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       row_perm: Optional[torch.Tensor] = None, first_logprobs=None):
         """``_decode_greedy_impl`` plus the safety net of the persistent single-sequence kernel: its software grid barriers
         need every workgroup resident; if one times out (the GPU was shared with another persistent kernel) the kernel
         raises an error word and finishes with garbage.  That state is fully re-initialised by decoding the same tokens
         again (K / V rows at positions >= ``pos``, the id history, the position buffer), so the call is repeated on the
         batched kernels and the persistent kernel is switched off for this model."""
         hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, rows, eos_id, check_every, allow_b1,
-                                        temperature, top_p, generator, row_perm)
+                                        temperature, top_p, generator, row_perm, first_logprobs)
         if self._b1_used:
             torch.cuda.current_stream(self._device).synchronize()
             if int(self._b1_sync[64 * 11]) != 0:
@@ -1129,13 +1148,15 @@ class MoondreamModel:
                 self._graphs.clear()
                 warnings.warn("md_decode_step_b1: a grid barrier timed out (GPU shared with another persistent kernel?); "
                               "repeating the decode on the batched kernels and disabling the single-sequence kernel", RuntimeWarning)
-                hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, rows, eos_id, check_every, False)
+                hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, rows, eos_id, check_every, False,
+                                                first_logprobs=first_logprobs)
         return hist
 
     def _decode_greedy_impl(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
                             rows: Union[int, _Rows] = 0, eos_id: Optional[int] = None, check_every: int = 16,
                             allow_b1: bool = True, temperature: float = 0.0, top_p: float = 0.0,
-                            generator: Optional[torch.Generator] = None, row_perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+                            generator: Optional[torch.Generator] = None, row_perm: Optional[torch.Tensor] = None,
+                            first_logprobs=None):
         """Device-resident decode loop: returns int32 [steps+1, B] (row 0 = ``first``).  ``temperature`` 0: greedy.  Otherwise every
         step draws each sequence's token with the reference's rule (moondream.py:521-528: softmax(logits / T), _apply_top_p,
         multinomial) from the step's own logits on the device (md_sample_top_p), with one uniform per (step, sequence) taken
@@ -1145,7 +1166,10 @@ class MoondreamModel:
         prompts differ in length decode in the same lockstep batch).
         With ``compile()`` the steps are replayed from a captured hipGraph in chunks.
         ``rows``: the routing of every step (``_Rows``); ``row_perm``: row i draws the uniforms of row row_perm[i], so that
-        sampled rows in another order see the draws of the copy path."""
+        sampled rows in another order see the draws of the copy path.
+        ``first_logprobs`` = (logprob fp32 [B], rank int32 [B]) of ``first``: the loop also keeps the log-probability and rank
+        of every token it picks (``_token_logprobs`` on the logits the step leaves, one launch after the step's pick, inside
+        the captured graph) and returns (hist, logprobs fp32 [steps+1, B], ranks int32 [steps+1, B]).  No id changes."""
         rows = _Rows.of(rows)
         b = first.shape[0]
         t = self.config.text
@@ -1158,8 +1182,14 @@ class MoondreamModel:
         hist = torch.zeros(max_tokens + 1, b, dtype=torch.int32, device=self._device)
         hist[0] = first
         self._b1_used = False
+        with_lp = first_logprobs is not None
+        if with_lp:
+            lp_hist = torch.full((max_tokens + 1, b), float("nan"), dtype=torch.float32, device=self._device)
+            rk_hist = torch.full((max_tokens + 1, b), -1, dtype=torch.int32, device=self._device)
+            lp_hist[0], rk_hist[0] = first_logprobs
+        done = lambda upto: (hist[:upto], lp_hist[:upto], rk_hist[:upto]) if with_lp else hist[:upto]
         if max_tokens == 0:
-            return hist
+            return done(1)
         pos_base = self._h2d(torch.tensor(pos_list, dtype=torch.int32))
         sample = temperature != 0
         uniforms = (torch.rand(max_tokens, b, device=self._device, dtype=torch.float32, generator=generator) if sample else None)
@@ -1177,13 +1207,16 @@ class MoondreamModel:
             while steps < max_tokens:
                 emb = self._embed(hist[steps].reshape(b, 1))
                 h = self._text_forward(emb, pos_h, rows, pos_dev=pos_t)
-                hist[steps + 1] = self._pick(self._lm_head(h), temperature, top_p, suppress_id, generator)
+                lg = self._lm_head(h)
+                hist[steps + 1] = self._pick(lg, temperature, top_p, suppress_id, generator)
+                if with_lp:
+                    self._token_logprobs(lg, hist[steps + 1], suppress_id, lp_hist[steps + 1], rk_hist[steps + 1])
                 pos_t.add_(1)
                 pos_h = [p + 1 for p in pos_h]
                 steps += 1
                 if check_every and steps % check_every == 0 and all_done(steps):
                     break
-            return hist[: steps + 1]
+            return done(steps + 1)
 
         logits = self._decode_logits(b)
         need = self._decode_ws_bytes(rows, b)
@@ -1203,7 +1236,12 @@ class MoondreamModel:
             ws = self._workspace(need, 2)
         step_logits = logits[:b]
 
-        def one_step(tok_in, tok_out, pos_buf, u_row=None):
+        def one_step(tok_in, tok_out, pos_buf, u_row=None, lp_row=None, rk_row=None):
+            step_pick(tok_in, tok_out, pos_buf, u_row)
+            if with_lp:  # the step (the single-sequence kernel too) left its logits in ``logits``; tok_out holds its pick
+                self._token_logprobs(step_logits, tok_out, suppress_id, lp_row, rk_row)
+
+        def step_pick(tok_in, tok_out, pos_buf, u_row):
             if b1:
                 _lib.check(
                     self.lib.md_decode_step_b1(
@@ -1221,11 +1259,12 @@ class MoondreamModel:
         if not self.use_graphs:
             pos_t = pos_base.clone()
             while steps < max_tokens:
-                one_step(hist[steps], hist[steps + 1], pos_t, uniforms[steps] if sample else None)
+                one_step(hist[steps], hist[steps + 1], pos_t, uniforms[steps] if sample else None,
+                         lp_hist[steps + 1] if with_lp else None, rk_hist[steps + 1] if with_lp else None)
                 steps += 1
                 if check_every and steps % check_every == 0 and all_done(steps):
                     break
-            return hist[: steps + 1]
+            return done(steps + 1)
 
         # ---- hipGraph path: one graph = `chunk` consecutive steps over fixed buffers
         chunk = max(1, min(check_every or 16, max_tokens))
@@ -1237,13 +1276,17 @@ class MoondreamModel:
                    torch.cuda.current_stream(self._device).cuda_stream, b1, float(temperature), float(top_p),
                    # the e4m3 copy decides the attention kernel a step bakes in (enable_fp8 also clears the graphs)
                    self._kv_k8.data_ptr() if self._kv8_scales is not None and self._kv_k8 is not None else 0) + rows.key()
+            if with_lp:  # a chunk with the logprob launches is another graph; without them the key and the graph are unchanged
+                key += ("logprobs",)
             entry = self._graphs.get(key)
             if entry is not None:
-                buf, pos_buf, u_buf = entry[1]
+                buf, pos_buf, u_buf, lp_buf, rk_buf = entry[1]
             else:
                 buf = torch.zeros(n + 1, b, dtype=torch.int32, device=self._device)
                 pos_buf = torch.zeros(b, dtype=torch.int32, device=self._device)
                 u_buf = torch.zeros(n, b, dtype=torch.float32, device=self._device)
+                lp_buf = torch.zeros(n, b, dtype=torch.float32, device=self._device) if with_lp else None
+                rk_buf = torch.zeros(n, b, dtype=torch.int32, device=self._device) if with_lp else None
             buf[0] = hist[steps]
             pos_buf.copy_(pos_base + steps)
             if sample:
@@ -1251,14 +1294,17 @@ class MoondreamModel:
 
             def body():
                 for i in range(n):
-                    one_step(buf[i], buf[i + 1], pos_buf, u_buf[i])
+                    one_step(buf[i], buf[i + 1], pos_buf, u_buf[i], lp_buf[i] if with_lp else None, rk_buf[i] if with_lp else None)
 
-            self._replay_or_capture(key, body, (buf, pos_buf, u_buf))
+            self._replay_or_capture(key, body, (buf, pos_buf, u_buf, lp_buf, rk_buf))
             hist[steps + 1 : steps + n + 1] = buf[1:]
+            if with_lp:
+                lp_hist[steps + 1 : steps + n + 1] = lp_buf
+                rk_hist[steps + 1 : steps + n + 1] = rk_buf
             steps += n
             if all_done(steps):
                 break
-        return hist[: steps + 1]
+        return done(steps + 1)
 
     def _replay_or_capture(self, key, body, state=None, may_capture=None) -> bool:
         """Replay the graph stored under ``key``; a key not seen before runs ``body`` eagerly, then captures it and stores
@@ -1309,17 +1355,24 @@ class MoondreamModel:
         return out
 
     def _prefill_groups(self, groups: Sequence[Tuple[int, int]], embed, pos: int, rows: _Rows, sampler=None,
-                        logits_capture: Optional[torch.Tensor] = None, row_perm=None):
+                        logits_capture: Optional[torch.Tensor] = None, row_perm=None, first_logprobs=None, hidden_sink=None):
         """One decoder pass per group [r0, r1) of equal-length prompts: ``embed(r0, r1)`` [r1-r0, T, D] goes through the decoder
         at position ``pos`` into the slots of ``rows.sub(r0, r1)``, then lm_head and the pick of the first token (``sampler`` =
         (temperature, top_p, suppress_id, generator); None: argmax; ``row_perm(r0, r1)``: the draw order of a sampled group).
-        Returns (first int32 [B], hidden_last [B, D], next_pos list); the groups' logits go to ``logits_capture`` [B, V]."""
+        Returns (first int32 [B], hidden_last [B, D], next_pos list); the groups' logits go to ``logits_capture`` [B, V], the
+        log-probability and rank of each first token (unsuppressed, like the pick) to ``first_logprobs`` = (fp32 [B], int32 [B]).
+        ``hidden_sink(r0, r1, hidden [r1-r0, T, D])``: the scorer's form -- every hidden row of the pass goes to the sink, and
+        no first token is picked (``first`` and ``hidden_last`` are not filled)."""
         b = groups[-1][1]
         first = torch.empty(b, dtype=torch.int32, device=self._device)
         hidden_last = torch.empty(b, self.config.text.dim, dtype=BF16, device=self._device)
         next_pos = [0] * b
         for r0, r1 in groups:
             x = embed(r0, r1)
+            next_pos[r0:r1] = [pos + x.shape[1]] * (r1 - r0)
+            if hidden_sink is not None:
+                hidden_sink(r0, r1, self._text_forward(x, pos, rows.sub(r0, r1), keep="all"))
+                continue
             hidden = self._text_forward(x, pos, rows.sub(r0, r1), keep="last")  # [r1-r0, 1, D]
             logits = self._lm_head(hidden)
             if logits_capture is not None:
@@ -1328,12 +1381,14 @@ class MoondreamModel:
                 first[r0:r1] = self._pick(logits, 0.0, 0.0)
             else:
                 first[r0:r1] = self._pick(logits, *sampler, row_perm=row_perm(r0, r1) if row_perm is not None else None)
+            if first_logprobs is not None:
+                self._token_logprobs(logits, first[r0:r1], -1, first_logprobs[0][r0:r1], first_logprobs[1][r0:r1])
             hidden_last[r0:r1] = hidden[:, -1, :]
-            next_pos[r0:r1] = [pos + x.shape[1]] * (r1 - r0)
         return first, hidden_last, next_pos
 
     def _prepare_sequences(self, images, prompts: Sequence[Sequence[int]], mark=None, rows: Union[int, _Rows] = 0,
-                           fuse: bool = False, logits_capture: Optional[torch.Tensor] = None, sampler=None):
+                           fuse: bool = False, logits_capture: Optional[torch.Tensor] = None, sampler=None,
+                           first_logprobs=None, hidden_sink=None):
         """Everything before the first generated token, for B (image, prompt-ids) pairs: sequences are
         placed in KV slots in order of prompt length (stable), so that every group of equal-length
         prompts occupies a contiguous slot range; raw images are encoded together and prefilled
@@ -1341,7 +1396,8 @@ class MoondreamModel:
         distinct length.  Returns (order, first int32 [B], hidden_last [B, D], next_pos list) in slot
         order; ``order[slot]`` is the caller's index.  ``sampler`` = (temperature, top_p, suppress_id, generator) draws the first token
         as the reference's _prefill_prompt does (moondream.py:313-318; suppress_id -1 there); None = argmax.  Must run under
-        torch.inference_mode().  ``rows``: the routing of slots 0 .. B-1 (a per-row variant table is already in slot order)."""
+        torch.inference_mode().  ``rows``: the routing of slots 0 .. B-1 (a per-row variant table is already in slot order).
+        ``first_logprobs`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in slot order."""
         mark = mark or (lambda name: None)
         rows = _Rows.of(rows)
         b = len(images)
@@ -1369,7 +1425,8 @@ class MoondreamModel:
             mark("vision")
             bos = self._embed(torch.full((b, 1), self.config.tokenizer.bos_id, dtype=torch.int32))
             fused = lambda g0, g1: torch.cat([bos[g0:g1], img_emb[g0:g1], embed_prompts(g0, g1)], dim=1)
-            out = self._prefill_groups(_length_groups(prompts), fused, 0, rows, sampler, logits_capture)
+            out = self._prefill_groups(_length_groups(prompts), fused, 0, rows, sampler, logits_capture,
+                                       first_logprobs=first_logprobs, hidden_sink=hidden_sink)
             mark("image_prefill")
             mark("prompt_prefill")
             return (order, *out)
@@ -1385,7 +1442,8 @@ class MoondreamModel:
                     raise ValueError("EncodedImage with a different prefix length than the rest of the batch")
                 self.load_encoded_image(im, i)
                 pos = im.pos
-        out = self._prefill_groups(_length_groups(prompts), embed_prompts, pos, rows, sampler, logits_capture)  # one per prompt length
+        out = self._prefill_groups(_length_groups(prompts), embed_prompts, pos, rows, sampler, logits_capture,
+                                   first_logprobs=first_logprobs, hidden_sink=hidden_sink)  # one per prompt length
         mark("prompt_prefill")
         return (order, *out)
 
@@ -1415,7 +1473,8 @@ class MoondreamModel:
                 enc[id(im)] = self.encode_image(im, settings)
         return [enc[id(im)] for im in images]
 
-    def _prepare_sequences_shared(self, images, prompts: Sequence[Sequence[int]], mark=None, sampler=None):
+    def _prepare_sequences_shared(self, images, prompts: Sequence[Sequence[int]], mark=None, sampler=None,
+                                  first_logprobs=None, hidden_sink=None):
         """``_prepare_sequences`` with a SHARED image prefix (moondream_amd/shared_prefix.py): each distinct image (by identity)
         is prefilled or loaded ONCE, into prefix slot k < P; the rows take slots P + r and read the prefix from there.  Raw
         images go through one ViT batch and ``_prefill_images``; EncodedImages are loaded once.  In the fp8 KV mode both of these
@@ -1424,7 +1483,8 @@ class MoondreamModel:
         distinct length (md_text_forward_shared).  Returns (order, first, hidden_last, next_pos, rows, row_perm): the first
         four as ``_prepare_sequences`` returns them, in this path's row order; ``rows`` is the routing over the prefix table
         (``_Rows``); ``row_perm`` maps a row to its row in the copy
-        path's order (sampling draws).  Must run under torch.inference_mode()."""
+        path's order (sampling draws).  ``first_logprobs`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in this path's
+        row order.  Must run under torch.inference_mode()."""
         mark = mark or (lambda name: None)
         plan = plan_shared_prefix(list(images), [len(p) for p in prompts])
         if any(len(p) == 0 for p in prompts):
@@ -1462,7 +1522,8 @@ class MoondreamModel:
         # one prefill per distinct prompt length; a sampled group draws in the copy path's row order
         first, hidden_last, next_pos = self._prefill_groups(
             plan.groups, lambda r0, r1: self._embed(torch.tensor(prompts[r0:r1], dtype=torch.int32)), pos, rows, sampler,
-            row_perm=lambda r0, r1: row_perm[r0:r1] - min(plan.copy_rank[r0:r1]))
+            row_perm=lambda r0, r1: row_perm[r0:r1] - min(plan.copy_rank[r0:r1]), first_logprobs=first_logprobs,
+            hidden_sink=hidden_sink)
         mark("prompt_prefill")
         return plan.order, first, hidden_last, next_pos, rows, row_perm
 
@@ -1479,7 +1540,8 @@ class MoondreamModel:
         generator: Optional[torch.Generator] = None,
         share_prefix: bool = False,
         variants: Optional[Sequence[Optional[str]]] = None,
-    ) -> List[List[int]]:
+        return_logprobs: bool = False,
+    ):
         """Token ids for B (image, prompt-ids) pairs, decoded in lockstep; greedy by default.
 
         ``share_prefix``: rows whose image is the same object (the same ``EncodedImage``, or the same PIL image by identity)
@@ -1521,6 +1583,14 @@ class MoondreamModel:
         to the same row in a base-only call: the mixed call rounds fc1's output to bf16 before GELU, as the reference does
         (layers.py:130-137), where the base path applies GELU in the GEMM epilogue in fp32.  Not with ``variant=``;
         ``share_prefix`` is ignored (copy path).
+
+        ``return_logprobs``: returns ``(ids, logprobs, ranks)``; ``logprobs[i][j]`` and ``ranks[i][j]`` belong to ``ids[i][j]``
+        and are truncated as the ids are.  A log-probability is log softmax of the logits the token was picked from, in the
+        model's OWN distribution: temperature 1, untruncated, with ``answer_id`` left out from the second token on as generation
+        leaves it out -- not the tempered / top-p-renormalised distribution a sampled token was drawn from.  ``ranks[i][j]``
+        counts the tokens ahead of the pick in argmax order: 0 for every greedy token.  Computed on the device
+        (md_token_logprobs: one launch after each step's pick, inside the captured chunk; one copy to the host at the end with
+        the ids).  The flag changes no id; with it off the launches and captured graphs are unchanged.
         """
         b = len(images)
         assert b == len(prompts) and b > 0
@@ -1542,8 +1612,12 @@ class MoondreamModel:
         with torch.inference_mode():
             sampler = None if temperature == 0 else (float(temperature), float(top_p), -1, generator)
             rows, row_perm = _Rows(lora=lora), None
+            first_lp = None
+            if return_logprobs:
+                first_lp = (torch.empty(b, dtype=torch.float32, device=self._device), torch.empty(b, dtype=torch.int32, device=self._device))
             if multi_rows is None and share_prefix and self._shares_prefix(lora):
-                order, first, _, next_pos, rows, row_perm = self._prepare_sequences_shared(list(images), prompts, mark, sampler)
+                order, first, _, next_pos, rows, row_perm = self._prepare_sequences_shared(list(images), prompts, mark, sampler,
+                                                                                           first_logprobs=first_lp)
             else:
                 if multi_rows is not None:
                     # the slot order of _prepare_sequences (stable by prompt length), so that the table is in slot order too
@@ -1551,34 +1625,47 @@ class MoondreamModel:
                     rows = _Rows(variants=self._variant_table([multi_rows[i] for i in slot_order]), bank=self._bank)
                 elif share_prefix:  # the copy path over each distinct image's EncodedImage
                     images = self._encode_distinct(images, {"variant": variant})
-                order, first, _, next_pos = self._prepare_sequences(list(images), prompts, mark, rows, fuse=True, sampler=sampler)
+                order, first, _, next_pos = self._prepare_sequences(list(images), prompts, mark, rows, fuse=True, sampler=sampler,
+                                                                    first_logprobs=first_lp)
             b = len(order)
             stop = None if ignore_eos else eos
             hist = self._decode_greedy(first, next_pos if len(set(next_pos)) > 1 else next_pos[0], max_tokens,
                                        tk.answer_id, rows, stop, temperature=float(temperature), top_p=float(top_p),
-                                       generator=generator, row_perm=row_perm)
+                                       generator=generator, row_perm=row_perm, first_logprobs=first_lp)
             mark("decode")
-            cols = hist.t().tolist()
+            if return_logprobs:  # ids, logprobs (as raw words) and ranks in ONE copy to the host
+                hist, lp_hist, rk_hist = hist
+                packed = torch.stack([hist, lp_hist.view(torch.int32), rk_hist]).cpu().numpy()
+                cols = packed[0].T.tolist()
+                lp_cols, rk_cols = packed[1].view(np.float32).T.tolist(), packed[2].T.tolist()
+            else:
+                cols = hist.t().tolist()
             if b == 1:
                 self._check_b1_barriers()
             results: List[Optional[List[int]]] = [None] * b
+            logprobs: List[Optional[List[float]]] = [None] * b
+            ranks: List[Optional[List[int]]] = [None] * b
             for slot, src in enumerate(order):
                 results[src] = self._truncate(cols[slot], stop, max_tokens)
+                if return_logprobs:  # _truncate keeps a leading run of the ids: the same run of their values
+                    logprobs[src], ranks[src] = lp_cols[slot][: len(results[src])], rk_cols[slot][: len(results[src])]
         self._phase_times(marks)
-        return results  # type: ignore[return-value]
+        return (results, logprobs, ranks) if return_logprobs else results  # type: ignore[return-value]
 
     def batch_generate_ids_continuous(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                                       eos_id: Optional[int] = None, ignore_eos: bool = False, max_live: int = 64, chunk: int = 16,
                                       temperature: Union[float, Sequence[float]] = 0.0,
                                       top_p: Union[float, Sequence[float]] = DEFAULT_TOP_P, seeds=None,
-                                      variant: Optional[str] = None) -> List[List[int]]:
+                                      variant: Optional[str] = None, return_logprobs: bool = False):
         """``batch_generate_ids`` with continuous batching (moondream_amd/continuous.py): per-request ``max_tokens`` and EOS
         exit, freed KV slots refilled from the queue mid-decode; same greedy ids as the lockstep path.  ``temperature`` and
-        ``top_p``: one float, or one per request (greedy and sampled requests share the decode steps)."""
+        ``top_p``: one float, or one per request (greedy and sampled requests share the decode steps).  ``return_logprobs``:
+        (ids, logprobs, ranks) as ``batch_generate_ids`` returns them (``ContinuousEngine(logprobs=True)``)."""
         from .continuous import ContinuousEngine
 
-        return ContinuousEngine(self, max_live, chunk).generate(images, prompts, max_tokens, eos_id, ignore_eos, seeds, variant,
-                                                                 temperature, top_p)
+        eng = ContinuousEngine(self, max_live, chunk, logprobs=bool(return_logprobs))
+        return eng.generate(images, prompts, max_tokens, eos_id, ignore_eos, seeds, variant, temperature, top_p,
+                            return_logprobs=bool(return_logprobs))
 
     def teacher_forced_logits(self, images, prompts: Sequence[Sequence[int]], forced_ids, gather_idx) -> torch.Tensor:
         """Parity instrument (tests / bench.py): the logits of every greedy decision when each sequence is FORCED to follow
@@ -1614,6 +1701,83 @@ class MoondreamModel:
                 vals[:, j + 1] = torch.gather(logits[:b].float(), 1, idx_s[:, j + 1])
             out[src] = vals.cpu()
         return out
+
+    # ------------------------------------------------------------- scoring
+    def _check_score_args(self, images, prompts, continuations) -> None:
+        """``score_ids``' argument checks: host data only, before any device work."""
+        if self._kv8_scales is not None or bool(self.w.text.fp8) or bool(self.w.text.f8):
+            raise ValueError("score_ids is not served in the fp8 modes")
+        n = len(images)
+        if n == 0 or len(prompts) != n or len(continuations) != n:
+            raise ValueError(f"score_ids: {n} images, {len(prompts)} prompts and {len(continuations)} continuations")
+        for i in range(n):
+            if not isinstance(images[i], (EncodedImage, Image.Image)):
+                raise ValueError("image must be a PIL Image or EncodedImage")
+            if len(prompts[i]) == 0:
+                raise ValueError(f"score_ids: empty prompt (row {i})")
+            if len(continuations[i]) == 0:
+                raise ValueError(f"score_ids: empty continuation (row {i})")
+            prefix = images[i].pos if isinstance(images[i], EncodedImage) else 1 + self.config.vision.n_patches
+            total = prefix + len(prompts[i]) + len(continuations[i])
+            if total > self.config.text.max_context:
+                raise ValueError(f"score_ids: image prefix + prompt + continuation ({total} positions, row {i}) do not fit the "
+                                 f"{self.config.text.max_context}-slot context")
+
+    def score_ids(self, images: Sequence[Union[Image.Image, EncodedImage]], prompts: Sequence[Sequence[int]],
+                  continuations: Sequence[Sequence[int]], share_prefix: bool = False, variant: Optional[str] = None):
+        """Score GIVEN continuations: returns ``(logprobs, ranks)``, one list per row with one entry per token of
+        ``continuations[i]`` -- the values ``batch_generate_ids(..., return_logprobs=True)`` attaches to a token it generates,
+        for the tokens the caller supplies.  ``logprobs[i][j]`` is log softmax of the model's logits after
+        (images[i], prompts[i], continuations[i][:j]) at continuations[i][j]: the model's OWN distribution at temperature 1,
+        untruncated, with ``answer_id`` left out from the second token on as generation leaves it out -- not a tempered or
+        top-p-renormalised one.  ``ranks[i][j]`` counts the tokens ahead of it in argmax order (0: greedy decoding picks it).
+
+        No decode step runs: row i prefills ``prompts[i] + continuations[i][:-1]`` after its image prefix exactly as a prompt
+        is prefilled (one pass per sequence length; ``share_prefix``: rows of the same image object read one copy of its
+        prefix, bit-equal to the copy path; a LoRA ``variant`` takes the copy path), the hidden rows of the decisions are
+        gathered compactly, lm_head runs over them in launches of <= 64 rows (the decode-regime kernels whatever the call's
+        size: a row's values do not depend on what else is scored) and ONE md_token_logprobs launch reduces every row.  The
+        KV slots used are scratch, as in any batch call.  ValueError, before any device work: an empty prompt or
+        continuation, lists of different lengths, prefix + prompt + continuation beyond ``max_context``, the fp8 modes."""
+        self._check_score_args(images, prompts, continuations)
+        conts = [[int(t) for t in c] for c in continuations]
+        seqs = [[int(t) for t in p] + c[:-1] for p, c in zip(prompts, conts)]
+        tk, d = self.config.tokenizer, self.config.text.dim
+        lora = self._lora({"variant": variant})
+        with torch.inference_mode():
+            passes: list = []  # (r0, r1, hidden [r1-r0, T, D]) per prefill pass, rows in slot order
+            sink = lambda r0, r1, h: passes.append((r0, r1, h))
+            if share_prefix and self._shares_prefix(lora):
+                order = self._prepare_sequences_shared(list(images), seqs, hidden_sink=sink)[0]
+            else:
+                if share_prefix:  # the copy path over each distinct image's EncodedImage
+                    images = self._encode_distinct(images, {"variant": variant})
+                order = self._prepare_sequences(list(images), seqs, rows=_Rows(lora=lora), fuse=True, hidden_sink=sink)[0]
+            # row (j, k) of the compact table: decision k of slot j, the hidden row at offset len(prompt) - 1 + k of its
+            # sequence -- the last len(continuation) rows of the pass
+            parts, targets, suppress, span = [], [], [], {}
+            for r0, r1, h in passes:
+                t_len, idx = h.shape[1], []
+                for j in range(r0, r1):
+                    c = conts[order[j]]
+                    idx += [(j - r0) * t_len + t_len - len(c) + k for k in range(len(c))]
+                    span[order[j]] = (len(targets), len(targets) + len(c))
+                    targets += c
+                    suppress += [0] + [1] * (len(c) - 1)  # decision 0 is the prompt pass's: unsuppressed (moondream.py:313-318)
+                parts.append(h.reshape(-1, d).index_select(0, self._h2d(torch.tensor(idx, dtype=torch.int64))))
+            hidden = torch.cat(parts).unsqueeze(1)  # [R, 1, D]
+            r = hidden.shape[0]
+            logits = torch.empty(r, self.config.text.vocab_size, dtype=BF16, device=self._device)
+            for i0 in range(0, r, 64):
+                self._lm_head(hidden[i0 : i0 + 64], out=logits[i0 : i0 + 64])
+            tab = self._h2d(torch.tensor([targets, suppress], dtype=torch.int32))
+            lp = torch.empty(r, dtype=torch.float32, device=self._device)
+            rk = torch.empty(r, dtype=torch.int32, device=self._device)
+            self._token_logprobs(logits, tab[0], tk.answer_id, lp, rk, suppress_rows=tab[1])
+            packed = torch.stack([lp.view(torch.int32), rk]).cpu().numpy()  # one copy to the host
+        lp_h, rk_h = packed[0].view(np.float32).tolist(), packed[1].tolist()
+        n = len(conts)
+        return [lp_h[span[i][0] : span[i][1]] for i in range(n)], [rk_h[span[i][0] : span[i][1]] for i in range(n)]
 
     # ------------------------------------------------------ pipelined batches
     def _streams(self):
@@ -2249,6 +2413,28 @@ class MoondreamModel:
         enc = self.encode_image(image, settings)
         ids = self.batch_generate_ids([enc] * len(prompts), prompts, share_prefix=True, **self._sampling_kwargs(settings))
         return [{"answer": self.tokenizer.decode(s)} for s in ids]
+
+    def query_choices(self, image, question: str, choices: Sequence[str], settings: Optional[dict] = None) -> dict:
+        """Multiple choice: which of ``choices`` the model prefers as the answer to ``question`` about ONE image.  The image is
+        encoded once; one row per choice over a single copy of its KV prefix (``score_ids`` with ``share_prefix``; a LoRA
+        ``variant`` in ``settings`` takes the copy path, as in ``query_many``).  Every row's prompt is ``query``'s, its
+        continuation the choice's tokens followed by ``eos_id`` -- a choice is scored as a COMPLETE answer.  No token is
+        generated.  Returns ``{"logprobs": [sum per choice], "mean_logprobs": [sum / n_tokens], "per_token": [[..], ..],
+        "best": argmax of logprobs, "best_normalized": argmax of mean_logprobs}`` (ties: the first choice).  The
+        log-probabilities are ``score_ids``': the model's own distribution at temperature 1, untruncated."""
+        choices = list(choices)
+        if not choices:
+            raise ValueError("query_choices: no choices")
+        prompt = self._query_prompts([question])[0]
+        eos = self.config.tokenizer.eos_id
+        conts = [list(self.tokenizer.encode(c).ids) + [eos] for c in choices]
+        enc = self.encode_image(image, settings)
+        n = len(conts)
+        per_token, _ = self.score_ids([enc] * n, [prompt] * n, conts, share_prefix=True, variant=(settings or {}).get("variant"))
+        sums = [math.fsum(p) for p in per_token]
+        means = [s_ / len(p) for s_, p in zip(sums, per_token)]
+        return {"logprobs": sums, "mean_logprobs": means, "per_token": per_token,
+                "best": max(range(n), key=lambda i: (sums[i], -i)), "best_normalized": max(range(n), key=lambda i: (means[i], -i))}
 
     def detect_many(self, image, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
         """``detect`` of many objects in ONE image over a single copy of its KV prefix.  Element i ==
