@@ -11,16 +11,24 @@ it, and the model with ONE key wrongly admitted or wrongly dropped is outside it
 And for the fp8 tile GEMM's references, util.gemm_f8_exact and util.compare_f8_elementwise: a float32 model of gemm_f8_kernel's
 arithmetic (64-wide K slices, the fp32 scale, the FMA with the bias, bf16 rounding, the GELU in its sigmoid form, the residual's
 second rounding, e4m3 rounding) is inside the intervals, and one dropped K element, one column that reads its neighbour's
-wscale and one bias taken from the next column are outside them, in the affected elements only."""
+wscale and one bias taken from the next column are outside them, in the affected elements only.
+
+And for the weight stream's instruments (tests/test_gemm_wstream_exact_gpu.py, util.wstream_exact): a float32 model of
+gemm_fp8w_kernel (two K halves of every 128-step summed apart and added in a fixed order, the fp32 scale, the bias add) and a
+chunked one with another association are inside the intervals; a product dropped in the last row, a channel that reads its
+neighbour's scale, a 128-step that reads the next step's (scale, zero), a single-rounding dequantisation in one nibble position
+and a step counted by two slices are each refused by the part that is meant to see them; the integer probe's headroom holds
+for every case of the GPU list."""
 import math
 
 import numpy as np
 import pytest
 import torch
 
+import test_gemm_wstream_exact_gpu as WS
 from test_attention_exact_gpu import DEC_CTX, PROBES, prefill_geometry, visibility
-from util import (attention_excess, compare_attention_elementwise, compare_elementwise, compare_f8_elementwise, elementwise_excess,
-                  f8_excess, gemm_f8_exact, round_to_bf16)
+from util import (attention_excess, compare_attention_elementwise, compare_elementwise, compare_f8_elementwise, dequantize_int4_single_rounding,
+                  elementwise_excess, f8_excess, gemm_f8_exact, int4_codes, pack_int4, quantize_int4, round_to_bf16, wstream_exact)
 
 BF16 = torch.bfloat16
 SHAPES = [(128, 2048, 3584), (100, 8192, 2048), (65, 704, 256), (97, 1024, 1000)]
@@ -427,3 +435,213 @@ def test_exact_probe_arithmetic_is_exact_in_fp32_for_every_shape_of_the_gpu_list
             compare_f8_elementwise(f"probe model k={k}", got, exact, mag, T.pad64(k), exact_acc=True)
     finally:
         T.DEV = old
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# md_gemm_fp8w: wstream_exact and the probes of tests/test_gemm_wstream_exact_gpu.py
+# ---------------------------------------------------------------------------------------------------------------------
+WS_SHAPE = (64, 2048, 256)   # the shape at which the rel-rms tolerances let these mutations pass
+U23 = 2.0 ** -23
+
+
+def ws_operands(fmt, m=WS_SHAPE[0], k=WS_SHAPE[1], n=WS_SHAPE[2]):
+    layer = WS.random_layer(fmt, k, n, "cpu")
+    g = WS.gen("cpu", 4, fmt, m, k, n)
+    a = WS.random_activations(m, k, "cpu", g)
+    a[-1, -1] = math.copysign(max(1.0, abs(float(a[-1, -1]))), float(a[-1, -1]))   # the product the mutation drops carries a sigma
+    bias = WS.random_bias(layer.n_pad, n, "cpu", g)
+    seen = torch.zeros(m, layer.k_pad, dtype=BF16)
+    seen[:, :k] = a
+    return layer, seen, bias
+
+
+def ws_acc(a, q, order="kernel"):
+    """The fp32 accumulator of fp8w_body.  "kernel": the two 64-wide halves of every 128-step summed apart, step after step, then
+    first half + second half.  "chunked": 64-wide chunks from the last to the first into ONE accumulator."""
+    af, qf = a.float(), q.float()
+    k = af.shape[1]
+    part = lambda c: af[:, c * 64 : (c + 1) * 64] @ qf[:, c * 64 : (c + 1) * 64].t()
+    if order == "chunked":
+        acc = torch.zeros(af.shape[0], qf.shape[0])
+        for c in reversed(range(k // 64)):
+            acc = acc + part(c)
+        return acc
+    halves = [torch.zeros(af.shape[0], qf.shape[0]) for _ in range(2)]
+    for s in range(k // 128):
+        for h in range(2):
+            halves[h] = halves[h] + part(2 * s + h)
+    return halves[0] + halves[1]
+
+
+def ws_model(a, q, scale, bias, order="kernel"):
+    sc = torch.ones(q.shape[0]) if scale is None else scale.float()
+    return (ws_acc(a, q, order) * sc + bias.float()).to(BF16)
+
+
+def ws_rejected(name, got, exact, mag, k_pad, region, least, **kw):
+    f8_rejected(name, got, exact, mag, k_pad, region, least, accum_u=U23, **kw)
+
+
+@pytest.mark.parametrize("fmt", WS.FORMATS, ids=WS.case_id)
+def test_wstream_bound_accepts_the_float32_kernel_model(fmt):
+    for m, k, n in [WS_SHAPE, (40, 704, 256) if fmt == WS.E4M3 else (40, 640, 256), (3, 8192, 128)]:
+        layer, a, bias = ws_operands(fmt, m, k, n)
+        exact, mag = wstream_exact(a, layer.q, layer.scale, bias)
+        assert exact.dtype == torch.float64 and bool((mag >= exact.abs()).all())
+        for order in ("kernel", "chunked"):
+            pre = ws_model(a, layer.q, layer.scale, bias, order)
+            compare_f8_elementwise(f"wstream model {WS.FMT_NAME[fmt]} {m}x{k}x{n} {order}", pre, exact, mag, layer.k_pad, accum_u=U23)
+            gf = 8 * (n // 16) + 8
+            out = pre.clone()
+            out[:, gf:] = gelu_model(pre[:, gf:])
+            compare_f8_elementwise(f"wstream model gelu {WS.FMT_NAME[fmt]} {m}x{k}x{n} {order}", out, exact, mag, layer.k_pad, accum_u=U23, gelu_from=gf)
+
+
+@pytest.mark.parametrize("fmt", WS.FORMATS, ids=WS.case_id)
+def test_wstream_bound_rejects_the_last_product_dropped_in_the_last_row(fmt):
+    """|a w| of one product against half a bf16 spacing plus K u mag: at K = 2048 about half of the row's elements leave the
+    interval (the relative RMS over the whole output moves by 1.75e-3, inside the old 3e-3); at least a quarter is asserted."""
+    layer, a, bias = ws_operands(fmt)
+    m, n = a.shape[0], layer.n_pad
+    exact, mag = wstream_exact(a, layer.q, layer.scale, bias)
+    mut = a.clone()
+    mut[-1, WS_SHAPE[1] - 1] = 0
+    region = torch.zeros(m, n, dtype=torch.bool)
+    region[-1] = True
+    ws_rejected(f"dropped last product {WS.FMT_NAME[fmt]}", ws_model(mut, layer.q, layer.scale, bias), exact, mag, layer.k_pad, region, n // 4)
+
+
+def test_wstream_bound_and_one_hot_reject_a_neighbouring_channels_scale():
+    layer, a, bias = ws_operands(WS.E4M3)
+    m, n = a.shape[0], layer.n_pad
+    exact, mag = wstream_exact(a, layer.q, layer.scale, bias)
+    ratio = (layer.scale[1:] / layer.scale[:-1] - 1).abs()
+    col = int(ratio.argmax())
+    assert float(ratio[col]) >= 0.03
+    sc = layer.scale.clone()
+    sc[col] = layer.scale[col + 1]
+    region = torch.zeros(m, n, dtype=torch.bool)
+    region[:, col] = True
+    ws_rejected("neighbour's scale", ws_model(a, layer.q, sc, bias), exact, mag, layer.k_pad, region, m // 2)
+    # the one-hot probe compares bf16(q * scale): most of the channel's weights differ
+    wrong = (layer.q[col] * sc[col]).to(BF16)
+    assert float((wrong != layer.weight[col]).double().mean()) > 0.5
+
+
+def int4_triple(k, n):
+    w = torch.randn(n, k, generator=WS.gen("cpu", 1, WS.INT4, k, n)) / math.sqrt(k)
+    return quantize_int4(w, zero_shift=0.3)
+
+
+def test_wstream_bound_and_one_hot_reject_the_next_steps_qparams():
+    """One channel, one 128-step dequantised with the (scale, zero) of the step after it."""
+    m, k, n = WS_SHAPE
+    layer, a, bias = ws_operands(WS.INT4)
+    packed, scale, zero = int4_triple(k, n)
+    assert torch.equal(WS.dequantize_int4(packed, scale, zero, n), layer.weight[:n])
+    steps = k // 128
+    dz = (zero.reshape(n, steps)[:, 1:] - zero.reshape(n, steps)[:, :-1]).abs()
+    col, step = divmod(int(dz.argmax()), steps - 1)
+    s_mut, z_mut = scale.clone(), zero.clone()
+    s_mut[col * steps + step], z_mut[col * steps + step] = scale[col * steps + step + 1], zero[col * steps + step + 1]
+    w_mut = WS.dequantize_int4(packed, s_mut, z_mut, n)
+    differ = w_mut != layer.weight[:n]
+    assert bool(differ.any()) and not bool(differ[:, : step * 128].any()) and not bool(differ[:, (step + 1) * 128 :].any())
+    assert int(differ.any(1).sum()) == 1 and bool(differ[col].any()), "the one-hot probe sees it, in that channel and step only"
+    exact, mag = wstream_exact(a, layer.q, None, bias)
+    region = torch.zeros(m, layer.n_pad, dtype=torch.bool)
+    region[:, col] = True
+    q_mut = layer.q.clone()
+    q_mut[:n] = w_mut
+    ws_rejected("next step's qparams", ws_model(a, q_mut, None, bias), exact, mag, layer.k_pad, region, m // 2)
+
+
+def test_one_hot_probe_sees_a_single_rounding_in_one_nibble_position():
+    m, k, n = WS_SHAPE
+    packed, scale, zero = int4_triple(k, n)
+    double, single = WS.dequantize_int4(packed, scale, zero, n), dequantize_int4_single_rounding(packed, scale, zero, n)
+    assert float((double != single).double().mean()) >= 0.10
+    for j in range(8):
+        mut = double.clone()
+        mut[:, j::8] = single[:, j::8]
+        differ = mut != double
+        print(f"single rounding in nibble {j}: {int(differ.sum())} of {differ.numel()} weights differ")
+        assert int(differ.sum()) >= 1 and not torch.equal(mut, double)
+        assert float(differ[:, j::8].double().mean()) >= 0.10 and int(differ.sum()) == int(differ[:, j::8].sum())
+
+
+def test_int4_helpers_round_trip():
+    q = torch.randint(0, 16, (6, 256), generator=torch.Generator().manual_seed(3)).to(torch.uint8)
+    scale, zero = torch.rand(6, 2) + 0.5, torch.rand(6, 2) * 15
+    packed, s, z = pack_int4(q, scale, zero)
+    assert torch.equal(int4_codes(packed).reshape(6, 256), q) and tuple(s.shape) == tuple(z.shape) == (12, 1)
+    want = ((q.float() - zero.repeat_interleave(128, 1)).to(BF16).float() * scale.repeat_interleave(128, 1)).to(BF16)
+    assert torch.equal(WS.dequantize_int4(packed, s, z, 6), want)
+
+
+@pytest.mark.parametrize("fmt", WS.FORMATS, ids=WS.case_id)
+def test_per_slice_check_rejects_a_step_counted_in_two_slices(fmt):
+    """The fp32 partials of the pair launch, slice by slice: the clean model passes; slice 0 running one 128-step into slice 1
+    is refused with random operands and differs from the exact sum with the integer ones."""
+    m, (k, n) = 33, (2048, 256)
+    slices, per = WS.partial_slices(n, k)
+    assert (slices, per) == (2, 8)
+    (lo, hi), _ = WS.slice_ranges(k, slices, per)
+    for kind in ("random", "integer"):
+        layer = (WS.random_layer if kind == "random" else WS.probe_layer)(fmt, k, n, "cpu")
+        g = WS.gen("cpu", 6, fmt, m, k, n)
+        a = WS.random_activations(m, k, "cpu", g) if kind == "random" else WS.probe_activations(fmt, m, k, 0, "cpu", g)
+        sc = torch.ones(n) if layer.scale is None else layer.scale
+        w64 = layer.q.double() * sc.double()[:, None]
+        clean = ws_acc(a[:, lo:hi], layer.q[:, lo:hi]) * sc
+        twice = ws_acc(a[:, lo : hi + 128], layer.q[:, lo : hi + 128]) * sc
+        if kind == "random":
+            compare_elementwise(f"slice model {WS.FMT_NAME[fmt]}", clean, a[:, lo:hi], w64[:, lo:hi], None, rounded=False)
+            with pytest.raises(AssertionError, match="exceed the per-element bound"):
+                compare_elementwise(f"step in two slices {WS.FMT_NAME[fmt]}", twice, a[:, lo:hi], w64[:, lo:hi], None, rounded=False)
+            bad = elementwise_excess(twice, a[:, lo:hi], w64[:, lo:hi], None, rounded=False) > 0
+            assert float(bad.double().mean()) > 0.9
+        else:
+            exact = a[:, lo:hi].double() @ w64[:, lo:hi].t()
+            assert torch.equal(clean.double(), exact) and not torch.equal(twice.double(), exact)
+
+
+def test_wstream_integer_probe_is_exact_in_fp32_for_every_case_of_the_gpu_list():
+    """probe_headroom for every launch of the GPU file, the stated slice splits against the host rule and the library, and on
+    small shapes the claim itself: the float32 model equals the rounded float64 value bit for bit in both associations."""
+    import ctypes as C
+
+    from moondream_amd import _lib
+
+    for case, fmt in WS.CASE_FORMATS:
+        for shift in (0, WS.probe_a_shift(fmt, case.k)):
+            WS.probe_headroom(fmt, WS.pad128(case.k), shift)
+        assert case.gelu_from() % 8 == 0 and 0 < case.gelu_from() < case.n and case.gelu_from() % 32 != 0
+    lib = _lib.load()
+    for pair in WS.PAIRS:
+        for p in pair:
+            for fmt in WS.FORMATS:
+                WS.probe_headroom(fmt, p.k, 0)
+            assert WS.partial_slices(p.n, p.k) == (p.slices, p.per)
+            st = _lib.MdLinearFp8(None, None, None, p.n, p.k, WS.pad64(p.n), p.k, WS.E4M3)
+            assert int(lib.md_gemm_fp8w_partial_slices(C.byref(st))) == p.slices
+            ranges = WS.slice_ranges(p.k, p.slices, p.per)
+            assert [hi - lo for lo, hi in ranges][:-1] == [p.per * 128] * (p.slices - 1) and ranges[-1][1] == p.k
+    assert any(len({hi - lo for lo, hi in WS.slice_ranges(p.k, p.slices, p.per)}) > 1 for pair in WS.PAIRS for p in pair)
+    with pytest.raises(AssertionError):
+        WS.probe_headroom(WS.E4M3, 16384, 0)          # 16384 * 4 * 448 + 3 needs more than 24 bits
+    for fmt in WS.FORMATS:
+        for m, k, n in [(9, 640, 72), (5, 1152, 64)]:
+            layer = WS.probe_layer(fmt, k, n, "cpu")
+            bias = WS.probe_bias(layer.n_pad, n, "cpu")
+            for shift in (0, WS.probe_a_shift(fmt, k)):
+                a = WS.probe_activations(fmt, m, k, shift, "cpu", WS.gen("cpu", 3, fmt, m, k, n))
+                exact, mag = wstream_exact(a, layer.q, layer.scale, bias)
+                for order in ("kernel", "chunked"):
+                    got = ws_model(a, layer.q, layer.scale, bias, order)
+                    assert torch.equal(got, exact.to(BF16)) and torch.equal(got.double(), round_to_bf16(exact))
+                    compare_f8_elementwise(f"wstream probe model {WS.FMT_NAME[fmt]} k={k}", got, exact, mag, layer.k_pad, exact_acc=True)
+                    off = got.clone()
+                    off.view(torch.int16)[m - 1, n - 1] += 1
+                    with pytest.raises(AssertionError, match="1 of"):
+                        compare_f8_elementwise("one bf16 step", off, exact, mag, layer.k_pad, exact_acc=True)

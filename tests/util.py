@@ -470,3 +470,47 @@ def quantize_int4(w, group=128, zero_shift=0.0):
     q = torch.clamp(torch.round(rows / scale + zero), 0, 15).to(torch.uint8)
     step = q.shape[0] // 2
     return (q[:step] << 4) | q[step:], scale, zero
+
+
+def int4_codes(packed: torch.Tensor) -> torch.Tensor:
+    """The nibbles of the checkpoint format as uint8 group rows [2 * packed.shape[0], 128]: high nibbles first (dequantize_int4)."""
+    return torch.cat([(packed & 0xF0) >> 4, packed & 0x0F], 0)
+
+
+def pack_int4(q: torch.Tensor, scale: torch.Tensor, zero: torch.Tensor, group=128):
+    """The inverse of int4_codes with given quantisation parameters: ``q`` uint8 [n, k] nibbles, ``scale`` / ``zero`` [n, k / group]
+    -> (packed, scale, zero) as quantize_int4 returns them, so that a test can choose every stored number itself."""
+    rows = q.to(torch.uint8).cpu().reshape(-1, group)
+    assert rows.shape[0] % 2 == 0 and tuple(scale.shape) == tuple(zero.shape) == (q.shape[0], q.shape[1] // group)
+    step = rows.shape[0] // 2
+    return (rows[:step] << 4) | rows[step:], scale.float().cpu().reshape(-1, 1), zero.float().cpu().reshape(-1, 1)
+
+
+def dequantize_int4_single_rounding(packed, scale, zero, out_features: int) -> torch.Tensor:
+    """NOT the checkpoint's weights: bf16((q - zero) * scale) with ONE rounding, the mistake a kernel makes that keeps q - zero
+    in fp32.  The tests use it as a mutation, and to show that their operands tell it from dequantize_int4's two roundings."""
+    w = ((int4_codes(packed).float() - zero.float()) * scale.float()).to(torch.bfloat16)
+    return w.reshape(out_features, -1)
+
+
+def wstream_exact(a: torch.Tensor, q: torch.Tensor, scale, bias, row_chunk: int = 8192):
+    """md_gemm_fp8w before its epilogue, in float64 from the operands the kernel sees with NO intermediate rounding:
+    ``exact = (A . q^T) * scale[n] + bias`` and ``mag``, the same expression over absolute values.  a [m, K] bf16 (may be a
+    strided view); q [n, K]: for the e4m3 stream the code VALUES (PackedLinearFp8.q) with ``scale`` [n] the fp32 per-channel
+    scale, for the int4 stream dequantize_int4's bf16 weight with ``scale`` None (= 1: the group scales are inside the
+    operand); bias [n] bf16 or None.  Evaluated on a's device in chunks of rows."""
+    dev = a.device
+    q64 = q.detach().to(dev).float().double()
+    n = q64.shape[0]
+    s64 = torch.ones(n, dtype=torch.float64, device=dev) if scale is None else scale.detach().to(dev).double()
+    b64 = torch.zeros(n, dtype=torch.float64, device=dev) if bias is None else bias.detach().to(dev).double()
+    assert a.dim() == 2 and q64.dim() == 2 and a.shape[1] == q64.shape[1] and s64.shape == b64.shape == (n,)
+    m = a.shape[0]
+    exact = torch.empty(m, n, dtype=torch.float64, device=dev)
+    mag = torch.empty_like(exact)
+    qt, qt_abs = q64.t().contiguous(), q64.abs().t().contiguous()
+    for r0 in range(0, m, row_chunk):
+        a64 = a[r0 : r0 + row_chunk].detach().double()
+        exact[r0 : r0 + row_chunk] = (a64 @ qt) * s64 + b64
+        mag[r0 : r0 + row_chunk] = (a64.abs() @ qt_abs) * s64.abs() + b64.abs()
+    return exact, mag
