@@ -461,38 +461,27 @@ class ContinuousEngine:
         request: (token,), or with ``logprobs`` (token, logprob, rank) of the same logits, unsuppressed like the pick."""
         import torch
 
+        from .decode_loop import Sampling
+
         m = self.model
-        out, lps, rks = [], [], []
-
-        def score(lg, picked):
-            if self.logprobs:
-                lp = torch.empty(lg.shape[0], dtype=torch.float32, device=m.device)
-                rk = torch.empty(lg.shape[0], dtype=torch.int32, device=m.device)
-                m._token_logprobs(lg, picked, -1, lp, rk)
-                lps.append(lp)
-                rks.append(rk)
-            out.append(picked)
-
-        for i0 in range(0, len(reqs), 64):
+        k = len(reqs)
+        first = torch.empty(k, dtype=torch.int32, device=m.device)
+        lp = torch.empty(k, dtype=torch.float32, device=m.device) if self.logprobs else None
+        rk = torch.empty(k, dtype=torch.int32, device=m.device) if self.logprobs else None
+        for i0 in range(0, k, 64):
             part = reqs[i0 : i0 + 64]
-            lg = m._lm_head(hidden[i0 : i0 + len(part)])
-            if all(r.temperature == 0 for r in part):
-                score(lg, m._pick(lg, 0.0, 0.0))
-                continue
-            # one H2D copy of [temperature | top_p | uniform] rows; a greedy request draws nothing
-            k = len(part)
-            st = torch.zeros(3, k, dtype=torch.float32)
-            st[0] = torch.tensor([r.temperature for r in part], dtype=torch.float32)
-            st[1] = torch.tensor([r.top_p for r in part], dtype=torch.float32)
-            for j, r in enumerate(part):
-                if r.temperature != 0:
-                    st[2, j] = self._uniforms(r, 1)[0]
-            st_d = m._h2d(st)
-            score(lg, m._pick_rows(lg, st_d[0], st_d[1], -1, st_d[2]))
-        first = torch.cat(out).tolist()
+            i1 = i0 + len(part)
+            pick = st_d = None
+            if any(r.temperature != 0 for r in part):
+                # one H2D copy of [temperature | top_p | uniform] rows; a greedy request draws nothing
+                draws = [float(self._uniforms(r, 1)[0]) if r.temperature != 0 else 0.0 for r in part]
+                st_d = m._h2d(torch.tensor([[r.temperature for r in part], [r.top_p for r in part], draws], dtype=torch.float32))
+                pick = Sampling(st_d[0], st_d[1])
+            first[i0:i1] = m._first_token(m._lm_head(hidden[i0:i1]), pick, uniforms=st_d[2] if pick is not None else None,
+                                          logprobs=(lp[i0:i1], rk[i0:i1]) if self.logprobs else None)
         if not self.logprobs:
-            return [(f,) for f in first]
-        return list(zip(first, torch.cat(lps).tolist(), torch.cat(rks).tolist()))
+            return [(f,) for f in first.tolist()]
+        return list(zip(first.tolist(), lp.tolist(), rk.tolist()))
 
     def _admit(self, reqs: List[Request]) -> List[Tuple[int, int]]:
         """ViT over the admitted raw images as one batch, then the prefill into their slots with the choices of
@@ -588,6 +577,8 @@ class ContinuousEngine:
     def _step(self, plan: ChunkPlan) -> np.ndarray:
         import torch
 
+        from .decode_loop import DecodeChunk, Sampling, run_chunk
+
         m = self.model
         if m._kv_k.data_ptr() != self._kv_ptr:
             raise RuntimeError("the KV slab was reallocated during a continuous-batching run")
@@ -621,48 +612,25 @@ class ContinuousEngine:
                     k = min(n, r.remaining)
                     uh[:k, r_idx] = self._uniforms(r, k).numpy()
             u_dev.copy_(u_host, non_blocking=True)
-        u2 = u_dev[: c * B].view(c, B)
-        temp_d, top_p_d = u_dev[c * B : c * B + B], u_dev[c * B + B :]
-        logits = m._decode_logits(B)
-        ws = m._workspace(self._decode_ws_bytes(B), 2)
-        kv = m._kv_struct(0)
-        answer_id = m.config.tokenizer.answer_id
-        step_logits = logits[:B]
-        with_lp = self.logprobs
-        if with_lp:
-            lp_words = self._logprob_buffers(B)
-            lp_d, rk_d = lp_words[0].view(torch.float32), lp_words[1]
+        lp_words = self._logprob_buffers(B) if self.logprobs else None
+        # step i's routing: row i of the slot table; a LoRA row in the chunk: the chunk's row-variant table with it
+        rows_of = lambda i: self._rows(slots_d[i], var_d if lora else None)
+        # a sampling row in the chunk: every row picks with its own settings (a greedy row its argmax again, an idle row
+        # nothing); the settings are device data, in the allocation of the uniforms
+        pick = Sampling(u_dev[c * B : c * B + B], u_dev[c * B + B :]) if sample else None
+        # (an idle or padding row's log-probability is never read: SlotScheduler.commit)
+        planes = (lp_words[0].view(torch.float32), lp_words[1]) if self.logprobs else None
+        chunk = DecodeChunk(B, hist, pos_d, rows_of, m.config.tokenizer.answer_id, self._decode_ws_bytes(B), pick,
+                            u_dev[: c * B].view(c, B), planes)
+        stream = torch.cuda.current_stream(m.device).cuda_stream if m.use_graphs else None
 
-        def step_rows(i):  # step i's row of the slot table; a LoRA row in the chunk: the chunk's row-variant table with it
-            return self._rows(slots_d[i], var_d if lora else None)
+        def below_cap():
+            return sum(1 for k in m._graphs if isinstance(k, tuple) and k and k[0] == "continuous" and k[1] == stream) < MAX_GRAPHS
 
-        def body():
-            for i in range(n):
-                m._decode_step(step_rows(i), hist[i], hist[i + 1], pos_d, B, answer_id, logits, ws, kv)
-                if sample:  # the step left its logits in ``logits``: every sampling row draws from them instead of the argmax it
-                    # wrote (a greedy row takes the same argmax again; an idle row keeps it)
-                    m._pick_rows(step_logits, temp_d, top_p_d, answer_id, u2[i], out=hist[i + 1])
-                if with_lp:  # targets = the step's tokens; an idle or padding row's value is never read (SlotScheduler.commit)
-                    m._token_logprobs(step_logits, hist[i + 1], answer_id, lp_d[i], rk_d[i])
-
-        if not m.use_graphs:
-            body()
-        else:
-            stream = torch.cuda.current_stream(m.device).cuda_stream
-            # (the bank's generation in the routing's key part: its ranks are launch shapes of the capture.  Of the sampling
-            # settings only "this chunk has a sampling launch": the values are device data, in the allocation of the uniforms)
-            key = ("continuous", stream, B, n, dev.data_ptr(), ws.data_ptr(), m._kv_k.data_ptr(), logits.data_ptr(), sample,
-                   u_dev.data_ptr()) + step_rows(0).key()
-            if with_lp:  # a chunk with the logprob launches is another graph; without them key and graph are unchanged
-                key += ("logprobs", lp_words.data_ptr())
-
-            def below_cap():
-                return sum(1 for k in m._graphs if isinstance(k, tuple) and k and k[0] == "continuous" and k[1] == stream) < MAX_GRAPHS
-
-            if m._replay_or_capture(key, body, may_capture=below_cap):
-                self.stats.graph_captures += 1
+        if run_chunk(m, chunk, n, "continuous", stream, below_cap):
+            self.stats.graph_captures += 1
         out = hist[1 : n + 1].cpu().numpy()  # the chunk's D2H copy of the ids (the lockstep loop syncs here too)
-        if not with_lp:
+        if lp_words is None:
             return out
         words = lp_words[:, :n].cpu().numpy()  # ... and one more of both planes
         return out, words[0].view(np.float32), words[1]

@@ -1,0 +1,104 @@
+"""What the lockstep loop (``MoondreamModel._decode_greedy_impl``) and the continuous engine (``ContinuousEngine._step``)
+share: the description of a chunk of consecutive decode steps over fixed buffers, and the one runner that launches it.
+``run_chunk`` holds the only step body of the package -- decode step, then the optional sampling pick, then the optional
+log-probability launch -- and the only decode graph key.  No torch here: the runner moves no data, it orders launches."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Any, Callable, Optional, Tuple
+
+
+@dataclass(frozen=True, eq=False)
+class Sampling:
+    """How tokens are sampled (``None`` where one is expected: greedy): the reference's temperature / top-p rule with one
+    uniform per (token, sequence).  Two floats are a whole call's settings: the uniforms come from ``generator`` (a device
+    generator; None: the device's default one) and row i draws the uniform of row ``row_perm[i]`` (device int64 [B]: the
+    shared-prefix rows see the draws of the copy path's row order).  Two device fp32 [B] tensors are every row's own
+    settings (md_sample_rows): temperature > 0 samples, 0 takes the argmax, < 0 leaves the row alone."""
+
+    temperature: Any
+    top_p: Any
+    generator: Any = None
+    row_perm: Any = None
+
+    @property
+    def per_row(self) -> bool:
+        return hasattr(self.temperature, "data_ptr")
+
+
+@dataclass(frozen=True, eq=False)
+class DecodeChunk:
+    """What ``n`` consecutive decode steps over ``b`` rows read and write, all at fixed addresses: step i consumes
+    ``tokens[i]`` and writes ``tokens[i + 1]`` (int32 [>= n + 1, b]); ``pos`` (int32 [b]) is advanced by the steps;
+    ``rows_of(i)`` is the routing of step i (``_Rows``; ``rows_of(0)`` stands for the chunk in the graph key: the others
+    differ in data at fixed addresses only).  ``pick`` None keeps each step's argmax; otherwise step i draws every row from
+    ``uniforms[i]`` (fp32 [>= n, b]) with the call's settings (``_pick``) or each row's own (``_pick_rows``).
+    ``logprobs`` = (fp32, int32) planes [>= n, b]: row i takes the log-probability and rank of the tokens of step i.
+    ``b1``: the single-sequence persistent kernel takes the steps (b = 1, greedy).  ``step(tok_in) -> logits``: the step
+    made from its pieces instead of the fused one (a LoRA adapter; eager only, its pick writes ``tokens[i + 1]``)."""
+
+    b: int
+    tokens: Any
+    pos: Any
+    rows_of: Callable[[int], Any]
+    suppress_id: int
+    ws_bytes: int = 0
+    pick: Optional[Sampling] = None
+    uniforms: Any = None
+    logprobs: Optional[Tuple[Any, Any]] = None
+    b1: bool = False
+    step: Optional[Callable[[Any], Any]] = None
+
+
+def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_stream: Optional[int] = None,
+              may_capture: Optional[Callable[[], bool]] = None) -> bool:
+    """Run steps 0 .. n-1 of ``chunk`` on ``model``.  ``capture_stream`` None: eagerly.  Otherwise the handle of the current
+    stream: the chunk is replayed from the graph captured for it on that stream, or, first, run eagerly and captured
+    (``model._replay_or_capture``; ``may_capture`` as it takes it).  The key starts (``tag``, stream) and names everything the
+    launches bake in.  Returns True when it captured.  Of the model it uses _decode_logits, _workspace, _kv_struct,
+    _decode_step, _decode_step_b1, _pick, _pick_rows, _token_logprobs and _replay_or_capture."""
+    c = chunk
+    pieces = c.step is not None
+    assert not (pieces and (capture_stream is not None or c.b1))
+    assert not c.b1 or (c.b == 1 and c.pick is None)
+    if not pieces:
+        logits = model._decode_logits(c.b)
+        ws = model._workspace(c.ws_bytes, 2)
+        kv = model._kv_struct(c.rows_of(0).slot0)
+        left = logits[: c.b]  # where every fused step (the single-sequence kernel too) leaves its logits
+    lp, rk = c.logprobs if c.logprobs is not None else (None, None)
+    by_row = c.pick is not None and c.pick.per_row
+
+    def body():
+        for i in range(n):
+            tok_in, tok_out = c.tokens[i], c.tokens[i + 1]
+            if c.b1:
+                model._decode_step_b1(tok_in, tok_out, c.pos, c.suppress_id, logits, ws, kv)
+            elif not pieces:
+                model._decode_step(c.rows_of(i), tok_in, tok_out, c.pos, c.b, c.suppress_id, logits, ws, kv)
+            lg = c.step(tok_in) if pieces else left
+            # a fused step wrote its argmax to tok_out: a pick draws from the logits it left instead (of per-row settings,
+            # a greedy row takes the same argmax again and an idle row keeps what is there)
+            if by_row:
+                model._pick_rows(lg, c.pick.temperature, c.pick.top_p, c.suppress_id, c.uniforms[i], out=tok_out)
+            elif c.pick is not None:
+                model._pick(lg, c.pick.temperature, c.pick.top_p, c.suppress_id, c.pick.generator,
+                            uniforms=c.uniforms[i] if c.uniforms is not None else None, out=tok_out)
+            if lp is not None:  # targets = the step's tokens
+                model._token_logprobs(lg, tok_out, c.suppress_id, lp[i], rk[i])
+
+    if capture_stream is None:
+        body()
+        return False
+    # a graph is replayed only on the stream it was captured for.  Of per-row settings and uniforms only their addresses
+    # are baked in (the values are device data); scalar settings are launch arguments.  The e4m3 KV copy decides the
+    # attention kernel a step bakes in; the routing's part carries the bank's generation (its ranks are launch shapes).
+    if by_row:
+        pick = ("rows", c.pick.temperature.data_ptr(), c.pick.top_p.data_ptr())
+    else:
+        pick = None if c.pick is None else (float(c.pick.temperature), float(c.pick.top_p))
+    key = (tag, capture_stream, c.b, n, c.suppress_id, c.tokens.data_ptr(), c.pos.data_ptr(), ws.data_ptr(), kv.k, kv.k8 or 0,
+           logits.data_ptr(), c.b1, pick, c.uniforms.data_ptr() if c.uniforms is not None else 0) + c.rows_of(0).key()
+    if lp is not None:  # a chunk with the logprob launches is another graph; without them key and graph are unchanged
+        key += ("logprobs", lp.data_ptr(), rk.data_ptr())
+    return model._replay_or_capture(key, body, may_capture=may_capture)

@@ -29,6 +29,7 @@ from PIL import Image
 
 from . import _lib
 from .config import MoondreamConfig
+from .decode_loop import DecodeChunk, Sampling, run_chunk
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
 from .lora import variant_state_dict
@@ -687,6 +688,22 @@ class MoondreamModel:
             rows.step_entry,
         )
 
+    def _decode_step_b1(self, tok_in: torch.Tensor, tok_out: torch.Tensor, pos_buf: torch.Tensor, suppress_id: int,
+                        logits: torch.Tensor, ws: torch.Tensor, kv: _lib.MdKvCache):
+        """``_decode_step`` of ONE sequence, greedy, plain contiguous routing, as one persistent launch (csrc/decode_b1.hip)."""
+        st = self.lib.md_decode_step_b1(
+            C.byref(self.w.text), tok_in.data_ptr(), tok_out.data_ptr(), pos_buf.data_ptr(), C.byref(kv), suppress_id,
+            logits.data_ptr(), self.config.text.vocab_size, ws.data_ptr(), ws.numel(), self._b1_sync.data_ptr(), self._stream())
+        _lib.check(st, "md_decode_step_b1")
+
+    def _step_from_pieces(self, x: torch.Tensor, pos: Union[int, Sequence[int]], rows: Union[int, _Rows] = 0,
+                          pos_dev: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One decode step from its pieces, for what the fused step does not serve (a LoRA adapter, an embedding that is not
+        a token's, a host decision per token): ``x`` token ids (integer [B, 1]) or embeddings [B, 1, D] -> decoder at ``pos``
+        -> lm_head.  Returns (hidden [B, 1, D], logits [B, V]); the pick is the caller's."""
+        hidden = self._text_forward(x if x.is_floating_point() else self._embed(x), pos, rows, pos_dev=pos_dev)
+        return hidden, self._lm_head(hidden)
+
     def _lm_head(self, hidden: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """hidden [B,T,D] -> logits of the last token [B,V] (into ``out`` when given).  reference: text.py:163-167."""
         b, t, d = hidden.shape
@@ -1114,6 +1131,22 @@ class MoondreamModel:
             "md_token_logprobs",
         )
 
+    def _first_token(self, logits: torch.Tensor, pick: Optional[Sampling] = None, row_perm=None,
+                     uniforms: Optional[torch.Tensor] = None, logprobs=None) -> torch.Tensor:
+        """The first generated token of every row, int32 [B], from its prompt pass's logits [B, V]: the argmax (``pick``
+        None), a draw with the call's settings (``row_perm``: the draw order of these rows) or with each row's own (and
+        ``uniforms`` fp32 [B]).  Nothing is suppressed (moondream.py:313-318).  ``logprobs`` = (fp32 [B], int32 [B]): filled
+        with the token's log-probability and rank, unsuppressed like the pick."""
+        if pick is None:
+            first = self._pick(logits, 0.0, 0.0)
+        elif pick.per_row:
+            first = self._pick_rows(logits, pick.temperature, pick.top_p, -1, uniforms)
+        else:
+            first = self._pick(logits, pick.temperature, pick.top_p, -1, pick.generator, row_perm=row_perm)
+        if logprobs is not None:
+            self._token_logprobs(logits, first, -1, *logprobs)
+        return first
+
     # ---------------------------------------------------------- batched engine
     def _prefill_prompts(self, prompts: Sequence[Sequence[int]], pos: int, rows: Union[int, _Rows] = 0, prompt_embs=None,
                          last_only: bool = False):
@@ -1127,16 +1160,13 @@ class MoondreamModel:
         return self._lm_head(hidden), hidden, pos + ids.shape[1]
 
     def _decode_greedy(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
-                       rows: Union[int, _Rows] = 0, eos_id: Optional[int] = None, check_every: int = 16, allow_b1: bool = True,
-                       temperature: float = 0.0, top_p: float = 0.0, generator: Optional[torch.Generator] = None,
-                       row_perm: Optional[torch.Tensor] = None, first_logprobs=None):
-        """``_decode_greedy_impl`` plus the safety net of the persistent single-sequence kernel: its software grid barriers
-        need every workgroup resident; if one times out (the GPU was shared with another persistent kernel) the kernel
-        raises an error word and finishes with garbage.  That state is fully re-initialised by decoding the same tokens
-        again (K / V rows at positions >= ``pos``, the id history, the position buffer), so the call is repeated on the
-        batched kernels and the persistent kernel is switched off for this model."""
-        hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, rows, eos_id, check_every, allow_b1,
-                                        temperature, top_p, generator, row_perm, first_logprobs)
+                       rows: Union[int, _Rows] = 0, eos_id: Optional[int] = None, **kw):
+        """``_decode_greedy_impl`` (``kw``: its further arguments) plus the safety net of the persistent single-sequence
+        kernel: its software grid barriers need every workgroup resident; if one times out (the GPU was shared with another
+        persistent kernel) the kernel raises an error word and finishes with garbage.  That state is fully re-initialised by
+        decoding the same tokens again (K / V rows at positions >= ``pos``, the id history, the position buffer), so the call
+        is repeated on the batched kernels and the persistent kernel is switched off for this model."""
+        hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, rows, eos_id, **kw)
         if self._b1_used:
             torch.cuda.current_stream(self._device).synchronize()
             if int(self._b1_sync[64 * 11]) != 0:
@@ -1148,25 +1178,22 @@ class MoondreamModel:
                 self._graphs.clear()
                 warnings.warn("md_decode_step_b1: a grid barrier timed out (GPU shared with another persistent kernel?); "
                               "repeating the decode on the batched kernels and disabling the single-sequence kernel", RuntimeWarning)
-                hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, rows, eos_id, check_every, False,
-                                                first_logprobs=first_logprobs)
+                hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, rows, eos_id, **{**kw, "allow_b1": False})
         return hist
 
     def _decode_greedy_impl(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
                             rows: Union[int, _Rows] = 0, eos_id: Optional[int] = None, check_every: int = 16,
-                            allow_b1: bool = True, temperature: float = 0.0, top_p: float = 0.0,
-                            generator: Optional[torch.Generator] = None, row_perm: Optional[torch.Tensor] = None,
-                            first_logprobs=None):
-        """Device-resident decode loop: returns int32 [steps+1, B] (row 0 = ``first``).  ``temperature`` 0: greedy.  Otherwise every
+                            allow_b1: bool = True, sampling: Optional[Sampling] = None, first_logprobs=None):
+        """Device-resident decode loop: returns int32 [steps+1, B] (row 0 = ``first``).  ``sampling`` None: greedy.  Otherwise every
         step draws each sequence's token with the reference's rule (moondream.py:521-528: softmax(logits / T), _apply_top_p,
         multinomial) from the step's own logits on the device (md_sample_top_p), with one uniform per (step, sequence) taken
-        UP FRONT from torch's generator -- no host round trip per token, replayable from a hipGraph.
+        UP FRONT from torch's generator -- no host round trip per token, replayable from a hipGraph -- and permuted by
+        ``sampling.row_perm``, so that sampled rows in another order see the draws of the copy path.
         reference: the generator of moondream.py:471-530 without its per-token host sync.
         ``pos`` is the position of the next token, one int or one per sequence (sequences whose
         prompts differ in length decode in the same lockstep batch).
-        With ``compile()`` the steps are replayed from a captured hipGraph in chunks.
-        ``rows``: the routing of every step (``_Rows``); ``row_perm``: row i draws the uniforms of row row_perm[i], so that
-        sampled rows in another order see the draws of the copy path.
+        The steps run in chunks (``run_chunk``): eagerly over the history itself, or with ``compile()`` replayed from a
+        captured hipGraph over the fixed buffers of the chunk's shape.  ``rows``: the routing of every step (``_Rows``).
         ``first_logprobs`` = (logprob fp32 [B], rank int32 [B]) of ``first``: the loop also keeps the log-probability and rank
         of every token it picks (``_token_logprobs`` on the logits the step leaves, one launch after the step's pick, inside
         the captured graph) and returns (hist, logprobs fp32 [steps+1, B], ranks int32 [steps+1, B]).  No id changes."""
@@ -1191,130 +1218,88 @@ class MoondreamModel:
         if max_tokens == 0:
             return done(1)
         pos_base = self._h2d(torch.tensor(pos_list, dtype=torch.int32))
-        sample = temperature != 0
-        uniforms = (torch.rand(max_tokens, b, device=self._device, dtype=torch.float32, generator=generator) if sample else None)
-        if sample and row_perm is not None:
-            uniforms = uniforms[:, row_perm].contiguous()
-
-        def all_done(upto):
-            return eos_id is not None and bool((hist[: upto + 1] == eos_id).any(dim=0).all())
-
-        steps = 0
+        uniforms = None
+        if sampling is not None:
+            uniforms = torch.rand(max_tokens, b, device=self._device, dtype=torch.float32, generator=sampling.generator)
+            if sampling.row_perm is not None:
+                uniforms = uniforms[:, sampling.row_perm].contiguous()
+        pos_t = pos_base.clone()  # what eager steps advance
         if rows.lora is not None:
-            # LoRA variant: the fused device-resident step has no side path; same loop from its pieces
-            # (embed -> decoder with the low-rank pairs -> lm_head -> suppress + argmax), still without a host sync per token
-            pos_t, pos_h = pos_base.clone(), list(pos_list)
-            while steps < max_tokens:
-                emb = self._embed(hist[steps].reshape(b, 1))
-                h = self._text_forward(emb, pos_h, rows, pos_dev=pos_t)
-                lg = self._lm_head(h)
-                hist[steps + 1] = self._pick(lg, temperature, top_p, suppress_id, generator)
-                if with_lp:
-                    self._token_logprobs(lg, hist[steps + 1], suppress_id, lp_hist[steps + 1], rk_hist[steps + 1])
-                pos_t.add_(1)
-                pos_h = [p + 1 for p in pos_h]
-                steps += 1
-                if check_every and steps % check_every == 0 and all_done(steps):
-                    break
-            return done(steps + 1)
+            # LoRA variant: the fused device-resident step has no side path; the same loop with the step from its pieces, eager,
+            # still without a host sync per token.  Its pick (the argmax too) is a launch of its own, and a sampled one draws
+            # AGAIN, per step, from the generator the unused ``uniforms`` above came from: odd, but these are the ids a sampled
+            # LoRA call has always returned, and this loop keeps them.
+            taken = 0
 
-        logits = self._decode_logits(b)
-        need = self._decode_ws_bytes(rows, b)
-        ws = self._workspace(need, 2)
-        kv = self._kv_struct(rows.slot0)
-        # one sequence, greedy, plain contiguous routing: the whole step as ONE persistent launch (csrc/decode_b1.hip) when the
-        # library says this model / cache / device fits its static limits and its grid can be co-resident; anything else
-        # decodes on the batched kernels.  Never from the pipelined engine (allow_b1 = False): a second stream's persistent
-        # GEMMs could keep workgroups of the grid off the chip and its software barriers would time out.
-        b1 = (b == 1 and allow_b1 and not sample and self.single_sequence_kernel and rows.plain and not bool(self.w.text.fp8)
-              and bool(self.lib.md_decode_step_b1_supported(C.byref(self.w.text), C.byref(kv))))
-        self._b1_used = b1
-        if b1:
-            if self._b1_sync is None:
-                self._b1_sync = torch.zeros(4096, dtype=torch.int32, device=self._device)
-            need = max(need, self.lib.md_decode_step_b1_workspace_bytes(C.byref(self.w.text)))
-            ws = self._workspace(need, 2)
-        step_logits = logits[:b]
+            def lora_step(tok_in):
+                nonlocal taken
+                if taken:
+                    pos_t.add_(1)
+                pos_h = [p + taken for p in pos_list]
+                taken += 1
+                return self._step_from_pieces(tok_in.reshape(b, 1), pos_h, rows, pos_dev=pos_t)[1]
 
-        def one_step(tok_in, tok_out, pos_buf, u_row=None, lp_row=None, rk_row=None):
-            step_pick(tok_in, tok_out, pos_buf, u_row)
-            if with_lp:  # the step (the single-sequence kernel too) left its logits in ``logits``; tok_out holds its pick
-                self._token_logprobs(step_logits, tok_out, suppress_id, lp_row, rk_row)
-
-        def step_pick(tok_in, tok_out, pos_buf, u_row):
+            chunk = DecodeChunk(b, hist, pos_t, lambda i: rows, suppress_id, pick=sampling or Sampling(0.0, 0.0), step=lora_step)
+            graphs, uniforms = False, None
+        else:
+            need = self._decode_ws_bytes(rows, b)
+            # one sequence, greedy, plain contiguous routing: the whole step as ONE persistent launch (csrc/decode_b1.hip) when the
+            # library says this model / cache / device fits its static limits and its grid can be co-resident; anything else
+            # decodes on the batched kernels.  Never from the pipelined engine (allow_b1 = False): a second stream's persistent
+            # GEMMs could keep workgroups of the grid off the chip and its software barriers would time out.
+            b1 = (b == 1 and allow_b1 and sampling is None and self.single_sequence_kernel and rows.plain and not bool(self.w.text.fp8)
+                  and bool(self.lib.md_decode_step_b1_supported(C.byref(self.w.text), C.byref(self._kv_struct(rows.slot0)))))
+            self._b1_used = b1
             if b1:
-                _lib.check(
-                    self.lib.md_decode_step_b1(
-                        C.byref(self.w.text), tok_in.data_ptr(), tok_out.data_ptr(), pos_buf.data_ptr(), C.byref(kv),
-                        suppress_id, logits.data_ptr(), t.vocab_size, ws.data_ptr(), ws.numel(), self._b1_sync.data_ptr(),
-                        self._stream(),
-                    ),
-                    "md_decode_step_b1",
-                )
-                return
-            self._decode_step(rows, tok_in, tok_out, pos_buf, b, suppress_id, logits, ws, kv)
-            if sample:  # the step left its logits [B, V] in ``logits``: draw from them instead of the argmax it wrote
-                self._pick(step_logits, temperature, top_p, suppress_id, uniforms=u_row, out=tok_out)
-
-        if not self.use_graphs:
-            pos_t = pos_base.clone()
-            while steps < max_tokens:
-                one_step(hist[steps], hist[steps + 1], pos_t, uniforms[steps] if sample else None,
-                         lp_hist[steps + 1] if with_lp else None, rk_hist[steps + 1] if with_lp else None)
-                steps += 1
-                if check_every and steps % check_every == 0 and all_done(steps):
-                    break
-            return done(steps + 1)
-
-        # ---- hipGraph path: one graph = `chunk` consecutive steps over fixed buffers
-        chunk = max(1, min(check_every or 16, max_tokens))
+                if self._b1_sync is None:
+                    self._b1_sync = torch.zeros(4096, dtype=torch.int32, device=self._device)
+                need = max(need, self.lib.md_decode_step_b1_workspace_bytes(C.byref(self.w.text)))
+            chunk = DecodeChunk(b, hist, pos_t, lambda i: rows, suppress_id, need, sampling, b1=b1)
+            graphs = self.use_graphs
+        # one graph = `per` consecutive steps over fixed buffers; eager chunks end where the all-done check is due
+        per = max(1, min(check_every or 16, max_tokens)) if graphs else (check_every or max_tokens)
+        stream = torch.cuda.current_stream(self._device).cuda_stream if graphs else None
+        steps = 0
         while steps < max_tokens:
-            n = min(chunk, max_tokens - steps)
-            # a graph is replayed only on the stream (context) it was captured for: the pipelined engine's
-            # decode stream and the default stream each keep their own captures
-            key = ("decode", b, n, suppress_id, ws.data_ptr(), self._kv_k.data_ptr(), logits.data_ptr(),
-                   torch.cuda.current_stream(self._device).cuda_stream, b1, float(temperature), float(top_p),
-                   # the e4m3 copy decides the attention kernel a step bakes in (enable_fp8 also clears the graphs)
-                   self._kv_k8.data_ptr() if self._kv8_scales is not None and self._kv_k8 is not None else 0) + rows.key()
-            if with_lp:  # a chunk with the logprob launches is another graph; without them the key and the graph are unchanged
-                key += ("logprobs",)
-            entry = self._graphs.get(key)
-            if entry is not None:
-                buf, pos_buf, u_buf, lp_buf, rk_buf = entry[1]
+            n = min(per, max_tokens - steps)
+            if graphs:
+                # the fixed buffers of this shape on this stream (the pipelined engine's decode stream and the default stream
+                # each have their own), refreshed before each replay; its graphs share them: a stream runs one chunk at a time
+                fixed = self.__dict__.setdefault("_chunk_bufs", {})
+                if (stream, b, n) not in fixed:
+                    zeros = lambda rows, dtype: torch.zeros(rows, b, dtype=dtype, device=self._device)
+                    fixed[stream, b, n] = (zeros(n + 1, torch.int32), zeros(1, torch.int32)[0], zeros(n, torch.float32),
+                                           zeros(n, torch.float32), zeros(n, torch.int32))
+                buf, pos_buf, u_buf, lp_buf, rk_buf = fixed[stream, b, n]
+                buf[0] = hist[steps]
+                pos_buf.copy_(pos_base + steps)
+                if uniforms is not None:
+                    u_buf.copy_(uniforms[steps : steps + n])
+                part = replace(chunk, tokens=buf, pos=pos_buf, uniforms=u_buf if uniforms is not None else None,
+                               logprobs=(lp_buf, rk_buf) if with_lp else None)
             else:
-                buf = torch.zeros(n + 1, b, dtype=torch.int32, device=self._device)
-                pos_buf = torch.zeros(b, dtype=torch.int32, device=self._device)
-                u_buf = torch.zeros(n, b, dtype=torch.float32, device=self._device)
-                lp_buf = torch.zeros(n, b, dtype=torch.float32, device=self._device) if with_lp else None
-                rk_buf = torch.zeros(n, b, dtype=torch.int32, device=self._device) if with_lp else None
-            buf[0] = hist[steps]
-            pos_buf.copy_(pos_base + steps)
-            if sample:
-                u_buf.copy_(uniforms[steps : steps + n])
-
-            def body():
-                for i in range(n):
-                    one_step(buf[i], buf[i + 1], pos_buf, u_buf[i], lp_buf[i] if with_lp else None, rk_buf[i] if with_lp else None)
-
-            self._replay_or_capture(key, body, (buf, pos_buf, u_buf, lp_buf, rk_buf))
-            hist[steps + 1 : steps + n + 1] = buf[1:]
-            if with_lp:
-                lp_hist[steps + 1 : steps + n + 1] = lp_buf
-                rk_hist[steps + 1 : steps + n + 1] = rk_buf
+                part = replace(chunk, tokens=hist[steps:], uniforms=uniforms[steps:] if uniforms is not None else None,
+                               logprobs=(lp_hist[steps + 1 :], rk_hist[steps + 1 :]) if with_lp else None)
+            run_chunk(self, part, n, capture_stream=stream)
+            if graphs:
+                hist[steps + 1 : steps + n + 1] = buf[1:]
+                if with_lp:
+                    lp_hist[steps + 1 : steps + n + 1] = lp_buf
+                    rk_hist[steps + 1 : steps + n + 1] = rk_buf
             steps += n
-            if all_done(steps):
-                break
+            if steps < max_tokens and eos_id is not None and bool((hist[: steps + 1] == eos_id).any(dim=0).all()):
+                break  # every sequence has emitted its EOS
         return done(steps + 1)
 
-    def _replay_or_capture(self, key, body, state=None, may_capture=None) -> bool:
+    def _replay_or_capture(self, key, body, may_capture=None) -> bool:
         """Replay the graph stored under ``key``; a key not seen before runs ``body`` eagerly, then captures it and stores
-        (graph, ``state``): the fixed buffers the body addresses stay alive with it.  An eager warm-up on scratch state is not
+        the graph (the fixed buffers the body addresses are kept alive by their owners).  An eager warm-up on scratch state is not
         possible (KV side effects), so the first chunk of a new shape IS the eager run and the graph is captured after a
         device synchronise; the capture does not execute, there is nothing to undo.  ``may_capture`` (asked on a miss
         only): False runs eagerly without storing.  Returns True when it captured."""
-        entry = self._graphs.get(key)
-        if entry is not None:
-            entry[0].replay()
+        graph = self._graphs.get(key)
+        if graph is not None:
+            graph.replay()
             return False
         body()
         if may_capture is not None and not may_capture():
@@ -1323,7 +1308,7 @@ class MoondreamModel:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             body()
-        self._graphs[key] = (g, state)
+        self._graphs[key] = g
         return True
 
     def _check_b1_barriers(self):
@@ -1354,11 +1339,11 @@ class MoondreamModel:
             out.append(tok)
         return out
 
-    def _prefill_groups(self, groups: Sequence[Tuple[int, int]], embed, pos: int, rows: _Rows, sampler=None,
-                        logits_capture: Optional[torch.Tensor] = None, row_perm=None, first_logprobs=None, hidden_sink=None):
+    def _prefill_groups(self, groups: Sequence[Tuple[int, int]], embed, pos: int, rows: _Rows, sampling: Optional[Sampling] = None,
+                        logits_capture: Optional[torch.Tensor] = None, first_logprobs=None, hidden_sink=None):
         """One decoder pass per group [r0, r1) of equal-length prompts: ``embed(r0, r1)`` [r1-r0, T, D] goes through the decoder
-        at position ``pos`` into the slots of ``rows.sub(r0, r1)``, then lm_head and the pick of the first token (``sampler`` =
-        (temperature, top_p, suppress_id, generator); None: argmax; ``row_perm(r0, r1)``: the draw order of a sampled group).
+        at position ``pos`` into the slots of ``rows.sub(r0, r1)``, then lm_head and the pick of the first token (``_first_token``;
+        ``sampling`` None: argmax; a group draws in its rows' order among themselves in ``sampling.row_perm``).
         Returns (first int32 [B], hidden_last [B, D], next_pos list); the groups' logits go to ``logits_capture`` [B, V], the
         log-probability and rank of each first token (unsuppressed, like the pick) to ``first_logprobs`` = (fp32 [B], int32 [B]).
         ``hidden_sink(r0, r1, hidden [r1-r0, T, D])``: the scorer's form -- every hidden row of the pass goes to the sink, and
@@ -1377,25 +1362,22 @@ class MoondreamModel:
             logits = self._lm_head(hidden)
             if logits_capture is not None:
                 logits_capture[r0:r1] = logits
-            if sampler is None:
-                first[r0:r1] = self._pick(logits, 0.0, 0.0)
-            else:
-                first[r0:r1] = self._pick(logits, *sampler, row_perm=row_perm(r0, r1) if row_perm is not None else None)
-            if first_logprobs is not None:
-                self._token_logprobs(logits, first[r0:r1], -1, first_logprobs[0][r0:r1], first_logprobs[1][r0:r1])
+            perm = sampling.row_perm[r0:r1] if sampling is not None and sampling.row_perm is not None else None
+            first[r0:r1] = self._first_token(logits, sampling, perm - perm.min() if perm is not None else None,
+                                             logprobs=[x[r0:r1] for x in first_logprobs] if first_logprobs is not None else None)
             hidden_last[r0:r1] = hidden[:, -1, :]
         return first, hidden_last, next_pos
 
     def _prepare_sequences(self, images, prompts: Sequence[Sequence[int]], mark=None, rows: Union[int, _Rows] = 0,
-                           fuse: bool = False, logits_capture: Optional[torch.Tensor] = None, sampler=None,
-                           first_logprobs=None, hidden_sink=None):
+                           fuse: bool = False, logits_capture: Optional[torch.Tensor] = None,
+                           sampling: Optional[Sampling] = None, first_logprobs=None, hidden_sink=None):
         """Everything before the first generated token, for B (image, prompt-ids) pairs: sequences are
         placed in KV slots in order of prompt length (stable), so that every group of equal-length
         prompts occupies a contiguous slot range; raw images are encoded together and prefilled
         straight into their slots, EncodedImages are copied into theirs; one prompt prefill per
         distinct length.  Returns (order, first int32 [B], hidden_last [B, D], next_pos list) in slot
-        order; ``order[slot]`` is the caller's index.  ``sampler`` = (temperature, top_p, suppress_id, generator) draws the first token
-        as the reference's _prefill_prompt does (moondream.py:313-318; suppress_id -1 there); None = argmax.  Must run under
+        order; ``order[slot]`` is the caller's index.  ``sampling`` draws the first token
+        as the reference's _prefill_prompt does (moondream.py:313-318; nothing suppressed there); None = argmax.  Must run under
         torch.inference_mode().  ``rows``: the routing of slots 0 .. B-1 (a per-row variant table is already in slot order).
         ``first_logprobs`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in slot order."""
         mark = mark or (lambda name: None)
@@ -1425,7 +1407,7 @@ class MoondreamModel:
             mark("vision")
             bos = self._embed(torch.full((b, 1), self.config.tokenizer.bos_id, dtype=torch.int32))
             fused = lambda g0, g1: torch.cat([bos[g0:g1], img_emb[g0:g1], embed_prompts(g0, g1)], dim=1)
-            out = self._prefill_groups(_length_groups(prompts), fused, 0, rows, sampler, logits_capture,
+            out = self._prefill_groups(_length_groups(prompts), fused, 0, rows, sampling, logits_capture,
                                        first_logprobs=first_logprobs, hidden_sink=hidden_sink)
             mark("image_prefill")
             mark("prompt_prefill")
@@ -1442,7 +1424,7 @@ class MoondreamModel:
                     raise ValueError("EncodedImage with a different prefix length than the rest of the batch")
                 self.load_encoded_image(im, i)
                 pos = im.pos
-        out = self._prefill_groups(_length_groups(prompts), embed_prompts, pos, rows, sampler, logits_capture,
+        out = self._prefill_groups(_length_groups(prompts), embed_prompts, pos, rows, sampling, logits_capture,
                                    first_logprobs=first_logprobs, hidden_sink=hidden_sink)  # one per prompt length
         mark("prompt_prefill")
         return (order, *out)
@@ -1473,18 +1455,17 @@ class MoondreamModel:
                 enc[id(im)] = self.encode_image(im, settings)
         return [enc[id(im)] for im in images]
 
-    def _prepare_sequences_shared(self, images, prompts: Sequence[Sequence[int]], mark=None, sampler=None,
+    def _prepare_sequences_shared(self, images, prompts: Sequence[Sequence[int]], mark=None, sampling: Optional[Sampling] = None,
                                   first_logprobs=None, hidden_sink=None):
         """``_prepare_sequences`` with a SHARED image prefix (moondream_amd/shared_prefix.py): each distinct image (by identity)
         is prefilled or loaded ONCE, into prefix slot k < P; the rows take slots P + r and read the prefix from there.  Raw
         images go through one ViT batch and ``_prefill_images``; EncodedImages are loaded once.  In the fp8 KV mode both of these
         also write the prefix slot's e4m3 rows (the prefill quantises, ``load_encoded_image`` calls md_kv_quantize_f8), once per
         image; the prompt prefill quantises its rows into the rows' own slots.  One prompt prefill per
-        distinct length (md_text_forward_shared).  Returns (order, first, hidden_last, next_pos, rows, row_perm): the first
+        distinct length (md_text_forward_shared).  Returns (order, first, hidden_last, next_pos, rows, sampling): the first
         four as ``_prepare_sequences`` returns them, in this path's row order; ``rows`` is the routing over the prefix table
-        (``_Rows``); ``row_perm`` maps a row to its row in the copy
-        path's order (sampling draws).  ``first_logprobs`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in this path's
-        row order.  Must run under torch.inference_mode()."""
+        (``_Rows``); ``sampling`` is the caller's with ``row_perm`` set: a row's row in the copy path's order (None stays None).
+        ``first_logprobs`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in this path's row order.  Must run under torch.inference_mode()."""
         mark = mark or (lambda name: None)
         plan = plan_shared_prefix(list(images), [len(p) for p in prompts])
         if any(len(p) == 0 for p in prompts):
@@ -1518,14 +1499,14 @@ class MoondreamModel:
             self._shared_buf = buf
         buf[: 3 * b].copy_(self._h2d(torch.tensor(plan.own_slots + plan.prefix_slots + [pos] * b, dtype=torch.int32)))
         rows = _Rows(slots=buf[0:b], n_slots=plan.n_slots, prefix_slots=buf[b : 2 * b], prefix_len=buf[2 * b : 3 * b])
-        row_perm = torch.tensor(plan.copy_rank, dtype=torch.int64, device=self._device)
+        if sampling is not None:
+            sampling = replace(sampling, row_perm=torch.tensor(plan.copy_rank, dtype=torch.int64, device=self._device))
         # one prefill per distinct prompt length; a sampled group draws in the copy path's row order
         first, hidden_last, next_pos = self._prefill_groups(
-            plan.groups, lambda r0, r1: self._embed(torch.tensor(prompts[r0:r1], dtype=torch.int32)), pos, rows, sampler,
-            row_perm=lambda r0, r1: row_perm[r0:r1] - min(plan.copy_rank[r0:r1]), first_logprobs=first_logprobs,
-            hidden_sink=hidden_sink)
+            plan.groups, lambda r0, r1: self._embed(torch.tensor(prompts[r0:r1], dtype=torch.int32)), pos, rows, sampling,
+            first_logprobs=first_logprobs, hidden_sink=hidden_sink)
         mark("prompt_prefill")
-        return plan.order, first, hidden_last, next_pos, rows, row_perm
+        return plan.order, first, hidden_last, next_pos, rows, sampling
 
     def batch_generate_ids(
         self,
@@ -1610,13 +1591,13 @@ class MoondreamModel:
         mark = lambda name: self._mark(marks, name)
         lora = self._lora({"variant": variant})
         with torch.inference_mode():
-            sampler = None if temperature == 0 else (float(temperature), float(top_p), -1, generator)
-            rows, row_perm = _Rows(lora=lora), None
+            sampling = None if temperature == 0 else Sampling(float(temperature), float(top_p), generator)
+            rows = _Rows(lora=lora)
             first_lp = None
             if return_logprobs:
                 first_lp = (torch.empty(b, dtype=torch.float32, device=self._device), torch.empty(b, dtype=torch.int32, device=self._device))
             if multi_rows is None and share_prefix and self._shares_prefix(lora):
-                order, first, _, next_pos, rows, row_perm = self._prepare_sequences_shared(list(images), prompts, mark, sampler,
+                order, first, _, next_pos, rows, sampling = self._prepare_sequences_shared(list(images), prompts, mark, sampling,
                                                                                            first_logprobs=first_lp)
             else:
                 if multi_rows is not None:
@@ -1625,13 +1606,12 @@ class MoondreamModel:
                     rows = _Rows(variants=self._variant_table([multi_rows[i] for i in slot_order]), bank=self._bank)
                 elif share_prefix:  # the copy path over each distinct image's EncodedImage
                     images = self._encode_distinct(images, {"variant": variant})
-                order, first, _, next_pos = self._prepare_sequences(list(images), prompts, mark, rows, fuse=True, sampler=sampler,
+                order, first, _, next_pos = self._prepare_sequences(list(images), prompts, mark, rows, fuse=True, sampling=sampling,
                                                                     first_logprobs=first_lp)
             b = len(order)
             stop = None if ignore_eos else eos
             hist = self._decode_greedy(first, next_pos if len(set(next_pos)) > 1 else next_pos[0], max_tokens,
-                                       tk.answer_id, rows, stop, temperature=float(temperature), top_p=float(top_p),
-                                       generator=generator, row_perm=row_perm, first_logprobs=first_lp)
+                                       tk.answer_id, rows, stop, sampling=sampling, first_logprobs=first_lp)
             mark("decode")
             if return_logprobs:  # ids, logprobs (as raw words) and ranks in ONE copy to the host
                 hist, lp_hist, rk_hist = hist
@@ -1867,7 +1847,7 @@ class MoondreamModel:
                         else:
                             pos = self._prefill_images(img_emb, slot0)
                             logits, _, p1 = self._prefill_prompts(prompts, pos, slot0, last_only=True)
-                        firsts.append(self._pick(logits, 0.0, 0.0))
+                        firsts.append(self._first_token(logits))
                     p1s.append(p1)
                     sizes.append(nb)
                     cur = nxt
@@ -1993,7 +1973,7 @@ class MoondreamModel:
                     emb[ids.to(self._device) == self.config.tokenizer.size_id] = enc["sizes"]
             hidden = self._text_forward(emb, pos, _Rows(lora=lora if isinstance(lora, PackedLora) else None), causal=causal)
             logits = self._lm_head(hidden)
-            nxt = self._pick(logits, temperature, top_p)
+            nxt = self._first_token(logits, Sampling(temperature, top_p) if temperature != 0 else None)
         return logits, hidden, nxt.reshape(1, 1), pos + ids.shape[1]
 
     def _generate_answer(self, prompt_tokens: torch.Tensor, pos: int, settings: Optional[dict] = None,
@@ -2036,9 +2016,7 @@ class MoondreamModel:
                     if cur_pos >= self.config.text.max_context:  # context full: same bound as the greedy loop
                         return
                     with torch.inference_mode():
-                        emb = self._embed(tok.reshape(1, 1))
-                        hidden = self._text_forward(emb, cur_pos, rows)
-                        logits = self._lm_head(hidden)
+                        _, logits = self._step_from_pieces(tok.reshape(1, 1), cur_pos, rows)
                         cur_pos += 1
                         tok = self._pick(logits, temperature, top_p, self.config.tokenizer.answer_id)  # moondream.py:517
 
@@ -2159,12 +2137,11 @@ class MoondreamModel:
                 text_chunks[-1].append(tok)
                 if tok == tk.coord_id:
                     # coordinate bin from the hidden state, value fed back through the coordinate encoder (device resident)
-                    emb = self._region_pick_encode(last_hidden, "coord", bins)
+                    x = self._region_pick_encode(last_hidden, "coord", bins).reshape(1, 1, -1)
                     grounding_chunks[-1].append((bins[0, 0].to(torch.int64) / n_bins).item())
                 else:
-                    emb = self._embed(torch.tensor([[tok]]))
-                h = self._text_forward(emb.reshape(1, 1, -1), pos, rows)
-                logits = self._lm_head(h)
+                    x = torch.tensor([[tok]])
+                h, logits = self._step_from_pieces(x, pos, rows)
                 logits[:, suppress] = float("-inf")  # moondream.py:397-398
                 pos += 1
                 last_hidden = h.reshape(1, -1)
