@@ -645,3 +645,203 @@ def test_wstream_integer_probe_is_exact_in_fp32_for_every_case_of_the_gpu_list()
                     off.view(torch.int16)[m - 1, n - 1] += 1
                     with pytest.raises(AssertionError, match="1 of"):
                         compare_f8_elementwise("one bf16 step", off, exact, mag, layer.k_pad, exact_acc=True)
+
+
+# ---- the instruments of tests/test_decode_b1_exact_gpu.py ---------------------------------------------------------------------
+import util as B1
+from moondream_amd.weights import rope_table
+from util import (B1_BRANCHES, b1_barriers, b1_block_ref, b1_branches, b1_layout, bf16_spacing, err_in_spacings, gelu_interval)
+
+B1_CU = 256  # the branch map at the CU count the shapes were chosen for; the GPU module repeats it with the device's own
+
+
+def test_b1_case_list_takes_every_branch_at_256_cus():
+    sh = B1.b1_shapes(B1_CU)
+    assert sh["S3"]["dim"] == 2560
+    per_shape = {}
+    for name, n_layers, L, ctx, vocab in B1.b1_case_list():
+        s = sh[name]
+        per_shape.setdefault(name, set()).update(b1_branches(B1_CU, dim=s["dim"], n_heads=s["dim"] // 64, ff=s["ff"], L=L, ctx=ctx, vocab=vocab))
+    assert set().union(*per_shape.values()) == set(B1_BRANCHES)
+    assert {"empty proj half", "phase A idle waves", "empty key slice", "L = 8k + 1", "slice fills sc[] (chunk == B1_MAX_KEYS)",
+            "pos == ctx - 1", "key index clamp to ctx - 1 binds", "phase D fewer row pairs than workgroups",
+            "phase D second row pair per wave"} <= per_shape["S1"]
+    assert {"two live proj halves, unequal", "two live fc2 halves, unequal", "fc2 half boundary not a multiple of 512 from the end"} <= per_shape["S2"]
+    assert {"second (head, slice) item per workgroup", "phase C second pass", "combine second pass", "phase A second row pair per wave"} <= per_shape["S3"]
+    assert {"dim limit (4096)", "ff limit (8192)"} <= per_shape["S4"]
+    # the tiny and the 2b model on 256 CUs take none of the second passes: what the suite missed before
+    for dim, ff in ((256, 704), (2048, 8192)):
+        got = b1_branches(B1_CU, dim=dim, n_heads=dim // 64, ff=ff, L=740, ctx=2048, vocab=0)
+        assert not got & {"second (head, slice) item per workgroup", "phase C second pass", "combine second pass"}, got
+    assert b1_layout(256, 704, 4) == {"x0": 0, "x1": 512, "act": 1024, "part": 1024 + 3072, "total": 4096 + 8704}
+    assert [b1_barriers(1, False), b1_barriers(2, False), b1_barriers(3, False), b1_barriers(1, True)] == [2, 5, 8, 4]
+
+
+def _torch_bf16_block(x, w, kc, vc, pos, cs, sn, rot):
+    """The block in float32 torch with a bf16 rounding at every documented point (reference layers.py / text.py / rope.py)."""
+    F = torch.nn.functional
+    f = lambda t: t.float()
+    d = x.numel()
+    h = d // 64
+    ln = F.layer_norm(f(x), (d,), f(w["ln_w"]), f(w["ln_b"]), 1e-5).to(BF16)
+    pre = F.linear(f(ln), f(w["w1"]), f(w["b1"])).to(BF16)
+    g = F.gelu(f(pre[3 * d:]), approximate="tanh").to(BF16)
+    q, k, v = pre[: 3 * d].view(3, h, 64)
+
+    def rope(t):
+        t = f(t)
+        re, im = t[..., : rot // 2], t[..., rot // 2: rot]
+        out = torch.stack((re * cs - im * sn, re * sn + im * cs), dim=-1).flatten(-2)
+        return torch.cat([out, t[..., rot:]], dim=-1).to(BF16)
+
+    qr, kr = rope(q), rope(k)
+    keys, vals = torch.cat([f(kc[:, :pos]), f(kr)[:, None]], 1), torch.cat([f(vc[:, :pos]), f(v)[:, None]], 1)
+    s = torch.einsum("hd,hjd->hj", f(qr), keys) * 0.125
+    p = torch.exp(s - s.amax(-1, keepdim=True))
+    att = (torch.einsum("hj,hjd->hd", f(p.to(BF16)), vals) / p.sum(-1, keepdim=True)).to(BF16).reshape(d)
+    t1, t2 = F.linear(f(att), f(w["wp"]), f(w["bp"])).to(BF16), F.linear(f(g), f(w["w2"]), f(w["b2"])).to(BF16)
+    x1 = (f(x) + f(t1)).to(BF16)
+    return {"hidden": (f(x1) + f(t2)).to(BF16), "k": kr, "v": v, "act": torch.cat([pre[: 3 * d], g]), "att": att}
+
+
+@pytest.mark.parametrize("name,pos,rot", [("S1", 9, 32), ("S2", 130, 32), ("S1", 40, 16), ("S1", 40, 64)])
+def test_b1_rounded_reference_is_the_torch_bf16_block(name, pos, rot):
+    s = B1.b1_shapes(B1_CU)[name]
+    w, kc, vc, x = B1.tier2_inputs(s["dim"], s["ff"], "cpu")
+    fr = rope_table(rot, B1.TIER2_CTX)[pos]
+    ref = b1_block_ref(x.double(), w, kc.double(), vc.double(), pos, fr[:, 0].double(), fr[:, 1].double(), rot, rounded=True)
+    alt = _torch_bf16_block(x, w, kc, vc, pos, fr[:, 0], fr[:, 1], rot)
+    for key in ("act", "k", "v", "att", "hidden"):
+        a, b = ref[key].reshape(-1), alt[key].double().reshape(-1)
+        same = float((a == b).double().mean())
+        worst = float(((a - b).abs() / bf16_spacing(a)).max())
+        print(f"{name} pos {pos} rot {rot} {key}: {same:.4f} equal, worst {worst:.2f} spacings")
+        # float32 against float64 between the roundings: a value next to a rounding boundary may fall on the other side
+        assert same >= 0.97 and worst <= 1.0, (key, same, worst)
+
+
+@pytest.mark.parametrize("L", [2, 9, 17, 2041])
+def test_b1_slice_probe_sees_a_dropped_and_a_stale_key(L):
+    s = B1.b1_shapes(B1_CU)["S1"]
+    d, H, pos = s["dim"], s["dim"] // 64, L - 1
+    w, vplant, kcache = B1.slice_probe_inputs(d, s["ff"], L, dev="cpu")
+    kc, vc = kcache.clone(), vplant.clone()
+    kc[:, pos], vc[:, pos] = float("nan"), float("nan")  # what the GPU probe leaves in row pos before the launch
+    fr = rope_table(32, 2048)[pos].double()
+    run = lambda **kw: b1_block_ref(torch.zeros(d, dtype=torch.float64), w, kc, vc, pos, fr[:, 0], fr[:, 1], 32, rounded=True, **kw)
+    good = run()
+    assert torch.equal(good["hidden"], round_to_bf16(vplant.sum(1).reshape(-1) / L))  # the probe's own expectation
+    assert torch.equal(good["v"], vplant[:, pos])
+    chunk = (L + 7) // 8
+    for h, j in {(0, 0), (H - 1, pos), (1, min(chunk, pos)), (2, max(0, min(chunk, pos) - 1))}:
+        bad = run(mutation="drop_key", drop=(h, j))["hidden"]
+        # (the combined row is rounded to bf16: among 2041 keys one small power of two is below its spacing, which is why the
+        # probe holds every partial, not only the row, to the exact sum)
+        assert L > 17 or not torch.equal(bad, good["hidden"]), (h, j)
+        # the partial the GPU probe compares exactly: the slice's sum without the key, or with another head's key in its place
+        sl = j // chunk
+        full = vplant[h, sl * chunk: min(L, sl * chunk + chunk)].sum(0)
+        assert not torch.equal(full - vplant[h, j], full)
+        assert not torch.equal(full - vplant[h, j] + vplant[(h + 1) % H, j], full)
+        assert not torch.equal(full + vplant[h, j], full)
+    assert bool(torch.isnan(run(mutation="stale_key")["hidden"]).any())  # the NaN row reaches hidden: the probe's NaN check fires
+
+
+@pytest.mark.parametrize("name", ["S1", "S2"])
+def test_b1_integer_block_sees_a_lost_rounding(name):
+    s = B1.b1_shapes(B1_CU)[name]
+    d, ff = s["dim"], s["ff"]
+    one, zero = torch.ones(16, dtype=torch.float64), torch.zeros(16, dtype=torch.float64)
+    H = d // 64
+    nan = torch.full((H, 1, 64), float("nan"), dtype=torch.float64)
+    x = B1.int_x(d, 22, "cpu")
+    # residual chain: fc1 biases whose GELU is exact
+    w = B1.int_weights(d, ff, 21, fc1_live=False, dev="cpu")
+    good = b1_block_ref(x, w, nan, nan, 0, one, zero, 32, rounded=True)
+    B1.assert_exact_block(name, w, good["att"], good["act"][3 * d:])
+    want, single, swapped = B1.residual_chain(x, good["att"], good["act"][3 * d:], w)
+    assert torch.equal(good["hidden"], want)
+    bad = b1_block_ref(x, w, nan, nan, 0, one, zero, 32, rounded=True, mutation="one_residual_rounding")["hidden"]
+    assert torch.equal(bad, single)
+    for other in (single, swapped):
+        assert float((other != want).double().mean()) >= 0.05
+    # GELU before the rounding: outside the interval the phase-A check allows
+    w = B1.int_weights(d, ff, 21, dev="cpu")
+    good = b1_block_ref(x, w, nan, nan, 0, one, zero, 32, rounded=True)
+    pre = w["w1"] @ w["ln_b"] + w["b1"]
+    assert torch.equal(good["act"][: 3 * d], round_to_bf16(pre[: 3 * d]))
+    lo, hi = gelu_interval(round_to_bf16(pre[3 * d:]))
+    inside = lambda t: (t >= lo) & (t <= hi)
+    assert bool(inside(good["act"][3 * d:]).all())
+    bad = b1_block_ref(x, w, nan, nan, 0, one, zero, 32, rounded=True, mutation="gelu_before_rounding")["act"][3 * d:]
+    share = float((~inside(bad)).double().mean())
+    print(f"{name}: GELU before the rounding leaves the interval on {share:.3f} of the fc1 columns")
+    assert share >= 0.05, share
+
+
+def test_b1_second_pass_probe_sees_a_neighbouring_row_pair():
+    s = B1.b1_shapes(B1_CU)["S3"]
+    d, ff = s["dim"], s["ff"]
+    one, zero = torch.ones(16, dtype=torch.float64), torch.zeros(16, dtype=torch.float64)
+    nan = torch.full((d // 64, 1, 64), float("nan"), dtype=torch.float64)
+    x = B1.int_x(d, 22, "cpu")
+    w = B1.int_weights(d, ff, 21, fc1_live=False, dev="cpu")
+    good = b1_block_ref(x, w, nan, nan, 0, one, zero, 32, rounded=True)["hidden"]
+    bad = b1_block_ref(x, w, nan, nan, 0, one, zero, 32, rounded=True, mutation="neighbour_pair", n_cu=B1_CU)["hidden"]
+    diff = bad != good
+    assert not bool(diff[: 2 * B1_CU].any()) and float(diff[2 * B1_CU:].double().mean()) > 0.9
+    # and the one-column probe: neighbouring rows differ in most of the columns it plants
+    for mat in (w["wp"], w["w2"]):
+        assert float((mat[2 * B1_CU: -2] != mat[2 * B1_CU + 2:]).double().mean()) > 0.8
+
+
+# The Tier 2 margins compare two implementations of the SAME rounding points.  Their stand-ins here: the float64 block with those
+# roundings (an ideal kernel) in the place of the persistent kernel, the float32 torch block in the place of the batched kernels.
+# The ideal kernel must pass the Tier 2 check on the Tier 2 inputs in the Tier 2 unit (util.err_in_spacings with the addends).  Its
+# own distance from the truth is printed: about one spacing RMS, while single elements reach 4 to 15 spacings where a dot product
+# (proj, fc2, a logit) is itself a cancelled sum that carries the rounding of the layer norm and of the gelu row in every term --
+# shared by every implementation of these rounding points, which is why the margins are relative to the batched kernels.
+@pytest.mark.parametrize("name,positions", B1.TIER2_CASES)
+def test_b1_tier2_inputs_keep_the_rounded_reference_within_the_margins(name, positions):
+    s = B1.b1_shapes(B1_CU)[name]
+    w, kc, vc, x = B1.tier2_inputs(s["dim"], s["ff"], "cpu")
+    table = rope_table(32, B1.TIER2_CTX)
+    for pos in positions:
+        cs, sn = table[pos, :, 0], table[pos, :, 1]
+        a = (x.double(), w, kc.double(), vc.double(), pos, cs.double(), sn.double(), 32)
+        truth, rnd = b1_block_ref(*a, rounded=False), b1_block_ref(*a, rounded=True)
+        yard = _torch_bf16_block(x, w, kc, vc, pos, cs, sn, 32)
+        for key in ("hidden", "k", "v"):
+            terms = B1.hidden_terms(truth) if key == "hidden" else ()
+            (rms, mx), (yr, ym) = (err_in_spacings(t[key].reshape(-1), truth[key].reshape(-1), *terms) for t in (rnd, yard))
+            print(f"{name} pos {pos} {key}: rounded reference rms {rms:.3f} max {mx:.2f} | float32 torch block rms {yr:.3f} max {ym:.2f} spacings")
+            assert rms <= B1.B1_RMS_RATIO * yr and mx <= ym + B1.B1_MAX_EXTRA, (name, pos, key, rms, mx, yr, ym)
+
+
+def test_b1_tier2_step_inputs_keep_the_rounded_logits_within_the_margins():
+    F = torch.nn.functional
+    s = B1.b1_shapes(B1_CU)["S1"]
+    d = s["dim"]
+    w, head, kc, vc = B1.tier2_step_inputs(d, s["ff"], "cpu")
+    pos, token = B1.TIER2_STEP["pos"], B1.TIER2_STEP["token"]
+    fr = rope_table(32, B1.TIER2_CTX)[pos]
+    x = head["wte"][token]
+    a = (x, w, kc.double(), vc.double(), pos, fr[:, 0].double(), fr[:, 1].double(), 32)
+    h = [head[k] for k in ("post_w", "post_b", "lm_w", "lm_b")]
+    lt, dot = B1.b1_logits_ref(b1_block_ref(*a, rounded=False)["hidden"], *h, rounded=False, parts=True)
+    lr = B1.b1_logits_ref(b1_block_ref(*a, rounded=True)["hidden"], *h, rounded=True)
+    hid = _torch_bf16_block(x.to(BF16), w, kc, vc, pos, fr[:, 0], fr[:, 1], 32)["hidden"]
+    ln = F.layer_norm(hid.float(), (d,), h[0].float(), h[1].float(), 1e-5).to(BF16)
+    ly = F.linear(ln.float(), h[2].float(), h[3].float()).to(BF16)
+    (rms, mx), (yr, ym) = err_in_spacings(lr, lt, dot), err_in_spacings(ly, lt, dot)
+    print(f"step logits: rounded reference rms {rms:.3f} max {mx:.2f} | float32 torch rms {yr:.3f} max {ym:.2f} spacings from the truth")
+    assert rms <= B1.B1_RMS_RATIO * yr and mx <= ym + B1.B1_MAX_EXTRA, (rms, mx, yr, ym)
+
+
+def test_err_in_spacings_counts_in_the_spacing_of_the_addends():
+    truth = torch.tensor([1.0, 2.0 ** -10, 3.0], dtype=torch.float64)
+    term = torch.tensor([0.25, 1.0, 0.5], dtype=torch.float64)
+    got = truth + torch.tensor([2.0 ** -7, 2.0 ** -7, 2.0 ** -6], dtype=torch.float64)
+    assert err_in_spacings(got, truth)[1] == 2.0 ** -7 / 2.0 ** -17          # the cancelled element alone: 1024 spacings
+    assert err_in_spacings(got, truth, term) == (1.0, 1.0)                    # one spacing of its largest addend
+    assert err_in_spacings(truth * (1 + 2.0 ** -4), truth, term)[1] >= 8.0    # a 6 % error of a result is still many spacings

@@ -514,3 +514,332 @@ def wstream_exact(a: torch.Tensor, q: torch.Tensor, scale, bias, row_chunk: int 
         exact[r0 : r0 + row_chunk] = (a64 @ qt) * s64 + b64
         mag[r0 : r0 + row_chunk] = (a64.abs() @ qt_abs) * s64.abs() + b64.abs()
     return exact, mag
+
+
+# ---- the single-sequence decode kernel (csrc/decode_b1.hip): layout, branch map and a float64 decoder block --------------------
+B1_SLICES, B1_PART, B1_NWV, B1_MAX_KEYS = 8, 68, 8, 256   # key slices per head, floats per partial, waves per workgroup, keys per slice
+B1_ERR_WORD = 64 * 11                                     # word of the sync state a timed-out barrier raises
+
+
+def b1_layout(dim: int, ff_pad: int, n_heads: int) -> dict:
+    """Byte offsets of the workspace as b1_fill lays it out: the two residual rows x[0], x[1], the fused [q | k | v | gelu(fc1)]
+    row ``act`` and the attention partials ``part`` [n_heads][8][68] fp32, each rounded up to 256 bytes; ``total`` must equal
+    md_decode_b1_workspace_bytes."""
+    a256 = lambda v: (v + 255) // 256 * 256
+    xb, ab, pb = a256(dim * 2), a256((3 * dim + ff_pad) * 2), a256(n_heads * B1_SLICES * B1_PART * 4)
+    return {"x0": 0, "x1": xb, "act": 2 * xb, "part": 2 * xb + ab, "total": 2 * xb + ab + pb}
+
+
+B1_BRANCHES = (
+    "second (head, slice) item per workgroup", "phase C second pass", "combine second pass", "phase A second row pair per wave",
+    "phase A idle waves", "phase D second row pair per wave", "phase D fewer row pairs than workgroups", "empty proj half",
+    "two live proj halves, unequal", "two live fc2 halves, unequal", "fc2 half boundary not a multiple of 512 from the end",
+    "empty key slice", "L = 8k", "L = 8k + 1", "slice fills sc[] (chunk == B1_MAX_KEYS)", "pos == ctx - 1",
+    "key index clamp to ctx - 1 binds", "dim limit (4096)", "ff limit (8192)",
+)
+
+
+def b1_branches(n_cu: int, *, dim: int, n_heads: int, ff: int, L: int, ctx: int, vocab: int = 0) -> set:
+    """Which of B1_BRANCHES one launch of decode_b1_kernel<8> takes on a device with ``n_cu`` workgroups, restating the kernel's
+    own expressions (np_a, npw_a, np_c, npw_c, PPP, nchd, nch2, chunk, j0 / j1, load_kv's clamp, np_d, npw_d)."""
+    nwv, nt, ppp = B1_NWV, 64 * B1_NWV, B1_NWV // 2
+    npw = lambda n_pairs, b: (n_pairs - 1 - b) // n_cu + 1 if b < n_pairs else 0
+    s = set()
+    if n_heads * B1_SLICES > n_cu:
+        s.add("second (head, slice) item per workgroup")
+    np_c = dim // 2
+    if npw(np_c, 0) > ppp:
+        s.add("phase C second pass")
+    if dim // 4 > nt:
+        s.add("combine second pass")
+    np_a = (3 * dim + ff) // 2
+    if npw(np_a, 0) > nwv:
+        s.add("phase A second row pair per wave")
+    if npw(np_a, n_cu - 1) < nwv:
+        s.add("phase A idle waves")
+    if vocab:
+        np_d = vocab // 2
+        if npw(np_d, 0) > nwv:
+            s.add("phase D second row pair per wave")
+        if np_d < n_cu:
+            s.add("phase D fewer row pairs than workgroups")
+    halves = lambda k: (max(min(k, 512 * (((k + 511) // 512) // 2)), 0), k - max(min(k, 512 * (((k + 511) // 512) // 2)), 0))
+    kp, kf = halves(dim), halves(ff)
+    if kp[0] == 0:
+        s.add("empty proj half")
+    if kp[0] > 0 and kp[1] > 0 and kp[0] != kp[1]:
+        s.add("two live proj halves, unequal")
+    if kf[0] > 0 and kf[1] > 0 and kf[0] != kf[1]:
+        s.add("two live fc2 halves, unequal")
+    if kf[0] > 0 and kf[1] % 512 != 0:
+        s.add("fc2 half boundary not a multiple of 512 from the end")
+    chunk = (L + B1_SLICES - 1) // B1_SLICES
+    if any(sl * chunk >= L for sl in range(B1_SLICES)):
+        s.add("empty key slice")
+    if L % 8 == 0:
+        s.add("L = 8k")
+    if L % 8 == 1 and L > 1:
+        s.add("L = 8k + 1")
+    if chunk == B1_MAX_KEYS:
+        s.add("slice fills sc[] (chunk == B1_MAX_KEYS)")
+    if L == ctx:
+        s.add("pos == ctx - 1")
+    # load_kv: j = min(min(j0 + g + NG i, j1 - 1), ctx - 1) with j1 = max(min(L, j0 + chunk), j0 + 1)
+    if any(max(min(L, sl * chunk + chunk), sl * chunk + 1) - 1 > ctx - 1 for sl in range(B1_SLICES)):
+        s.add("key index clamp to ctx - 1 binds")
+    if dim == 4096:
+        s.add("dim limit (4096)")
+    if ff == 8192:
+        s.add("ff limit (8192)")
+    return s
+
+
+def b1_barriers(n_layers: int, step: bool) -> int:
+    """Grid barriers of one launch: two per block, one more behind every block that another block or phase D follows, and the
+    one in front of phase D's final choice."""
+    return 3 * n_layers + 1 if step else 3 * n_layers - 1
+
+
+def rope64(v: torch.Tensor, cs: torch.Tensor, sn: torch.Tensor, rot: int) -> torch.Tensor:
+    """The kernel's RoPE of head rows v [..., 64] at one position (float64): with re = v[j], im = v[rot / 2 + j], j < rot / 2,
+    out[2 j] = re cs[j] - im sn[j] and out[2 j + 1] = re sn[j] + im cs[j] (the reference interleaves its output); columns
+    >= rot pass.  At position 0 (cs = 1, sn = 0) this is the permutation alone."""
+    hr = rot // 2
+    re, im = v[..., :hr], v[..., hr:rot]
+    out = v.clone()
+    out[..., 0:rot:2] = re * cs - im * sn
+    out[..., 1:rot:2] = re * sn + im * cs
+    return out
+
+
+B1_MUTATIONS = ("drop_key", "stale_key", "one_residual_rounding", "gelu_before_rounding", "neighbour_pair")
+
+
+def b1_block_ref(x, w, kc, vc, pos: int, cs, sn, rot: int, *, rounded: bool, mutation=None, n_cu: int = 256, drop=(0, 0)):
+    """One decoder block at one row in float64 (layers.py / text.py of the reference at batch 1, q_len 1).
+    x [D]; w: dict of float64 tensors ln_w, ln_b [D], w1 [3 D + ff, D], b1, wp [D, D], bp, w2 [D, ff], b2 holding bf16 values;
+    kc / vc [H, ctx, 64]: the slabs, rows < pos are the cache (row pos is read only by the "stale_key" mutation); cs / sn
+    [rot / 2]: the fp32 table's row of position pos.
+    ``rounded = False``: the truth, no intermediate rounding.  ``rounded = True``: round_to_bf16 at the rounding points both
+    kernel families share -- the layer-norm output, each linear plus bias, GELU on the bf16 value and rounded again, the rotated
+    q and k, the probabilities that enter P.V (the row sum adds them unrounded), the attention row, and the two sequential
+    residual adds bf16(bf16(x + proj) + fc2).
+    ``mutation``: one of B1_MUTATIONS, the mistakes the probes must see -- key ``drop`` = (head, index) left out; the key at
+    pos read from the slab instead of the new rotated row; one rounding for both residual adds; GELU of the unrounded fc1;
+    the weight rows of every output pair >= n_cu (the second pass of a workgroup) taken from the neighbouring pair.
+    Returns hidden [D], k / v [H, 64] (the new slab rows), act [3 D + ff] (q | k | v | gelu(fc1) before RoPE), att [D], and the
+    terms of the residual chain: x, proj = Wp att + bp, fc2 = W2 gelu + b2."""
+    assert mutation is None or mutation in B1_MUTATIONS
+    r = round_to_bf16 if rounded else (lambda t: t)
+    d = x.numel()
+    h = d // 64
+    mean = x.mean()
+    var = ((x - mean) ** 2).mean()
+    ln = r((x - mean) / torch.sqrt(var + float(np.float32(1e-5))) * w["ln_w"] + w["ln_b"])
+    pre = w["w1"] @ ln + w["b1"]
+    g = r(_gelu64(pre[3 * d:] if mutation == "gelu_before_rounding" else r(pre[3 * d:]))[0])
+    qkv = r(pre[: 3 * d])
+    q, k, v = qkv.view(3, h, 64)
+    qr, kr = r(rope64(q, cs, sn, rot)), r(rope64(k, cs, sn, rot))
+    keys, vals = kc[:, : pos + 1].clone(), vc[:, : pos + 1].clone()
+    if mutation != "stale_key":
+        keys[:, pos] = kr
+    vals[:, pos] = v
+    s = torch.einsum("hd,hjd->hj", qr, keys) * 0.125
+    if mutation == "drop_key":
+        s[drop[0], drop[1]] = float("-inf")
+    p = torch.exp(s - s.amax(-1, keepdim=True))
+    att = r(torch.einsum("hj,hjd->hd", r(p), vals) / p.sum(-1, keepdim=True)).reshape(d)
+    wp, w2 = w["wp"], w["w2"]
+    if mutation == "neighbour_pair" and d // 2 > n_cu:
+        pair = torch.arange(d // 2, device=x.device)
+        src = torch.where(pair >= n_cu, torch.where(pair + 1 < d // 2, pair + 1, pair - 1), pair)
+        rows = (2 * src[:, None] + torch.arange(2, device=x.device)).reshape(-1)
+        wp, w2 = wp[rows], w2[rows]
+    t1, t2 = r(wp @ att + w["bp"]), r(w2 @ g + w["b2"])
+    hidden = r(x + t1 + t2) if mutation == "one_residual_rounding" else r(r(x + t1) + t2)
+    return {"hidden": hidden, "k": kr, "v": v, "act": torch.cat([qkv, g]), "att": att, "x": x, "proj": t1, "fc2": t2}
+
+
+def b1_logits_ref(hidden, post_w, post_b, lm_w, lm_b, *, rounded: bool, parts: bool = False):
+    """The final layer norm and lm_head of the step entry in float64, with or without the two bf16 roundings.  ``parts``: also
+    the dot products lm_w . ln without the bias."""
+    r = round_to_bf16 if rounded else (lambda t: t)
+    mean = hidden.mean()
+    var = ((hidden - mean) ** 2).mean()
+    ln = r((hidden - mean) / torch.sqrt(var + float(np.float32(1e-5))) * post_w + post_b)
+    return (r(lm_w @ ln + lm_b), lm_w @ ln) if parts else r(lm_w @ ln + lm_b)
+
+
+def gelu_interval(p: torch.Tensor):
+    """[lo, hi] of bf16 values gelu_tanh_f32x2 may store for the bf16 pre-activation p (float64): the float64 GELU widened by the
+    bound _gelu64 states, rounded at both ends.  (The probes keep p outside the dip bracket or accept its two ends.)"""
+    y, g = _gelu64(p)
+    return round_to_bf16(y - g - 2.0 ** -50 * y.abs()), round_to_bf16(y + g + 2.0 ** -50 * y.abs())
+
+
+def err_in_spacings(got: torch.Tensor, truth: torch.Tensor, *terms):
+    """(RMS, maximum) of |got - truth| per element, in units of the bf16 spacing at the largest of |truth| and |terms| (float64
+    tensors of truth's shape: the addends the kernel rounds on the way to the result).  A result is as accurate as the roundings
+    of its addends allow: where x + proj + fc2 cancels, one rounding of a term falling the other way under another summation
+    order is many spacings of the small sum but one spacing of the term -- the unit that makes that count as one, and still
+    counts an error of the terms in THEIR spacing instead of the spacing of a large x."""
+    big = truth.abs()
+    for t in terms:
+        big = torch.maximum(big, t.reshape(truth.shape).abs())
+    e = (got.double().reshape(truth.shape) - truth).abs() / bf16_spacing(big)
+    assert torch.isfinite(e).all(), "non-finite error"
+    return float(e.pow(2).mean().sqrt()), float(e.max())
+
+
+def hidden_terms(ref: dict):
+    """The addends of b1_block_ref's hidden, for err_in_spacings."""
+    return ref["x"], ref["proj"], ref["fc2"]
+
+
+# ---- inputs of tests/test_decode_b1_exact_gpu.py (built here so that the CPU tests of the instruments use the same numbers) ---
+def b1_shapes(n_cu: int) -> dict:
+    """The smallest shapes that reach each branch, from the CU count: S3 has more (head, slice) items than workgroups, more
+    than 4 output pairs per workgroup in phase C and more than 512 four-feature groups; S4 sits on every static limit."""
+    h3 = max(n_cu // 8 + 8, 4 * n_cu // 32 + 8, 2048 // 64 + 8)  # 40 at 256 CUs
+    return {"S1": dict(dim=256, ff=704), "S2": dict(dim=640, ff=1096), "S3": dict(dim=64 * h3, ff=520), "S4": dict(dim=4096, ff=8192)}
+
+
+KEY_COUNTS = (1, 2, 7, 8, 9, 16, 17, 2041, 2048)
+
+
+def b1_case_list():
+    """(shape, n_layers, L, ctx, vocab): every launch geometry tests/test_decode_b1_exact_gpu.py plans (vocab 0: the layers
+    entry).  The GPU module records what it launches and asserts that it is exactly this list."""
+    cases = [("S1", n, 1, 64, 0) for n in (1, 2, 3)] + [("S2", 1, 1, 64, 0), ("S2", 2, 1, 64, 0), ("S3", 1, 1, 64, 0), ("S3", 2, 1, 64, 0),
+                                                        ("S4", 1, 1, 64, 0)]
+    cases += [("S1", 1, L, 2048, 0) for L in KEY_COUNTS] + [("S1", 1, 40, 40, 0), ("S1", 1, 34, 34, 0), ("S1", 1, 41, 2048, 0)]
+    cases += [("S2", 1, 17, 2048, 0), ("S3", 1, 7, 2048, 0), ("S3", 1, 9, 2048, 0), ("S3", 1, 2048, 2048, 0), ("S4", 1, 2048, 2048, 0)]
+    cases += [("S1", 1, L, 64, v) for L in (1, 6) for v in (256, 4610)] + [("S1", 1, 778, 2048, 4616)]
+    cases += [(s, 1, L, 2048, 0) for s in ("S1", "S2", "S3") for L in (1, 9, 778, 2048)] + [("S4", 1, 778, 2048, 0)]
+    return sorted(set(cases))
+
+
+def zero_weights(dim, ff, dev="cpu"):
+    z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)
+    return {"ln_w": z(dim), "ln_b": z(dim), "w1": z(3 * dim + ff, dim), "b1": z(3 * dim + ff), "wp": z(dim, dim), "bp": z(dim),
+            "w2": z(dim, ff), "b2": z(dim)}
+
+
+def gen(seed, dev="cpu"):
+    return torch.Generator(device=dev).manual_seed(seed)
+
+
+def rint(g, lo, hi, *shape):
+    """Integers of [lo, hi] as float64, drawn on the generator's device."""
+    return torch.randint(lo, hi + 1, shape, generator=g, device=g.device).double()
+
+
+def assert_fp32_exact(name, mat, vec, bias, unit):
+    """Every term of mat @ vec + bias is a multiple of ``unit`` and the sum of their magnitudes stays below 2^24 units: every
+    partial sum in any order is exact in fp32."""
+    for t in (mat[:, :1] * vec[:1], bias):
+        assert bool((torch.round(t / unit) * unit == t).all()), name
+    mag = float((mat.abs() @ vec.abs() + bias.abs()).max())
+    assert mag < 2.0 ** 24 * unit, f"{name}: magnitude {mag} needs more than 24 bits at unit {unit}"
+
+
+SAFE_GELU = (0., 4., 5., 6., 7., 8.)  # pre-activations whose GELU rounds to themselves in bf16 under util.gelu_interval
+
+
+def int_weights(dim, ff, seed, *, fc1_live=True, dev="cpu"):
+    """One block whose every sum is exact in fp32 with ln.w = 0 (assert_exact_block): ln.b integers in [-4, 4]; q rows zero
+    (uniform scores); k and fc1 rows integers in [-8, 8] / 64 with biases k / 128; v rows integers in [-2, 2] with integer
+    biases, so that the attention row of one key is an integer vector; Wp integers in [-8, 8] / 64, W2 integers in [-32, 32] / 64
+    against gelu values <= 8, their biases k / 128.  fc1_live = False: fc1 weights zero and fc1 biases in SAFE_GELU."""
+    g = gen(seed, dev)
+    w = zero_weights(dim, ff, dev)
+    w["ln_b"] = rint(g, -4, 4, dim)
+    w["w1"] = rint(g, -8, 8, 3 * dim + ff, dim) / 64
+    w["b1"] = rint(g, -255, 255, 3 * dim + ff) / 128
+    w["w1"][:dim] = 0  # q = 0: uniform scores
+    w["b1"][:dim] = 0
+    w["w1"][2 * dim: 3 * dim] = rint(g, -2, 2, dim, dim)
+    w["b1"][2 * dim: 3 * dim] = rint(g, -64, 64, dim)
+    if not fc1_live:
+        w["w1"][3 * dim:] = 0
+        w["b1"][3 * dim:] = torch.tensor(SAFE_GELU, dtype=torch.float64, device=dev)[rint(g, 0, 5, ff).long()]
+    w["wp"] = rint(g, -8, 8, dim, dim) / 64
+    w["bp"] = rint(g, -255, 255, dim) / 128
+    w["w2"] = rint(g, -32, 32, dim, ff) / 64
+    w["b2"] = rint(g, -255, 255, dim) / 128
+    return w
+
+
+def int_x(dim, seed, dev="cpu"):
+    return rint(gen(seed, dev), -255, 255, dim) / 128
+
+
+def assert_exact_block(name, w, att, gel):
+    d = w["ln_w"].numel()
+    assert_fp32_exact(f"{name}: fused rows", w["w1"], w["ln_b"], w["b1"], 2.0 ** -7)
+    assert_fp32_exact(f"{name}: proj", w["wp"], att, w["bp"], 2.0 ** -7)
+    assert_fp32_exact(f"{name}: fc2", w["w2"], gel, w["b2"], 2.0 ** -7)
+
+
+def residual_chain(x, att, gel, w):
+    """x' = bf16(bf16(x + bf16(Wp att + bp)) + bf16(W2 gelu + b2)) in float64 with its four roundings, and the two evaluations a
+    wrong kernel could make: one rounding for both adds, and fc2 added first."""
+    r = round_to_bf16
+    t1, t2 = r(w["wp"] @ att + w["bp"]), r(w["w2"] @ gel + w["b2"])
+    return r(r(x + t1) + t2), r(x + t1 + t2), r(r(x + t2) + t1)
+
+
+def planted_v(H, n_keys):
+    """V[h, j]: 2^((j // 64) % 16) in column (j + 7 h) % 64, else 0: within a slice (<= 256 consecutive keys) every key owns its
+    (column, bit); a key missing, doubled or taken from another head changes the slice's sum, which stays below 2^17."""
+    v = torch.zeros(H, n_keys, 64, dtype=torch.float64)
+    j = torch.arange(n_keys)
+    for h in range(H):
+        v[h, j, (j + 7 * h) % 64] = torch.exp2(((j // 64) % 16).double())
+    return v
+
+
+def slice_probe_inputs(dim, ff, L, seed=31, dev="cpu"):
+    """(weights, planted V [H, L, 64], cache K [H, L, 64]) of the uniform-score probe with L keys, the last one the new token's."""
+    H, pos = dim // 64, L - 1
+    g = gen(seed + L, dev)
+    w = zero_weights(dim, ff, dev)
+    vplant = planted_v(H, L).to(dev)
+    w["b1"][dim: 2 * dim] = rint(g, -255, 255, dim) / 64
+    w["b1"][2 * dim: 3 * dim] = vplant[:, pos].reshape(-1)
+    w["wp"] = torch.eye(dim, dtype=torch.float64, device=dev)
+    return w, vplant, rint(g, -255, 255, H, L, 64) / 64
+
+
+B1_RMS_RATIO, B1_MAX_EXTRA = 1.5, 2.0    # the persistent kernel against the batched kernels: RMS ratio, spacings more at the maximum
+TIER2_CASES = [("S1", (0, 8, 777, 2047)), ("S2", (0, 8, 777, 2047)), ("S3", (0, 8, 777, 2047)), ("S4", (777,))]
+TIER2_CTX = 2048
+TIER2_STEP = dict(vocab=4616, pos=777, token=1234)  # a second row pair in some waves; a multiple of 8 for the batched GEMM's stores
+
+
+def random_weights(dim, ff, seed, dev="cpu"):
+    """randn operands of one block (weights scaled by 1 / sqrt(K), biases by 0.1) as bf16 values in float64, drawn on the CPU:
+    the same numbers with and without a GPU.  Returns (weights, the generator)."""
+    g = gen(seed, "cpu")
+    rn = lambda *s: torch.randn(*s, generator=g)
+    q = lambda t: t.to(torch.bfloat16).to(dev).double()
+    return {"ln_w": q(1 + 0.1 * rn(dim)), "ln_b": q(0.1 * rn(dim)), "w1": q(rn(3 * dim + ff, dim) / dim ** 0.5), "b1": q(0.1 * rn(3 * dim + ff)),
+            "wp": q(rn(dim, dim) / dim ** 0.5), "bp": q(0.1 * rn(dim)), "w2": q(rn(dim, ff) / ff ** 0.5), "b2": q(0.1 * rn(dim))}, g
+
+
+def tier2_inputs(dim, ff, dev="cpu"):
+    """(weights, cache K, cache V [H, ctx, 64] bf16, x [D] bf16) of the random-operand cases: all randn."""
+    w, g = random_weights(dim, ff, 81, dev)
+    kc, vc = (torch.randn(dim // 64, TIER2_CTX, 64, generator=g).to(torch.bfloat16).to(dev) for _ in range(2))
+    return w, kc, vc, torch.randn(dim, generator=g).to(torch.bfloat16).to(dev)
+
+
+def tier2_step_inputs(dim, ff, dev="cpu"):
+    """(weights, head, cache K, cache V) of the random step: head = post_w, post_b, lm_w [V, D], lm_b, wte [V, D], all randn."""
+    w, g = random_weights(dim, ff, 91, dev)
+    rn = lambda *s: torch.randn(*s, generator=g).to(torch.bfloat16).to(dev).double()
+    v = TIER2_STEP["vocab"]
+    head = dict(post_w=1 + 0.1 * rn(dim), post_b=0.1 * rn(dim), lm_w=rn(v, dim) / dim ** 0.5, lm_b=0.1 * rn(v), wte=rn(v, dim))
+    head = {k: t.to(torch.bfloat16).double() for k, t in head.items()}
+    return w, head, rn(dim // 64, TIER2_CTX, 64).to(torch.bfloat16), rn(dim // 64, TIER2_CTX, 64).to(torch.bfloat16)
