@@ -860,6 +860,88 @@ md_status md_decode_step_multi_lora(const md_text_model* m, const md_lora_bank* 
                                     const md_kv_cache* kv, int32_t suppress_id, void* logits, int64_t ld_logits, void* workspace,
                                     size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ *
+ * Reasoning queries in lockstep                                       *
+ * ------------------------------------------------------------------ */
+
+/* query(image, question, reasoning=True) (reference: moondream.py:541-618 over :323-432 and :434-539) for B rows as ONE
+ * lockstep decode loop with a phase per row.  With a one-token query suffix the reference's suffix pass (:604) is an
+ * ordinary decode step that feeds the suffix token, so a row is, step by step:
+ *   REASON  feeds the picked token -- or, after a coordinate token, the coordinate encoder's output for the bin the
+ *           coordinate decoder picks on the hidden state that predicted the token (moondream.py:377-389); the step's
+ *           logits lose eos_id and size_id (:397-398);
+ *   then ONE step that feeds suffix_id, nothing suppressed (the pick of a prompt pass, :313-318);
+ *   ANSWER  feeds the picked token; the step's logits lose answer_id (:517);
+ *   DONE    still travels in the lockstep, as finished rows of md_decode_step do.
+ * The very first token of a row is picked by the caller from its prompt pass, nothing suppressed. */
+enum { MD_REASON_PHASE_IDLE = -1, MD_REASON_PHASE_REASON = 0, MD_REASON_PHASE_ANSWER = 1, MD_REASON_PHASE_DONE = 2 };
+enum { MD_REASON_KIND_NONE = 0, MD_REASON_KIND_REASON = 1, MD_REASON_KIND_SUFFIX = 2, MD_REASON_KIND_ANSWER = 3 };
+
+/* The coordinate half of the region head (reference: region.py:32-57): decoder MLP, Fourier matrix, encoder, and the
+ * bin -> value table md_region_pick_encode reads (bf16 [n_bins]: bin / n_bins). */
+typedef struct {
+  md_linear dec_fc1, dec_fc2; /* coordinate decoder MLP: dim -> inner -> n_bins */
+  md_linear encoder;          /* coordinate encoder: 2 * half -> dim */
+  const void* fourier_w;      /* bf16 [1][half] */
+  const void* value_table;    /* bf16 [n_bins] */
+  int32_t half;
+  int32_t n_bins;
+} md_region_coord;
+
+/* A step's view of the rows' reasoning state: device arrays of `batch` entries (suppress: [batch][2]) and the ids. */
+typedef struct {
+  int32_t *phase, *n_reason, *n_answer; /* in / out: MD_REASON_PHASE_*, reasoning / answer tokens kept so far */
+  int32_t *kind, *ground, *suppress;    /* out: MD_REASON_KIND_* of the consumed token, its coordinate bin or -1, the ids to mask */
+  int32_t* coord_bin;                   /* the bin md_region_pick_encode wrote for the row (written by md_decode_step_reason) */
+  void* hidden_prev;                    /* bf16 [batch][dim], in / out: the hidden state that predicted the consumed token */
+  const int32_t* forced;                /* [batch] or NULL: a value >= 0 replaces the consumed token (teacher forcing) */
+  int32_t max_reason, max_answer;
+  int32_t answer_id, eos_id, size_id, coord_id, suffix_id;
+} md_reason_state;
+
+/* The input stage of a step, one workgroup per row.  t = forced[b] if forced != NULL and forced[b] >= 0, else tokens[b].
+ *   phase REASON, t == answer_id or n_reason[b] >= max_reason:  phase = ANSWER, kind = SUFFIX, x = wte[suffix_id],
+ *       suppress = {-1, -1}, ground = -1  (t is fed nowhere and kept nowhere);
+ *   phase REASON otherwise:  kind = REASON, n_reason[b] += 1, suppress = {eos_id, size_id};  t == coord_id: x = coord_emb[b],
+ *       ground = coord_bin[b];  else x = wte[t], ground = -1;
+ *   phase ANSWER, t == eos_id or n_answer[b] >= max_answer:  phase = DONE, kind = NONE, x = wte[t], suppress = {-1, -1};
+ *   phase ANSWER otherwise:  kind = ANSWER, n_answer[b] += 1, x = wte[t], suppress = {answer_id, -1};
+ *   phase DONE:  kind = NONE, x = wte[t], suppress = {-1, -1};
+ *   phase < 0 (idle):  nothing of the row is read or written -- kind, ground, suppress and x keep the caller's contents.
+ * x rows are bit copies of the table row or of coord_emb[b]; a t outside [0, vocab) copies row 0 (never an index out of
+ * range).  hidden_prev is not used here.  dim % 8 == 0; wte, coord_emb, x 16-byte aligned with leading dimensions
+ * (elements) that are multiples of 8.  No host sync, no allocation: capturable.  MD_ERR_INVALID_ARG: a NULL pointer
+ * (forced excepted), batch / vocab / dim <= 0, a negative budget, suffix_id outside [0, vocab), a bad stride. */
+md_status md_reason_route(const md_reason_state* st, const int32_t* tokens, const void* wte, int64_t ld_wte, int32_t vocab,
+                          const void* coord_emb, int64_t ld_coord, void* x, int64_t ldx, int32_t batch, int32_t dim,
+                          void* stream);
+
+/* logits[b][ids[b][k]] = bf16 -inf for k = 0, 1 and every ids[b][k] in [0, vocab) (ids: device int32 [batch][2]).  No other
+ * bit of the row changes; a negative id masks nothing, a row with both ids negative is untouched, equal ids are one
+ * write.  The pick then runs with suppress_id = -1 (md_sample_rows: a greedy row takes its argmax).  Capturable.
+ * MD_ERR_INVALID_ARG: NULL logits / ids, batch <= 0, vocab <= 0, ld < vocab. */
+md_status md_mask_logits_rows(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* ids, void* stream);
+
+/* One reasoning step for the whole batch, device resident; the rows are routed as md_decode_step_shared routes them
+ * (slots == NULL: row b in slot b; prefix_slots == NULL: no shared prefix).  In launch order:
+ *   1. coordinate decoder MLP on st->hidden_prev for ALL rows (there is no skipping it without a host decision), as
+ *      decode-regime GEMMs over blocks of <= 64 rows: a row's bits do not depend on the batch;
+ *   2. md_region_pick_encode -> st->coord_bin;  3. coordinate encoder -> coord_emb;
+ *   4. md_reason_route(st, tokens) -> x;  5. the decoder at pos[b] (q_len 1);  6. the step's hidden -> st->hidden_prev;
+ *   7. md_lm_head -> logits [batch][ld_logits];  8. md_mask_logits_rows(st->suppress);  pos[b] += 1 for every row.
+ * The pick from the masked logits is the caller's launch (md_sample_rows with suppress_id -1).  An idle row
+ * (phase < 0) should carry an idle slot and suppress = {-1, -1}.  bank != NULL (mixed LoRA variants): MD_ERR_UNSUPPORTED.
+ * Argument errors are reported before any launch: NULL pointers / batch <= 0 / negative budgets / ld_logits < vocab
+ * MD_ERR_INVALID_ARG; a region head whose shapes do not chain onto the model's (dec_fc1.k_pad == dim, dec_fc2.k_pad ==
+ * dec_fc1.n_pad, dec_fc2.n == n_bins, encoder.k_pad == 2 * half, encoder.n == encoder.n_pad == dim) MD_ERR_UNSUPPORTED;
+ * workspace below md_decode_reason_workspace_bytes MD_ERR_WORKSPACE. */
+size_t md_decode_reason_workspace_bytes(const md_text_model* m, const md_region_coord* rc, int32_t batch);
+md_status md_decode_step_reason(const md_text_model* m, const md_region_coord* rc, const md_reason_state* st,
+                                const md_lora_bank* bank, const int32_t* tokens, int32_t* pos, int32_t batch,
+                                const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots, const int32_t* prefix_len,
+                                const md_kv_cache* kv, void* logits, int64_t ld_logits, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

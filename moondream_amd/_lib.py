@@ -158,6 +158,22 @@ class MdKvCache(C.Structure):
                 ("k8", c_void_p), ("v8", c_void_p), ("k_scale", c_void_p), ("v_scale", c_void_p)]
 
 
+MD_REASON_PHASE_IDLE, MD_REASON_PHASE_REASON, MD_REASON_PHASE_ANSWER, MD_REASON_PHASE_DONE = -1, 0, 1, 2
+MD_REASON_KIND_NONE, MD_REASON_KIND_REASON, MD_REASON_KIND_SUFFIX, MD_REASON_KIND_ANSWER = 0, 1, 2, 3
+
+
+class MdRegionCoord(C.Structure):
+    _fields_ = [("dec_fc1", MdLinear), ("dec_fc2", MdLinear), ("encoder", MdLinear), ("fourier_w", c_void_p),
+                ("value_table", c_void_p), ("half", c_int32), ("n_bins", c_int32)]
+
+
+class MdReasonState(C.Structure):
+    _fields_ = [("phase", c_void_p), ("n_reason", c_void_p), ("n_answer", c_void_p), ("kind", c_void_p), ("ground", c_void_p),
+                ("suppress", c_void_p), ("coord_bin", c_void_p), ("hidden_prev", c_void_p), ("forced", c_void_p),
+                ("max_reason", c_int32), ("max_answer", c_int32), ("answer_id", c_int32), ("eos_id", c_int32),
+                ("size_id", c_int32), ("coord_id", c_int32), ("suffix_id", c_int32)]
+
+
 # name -> (restype, argtypes): every symbol include/moondream_hip.h declares
 P = C.POINTER
 SIGNATURES = {
@@ -265,6 +281,13 @@ SIGNATURES = {
                                        c_int32, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
     "md_decode_step_shared": (C.c_int, [P(MdTextModel), c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
                                         c_void_p, P(MdKvCache), c_int32, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "md_reason_route": (C.c_int, [P(MdReasonState), c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                                  c_int32, c_int32, c_void_p]),
+    "md_mask_logits_rows": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "md_decode_reason_workspace_bytes": (c_size_t, [P(MdTextModel), P(MdRegionCoord), c_int32]),
+    "md_decode_step_reason": (C.c_int, [P(MdTextModel), P(MdRegionCoord), P(MdReasonState), P(MdLoraBank), c_void_p, c_void_p,
+                                        c_int32, c_void_p, c_int32, c_void_p, c_void_p, P(MdKvCache), c_void_p, c_int64, c_void_p,
+                                        c_size_t, c_void_p]),
 }
 
 

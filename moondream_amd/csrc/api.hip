@@ -1209,6 +1209,103 @@ extern "C" md_status md_decode_step_multi_lora(const md_text_model* m, const md_
   return decode_step_impl(m, tokens, next, pos, batch, rows, kv, suppress_id, logits, ld_logits, workspace, workspace_bytes, stream);
 }
 
+// ------------------------------------------------------------- reasoning queries in lockstep (csrc/sampling_region.hip)
+namespace {
+struct ReasonWs {
+  void *ff, *logits, *feats, *coord_emb, *splitk;
+  size_t splitk_bytes, total;
+};
+ReasonWs reason_layout(const md_region_coord* rc, int batch, void* base) {
+  const size_t B = (size_t)batch;
+  Arena a{(char*)base, 0};
+  ReasonWs w;
+  w.ff = a.take(B * rc->dec_fc1.n_pad * 2);
+  w.logits = a.take(B * rc->dec_fc2.n_pad * 2);
+  w.feats = a.take(B * rc->encoder.k_pad * 2);
+  w.coord_emb = a.take(B * rc->encoder.n_pad * 2);
+  // decode-regime split-K scratch shared by the three linears (stream-ordered); a function of the layer shapes
+  w.splitk_bytes = std::max(std::max(md_gemm_workspace_bytes(&rc->dec_fc1, 64, 1), md_gemm_workspace_bytes(&rc->dec_fc2, 64, 1)),
+                            md_gemm_workspace_bytes(&rc->encoder, 64, 1));
+  w.splitk = a.take(w.splitk_bytes);
+  w.total = a.off;
+  return w;
+}
+// the checks of md_decode_step_reason that need no device
+md_status reason_args_ok(const md_text_model* m, const md_region_coord* rc, const md_reason_state* st) {
+  MD_CHECK_ARG(m && m->blocks && m->wte && rc && st);
+  MD_CHECK_ARG(rc->dec_fc1.w && rc->dec_fc2.w && rc->encoder.w && rc->fourier_w && rc->value_table && rc->half > 0 && rc->n_bins > 0);
+  MD_CHECK_ARG(st->phase && st->n_reason && st->n_answer && st->kind && st->ground && st->suppress && st->coord_bin && st->hidden_prev);
+  MD_CHECK_ARG(st->max_reason >= 0 && st->max_answer >= 0 && st->suffix_id >= 0 && st->suffix_id < m->vocab);
+  if (rc->dec_fc1.k_pad != m->dim || rc->dec_fc2.k_pad != rc->dec_fc1.n_pad || rc->dec_fc2.n != rc->n_bins ||
+      rc->encoder.k_pad != 2 * rc->half || rc->encoder.n != m->dim || rc->encoder.n_pad != m->dim || m->dim % 8 != 0)
+    return MD_ERR_UNSUPPORTED;
+  return MD_OK;
+}
+}  // namespace
+
+extern "C" size_t md_decode_reason_workspace_bytes(const md_text_model* m, const md_region_coord* rc, int32_t batch) {
+  const size_t base = md_decode_workspace_bytes(m, batch);
+  if (base == 0 || rc == nullptr) return 0;
+  return base + reason_layout(rc, batch, nullptr).total;
+}
+
+// reference: one iteration of the loop of moondream.py:357-405 / :512-530 per row, whichever the row is in; device resident
+extern "C" md_status md_decode_step_reason(const md_text_model* m, const md_region_coord* rc, const md_reason_state* st,
+                                           const md_lora_bank* bank, const int32_t* tokens, int32_t* pos, int32_t batch,
+                                           const int32_t* slots, int32_t n_slots, const int32_t* prefix_slots,
+                                           const int32_t* prefix_len, const md_kv_cache* kv, void* logits, int64_t ld_logits,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  MD_TRY(reason_args_ok(m, rc, st));
+  MD_CHECK_ARG(tokens && pos && kv && logits && workspace && batch > 0 && ld_logits >= m->vocab);
+  if (bank != nullptr) return MD_ERR_UNSUPPORTED;
+  const RowMap rows{slots, n_slots, prefix_slots, prefix_len};
+  MD_TRY(shared_args_ok(kv, rows));
+  MD_CHECK_ARG(tile_policy_ok(m->tile_policy));
+  if (workspace_bytes < md_decode_reason_workspace_bytes(m, rc, batch)) return MD_ERR_WORKSPACE;
+  TilePolicyScope tile_scope(m->tile_policy);
+  hipStream_t s = (hipStream_t)stream;
+  const int D = m->dim;
+  Arena a{(char*)workspace, 0};
+  void* x = a.take((size_t)batch * D * 2);
+  void* lmws = a.take(md_lm_head_workspace_bytes(m, batch));
+  const ReasonWs w = reason_layout(rc, batch, a.take(0));
+  a.take(w.total);
+  void* tws = a.take(0);
+  const size_t tws_bytes = workspace_bytes - a.off;
+  // 1-3: the coordinate every row WOULD feed -- bin from the hidden state that predicted its token, re-encoded
+  // (moondream.py:377-389).  Blocks of 64 rows: every launch in the decode regime, whatever the batch.
+  if (w.splitk_bytes) MD_TRY(zero_fill(w.splitk, 8192, s));  // arrival tickets
+  const int64_t ffld = rc->dec_fc1.n_pad, lgld = rc->dec_fc2.n_pad, ftld = rc->encoder.k_pad;
+  for (int b0 = 0; b0 < batch; b0 += 64) {
+    const int nb = std::min(64, batch - b0);
+    MD_TRY(gemm((const char*)st->hidden_prev + (int64_t)b0 * D * 2, D, rc->dec_fc1, (char*)w.ff + b0 * ffld * 2, ffld, nb,
+                MD_EPI_GELU, nullptr, 0, 0, 1, s, w.splitk, w.splitk_bytes));
+    MD_TRY(gemm((const char*)w.ff + b0 * ffld * 2, ffld, rc->dec_fc2, (char*)w.logits + b0 * lgld * 2, lgld, nb, MD_EPI_BIAS, nullptr,
+                0, 0, 1, s, w.splitk, w.splitk_bytes));
+  }
+  MD_TRY(md_region_pick_encode(w.logits, lgld, batch, 1, rc->n_bins, rc->value_table, rc->fourier_w, rc->half, st->coord_bin, 1,
+                               w.feats, ftld, s));
+  for (int b0 = 0; b0 < batch; b0 += 64) {
+    const int nb = std::min(64, batch - b0);
+    MD_TRY(gemm((const char*)w.feats + b0 * ftld * 2, ftld, rc->encoder, (char*)w.coord_emb + (int64_t)b0 * D * 2, D, nb, MD_EPI_BIAS,
+                nullptr, 0, 0, 1, s, w.splitk, w.splitk_bytes));
+  }
+  // 4: each row's input embedding, phase and the ids its logits lose
+  MD_TRY(md_reason_route(st, tokens, m->wte, D, m->vocab, w.coord_emb, D, x, D, batch, D, s));
+  // 5-7: as decode_step_impl
+  MD_TRY(text_forward_impl(m, x, x, batch, 1, pos, rows, kv, tws, tws_bytes, s));
+  if (hipMemcpyAsync(st->hidden_prev, x, (size_t)batch * D * 2, hipMemcpyDeviceToDevice, s) != hipSuccess) return MD_ERR_LAUNCH;
+  if (decode_tall_rows(m, batch, 1) && !(kv->k8 && kv->v8)) {
+    md_text_model tallm = *m;
+    tallm.tile_policy = MD_TILE_DECODE_TALL;
+    MD_TRY(md_lm_head(&tallm, x, batch, 1, logits, ld_logits, lmws, md_lm_head_workspace_bytes(m, batch), s));
+  } else {
+    MD_TRY(md_lm_head(m, x, batch, 1, logits, ld_logits, lmws, md_lm_head_workspace_bytes(m, batch), s));
+  }
+  // 8: the suppression of the row's phase; pos[b] += 1
+  return md_mask_logits_advance(logits, ld_logits, batch, m->vocab, st->suppress, pos, s);
+}
+
 extern "C" size_t md_decode_step_b1_workspace_bytes(const md_text_model* m) {
   if (!m || !m->blocks) return 0;
   return align_up(md_decode_b1_workspace_bytes(m));

@@ -4,7 +4,7 @@
 //     images needs no host round trip per coordinate;
 //   * temperature / top-p sampling (reference: moondream.py:270-278, 313-318, 521-528).
 // HBM-bound row kernels: one workgroup per sequence, 16-byte loads, wave shuffles.
-#include "md_common.hpp"
+#include "text_internal.hpp"
 
 namespace {
 
@@ -446,7 +446,118 @@ __global__ __launch_bounds__(LOGPROB_THREADS) void token_logprobs_kernel(const b
   }
 }
 
+// ---------------------------------------------------------------------------
+// The reasoning query's control flow, per row, on the device (reference: moondream.py:323-432 then :434-539 after the
+// suffix pass of :604): which embedding the row feeds to this decode step, which ids the step's logits lose before the
+// pick, and when the row moves from reasoning to answering to done.  One workgroup per row; the row's state is a few
+// words that every wave reads BEFORE thread 0 rewrites them (the barrier), the embedding is a 16-byte-chunk copy.
+struct ReasonRoute {
+  const int32_t *tokens, *forced, *coord_bin;
+  int32_t *phase, *n_reason, *n_answer, *kind, *ground, *suppress;
+  int max_reason, max_answer, answer_id, eos_id, size_id, coord_id, suffix_id, vocab;
+  const bf16_t *wte, *coord_emb;
+  int64_t ld_wte, ld_coord, ldx;
+  bf16_t* x;
+  int dim;
+};
+
+__global__ __launch_bounds__(256) void reason_route_kernel(ReasonRoute a) {
+  const int b = blockIdx.x;
+  const int ph = a.phase[b];
+  if (ph < 0) return;  // idle: taken by the whole workgroup, before the barrier; nothing of the row is read or written
+  int t = a.tokens[b];
+  if (a.forced) {
+    const int f = a.forced[b];
+    if (f >= 0) t = f;
+  }
+  const int nr = a.n_reason[b], na = a.n_answer[b];
+  __syncthreads();
+  int nph = ph, kind = MD_REASON_KIND_NONE, ground = -1, s0 = -1, s1 = -1, src = t, nr2 = nr, na2 = na;
+  bool from_coord = false;
+  if (ph == MD_REASON_PHASE_REASON) {
+    if (t == a.answer_id || nr >= a.max_reason) {  // the loop of moondream.py:357 ends; the suffix pass (:604) is this step
+      nph = MD_REASON_PHASE_ANSWER;
+      kind = MD_REASON_KIND_SUFFIX;
+      src = a.suffix_id;
+    } else {
+      kind = MD_REASON_KIND_REASON;
+      nr2 = nr + 1;
+      s0 = a.eos_id;  // moondream.py:397-398
+      s1 = a.size_id;
+      if (t == a.coord_id) {
+        from_coord = true;
+        ground = a.coord_bin[b];
+      }
+    }
+  } else if (ph == MD_REASON_PHASE_ANSWER) {
+    if (t == a.eos_id || na >= a.max_answer) {
+      nph = MD_REASON_PHASE_DONE;
+    } else {
+      kind = MD_REASON_KIND_ANSWER;
+      na2 = na + 1;
+      s0 = a.answer_id;  // moondream.py:517
+    }
+  }
+  if (src < 0 || src >= a.vocab) src = 0;  // never a table index out of range (a finished row's token is whatever was picked)
+  const u32x4* from = (const u32x4*)(from_coord ? a.coord_emb + (int64_t)b * a.ld_coord : a.wte + (int64_t)src * a.ld_wte);
+  u32x4* to = (u32x4*)(a.x + (int64_t)b * a.ldx);
+  for (int ch = threadIdx.x; ch < (a.dim >> 3); ch += 256) to[ch] = from[ch];
+  if (threadIdx.x == 0) {
+    a.phase[b] = nph;
+    a.n_reason[b] = nr2;
+    a.n_answer[b] = na2;
+    a.kind[b] = kind;
+    a.ground[b] = ground;
+    a.suppress[2 * b] = s0;
+    a.suppress[2 * b + 1] = s1;
+  }
+}
+
+// logits[b][ids[b][k]] = -inf (bf16 0xff80) for the ids inside [0, vocab); optionally pos[b] += 1 (the step's advance)
+__global__ __launch_bounds__(64) void mask_logits_rows_kernel(bf16_t* __restrict__ logits, int64_t ld, int vocab,
+                                                              const int32_t* __restrict__ ids, int32_t* __restrict__ pos_inc) {
+  const int b = blockIdx.x, k = threadIdx.x;
+  if (k < 2) {
+    const int id = ids[2 * b + k];
+    if (id >= 0 && id < vocab) logits[(int64_t)b * ld + id] = (bf16_t)0xff80;
+  }
+  if (k == 2 && pos_inc) pos_inc[b] += 1;
+}
+
 }  // namespace
+
+extern "C" md_status md_reason_route(const md_reason_state* st, const int32_t* tokens, const void* wte, int64_t ld_wte,
+                                     int32_t vocab, const void* coord_emb, int64_t ld_coord, void* x, int64_t ldx,
+                                     int32_t batch, int32_t dim, void* stream) {
+  MD_CHECK_ARG(st && tokens && wte && coord_emb && x && batch > 0 && vocab > 0 && dim > 0 && dim % 8 == 0);
+  MD_CHECK_ARG(st->phase && st->n_reason && st->n_answer && st->kind && st->ground && st->suppress && st->coord_bin);
+  MD_CHECK_ARG(st->max_reason >= 0 && st->max_answer >= 0 && st->suffix_id >= 0 && st->suffix_id < vocab);
+  MD_CHECK_ARG(ld_wte >= dim && ld_coord >= dim && ldx >= dim && ld_wte % 8 == 0 && ld_coord % 8 == 0 && ldx % 8 == 0);
+  MD_CHECK_ARG((((uintptr_t)wte | (uintptr_t)coord_emb | (uintptr_t)x) & 15) == 0);
+  ReasonRoute a;
+  a.tokens = tokens; a.forced = st->forced; a.coord_bin = st->coord_bin;
+  a.phase = st->phase; a.n_reason = st->n_reason; a.n_answer = st->n_answer; a.kind = st->kind; a.ground = st->ground;
+  a.suppress = st->suppress;
+  a.max_reason = st->max_reason; a.max_answer = st->max_answer; a.answer_id = st->answer_id; a.eos_id = st->eos_id;
+  a.size_id = st->size_id; a.coord_id = st->coord_id; a.suffix_id = st->suffix_id; a.vocab = vocab;
+  a.wte = (const bf16_t*)wte; a.coord_emb = (const bf16_t*)coord_emb; a.ld_wte = ld_wte; a.ld_coord = ld_coord; a.ldx = ldx;
+  a.x = (bf16_t*)x; a.dim = dim;
+  hipLaunchKernelGGL(reason_route_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, a);
+  return md_launch_status();
+}
+
+// internal (api.hip): the mask that also advances pos
+md_status md_mask_logits_advance(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* ids, int32_t* pos,
+                                 hipStream_t stream) {
+  hipLaunchKernelGGL(mask_logits_rows_kernel, dim3(batch), dim3(64), 0, stream, (bf16_t*)logits, ld, vocab, ids, pos);
+  return md_launch_status();
+}
+
+extern "C" md_status md_mask_logits_rows(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* ids,
+                                         void* stream) {
+  MD_CHECK_ARG(logits && ids && batch > 0 && vocab > 0 && ld >= vocab);
+  return md_mask_logits_advance(logits, ld, batch, vocab, ids, nullptr, (hipStream_t)stream);
+}
 
 extern "C" md_status md_fourier_features(const void* x, int64_t ldx, int32_t rows, int32_t in_dim, const void* w,
                                          int32_t half, void* out, int64_t ld_out, void* stream) {

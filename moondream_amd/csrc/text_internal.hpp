@@ -69,6 +69,9 @@ md_status md_stitch_pool_batched(const void* feats, void* out, int64_t ld_out, i
                                  int32_t dim, int32_t grid, int32_t margin, int32_t tiles_h, int32_t tiles_w, hipStream_t stream);
 md_status md_pool_grid_concat(const void* global_feats, const void* grid_feats, int32_t H, int32_t W, void* out, int64_t ld_out,
                               int32_t dim, int32_t grid, hipStream_t stream);
+// sampling_region.hip: md_mask_logits_rows that also advances pos (pos == nullptr: the public form)
+md_status md_mask_logits_advance(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* ids, int32_t* pos,
+                                 hipStream_t stream);
 // lora_multi.hip
 md_status lora_bank_ok(const md_lora_bank* bank);
 int32_t md_lora_shrink_cols(const md_lora_bank* bank, int32_t pairs);

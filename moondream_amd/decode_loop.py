@@ -1,7 +1,7 @@
 """What the lockstep loop (``MoondreamModel._decode_greedy_impl``) and the continuous engine (``ContinuousEngine._step``)
 share: the description of a chunk of consecutive decode steps over fixed buffers, and the one runner that launches it.
-``run_chunk`` holds the only step body of the package -- decode step, then the optional sampling pick, then the optional
-log-probability launch -- and the only decode graph key.  No torch here: the runner moves no data, it orders launches."""
+``run_chunk`` holds the only step body of the package -- decode step (or, for a reasoning query, the reasoning step), then
+the optional sampling pick, then the optional log-probability launch -- and the only decode graph key.  No torch here: the runner moves no data, it orders launches."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -27,6 +27,37 @@ class Sampling:
 
 
 @dataclass(frozen=True, eq=False)
+class ReasonChunk:
+    """The reasoning state of a chunk (``query(reasoning=True)`` in lockstep: md_decode_step_reason), all device memory at
+    fixed addresses.  Per row (int32 [b] unless said): ``phase``, ``n_reason``, ``n_answer``, ``suppress`` [b, 2],
+    ``coord_bin`` and ``hidden_prev`` (bf16 [b, D]: the hidden state that predicted the token a step consumes) are read and
+    rewritten by every step.  Per step, int32 planes [>= n, b]: step i writes ``kind[i]`` / ``ground[i]`` -- what the token
+    it consumed was (MD_REASON_KIND_*) and its coordinate bin, or -1 -- and, when ``forced`` is given, consumes
+    ``forced[i][r]`` instead of the picked token wherever that is >= 0 (teacher forcing).  ``max_reason`` / ``max_answer``
+    bound the two phases; ``region`` is the coordinate head's struct (``_lib.MdRegionCoord``)."""
+
+    phase: Any
+    n_reason: Any
+    n_answer: Any
+    suppress: Any
+    coord_bin: Any
+    hidden_prev: Any
+    kind: Any
+    ground: Any
+    max_reason: int
+    max_answer: int
+    region: Any
+    forced: Any = None
+
+    def key(self) -> tuple:
+        """What a captured chunk bakes in of the reasoning state: addresses and the two budgets."""
+        return ("reason",) + tuple(t.data_ptr() for t in (self.phase, self.n_reason, self.n_answer, self.suppress, self.coord_bin,
+                                                          self.hidden_prev, self.kind, self.ground)) + (
+            self.forced.data_ptr() if self.forced is not None else 0, int(self.max_reason), int(self.max_answer),
+            int(self.region.dec_fc1.w or 0))
+
+
+@dataclass(frozen=True, eq=False)
 class DecodeChunk:
     """What ``n`` consecutive decode steps over ``b`` rows read and write, all at fixed addresses: step i consumes
     ``tokens[i]`` and writes ``tokens[i + 1]`` (int32 [>= n + 1, b]); ``pos`` (int32 [b]) is advanced by the steps;
@@ -35,7 +66,9 @@ class DecodeChunk:
     ``uniforms[i]`` (fp32 [>= n, b]) with the call's settings (``_pick``) or each row's own (``_pick_rows``).
     ``logprobs`` = (fp32, int32) planes [>= n, b]: row i takes the log-probability and rank of the tokens of step i.
     ``b1``: the single-sequence persistent kernel takes the steps (b = 1, greedy).  ``step(tok_in) -> logits``: the step
-    made from its pieces instead of the fused one (a LoRA adapter; eager only, its pick writes ``tokens[i + 1]``)."""
+    made from its pieces instead of the fused one (a LoRA adapter; eager only, its pick writes ``tokens[i + 1]``).
+    ``reason`` (``ReasonChunk``): the steps are md_decode_step_reason's -- each row's phase decides what it feeds and which
+    ids its logits lose (``suppress_id`` is not used), and every step's pick is the per-row one; not with ``logprobs``."""
 
     b: int
     tokens: Any
@@ -48,6 +81,7 @@ class DecodeChunk:
     logprobs: Optional[Tuple[Any, Any]] = None
     b1: bool = False
     step: Optional[Callable[[Any], Any]] = None
+    reason: Optional[ReasonChunk] = None
 
 
 def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_stream: Optional[int] = None,
@@ -56,9 +90,10 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     stream: the chunk is replayed from the graph captured for it on that stream, or, first, run eagerly and captured
     (``model._replay_or_capture``; ``may_capture`` as it takes it).  The key starts (``tag``, stream) and names everything the
     launches bake in.  Returns True when it captured.  Of the model it uses _decode_logits, _workspace, _kv_struct,
-    _decode_step, _decode_step_b1, _pick, _pick_rows, _token_logprobs and _replay_or_capture."""
+    _decode_step, _decode_step_b1, _decode_step_reason, _pick, _pick_rows, _token_logprobs and _replay_or_capture."""
     c = chunk
     pieces = c.step is not None
+    assert c.reason is None or (not pieces and not c.b1 and c.logprobs is None and c.pick is not None and c.pick.per_row)
     assert not (pieces and (capture_stream is not None or c.b1))
     assert not c.b1 or (c.b == 1 and c.pick is None)
     if not pieces:
@@ -72,6 +107,11 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     def body():
         for i in range(n):
             tok_in, tok_out = c.tokens[i], c.tokens[i + 1]
+            if c.reason is not None:
+                # the step masks its logits per row and leaves the pick to the per-row kernel, nothing suppressed there
+                model._decode_step_reason(c.rows_of(i), c.reason, i, tok_in, c.pos, c.b, logits, ws, kv)
+                model._pick_rows(left, c.pick.temperature, c.pick.top_p, -1, c.uniforms[i], out=tok_out)
+                continue
             if c.b1:
                 model._decode_step_b1(tok_in, tok_out, c.pos, c.suppress_id, logits, ws, kv)
             elif not pieces:
@@ -101,4 +141,6 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
            logits.data_ptr(), c.b1, pick, c.uniforms.data_ptr() if c.uniforms is not None else 0) + c.rows_of(0).key()
     if lp is not None:  # a chunk with the logprob launches is another graph; without them key and graph are unchanged
         key += ("logprobs", lp.data_ptr(), rk.data_ptr())
+    if c.reason is not None:  # likewise: another graph, keyed by the state's addresses
+        key += c.reason.key()
     return model._replay_or_capture(key, body, may_capture=may_capture)

@@ -29,7 +29,7 @@ from PIL import Image
 
 from . import _lib
 from .config import MoondreamConfig
-from .decode_loop import DecodeChunk, Sampling, run_chunk
+from .decode_loop import DecodeChunk, ReasonChunk, Sampling, run_chunk
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
 from .lora import variant_state_dict
@@ -687,6 +687,33 @@ class MoondreamModel:
             ),
             rows.step_entry,
         )
+
+    def _decode_step_reason(self, rows: _Rows, reason: ReasonChunk, i: int, tok_in: torch.Tensor, pos_buf: torch.Tensor, b: int,
+                            logits: torch.Tensor, ws: torch.Tensor, kv: _lib.MdKvCache):
+        """Step ``i`` of a reasoning chunk over b rows (md_decode_step_reason): region head on the previous hidden state ->
+        each row's input by its phase -> decoder -> lm_head -> the phase's ids masked in ``logits`` [b, V]; the pick is the
+        caller's.  Routing: contiguous, a slot table or a shared prefix; no adapters."""
+        if rows.kind not in ("", "_slots", "_shared"):
+            raise ValueError("the reasoning step is not served with LoRA adapters")
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        st = _lib.MdReasonState(
+            reason.phase.data_ptr(), reason.n_reason.data_ptr(), reason.n_answer.data_ptr(), reason.kind[i].data_ptr(),
+            reason.ground[i].data_ptr(), reason.suppress.data_ptr(), reason.coord_bin.data_ptr(), reason.hidden_prev.data_ptr(),
+            reason.forced[i].data_ptr() if reason.forced is not None else None, int(reason.max_reason), int(reason.max_answer),
+            *self._reason_ids())
+        _lib.check(
+            self.lib.md_decode_step_reason(
+                C.byref(self.w.text), C.byref(reason.region), C.byref(st), None, tok_in.data_ptr(), pos_buf.data_ptr(), b,
+                ptr(rows.slots), rows.n_slots, ptr(rows.prefix_slots), ptr(rows.prefix_len), C.byref(kv), logits.data_ptr(),
+                self.config.text.vocab_size, ws.data_ptr(), ws.numel(), self._stream(),
+            ),
+            "md_decode_step_reason",
+        )
+
+    def _reason_ids(self) -> Tuple[int, int, int, int, int]:
+        """(answer_id, eos_id, size_id, coord_id, suffix_id) of md_reason_state."""
+        tk = self.config.tokenizer
+        return tk.answer_id, tk.eos_id, tk.size_id, tk.coord_id, int(tk.templates["query"]["suffix"][0])
 
     def _decode_step_b1(self, tok_in: torch.Tensor, tok_out: torch.Tensor, pos_buf: torch.Tensor, suppress_id: int,
                         logits: torch.Tensor, ws: torch.Tensor, kv: _lib.MdKvCache):
@@ -1943,7 +1970,20 @@ class MoondreamModel:
             for q in questions
         ]
 
-    def batch_query(self, images, questions: Sequence[str], settings: Optional[dict] = None) -> List[str]:
+    def batch_query(self, images, questions: Sequence[str], settings: Optional[dict] = None, reasoning: bool = False):
+        """Answers for B (image, question) pairs in lockstep: a list of strings.
+        ``reasoning=True``: a list of ``{"reasoning": {"text", "grounding"}, "answer": str}`` -- element i is what
+        ``query(images[i], questions[i], reasoning=True, settings=settings)`` returns (reference: moondream.py:541-618), with
+        the whole control flow on the device: one lockstep decode loop in which every row is reasoning, being fed the query
+        suffix, answering or done (md_decode_step_reason).  ``settings``: ``temperature`` / ``top_p`` /
+        ``max_tokens`` (defaults 0.5 / 0.3 / 768; ``max_tokens`` bounds the reasoning and the answer separately, as in the
+        reference) and ``generator``.  At ``{"temperature": 0}`` the ids are the single-sequence path's (bit for bit under
+        ``set_strict_batch_invariance``).  A sampled row draws one uniform per step, taken up front from the call's generator
+        on the device (the step that feeds the suffix token consumes a draw like any other), where ``query`` draws per token:
+        the same distribution per decision, other ids.  Not served, NotImplementedError: LoRA ``variant`` / ``variants``, the fp8
+        modes, a query template whose suffix is not one token, a checkpoint without a region head."""
+        if reasoning:
+            return self._reasoning_answers(self._batch_query_reasoning(images, questions, settings, share_prefix=False))
         ids = self.batch_generate_ids(images, self._query_prompts(questions), **self._sampling_kwargs(settings))
         return [self.tokenizer.decode(s) for s in ids]
 
@@ -2338,6 +2378,191 @@ class MoondreamModel:
             out.append(objs)
         return out
 
+    # ------------------------------------------------- reasoning queries in lockstep
+    def _region_coord(self) -> _lib.MdRegionCoord:
+        """The coordinate half of the region head as md_decode_step_reason takes it (kept: a captured chunk bakes it in)."""
+        if getattr(self, "_region_coord_struct", None) is None:
+            r, tabs = self._region()
+            fw = r["coord_features"]
+            self._region_coord_struct = _lib.MdRegionCoord(
+                r["coord_dec_fc1"].struct(), r["coord_dec_fc2"].struct(), r["coord_encoder"].struct(), fw.data_ptr(),
+                tabs["coord"].data_ptr(), int(fw.shape[1]), int(self.config.region.coord_out_dim))
+        return self._region_coord_struct
+
+    def _reason_buffers(self, stream, b: int, n: int):
+        """The fixed buffers of the reasoning loop: the rows' state per (stream, b) -- it lives across the chunks of a call
+        -- and the per-step planes per (stream, b, n).  Captured chunks keep these addresses."""
+        fixed = self.__dict__.setdefault("_reason_bufs", {})
+        i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=self._device)
+        f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=self._device)
+        if (stream, b) not in fixed:
+            fixed[stream, b] = dict(phase=i32(b), n_reason=i32(b), n_answer=i32(b), suppress=i32(b, 2), coord_bin=i32(b), pos=i32(b),
+                                    hidden_prev=torch.zeros(b, self.config.text.dim, dtype=BF16, device=self._device),
+                                    temperature=f32(b), top_p=f32(b))
+        if (stream, b, n) not in fixed:
+            fixed[stream, b, n] = dict(tokens=i32(n + 1, b), kind=i32(n, b), ground=i32(n, b), forced=i32(n, b), uniforms=f32(n, b))
+        return fixed[stream, b], fixed[stream, b, n]
+
+    def _reason_loop(self, hidden: torch.Tensor, first: torch.Tensor, pos: Sequence[int], rows: Union[int, _Rows], max_tokens: int,
+                     sampling: Optional[Sampling] = None, forced: Optional[torch.Tensor] = None, check_every: int = 16,
+                     on_chunk=None) -> List[dict]:
+        """The loops of moondream.py:323-432 (reasoning), the suffix pass of :604 and :434-539 (answer) for B sequences as
+        ONE lockstep decode loop with a phase per row (md_decode_step_reason), the counterpart of ``_points_loop``.
+        ``hidden`` [B, D]: the last prompt position, ``first`` int32 [B]: the token picked from the prompt pass (nothing
+        suppressed), ``pos[b]``: the next position, ``rows``: the routing.  ``max_tokens`` bounds each phase separately.
+        At most 2 * max_tokens + 1 steps (every reasoning token, the suffix, every answer token), bounded by the context as
+        ``_decode_greedy_impl`` bounds it, in chunks of ``check_every``: eager, or with ``compile()`` replayed from a captured
+        graph; both over the fixed buffers of ``_reason_buffers``.  One D2H copy of the phases per chunk boundary decides
+        whether every row is done.  ``sampling``: the call's settings (None: greedy); a sampled row draws one uniform per
+        step, taken up front from the generator -- the step that feeds the suffix token consumes one like any other.
+        ``forced``: int32 [steps, B], -1 = not forced: the token a step consumes instead of the picked one (tests).
+        ``on_chunk(step0, n, state, planes)``: called after every chunk (tests: the buffers of the steps just run).
+        Returns per row ``{"reasoning_ids", "answer_ids", "text", "grounding", "pos"}``: ``text`` / ``grounding`` as
+        ``_generate_reasoning`` builds them, ``pos`` the position after the reasoning tokens (what it returns)."""
+        rows = _Rows.of(rows)
+        b = first.shape[0]
+        t, tk = self.config.text, self.config.tokenizer
+        self._ensure_batch(rows.span(b))
+        pos_list = [int(p) for p in pos]
+        assert len(pos_list) == b and hidden.shape[0] == b
+        max_steps = max(0, min(2 * max_tokens + 1, t.max_context - 1 - max(pos_list)))
+        region = self._region_coord()
+        need = self.lib.md_decode_reason_workspace_bytes(C.byref(self.w.text), C.byref(region), b)
+        graphs = self.use_graphs
+        stream = torch.cuda.current_stream(self._device).cuda_stream
+        per = max(1, min(check_every or 16, max(1, max_steps)))
+        state, _ = self._reason_buffers(stream, b, per)
+        state["phase"].fill_(_lib.MD_REASON_PHASE_REASON)
+        state["n_reason"].zero_()
+        state["n_answer"].zero_()
+        state["suppress"].fill_(-1)
+        state["hidden_prev"].copy_(hidden.reshape(b, -1))
+        state["pos"].copy_(self._h2d(torch.tensor(pos_list, dtype=torch.int32)))
+        state["temperature"].fill_(float(sampling.temperature) if sampling is not None else 0.0)
+        state["top_p"].fill_(float(sampling.top_p) if sampling is not None else 1.0)
+        pick = Sampling(state["temperature"], state["top_p"])
+        uniforms = None
+        if sampling is not None and max_steps:
+            uniforms = torch.rand(max_steps, b, device=self._device, dtype=torch.float32, generator=sampling.generator)
+            if sampling.row_perm is not None:
+                uniforms = uniforms[:, sampling.row_perm].contiguous()
+        if forced is not None:
+            forced = forced.to(device=self._device, dtype=torch.int32)
+            assert forced.dim() == 2 and forced.shape[1] == b
+            if forced.shape[0] < max_steps:
+                forced = torch.cat([forced, torch.full((max_steps - forced.shape[0], b), -1, dtype=torch.int32, device=self._device)])
+        hist = torch.zeros(3, max_steps + 1, b, dtype=torch.int32, device=self._device)  # tokens, kind, ground (row i: step i)
+        hist[0, 0] = first
+        steps = 0
+        while steps < max_steps:
+            n = min(per, max_steps - steps)
+            state, planes = self._reason_buffers(stream, b, n)
+            planes["tokens"][0] = hist[0, steps]
+            if uniforms is not None:
+                planes["uniforms"].copy_(uniforms[steps : steps + n])
+            if forced is not None:
+                planes["forced"].copy_(forced[steps : steps + n])
+            reason = ReasonChunk(state["phase"], state["n_reason"], state["n_answer"], state["suppress"], state["coord_bin"],
+                                 state["hidden_prev"], planes["kind"], planes["ground"], max_tokens, max_tokens, region,
+                                 planes["forced"] if forced is not None else None)
+            chunk = DecodeChunk(b, planes["tokens"], state["pos"], lambda i: rows, -1, need, pick, planes["uniforms"], reason=reason)
+            run_chunk(self, chunk, n, tag="reason", capture_stream=stream if graphs else None)
+            hist[0, steps + 1 : steps + n + 1] = planes["tokens"][1:]
+            hist[1, steps : steps + n] = planes["kind"]
+            hist[2, steps : steps + n] = planes["ground"]
+            if on_chunk is not None:
+                on_chunk(steps, n, state, planes)
+            steps += n
+            if steps < max_steps and bool((state["phase"] == _lib.MD_REASON_PHASE_DONE).all()):
+                break
+        self.last_reason_steps = steps  # (tools/bench_reasoning.py: the decode steps the call ran)
+        toks_h, kind_h, ground_h = hist[:, :steps].cpu().tolist() if steps else ([], [], [])
+        forced_h = forced[:steps].cpu().tolist() if forced is not None and steps else None
+        n_bins = self.config.region.coord_out_dim
+        out = []
+        for r in range(b):
+            reasoning, answer = [], []
+            text_chunks: List[List[int]] = [[]]
+            bins: List[List[int]] = [[]]
+            for i in range(steps):
+                tok = forced_h[i][r] if forced_h is not None and forced_h[i][r] >= 0 else toks_h[i][r]
+                if kind_h[i][r] == _lib.MD_REASON_KIND_REASON:
+                    reasoning.append(tok)
+                    if tok in (tk.start_ground_points_id, tk.end_ground_id):
+                        text_chunks.append([])
+                        bins.append([])
+                    text_chunks[-1].append(tok)
+                    if tok == tk.coord_id:
+                        bins[-1].append(ground_h[i][r])
+                elif kind_h[i][r] == _lib.MD_REASON_KIND_ANSWER:
+                    answer.append(tok)
+            texts = [self.tokenizer.decode(c) for c in text_chunks]
+            grounding, start = [], 0
+            for txt, bn in zip(texts, bins):
+                g = (torch.tensor(bn, dtype=torch.int64) / n_bins).tolist()  # moondream.py:381: int64 / int, as a float
+                if len(g) > 1:
+                    pts = [(g[i], g[i + 1]) for i in range(0, len(g) - (len(g) % 2), 2)]
+                    grounding.append({"start_idx": start, "end_idx": start + len(txt), "points": pts})
+                start += len(txt)
+            out.append({"reasoning_ids": reasoning, "answer_ids": answer, "text": "".join(texts), "grounding": grounding,
+                        "pos": pos_list[r] + len(reasoning)})
+        return out
+
+    def _check_reasoning_served(self, settings: Optional[dict]) -> None:
+        """What the batched reasoning query does not serve raises NotImplementedError, naming the reason."""
+        st = settings or {}
+        if st.get("variant") is not None or st.get("variants") is not None:
+            raise NotImplementedError("batched reasoning queries are not served with LoRA variants (variant / variants): "
+                                      "use query(reasoning=True) per image")
+        if self._kv8_scales is not None or bool(self.w.text.fp8) or bool(self.w.text.f8):
+            raise NotImplementedError("batched reasoning queries are not served in the fp8 modes")
+        tpl = self.config.tokenizer.templates["query"]
+        if tpl is None:
+            raise NotImplementedError("Model does not support querying.")
+        if len(tpl["suffix"]) != 1:
+            raise NotImplementedError(f"batched reasoning queries need a one-token query suffix (the suffix pass is one decode "
+                                      f"step); this template's has {len(tpl['suffix'])} tokens")
+        if self.w.region is None:
+            raise NotImplementedError("batched reasoning queries need a region head (grounding): checkpoint has no region head")
+
+    def _batch_query_reasoning(self, images, questions: Sequence[str], settings: Optional[dict], share_prefix: bool,
+                               forced: Optional[torch.Tensor] = None) -> List[dict]:
+        """``batch_query(reasoning=True)`` / ``query_many_reasoning``: ``_reason_loop``'s rows in the caller's order.
+        ``forced`` [steps, B] in the caller's row order (tests)."""
+        self._check_reasoning_served(settings)
+        if len(images) != len(questions) or not len(images):
+            raise ValueError("batch_query: one question per image, at least one")
+        tk = self.config.tokenizer
+        tpl = tk.templates["query"]
+        st = settings or {}
+        max_tokens = st.get("max_tokens", DEFAULT_MAX_TOKENS)
+        temperature, top_p = st.get("temperature", DEFAULT_TEMPERATURE), st.get("top_p", DEFAULT_TOP_P)
+        # moondream.py:586-603: [prefix | question | suffix | thinking]
+        prompts = [list(tpl["prefix"]) + list(self.tokenizer.encode(q).ids) + list(tpl["suffix"]) + [tk.thinking_id] for q in questions]
+        marks: list = []
+        mark = lambda name: self._mark(marks, name)
+        with torch.inference_mode():
+            sampling = None if temperature == 0 else Sampling(float(temperature), float(top_p), st.get("generator"))
+            if share_prefix:
+                order, first, hidden, next_pos, rows, sampling = self._prepare_sequences_shared(list(images), prompts, mark, sampling)
+            else:
+                rows = _Rows()
+                order, first, hidden, next_pos = self._prepare_sequences(list(images), prompts, mark, rows, fuse=True, sampling=sampling)
+            if forced is not None:
+                forced = forced.to(self._device)[:, torch.tensor(list(order), device=self._device)]
+            res = self._reason_loop(hidden, first, next_pos, rows, max_tokens, sampling, forced)
+            mark("reason_loop")
+        self._phase_times(marks)
+        out: List[Optional[dict]] = [None] * len(order)
+        for slot, src in enumerate(order):
+            out[src] = res[slot]
+        return out  # type: ignore[return-value]
+
+    def _reasoning_answers(self, rows: List[dict]) -> List[dict]:
+        """``_reason_loop``'s rows in the shape ``query(reasoning=True)`` returns."""
+        return [{"reasoning": {"text": r["text"], "grounding": r["grounding"]}, "answer": self.tokenizer.decode(r["answer_ids"])}
+                for r in rows]
+
     def _generate_points(self, hidden: torch.Tensor, next_token: torch.Tensor, pos: int, include_size: bool = True,
                          max_objects: int = DEFAULT_MAX_OBJECTS):
         """reference: moondream.py:653-733 (B = 1 form of the lockstep loop; KV slot 0)."""
@@ -2385,11 +2610,20 @@ class MoondreamModel:
         """Many questions about ONE image (reference pattern: encode_image once, then query per question,
         moondream.py:230-268,620-623), answered in one batch that reads a single copy of the image's KV prefix.  Element i ==
         ``{"answer": batch_query([encode_image(image)] * N, questions)[i]}``, in the bf16 mode and in the fp8 KV mode.  A LoRA
-        ``variant`` (settings) takes the copy path, with the same results."""
+        ``variant`` (settings) takes the copy path, with the same results.  With reasoning: ``query_many_reasoning``."""
         prompts = self._query_prompts(questions)
         enc = self.encode_image(image, settings)
         ids = self.batch_generate_ids([enc] * len(prompts), prompts, share_prefix=True, **self._sampling_kwargs(settings))
         return [{"answer": self.tokenizer.decode(s)} for s in ids]
+
+    def query_many_reasoning(self, image, questions: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
+        """``query_many`` with reasoning: ``query(image, q, reasoning=True)`` for many questions about ONE image, in one
+        lockstep batch over a single copy of the image's KV prefix.  Element i ==
+        ``batch_query([encode_image(image)] * N, questions, settings, reasoning=True)[i]``; settings and refusals as there.
+        (A method of its own: ``query_many``'s three-parameter signature is part of its contract.)"""
+        self._check_reasoning_served(settings)
+        enc = self.encode_image(image, settings)
+        return self._reasoning_answers(self._batch_query_reasoning([enc] * len(questions), questions, settings, share_prefix=True))
 
     def query_choices(self, image, question: str, choices: Sequence[str], settings: Optional[dict] = None) -> dict:
         """Multiple choice: which of ``choices`` the model prefers as the answer to ``question`` about ONE image.  The image is
