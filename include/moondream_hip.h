@@ -459,6 +459,23 @@ md_status md_token_logprobs(const void* logits, int64_t ld, int32_t rows, int32_
                             const int32_t* suppress_rows, const int32_t* targets, float* logprob, int32_t* rank,
                             void* stream);
 
+/* The k most probable live tokens of every row with their log-probabilities: entry j of row r is the live token whose
+ * md_token_logprobs rank is j (greater logit first, equal logits by lower id; +0.0 and -0.0 tie; a -inf logit is live, sorts
+ * last by id and has log-probability -inf).  top_ids int32 [rows][k], top_logprobs fp32 [rows][k]; one workgroup per row, a
+ * row's result independent of the rows beside it.
+ *   Live tokens, m, s and their summation order: md_token_logprobs'.  top_logprobs[r][j] = (float(logit[id]) - m) - log(s),
+ *     bit for bit what md_token_logprobs returns for targets[r] = top_ids[r][j] on the same row.
+ *   gate (int32 [rows], or NULL: every row): row r is computed iff 0 <= gate[r] < vocab -- the step's token, as targets gate
+ *     md_token_logprobs.  A gated-off row is not read; its k entries are -1 / NaN.
+ *   A row with fewer than k live tokens: the remaining entries are -1 / NaN.  A NaN logit is out of contract.
+ * Selection by a two-level radix select over the 16-bit keys of the bf16 logits (csrc/sampling_region.hip), not k arg-max
+ * passes.  Plain loads: no vocab % 8 / ld % 8 requirement.  No host sync, no allocation: capturable.  rows == 0: MD_OK, nothing
+ * launched.  MD_ERR_INVALID_ARG: NULL logits / top_ids / top_logprobs, k < 1, k > MD_TOPK_MAX, rows < 0, vocab < 1, ld < vocab. */
+#define MD_TOPK_MAX 32
+md_status md_topk_logprobs(const void* logits, int64_t ld, int32_t rows, int32_t vocab, int32_t suppress_id,
+                           const int32_t* suppress_rows, const int32_t* gate, int32_t k, int32_t* top_ids,
+                           float* top_logprobs, void* stream);
+
 /* Region head, device resident (reference: region.py:12-71 inside the loop of moondream.py:653-733).
  * md_fourier_features: out[r] = [cos(f) | sin(f)], f = bf16(bf16(2 pi x[r, :in_dim]) . w[in_dim][half])
  *   (region.py:12-29; in_dim 1 for coordinates, 2 for sizes) -- the input of coord_encoder /

@@ -45,6 +45,11 @@ def row_buckets(max_live: int) -> List[int]:
     return sorted(set(small + [b for b in big if b >= 32] + [max_live]))
 
 
+def _pairs(top_ids, top_logprobs) -> List[Tuple[int, float]]:
+    """One decision's alternatives, k ids and k log-probabilities in rank order -> its (token_id, logprob) pairs."""
+    return [(int(t), float(x)) for t, x in zip(top_ids, top_logprobs)]
+
+
 @dataclass(eq=False)  # identity: a request is itself, whatever its fields
 class Request:
     """One generation request.  ``pos`` is the position of the next token to decode (the prompt's end after the prefill);
@@ -70,6 +75,7 @@ class Request:
     top_p: float = DEFAULT_TOP_P
     logprobs: List[float] = field(default_factory=list)  # of ``ids``, entry for entry (an engine with logprobs=True)
     ranks: List[int] = field(default_factory=list)
+    alternatives: List[list] = field(default_factory=list)  # of ``ids`` too: k (token_id, logprob) pairs each (top_logprobs=k)
 
     @property
     def remaining(self) -> int:
@@ -143,10 +149,12 @@ class SlotScheduler:
         self.stats.admissions += 1
         return out
 
-    def start(self, req: Request, first: int, pos: int, logprob: Optional[float] = None, rank: Optional[int] = None) -> bool:
+    def start(self, req: Request, first: int, pos: int, logprob: Optional[float] = None, rank: Optional[int] = None,
+              alternatives: Optional[list] = None) -> bool:
         """The prefill of ``req`` picked ``first`` with the next token at position ``pos`` (``logprob`` / ``rank``: its values,
-        kept beside it).  Returns True if the request is already finished (it then no longer holds its slot)."""
-        req.logprobs, req.ranks = [], []
+        kept beside it; ``alternatives``: the decision's (token_id, logprob) pairs, likewise).  Returns True if the request
+        is already finished (it then no longer holds its slot)."""
+        req.logprobs, req.ranks, req.alternatives = [], [], []
         req.pos = int(pos)
         req.steps = 0
         req.step_limit = max(0, min(req.max_tokens - 1, self.max_context - 1 - req.pos))
@@ -157,6 +165,8 @@ class SlotScheduler:
         req.ids = [int(first)]
         if logprob is not None:
             req.logprobs, req.ranks = [float(logprob)], [int(rank)]
+        if alternatives is not None:
+            req.alternatives = [_pairs(*alternatives)]
         if req.step_limit == 0:
             return self._retire(req)
         self.live.append(req)
@@ -194,10 +204,12 @@ class SlotScheduler:
         return ChunkPlan(rows, bucket, n, slots, tokens, pos)
 
     def commit(self, plan: ChunkPlan, out: np.ndarray, logprobs: Optional[np.ndarray] = None,
-               ranks: Optional[np.ndarray] = None) -> List[Request]:
-        """``out[i][r]``: the token row r produced in step i (``logprobs[i][r]`` / ``ranks[i][r]``: its values, appended in step
-        with the ids; idle and padding rows are never read).  Advances every row, retires the finished ones (their slots
-        return to the pool) and returns them in row order."""
+               ranks: Optional[np.ndarray] = None, top_ids: Optional[np.ndarray] = None,
+               top_logprobs: Optional[np.ndarray] = None) -> List[Request]:
+        """``out[i][r]``: the token row r produced in step i (``logprobs[i][r]`` / ``ranks[i][r]``: its values, and
+        ``top_ids[i][r]`` / ``top_logprobs[i][r]`` [k]: the decision's alternatives, appended in step with the ids; idle and
+        padding rows are never read).  Advances every row, retires the finished ones (their slots return to the pool) and
+        returns them in row order."""
         self.stats.decode_steps += plan.n
         self.stats.padded_row_steps += plan.n * plan.bucket
         self.stats.live_row_steps += plan.live_row_steps
@@ -216,6 +228,8 @@ class SlotScheduler:
                 if logprobs is not None:
                     r.logprobs.append(float(logprobs[i][r_idx]))
                     r.ranks.append(int(ranks[i][r_idx]))
+                if top_ids is not None:
+                    r.alternatives.append(_pairs(top_ids[i][r_idx], top_logprobs[i][r_idx]))
                 if r.steps >= r.step_limit:
                     fin = True
                     break
@@ -228,7 +242,8 @@ class SlotScheduler:
             step: Callable[[ChunkPlan], np.ndarray]) -> Iterator[Request]:
         """Drive the schedule: ``admit(requests)`` prefills them and returns (first token, next position) per request,
         ``step(plan)`` runs a chunk and returns its tokens [n, bucket].  With log-probabilities: (first token, next position,
-        logprob, rank) and (tokens, logprobs, ranks).  Yields requests in completion order."""
+        logprob, rank) and (tokens, logprobs, ranks); with alternatives one more element, (top ids [k], top logprobs [k]),
+        and two more planes [n, bucket, k].  Yields requests in completion order."""
         while self.pending():
             adm = self.take_admissions()
             if adm:
@@ -265,12 +280,21 @@ class ContinuousEngine:
     captured chunk), and every ``Request`` carries ``logprobs`` / ``ranks`` beside its ids: ``run(with_logprobs=True)``.  They
     are the values of ``MoondreamModel.batch_generate_ids(..., return_logprobs=True)`` -- the model's own distribution at
     temperature 1, untruncated, whatever the request's sampling settings -- bit for bit.  Off: the launches and graphs of
-    an engine without the flag."""
+    an engine without the flag.
+
+    ``top_logprobs`` = k in 1 .. 32 (with ``logprobs``; engine-wide and part of the chunk graph key too): every step also
+    selects each row's k most probable live tokens (md_topk_logprobs, the launch after md_token_logprobs, gated by the
+    step's tokens), and every ``Request`` carries ``alternatives``, one list of k (token_id, logprob) pairs per id -- the
+    fourth element of ``run(with_logprobs=True)`` / ``generate(..., return_logprobs=True)`` on such an engine, bit for bit
+    the ``alternatives`` of ``batch_generate_ids(..., top_logprobs=k)``."""
 
     def __init__(self, model, max_live: int = 64, chunk: int = 16, temperature: float = 0.0, top_p: float = DEFAULT_TOP_P,
-                 admit_threshold: Optional[int] = None, logprobs: bool = False):
+                 admit_threshold: Optional[int] = None, logprobs: bool = False, top_logprobs: Optional[int] = None):
+        from .decode_loop import check_top_logprobs
+
         self.model = model
         self.logprobs = bool(logprobs)
+        self.top_logprobs = check_top_logprobs(top_logprobs, self.logprobs)
         self.max_live = int(max_live)
         self.chunk = int(chunk)
         self.temperature = float(temperature)
@@ -345,19 +369,27 @@ class ContinuousEngine:
         return self.submit(image, prompt, **kw)
 
     # ---- running
-    def run(self, with_logprobs: bool = False) -> Iterator[tuple]:
+    def run(self, with_logprobs: bool = False, with_alternatives: Optional[bool] = None) -> Iterator[tuple]:
         """Generate every queued request; yields (rid, ids) in completion order -- with ``with_logprobs`` (an engine made with
-        ``logprobs=True``) (rid, ids, logprobs, ranks).  Requests submitted while this runs are admitted too.  ``stats``
-        counts this run."""
+        ``logprobs=True``) (rid, ids, logprobs, ranks), and on an engine with ``top_logprobs`` (rid, ids, logprobs, ranks,
+        alternatives).  ``with_alternatives`` True insists on the fifth element (ValueError on an engine without
+        ``top_logprobs``, or without ``with_logprobs``), False leaves it out; None: whatever the engine has.  Requests
+        submitted while this runs are admitted too.  ``stats`` counts this run."""
         import torch
 
         if with_logprobs and not self.logprobs:
             raise ValueError("run(with_logprobs=True) needs ContinuousEngine(..., logprobs=True)")
+        if with_alternatives and not (with_logprobs and self.top_logprobs):
+            raise ValueError("run(with_logprobs=True, with_alternatives=True) needs ContinuousEngine(..., logprobs=True, top_logprobs=k)")
+        alts = bool(self.top_logprobs) if with_alternatives is None else bool(with_alternatives)
         self.sched.stats = EngineStats()
         with torch.inference_mode():
             self._prepare_run()
             for r in self.sched.run(self._admit, self._step):
-                yield (r.rid, list(r.ids), list(r.logprobs), list(r.ranks)) if with_logprobs else (r.rid, list(r.ids))
+                if not with_logprobs:
+                    yield r.rid, list(r.ids)
+                else:
+                    yield (r.rid, list(r.ids), list(r.logprobs), list(r.ranks)) + ((list(r.alternatives),) if alts else ())
 
     def _prepare_run(self) -> None:
         """Size the KV slab (once, before the first admission: never grown during a run) and the decode buffers of the
@@ -395,7 +427,7 @@ class ContinuousEngine:
                  top_p: Union[None, float, Sequence[float]] = None, return_logprobs: bool = False):
         """Ids for (images[i], prompts[i]) in input order; ``max_tokens`` one int or one per request, ``temperature`` and
         ``top_p`` one float or one per request (None: the engine's).  ``return_logprobs`` (an engine made with
-        ``logprobs=True``): (ids, logprobs, ranks), each in input order."""
+        ``logprobs=True``): (ids, logprobs, ranks), each in input order; an engine with ``top_logprobs``: alternatives too."""
         if return_logprobs and not self.logprobs:
             raise ValueError("generate(return_logprobs=True) needs ContinuousEngine(..., logprobs=True)")
         n = len(images)
@@ -416,9 +448,9 @@ class ContinuousEngine:
 
         temps, tps = per_request(temperature, "temperature"), per_request(top_p, "top_p")
         rids = [self.submit(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant, temps[i], tps[i]) for i in range(n)]
-        if return_logprobs:
+        if return_logprobs:  # (ids, logprobs, ranks), and alternatives on an engine with top_logprobs
             got3 = {rid: rest for rid, *rest in self.run(with_logprobs=True)}
-            return tuple([got3[r][k] for r in rids] for k in range(3))
+            return tuple([got3[r][k] for r in rids] for k in range(4 if self.top_logprobs else 3))
         got = dict(self.run())
         return [got[r] for r in rids]
 
@@ -458,7 +490,8 @@ class ContinuousEngine:
         """hidden [k, 1, D], the last rows of a prefill -> the first token of each request from its last row, as _prepare_sequences picks it (argmax, or
         top-p sampling with the request's own settings and first uniform: md_sample_rows over the group; no suppression).
         lm_head in launches of <= 64 rows: the decode-regime kernels, whatever the admission size.  Returns one tuple per
-        request: (token,), or with ``logprobs`` (token, logprob, rank) of the same logits, unsuppressed like the pick."""
+        request: (token,), or with ``logprobs`` (token, logprob, rank) of the same logits, unsuppressed like the pick, and
+        with ``top_logprobs`` one more element: (top ids [k], top logprobs [k]) of that decision."""
         import torch
 
         from .decode_loop import Sampling
@@ -468,6 +501,9 @@ class ContinuousEngine:
         first = torch.empty(k, dtype=torch.int32, device=m.device)
         lp = torch.empty(k, dtype=torch.float32, device=m.device) if self.logprobs else None
         rk = torch.empty(k, dtype=torch.int32, device=m.device) if self.logprobs else None
+        kk = self.top_logprobs
+        ti = torch.empty(k, kk, dtype=torch.int32, device=m.device) if kk else None
+        tl = torch.empty(k, kk, dtype=torch.float32, device=m.device) if kk else None
         for i0 in range(0, k, 64):
             part = reqs[i0 : i0 + 64]
             i1 = i0 + len(part)
@@ -478,10 +514,13 @@ class ContinuousEngine:
                 st_d = m._h2d(torch.tensor([[r.temperature for r in part], [r.top_p for r in part], draws], dtype=torch.float32))
                 pick = Sampling(st_d[0], st_d[1])
             first[i0:i1] = m._first_token(m._lm_head(hidden[i0:i1]), pick, uniforms=st_d[2] if pick is not None else None,
-                                          logprobs=(lp[i0:i1], rk[i0:i1]) if self.logprobs else None)
+                                          logprobs=(lp[i0:i1], rk[i0:i1]) if self.logprobs else None,
+                                          topk=(ti[i0:i1], tl[i0:i1]) if kk else None)
         if not self.logprobs:
             return [(f,) for f in first.tolist()]
-        return list(zip(first.tolist(), lp.tolist(), rk.tolist()))
+        if not kk:
+            return list(zip(first.tolist(), lp.tolist(), rk.tolist()))
+        return list(zip(first.tolist(), lp.tolist(), rk.tolist(), zip(ti.cpu().numpy(), tl.cpu().numpy())))
 
     def _admit(self, reqs: List[Request]) -> List[Tuple[int, int]]:
         """ViT over the admitted raw images as one batch, then the prefill into their slots with the choices of
@@ -574,6 +613,19 @@ class ContinuousEngine:
             b = bufs[key] = torch.zeros(2, self.chunk, bucket, dtype=torch.int32, device=self.model.device)
         return b
 
+    def _topk_buffers(self, bucket: int):
+        """Fixed-address int32 device words [2, chunk, bucket, k] of a (chunk, bucket, k): plane 0 the alternatives' ids of a
+        chunk's decisions, plane 1 their fp32 log-probabilities (as raw words) -- one D2H copy of both.  Only an engine with
+        ``top_logprobs`` has them."""
+        import torch
+
+        bufs = self.model.__dict__.setdefault("_continuous_topk_bufs", {})
+        key = (self.chunk, bucket, self.top_logprobs)
+        b = bufs.get(key)
+        if b is None:
+            b = bufs[key] = torch.zeros(2, self.chunk, bucket, self.top_logprobs, dtype=torch.int32, device=self.model.device)
+        return b
+
     def _step(self, plan: ChunkPlan) -> np.ndarray:
         import torch
 
@@ -620,8 +672,10 @@ class ContinuousEngine:
         pick = Sampling(u_dev[c * B : c * B + B], u_dev[c * B + B :]) if sample else None
         # (an idle or padding row's log-probability is never read: SlotScheduler.commit)
         planes = (lp_words[0].view(torch.float32), lp_words[1]) if self.logprobs else None
+        tk_words = self._topk_buffers(B) if self.top_logprobs else None
+        tk_planes = (tk_words[0], tk_words[1].view(torch.float32)) if self.top_logprobs else None
         chunk = DecodeChunk(B, hist, pos_d, rows_of, m.config.tokenizer.answer_id, self._decode_ws_bytes(B), pick,
-                            u_dev[: c * B].view(c, B), planes)
+                            u_dev[: c * B].view(c, B), planes, topk=tk_planes)
         stream = torch.cuda.current_stream(m.device).cuda_stream if m.use_graphs else None
 
         def below_cap():
@@ -633,4 +687,7 @@ class ContinuousEngine:
         if lp_words is None:
             return out
         words = lp_words[:, :n].cpu().numpy()  # ... and one more of both planes
-        return out, words[0].view(np.float32), words[1]
+        if tk_words is None:
+            return out, words[0].view(np.float32), words[1]
+        top = tk_words[:, :n].cpu().numpy()  # ... and of the alternatives' two
+        return out, words[0].view(np.float32), words[1], top[0], top[1].view(np.float32)

@@ -1,11 +1,34 @@
 """What the lockstep loop (``MoondreamModel._decode_greedy_impl``) and the continuous engine (``ContinuousEngine._step``)
 share: the description of a chunk of consecutive decode steps over fixed buffers, and the one runner that launches it.
 ``run_chunk`` holds the only step body of the package -- decode step (or, for a reasoning query, the reasoning step), then
-the optional sampling pick, then the optional log-probability launch -- and the only decode graph key.  No torch here: the runner moves no data, it orders launches."""
+the optional sampling pick, then the optional log-probability launch and the optional top-k launch -- and the only decode
+graph key.  No torch here: the runner moves no data, it orders launches."""
 from __future__ import annotations
 
+import operator
 from dataclasses import dataclass
 from typing import Any, Callable, Optional, Tuple
+
+
+TOPK_MAX = 32  # MD_TOPK_MAX of include/moondream_hip.h
+
+
+def check_top_logprobs(top_logprobs: Optional[int], with_logprobs: bool) -> int:
+    """The ``top_logprobs`` argument of the generation and scoring calls -> k (0: none).  ValueError for a k outside
+    1 .. TOPK_MAX, or one asked for without the log-probabilities it extends: host values only, before any GPU work."""
+    if top_logprobs is None:
+        return 0
+    try:
+        k = operator.index(top_logprobs)
+    except TypeError:
+        k = -1
+    if k == 0:
+        return 0
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"top_logprobs must be an integer in 1 .. {TOPK_MAX} (0 / None: none), not {top_logprobs!r}")
+    if not with_logprobs:
+        raise ValueError("top_logprobs extends the log-probabilities: it needs return_logprobs=True / logprobs=True")
+    return k
 
 
 @dataclass(frozen=True, eq=False)
@@ -65,6 +88,8 @@ class DecodeChunk:
     differ in data at fixed addresses only).  ``pick`` None keeps each step's argmax; otherwise step i draws every row from
     ``uniforms[i]`` (fp32 [>= n, b]) with the call's settings (``_pick``) or each row's own (``_pick_rows``).
     ``logprobs`` = (fp32, int32) planes [>= n, b]: row i takes the log-probability and rank of the tokens of step i.
+    ``topk`` = (int32 ids, fp32 log-probabilities) planes [>= n, b, k]: row i takes the k alternatives of every row's
+    decision in step i (md_topk_logprobs after the step's md_token_logprobs, gated by the step's tokens); with ``logprobs`` only.
     ``b1``: the single-sequence persistent kernel takes the steps (b = 1, greedy).  ``step(tok_in) -> logits``: the step
     made from its pieces instead of the fused one (a LoRA adapter; eager only, its pick writes ``tokens[i + 1]``).
     ``reason`` (``ReasonChunk``): the steps are md_decode_step_reason's -- each row's phase decides what it feeds and which
@@ -82,6 +107,7 @@ class DecodeChunk:
     b1: bool = False
     step: Optional[Callable[[Any], Any]] = None
     reason: Optional[ReasonChunk] = None
+    topk: Optional[Tuple[Any, Any]] = None
 
 
 def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_stream: Optional[int] = None,
@@ -90,18 +116,20 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     stream: the chunk is replayed from the graph captured for it on that stream, or, first, run eagerly and captured
     (``model._replay_or_capture``; ``may_capture`` as it takes it).  The key starts (``tag``, stream) and names everything the
     launches bake in.  Returns True when it captured.  Of the model it uses _decode_logits, _workspace, _kv_struct,
-    _decode_step, _decode_step_b1, _decode_step_reason, _pick, _pick_rows, _token_logprobs and _replay_or_capture."""
+    _decode_step, _decode_step_b1, _decode_step_reason, _pick, _pick_rows, _token_logprobs, _topk_logprobs and _replay_or_capture."""
     c = chunk
     pieces = c.step is not None
     assert c.reason is None or (not pieces and not c.b1 and c.logprobs is None and c.pick is not None and c.pick.per_row)
     assert not (pieces and (capture_stream is not None or c.b1))
     assert not c.b1 or (c.b == 1 and c.pick is None)
+    assert c.topk is None or c.logprobs is not None
     if not pieces:
         logits = model._decode_logits(c.b)
         ws = model._workspace(c.ws_bytes, 2)
         kv = model._kv_struct(c.rows_of(0).slot0)
         left = logits[: c.b]  # where every fused step (the single-sequence kernel too) leaves its logits
     lp, rk = c.logprobs if c.logprobs is not None else (None, None)
+    tk_ids, tk_lp = c.topk if c.topk is not None else (None, None)
     by_row = c.pick is not None and c.pick.per_row
 
     def body():
@@ -126,6 +154,8 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
                             uniforms=c.uniforms[i] if c.uniforms is not None else None, out=tok_out)
             if lp is not None:  # targets = the step's tokens
                 model._token_logprobs(lg, tok_out, c.suppress_id, lp[i], rk[i])
+            if tk_ids is not None:  # the decision's alternatives; a row whose token is no id (idle) is not read
+                model._topk_logprobs(lg, tok_out, c.suppress_id, tk_ids[i], tk_lp[i])
 
     if capture_stream is None:
         body()
@@ -141,6 +171,8 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
            logits.data_ptr(), c.b1, pick, c.uniforms.data_ptr() if c.uniforms is not None else 0) + c.rows_of(0).key()
     if lp is not None:  # a chunk with the logprob launches is another graph; without them key and graph are unchanged
         key += ("logprobs", lp.data_ptr(), rk.data_ptr())
+    if tk_ids is not None:  # and one more with the top-k launches
+        key += ("topk", int(tk_ids.shape[-1]), tk_ids.data_ptr(), tk_lp.data_ptr())
     if c.reason is not None:  # likewise: another graph, keyed by the state's addresses
         key += c.reason.key()
     return model._replay_or_capture(key, body, may_capture=may_capture)

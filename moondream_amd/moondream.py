@@ -29,7 +29,7 @@ from PIL import Image
 
 from . import _lib
 from .config import MoondreamConfig
-from .decode_loop import DecodeChunk, ReasonChunk, Sampling, run_chunk
+from .decode_loop import DecodeChunk, ReasonChunk, Sampling, check_top_logprobs, run_chunk
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
 from .lora import variant_state_dict
@@ -1158,12 +1158,35 @@ class MoondreamModel:
             "md_token_logprobs",
         )
 
+    def _topk_logprobs(self, logits: torch.Tensor, gate: Optional[torch.Tensor], suppress_id: int, top_ids: torch.Tensor,
+                       top_logprobs: torch.Tensor, suppress_rows: Optional[torch.Tensor] = None):
+        """The k alternatives of every row of ``logits`` [R, V]: md_topk_logprobs.  ``top_ids`` (device int32 [R, k]) and
+        ``top_logprobs`` (device fp32 [R, k]) take, at entry j, the live token of rank j and its log-probability -- the
+        distribution, the suppression rule and the bits of ``_token_logprobs``.  ``gate`` (device int32 [R] or None): a row
+        whose gate is no token id is not read and gets -1 / NaN (the step's tokens: idle rows).  Nothing is allocated and
+        nothing synchronises: capturable."""
+        r, v = logits.shape
+        k = top_ids.shape[-1]
+        for t in (top_ids, top_logprobs):
+            assert t.is_contiguous() and t.shape == (r, k) and t.device == logits.device
+        for t in (gate, suppress_rows):
+            assert t is None or (t.is_contiguous() and t.numel() == r and t.dtype == torch.int32 and t.device == logits.device)
+        assert top_ids.dtype == torch.int32 and top_logprobs.dtype == torch.float32
+        _lib.check(
+            self.lib.md_topk_logprobs(logits.data_ptr(), logits.stride(0), r, v, suppress_id,
+                                      suppress_rows.data_ptr() if suppress_rows is not None else None,
+                                      gate.data_ptr() if gate is not None else None, k, top_ids.data_ptr(),
+                                      top_logprobs.data_ptr(), self._stream()),
+            "md_topk_logprobs",
+        )
+
     def _first_token(self, logits: torch.Tensor, pick: Optional[Sampling] = None, row_perm=None,
-                     uniforms: Optional[torch.Tensor] = None, logprobs=None) -> torch.Tensor:
+                     uniforms: Optional[torch.Tensor] = None, logprobs=None, topk=None) -> torch.Tensor:
         """The first generated token of every row, int32 [B], from its prompt pass's logits [B, V]: the argmax (``pick``
         None), a draw with the call's settings (``row_perm``: the draw order of these rows) or with each row's own (and
         ``uniforms`` fp32 [B]).  Nothing is suppressed (moondream.py:313-318).  ``logprobs`` = (fp32 [B], int32 [B]): filled
-        with the token's log-probability and rank, unsuppressed like the pick."""
+        with the token's log-probability and rank, unsuppressed like the pick; ``topk`` = (int32 [B, k], fp32 [B, k]): with
+        the decision's alternatives, unsuppressed too."""
         if pick is None:
             first = self._pick(logits, 0.0, 0.0)
         elif pick.per_row:
@@ -1172,6 +1195,8 @@ class MoondreamModel:
             first = self._pick(logits, pick.temperature, pick.top_p, -1, pick.generator, row_perm=row_perm)
         if logprobs is not None:
             self._token_logprobs(logits, first, -1, *logprobs)
+        if topk is not None:
+            self._topk_logprobs(logits, None, -1, *topk)
         return first
 
     # ---------------------------------------------------------- batched engine
@@ -1223,7 +1248,9 @@ class MoondreamModel:
         captured hipGraph over the fixed buffers of the chunk's shape.  ``rows``: the routing of every step (``_Rows``).
         ``first_logprobs`` = (logprob fp32 [B], rank int32 [B]) of ``first``: the loop also keeps the log-probability and rank
         of every token it picks (``_token_logprobs`` on the logits the step leaves, one launch after the step's pick, inside
-        the captured graph) and returns (hist, logprobs fp32 [steps+1, B], ranks int32 [steps+1, B]).  No id changes."""
+        the captured graph) and returns (hist, logprobs fp32 [steps+1, B], ranks int32 [steps+1, B]).  No id changes.
+        With two more tensors, (.., top ids int32 [B, k], top logprobs fp32 [B, k]) of ``first``'s decision, it keeps every
+        decision's k alternatives too (``_topk_logprobs``, the launch after) and returns two more planes [steps+1, B, k]."""
         rows = _Rows.of(rows)
         b = first.shape[0]
         t = self.config.text
@@ -1240,8 +1267,15 @@ class MoondreamModel:
         if with_lp:
             lp_hist = torch.full((max_tokens + 1, b), float("nan"), dtype=torch.float32, device=self._device)
             rk_hist = torch.full((max_tokens + 1, b), -1, dtype=torch.int32, device=self._device)
-            lp_hist[0], rk_hist[0] = first_logprobs
-        done = lambda upto: (hist[:upto], lp_hist[:upto], rk_hist[:upto]) if with_lp else hist[:upto]
+            lp_hist[0], rk_hist[0] = first_logprobs[:2]
+        with_tk = with_lp and len(first_logprobs) == 4
+        top_k = first_logprobs[2].shape[1] if with_tk else 0
+        if with_tk:
+            ti_hist = torch.full((max_tokens + 1, b, top_k), -1, dtype=torch.int32, device=self._device)
+            tl_hist = torch.full((max_tokens + 1, b, top_k), float("nan"), dtype=torch.float32, device=self._device)
+            ti_hist[0], tl_hist[0] = first_logprobs[2:]
+        done = lambda upto: (((hist[:upto], lp_hist[:upto], rk_hist[:upto]) + ((ti_hist[:upto], tl_hist[:upto]) if with_tk else ()))
+                             if with_lp else hist[:upto])
         if max_tokens == 0:
             return done(1)
         pos_base = self._h2d(torch.tensor(pos_list, dtype=torch.int32))
@@ -1298,21 +1332,30 @@ class MoondreamModel:
                     fixed[stream, b, n] = (zeros(n + 1, torch.int32), zeros(1, torch.int32)[0], zeros(n, torch.float32),
                                            zeros(n, torch.float32), zeros(n, torch.int32))
                 buf, pos_buf, u_buf, lp_buf, rk_buf = fixed[stream, b, n]
+                if with_tk:  # the alternatives' planes of this shape and k, beside the others
+                    if (stream, b, n, top_k) not in fixed:
+                        fixed[stream, b, n, top_k] = (torch.zeros(n, b, top_k, dtype=torch.int32, device=self._device),
+                                                      torch.zeros(n, b, top_k, dtype=torch.float32, device=self._device))
+                    ti_buf, tl_buf = fixed[stream, b, n, top_k]
                 buf[0] = hist[steps]
                 pos_buf.copy_(pos_base + steps)
                 if uniforms is not None:
                     u_buf.copy_(uniforms[steps : steps + n])
                 part = replace(chunk, tokens=buf, pos=pos_buf, uniforms=u_buf if uniforms is not None else None,
-                               logprobs=(lp_buf, rk_buf) if with_lp else None)
+                               logprobs=(lp_buf, rk_buf) if with_lp else None, topk=(ti_buf, tl_buf) if with_tk else None)
             else:
                 part = replace(chunk, tokens=hist[steps:], uniforms=uniforms[steps:] if uniforms is not None else None,
-                               logprobs=(lp_hist[steps + 1 :], rk_hist[steps + 1 :]) if with_lp else None)
+                               logprobs=(lp_hist[steps + 1 :], rk_hist[steps + 1 :]) if with_lp else None,
+                               topk=(ti_hist[steps + 1 :], tl_hist[steps + 1 :]) if with_tk else None)
             run_chunk(self, part, n, capture_stream=stream)
             if graphs:
                 hist[steps + 1 : steps + n + 1] = buf[1:]
                 if with_lp:
                     lp_hist[steps + 1 : steps + n + 1] = lp_buf
                     rk_hist[steps + 1 : steps + n + 1] = rk_buf
+                if with_tk:
+                    ti_hist[steps + 1 : steps + n + 1] = ti_buf
+                    tl_hist[steps + 1 : steps + n + 1] = tl_buf
             steps += n
             if steps < max_tokens and eos_id is not None and bool((hist[: steps + 1] == eos_id).any(dim=0).all()):
                 break  # every sequence has emitted its EOS
@@ -1372,7 +1415,8 @@ class MoondreamModel:
         at position ``pos`` into the slots of ``rows.sub(r0, r1)``, then lm_head and the pick of the first token (``_first_token``;
         ``sampling`` None: argmax; a group draws in its rows' order among themselves in ``sampling.row_perm``).
         Returns (first int32 [B], hidden_last [B, D], next_pos list); the groups' logits go to ``logits_capture`` [B, V], the
-        log-probability and rank of each first token (unsuppressed, like the pick) to ``first_logprobs`` = (fp32 [B], int32 [B]).
+        log-probability and rank of each first token (unsuppressed, like the pick) to ``first_logprobs`` = (fp32 [B], int32 [B])
+        -- with two more tensors, (.., int32 [B, k], fp32 [B, k]), the first decision's k alternatives go to those.
         ``hidden_sink(r0, r1, hidden [r1-r0, T, D])``: the scorer's form -- every hidden row of the pass goes to the sink, and
         no first token is picked (``first`` and ``hidden_last`` are not filled)."""
         b = groups[-1][1]
@@ -1390,8 +1434,9 @@ class MoondreamModel:
             if logits_capture is not None:
                 logits_capture[r0:r1] = logits
             perm = sampling.row_perm[r0:r1] if sampling is not None and sampling.row_perm is not None else None
+            own = [x[r0:r1] for x in first_logprobs] if first_logprobs is not None else []  # (logprob, rank[, top ids, top logprobs])
             first[r0:r1] = self._first_token(logits, sampling, perm - perm.min() if perm is not None else None,
-                                             logprobs=[x[r0:r1] for x in first_logprobs] if first_logprobs is not None else None)
+                                             logprobs=own[:2] or None, topk=own[2:] or None)
             hidden_last[r0:r1] = hidden[:, -1, :]
         return first, hidden_last, next_pos
 
@@ -1549,6 +1594,7 @@ class MoondreamModel:
         share_prefix: bool = False,
         variants: Optional[Sequence[Optional[str]]] = None,
         return_logprobs: bool = False,
+        top_logprobs: Optional[int] = None,
     ):
         """Token ids for B (image, prompt-ids) pairs, decoded in lockstep; greedy by default.
 
@@ -1599,7 +1645,16 @@ class MoondreamModel:
         counts the tokens ahead of the pick in argmax order: 0 for every greedy token.  Computed on the device
         (md_token_logprobs: one launch after each step's pick, inside the captured chunk; one copy to the host at the end with
         the ids).  The flag changes no id; with it off the launches and captured graphs are unchanged.
+
+        ``top_logprobs`` = k in 1 .. 32 (with ``return_logprobs``): returns ``(ids, logprobs, ranks, alternatives)``;
+        ``alternatives[i][j]`` is a list of k ``(token_id, logprob)`` pairs, the k most probable live tokens of the decision
+        that produced ``ids[i][j]`` in rank order (entry ``ranks[i][j]``, when below k, is the token itself with its own
+        log-probability, bit for bit) -- the same distribution: the first decision unsuppressed, the later ones without
+        ``answer_id``.  md_topk_logprobs: one more launch per step, after md_token_logprobs, in the same captured chunk;
+        the same single copy to the host.  It changes no pick (this is not a top-k sampling rule); 0 / None: the call
+        without it.  ValueError, before any GPU work: ``top_logprobs`` without ``return_logprobs``, or outside 1 .. 32.
         """
+        top_k = check_top_logprobs(top_logprobs, return_logprobs)
         b = len(images)
         assert b == len(prompts) and b > 0
         multi_rows = None
@@ -1623,6 +1678,9 @@ class MoondreamModel:
             first_lp = None
             if return_logprobs:
                 first_lp = (torch.empty(b, dtype=torch.float32, device=self._device), torch.empty(b, dtype=torch.int32, device=self._device))
+                if top_k:
+                    first_lp += (torch.empty(b, top_k, dtype=torch.int32, device=self._device),
+                                 torch.empty(b, top_k, dtype=torch.float32, device=self._device))
             if multi_rows is None and share_prefix and self._shares_prefix(lora):
                 order, first, _, next_pos, rows, sampling = self._prepare_sequences_shared(list(images), prompts, mark, sampling,
                                                                                            first_logprobs=first_lp)
@@ -1640,9 +1698,19 @@ class MoondreamModel:
             hist = self._decode_greedy(first, next_pos if len(set(next_pos)) > 1 else next_pos[0], max_tokens,
                                        tk.answer_id, rows, stop, sampling=sampling, first_logprobs=first_lp)
             mark("decode")
-            if return_logprobs:  # ids, logprobs (as raw words) and ranks in ONE copy to the host
+            if top_k:  # ... and the alternatives: [T, B] words of ids, logprobs, ranks, then [T, B, k] of top ids, top logprobs
+                hist, lp_hist, rk_hist, ti_hist, tl_hist = hist
+                n_t = hist.shape[0]
+                flat = torch.cat([hist.reshape(-1), lp_hist.view(torch.int32).reshape(-1), rk_hist.reshape(-1),
+                                  ti_hist.reshape(-1), tl_hist.view(torch.int32).reshape(-1)]).cpu().numpy()
+                packed = flat[: 3 * n_t * b].reshape(3, n_t, b)
+                top = flat[3 * n_t * b :].reshape(2, n_t, b, top_k)
+                ti_cols = top[0].transpose(1, 0, 2).tolist()  # [B][T][k]
+                tl_cols = top[1].view(np.float32).transpose(1, 0, 2).tolist()
+            elif return_logprobs:  # ids, logprobs (as raw words) and ranks in ONE copy to the host
                 hist, lp_hist, rk_hist = hist
                 packed = torch.stack([hist, lp_hist.view(torch.int32), rk_hist]).cpu().numpy()
+            if return_logprobs:
                 cols = packed[0].T.tolist()
                 lp_cols, rk_cols = packed[1].view(np.float32).T.tolist(), packed[2].T.tolist()
             else:
@@ -1652,25 +1720,32 @@ class MoondreamModel:
             results: List[Optional[List[int]]] = [None] * b
             logprobs: List[Optional[List[float]]] = [None] * b
             ranks: List[Optional[List[int]]] = [None] * b
+            alternatives: list = [None] * b
             for slot, src in enumerate(order):
                 results[src] = self._truncate(cols[slot], stop, max_tokens)
                 if return_logprobs:  # _truncate keeps a leading run of the ids: the same run of their values
                     logprobs[src], ranks[src] = lp_cols[slot][: len(results[src])], rk_cols[slot][: len(results[src])]
+                if top_k:
+                    alternatives[src] = [list(zip(ti_cols[slot][j], tl_cols[slot][j])) for j in range(len(results[src]))]
         self._phase_times(marks)
+        if top_k:
+            return results, logprobs, ranks, alternatives
         return (results, logprobs, ranks) if return_logprobs else results  # type: ignore[return-value]
 
     def batch_generate_ids_continuous(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                                       eos_id: Optional[int] = None, ignore_eos: bool = False, max_live: int = 64, chunk: int = 16,
                                       temperature: Union[float, Sequence[float]] = 0.0,
                                       top_p: Union[float, Sequence[float]] = DEFAULT_TOP_P, seeds=None,
-                                      variant: Optional[str] = None, return_logprobs: bool = False):
+                                      variant: Optional[str] = None, return_logprobs: bool = False,
+                                      top_logprobs: Optional[int] = None):
         """``batch_generate_ids`` with continuous batching (moondream_amd/continuous.py): per-request ``max_tokens`` and EOS
         exit, freed KV slots refilled from the queue mid-decode; same greedy ids as the lockstep path.  ``temperature`` and
         ``top_p``: one float, or one per request (greedy and sampled requests share the decode steps).  ``return_logprobs``:
-        (ids, logprobs, ranks) as ``batch_generate_ids`` returns them (``ContinuousEngine(logprobs=True)``)."""
+        (ids, logprobs, ranks) as ``batch_generate_ids`` returns them (``ContinuousEngine(logprobs=True)``); with
+        ``top_logprobs`` = k also its ``alternatives`` (``ContinuousEngine(logprobs=True, top_logprobs=k)``)."""
         from .continuous import ContinuousEngine
 
-        eng = ContinuousEngine(self, max_live, chunk, logprobs=bool(return_logprobs))
+        eng = ContinuousEngine(self, max_live, chunk, logprobs=bool(return_logprobs), top_logprobs=top_logprobs)
         return eng.generate(images, prompts, max_tokens, eos_id, ignore_eos, seeds, variant, temperature, top_p,
                             return_logprobs=bool(return_logprobs))
 
@@ -1731,7 +1806,8 @@ class MoondreamModel:
                                  f"{self.config.text.max_context}-slot context")
 
     def score_ids(self, images: Sequence[Union[Image.Image, EncodedImage]], prompts: Sequence[Sequence[int]],
-                  continuations: Sequence[Sequence[int]], share_prefix: bool = False, variant: Optional[str] = None):
+                  continuations: Sequence[Sequence[int]], share_prefix: bool = False, variant: Optional[str] = None,
+                  top_logprobs: Optional[int] = None):
         """Score GIVEN continuations: returns ``(logprobs, ranks)``, one list per row with one entry per token of
         ``continuations[i]`` -- the values ``batch_generate_ids(..., return_logprobs=True)`` attaches to a token it generates,
         for the tokens the caller supplies.  ``logprobs[i][j]`` is log softmax of the model's logits after
@@ -1745,7 +1821,13 @@ class MoondreamModel:
         gathered compactly, lm_head runs over them in launches of <= 64 rows (the decode-regime kernels whatever the call's
         size: a row's values do not depend on what else is scored) and ONE md_token_logprobs launch reduces every row.  The
         KV slots used are scratch, as in any batch call.  ValueError, before any device work: an empty prompt or
-        continuation, lists of different lengths, prefix + prompt + continuation beyond ``max_context``, the fp8 modes."""
+        continuation, lists of different lengths, prefix + prompt + continuation beyond ``max_context``, the fp8 modes.
+
+        ``top_logprobs`` = k in 1 .. 32: returns ``(logprobs, ranks, alternatives)``; ``alternatives[i][j]`` is the list of
+        the k most probable live tokens of decision j as ``(token_id, logprob)`` pairs in rank order, as
+        ``batch_generate_ids(..., top_logprobs=k)`` gives them: ONE md_topk_logprobs launch over the same logits and
+        suppression table, and the same copy to the host.  ValueError for a k outside 1 .. 32."""
+        top_k = check_top_logprobs(top_logprobs, True)
         self._check_score_args(images, prompts, continuations)
         conts = [[int(t) for t in c] for c in continuations]
         seqs = [[int(t) for t in p] + c[:-1] for p, c in zip(prompts, conts)]
@@ -1781,10 +1863,21 @@ class MoondreamModel:
             lp = torch.empty(r, dtype=torch.float32, device=self._device)
             rk = torch.empty(r, dtype=torch.int32, device=self._device)
             self._token_logprobs(logits, tab[0], tk.answer_id, lp, rk, suppress_rows=tab[1])
-            packed = torch.stack([lp.view(torch.int32), rk]).cpu().numpy()  # one copy to the host
-        lp_h, rk_h = packed[0].view(np.float32).tolist(), packed[1].tolist()
+            words = [lp.view(torch.int32), rk]
+            if top_k:
+                ti = torch.empty(r, top_k, dtype=torch.int32, device=self._device)
+                tl = torch.empty(r, top_k, dtype=torch.float32, device=self._device)
+                self._topk_logprobs(logits, None, tk.answer_id, ti, tl, suppress_rows=tab[1])
+                words += [ti.reshape(-1), tl.view(torch.int32).reshape(-1)]
+            packed = torch.cat(words).cpu().numpy()  # one copy to the host
+        lp_h, rk_h = packed[:r].view(np.float32).tolist(), packed[r : 2 * r].tolist()
         n = len(conts)
-        return [lp_h[span[i][0] : span[i][1]] for i in range(n)], [rk_h[span[i][0] : span[i][1]] for i in range(n)]
+        out = [lp_h[span[i][0] : span[i][1]] for i in range(n)], [rk_h[span[i][0] : span[i][1]] for i in range(n)]
+        if not top_k:
+            return out
+        ti_h = packed[2 * r : 2 * r + r * top_k].reshape(r, top_k).tolist()
+        tl_h = packed[2 * r + r * top_k :].view(np.float32).reshape(r, top_k).tolist()
+        return out + ([[list(zip(ti_h[j], tl_h[j])) for j in range(*span[i])] for i in range(n)],)
 
     # ------------------------------------------------------ pipelined batches
     def _streams(self):
