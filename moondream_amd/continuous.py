@@ -25,6 +25,9 @@ from typing import Callable, Deque, Dict, Iterator, List, Optional, Sequence, Tu
 
 import numpy as np
 
+from .decode_loop import DecodeChunk, Sampling, check_top_logprobs, run_chunk
+from .scores import HostScores, Scores
+
 DEFAULT_MAX_TOKENS = 768  # moondream.py (the reference's default, moondream.py:50-53)
 DEFAULT_TOP_P = 0.3
 MAX_GRAPHS = 16  # captured decode chunks per (model, stream)
@@ -43,11 +46,6 @@ def row_buckets(max_live: int) -> List[int]:
         step *= 2
     big = list(range(step, max_live, step)) + [max_live]
     return sorted(set(small + [b for b in big if b >= 32] + [max_live]))
-
-
-def _pairs(top_ids, top_logprobs) -> List[Tuple[int, float]]:
-    """One decision's alternatives, k ids and k log-probabilities in rank order -> its (token_id, logprob) pairs."""
-    return [(int(t), float(x)) for t, x in zip(top_ids, top_logprobs)]
 
 
 @dataclass(eq=False)  # identity: a request is itself, whatever its fields
@@ -166,7 +164,7 @@ class SlotScheduler:
         if logprob is not None:
             req.logprobs, req.ranks = [float(logprob)], [int(rank)]
         if alternatives is not None:
-            req.alternatives = [_pairs(*alternatives)]
+            req.alternatives = [HostScores(logprob, rank, *alternatives).alternatives()]
         if req.step_limit == 0:
             return self._retire(req)
         self.live.append(req)
@@ -214,6 +212,7 @@ class SlotScheduler:
         self.stats.padded_row_steps += plan.n * plan.bucket
         self.stats.live_row_steps += plan.live_row_steps
         finished = []
+        host = HostScores(logprobs, ranks, top_ids, top_logprobs)
         for r_idx, r in enumerate(plan.rows):
             fin = False
             for i in range(min(plan.n, r.remaining)):
@@ -229,7 +228,7 @@ class SlotScheduler:
                     r.logprobs.append(float(logprobs[i][r_idx]))
                     r.ranks.append(int(ranks[i][r_idx]))
                 if top_ids is not None:
-                    r.alternatives.append(_pairs(top_ids[i][r_idx], top_logprobs[i][r_idx]))
+                    r.alternatives.append(host.alternatives((i, r_idx)))
                 if r.steps >= r.step_limit:
                     fin = True
                     break
@@ -275,23 +274,17 @@ class ContinuousEngine:
     captured chunks.  Each sampled request draws its uniforms from its own generator (``seed``): its tokens depend neither
     on which other requests share its steps nor on their settings.
 
-    ``logprobs`` (engine-wide, part of the chunk graph key): every step of a chunk also reduces each row's logits to the
-    log-probability and rank of the token the row picked (md_token_logprobs with targets = the step's tokens, inside the
-    captured chunk), and every ``Request`` carries ``logprobs`` / ``ranks`` beside its ids: ``run(with_logprobs=True)``.  They
-    are the values of ``MoondreamModel.batch_generate_ids(..., return_logprobs=True)`` -- the model's own distribution at
-    temperature 1, untruncated, whatever the request's sampling settings -- bit for bit.  Off: the launches and graphs of
-    an engine without the flag.
-
-    ``top_logprobs`` = k in 1 .. 32 (with ``logprobs``; engine-wide and part of the chunk graph key too): every step also
-    selects each row's k most probable live tokens (md_topk_logprobs, the launch after md_token_logprobs, gated by the
-    step's tokens), and every ``Request`` carries ``alternatives``, one list of k (token_id, logprob) pairs per id -- the
-    fourth element of ``run(with_logprobs=True)`` / ``generate(..., return_logprobs=True)`` on such an engine, bit for bit
-    the ``alternatives`` of ``batch_generate_ids(..., top_logprobs=k)``."""
+    ``logprobs``, and with it ``top_logprobs`` = k in 1 .. 32 (engine-wide, part of the chunk graph key): every step of a
+    chunk also fills one row of the bucket's ``Scores`` record inside the captured chunk -- each row's log-probability and
+    rank of the token it picked (md_token_logprobs, targets = the step's tokens) and its k most probable live tokens
+    (md_topk_logprobs, the launch after, gated by the step's tokens) -- and every ``Request`` carries ``logprobs`` / ``ranks``
+    and ``alternatives`` (k (token_id, logprob) pairs per id) beside its ids: ``run(with_logprobs=True)``.  They are, bit for
+    bit, the values of ``MoondreamModel.batch_generate_ids(..., return_logprobs=True, top_logprobs=k)``: the model's own
+    distribution at temperature 1, untruncated, whatever the request's sampling settings.  Off: the launches and graphs
+    of an engine without the flags."""
 
     def __init__(self, model, max_live: int = 64, chunk: int = 16, temperature: float = 0.0, top_p: float = DEFAULT_TOP_P,
                  admit_threshold: Optional[int] = None, logprobs: bool = False, top_logprobs: Optional[int] = None):
-        from .decode_loop import check_top_logprobs
-
         self.model = model
         self.logprobs = bool(logprobs)
         self.top_logprobs = check_top_logprobs(top_logprobs, self.logprobs)
@@ -490,20 +483,13 @@ class ContinuousEngine:
         """hidden [k, 1, D], the last rows of a prefill -> the first token of each request from its last row, as _prepare_sequences picks it (argmax, or
         top-p sampling with the request's own settings and first uniform: md_sample_rows over the group; no suppression).
         lm_head in launches of <= 64 rows: the decode-regime kernels, whatever the admission size.  Returns one tuple per
-        request: (token,), or with ``logprobs`` (token, logprob, rank) of the same logits, unsuppressed like the pick, and
-        with ``top_logprobs`` one more element: (top ids [k], top logprobs [k]) of that decision."""
+        request: (token,) and, of the same logits and unsuppressed like the pick, what ``SlotScheduler.start`` takes after it."""
         import torch
-
-        from .decode_loop import Sampling
 
         m = self.model
         k = len(reqs)
         first = torch.empty(k, dtype=torch.int32, device=m.device)
-        lp = torch.empty(k, dtype=torch.float32, device=m.device) if self.logprobs else None
-        rk = torch.empty(k, dtype=torch.int32, device=m.device) if self.logprobs else None
-        kk = self.top_logprobs
-        ti = torch.empty(k, kk, dtype=torch.int32, device=m.device) if kk else None
-        tl = torch.empty(k, kk, dtype=torch.float32, device=m.device) if kk else None
+        scores = Scores.new((k,), self.top_logprobs, m.device) if self.logprobs else None
         for i0 in range(0, k, 64):
             part = reqs[i0 : i0 + 64]
             i1 = i0 + len(part)
@@ -514,13 +500,12 @@ class ContinuousEngine:
                 st_d = m._h2d(torch.tensor([[r.temperature for r in part], [r.top_p for r in part], draws], dtype=torch.float32))
                 pick = Sampling(st_d[0], st_d[1])
             first[i0:i1] = m._first_token(m._lm_head(hidden[i0:i1]), pick, uniforms=st_d[2] if pick is not None else None,
-                                          logprobs=(lp[i0:i1], rk[i0:i1]) if self.logprobs else None,
-                                          topk=(ti[i0:i1], tl[i0:i1]) if kk else None)
-        if not self.logprobs:
+                                          scores=scores and scores[i0:i1])
+        if scores is None:
             return [(f,) for f in first.tolist()]
-        if not kk:
-            return list(zip(first.tolist(), lp.tolist(), rk.tolist()))
-        return list(zip(first.tolist(), lp.tolist(), rk.tolist(), zip(ti.cpu().numpy(), tl.cpu().numpy())))
+        host = scores.to_host(first)  # the tokens and their scores in one copy
+        top = [zip(host.top_ids, host.top_logprobs)] if self.top_logprobs else []
+        return list(zip(host.extra[0].tolist(), host.logprob.tolist(), host.rank.tolist(), *top))
 
     def _admit(self, reqs: List[Request]) -> List[Tuple[int, int]]:
         """ViT over the admitted raw images as one batch, then the prefill into their slots with the choices of
@@ -601,35 +586,15 @@ class ContinuousEngine:
             b = bufs[key] = (dev, host, u_dev, u_host, n_in)
         return b
 
-    def _logprob_buffers(self, bucket: int):
-        """Fixed-address int32 device words [2, chunk, bucket] of a (chunk, bucket): plane 0 the fp32 log-probabilities of a
-        chunk's tokens (as raw words), plane 1 their ranks -- one D2H copy of both.  Only an engine with ``logprobs`` has them."""
-        import torch
-
-        bufs = self.model.__dict__.setdefault("_continuous_logprob_bufs", {})
-        key = (self.chunk, bucket)
-        b = bufs.get(key)
-        if b is None:
-            b = bufs[key] = torch.zeros(2, self.chunk, bucket, dtype=torch.int32, device=self.model.device)
-        return b
-
-    def _topk_buffers(self, bucket: int):
-        """Fixed-address int32 device words [2, chunk, bucket, k] of a (chunk, bucket, k): plane 0 the alternatives' ids of a
-        chunk's decisions, plane 1 their fp32 log-probabilities (as raw words) -- one D2H copy of both.  Only an engine with
-        ``top_logprobs`` has them."""
-        import torch
-
-        bufs = self.model.__dict__.setdefault("_continuous_topk_bufs", {})
+    def _score_buffers(self, bucket: int):
+        """The fixed-address ``Scores`` over (chunk, bucket) with the engine's k that a chunk's steps fill (``logprobs`` only)."""
+        bufs = self.model.__dict__.setdefault("_continuous_score_bufs", {})
         key = (self.chunk, bucket, self.top_logprobs)
-        b = bufs.get(key)
-        if b is None:
-            b = bufs[key] = torch.zeros(2, self.chunk, bucket, self.top_logprobs, dtype=torch.int32, device=self.model.device)
-        return b
+        bufs[key] = bufs.get(key) or Scores.new((self.chunk, bucket), self.top_logprobs, self.model.device)
+        return bufs[key]
 
     def _step(self, plan: ChunkPlan) -> np.ndarray:
         import torch
-
-        from .decode_loop import DecodeChunk, Sampling, run_chunk
 
         m = self.model
         if m._kv_k.data_ptr() != self._kv_ptr:
@@ -664,18 +629,14 @@ class ContinuousEngine:
                     k = min(n, r.remaining)
                     uh[:k, r_idx] = self._uniforms(r, k).numpy()
             u_dev.copy_(u_host, non_blocking=True)
-        lp_words = self._logprob_buffers(B) if self.logprobs else None
+        scores = self._score_buffers(B) if self.logprobs else None  # (an idle or padding row's are never read: SlotScheduler.commit)
         # step i's routing: row i of the slot table; a LoRA row in the chunk: the chunk's row-variant table with it
         rows_of = lambda i: self._rows(slots_d[i], var_d if lora else None)
         # a sampling row in the chunk: every row picks with its own settings (a greedy row its argmax again, an idle row
         # nothing); the settings are device data, in the allocation of the uniforms
         pick = Sampling(u_dev[c * B : c * B + B], u_dev[c * B + B :]) if sample else None
-        # (an idle or padding row's log-probability is never read: SlotScheduler.commit)
-        planes = (lp_words[0].view(torch.float32), lp_words[1]) if self.logprobs else None
-        tk_words = self._topk_buffers(B) if self.top_logprobs else None
-        tk_planes = (tk_words[0], tk_words[1].view(torch.float32)) if self.top_logprobs else None
         chunk = DecodeChunk(B, hist, pos_d, rows_of, m.config.tokenizer.answer_id, self._decode_ws_bytes(B), pick,
-                            u_dev[: c * B].view(c, B), planes, topk=tk_planes)
+                            u_dev[: c * B].view(c, B), **(scores.chunk_fields() if scores else {}))
         stream = torch.cuda.current_stream(m.device).cuda_stream if m.use_graphs else None
 
         def below_cap():
@@ -684,10 +645,7 @@ class ContinuousEngine:
         if run_chunk(m, chunk, n, "continuous", stream, below_cap):
             self.stats.graph_captures += 1
         out = hist[1 : n + 1].cpu().numpy()  # the chunk's D2H copy of the ids (the lockstep loop syncs here too)
-        if lp_words is None:
+        if scores is None:
             return out
-        words = lp_words[:, :n].cpu().numpy()  # ... and one more of both planes
-        if tk_words is None:
-            return out, words[0].view(np.float32), words[1]
-        top = tk_words[:, :n].cpu().numpy()  # ... and of the alternatives' two
-        return out, words[0].view(np.float32), words[1], top[0], top[1].view(np.float32)
+        host = scores[:n].to_host()  # ... and one more of the chunk's scores
+        return (out, host.logprob, host.rank) + ((host.top_ids, host.top_logprobs) if self.top_logprobs else ())

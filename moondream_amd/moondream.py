@@ -33,6 +33,7 @@ from .decode_loop import DecodeChunk, ReasonChunk, Sampling, check_top_logprobs,
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
 from .lora import variant_state_dict
+from .scores import Scores
 from .shared_prefix import check_shared_table, plan_shared_prefix
 from .weights import PackedLora, PackedLoraBank, PackedModel
 
@@ -1180,23 +1181,27 @@ class MoondreamModel:
             "md_topk_logprobs",
         )
 
+    def _score(self, logits: torch.Tensor, targets: torch.Tensor, suppress_id: int, scores: Scores,
+               gate: Optional[torch.Tensor] = None, suppress_rows: Optional[torch.Tensor] = None):
+        """Fill ``scores`` (over [R]) for ``targets`` in ``logits`` [R, V]: ``_token_logprobs``, then ``_topk_logprobs`` if it has k."""
+        self._token_logprobs(logits, targets, suppress_id, scores.logprob, scores.rank, suppress_rows=suppress_rows)
+        if scores.k:
+            self._topk_logprobs(logits, gate, suppress_id, scores.top_ids, scores.top_logprobs, suppress_rows=suppress_rows)
+
     def _first_token(self, logits: torch.Tensor, pick: Optional[Sampling] = None, row_perm=None,
-                     uniforms: Optional[torch.Tensor] = None, logprobs=None, topk=None) -> torch.Tensor:
+                     uniforms: Optional[torch.Tensor] = None, scores: Optional[Scores] = None) -> torch.Tensor:
         """The first generated token of every row, int32 [B], from its prompt pass's logits [B, V]: the argmax (``pick``
         None), a draw with the call's settings (``row_perm``: the draw order of these rows) or with each row's own (and
-        ``uniforms`` fp32 [B]).  Nothing is suppressed (moondream.py:313-318).  ``logprobs`` = (fp32 [B], int32 [B]): filled
-        with the token's log-probability and rank, unsuppressed like the pick; ``topk`` = (int32 [B, k], fp32 [B, k]): with
-        the decision's alternatives, unsuppressed too."""
+        ``uniforms`` fp32 [B]).  Nothing is suppressed (moondream.py:313-318).  ``scores`` (a record over [B]): filled with
+        the decision's log-probability, rank and alternatives, unsuppressed like the pick."""
         if pick is None:
             first = self._pick(logits, 0.0, 0.0)
         elif pick.per_row:
             first = self._pick_rows(logits, pick.temperature, pick.top_p, -1, uniforms)
         else:
             first = self._pick(logits, pick.temperature, pick.top_p, -1, pick.generator, row_perm=row_perm)
-        if logprobs is not None:
-            self._token_logprobs(logits, first, -1, *logprobs)
-        if topk is not None:
-            self._topk_logprobs(logits, None, -1, *topk)
+        if scores is not None:
+            self._score(logits, first, -1, scores)
         return first
 
     # ---------------------------------------------------------- batched engine
@@ -1235,7 +1240,7 @@ class MoondreamModel:
 
     def _decode_greedy_impl(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
                             rows: Union[int, _Rows] = 0, eos_id: Optional[int] = None, check_every: int = 16,
-                            allow_b1: bool = True, sampling: Optional[Sampling] = None, first_logprobs=None):
+                            allow_b1: bool = True, sampling: Optional[Sampling] = None, scores: Optional[Scores] = None):
         """Device-resident decode loop: returns int32 [steps+1, B] (row 0 = ``first``).  ``sampling`` None: greedy.  Otherwise every
         step draws each sequence's token with the reference's rule (moondream.py:521-528: softmax(logits / T), _apply_top_p,
         multinomial) from the step's own logits on the device (md_sample_top_p), with one uniform per (step, sequence) taken
@@ -1246,11 +1251,9 @@ class MoondreamModel:
         prompts differ in length decode in the same lockstep batch).
         The steps run in chunks (``run_chunk``): eagerly over the history itself, or with ``compile()`` replayed from a
         captured hipGraph over the fixed buffers of the chunk's shape.  ``rows``: the routing of every step (``_Rows``).
-        ``first_logprobs`` = (logprob fp32 [B], rank int32 [B]) of ``first``: the loop also keeps the log-probability and rank
-        of every token it picks (``_token_logprobs`` on the logits the step leaves, one launch after the step's pick, inside
-        the captured graph) and returns (hist, logprobs fp32 [steps+1, B], ranks int32 [steps+1, B]).  No id changes.
-        With two more tensors, (.., top ids int32 [B, k], top logprobs fp32 [B, k]) of ``first``'s decision, it keeps every
-        decision's k alternatives too (``_topk_logprobs``, the launch after) and returns two more planes [steps+1, B, k]."""
+        ``scores``: a record over [>= max_tokens + 1, B] whose row 0 holds ``first``'s decision; the loop fills row i for the
+        tokens of ``hist[i]`` (``_token_logprobs`` on the logits the step leaves, then ``_topk_logprobs`` when the record has
+        alternatives: the launches after the step's pick, inside the captured graph) and changes no id for it."""
         rows = _Rows.of(rows)
         b = first.shape[0]
         t = self.config.text
@@ -1263,21 +1266,8 @@ class MoondreamModel:
         hist = torch.zeros(max_tokens + 1, b, dtype=torch.int32, device=self._device)
         hist[0] = first
         self._b1_used = False
-        with_lp = first_logprobs is not None
-        if with_lp:
-            lp_hist = torch.full((max_tokens + 1, b), float("nan"), dtype=torch.float32, device=self._device)
-            rk_hist = torch.full((max_tokens + 1, b), -1, dtype=torch.int32, device=self._device)
-            lp_hist[0], rk_hist[0] = first_logprobs[:2]
-        with_tk = with_lp and len(first_logprobs) == 4
-        top_k = first_logprobs[2].shape[1] if with_tk else 0
-        if with_tk:
-            ti_hist = torch.full((max_tokens + 1, b, top_k), -1, dtype=torch.int32, device=self._device)
-            tl_hist = torch.full((max_tokens + 1, b, top_k), float("nan"), dtype=torch.float32, device=self._device)
-            ti_hist[0], tl_hist[0] = first_logprobs[2:]
-        done = lambda upto: (((hist[:upto], lp_hist[:upto], rk_hist[:upto]) + ((ti_hist[:upto], tl_hist[:upto]) if with_tk else ()))
-                             if with_lp else hist[:upto])
         if max_tokens == 0:
-            return done(1)
+            return hist
         pos_base = self._h2d(torch.tensor(pos_list, dtype=torch.int32))
         uniforms = None
         if sampling is not None:
@@ -1323,43 +1313,34 @@ class MoondreamModel:
         steps = 0
         while steps < max_tokens:
             n = min(per, max_tokens - steps)
+            into = scores and scores[steps + 1 :]  # where the steps leave their scores: in the record itself, or ...
             if graphs:
                 # the fixed buffers of this shape on this stream (the pipelined engine's decode stream and the default stream
                 # each have their own), refreshed before each replay; its graphs share them: a stream runs one chunk at a time
                 fixed = self.__dict__.setdefault("_chunk_bufs", {})
                 if (stream, b, n) not in fixed:
                     zeros = lambda rows, dtype: torch.zeros(rows, b, dtype=dtype, device=self._device)
-                    fixed[stream, b, n] = (zeros(n + 1, torch.int32), zeros(1, torch.int32)[0], zeros(n, torch.float32),
-                                           zeros(n, torch.float32), zeros(n, torch.int32))
-                buf, pos_buf, u_buf, lp_buf, rk_buf = fixed[stream, b, n]
-                if with_tk:  # the alternatives' planes of this shape and k, beside the others
-                    if (stream, b, n, top_k) not in fixed:
-                        fixed[stream, b, n, top_k] = (torch.zeros(n, b, top_k, dtype=torch.int32, device=self._device),
-                                                      torch.zeros(n, b, top_k, dtype=torch.float32, device=self._device))
-                    ti_buf, tl_buf = fixed[stream, b, n, top_k]
+                    fixed[stream, b, n] = (zeros(n + 1, torch.int32), zeros(1, torch.int32)[0], zeros(n, torch.float32))
+                buf, pos_buf, u_buf = fixed[stream, b, n]
+                if scores is not None:  # ... in the fixed planes of this shape and k, which only a call that asks makes
+                    key = (stream, b, n, "scores", scores.k)
+                    into = fixed[key] = fixed.get(key) or Scores.new((n, b), scores.k, self._device)
                 buf[0] = hist[steps]
                 pos_buf.copy_(pos_base + steps)
                 if uniforms is not None:
                     u_buf.copy_(uniforms[steps : steps + n])
-                part = replace(chunk, tokens=buf, pos=pos_buf, uniforms=u_buf if uniforms is not None else None,
-                               logprobs=(lp_buf, rk_buf) if with_lp else None, topk=(ti_buf, tl_buf) if with_tk else None)
+                part = replace(chunk, tokens=buf, pos=pos_buf, uniforms=u_buf if uniforms is not None else None)
             else:
-                part = replace(chunk, tokens=hist[steps:], uniforms=uniforms[steps:] if uniforms is not None else None,
-                               logprobs=(lp_hist[steps + 1 :], rk_hist[steps + 1 :]) if with_lp else None,
-                               topk=(ti_hist[steps + 1 :], tl_hist[steps + 1 :]) if with_tk else None)
-            run_chunk(self, part, n, capture_stream=stream)
+                part = replace(chunk, tokens=hist[steps:], uniforms=uniforms[steps:] if uniforms is not None else None)
+            run_chunk(self, replace(part, **into.chunk_fields()) if into else part, n, capture_stream=stream)
             if graphs:
                 hist[steps + 1 : steps + n + 1] = buf[1:]
-                if with_lp:
-                    lp_hist[steps + 1 : steps + n + 1] = lp_buf
-                    rk_hist[steps + 1 : steps + n + 1] = rk_buf
-                if with_tk:
-                    ti_hist[steps + 1 : steps + n + 1] = ti_buf
-                    tl_hist[steps + 1 : steps + n + 1] = tl_buf
+                if scores is not None:
+                    scores[steps + 1 : steps + n + 1].copy_(into)
             steps += n
             if steps < max_tokens and eos_id is not None and bool((hist[: steps + 1] == eos_id).any(dim=0).all()):
                 break  # every sequence has emitted its EOS
-        return done(steps + 1)
+        return hist[: steps + 1]
 
     def _replay_or_capture(self, key, body, may_capture=None) -> bool:
         """Replay the graph stored under ``key``; a key not seen before runs ``body`` eagerly, then captures it and stores
@@ -1410,13 +1391,12 @@ class MoondreamModel:
         return out
 
     def _prefill_groups(self, groups: Sequence[Tuple[int, int]], embed, pos: int, rows: _Rows, sampling: Optional[Sampling] = None,
-                        logits_capture: Optional[torch.Tensor] = None, first_logprobs=None, hidden_sink=None):
+                        logits_capture: Optional[torch.Tensor] = None, scores: Optional[Scores] = None, hidden_sink=None):
         """One decoder pass per group [r0, r1) of equal-length prompts: ``embed(r0, r1)`` [r1-r0, T, D] goes through the decoder
         at position ``pos`` into the slots of ``rows.sub(r0, r1)``, then lm_head and the pick of the first token (``_first_token``;
         ``sampling`` None: argmax; a group draws in its rows' order among themselves in ``sampling.row_perm``).
-        Returns (first int32 [B], hidden_last [B, D], next_pos list); the groups' logits go to ``logits_capture`` [B, V], the
-        log-probability and rank of each first token (unsuppressed, like the pick) to ``first_logprobs`` = (fp32 [B], int32 [B])
-        -- with two more tensors, (.., int32 [B, k], fp32 [B, k]), the first decision's k alternatives go to those.
+        Returns (first int32 [B], hidden_last [B, D], next_pos list); the groups' logits go to ``logits_capture`` [B, V], each
+        first decision's log-probability, rank and alternatives (unsuppressed, like the pick) to ``scores``, a record over [B].
         ``hidden_sink(r0, r1, hidden [r1-r0, T, D])``: the scorer's form -- every hidden row of the pass goes to the sink, and
         no first token is picked (``first`` and ``hidden_last`` are not filled)."""
         b = groups[-1][1]
@@ -1434,15 +1414,14 @@ class MoondreamModel:
             if logits_capture is not None:
                 logits_capture[r0:r1] = logits
             perm = sampling.row_perm[r0:r1] if sampling is not None and sampling.row_perm is not None else None
-            own = [x[r0:r1] for x in first_logprobs] if first_logprobs is not None else []  # (logprob, rank[, top ids, top logprobs])
             first[r0:r1] = self._first_token(logits, sampling, perm - perm.min() if perm is not None else None,
-                                             logprobs=own[:2] or None, topk=own[2:] or None)
+                                             scores=scores and scores[r0:r1])
             hidden_last[r0:r1] = hidden[:, -1, :]
         return first, hidden_last, next_pos
 
     def _prepare_sequences(self, images, prompts: Sequence[Sequence[int]], mark=None, rows: Union[int, _Rows] = 0,
                            fuse: bool = False, logits_capture: Optional[torch.Tensor] = None,
-                           sampling: Optional[Sampling] = None, first_logprobs=None, hidden_sink=None):
+                           sampling: Optional[Sampling] = None, scores: Optional[Scores] = None, hidden_sink=None):
         """Everything before the first generated token, for B (image, prompt-ids) pairs: sequences are
         placed in KV slots in order of prompt length (stable), so that every group of equal-length
         prompts occupies a contiguous slot range; raw images are encoded together and prefilled
@@ -1451,7 +1430,7 @@ class MoondreamModel:
         order; ``order[slot]`` is the caller's index.  ``sampling`` draws the first token
         as the reference's _prefill_prompt does (moondream.py:313-318; nothing suppressed there); None = argmax.  Must run under
         torch.inference_mode().  ``rows``: the routing of slots 0 .. B-1 (a per-row variant table is already in slot order).
-        ``first_logprobs`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in slot order."""
+        ``scores`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in slot order."""
         mark = mark or (lambda name: None)
         rows = _Rows.of(rows)
         b = len(images)
@@ -1480,7 +1459,7 @@ class MoondreamModel:
             bos = self._embed(torch.full((b, 1), self.config.tokenizer.bos_id, dtype=torch.int32))
             fused = lambda g0, g1: torch.cat([bos[g0:g1], img_emb[g0:g1], embed_prompts(g0, g1)], dim=1)
             out = self._prefill_groups(_length_groups(prompts), fused, 0, rows, sampling, logits_capture,
-                                       first_logprobs=first_logprobs, hidden_sink=hidden_sink)
+                                       scores=scores, hidden_sink=hidden_sink)
             mark("image_prefill")
             mark("prompt_prefill")
             return (order, *out)
@@ -1497,7 +1476,7 @@ class MoondreamModel:
                 self.load_encoded_image(im, i)
                 pos = im.pos
         out = self._prefill_groups(_length_groups(prompts), embed_prompts, pos, rows, sampling, logits_capture,
-                                   first_logprobs=first_logprobs, hidden_sink=hidden_sink)  # one per prompt length
+                                   scores=scores, hidden_sink=hidden_sink)  # one per prompt length
         mark("prompt_prefill")
         return (order, *out)
 
@@ -1528,7 +1507,7 @@ class MoondreamModel:
         return [enc[id(im)] for im in images]
 
     def _prepare_sequences_shared(self, images, prompts: Sequence[Sequence[int]], mark=None, sampling: Optional[Sampling] = None,
-                                  first_logprobs=None, hidden_sink=None):
+                                  scores: Optional[Scores] = None, hidden_sink=None):
         """``_prepare_sequences`` with a SHARED image prefix (moondream_amd/shared_prefix.py): each distinct image (by identity)
         is prefilled or loaded ONCE, into prefix slot k < P; the rows take slots P + r and read the prefix from there.  Raw
         images go through one ViT batch and ``_prefill_images``; EncodedImages are loaded once.  In the fp8 KV mode both of these
@@ -1537,7 +1516,7 @@ class MoondreamModel:
         distinct length (md_text_forward_shared).  Returns (order, first, hidden_last, next_pos, rows, sampling): the first
         four as ``_prepare_sequences`` returns them, in this path's row order; ``rows`` is the routing over the prefix table
         (``_Rows``); ``sampling`` is the caller's with ``row_perm`` set: a row's row in the copy path's order (None stays None).
-        ``first_logprobs`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in this path's row order.  Must run under torch.inference_mode()."""
+        ``scores`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in this path's row order.  Must run under torch.inference_mode()."""
         mark = mark or (lambda name: None)
         plan = plan_shared_prefix(list(images), [len(p) for p in prompts])
         if any(len(p) == 0 for p in prompts):
@@ -1576,7 +1555,7 @@ class MoondreamModel:
         # one prefill per distinct prompt length; a sampled group draws in the copy path's row order
         first, hidden_last, next_pos = self._prefill_groups(
             plan.groups, lambda r0, r1: self._embed(torch.tensor(prompts[r0:r1], dtype=torch.int32)), pos, rows, sampling,
-            first_logprobs=first_logprobs, hidden_sink=hidden_sink)
+            scores=scores, hidden_sink=hidden_sink)
         mark("prompt_prefill")
         return plan.order, first, hidden_last, next_pos, rows, sampling
 
@@ -1675,15 +1654,11 @@ class MoondreamModel:
         with torch.inference_mode():
             sampling = None if temperature == 0 else Sampling(float(temperature), float(top_p), generator)
             rows = _Rows(lora=lora)
-            first_lp = None
-            if return_logprobs:
-                first_lp = (torch.empty(b, dtype=torch.float32, device=self._device), torch.empty(b, dtype=torch.int32, device=self._device))
-                if top_k:
-                    first_lp += (torch.empty(b, top_k, dtype=torch.int32, device=self._device),
-                                 torch.empty(b, top_k, dtype=torch.float32, device=self._device))
+            rows_t = max(0, min(max_tokens, self.config.text.max_context)) + 1  # row 0: the prefill's decision, then the loop's
+            scores = Scores.new((rows_t, b), top_k, self._device, fill=True) if return_logprobs else None
             if multi_rows is None and share_prefix and self._shares_prefix(lora):
                 order, first, _, next_pos, rows, sampling = self._prepare_sequences_shared(list(images), prompts, mark, sampling,
-                                                                                           first_logprobs=first_lp)
+                                                                                           scores=scores and scores[0])
             else:
                 if multi_rows is not None:
                     # the slot order of _prepare_sequences (stable by prompt length), so that the table is in slot order too
@@ -1692,45 +1667,25 @@ class MoondreamModel:
                 elif share_prefix:  # the copy path over each distinct image's EncodedImage
                     images = self._encode_distinct(images, {"variant": variant})
                 order, first, _, next_pos = self._prepare_sequences(list(images), prompts, mark, rows, fuse=True, sampling=sampling,
-                                                                    first_logprobs=first_lp)
-            b = len(order)
+                                                                    scores=scores and scores[0])
             stop = None if ignore_eos else eos
             hist = self._decode_greedy(first, next_pos if len(set(next_pos)) > 1 else next_pos[0], max_tokens,
-                                       tk.answer_id, rows, stop, sampling=sampling, first_logprobs=first_lp)
+                                       tk.answer_id, rows, stop, sampling=sampling, scores=scores)
             mark("decode")
-            if top_k:  # ... and the alternatives: [T, B] words of ids, logprobs, ranks, then [T, B, k] of top ids, top logprobs
-                hist, lp_hist, rk_hist, ti_hist, tl_hist = hist
-                n_t = hist.shape[0]
-                flat = torch.cat([hist.reshape(-1), lp_hist.view(torch.int32).reshape(-1), rk_hist.reshape(-1),
-                                  ti_hist.reshape(-1), tl_hist.view(torch.int32).reshape(-1)]).cpu().numpy()
-                packed = flat[: 3 * n_t * b].reshape(3, n_t, b)
-                top = flat[3 * n_t * b :].reshape(2, n_t, b, top_k)
-                ti_cols = top[0].transpose(1, 0, 2).tolist()  # [B][T][k]
-                tl_cols = top[1].view(np.float32).transpose(1, 0, 2).tolist()
-            elif return_logprobs:  # ids, logprobs (as raw words) and ranks in ONE copy to the host
-                hist, lp_hist, rk_hist = hist
-                packed = torch.stack([hist, lp_hist.view(torch.int32), rk_hist]).cpu().numpy()
-            if return_logprobs:
-                cols = packed[0].T.tolist()
-                lp_cols, rk_cols = packed[1].view(np.float32).T.tolist(), packed[2].T.tolist()
-            else:
-                cols = hist.t().tolist()
+            host = scores and scores[: hist.shape[0]].to_host(hist)  # ids, logprobs, ranks, alternatives: ONE copy to the host
+            cols = (host.extra[0].T if host else hist.t()).tolist()
             if b == 1:
                 self._check_b1_barriers()
-            results: List[Optional[List[int]]] = [None] * b
-            logprobs: List[Optional[List[float]]] = [None] * b
-            ranks: List[Optional[List[int]]] = [None] * b
-            alternatives: list = [None] * b
+            results, logprobs, ranks, alternatives = ([None] * b for _ in range(4))  # per caller's row
             for slot, src in enumerate(order):
                 results[src] = self._truncate(cols[slot], stop, max_tokens)
-                if return_logprobs:  # _truncate keeps a leading run of the ids: the same run of their values
-                    logprobs[src], ranks[src] = lp_cols[slot][: len(results[src])], rk_cols[slot][: len(results[src])]
+                n = len(results[src])  # _truncate keeps a leading run of the ids: the same run of their values
+                if return_logprobs:
+                    logprobs[src], ranks[src] = host.logprob[:n, slot].tolist(), host.rank[:n, slot].tolist()
                 if top_k:
-                    alternatives[src] = [list(zip(ti_cols[slot][j], tl_cols[slot][j])) for j in range(len(results[src]))]
+                    alternatives[src] = host.alternatives((slice(n), slot))
         self._phase_times(marks)
-        if top_k:
-            return results, logprobs, ranks, alternatives
-        return (results, logprobs, ranks) if return_logprobs else results  # type: ignore[return-value]
+        return (results, logprobs, ranks, alternatives)[: 4 if top_k else 3] if return_logprobs else results
 
     def batch_generate_ids_continuous(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                                       eos_id: Optional[int] = None, ignore_eos: bool = False, max_live: int = 64, chunk: int = 16,
@@ -1860,24 +1815,12 @@ class MoondreamModel:
             for i0 in range(0, r, 64):
                 self._lm_head(hidden[i0 : i0 + 64], out=logits[i0 : i0 + 64])
             tab = self._h2d(torch.tensor([targets, suppress], dtype=torch.int32))
-            lp = torch.empty(r, dtype=torch.float32, device=self._device)
-            rk = torch.empty(r, dtype=torch.int32, device=self._device)
-            self._token_logprobs(logits, tab[0], tk.answer_id, lp, rk, suppress_rows=tab[1])
-            words = [lp.view(torch.int32), rk]
-            if top_k:
-                ti = torch.empty(r, top_k, dtype=torch.int32, device=self._device)
-                tl = torch.empty(r, top_k, dtype=torch.float32, device=self._device)
-                self._topk_logprobs(logits, None, tk.answer_id, ti, tl, suppress_rows=tab[1])
-                words += [ti.reshape(-1), tl.view(torch.int32).reshape(-1)]
-            packed = torch.cat(words).cpu().numpy()  # one copy to the host
-        lp_h, rk_h = packed[:r].view(np.float32).tolist(), packed[r : 2 * r].tolist()
-        n = len(conts)
-        out = [lp_h[span[i][0] : span[i][1]] for i in range(n)], [rk_h[span[i][0] : span[i][1]] for i in range(n)]
-        if not top_k:
-            return out
-        ti_h = packed[2 * r : 2 * r + r * top_k].reshape(r, top_k).tolist()
-        tl_h = packed[2 * r + r * top_k :].view(np.float32).reshape(r, top_k).tolist()
-        return out + ([[list(zip(ti_h[j], tl_h[j])) for j in range(*span[i])] for i in range(n)],)
+            scores = Scores.new((r,), top_k, self._device)
+            self._score(logits, tab[0], tk.answer_id, scores, suppress_rows=tab[1])
+            host = scores.to_host()  # one copy to the host
+        spans = [slice(*span[i]) for i in range(len(conts))]
+        out = [host.logprob[s].tolist() for s in spans], [host.rank[s].tolist() for s in spans]
+        return out + ([host.alternatives(s) for s in spans],) if top_k else out
 
     # ------------------------------------------------------ pipelined batches
     def _streams(self):

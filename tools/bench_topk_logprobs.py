@@ -4,11 +4,12 @@ profiles/topk_logprobs_bench.json.
   generation   B = 64 synthetic images, the caption prompt, greedy, 32 tokens with ``ignore_eos``: images/s of
                ``batch_generate_ids`` in the legs logprobs off, ``return_logprobs`` only, ``top_logprobs=5`` and
                ``top_logprobs=20`` and, with ``--parent-repo DIR`` (a built checkout of the parent commit), that tree's
-               ``return_logprobs`` and off legs -- each in ``--procs`` fresh processes that alternate (off, lp, top5, top20,
-               parent, parent_off, off, ..); per process the median of ``--repeats`` timed calls after a warm-up (graph
-               captures), per leg the median and the span of the process medians.  ``top5_vs_lp`` / ``top20_vs_lp``: the
-               flag's cost against the ``return_logprobs`` leg of the same run; ``off_within_parent_span`` /
-               ``lp_within_parent_span``: whether this tree's median lies inside the span of the parent's same leg.
+               ``return_logprobs``, off and ``top_logprobs=5`` legs -- each in ``--procs`` fresh processes that alternate (off,
+               lp, top5, top20, parent, parent_off, parent_top5, off, ..); per process the median of ``--repeats`` timed calls
+               after a warm-up (graph captures), per leg the median and the span of the process medians.  ``top5_vs_lp`` /
+               ``top20_vs_lp``: the flag's cost against the ``return_logprobs`` leg of the same run; ``off_within_parent_span``
+               / ``lp_within_parent_span`` / ``top5_within_parent_span``: whether this tree's median lies inside the span of
+               the parent's same leg.
   score        one ``score_ids(..., top_logprobs=5)`` call over 64 eight-token continuations after one encoded image, in
                continuations per second, against the only route to these numbers without it: the same decisions as forced
                decode steps through ``teacher_forced_logits`` gathering the whole vocabulary, then ``log_softmax`` and
@@ -28,7 +29,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bench_logprobs import B, CHOICE_IDS, N_CHOICES, TOKENS, build_model, timed  # noqa: E402
 
 LEGS = {"off": {}, "lp": {"return_logprobs": True}, "top5": {"return_logprobs": True, "top_logprobs": 5},
-        "top20": {"return_logprobs": True, "top_logprobs": 20}, "parent": {"return_logprobs": True}, "parent_off": {}}
+        "top20": {"return_logprobs": True, "top_logprobs": 20}, "parent": {"return_logprobs": True}, "parent_off": {},
+        "parent_top5": {"return_logprobs": True, "top_logprobs": 5}}
 SCORE_K = 5
 
 
@@ -101,7 +103,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--procs", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--parent-repo", default=None, help="a built checkout of the parent commit (its return_logprobs leg)")
+    ap.add_argument("--parent-repo", default=None, help="a built checkout of the parent commit (its legs)")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "topk_logprobs_bench.json"))
     ap.add_argument("--worker", choices=("generation", "score"))
     ap.add_argument("--leg", choices=tuple(LEGS), default="off")
@@ -132,7 +134,7 @@ def main():
         gen[f"{leg}_vs_lp"] = round(gen[leg]["images_per_s_median"] / gen["lp"]["images_per_s_median"], 4)
     gen["lp_vs_off"] = round(gen["lp"]["images_per_s_median"] / gen["off"]["images_per_s_median"], 4)
     if args.parent_repo:
-        for leg, parent in (("lp", "parent"), ("off", "parent_off")):
+        for leg, parent in (("lp", "parent"), ("off", "parent_off"), ("top5", "parent_top5")):
             lo, hi = gen[parent]["images_per_s_span"]
             gen[f"{leg}_within_parent_span"] = lo <= gen[leg]["images_per_s_median"] <= hi
     result["generation"] = gen
