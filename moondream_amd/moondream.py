@@ -34,7 +34,7 @@ from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
 from .lora import variant_state_dict
 from .scores import Scores
-from .shared_prefix import check_shared_table, plan_shared_prefix
+from .shared_prefix import RowPlan, check_shared_table, plan_rows
 from .weights import PackedLora, PackedLoraBank, PackedModel
 
 BF16 = torch.bfloat16
@@ -168,16 +168,27 @@ def _runs(idx: Sequence[int]) -> List[Tuple[int, int]]:
     return out
 
 
-def _length_groups(prompts: Sequence[Sequence[int]]) -> List[Tuple[int, int]]:
-    """[g0, g1) ranges of consecutive prompts of equal length."""
-    out, g0 = [], 0
-    while g0 < len(prompts):
-        g1 = g0
-        while g1 < len(prompts) and len(prompts[g1]) == len(prompts[g0]):
-            g1 += 1
-        out.append((g0, g1))
-        g0 = g1
-    return out
+@dataclass(frozen=True)
+class Prepared:
+    """What ``_prepare_sequences`` leaves for the decode loop, rows in slot order."""
+
+    order: List[int]           # order[r] = the caller's index of row r
+    first: torch.Tensor        # int32 [B]: the first token of each row
+    hidden_last: torch.Tensor  # [B, D]: the prompt pass's last hidden row
+    next_pos: List[int]
+    rows: _Rows                # the routing the decode loop must use
+    sampling: Optional[Sampling]  # the caller's; on the shared route with ``row_perm`` set
+
+    def in_caller_order(self, per_row: Sequence) -> list:
+        out = [None] * len(self.order)
+        for r, src in enumerate(self.order):
+            out[src] = per_row[r]
+        return out
+
+    @property
+    def pos(self) -> Union[int, List[int]]:
+        """The decode loop's start position: one int when every row has the same."""
+        return self.next_pos if len(set(self.next_pos)) > 1 else self.next_pos[0]
 
 
 class IdTokenizer:
@@ -483,7 +494,7 @@ class MoondreamModel:
         try:
             with torch.inference_mode():
                 n = len(calibration_images)
-                self._prepare_sequences(list(calibration_images), [prompt] * n, fuse=True)
+                self._prepare_sequences(calibration_images, [prompt] * n, fuse=True)
                 torch.cuda.synchronize(self._device)
                 t = self.config.text
                 p1 = t.prefix_attn + len(prompt)
@@ -1419,66 +1430,97 @@ class MoondreamModel:
             hidden_last[r0:r1] = hidden[:, -1, :]
         return first, hidden_last, next_pos
 
+    def _place_images(self, images, rows: _Rows, mark) -> int:
+        """Image k's KV prefix into slot k of ``rows``: the raw images go through ONE ViT batch and every run of consecutive
+        slots through one ``_prefill_images`` (which, like ``load_encoded_image``, also writes the slot's e4m3 rows in the fp8
+        KV mode); EncodedImages are loaded.  Returns the prefix length, the same for every image."""
+        raw = [k for k, im in enumerate(images) if not isinstance(im, EncodedImage)]
+        for k in raw:
+            if not isinstance(images[k], Image.Image):
+                raise ValueError("image must be a PIL Image or EncodedImage")
+        pos = None
+        if raw:
+            img_emb = self._run_vision_encoder_batch([images[k] for k in raw], mark)
+            mark("vision")
+            for j0, j1 in _runs(raw):
+                pos = self._prefill_images(img_emb[j0:j1], rows.sub(raw[j0], raw[j1 - 1] + 1))
+            mark("image_prefill")
+        for k, im in enumerate(images):
+            if isinstance(im, EncodedImage):
+                if pos is not None and im.pos != pos:
+                    raise ValueError("EncodedImage with a different prefix length than the rest of the batch")
+                self.load_encoded_image(im, k)
+                pos = im.pos
+        return pos
+
+    def _shared_routing(self, plan: RowPlan, pos: int) -> _Rows:
+        """The routing of a shared plan's rows over its prefix table (every prefix ``pos`` positions long), checked."""
+        b = len(plan.order)
+        check_shared_table(plan.own_slots, plan.prefix_slots, [pos] * b, [pos] * b, plan.n_slots)
+        buf = getattr(self, "_shared_buf", None)  # one persistent buffer: captured decode graphs keep its addresses
+        if buf is None or buf.numel() < 3 * b:
+            buf = torch.empty(3 * max(b, 64), dtype=torch.int32, device=self._device)
+            self._shared_buf = buf
+        buf[: 3 * b].copy_(self._h2d(torch.tensor(plan.own_slots + plan.prefix_slots + [pos] * b, dtype=torch.int32)))
+        return _Rows(slots=buf[0:b], n_slots=plan.n_slots, prefix_slots=buf[b : 2 * b], prefix_len=buf[2 * b : 3 * b])
+
     def _prepare_sequences(self, images, prompts: Sequence[Sequence[int]], mark=None, rows: Union[int, _Rows] = 0,
-                           fuse: bool = False, logits_capture: Optional[torch.Tensor] = None,
-                           sampling: Optional[Sampling] = None, scores: Optional[Scores] = None, hidden_sink=None):
-        """Everything before the first generated token, for B (image, prompt-ids) pairs: sequences are
-        placed in KV slots in order of prompt length (stable), so that every group of equal-length
-        prompts occupies a contiguous slot range; raw images are encoded together and prefilled
-        straight into their slots, EncodedImages are copied into theirs; one prompt prefill per
-        distinct length.  Returns (order, first int32 [B], hidden_last [B, D], next_pos list) in slot
-        order; ``order[slot]`` is the caller's index.  ``sampling`` draws the first token
-        as the reference's _prefill_prompt does (moondream.py:313-318; nothing suppressed there); None = argmax.  Must run under
-        torch.inference_mode().  ``rows``: the routing of slots 0 .. B-1 (a per-row variant table is already in slot order).
-        ``scores`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in slot order."""
+                           fuse: bool = False, share_prefix: bool = False, variants: Optional[Sequence[int]] = None,
+                           encode_settings: Optional[dict] = None, logits_capture: Optional[torch.Tensor] = None,
+                           sampling: Optional[Sampling] = None, scores: Optional[Scores] = None, hidden_sink=None) -> Prepared:
+        """Everything before the first generated token, for B (image, prompt-ids) pairs, as ``plan_rows`` lays them out
+        (moondream_amd/shared_prefix.py): every image's KV prefix is placed (``_place_images``), then one prompt prefill per
+        distinct length picks the first tokens.  Returns a ``Prepared``, rows in slot order.  The COPY route gives row r slot
+        r under ``rows``, rows in stable order of prompt length.  The SHARED route (``share_prefix``, when ``_shares_prefix``
+        and no ``variants``) places each distinct image (by identity) ONCE, into prefix slot k < P; the rows take slots P + r
+        and read the prefix from there (md_text_forward_shared), and a sampled group draws in the copy route's row order
+        (``row_perm``).  ``share_prefix`` that is not served shared runs the copy route over each distinct image's
+        EncodedImage (``encode_settings``).  ``variants``: each row's bank index (-1: the base model) in the CALLER's order;
+        the device table is built in slot order here.  ``fuse``: an all-raw copy route takes the one-pass prefill below.
+        ``sampling`` draws the first token as the reference's _prefill_prompt does (moondream.py:313-318; nothing suppressed
+        there); None = argmax.
+        ``logits_capture`` / ``scores`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in slot order.  Must run under
+        torch.inference_mode()."""
         mark = mark or (lambda name: None)
         rows = _Rows.of(rows)
-        b = len(images)
-        self._select_kernels(b)
-        order = sorted(range(b), key=lambda i: len(prompts[i]))
-        images = [images[i] for i in order]
-        prompts = [list(prompts[i]) for i in order]
+        share = share_prefix and variants is None and self._shares_prefix(rows.lora)
         if any(len(p) == 0 for p in prompts):
             raise ValueError("empty prompt")
-        self._ensure_batch(b)
-        raw_idx = [i for i, im in enumerate(images) if not isinstance(im, EncodedImage)]
-        for i in raw_idx:
-            if not isinstance(images[i], Image.Image):
-                raise ValueError("image must be a PIL Image or EncodedImage")
+        if share_prefix and variants is None and not share:
+            images = self._encode_distinct(images, encode_settings)
+        plan = plan_rows(list(images), [len(p) for p in prompts], share)
+        b = len(plan.order)
+        self._select_kernels(b)
+        prompts = [list(prompts[i]) for i in plan.order]
+        self._ensure_batch(plan.n_slots)
+        if variants is not None:
+            rows = _Rows(variants=self._variant_table([variants[i] for i in plan.order]), bank=self._bank)
         mark("start")
-        pos = None
-        embed_prompts = lambda g0, g1: self._embed(torch.tensor(prompts[g0:g1], dtype=torch.int32))
-        if len(raw_idx) == b and fuse and self.fused_prefill:
+        embed_prompts = lambda r0, r1: self._embed(torch.tensor(prompts[r0:r1], dtype=torch.int32))
+        fused = fuse and self.fused_prefill and not share and all(isinstance(im, Image.Image) for im in plan.placed)
+        if fused:
             # Every image is raw: image prefix and prompt go through the decoder in ONE pass per group of equal-length
             # prompts ([bos | 729 image embeddings | prompt] at position 0).  The attention kernels evaluate the
             # reference's mask rule per element (bidirectional inside the first 730 positions, causal after), so this is
             # the same computation as the reference's two passes (moondream.py:228-262 then 280-321) up to accumulation
             # order -- one pass over the weights saved (fused_prefill = False keeps the two passes).
-            img_emb = self._run_vision_encoder_batch(images, mark)
+            img_emb = self._run_vision_encoder_batch(plan.placed, mark)
             mark("vision")
             bos = self._embed(torch.full((b, 1), self.config.tokenizer.bos_id, dtype=torch.int32))
-            fused = lambda g0, g1: torch.cat([bos[g0:g1], img_emb[g0:g1], embed_prompts(g0, g1)], dim=1)
-            out = self._prefill_groups(_length_groups(prompts), fused, 0, rows, sampling, logits_capture,
-                                       scores=scores, hidden_sink=hidden_sink)
+            embed = lambda r0, r1: torch.cat([bos[r0:r1], img_emb[r0:r1], embed_prompts(r0, r1)], dim=1)
+            pos = 0
+        else:
+            embed = embed_prompts
+            pos = self._place_images(plan.placed, _Rows() if share else rows, mark)
+            if share:
+                rows = self._shared_routing(plan, pos)
+                if sampling is not None:
+                    sampling = replace(sampling, row_perm=torch.tensor(plan.copy_rank, dtype=torch.int64, device=self._device))
+        out = self._prefill_groups(plan.groups, embed, pos, rows, sampling, logits_capture, scores=scores, hidden_sink=hidden_sink)
+        if fused:  # the one pass is both
             mark("image_prefill")
-            mark("prompt_prefill")
-            return (order, *out)
-        if raw_idx:
-            img_emb = self._run_vision_encoder_batch([images[i] for i in raw_idx], mark)
-            mark("vision")
-            for j0, j1 in _runs(raw_idx):  # every run of consecutive raw images is prefilled straight into its own slots
-                pos = self._prefill_images(img_emb[j0:j1], rows.sub(raw_idx[j0], raw_idx[j1 - 1] + 1))
-            mark("image_prefill")
-        for i, im in enumerate(images):
-            if isinstance(im, EncodedImage):
-                if pos is not None and im.pos != pos:
-                    raise ValueError("EncodedImage with a different prefix length than the rest of the batch")
-                self.load_encoded_image(im, i)
-                pos = im.pos
-        out = self._prefill_groups(_length_groups(prompts), embed_prompts, pos, rows, sampling, logits_capture,
-                                   scores=scores, hidden_sink=hidden_sink)  # one per prompt length
         mark("prompt_prefill")
-        return (order, *out)
+        return Prepared(plan.order, *out, rows, sampling)
 
     def _mark(self, marks: list, name: str):
         """Phase timing (``collect_timing``): an event on the current stream, named after the phase that ends there."""
@@ -1505,59 +1547,6 @@ class MoondreamModel:
             if id(im) not in enc:
                 enc[id(im)] = self.encode_image(im, settings)
         return [enc[id(im)] for im in images]
-
-    def _prepare_sequences_shared(self, images, prompts: Sequence[Sequence[int]], mark=None, sampling: Optional[Sampling] = None,
-                                  scores: Optional[Scores] = None, hidden_sink=None):
-        """``_prepare_sequences`` with a SHARED image prefix (moondream_amd/shared_prefix.py): each distinct image (by identity)
-        is prefilled or loaded ONCE, into prefix slot k < P; the rows take slots P + r and read the prefix from there.  Raw
-        images go through one ViT batch and ``_prefill_images``; EncodedImages are loaded once.  In the fp8 KV mode both of these
-        also write the prefix slot's e4m3 rows (the prefill quantises, ``load_encoded_image`` calls md_kv_quantize_f8), once per
-        image; the prompt prefill quantises its rows into the rows' own slots.  One prompt prefill per
-        distinct length (md_text_forward_shared).  Returns (order, first, hidden_last, next_pos, rows, sampling): the first
-        four as ``_prepare_sequences`` returns them, in this path's row order; ``rows`` is the routing over the prefix table
-        (``_Rows``); ``sampling`` is the caller's with ``row_perm`` set: a row's row in the copy path's order (None stays None).
-        ``scores`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in this path's row order.  Must run under torch.inference_mode()."""
-        mark = mark or (lambda name: None)
-        plan = plan_shared_prefix(list(images), [len(p) for p in prompts])
-        if any(len(p) == 0 for p in prompts):
-            raise ValueError("empty prompt")
-        b, n_img = len(plan.order), len(plan.distinct)
-        self._select_kernels(b)
-        prompts = [list(prompts[i]) for i in plan.order]
-        for im in plan.distinct:
-            if not isinstance(im, (EncodedImage, Image.Image)):
-                raise ValueError("image must be a PIL Image or EncodedImage")
-        self._ensure_batch(plan.n_slots)
-        mark("start")
-        pos = None
-        raw = [k for k, im in enumerate(plan.distinct) if not isinstance(im, EncodedImage)]
-        if raw:
-            img_emb = self._run_vision_encoder_batch([plan.distinct[k] for k in raw], mark)
-            mark("vision")
-            for j0, j1 in _runs(raw):  # every run of consecutive prefix slots in one prefill
-                pos = self._prefill_images(img_emb[j0:j1], raw[j0])
-            mark("image_prefill")
-        for k, im in enumerate(plan.distinct):
-            if isinstance(im, EncodedImage):
-                if pos is not None and im.pos != pos:
-                    raise ValueError("EncodedImage with a different prefix length than the rest of the batch")
-                self.load_encoded_image(im, k)
-                pos = im.pos
-        check_shared_table(plan.own_slots, plan.prefix_slots, [pos] * b, [pos] * b, plan.n_slots)
-        buf = getattr(self, "_shared_buf", None)  # one persistent buffer: captured decode graphs keep its addresses
-        if buf is None or buf.numel() < 3 * b:
-            buf = torch.empty(3 * max(b, 64), dtype=torch.int32, device=self._device)
-            self._shared_buf = buf
-        buf[: 3 * b].copy_(self._h2d(torch.tensor(plan.own_slots + plan.prefix_slots + [pos] * b, dtype=torch.int32)))
-        rows = _Rows(slots=buf[0:b], n_slots=plan.n_slots, prefix_slots=buf[b : 2 * b], prefix_len=buf[2 * b : 3 * b])
-        if sampling is not None:
-            sampling = replace(sampling, row_perm=torch.tensor(plan.copy_rank, dtype=torch.int64, device=self._device))
-        # one prefill per distinct prompt length; a sampled group draws in the copy path's row order
-        first, hidden_last, next_pos = self._prefill_groups(
-            plan.groups, lambda r0, r1: self._embed(torch.tensor(prompts[r0:r1], dtype=torch.int32)), pos, rows, sampling,
-            scores=scores, hidden_sink=hidden_sink)
-        mark("prompt_prefill")
-        return plan.order, first, hidden_last, next_pos, rows, sampling
 
     def batch_generate_ids(
         self,
@@ -1653,39 +1642,28 @@ class MoondreamModel:
         lora = self._lora({"variant": variant})
         with torch.inference_mode():
             sampling = None if temperature == 0 else Sampling(float(temperature), float(top_p), generator)
-            rows = _Rows(lora=lora)
             rows_t = max(0, min(max_tokens, self.config.text.max_context)) + 1  # row 0: the prefill's decision, then the loop's
             scores = Scores.new((rows_t, b), top_k, self._device, fill=True) if return_logprobs else None
-            if multi_rows is None and share_prefix and self._shares_prefix(lora):
-                order, first, _, next_pos, rows, sampling = self._prepare_sequences_shared(list(images), prompts, mark, sampling,
-                                                                                           scores=scores and scores[0])
-            else:
-                if multi_rows is not None:
-                    # the slot order of _prepare_sequences (stable by prompt length), so that the table is in slot order too
-                    slot_order = sorted(range(b), key=lambda i: len(prompts[i]))
-                    rows = _Rows(variants=self._variant_table([multi_rows[i] for i in slot_order]), bank=self._bank)
-                elif share_prefix:  # the copy path over each distinct image's EncodedImage
-                    images = self._encode_distinct(images, {"variant": variant})
-                order, first, _, next_pos = self._prepare_sequences(list(images), prompts, mark, rows, fuse=True, sampling=sampling,
-                                                                    scores=scores and scores[0])
+            prep = self._prepare_sequences(images, prompts, mark, _Rows(lora=lora), fuse=True, share_prefix=share_prefix,
+                                           variants=multi_rows, encode_settings={"variant": variant}, sampling=sampling,
+                                           scores=scores and scores[0])
             stop = None if ignore_eos else eos
-            hist = self._decode_greedy(first, next_pos if len(set(next_pos)) > 1 else next_pos[0], max_tokens,
-                                       tk.answer_id, rows, stop, sampling=sampling, scores=scores)
+            hist = self._decode_greedy(prep.first, prep.pos, max_tokens, tk.answer_id, prep.rows, stop, sampling=prep.sampling,
+                                       scores=scores)
             mark("decode")
             host = scores and scores[: hist.shape[0]].to_host(hist)  # ids, logprobs, ranks, alternatives: ONE copy to the host
             cols = (host.extra[0].T if host else hist.t()).tolist()
             if b == 1:
                 self._check_b1_barriers()
-            results, logprobs, ranks, alternatives = ([None] * b for _ in range(4))  # per caller's row
-            for slot, src in enumerate(order):
-                results[src] = self._truncate(cols[slot], stop, max_tokens)
-                n = len(results[src])  # _truncate keeps a leading run of the ids: the same run of their values
-                if return_logprobs:
-                    logprobs[src], ranks[src] = host.logprob[:n, slot].tolist(), host.rank[:n, slot].tolist()
-                if top_k:
-                    alternatives[src] = host.alternatives((slice(n), slot))
+            out = [[self._truncate(c, stop, max_tokens) for c in cols]]  # ids [, logprobs, ranks [, alternatives]] per slot
+            n = [len(ids) for ids in out[0]]  # _truncate keeps a leading run of the ids: the same run of their values
+            if return_logprobs:
+                out += [[plane[: n[r], r].tolist() for r in range(b)] for plane in (host.logprob, host.rank)]
+            if top_k:
+                out.append([host.alternatives((slice(n[r]), r)) for r in range(b)])
         self._phase_times(marks)
-        return (results, logprobs, ranks, alternatives)[: 4 if top_k else 3] if return_logprobs else results
+        out = tuple(prep.in_caller_order(per_row) for per_row in out)
+        return out if return_logprobs else out[0]
 
     def batch_generate_ids_continuous(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                                       eos_id: Optional[int] = None, ignore_eos: bool = False, max_live: int = 64, chunk: int = 16,
@@ -1721,18 +1699,18 @@ class MoondreamModel:
         out = torch.empty(b, t_steps + 1, idx.shape[2], dtype=torch.float32)
         with torch.inference_mode():
             cap = torch.empty(b, t.vocab_size, dtype=BF16, device=self._device)
-            order, _, _, next_pos = self._prepare_sequences(list(images), prompts, fuse=True, logits_capture=cap)
-            src = torch.tensor(order, dtype=torch.int64)
+            prep = self._prepare_sequences(images, prompts, fuse=True, logits_capture=cap)
+            src = torch.tensor(prep.order, dtype=torch.int64)
             forced_s, idx_s = forced[src].to(self._device), idx[src].to(self._device)  # slot order
             vals = torch.empty(b, t_steps + 1, idx.shape[2], dtype=torch.float32, device=self._device)
             vals[:, 0] = torch.gather(cap.float(), 1, idx_s[:, 0])
             hist = torch.cat([forced_s.t().contiguous(), torch.zeros(1, b, dtype=torch.int32, device=self._device)], 0)
             scratch = torch.empty(b, dtype=torch.int32, device=self._device)
             logits = self._decode_logits(b)
-            rows = _Rows()
+            rows = prep.rows
             ws = self._workspace(self._decode_ws_bytes(rows, b), 2)
             kv = self._kv_struct(0)
-            pos_t = torch.tensor([int(p) for p in next_pos], dtype=torch.int32, device=self._device)
+            pos_t = torch.tensor([int(p) for p in prep.next_pos], dtype=torch.int32, device=self._device)
             for j in range(t_steps):
                 self._decode_step(rows, hist[j], scratch, pos_t, b, tk.answer_id, logits, ws, kv)
                 vals[:, j + 1] = torch.gather(logits[:b].float(), 1, idx_s[:, j + 1])
@@ -1791,21 +1769,17 @@ class MoondreamModel:
         with torch.inference_mode():
             passes: list = []  # (r0, r1, hidden [r1-r0, T, D]) per prefill pass, rows in slot order
             sink = lambda r0, r1, h: passes.append((r0, r1, h))
-            if share_prefix and self._shares_prefix(lora):
-                order = self._prepare_sequences_shared(list(images), seqs, hidden_sink=sink)[0]
-            else:
-                if share_prefix:  # the copy path over each distinct image's EncodedImage
-                    images = self._encode_distinct(images, {"variant": variant})
-                order = self._prepare_sequences(list(images), seqs, rows=_Rows(lora=lora), fuse=True, hidden_sink=sink)[0]
+            prep = self._prepare_sequences(images, seqs, rows=_Rows(lora=lora), fuse=True, share_prefix=share_prefix,
+                                           encode_settings={"variant": variant}, hidden_sink=sink)
             # row (j, k) of the compact table: decision k of slot j, the hidden row at offset len(prompt) - 1 + k of its
             # sequence -- the last len(continuation) rows of the pass
-            parts, targets, suppress, span = [], [], [], {}
+            parts, targets, suppress, spans = [], [], [], []  # spans: each slot's rows of the table, in slot order
             for r0, r1, h in passes:
                 t_len, idx = h.shape[1], []
                 for j in range(r0, r1):
-                    c = conts[order[j]]
+                    c = conts[prep.order[j]]
                     idx += [(j - r0) * t_len + t_len - len(c) + k for k in range(len(c))]
-                    span[order[j]] = (len(targets), len(targets) + len(c))
+                    spans.append(slice(len(targets), len(targets) + len(c)))
                     targets += c
                     suppress += [0] + [1] * (len(c) - 1)  # decision 0 is the prompt pass's: unsuppressed (moondream.py:313-318)
                 parts.append(h.reshape(-1, d).index_select(0, self._h2d(torch.tensor(idx, dtype=torch.int64))))
@@ -1818,7 +1792,7 @@ class MoondreamModel:
             scores = Scores.new((r,), top_k, self._device)
             self._score(logits, tab[0], tk.answer_id, scores, suppress_rows=tab[1])
             host = scores.to_host()  # one copy to the host
-        spans = [slice(*span[i]) for i in range(len(conts))]
+        spans = prep.in_caller_order(spans)
         out = [host.logprob[s].tolist() for s in spans], [host.rank[s].tolist() for s in spans]
         return out + ([host.alternatives(s) for s in spans],) if top_k else out
 
@@ -2579,20 +2553,13 @@ class MoondreamModel:
         mark = lambda name: self._mark(marks, name)
         with torch.inference_mode():
             sampling = None if temperature == 0 else Sampling(float(temperature), float(top_p), st.get("generator"))
-            if share_prefix:
-                order, first, hidden, next_pos, rows, sampling = self._prepare_sequences_shared(list(images), prompts, mark, sampling)
-            else:
-                rows = _Rows()
-                order, first, hidden, next_pos = self._prepare_sequences(list(images), prompts, mark, rows, fuse=True, sampling=sampling)
+            prep = self._prepare_sequences(images, prompts, mark, fuse=True, share_prefix=share_prefix, sampling=sampling)
             if forced is not None:
-                forced = forced.to(self._device)[:, torch.tensor(list(order), device=self._device)]
-            res = self._reason_loop(hidden, first, next_pos, rows, max_tokens, sampling, forced)
+                forced = forced.to(self._device)[:, torch.tensor(prep.order, device=self._device)]
+            res = self._reason_loop(prep.hidden_last, prep.first, prep.next_pos, prep.rows, max_tokens, prep.sampling, forced)
             mark("reason_loop")
         self._phase_times(marks)
-        out: List[Optional[dict]] = [None] * len(order)
-        for slot, src in enumerate(order):
-            out[src] = res[slot]
-        return out  # type: ignore[return-value]
+        return prep.in_caller_order(res)
 
     def _reasoning_answers(self, rows: List[dict]) -> List[dict]:
         """``_reason_loop``'s rows in the shape ``query(reasoning=True)`` returns."""
@@ -2618,21 +2585,13 @@ class MoondreamModel:
         marks: list = []
         mark = lambda name: self._mark(marks, name)
         with torch.inference_mode():
-            rows = _Rows(lora=lora)
-            if share_prefix and self._shares_prefix(lora):
-                order, first, hidden, next_pos, rows, _ = self._prepare_sequences_shared(list(images), prompts, mark)
-            else:
-                if share_prefix:
-                    images = self._encode_distinct(images, settings)
-                order, first, hidden, next_pos = self._prepare_sequences(list(images), prompts, mark, rows)
-            res = self._points_loop(hidden, first, next_pos, rows, include_size, max_objects,
+            prep = self._prepare_sequences(images, prompts, mark, _Rows(lora=lora), share_prefix=share_prefix,
+                                           encode_settings=settings)
+            res = self._points_loop(prep.hidden_last, prep.first, prep.next_pos, prep.rows, include_size, max_objects,
                                     run_all=bool((settings or {}).get("_run_all_objects", False)))
             mark("points_loop")
         self._phase_times(marks)
-        out = [None] * len(order)
-        for slot, src in enumerate(order):
-            out[src] = res[slot]
-        return out
+        return prep.in_caller_order(res)
 
     def batch_detect(self, images, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
         """B (image, object) pairs in lockstep; element i == detect(images[i], objects[i])."""

@@ -200,6 +200,26 @@ def test_uniform_variant_agrees_with_the_single_variant_path(tiny128):
             assert (got.float().gather(1, top) - want.float().gather(1, top)).abs().max() < 0.5, name
 
 
+def test_variant_table_follows_the_slot_order_of_the_prompt_lengths(tiny128):
+    """Prompt lengths [5, 3, 4]: the slots are not in the caller's order, and each row must still carry ITS variant.  Every
+    row's ids are bit-equal to its ids in the same mixed call with the caller's rows already in length order (where the
+    table needs no permutation)."""
+    cfg, model, variants = tiny128
+    imgs = [synth.synthetic_image(i, 5) for i in range(3)]
+    prompts = [[11, 12, 13, 14, 15], [21, 22, 23], [31, 32, 33, 34]]
+    names = ["r8", None, "r64"]
+    by_length = [1, 2, 0]
+    pick = lambda xs, idx: [xs[i] for i in idx]
+    got = model.batch_generate_ids(imgs, prompts, max_tokens=6, ignore_eos=True, variants=names)
+    want = model.batch_generate_ids(pick(imgs, by_length), pick(prompts, by_length), max_tokens=6, ignore_eos=True,
+                                    variants=pick(names, by_length))
+    assert pick(got, by_length) == want
+    # the check can see a table left in the caller's order: slot s holds caller by_length[s], so callers 1 and 2 would trade
+    # the base model for an adapter, which flips their ids by construction (synth.synthetic_lora)
+    misplaced = model.batch_generate_ids(imgs, prompts, max_tokens=6, ignore_eos=True, variants=["r64", "r8", None])
+    assert misplaced[1] != got[1] and misplaced[2] != got[2]
+
+
 # ------------------------------------------------------------------ goldens through batch_generate_ids
 def mixed_goldens(model, cfg, g, use_graphs):
     model.register_variant("synthetic", synth.synthetic_lora(cfg, seed=int(g["seed"]), rank=int(g["rank"]), device="cuda"))

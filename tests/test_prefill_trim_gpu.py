@@ -183,9 +183,9 @@ def test_batch_generate_ids_equals_the_untrimmed_model(tiny):
             cap = torch.empty(3, cfg.text.vocab_size, dtype=BF16, device="cuda")
             with torch.inference_mode():
                 model._select_kernels(3)
-                order, first, hidden_last, _ = model._prepare_sequences(list(images), prompts, fuse=True, logits_capture=cap)
+                prep = model._prepare_sequences(list(images), prompts, fuse=True, logits_capture=cap)
             torch.cuda.synchronize()
-            out[trim] = (ids, list(order), first.tolist(), bits(cap).cpu(), bits(hidden_last).cpu())
+            out[trim] = (ids, list(prep.order), prep.first.tolist(), bits(cap).cpu(), bits(prep.hidden_last).cpu())
     finally:
         model.prefill_trim = True
     assert out[True][:3] == out[False][:3]

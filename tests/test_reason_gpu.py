@@ -182,9 +182,9 @@ def test_suppression_rule_per_phase(tiny, which):
     try:
         with torch.inference_mode():
             bias[hot] = 1000.0
-            order, first, hidden, next_pos = model._prepare_sequences(imgs, [prompt] * 2, rows=_Rows())
-            assert first.tolist() == [hot, hot]  # the prompt pass's pick suppresses nothing
-            res = model._reason_loop(hidden, first, next_pos, _Rows(), mt, None, forced.cuda(), check_every=1, on_chunk=on_chunk)
+            prep = model._prepare_sequences(imgs, [prompt] * 2, rows=_Rows())
+            assert prep.first.tolist() == [hot, hot]  # the prompt pass's pick suppresses nothing
+            res = model._reason_loop(prep.hidden_last, prep.first, prep.next_pos, _Rows(), mt, None, forced.cuda(), check_every=1, on_chunk=on_chunk)
     finally:
         with torch.inference_mode():
             bias[hot] = old

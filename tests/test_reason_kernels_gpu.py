@@ -201,9 +201,9 @@ def tiny_prefilled():
     prompt = list(tpl["prefix"]) + [11, 12, 13] + list(tpl["suffix"]) + [tk.thinking_id]
     imgs = [synth.synthetic_image(i, 1) for i in range(4)]
     with torch.inference_mode():
-        order, first, hidden, next_pos = model._prepare_sequences(imgs, [prompt] * 4, rows=_Rows())
-    assert list(order) == [0, 1, 2, 3]
-    return cfg, model, hidden.clone(), next_pos
+        prep = model._prepare_sequences(imgs, [prompt] * 4, rows=_Rows())
+    assert list(prep.order) == [0, 1, 2, 3]
+    return cfg, model, prep.hidden_last.clone(), prep.next_pos
 
 
 def fused_step(model, cfg, hidden, tokens, pos, rows):

@@ -6,7 +6,7 @@ import pytest
 
 from moondream_amd import _lib
 from moondream_amd.config import get_config
-from moondream_amd.shared_prefix import check_shared_table, plan_shared_prefix
+from moondream_amd.shared_prefix import check_shared_table, plan_rows, plan_shared_prefix
 
 ERR_ARG = 1
 
@@ -124,3 +124,65 @@ def test_share_prefix_defaults_off():
     for name in ("query_many", "detect_many", "point_many"):
         assert list(inspect.signature(getattr(MoondreamModel, name)).parameters)[1:] == ["image", "questions" if name == "query_many" else "objects", "settings"]
     assert get_config("tiny").text.n_heads % get_config("tiny").text.n_kv_heads == 0
+
+
+# ------------------------------------------------------------------ one plan for both routings (plan_rows)
+def test_copy_plan_is_the_stable_sort_by_length_with_every_row_its_own_image():
+    a, b = Img(), Img()
+    images = [a, b, a, a, b, Img()]  # repeated objects: the copy path places each row's own
+    lens = [5, 3, 5, 3, 4, 3]
+    plan = plan_rows(images, lens, share=False)
+    assert plan.order == sorted(range(6), key=lambda i: lens[i]) == [1, 3, 5, 4, 0, 2]
+    assert len(plan.placed) == 6 and all(plan.placed[r] is images[plan.order[r]] for r in range(6))  # image r -> slot r
+    assert plan.own_slots == list(range(6)) and plan.n_slots == 6
+    assert plan.prefix_slots == []  # no prefix table
+    assert plan.groups == [(0, 3), (3, 4), (4, 6)]
+    assert plan.copy_rank == list(range(6))
+    with pytest.raises(ValueError):
+        plan_rows([], [], share=False)
+    with pytest.raises(ValueError):
+        plan_rows([a], [1, 2], share=False)
+
+
+def shared_cases():
+    a, b, c = Img(), Img(), Img()
+    return [([a, b, a, c, b, a, a, c], [5, 5, 3, 5, 3, 5, 3, 5]), ([a, b, b, a, c], [4, 4, 4, 4, 4]), ([a, b], [1, 1])]
+
+
+FIELDS = ("placed", "distinct", "order", "own_slots", "prefix_slots", "groups", "copy_rank", "n_slots")
+
+
+def test_shared_plan_is_plan_shared_prefix():
+    for images, lens in shared_cases():
+        got, want = plan_rows(images, lens, share=True), plan_shared_prefix(images, lens)
+        for f in FIELDS:
+            assert getattr(got, f) == getattr(want, f), f
+        p = len(want.distinct)
+        assert want.n_slots == p + len(images) and want.own_slots == [p + r for r in range(len(images))]
+
+
+def test_copy_rank_is_the_row_of_the_same_caller_in_the_copy_plan():
+    for images, lens in shared_cases():
+        shared, copy = plan_rows(images, lens, share=True), plan_rows(images, lens, share=False)
+        for r, src in enumerate(shared.order):
+            assert copy.order[shared.copy_rank[r]] == src
+
+
+def test_prepared_in_caller_order_inverts_the_plan_order():
+    from moondream_amd.moondream import Prepared
+
+    images, lens = shared_cases()[0]
+    variants = [3, -1, 0, 2, -1, 1, 0, 3]  # per row, in the caller's order
+    for share in (False, True):
+        plan = plan_rows(images, lens, share)
+        per_slot = [f"row of caller {src}" for src in plan.order]
+        prep = Prepared(order=plan.order, first=per_slot, hidden_last=per_slot, next_pos=[730 + lens[i] for i in plan.order],
+                        rows=None, sampling=None)
+        assert prep.in_caller_order(per_slot) == [f"row of caller {i}" for i in range(8)]
+        # the variant table goes through the same ``order`` into slot order, and back
+        table = [variants[i] for i in plan.order]
+        assert all(table[r] == variants[src] for r, src in enumerate(plan.order))
+        assert prep.in_caller_order(table) == variants
+        assert prep.pos == prep.next_pos  # two prompt lengths: one position per row
+    one = Prepared(order=[0, 1], first=None, hidden_last=None, next_pos=[735, 735], rows=None, sampling=None)
+    assert one.pos == 735

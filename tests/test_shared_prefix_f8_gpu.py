@@ -358,22 +358,23 @@ def rows(encs, n, seed):
 
 
 class SharedRoute:
-    """Counts the calls of ``_prepare_sequences_shared``: without it every test below passes on the copy-path fallback."""
+    """Counts the calls of ``_shared_routing`` (one per preparation on the shared route, none on the copy path): without it
+    every test below passes on the copy-path fallback."""
 
     def __init__(self, model):
         self.model, self.calls = model, 0
-        self.inner = model._prepare_sequences_shared
+        self.inner = model._shared_routing
 
     def __enter__(self):
         def counted(*a, **kw):
             self.calls += 1
             return self.inner(*a, **kw)
 
-        self.model._prepare_sequences_shared = counted
+        self.model._shared_routing = counted
         return self
 
     def __exit__(self, *exc):
-        del self.model._prepare_sequences_shared
+        del self.model._shared_routing
 
 
 @pytest.fixture()

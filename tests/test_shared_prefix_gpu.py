@@ -328,6 +328,22 @@ def test_generate_shared_raw_images_equal_copy_path(tiny):
         model.single_sequence_kernel = True
 
 
+def test_prepared_record_of_the_shared_route_matches_batch_generate_ids(tiny):
+    """``_prepare_sequences(share_prefix=True)`` over 2 EncodedImages x 2 prompt lengths: the record carries the shared routing,
+    and its first tokens, put in the caller's order, are the first ids of the public call."""
+    g, cfg, sd, model = tiny
+    encs = [model.encode_image(im) for im in images3(cfg)[:2]]
+    imgs = [encs[0], encs[1], encs[0], encs[1]]
+    prompts = [[11, 12, 13, 14, 15], [21, 22, 23], [31, 32, 33], [41, 42, 43, 44, 45]]
+    with torch.inference_mode():
+        prep = model._prepare_sequences(imgs, prompts, share_prefix=True)
+    assert prep.rows.kind == "_shared"
+    assert sorted(prep.order) == [0, 1, 2, 3] and list(prep.order) != [0, 1, 2, 3]
+    first = prep.in_caller_order(prep.first.tolist())
+    ids = model.batch_generate_ids(imgs, prompts, share_prefix=True, max_tokens=1, ignore_eos=True)
+    assert ids == [[t] for t in first]
+
+
 def test_query_detect_point_many_equal_batch_calls(tiny, golden_dir):
     g, cfg, sd, model = tiny
     dg = load_golden(golden_dir, "tiny_detect.npz")
