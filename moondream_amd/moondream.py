@@ -21,6 +21,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass, replace
+from functools import partial
 from typing import Any, Dict, Iterable, List, Literal, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -29,6 +30,7 @@ from PIL import Image
 
 from . import _lib
 from .config import MoondreamConfig
+from .crop_staging import CropStager, crop_workers, upload_unique
 from .decode_loop import DecodeChunk, ReasonChunk, Sampling, check_top_logprobs, run_chunk
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
@@ -234,6 +236,27 @@ def _is_cjk_char(cp: int) -> bool:
     return (0x4E00 <= cp <= 0x9FFF) or (0x3400 <= cp <= 0x4DBF) or (0x2F800 <= cp <= 0x2FA1F)
 
 
+def _count_crops(v, image: Image.Image) -> int:
+    return crop_count(image.size[1], image.size[0], v.overlap_margin, v.max_crops, (v.crop_size, v.crop_size), v.enc_patch_size)[0]
+
+
+def _crop_into(v, image: Image.Image, out: np.ndarray):
+    """Cut the crops of ``image`` (vision config ``v``) into ``out`` [n, crop, crop, 3] uint8 -> (crops, tiling)."""
+    arr = np.asarray(image if image.mode == "RGB" else image.convert("RGB"))  # (convert() of an RGB image is a plain copy)
+    oc = overlap_crop_image(arr, max_crops=v.max_crops, overlap_margin=v.overlap_margin, base_size=(v.crop_size, v.crop_size),
+                            patch_size=v.enc_patch_size, out=out)
+    return oc["crops"], tuple(oc["tiling"])
+
+
+def _crop_pool_workers() -> int:
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    ranks_here = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1")) or 1))
+    return crop_workers(n, os.cpu_count() or n, ranks_here)
+
+
 def _tree_to_cpu(tree):
     """A nested dict of tensors (a LoRA variant) with every tensor copied to the host."""
     if isinstance(tree, dict):
@@ -295,6 +318,8 @@ class MoondreamModel:
         self.fused_prefill = True
         # encode byte-identical crops of an image once (images that fit one crop: global == local); off = what the reference does
         self.dedup_identical_crops = False
+        v = config.vision  # host tiling into pinned buffers: the ring, the pools and the batches staged ahead (crop_staging.py)
+        self._staging = CropStager(partial(_count_crops, v), partial(_crop_into, v), (v.crop_size, v.crop_size, 3), _crop_pool_workers)
         if setup_caches:
             self._setup_caches(max_batch)
 
@@ -818,73 +843,36 @@ class MoondreamModel:
     def _run_vision_encoder_batch(self, images: Sequence[Image.Image], mark=None, staged=None) -> torch.Tensor:
         """images -> [B,729,D] projected embeddings (reference: moondream.py:206-228, per image).
 
-        Host tiling (PIL, reference image_crops.py:58-167) runs on a thread pool and is
-        pipelined against the GPU: the ViT of image chunk k is enqueued (async) while
-        the crops of chunk k+1 are still being cut.  The workers cut their crops STRAIGHT
-        INTO the pinned staging buffer the H2D copy reads (the tiling, hence every image's
-        crop count and offset, follows from its size alone): no concatenation pass over the
-        crop bytes on the host."""
-        v = self.config.vision
-        n_img = len(images)
+        Host tiling (PIL, reference image_crops.py:58-167) runs on a thread pool and is pipelined against the GPU
+        (crop_staging.py): the ViT of image chunk k is enqueued (async) while the crops of chunk k+1 are still being cut.
+        ``staged``: these images' StagedBatch when the caller started it ahead; otherwise a prefetched one, or one made now."""
         if staged is None:
-            # (a prefetched entry is taken only when it is going to be USED: popped and dropped it would leak its pinned buffers)
-            pre = getattr(self, "_prefetched_crops", {}).pop(tuple(id(im) for im in images), None)
-            staged = pre[1] if pre is not None else self._stage_crops(images)
-            try:
-                return self._run_vision_encoder_batch(images, mark, staged)
-            except BaseException:
-                self._drain_staged(staged)  # this call owns the staging it made / took over: nothing stays marked busy
-                raise
-        chunks, staged = staged
+            staged = self._staging.take(images, self.vit_chunk_crops)
         cropped: List[Tuple[np.ndarray, Tuple[int, int]]] = []
         feat_parts = []
-        # OWNERSHIP of the pinned staging buffers: ``staged`` is consumed IN PLACE -- a chunk leaves the list at the moment its
-        # buffer is handed back (uploaded or released), so whoever holds the list (the pipelined engine's drain, on an early
-        # exit or an exception in here) releases exactly the chunks that are still in it and no token twice
-        for ci in range(len(staged)):
-            host, token, futs = staged[0]
-            part = [f.result() for f in futs]
-            if mark is not None and ci == 0:
-                mark("host_tiling")  # phase timing: the GPU has nothing of this batch to run before the first crops exist
-            cropped.extend(part)
-            if self.dedup_identical_crops:
-                # An image that is no larger than one crop has tiling (1, 1) and its single local crop holds the same
-                # pixels as the global crop (image_crops.py:124-167: both are the image resized to crop_size).  The
-                # encoder maps equal inputs to equal outputs whatever else is in the launch, so such a crop is encoded
-                # once and its features are used for both positions.  Opt-in: the reference encodes both.
-                uniq, expand = [], []
-                for c, tiling in part:
-                    if tiling == (1, 1) and c.shape[0] == 2 and np.array_equal(c[0], c[1]):
-                        expand += [len(uniq), len(uniq)]
-                        uniq.append(c[:1])
+        with staged:  # whatever raises in here, the chunks not consumed yet give their buffers back
+            for ci in range(len(staged.chunks)):
+                part, lease = staged.next_chunk()
+                with lease:  # the chunk's buffer is this block's: taken over by its upload, or given back here
+                    if mark is not None and ci == 0:
+                        mark("host_tiling")  # phase timing: the GPU has nothing of this batch to run before the first crops exist
+                    cropped.extend(part)
+                    if self.dedup_identical_crops:  # opt-in: the reference encodes both crops of an image that fits one
+                        dev_crops, expand = upload_unique(self._staging.ring, part, self._staging.crop_shape, self._device)
                     else:
-                        expand += list(range(len(uniq), len(uniq) + c.shape[0]))
-                        uniq.extend(c[k : k + 1] for k in range(c.shape[0]))
-                # ownership (advisor, round 5): from here this block owns the chunk's buffer (``token``: popped from ``staged``,
-                # so the drain no longer releases it) and the second buffer (``token2``) until the upload has taken it over;
-                # whatever raises in between, both go back exactly once
-                staged.pop(0)
-                try:
-                    host2, token2 = self._pinned_crops(len(uniq), (v.crop_size, v.crop_size, 3))
-                    try:
-                        np.concatenate(uniq, axis=0, out=host2)
-                        dev_crops = self._upload_pinned(host2, token2)
-                    except BaseException:
-                        self._release_pinned(token2)
-                        raise
-                finally:
-                    self._release_pinned(token)
+                        dev_crops, expand = lease.upload(self._device), None
                 f = self._vit_run(dev_crops, _lib.MD_CROPS_U8_HWC)
-                if len(expand) != dev_crops.shape[0]:
+                if expand is not None and len(expand) != dev_crops.shape[0]:
                     f = f[torch.tensor(expand, dtype=torch.int64, device=self._device)]
                 feat_parts.append(f)
-                continue
-            dev_crops = self._upload_pinned(host, token)
-            staged.pop(0)
-            feat_parts.append(self._vit_run(dev_crops, _lib.MD_CROPS_U8_HWC))
         feats = feat_parts[0] if len(feat_parts) == 1 else torch.cat(feat_parts, dim=0)  # [sum crops, 729, Dv]
-        out = torch.empty(n_img, v.n_patches, v.proj_out_dim, dtype=BF16, device=self._device)
-        # images with the same tiling are projected together
+        return self._project_by_tiling(feats, cropped)
+
+    def _project_by_tiling(self, feats: torch.Tensor, cropped) -> torch.Tensor:
+        """Encoder features of all crops [sum crops, 729, Dv] + each image's (crops, tiling) -> [B,729,D]: images with the
+        same tiling are projected together."""
+        v = self.config.vision
+        out = torch.empty(len(cropped), v.n_patches, v.proj_out_dim, dtype=BF16, device=self._device)
         offsets, off = [], 0
         for c, _ in cropped:
             offsets.append(off)
@@ -913,153 +901,26 @@ class MoondreamModel:
                 out[torch.tensor(idxs, device=self._device)] = o
         return out
 
-    def _stage_crops(self, images: Sequence[Image.Image], pool=None):
-        """Queue the host tiling of a batch on the thread pool, chunk by chunk, each image cutting its crops into its
-        slice of a pinned staging buffer.  Returns (chunks, staged) for ``_run_vision_encoder_batch``."""
-        v = self.config.vision
-        n_img = len(images)
-        pool = pool or self._crop_pool()
-        per_chunk = max(1, self.vit_chunk_crops // 2)  # images per ViT launch group (2 crops each at 378 x 378; more for large images)
-        counts = [crop_count(im.size[1], im.size[0], v.overlap_margin, v.max_crops, (v.crop_size, v.crop_size), v.enc_patch_size)
-                  for im in images]
-        # chunks: consecutive images whose crops total <= vit_chunk_crops (at least one image)
-        chunks, i0 = [], 0
-        while i0 < n_img:
-            i1, tot = i0, 0
-            while i1 < n_img and (i1 == i0 or (tot + counts[i1][0] <= max(self.vit_chunk_crops, 1) and i1 - i0 < per_chunk * 8)):
-                tot += counts[i1][0]
-                i1 += 1
-            chunks.append((i0, i1, tot))
-            i0 = i1
-        staged = []
-        for (c0, c1, tot) in chunks:  # all host work is queued up front; the GPU side follows chunk by chunk
-            host, token = self._pinned_crops(tot, (v.crop_size, v.crop_size, 3))
-            futs, off = [], 0
-            for i in range(c0, c1):
-                n = counts[i][0]
-                futs.append(pool.submit(self._crop_into, images[i], host[off : off + n]))
-                off += n
-            staged.append((host, token, futs))
-        return chunks, staged
+    prefetch_workers = 4
 
     def prefetch_crops(self, images: Sequence[Image.Image]) -> None:
         """Start the host tiling of a batch NOW (thread pool, pinned staging buffers) so that a later call that encodes
         exactly these image objects -- ``batch_detect``, ``batch_generate_ids``, ... -- finds its crops cut: a serving
         loop calls this for batch k+1 before it runs batch k, which hides the PIL resize of large images behind the
         GPU (the pipelined caption engine does the same by construction).  Results are identical."""
-        if not hasattr(self, "_prefetched_crops"):
-            self._prefetched_crops = {}
-        images = list(images)  # (kept alive with the entry: the key is made of object identities)
-        key = tuple(id(im) for im in images)
-        if key in self._prefetched_crops:
-            return
-        while len(self._prefetched_crops) >= 2:  # the batch about to run + one ahead
-            self.discard_prefetched_crops(next(iter(self._prefetched_crops)))
-        # a FEW background workers: the step that is running needs the host for its own launches, and the tiling of one
-        # batch (tens of ms of CPU per large image) has a whole step's GPU time to finish
-        pool = getattr(self, "_prefetch_pool", None)
-        if pool is None:
-            from concurrent.futures import ThreadPoolExecutor
-
-            pool = self._prefetch_pool = ThreadPoolExecutor(max_workers=max(1, int(self.prefetch_workers)))
-        self._prefetched_crops[key] = (images, self._stage_crops(images, pool))
+        self._staging.prefetch(images, self.vit_chunk_crops, self.prefetch_workers)
 
     def wait_prefetched_crops(self) -> None:
         """Block until every prefetched batch's crops are cut (tests, benchmarks: a steady-state serving loop never waits)."""
-        for _, (_, staged) in getattr(self, "_prefetched_crops", {}).values():
-            for _, _, futs in staged:
-                for f in futs:
-                    f.result()
+        self._staging.wait_prefetched()
 
     def discard_prefetched_crops(self, key=None) -> None:
         """Drop prefetched batches that were never encoded (waits for their workers, returns the pinned buffers)."""
-        d = getattr(self, "_prefetched_crops", {})
-        for k in ([key] if key is not None else list(d)):
-            _, staged = d.pop(k)
-            self._drain_staged(staged)
+        self._staging.discard(key)
 
-    def _drain_staged(self, staged) -> None:
-        """Return the pinned buffers of staged chunks that were never uploaded (``_run_vision_encoder_batch`` removes a chunk
-        from the list when it hands its buffer back, so what is left here is exactly what is still owned)."""
-        lst = staged[1]
-        while lst:
-            host, token, futs = lst.pop(0)
-            for f in futs:
-                try:
-                    f.result()  # the worker must be done with the buffer before it is handed out again
-                except Exception:
-                    pass  # (a failed crop was / will be reported by the consumer; here only the buffer matters)
-            self._release_pinned(token)
-
-    def _crop_into(self, image: Image.Image, out: np.ndarray):
-        v = self.config.vision
-        arr = np.asarray(image if image.mode == "RGB" else image.convert("RGB"))  # (convert() of an RGB image is a plain copy)
-        oc = overlap_crop_image(arr, max_crops=v.max_crops, overlap_margin=v.overlap_margin, base_size=(v.crop_size, v.crop_size),
-                                patch_size=v.enc_patch_size, out=out)
-        return oc["crops"], tuple(oc["tiling"])
-
-    # PINNED staging for the uint8 crops (a pageable source makes the runtime bounce the copy through its own small pinned
-    # buffers, synchronously: ~2x the time, and the host cannot queue the ViT launches behind it).  A small set of buffers
-    # rotates; a buffer is handed out again only after the copy that read it has completed (its event).
-    def _pinned_crops(self, n_crops: int, crop_shape):
-        shape = (int(n_crops),) + tuple(crop_shape)
-        nbytes = int(np.prod(shape))
-        ring = getattr(self, "_pinned", None)
-        if ring is None:
-            ring = self._pinned = {"bufs": [], "events": [], "busy": []}
-        pick = None
-        for i, (buf, busy) in enumerate(zip(ring["bufs"], ring["busy"])):
-            if not busy and buf.numel() >= nbytes:
-                pick = i
-                break
-        if pick is None:
-            with torch.inference_mode(False):
-                ring["bufs"].append(torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True))
-            ring["events"].append(None)
-            ring["busy"].append(False)
-            pick = len(ring["bufs"]) - 1
-        if ring["events"][pick] is not None:
-            ring["events"][pick].synchronize()
-            ring["events"][pick] = None
-        ring["busy"][pick] = True
-        host = ring["bufs"][pick][:nbytes].numpy().reshape(shape)
-        return host, pick
-
-    def _upload_pinned(self, host: np.ndarray, token: int) -> torch.Tensor:
-        ring = self._pinned
-        nbytes = int(host.size)
-        dev = ring["bufs"][token][:nbytes].view(host.shape).to(self._device, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self._device))
-        ring["events"][token] = ev
-        ring["busy"][token] = False  # reusable once the event has passed (checked when it is handed out again)
-        return dev
-
-    def _release_pinned(self, token: int):
-        self._pinned["busy"][token] = False
-
-    prefetch_workers = 4
-
-    def _crop_pool(self):
-        pool = getattr(self, "_pool", None)
-        if pool is None:
-            import os
-            from concurrent.futures import ThreadPoolExecutor
-
-            try:
-                n = len(os.sched_getaffinity(0))
-            except AttributeError:
-                n = os.cpu_count() or 1
-            # one process per GPU: the ranks of a node share its cores (8 ranks x 32 workers + prefetch workers would
-            # oversubscribe a 256-thread host)
-            ranks_here = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1")) or 1))
-            total = os.cpu_count() or n
-            if ranks_here > 1 and n * ranks_here <= total + ranks_here:
-                share = n          # the affinity mask already IS this rank's share (dist.bind_rank_cpus): do not divide twice
-            else:
-                share = n // ranks_here
-            pool = self._pool = ThreadPoolExecutor(max_workers=max(1, min(32, share - 2 if ranks_here > 1 else n)))
-        return pool
+    @property
+    def _prefetched_crops(self):
+        return self._staging.prefetched
 
     def _run_vision_encoder(self, image: Image.Image) -> torch.Tensor:
         self._select_kernels(1)
@@ -1823,17 +1684,7 @@ class MoondreamModel:
             (either makes the host wait for the device).
 
         Per batch the result is identical to ``batch_generate_ids`` (same kernels, same order)."""
-        pending = []
-        it = iter(batches)
-        cur = next(it, None)
-        staged = self._stage_crops(list(cur[0])) if cur is not None else None
-        try:
-            yield from self._pipelined_loop(it, cur, staged, pending, max_tokens, ignore_eos)
-        finally:
-            st = getattr(self, "_pipe_staged", None)  # a consumer that stops early: the tiling started ahead is drained, its buffers returned
-            self._pipe_staged = None
-            if st is not None:
-                self._drain_staged(st)
+        yield from self._pipelined_loop(batches, max_tokens, ignore_eos)
 
     # Round 6: the decode of TWO consecutive batches runs as one lockstep decode (<= 128 sequences) when the library takes that
     # many rows in one pass over the weights (md_decode_step: 65 .. 128 rows on the 128 x 64 weight-streaming tile, same bits as
@@ -1841,80 +1692,88 @@ class MoondreamModel:
     # (launches of 64 images: what BASELINE's batch=64 names), results are still yielded per batch and in order, one PAIR late.
     pair_decode = os.environ.get("MD_PIPE_PAIR", "1") not in ("0", "")
 
-    def _pipelined_loop(self, it, cur, staged, pending, max_tokens, ignore_eos):
+    def _pipelined_loop(self, batches, max_tokens, ignore_eos):
+        it = iter(batches)
+        cur = next(it, None)
+        pending = []
         tk = self.config.tokenizer
         eos = tk.eos_id
         run_s, dec_s = self._streams()
         if self.pipeline_streams not in (2, 3):
             dec_s = run_s
         group = 0
-        self._pipe_staged = staged
-        while cur is not None:
-            b = len(cur[0])
-            pair = self.pair_decode and 2 * b <= 128 and not bool(self.w.text.fp8) and self._kv8_scales is None
-            cap = 2 * b if pair else b            # slots of one group: two groups alternate (encode into one, decode from the other)
-            self._ensure_batch(2 * cap)
-            self._select_kernels(b)
-            base = group * cap
-            group ^= 1
-            firsts, p1s, sizes = [], [], []
-            with torch.inference_mode():
-                run_s.wait_stream(torch.cuda.current_stream(self._device))
-                while True:
-                    images, prompts = cur
-                    images = list(images)
-                    nb = len(images)
-                    assert nb == len(prompts) and nb > 0 and len({len(p) for p in prompts}) == 1
-                    slot0 = base + sum(sizes)
-                    nxt = next(it, None)
+        # the tiling started ahead is this generator's: drained when it ends, however it ends (a consumer that stops early)
+        staged = self._staging.stage(list(cur[0]), self.vit_chunk_crops) if cur is not None else None
+        try:
+            while cur is not None:
+                b = len(cur[0])
+                pair = self.pair_decode and 2 * b <= 128 and not bool(self.w.text.fp8) and self._kv8_scales is None
+                cap = 2 * b if pair else b            # slots of one group: two groups alternate (encode into one, decode from the other)
+                self._ensure_batch(2 * cap)
+                self._select_kernels(b)
+                base = group * cap
+                group ^= 1
+                firsts, p1s, sizes = [], [], []
+                with torch.inference_mode():
+                    run_s.wait_stream(torch.cuda.current_stream(self._device))
+                    while True:
+                        images, prompts = cur
+                        images = list(images)
+                        nb = len(images)
+                        assert nb == len(prompts) and nb > 0 and len({len(p) for p in prompts}) == 1
+                        slot0 = base + sum(sizes)
+                        nxt = next(it, None)
+                        with torch.cuda.stream(run_s):
+                            img_emb = self._run_vision_encoder_batch(images, staged=staged)
+                            # this batch's crops are cut and queued for upload: the pool is free for the next batch's tiling
+                            staged = self._staging.stage(list(nxt[0]), self.vit_chunk_crops) if nxt is not None else None
+                            if self.fused_prefill:  # [bos | image | prompt] in one decoder pass, as in _prepare_sequences
+                                # assembled in a PREALLOCATED arena (one per batch shape; stream-ordered reuse on run_s: the previous
+                                # pass has read it before these copies run) instead of a fresh torch.cat per step; the BOS column is
+                                # written once
+                                n_img, n_pr = img_emb.shape[1], len(prompts[0])
+                                x = self._prefill_arena(nb, 1 + n_img + n_pr, tk.bos_id)
+                                x[:, 1 : 1 + n_img].copy_(img_emb)
+                                x[:, 1 + n_img :].copy_(self._embed(torch.tensor(prompts, dtype=torch.int32)))
+                                logits = self._lm_head(self._text_forward(x, 0, slot0, keep="last"))
+                                p1 = x.shape[1]
+                            else:
+                                pos = self._prefill_images(img_emb, slot0)
+                                logits, _, p1 = self._prefill_prompts(prompts, pos, slot0, last_only=True)
+                            firsts.append(self._first_token(logits))
+                        p1s.append(p1)
+                        sizes.append(nb)
+                        cur = nxt
+                        if not pair or len(sizes) == 2 or cur is None or len(cur[0]) != b:
+                            break
                     with torch.cuda.stream(run_s):
-                        img_emb = self._run_vision_encoder_batch(images, staged=staged)
-                        # this batch's crops are cut and queued for upload: the pool is free for the next batch's tiling
-                        staged = self._pipe_staged = self._stage_crops(list(nxt[0])) if nxt is not None else None
-                        if self.fused_prefill:  # [bos | image | prompt] in one decoder pass, as in _prepare_sequences
-                            # assembled in a PREALLOCATED arena (one per batch shape; stream-ordered reuse on run_s: the previous
-                            # pass has read it before these copies run) instead of a fresh torch.cat per step; the BOS column is
-                            # written once
-                            n_img, n_pr = img_emb.shape[1], len(prompts[0])
-                            x = self._prefill_arena(nb, 1 + n_img + n_pr, tk.bos_id)
-                            x[:, 1 : 1 + n_img].copy_(img_emb)
-                            x[:, 1 + n_img :].copy_(self._embed(torch.tensor(prompts, dtype=torch.int32)))
-                            logits = self._lm_head(self._text_forward(x, 0, slot0, keep="last"))
-                            p1 = x.shape[1]
+                        first = firsts[0] if len(firsts) == 1 else torch.cat(firsts)
+                        if dec_s is not run_s:
+                            ev = torch.cuda.Event()
+                            ev.record(run_s)
+                    with torch.cuda.stream(dec_s):
+                        if dec_s is not run_s:
+                            dec_s.wait_event(ev)
+                            first.record_stream(dec_s)
+                        pos1 = p1s[0] if len(set(p1s)) == 1 else [p for p, n in zip(p1s, sizes) for _ in range(n)]
+                        hist = self._decode_greedy(first, pos1, max_tokens, tk.answer_id, base, None, check_every=16, allow_b1=False)
+                        # ids -> PINNED host memory behind the last decode step (a ``.tolist()`` at collection time is a
+                        # synchronous copy on the default stream: it waits for everything queued on the device)
+                        if self.pipeline_streams == 3:  # measurement only: rounds 1-3's collection (synchronous copy on the default stream)
+                            hist_host = hist
                         else:
-                            pos = self._prefill_images(img_emb, slot0)
-                            logits, _, p1 = self._prefill_prompts(prompts, pos, slot0, last_only=True)
-                        firsts.append(self._first_token(logits))
-                    p1s.append(p1)
-                    sizes.append(nb)
-                    cur = nxt
-                    if not pair or len(sizes) == 2 or cur is None or len(cur[0]) != b:
-                        break
-                with torch.cuda.stream(run_s):
-                    first = firsts[0] if len(firsts) == 1 else torch.cat(firsts)
-                    if dec_s is not run_s:
-                        ev = torch.cuda.Event()
-                        ev.record(run_s)
-                with torch.cuda.stream(dec_s):
-                    if dec_s is not run_s:
-                        dec_s.wait_event(ev)
-                        first.record_stream(dec_s)
-                    pos1 = p1s[0] if len(set(p1s)) == 1 else [p for p, n in zip(p1s, sizes) for _ in range(n)]
-                    hist = self._decode_greedy(first, pos1, max_tokens, tk.answer_id, base, None, check_every=16, allow_b1=False)
-                    # ids -> PINNED host memory behind the last decode step (a ``.tolist()`` at collection time is a
-                    # synchronous copy on the default stream: it waits for everything queued on the device)
-                    if self.pipeline_streams == 3:  # measurement only: rounds 1-3's collection (synchronous copy on the default stream)
-                        hist_host = hist
-                    else:
-                        hist_host = self._pinned_ids(tuple(hist.shape))   # recycled by _collect: no cudaHostAlloc per step
-                        hist_host.copy_(hist, non_blocking=True)
-                    done = torch.cuda.Event()
-                    done.record(dec_s)
-            pending.append((hist_host, done, sizes))
-            if len(pending) > 1:
+                            hist_host = self._pinned_ids(tuple(hist.shape))   # recycled by _collect: no cudaHostAlloc per step
+                            hist_host.copy_(hist, non_blocking=True)
+                        done = torch.cuda.Event()
+                        done.record(dec_s)
+                pending.append((hist_host, done, sizes))
+                if len(pending) > 1:
+                    yield from self._collect(pending.pop(0), None if ignore_eos else eos, max_tokens)
+            while pending:
                 yield from self._collect(pending.pop(0), None if ignore_eos else eos, max_tokens)
-        while pending:
-            yield from self._collect(pending.pop(0), None if ignore_eos else eos, max_tokens)
+        finally:
+            if staged is not None:
+                staged.drain()
 
     def _prefill_arena(self, b: int, t: int, bos_id: int) -> torch.Tensor:
         """bf16 [b, t, D] buffer of the pipelined engine's fused prefill input, column 0 = the BOS embedding."""

@@ -914,6 +914,63 @@ def test_prefetched_crops_are_used_and_identical(tiny):
     assert model.batch_generate_ids(images, prompts, max_tokens=6) == base
 
 
+def _two_chunks_two_tilings(g):
+    """Three 378 x 378 images and one 500 x 700 one: at ``vit_chunk_crops = 4`` at least two chunks, and two tilings."""
+    return [golden_image(g, i) for i in range(3)] + [synth.synthetic_image(5, 1).resize((700, 500))]
+
+
+def test_pipelined_generator_closed_early_returns_every_buffer(tiny):
+    """A consumer that stops after the first result: the tiling the engine had started ahead is drained, so no pinned
+    staging buffer stays marked busy and nothing is left in the prefetch table; the model goes on as before."""
+    g, cfg, sd, model = tiny
+    images = _two_chunks_two_tilings(g)
+    prompts = [cfg.tokenizer.templates["caption"]["normal"]] * 4
+    ring = model._staging.ring
+    chunk = model.vit_chunk_crops
+    model.vit_chunk_crops = 4
+    try:
+        base = model.batch_generate_ids(images, prompts, max_tokens=6)
+        gen = model.batch_generate_ids_pipelined([(list(images), prompts) for _ in range(6)], max_tokens=6)
+        first = next(gen)                          # batches 0-3 are queued (two decode pairs), batch 4 is being tiled, 5 waits
+        assert len(first) == 4
+        assert any(s.busy for s in ring.slots)     # ... in buffers that only the generator knows of
+        gen.close()
+        assert not any(s.busy for s in ring.slots) and not model._staging.prefetched
+        torch.cuda.synchronize()                   # (the decode of batches 2-3 is still queued on the engine's own streams)
+        assert model.batch_generate_ids(images, prompts, max_tokens=6) == base
+    finally:
+        model.vit_chunk_crops = chunk
+    torch.cuda.synchronize()
+
+
+def test_crop_worker_exception_returns_every_buffer(tiny, monkeypatch):
+    """A host exception in one image's crop worker (chunk 2 of 3): the call raises it, the buffers of the chunks that were
+    never uploaded come back, and the same call on good images gives the ids it gave before."""
+    g, cfg, sd, model = tiny
+    images = _two_chunks_two_tilings(g)
+    prompts = [cfg.tokenizer.templates["caption"]["normal"]] * 4
+    bad = images[2].copy()
+    crop_into = model._staging.crop_into
+
+    def failing(image, out):
+        if image is bad:
+            raise RuntimeError("crop failed")
+        return crop_into(image, out)
+
+    chunk = model.vit_chunk_crops
+    model.vit_chunk_crops = 4
+    try:
+        base = model.batch_generate_ids(images, prompts, max_tokens=6)
+        monkeypatch.setattr(model._staging, "crop_into", failing)
+        with pytest.raises(RuntimeError, match="crop failed"):
+            model.batch_generate_ids(images[:2] + [bad] + images[3:], prompts, max_tokens=6)
+        assert not any(s.busy for s in model._staging.ring.slots)
+        assert model.batch_generate_ids(images, prompts, max_tokens=6) == base
+    finally:
+        model.vit_chunk_crops = chunk
+    torch.cuda.synchronize()
+
+
 def test_mixed_encoded_and_raw_images_in_one_batch(tiny):
     """an EncodedImage next to raw PIL images must keep its own KV slot."""
     g, cfg, sd, model = tiny
