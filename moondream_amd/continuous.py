@@ -572,10 +572,7 @@ class ContinuousEngine:
         sampling row make.  The row-variant table sits next to the slot table; only chunks with a LoRA row read it."""
         import torch
 
-        bufs = self.model.__dict__.setdefault("_continuous_bufs", {})  # on the model: engines of one model share captured chunks
-        key = (self.chunk, bucket)
-        b = bufs.get(key)
-        if b is None:
+        def make():
             c = self.chunk
             n_in = c * bucket + bucket + bucket
             dev = torch.zeros(n_in + c * bucket + bucket, dtype=torch.int32, device=self.model.device)
@@ -583,15 +580,14 @@ class ContinuousEngine:
                 host = torch.zeros(n_in + bucket, dtype=torch.int32, pin_memory=True)
                 u_host = torch.zeros(c * bucket + 2 * bucket, dtype=torch.float32, pin_memory=True)
             u_dev = torch.zeros(c * bucket + 2 * bucket, dtype=torch.float32, device=self.model.device)
-            b = bufs[key] = (dev, host, u_dev, u_host, n_in)
-        return b
+            return dev, host, u_dev, u_host, n_in
+
+        return self.model._store.fixed("continuous", (self.chunk, bucket), make)  # the model's: its engines share captured chunks
 
     def _score_buffers(self, bucket: int):
         """The fixed-address ``Scores`` over (chunk, bucket) with the engine's k that a chunk's steps fill (``logprobs`` only)."""
-        bufs = self.model.__dict__.setdefault("_continuous_score_bufs", {})
-        key = (self.chunk, bucket, self.top_logprobs)
-        bufs[key] = bufs.get(key) or Scores.new((self.chunk, bucket), self.top_logprobs, self.model.device)
-        return bufs[key]
+        return self.model._store.fixed("continuous_scores", (self.chunk, bucket, self.top_logprobs),
+                                       lambda: Scores.new((self.chunk, bucket), self.top_logprobs, self.model.device))
 
     def _step(self, plan: ChunkPlan) -> np.ndarray:
         import torch
@@ -638,11 +634,7 @@ class ContinuousEngine:
         chunk = DecodeChunk(B, hist, pos_d, rows_of, m.config.tokenizer.answer_id, self._decode_ws_bytes(B), pick,
                             u_dev[: c * B].view(c, B), **(scores.chunk_fields() if scores else {}))
         stream = torch.cuda.current_stream(m.device).cuda_stream if m.use_graphs else None
-
-        def below_cap():
-            return sum(1 for k in m._graphs if isinstance(k, tuple) and k and k[0] == "continuous" and k[1] == stream) < MAX_GRAPHS
-
-        if run_chunk(m, chunk, n, "continuous", stream, below_cap):
+        if run_chunk(m, chunk, n, "continuous", stream, lambda: m._store.count("continuous", stream) < MAX_GRAPHS):
             self.stats.graph_captures += 1
         out = hist[1 : n + 1].cpu().numpy()  # the chunk's D2H copy of the ids (the lockstep loop syncs here too)
         if scores is None:

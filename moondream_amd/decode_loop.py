@@ -114,9 +114,9 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
               may_capture: Optional[Callable[[], bool]] = None) -> bool:
     """Run steps 0 .. n-1 of ``chunk`` on ``model``.  ``capture_stream`` None: eagerly.  Otherwise the handle of the current
     stream: the chunk is replayed from the graph captured for it on that stream, or, first, run eagerly and captured
-    (``model._replay_or_capture``; ``may_capture`` as it takes it).  The key starts (``tag``, stream) and names everything the
-    launches bake in.  Returns True when it captured.  Of the model it uses _decode_logits, _workspace, _kv_struct,
-    _decode_step, _decode_step_b1, _decode_step_reason, _pick, _pick_rows, _token_logprobs, _topk_logprobs and _replay_or_capture."""
+    (``model._replay_or_capture``: its ``GraphStore``'s, ``may_capture`` too).  The key starts (``tag``, stream) and names everything
+    the launches bake in.  Returns True when it captured.  Besides that, the model gives the buffers (_decode_logits, _workspace,
+    _kv_struct) and the launches (_decode_step, _decode_step_b1, _decode_step_reason, _pick, _pick_rows, _token_logprobs, _topk_logprobs)."""
     c = chunk
     pieces = c.step is not None
     assert c.reason is None or (not pieces and not c.b1 and c.logprobs is None and c.pick is not None and c.pick.per_row)

@@ -32,6 +32,7 @@ from . import _lib
 from .config import MoondreamConfig
 from .crop_staging import CropStager, crop_workers, upload_unique
 from .decode_loop import DecodeChunk, ReasonChunk, Sampling, check_top_logprobs, run_chunk
+from .graph_store import GraphStore
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
 from .lora import variant_state_dict
@@ -257,6 +258,13 @@ def _crop_pool_workers() -> int:
     return crop_workers(n, os.cpu_count() or n, ranks_here)
 
 
+def _capture_graph(body) -> torch.cuda.CUDAGraph:
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        body()
+    return g
+
+
 def _tree_to_cpu(tree):
     """A nested dict of tensors (a LoRA variant) with every tensor copied to the host."""
     if isinstance(tree, dict):
@@ -289,12 +297,12 @@ class MoondreamModel:
         # dequantisation is VALU-bound today (0.82x the bf16 stream's decode phase at B = 64, profiles/r04_int4_weight_stream.txt)
         self.int4_decode = False
         self.vit_chunk_crops = int(vit_chunk_crops)
-        self._arenas: Dict[int, torch.Tensor] = {}
         self._max_batch = 0
         self._kv_k = self._kv_v = None
         self._kv_k8 = self._kv_v8 = None   # fp8 mode: e4m3 copy of the cache for the decode steps
         self._kv8_scales = None            # (ctypes float[L] for K, for V) when that copy is in use
-        self._graphs: Dict[Any, Any] = {}
+        # the captured decode graphs and every buffer they bake in but the KV slabs (graph_store.py)
+        self._store = GraphStore(partial(torch.cuda.synchronize, self._device), _capture_graph)
         self.use_graphs = False
         self.collect_timing = False
         self.last_phase_ms: Dict[str, float] = {}
@@ -327,6 +335,10 @@ class MoondreamModel:
     @property
     def device(self) -> torch.device:
         return self._device
+
+    @property
+    def _graphs(self):
+        return self._store.graphs
 
     def _stream(self) -> C.c_void_p:
         return C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
@@ -368,7 +380,7 @@ class MoondreamModel:
                     self._kv_k8[:, :keep] = old_k8[:, :keep]
                     self._kv_v8[:, :keep] = old_v8[:, :keep]
         self._max_batch = b
-        self._graphs.clear()
+        self._store.invalidate()
 
     def _ensure_batch(self, b: int):
         if self._kv_k is None or b > self._max_batch:
@@ -392,12 +404,8 @@ class MoondreamModel:
         """Caller-owned arenas for the C ABI.  0: encode-side stages, 1: lm_head of the
         prompt prefill, 2: the decode loop (its own arena so that a decode running on
         the decode stream never shares scratch with an encode on the encode stream)."""
-        ws = self._arenas.get(which)
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.empty(int(nbytes * 1.05) + 4096, dtype=torch.uint8, device=self._device)
-            self._arenas[which] = ws
-            self._graphs.clear()
-        return ws
+        return self._store.grow(("arena", which), nbytes,
+                                lambda: torch.empty(int(nbytes * 1.05) + 4096, dtype=torch.uint8, device=self._device))
 
     @classmethod
     def from_pretrained(cls, weights_file: str, config: Optional[MoondreamConfig] = None, **kwargs):
@@ -434,10 +442,7 @@ class MoondreamModel:
         """The per-sequence variant table of a mixed batch on the device, in one persistent buffer (captured decode graphs
         keep its address)."""
         b = len(rows)
-        buf = getattr(self, "_variant_buf", None)
-        if buf is None or buf.numel() < b:
-            buf = torch.empty(max(b, 64), dtype=torch.int32, device=self._device)
-            self._variant_buf = buf
+        buf = self._store.grow("variants", b, lambda: torch.empty(max(b, 64), dtype=torch.int32, device=self._device))
         buf[:b].copy_(self._h2d(torch.tensor(list(rows), dtype=torch.int32)))
         return buf[:b]
 
@@ -465,7 +470,7 @@ class MoondreamModel:
             self.w.disable_fp8_decode()
             if self.int4_decode and self.w.has_int4_source():
                 self.w.enable_int4_decode()
-        self._graphs.clear()  # captured decode steps baked the other launches in
+        self._store.invalidate()  # captured decode steps baked the other launches in
 
     def enable_int4_decode(self, on: bool = True):
         """A checkpoint that stores the decoder blocks as the reference's QuantizedLinear triples (layers.py:47-109) carries
@@ -481,7 +486,7 @@ class MoondreamModel:
             if not self.w.has_int4_source():
                 raise ValueError("this checkpoint has no QuantizedLinear (int4) decoder blocks")
             self.w.enable_int4_decode()
-        self._graphs.clear()
+        self._store.invalidate()
 
     def enable_fp8(self, calibration_images: Optional[Sequence[Image.Image]] = None, prompt: Optional[Sequence[int]] = None,
                    on: bool = True, decode_weights: bool = True, margin: float = 1.5, kv_cache: bool = True) -> Optional[dict]:
@@ -499,7 +504,7 @@ class MoondreamModel:
         path once with range recording on (vision + image / prompt prefill), then the e4m3 weight copies are built.
         The reference has no fp8 path: outputs are judged by tolerance against the bf16 mode (tests/test_model_gpu.py),
         never by bit parity, and the mode is off by default.  Returns the recorded ranges."""
-        self._graphs.clear()
+        self._store.invalidate()
         if not on:
             self.w.disable_f8()
             if decode_weights:
@@ -558,7 +563,7 @@ class MoondreamModel:
         self.fused_prefill = not on
         self.strict_batch_invariance = bool(on)
         self._select_kernels(1)
-        self._graphs.clear()
+        self._store.invalidate()
 
     def _select_kernels(self, n_sequences: int):
         """The library's tile choice by row count would give a lone image (730 / 1458 rows) the small-shape tile configs and a
@@ -1104,7 +1109,7 @@ class MoondreamModel:
                 with torch.inference_mode():
                     self._b1_sync[64 * 11] = 0
                 self.single_sequence_kernel = False
-                self._graphs.clear()
+                self._store.invalidate()
                 warnings.warn("md_decode_step_b1: a grid barrier timed out (GPU shared with another persistent kernel?); "
                               "repeating the decode on the batched kernels and disabling the single-sequence kernel", RuntimeWarning)
                 hist = self._decode_greedy_impl(first, pos, max_tokens, suppress_id, rows, eos_id, **{**kw, "allow_b1": False})
@@ -1189,14 +1194,11 @@ class MoondreamModel:
             if graphs:
                 # the fixed buffers of this shape on this stream (the pipelined engine's decode stream and the default stream
                 # each have their own), refreshed before each replay; its graphs share them: a stream runs one chunk at a time
-                fixed = self.__dict__.setdefault("_chunk_bufs", {})
-                if (stream, b, n) not in fixed:
-                    zeros = lambda rows, dtype: torch.zeros(rows, b, dtype=dtype, device=self._device)
-                    fixed[stream, b, n] = (zeros(n + 1, torch.int32), zeros(1, torch.int32)[0], zeros(n, torch.float32))
-                buf, pos_buf, u_buf = fixed[stream, b, n]
+                zeros = lambda rows, dtype: torch.zeros(rows, b, dtype=dtype, device=self._device)
+                buf, pos_buf, u_buf = self._store.fixed("chunk", (stream, b, n), lambda: (
+                    zeros(n + 1, torch.int32), zeros(1, torch.int32)[0], zeros(n, torch.float32)))
                 if scores is not None:  # ... in the fixed planes of this shape and k, which only a call that asks makes
-                    key = (stream, b, n, "scores", scores.k)
-                    into = fixed[key] = fixed.get(key) or Scores.new((n, b), scores.k, self._device)
+                    into = self._store.fixed("chunk", (stream, b, n, "scores", scores.k), lambda: Scores.new((n, b), scores.k, self._device))
                 buf[0] = hist[steps]
                 pos_buf.copy_(pos_base + steps)
                 if uniforms is not None:
@@ -1215,24 +1217,7 @@ class MoondreamModel:
         return hist[: steps + 1]
 
     def _replay_or_capture(self, key, body, may_capture=None) -> bool:
-        """Replay the graph stored under ``key``; a key not seen before runs ``body`` eagerly, then captures it and stores
-        the graph (the fixed buffers the body addresses are kept alive by their owners).  An eager warm-up on scratch state is not
-        possible (KV side effects), so the first chunk of a new shape IS the eager run and the graph is captured after a
-        device synchronise; the capture does not execute, there is nothing to undo.  ``may_capture`` (asked on a miss
-        only): False runs eagerly without storing.  Returns True when it captured."""
-        graph = self._graphs.get(key)
-        if graph is not None:
-            graph.replay()
-            return False
-        body()
-        if may_capture is not None and not may_capture():
-            return False
-        torch.cuda.synchronize(self._device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            body()
-        self._graphs[key] = g
-        return True
+        return self._store.replay_or_capture(key, body, may_capture)
 
     def _check_b1_barriers(self):
         """Call after the tokens of a single-sequence decode have reached the host: the persistent kernel's grid barriers
@@ -1246,12 +1231,8 @@ class MoondreamModel:
                 "set single_sequence_kernel = False to decode on the batched kernels")
 
     def _decode_logits(self, b: int) -> torch.Tensor:
-        buf = getattr(self, "_logits_buf", None)
-        if buf is None or buf.shape[0] < b:
-            buf = torch.empty(max(b, self._max_batch), self.config.text.vocab_size, dtype=BF16, device=self._device)
-            self._logits_buf = buf
-            self._graphs.clear()
-        return buf
+        return self._store.grow("logits", b, lambda: torch.empty(max(b, self._max_batch), self.config.text.vocab_size, dtype=BF16,
+                                                                  device=self._device))
 
     @staticmethod
     def _truncate(seq: List[int], eos_id: Optional[int], max_tokens: int) -> List[int]:
@@ -1318,10 +1299,8 @@ class MoondreamModel:
         """The routing of a shared plan's rows over its prefix table (every prefix ``pos`` positions long), checked."""
         b = len(plan.order)
         check_shared_table(plan.own_slots, plan.prefix_slots, [pos] * b, [pos] * b, plan.n_slots)
-        buf = getattr(self, "_shared_buf", None)  # one persistent buffer: captured decode graphs keep its addresses
-        if buf is None or buf.numel() < 3 * b:
-            buf = torch.empty(3 * max(b, 64), dtype=torch.int32, device=self._device)
-            self._shared_buf = buf
+        # one persistent buffer: captured decode graphs keep its addresses
+        buf = self._store.grow("shared", 3 * b, lambda: torch.empty(3 * max(b, 64), dtype=torch.int32, device=self._device))
         buf[: 3 * b].copy_(self._h2d(torch.tensor(plan.own_slots + plan.prefix_slots + [pos] * b, dtype=torch.int32)))
         return _Rows(slots=buf[0:b], n_slots=plan.n_slots, prefix_slots=buf[b : 2 * b], prefix_len=buf[2 * b : 3 * b])
 
@@ -2261,16 +2240,14 @@ class MoondreamModel:
     def _reason_buffers(self, stream, b: int, n: int):
         """The fixed buffers of the reasoning loop: the rows' state per (stream, b) -- it lives across the chunks of a call
         -- and the per-step planes per (stream, b, n).  Captured chunks keep these addresses."""
-        fixed = self.__dict__.setdefault("_reason_bufs", {})
         i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=self._device)
         f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=self._device)
-        if (stream, b) not in fixed:
-            fixed[stream, b] = dict(phase=i32(b), n_reason=i32(b), n_answer=i32(b), suppress=i32(b, 2), coord_bin=i32(b), pos=i32(b),
-                                    hidden_prev=torch.zeros(b, self.config.text.dim, dtype=BF16, device=self._device),
-                                    temperature=f32(b), top_p=f32(b))
-        if (stream, b, n) not in fixed:
-            fixed[stream, b, n] = dict(tokens=i32(n + 1, b), kind=i32(n, b), ground=i32(n, b), forced=i32(n, b), uniforms=f32(n, b))
-        return fixed[stream, b], fixed[stream, b, n]
+        state = self._store.fixed("reason", (stream, b), lambda: dict(
+            phase=i32(b), n_reason=i32(b), n_answer=i32(b), suppress=i32(b, 2), coord_bin=i32(b), pos=i32(b),
+            hidden_prev=torch.zeros(b, self.config.text.dim, dtype=BF16, device=self._device), temperature=f32(b), top_p=f32(b)))
+        planes = self._store.fixed("reason", (stream, b, n), lambda: dict(
+            tokens=i32(n + 1, b), kind=i32(n, b), ground=i32(n, b), forced=i32(n, b), uniforms=f32(n, b)))
+        return state, planes
 
     def _reason_loop(self, hidden: torch.Tensor, first: torch.Tensor, pos: Sequence[int], rows: Union[int, _Rows], max_tokens: int,
                      sampling: Optional[Sampling] = None, forced: Optional[torch.Tensor] = None, check_every: int = 16,

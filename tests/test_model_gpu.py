@@ -1065,7 +1065,7 @@ def test_single_sequence_kernel_tracks_batched_kernels(tiny):
             first = torch.tensor([int(g["img0.cap.tokens"][0])], dtype=torch.int32, device="cuda")
             _, _, pos = model._prefill_prompts([g["img0.cap.prompt"].tolist()], enc.pos, 0)
             model._decode_greedy(first, pos, 1, cfg.tokenizer.answer_id, 0, None)
-            outs.append(model._logits_buf[0].float().cpu().clone())
+            outs.append(model._decode_logits(1)[0].float().cpu().clone())
         err = float((outs[0] - outs[1]).abs().max())
         assert err <= 0.25, err
     finally:

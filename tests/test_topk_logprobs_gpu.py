@@ -341,23 +341,23 @@ def test_fixed_score_buffers_survive_between_calls(tiny):
     prompts = [[1, 708, 9, 3], [1, 17, 708, 2, 382, 9, 3], [1, 708, 9, 3]]  # two lengths: two prefill groups
     kw = dict(max_tokens=5, ignore_eos=True)
     flat = lambda got: (got[0], [words(x) for x in got[1]], got[2], pairs_bits(got[3]))
-    m._graphs.clear()
-    m.__dict__.pop("_chunk_bufs", None)  # (no graph is left to address them)
+    m._store.forget_fixed("chunk")  # (with the graphs: none is left to address them)
+    bufs = m._store.fixed_view("chunk")
     m.compile()
     try:
         first = m.batch_generate_ids(tiny.images, prompts, return_logprobs=True, top_logprobs=3, **kw)
-        graphs, keys = len(m._graphs), set(m._chunk_bufs)
+        graphs, keys = len(m._graphs), set(bufs)
         assert sorted(k[1:] for k in keys) == [(3, 5), (3, 5, "scores", 3)]
         again = m.batch_generate_ids(tiny.images, prompts, return_logprobs=True, top_logprobs=3, **kw)
-        assert len(m._graphs) == graphs and set(m._chunk_bufs) == keys, "the second call must replay, not capture"
+        assert len(m._graphs) == graphs and set(bufs) == keys, "the second call must replay, not capture"
         assert flat(again) == flat(first)
         assert all(len(s) == 5 for s in first[0]) and not any(math.isnan(x) for s in first[1] for x in s)
-        assert m.batch_generate_ids(tiny.images, prompts, **kw) == first[0] and set(m._chunk_bufs) == keys
+        assert m.batch_generate_ids(tiny.images, prompts, **kw) == first[0] and set(bufs) == keys
         # a shape no scored call has had: its entry is tokens, position and uniforms, and nothing for scores
         short = m.batch_generate_ids(tiny.images, prompts, max_tokens=4, ignore_eos=True)
         assert short == [s[:4] for s in first[0]]
-        new = set(m._chunk_bufs) - keys
-        assert [k[1:] for k in new] == [(3, 4)] and len(m._chunk_bufs[new.pop()]) == 3
+        new = set(bufs) - keys
+        assert [k[1:] for k in new] == [(3, 4)] and len(bufs[new.pop()]) == 3
     finally:
         m.use_graphs = False
         m._graphs.clear()
