@@ -476,6 +476,31 @@ md_status md_topk_logprobs(const void* logits, int64_t ld, int32_t rows, int32_t
                            const int32_t* suppress_rows, const int32_t* gate, int32_t k, int32_t* top_ids,
                            float* top_logprobs, void* stream);
 
+/* Repetition, presence and frequency penalties on the logits a token is about to be picked from, from each row's OWN history
+ * of generated tokens, which the call also extends.  logits bf16 [batch][ld], updated in place; one workgroup per row, a row's
+ * result independent of the rows beside it.  hist int32 [n_slots][hist_cap] and hist_len int32 [n_slots] are the caller's
+ * device arrays; row r's history is that of slot s = slots ? slots[r] : slot0 + r (two live rows of one launch never share one).
+ *   s < 0 (idle row): nothing is read or written -- not the logits row, not a history, not a length.
+ *   Append: t = tokens_in[r], the token the row produced last.  If 0 <= t < vocab and hist_len[s] < hist_cap, hist[s][hist_len[s]] = t
+ *     and hist_len[s] grows by one.  A full history drops t; a t that is no id is not appended; the row is penalised either way.
+ *   Neutral row (repetition[r] == 1, presence[r] == 0, frequency[r] == 0): the append happens, the logits row is neither read
+ *     nor written.
+ *   Penalise: for every DISTINCT token v of the history (the one just appended included), c its count, x = float(logit[v]):
+ *       if repetition[r] != 1:  x = x > 0 ? x / repetition[r] : x * repetition[r]      (the HF / vLLM rule; zero stays zero)
+ *       x = x - (presence[r] + frequency[r] * float(c))
+ *     in fp32, every operation rounded on its own (no fused multiply-add), then logit[v] = bf16(x), round to nearest even.
+ *     Each distinct token is updated exactly once however often it occurs; a -inf logit stays -inf.
+ * Cost: the history's tokens are read once and one logit per distinct token is loaded and stored -- the row is never scanned
+ * (an LDS hash table finds each distinct token with its count: csrc/sampling_region.hip).  Plain loads: no vocab % 8 / ld % 8
+ * requirement.  The values in the three arrays are the caller's contract (finite, repetition > 0).  No host sync, no
+ * allocation: capturable.  batch == 0: MD_OK, nothing launched.
+ * MD_ERR_INVALID_ARG: NULL logits / tokens_in / hist / hist_len / repetition / presence / frequency, batch < 0, vocab < 1,
+ * ld < vocab, hist_cap < 1, hist_cap > MD_PENALTY_HIST_MAX (the table of 2 * hist_cap entries lives in 64 KiB of LDS). */
+#define MD_PENALTY_HIST_MAX 4096
+md_status md_penalize_rows(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* tokens_in,
+                           const int32_t* slots, int32_t slot0, int32_t* hist, int32_t hist_cap, int32_t* hist_len,
+                           const float* repetition, const float* presence, const float* frequency, void* stream);
+
 /* Region head, device resident (reference: region.py:12-71 inside the loop of moondream.py:653-733).
  * md_fourier_features: out[r] = [cos(f) | sin(f)], f = bf16(bf16(2 pi x[r, :in_dim]) . w[in_dim][half])
  *   (region.py:12-29; in_dim 1 for coordinates, 2 for sizes) -- the input of coord_encoder /

@@ -25,13 +25,14 @@ from typing import Callable, Deque, Dict, Iterator, List, Optional, Sequence, Tu
 
 import numpy as np
 
-from .decode_loop import DecodeChunk, Sampling, check_top_logprobs, run_chunk
+from .decode_loop import PENALTY_NEUTRAL, DecodeChunk, Penalty, Sampling, check_penalties, check_top_logprobs, run_chunk
 from .scores import HostScores, Scores
 
 DEFAULT_MAX_TOKENS = 768  # moondream.py (the reference's default, moondream.py:50-53)
 DEFAULT_TOP_P = 0.3
 MAX_GRAPHS = 16  # captured decode chunks per (model, stream)
 IDLE_SLOT = -1
+MD_PENALTY_HIST_MAX = 4096  # include/moondream_hip.h
 
 
 def row_buckets(max_live: int) -> List[int]:
@@ -74,6 +75,7 @@ class Request:
     logprobs: List[float] = field(default_factory=list)  # of ``ids``, entry for entry (an engine with logprobs=True)
     ranks: List[int] = field(default_factory=list)
     alternatives: List[list] = field(default_factory=list)  # of ``ids`` too: k (token_id, logprob) pairs each (top_logprobs=k)
+    penalties: Tuple[float, float, float] = PENALTY_NEUTRAL  # (repetition, presence, frequency): md_penalize_rows' rule
 
     @property
     def remaining(self) -> int:
@@ -83,7 +85,10 @@ class Request:
 @dataclass
 class ChunkPlan:
     """``n`` decode steps over ``bucket`` rows: ``rows[r]`` is the request of row r (rows past len(rows) are padding);
-    ``slots[i][r]`` the slot row r addresses in step i (IDLE_SLOT: padding, or a request past its step limit)."""
+    ``slots[i][r]`` the slot row r addresses in step i (IDLE_SLOT: padding, or a request past its step limit).
+    ``fresh[r]``: the slot of a row whose request takes its first decode step in this chunk (IDLE_SLOT otherwise) -- the
+    slot has just been refilled, and whatever is kept per slot beyond the KV rows (the penalty history's length) starts
+    from nothing here."""
 
     rows: List[Request]
     bucket: int
@@ -91,6 +96,7 @@ class ChunkPlan:
     slots: np.ndarray   # int32 [n, bucket]
     tokens: np.ndarray  # int32 [bucket]: the token each row consumes in step 0
     pos: np.ndarray     # int32 [bucket]: its position
+    fresh: Optional[np.ndarray] = None  # int32 [bucket]
 
     @property
     def live_row_steps(self) -> int:
@@ -195,11 +201,14 @@ class SlotScheduler:
         slots = np.full((n, bucket), IDLE_SLOT, dtype=np.int32)
         tokens = np.zeros(bucket, dtype=np.int32)
         pos = np.zeros(bucket, dtype=np.int32)
+        fresh = np.full(bucket, IDLE_SLOT, dtype=np.int32)
         for i, r in enumerate(rows):
             slots[: min(n, r.remaining), i] = r.slot  # past its step limit a row is idle: no cache row beyond its context
             tokens[i] = r.last
             pos[i] = r.pos
-        return ChunkPlan(rows, bucket, n, slots, tokens, pos)
+            if r.steps == 0:
+                fresh[i] = r.slot
+        return ChunkPlan(rows, bucket, n, slots, tokens, pos, fresh)
 
     def commit(self, plan: ChunkPlan, out: np.ndarray, logprobs: Optional[np.ndarray] = None,
                ranks: Optional[np.ndarray] = None, top_ids: Optional[np.ndarray] = None,
@@ -281,7 +290,16 @@ class ContinuousEngine:
     and ``alternatives`` (k (token_id, logprob) pairs per id) beside its ids: ``run(with_logprobs=True)``.  They are, bit for
     bit, the values of ``MoondreamModel.batch_generate_ids(..., return_logprobs=True, top_logprobs=k)``: the model's own
     distribution at temperature 1, untruncated, whatever the request's sampling settings.  Off: the launches and graphs
-    of an engine without the flags."""
+    of an engine without the flags.
+
+    ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` per request (``submit``; None: neutral):
+    ``batch_generate_ids``' rule over the request's generated tokens.  The histories are per KV SLOT -- a request changes
+    row from chunk to chunk and keeps its slot -- in one [max_live, max_context] table the engine owns for its lifetime; a
+    refilled slot's length is zeroed in the request's first chunk (``ChunkPlan.fresh``, uploaded with the rows' settings:
+    one more pinned H2D copy that only chunks with a penalised row make, no synchronisation).  Such chunks run
+    md_penalize_rows before each pick and are graphs of their own; chunks whose rows are all neutral take the graph of
+    an engine without penalties.  A request's ids depend on its own settings and seed only; with ``logprobs`` its scores
+    are those of the penalised logits."""
 
     def __init__(self, model, max_live: int = 64, chunk: int = 16, temperature: float = 0.0, top_p: float = DEFAULT_TOP_P,
                  admit_threshold: Optional[int] = None, logprobs: bool = False, top_logprobs: Optional[int] = None):
@@ -296,6 +314,7 @@ class ContinuousEngine:
         t = model.config.text
         self.sched = SlotScheduler(self.max_live, t.max_context, self.chunk, admit_threshold)
         self._next_rid = 0
+        self._penalty_hist = None  # (hist int32 [max_live + 1, max_context], hist_len int32 [max_live + 1]), made on first use
 
     @property
     def stats(self) -> EngineStats:
@@ -304,9 +323,11 @@ class ContinuousEngine:
     # ---- submission
     def submit(self, image, prompt_ids: Sequence[int], max_tokens: int = DEFAULT_MAX_TOKENS, eos_id: Optional[int] = None,
                seed: Optional[int] = None, ignore_eos: bool = False, variant: Optional[str] = None,
-               temperature: Optional[float] = None, top_p: Optional[float] = None) -> int:
+               temperature: Optional[float] = None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
+               presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None) -> int:
         """Queue one request; ``image`` is a PIL image or an EncodedImage.  ``eos_id`` None: the tokenizer's EOS
-        (``ignore_eos``: none).  ``temperature`` / ``top_p`` None: the engine's.  Returns its id."""
+        (``ignore_eos``: none).  ``temperature`` / ``top_p`` None: the engine's.  The three penalties (None: neutral):
+        one number each, ``batch_generate_ids``' rule and validation.  Returns its id."""
         from PIL import Image
 
         from .moondream import EncodedImage
@@ -317,6 +338,11 @@ class ContinuousEngine:
             raise ValueError(f"temperature must be finite and >= 0 (0: greedy), not {temp}")
         if not (math.isfinite(tp) and 0 < tp <= 1):
             raise ValueError(f"top_p must be in (0, 1], not {tp}")
+        for name, x in (("repetition_penalty", repetition_penalty), ("presence_penalty", presence_penalty),
+                        ("frequency_penalty", frequency_penalty)):
+            if isinstance(x, (list, tuple)):
+                raise ValueError(f"{name}: one number per request, not {x!r}")
+        pen = check_penalties(repetition_penalty, presence_penalty, frequency_penalty, 1)
         if not isinstance(image, (Image.Image, EncodedImage)):
             raise ValueError("image must be a PIL Image or EncodedImage")
         prompt = [int(p) for p in prompt_ids]
@@ -330,7 +356,8 @@ class ContinuousEngine:
         vidx = -1 if variant is None else self._variant_index(variant)
         rid = self._next_rid
         self._next_rid += 1
-        self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed, variant=vidx, temperature=temp, top_p=tp))
+        self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed, variant=vidx, temperature=temp, top_p=tp,
+                                  penalties=pen[0] if pen else PENALTY_NEUTRAL))
         return rid
 
     def _variant_index(self, variant: str) -> int:
@@ -417,9 +444,12 @@ class ContinuousEngine:
     def generate(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                  eos_id: Optional[int] = None, ignore_eos: bool = False, seeds: Optional[Sequence[Optional[int]]] = None,
                  variant: Optional[str] = None, temperature: Union[None, float, Sequence[float]] = None,
-                 top_p: Union[None, float, Sequence[float]] = None, return_logprobs: bool = False):
+                 top_p: Union[None, float, Sequence[float]] = None, return_logprobs: bool = False,
+                 repetition_penalty: Union[None, float, Sequence[float]] = None,
+                 presence_penalty: Union[None, float, Sequence[float]] = None,
+                 frequency_penalty: Union[None, float, Sequence[float]] = None):
         """Ids for (images[i], prompts[i]) in input order; ``max_tokens`` one int or one per request, ``temperature`` and
-        ``top_p`` one float or one per request (None: the engine's).  ``return_logprobs`` (an engine made with
+        ``top_p`` one float or one per request (None: the engine's), the three penalties likewise (None: neutral).  ``return_logprobs`` (an engine made with
         ``logprobs=True``): (ids, logprobs, ranks), each in input order; an engine with ``top_logprobs``: alternatives too."""
         if return_logprobs and not self.logprobs:
             raise ValueError("generate(return_logprobs=True) needs ContinuousEngine(..., logprobs=True)")
@@ -440,7 +470,9 @@ class ContinuousEngine:
             return x
 
         temps, tps = per_request(temperature, "temperature"), per_request(top_p, "top_p")
-        rids = [self.submit(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant, temps[i], tps[i]) for i in range(n)]
+        pens = check_penalties(repetition_penalty, presence_penalty, frequency_penalty, n) or [PENALTY_NEUTRAL] * n
+        rids = [self.submit(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant, temps[i], tps[i], *pens[i])
+                for i in range(n)]
         if return_logprobs:  # (ids, logprobs, ranks), and alternatives on an engine with top_logprobs
             got3 = {rid: rest for rid, *rest in self.run(with_logprobs=True)}
             return tuple([got3[r][k] for r in rids] for k in range(4 if self.top_logprobs else 3))
@@ -584,6 +616,27 @@ class ContinuousEngine:
 
         return self.model._store.fixed("continuous", (self.chunk, bucket), make)  # the model's: its engines share captured chunks
 
+    def _penalty_buffers(self, bucket: int):
+        """What a chunk with a penalised row needs beside ``_buffers``: the engine's histories (one per KV slot, and a spare
+        one past them where the length resets of rows that need none land) and, per bucket, the fixed-address settings fp32
+        [repetition | presence | frequency] (bucket each) and reset indices int64 [bucket], each with its pinned staging."""
+        import torch
+
+        m = self.model
+        if self._penalty_hist is None:
+            cap = min(m.config.text.max_context, MD_PENALTY_HIST_MAX)  # (a request generates fewer tokens than either)
+            self._penalty_hist = (torch.zeros(self.max_live + 1, cap, dtype=torch.int32, device=m.device),
+                                  torch.zeros(self.max_live + 1, dtype=torch.int32, device=m.device))
+
+        def make():
+            with torch.inference_mode(False):
+                st_host = torch.zeros(3 * bucket, dtype=torch.float32, pin_memory=True)
+                rs_host = torch.zeros(bucket, dtype=torch.int64, pin_memory=True)
+            return (torch.zeros(3 * bucket, dtype=torch.float32, device=m.device), st_host,
+                    torch.zeros(bucket, dtype=torch.int64, device=m.device), rs_host)
+
+        return self._penalty_hist + m._store.fixed("continuous_penalty", bucket, make)
+
     def _score_buffers(self, bucket: int):
         """The fixed-address ``Scores`` over (chunk, bucket) with the engine's k that a chunk's steps fill (``logprobs`` only)."""
         return self.model._store.fixed("continuous_scores", (self.chunk, bucket, self.top_logprobs),
@@ -625,6 +678,19 @@ class ContinuousEngine:
                     k = min(n, r.remaining)
                     uh[:k, r_idx] = self._uniforms(r, k).numpy()
             u_dev.copy_(u_host, non_blocking=True)
+        penalty = None
+        if any(r.penalties != PENALTY_NEUTRAL for r in plan.rows):
+            # the rows' settings (padding rows neutral) and the slots whose history starts here, in two small copies behind
+            # the chunk's others; the lengths are zeroed on the stream, before the chunk's first launch
+            p_hist, p_len, st_dev, st_host, rs_dev, rs_host = self._penalty_buffers(B)
+            sh = st_host.numpy().reshape(3, B)
+            sh[:] = np.asarray(PENALTY_NEUTRAL, dtype=np.float32)[:, None]
+            sh[:, : len(plan.rows)] = np.asarray([r.penalties for r in plan.rows], dtype=np.float32).T
+            rs_host.numpy()[:] = np.where(plan.fresh >= 0, plan.fresh, self.max_live)
+            st_dev.copy_(st_host, non_blocking=True)
+            rs_dev.copy_(rs_host, non_blocking=True)
+            p_len.index_fill_(0, rs_dev, 0)
+            penalty = Penalty(st_dev[:B], st_dev[B : 2 * B], st_dev[2 * B :], p_hist, p_len, p_hist.shape[1], by_slot=True)
         scores = self._score_buffers(B) if self.logprobs else None  # (an idle or padding row's are never read: SlotScheduler.commit)
         # step i's routing: row i of the slot table; a LoRA row in the chunk: the chunk's row-variant table with it
         rows_of = lambda i: self._rows(slots_d[i], var_d if lora else None)
@@ -632,7 +698,7 @@ class ContinuousEngine:
         # nothing); the settings are device data, in the allocation of the uniforms
         pick = Sampling(u_dev[c * B : c * B + B], u_dev[c * B + B :]) if sample else None
         chunk = DecodeChunk(B, hist, pos_d, rows_of, m.config.tokenizer.answer_id, self._decode_ws_bytes(B), pick,
-                            u_dev[: c * B].view(c, B), **(scores.chunk_fields() if scores else {}))
+                            u_dev[: c * B].view(c, B), penalty=penalty, **(scores.chunk_fields() if scores else {}))
         stream = torch.cuda.current_stream(m.device).cuda_stream if m.use_graphs else None
         if run_chunk(m, chunk, n, "continuous", stream, lambda: m._store.count("continuous", stream) < MAX_GRAPHS):
             self.stats.graph_captures += 1

@@ -794,6 +794,80 @@ extern "C" md_status md_reason_route(const md_reason_state* st, const int32_t* t
   return md_launch_status();
 }
 
+// ---------------------------------------------------------------------------
+// Repetition / presence / frequency penalties from each row's own history of generated tokens (md_penalize_rows).
+// One workgroup per row.  The row's token is appended to its history, then every DISTINCT token of the history is found
+// once, with its count, through an open-addressing hash table in LDS: each thread inserts its strided share of the
+// history (atomicCAS claims a key, atomicAdd counts it), and after a barrier each occupied entry is one token's update.
+// The table has at least twice as many entries as the history has tokens (a power of two chosen from the row's length, so
+// the clear and the scan cost what the history holds, not what it could hold): a probe sequence always ends.
+// Global traffic: the history's tokens (4 B each) and one 2-byte load and store per distinct token -- never the row.
+namespace {
+constexpr int PENALTY_THREADS = 256;
+
+__device__ __forceinline__ unsigned penalty_hash(int t, int bits) { return ((unsigned)t * 2654435761u) >> (32 - bits); }
+
+__global__ __launch_bounds__(PENALTY_THREADS) void penalize_rows_kernel(
+    bf16_t* __restrict__ logits, int64_t ld, int vocab, const int32_t* __restrict__ tokens_in, const int32_t* __restrict__ slots,
+    int slot0, int32_t* hist, int hist_cap, int32_t* __restrict__ hist_len, const float* __restrict__ repetition,
+    const float* __restrict__ presence, const float* __restrict__ frequency, int table_cap) {
+  extern __shared__ int penalty_smem[];
+  __shared__ int s_len;
+  int* keys = penalty_smem;            // [table_cap] token id, -1: empty
+  int* counts = penalty_smem + table_cap;
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int slot = slots ? slots[r] : slot0 + r;
+  if (slot < 0) return;  // idle: nothing read, nothing written (the whole workgroup leaves, before any barrier)
+  int32_t* h = hist + (int64_t)slot * hist_cap;
+  // ---- append: one thread owns the history's length
+  if (tid == 0) {
+    int len = min(max(hist_len[slot], 0), hist_cap);
+    const int t = tokens_in[r];
+    if (t >= 0 && t < vocab && len < hist_cap) {
+      h[len] = t;
+      hist_len[slot] = ++len;
+    }
+    s_len = len;
+  }
+  const float rep = repetition[r], pres = presence[r], freq = frequency[r];
+  if (rep == 1.f && pres == 0.f && freq == 0.f) return;  // neutral: the logits row is neither read nor written
+  __syncthreads();  // s_len; thread 0's store to h[len - 1] is visible to the workgroup after it too
+  const int len = s_len;
+  if (len == 0) return;
+  int bits = 6;
+  while ((1 << bits) < 2 * len) ++bits;  // 2 * len <= 2 * hist_cap <= table_cap
+  const int size = 1 << bits;
+  for (int e = tid; e < size; e += PENALTY_THREADS) {
+    keys[e] = -1;
+    counts[e] = 0;
+  }
+  __syncthreads();
+  for (int i = tid; i < len; i += PENALTY_THREADS) {
+    const int t = h[i];
+    if (t < 0 || t >= vocab) continue;  // not an id: the caller's memory was not a history; never an address
+    unsigned e = penalty_hash(t, bits);
+    for (int probe = 0; probe < size; ++probe) {  // load factor <= 1/2: ends long before `size` probes
+      const int prev = atomicCAS(&keys[e], -1, t);
+      if (prev == -1 || prev == t) {
+        atomicAdd(&counts[e], 1);
+        break;
+      }
+      e = (e + 1) & (size - 1);
+    }
+  }
+  __syncthreads();
+  bf16_t* lr = logits + (int64_t)r * ld;
+  for (int e = tid; e < size; e += PENALTY_THREADS) {
+    const int v = keys[e];
+    if (v < 0) continue;
+    float x = bf2f(lr[v]);
+    if (rep != 1.f) x = x > 0.f ? __fdiv_rn(x, rep) : __fmul_rn(x, rep);
+    x = __fsub_rn(x, __fadd_rn(pres, __fmul_rn(freq, (float)counts[e])));
+    lr[v] = f2bf(x);
+  }
+}
+}  // namespace
+
 // internal (api.hip): the mask that also advances pos
 md_status md_mask_logits_advance(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* ids, int32_t* pos,
                                  hipStream_t stream) {
@@ -864,5 +938,19 @@ extern "C" md_status md_topk_logprobs(const void* logits, int64_t ld, int32_t ro
   if (rows == 0) return MD_OK;
   hipLaunchKernelGGL(topk_logprobs_kernel, dim3(rows), dim3(TOPK_THREADS), 0, (hipStream_t)stream, (const bf16_t*)logits, ld,
                      vocab, suppress_id, suppress_rows, gate, k, top_ids, top_logprobs);
+  return md_launch_status();
+}
+
+extern "C" md_status md_penalize_rows(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* tokens_in,
+                                      const int32_t* slots, int32_t slot0, int32_t* hist, int32_t hist_cap, int32_t* hist_len,
+                                      const float* repetition, const float* presence, const float* frequency, void* stream) {
+  MD_CHECK_ARG(logits && tokens_in && hist && hist_len && repetition && presence && frequency);
+  MD_CHECK_ARG(batch >= 0 && vocab >= 1 && ld >= vocab && hist_cap >= 1 && hist_cap <= MD_PENALTY_HIST_MAX);
+  if (batch == 0) return MD_OK;
+  int table_cap = 64;
+  while (table_cap < 2 * hist_cap) table_cap *= 2;  // <= 2 * MD_PENALTY_HIST_MAX entries of 8 bytes: 64 KiB, the static limit
+  hipLaunchKernelGGL(penalize_rows_kernel, dim3(batch), dim3(PENALTY_THREADS), (size_t)table_cap * 8, (hipStream_t)stream,
+                     (bf16_t*)logits, ld, vocab, tokens_in, slots, slot0, hist, hist_cap, hist_len, repetition, presence,
+                     frequency, table_cap);
   return md_launch_status();
 }

@@ -1,13 +1,15 @@
 """What the lockstep loop (``MoondreamModel._decode_greedy_impl``) and the continuous engine (``ContinuousEngine._step``)
 share: the description of a chunk of consecutive decode steps over fixed buffers, and the one runner that launches it.
 ``run_chunk`` holds the only step body of the package -- decode step (or, for a reasoning query, the reasoning step), then
-the optional sampling pick, then the optional log-probability launch and the optional top-k launch -- and the only decode
-graph key.  No torch here: the runner moves no data, it orders launches."""
+the optional penalty launch, then the optional sampling pick, then the optional log-probability launch and the optional
+top-k launch -- and the only decode graph key.  No torch here: the runner moves no data, it orders launches."""
 from __future__ import annotations
 
+import math
+import numbers
 import operator
 from dataclasses import dataclass
-from typing import Any, Callable, Optional, Tuple
+from typing import Any, Callable, List, Optional, Tuple
 
 
 TOPK_MAX = 32  # MD_TOPK_MAX of include/moondream_hip.h
@@ -29,6 +31,76 @@ def check_top_logprobs(top_logprobs: Optional[int], with_logprobs: bool) -> int:
     if not with_logprobs:
         raise ValueError("top_logprobs extends the log-probabilities: it needs return_logprobs=True / logprobs=True")
     return k
+
+
+PENALTY_SETTINGS = ("repetition_penalty", "presence_penalty", "frequency_penalty")
+PENALTY_NEUTRAL = (1.0, 0.0, 0.0)
+
+
+def check_penalties(repetition_penalty, presence_penalty, frequency_penalty, n: int) -> Optional[List[Tuple[float, float, float]]]:
+    """The three penalty arguments of the generation calls, each one number or one per row (None: neutral) -> one
+    (repetition, presence, frequency) triple per row, or None when every row is neutral (1, 0, 0).  ValueError for a
+    repetition penalty that is not finite and > 0, a presence or frequency penalty that is not finite, or a list that is
+    not ``n`` long: host values only, before any GPU work."""
+    cols = []
+    for name, x, neutral in zip(PENALTY_SETTINGS, (repetition_penalty, presence_penalty, frequency_penalty), PENALTY_NEUTRAL):
+        try:
+            vals = [x] * n if x is None or isinstance(x, numbers.Real) else list(x)
+        except TypeError:
+            raise ValueError(f"{name} must be a number or one number per row, not {x!r}") from None
+        if len(vals) != n:
+            raise ValueError(f"{name}: {len(vals)} values for {n} rows (one number, or one per row)")
+        col = []
+        for v in vals:
+            try:
+                f = neutral if v is None else float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"{name} must be a number, not {v!r}") from None
+            if isinstance(v, bool) or not math.isfinite(f) or (name == "repetition_penalty" and f <= 0):
+                raise ValueError(f"{name} must be finite" + (" and > 0" if name == "repetition_penalty" else "") + f", not {v!r}")
+            col.append(f)
+        cols.append(col)
+    rows = list(zip(*cols))
+    return None if all(r == PENALTY_NEUTRAL for r in rows) else rows
+
+
+def penalties_of(settings: Optional[dict]) -> dict:
+    """The penalty entries of a ``settings`` dict as keyword arguments of the generation calls (absent: neutral)."""
+    st = settings or {}
+    return {name: st.get(name, neutral) for name, neutral in zip(PENALTY_SETTINGS, PENALTY_NEUTRAL)}
+
+
+def refuse_penalties(settings: Optional[dict], where: str, n: int = 1) -> None:
+    """An entry point that does not serve the penalties: ValueError naming ``where`` when ``settings`` carries a
+    non-neutral one (and the validation errors of ``check_penalties`` for a value that is none)."""
+    st = penalties_of(settings)
+    for name in PENALTY_SETTINGS:  # a per-row list is judged by its values, whatever its length
+        if isinstance(st[name], (list, tuple)):
+            n = len(st[name])
+    if check_penalties(*(st[name] for name in PENALTY_SETTINGS), n) is not None:
+        raise ValueError(f"repetition_penalty / presence_penalty / frequency_penalty are not served by {where}")
+
+
+@dataclass(frozen=True, eq=False)
+class Penalty:
+    """The penalty state of a chunk (md_penalize_rows), all device memory at fixed addresses.  ``repetition``, ``presence``
+    and ``frequency`` (fp32 [b]) are the rows' settings.  ``hist`` (int32 [n, hist_cap]) and ``hist_len`` (int32 [n]) hold
+    the generated tokens of each history and are extended by every step: row r's history is row r's own, or, ``by_slot``,
+    that of its KV slot ``rows.slots[r]`` (the continuous engine: a request changes row from chunk to chunk and keeps its
+    slot; a row of slot -1 is idle)."""
+
+    repetition: Any
+    presence: Any
+    frequency: Any
+    hist: Any
+    hist_len: Any
+    hist_cap: int
+    by_slot: bool = False
+
+    def key(self) -> tuple:
+        """What a captured chunk bakes in of the penalty state: addresses, the capacity and whose history a row's is."""
+        return ("penalty",) + tuple(t.data_ptr() for t in (self.repetition, self.presence, self.frequency, self.hist,
+                                                          self.hist_len)) + (int(self.hist_cap), bool(self.by_slot))
 
 
 @dataclass(frozen=True, eq=False)
@@ -93,7 +165,12 @@ class DecodeChunk:
     ``b1``: the single-sequence persistent kernel takes the steps (b = 1, greedy).  ``step(tok_in) -> logits``: the step
     made from its pieces instead of the fused one (a LoRA adapter; eager only, its pick writes ``tokens[i + 1]``).
     ``reason`` (``ReasonChunk``): the steps are md_decode_step_reason's -- each row's phase decides what it feeds and which
-    ids its logits lose (``suppress_id`` is not used), and every step's pick is the per-row one; not with ``logprobs``."""
+    ids its logits lose (``suppress_id`` is not used), and every step's pick is the per-row one; not with ``logprobs``.
+    ``penalty`` (``Penalty``): after each step and before its pick, every row's consumed token joins its history and the
+    row's logits take its penalties (md_penalize_rows).  The fused step's own argmax was taken from the raw logits, so
+    such a chunk always picks again -- with ``pick`` None by the argmax launch -- and the log-probabilities and
+    alternatives are those of the PENALISED logits, the distribution the token was picked from before temperature and
+    top-p (every greedy token still has rank 0).  Not with ``b1`` or ``reason``."""
 
     b: int
     tokens: Any
@@ -108,6 +185,7 @@ class DecodeChunk:
     step: Optional[Callable[[Any], Any]] = None
     reason: Optional[ReasonChunk] = None
     topk: Optional[Tuple[Any, Any]] = None
+    penalty: Optional[Penalty] = None
 
 
 def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_stream: Optional[int] = None,
@@ -116,13 +194,14 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     stream: the chunk is replayed from the graph captured for it on that stream, or, first, run eagerly and captured
     (``model._replay_or_capture``: its ``GraphStore``'s, ``may_capture`` too).  The key starts (``tag``, stream) and names everything
     the launches bake in.  Returns True when it captured.  Besides that, the model gives the buffers (_decode_logits, _workspace,
-    _kv_struct) and the launches (_decode_step, _decode_step_b1, _decode_step_reason, _pick, _pick_rows, _token_logprobs, _topk_logprobs)."""
+    _kv_struct) and the launches (_decode_step, _decode_step_b1, _decode_step_reason, _penalize, _pick, _pick_rows, _token_logprobs, _topk_logprobs)."""
     c = chunk
     pieces = c.step is not None
     assert c.reason is None or (not pieces and not c.b1 and c.logprobs is None and c.pick is not None and c.pick.per_row)
     assert not (pieces and (capture_stream is not None or c.b1))
     assert not c.b1 or (c.b == 1 and c.pick is None)
     assert c.topk is None or c.logprobs is not None
+    assert c.penalty is None or (not c.b1 and c.reason is None)
     if not pieces:
         logits = model._decode_logits(c.b)
         ws = model._workspace(c.ws_bytes, 2)
@@ -131,6 +210,8 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     lp, rk = c.logprobs if c.logprobs is not None else (None, None)
     tk_ids, tk_lp = c.topk if c.topk is not None else (None, None)
     by_row = c.pick is not None and c.pick.per_row
+    # penalised logits are picked from again: the fused step's argmax saw the raw ones
+    again = c.pick if c.pick is not None or c.penalty is None else Sampling(0.0, 0.0)
 
     def body():
         for i in range(n):
@@ -145,12 +226,14 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
             elif not pieces:
                 model._decode_step(c.rows_of(i), tok_in, tok_out, c.pos, c.b, c.suppress_id, logits, ws, kv)
             lg = c.step(tok_in) if pieces else left
+            if c.penalty is not None:  # tok_in joins each row's history, whose tokens' logits are penalised in place
+                model._penalize(lg, tok_in, c.rows_of(i), c.penalty)
             # a fused step wrote its argmax to tok_out: a pick draws from the logits it left instead (of per-row settings,
             # a greedy row takes the same argmax again and an idle row keeps what is there)
             if by_row:
                 model._pick_rows(lg, c.pick.temperature, c.pick.top_p, c.suppress_id, c.uniforms[i], out=tok_out)
-            elif c.pick is not None:
-                model._pick(lg, c.pick.temperature, c.pick.top_p, c.suppress_id, c.pick.generator,
+            elif again is not None:
+                model._pick(lg, again.temperature, again.top_p, c.suppress_id, again.generator,
                             uniforms=c.uniforms[i] if c.uniforms is not None else None, out=tok_out)
             if lp is not None:  # targets = the step's tokens
                 model._token_logprobs(lg, tok_out, c.suppress_id, lp[i], rk[i])
@@ -175,4 +258,6 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
         key += ("topk", int(tk_ids.shape[-1]), tk_ids.data_ptr(), tk_lp.data_ptr())
     if c.reason is not None:  # likewise: another graph, keyed by the state's addresses
         key += c.reason.key()
+    if c.penalty is not None:  # and another with the penalty launches
+        key += c.penalty.key()
     return model._replay_or_capture(key, body, may_capture=may_capture)

@@ -31,7 +31,8 @@ from PIL import Image
 from . import _lib
 from .config import MoondreamConfig
 from .crop_staging import CropStager, crop_workers, upload_unique
-from .decode_loop import DecodeChunk, ReasonChunk, Sampling, check_top_logprobs, run_chunk
+from .decode_loop import (DecodeChunk, Penalty, ReasonChunk, Sampling, check_penalties, check_top_logprobs, penalties_of,
+                          refuse_penalties, run_chunk)
 from .graph_store import GraphStore
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
@@ -1018,6 +1019,41 @@ class MoondreamModel:
         )
         return nxt
 
+    def _penalize(self, logits: torch.Tensor, tok_in: torch.Tensor, rows: "_Rows", pen: Penalty):
+        """Every row's consumed token ``tok_in[r]`` (device int32 [B]) joins its history in ``pen`` and the logits [B, V] of
+        the tokens in that history take the row's penalties in place: md_penalize_rows.  A row's history is its own, or
+        (``pen.by_slot``) that of its KV slot in ``rows``; an idle row is left alone.  Nothing is allocated and nothing
+        synchronises: capturable."""
+        b, v = logits.shape
+        assert tok_in.dtype == torch.int32 and tok_in.is_contiguous() and tok_in.numel() == b and tok_in.device == logits.device
+        for t in (pen.repetition, pen.presence, pen.frequency):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == b and t.device == logits.device
+        assert pen.hist.dtype == torch.int32 and pen.hist_len.dtype == torch.int32 and pen.hist.is_contiguous()
+        assert pen.hist.shape == (pen.hist_len.numel(), pen.hist_cap)
+        slots = rows.slots if pen.by_slot else None
+        assert slots is not None or pen.hist_len.numel() >= b
+        _lib.check(
+            self.lib.md_penalize_rows(logits.data_ptr(), logits.stride(0), b, v, tok_in.data_ptr(),
+                                      slots.data_ptr() if slots is not None else None, 0, pen.hist.data_ptr(), pen.hist_cap,
+                                      pen.hist_len.data_ptr(), pen.repetition.data_ptr(), pen.presence.data_ptr(),
+                                      pen.frequency.data_ptr(), self._stream()),
+            "md_penalize_rows",
+        )
+
+    def _penalty_record(self, rows: Optional[Sequence[Tuple[float, float, float]]]) -> Optional[Penalty]:
+        """``check_penalties``' triples, one per row in the decode loop's row order -> the ``Penalty`` record of a lockstep
+        decode with every history empty (None for None).  The buffers are the store's, one set per row count: captured
+        chunks keep their addresses."""
+        if rows is None:
+            return None
+        b, cap = len(rows), min(self.config.text.max_context, _lib.MD_PENALTY_HIST_MAX)  # (more than a row can generate)
+        st, hist, hist_len = self._store.fixed("penalty", b, lambda: (
+            torch.empty(3, b, dtype=torch.float32, device=self._device),
+            torch.zeros(b, cap, dtype=torch.int32, device=self._device), torch.zeros(b, dtype=torch.int32, device=self._device)))
+        st.copy_(self._h2d(torch.tensor(rows, dtype=torch.float32).t().contiguous()))
+        hist_len.zero_()
+        return Penalty(st[0], st[1], st[2], hist, hist_len, cap)
+
     def _token_logprobs(self, logits: torch.Tensor, targets: torch.Tensor, suppress_id: int, logprob: torch.Tensor,
                         rank: torch.Tensor, suppress_rows: Optional[torch.Tensor] = None):
         """``logprob[r]`` (device fp32 [R]) and ``rank[r]`` (device int32 [R]) of token ``targets[r]`` (device int32 [R]) in row
@@ -1117,7 +1153,8 @@ class MoondreamModel:
 
     def _decode_greedy_impl(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
                             rows: Union[int, _Rows] = 0, eos_id: Optional[int] = None, check_every: int = 16,
-                            allow_b1: bool = True, sampling: Optional[Sampling] = None, scores: Optional[Scores] = None):
+                            allow_b1: bool = True, sampling: Optional[Sampling] = None, scores: Optional[Scores] = None,
+                            penalty: Optional[Penalty] = None):
         """Device-resident decode loop: returns int32 [steps+1, B] (row 0 = ``first``).  ``sampling`` None: greedy.  Otherwise every
         step draws each sequence's token with the reference's rule (moondream.py:521-528: softmax(logits / T), _apply_top_p,
         multinomial) from the step's own logits on the device (md_sample_top_p), with one uniform per (step, sequence) taken
@@ -1130,7 +1167,10 @@ class MoondreamModel:
         captured hipGraph over the fixed buffers of the chunk's shape.  ``rows``: the routing of every step (``_Rows``).
         ``scores``: a record over [>= max_tokens + 1, B] whose row 0 holds ``first``'s decision; the loop fills row i for the
         tokens of ``hist[i]`` (``_token_logprobs`` on the logits the step leaves, then ``_topk_logprobs`` when the record has
-        alternatives: the launches after the step's pick, inside the captured graph) and changes no id for it."""
+        alternatives: the launches after the step's pick, inside the captured graph) and changes no id for it.
+        ``penalty``: the rows' penalty record (``_penalty_record``) -- every step extends the histories by the tokens it
+        consumes (``first`` in its first step) and penalises its logits before the pick; the scores are then those of the
+        penalised logits.  Such a call decodes on the batched kernels, never on the single-sequence one."""
         rows = _Rows.of(rows)
         b = first.shape[0]
         t = self.config.text
@@ -1167,7 +1207,8 @@ class MoondreamModel:
                 taken += 1
                 return self._step_from_pieces(tok_in.reshape(b, 1), pos_h, rows, pos_dev=pos_t)[1]
 
-            chunk = DecodeChunk(b, hist, pos_t, lambda i: rows, suppress_id, pick=sampling or Sampling(0.0, 0.0), step=lora_step)
+            chunk = DecodeChunk(b, hist, pos_t, lambda i: rows, suppress_id, pick=sampling or Sampling(0.0, 0.0), step=lora_step,
+                                penalty=penalty)
             graphs, uniforms = False, None
         else:
             need = self._decode_ws_bytes(rows, b)
@@ -1175,14 +1216,15 @@ class MoondreamModel:
             # library says this model / cache / device fits its static limits and its grid can be co-resident; anything else
             # decodes on the batched kernels.  Never from the pipelined engine (allow_b1 = False): a second stream's persistent
             # GEMMs could keep workgroups of the grid off the chip and its software barriers would time out.
-            b1 = (b == 1 and allow_b1 and sampling is None and self.single_sequence_kernel and rows.plain and not bool(self.w.text.fp8)
+            b1 = (b == 1 and allow_b1 and sampling is None and penalty is None and self.single_sequence_kernel and rows.plain
+                  and not bool(self.w.text.fp8)
                   and bool(self.lib.md_decode_step_b1_supported(C.byref(self.w.text), C.byref(self._kv_struct(rows.slot0)))))
             self._b1_used = b1
             if b1:
                 if self._b1_sync is None:
                     self._b1_sync = torch.zeros(4096, dtype=torch.int32, device=self._device)
                 need = max(need, self.lib.md_decode_step_b1_workspace_bytes(C.byref(self.w.text)))
-            chunk = DecodeChunk(b, hist, pos_t, lambda i: rows, suppress_id, need, sampling, b1=b1)
+            chunk = DecodeChunk(b, hist, pos_t, lambda i: rows, suppress_id, need, sampling, b1=b1, penalty=penalty)
             graphs = self.use_graphs
         # one graph = `per` consecutive steps over fixed buffers; eager chunks end where the all-done check is due
         per = max(1, min(check_every or 16, max_tokens)) if graphs else (check_every or max_tokens)
@@ -1403,6 +1445,9 @@ class MoondreamModel:
         variants: Optional[Sequence[Optional[str]]] = None,
         return_logprobs: bool = False,
         top_logprobs: Optional[int] = None,
+        repetition_penalty: Union[float, Sequence[float]] = 1.0,
+        presence_penalty: Union[float, Sequence[float]] = 0.0,
+        frequency_penalty: Union[float, Sequence[float]] = 0.0,
     ):
         """Token ids for B (image, prompt-ids) pairs, decoded in lockstep; greedy by default.
 
@@ -1461,10 +1506,27 @@ class MoondreamModel:
         ``answer_id``.  md_topk_logprobs: one more launch per step, after md_token_logprobs, in the same captured chunk;
         the same single copy to the host.  It changes no pick (this is not a top-k sampling rule); 0 / None: the call
         without it.  ValueError, before any GPU work: ``top_logprobs`` without ``return_logprobs``, or outside 1 .. 32.
+
+        ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: one number, or one per row in the caller's
+        order.  Before a token is picked, every token v the row has GENERATED so far (c times) has its logit x changed, in
+        fp32: ``x = x / repetition_penalty if x > 0 else x * repetition_penalty`` (the HF / vLLM rule), then
+        ``x -= presence_penalty + frequency_penalty * c`` (the OpenAI rule), rounded back to bf16 -- on the device
+        (md_penalize_rows: one launch per step before the pick, inside the captured chunk; the histories live on the
+        device).  The history is the generated tokens only: the first token, picked from the prompt pass's logits with
+        an empty history, is in it, the prompt is not.  For ``repetition_penalty`` that differs from HF's processor,
+        which also counts the prompt's tokens.  Sampling (``temperature``) draws from the penalised logits.  With
+        ``return_logprobs`` the log-probabilities, ranks and alternatives are those of the PENALISED logits -- the
+        distribution the token was picked from, before temperature and top-p -- so every greedy token still has rank 0.
+        A row's ids depend on its own settings only; with every row neutral (1, 0, 0) the call is the one without the
+        arguments, launch for launch.  Served in every mode of this call (``share_prefix``, ``variant``, ``variants``,
+        the fp8 modes: a step leaves bf16 logits in the same buffer in all of them); a lone penalised sequence decodes on
+        the batched kernels.  ValueError, before any GPU work: a repetition penalty that is not finite and > 0, a
+        presence or frequency penalty that is not finite, a list that is not one per row.
         """
         top_k = check_top_logprobs(top_logprobs, return_logprobs)
         b = len(images)
         assert b == len(prompts) and b > 0
+        penalties = check_penalties(repetition_penalty, presence_penalty, frequency_penalty, b)
         multi_rows = None
         if variants is not None:
             if variant is not None:
@@ -1488,8 +1550,9 @@ class MoondreamModel:
                                            variants=multi_rows, encode_settings={"variant": variant}, sampling=sampling,
                                            scores=scores and scores[0])
             stop = None if ignore_eos else eos
+            penalty = self._penalty_record(penalties and [penalties[i] for i in prep.order])  # rows in slot order
             hist = self._decode_greedy(prep.first, prep.pos, max_tokens, tk.answer_id, prep.rows, stop, sampling=prep.sampling,
-                                       scores=scores)
+                                       scores=scores, penalty=penalty)
             mark("decode")
             host = scores and scores[: hist.shape[0]].to_host(hist)  # ids, logprobs, ranks, alternatives: ONE copy to the host
             cols = (host.extra[0].T if host else hist.t()).tolist()
@@ -1510,17 +1573,22 @@ class MoondreamModel:
                                       temperature: Union[float, Sequence[float]] = 0.0,
                                       top_p: Union[float, Sequence[float]] = DEFAULT_TOP_P, seeds=None,
                                       variant: Optional[str] = None, return_logprobs: bool = False,
-                                      top_logprobs: Optional[int] = None):
+                                      top_logprobs: Optional[int] = None, repetition_penalty=None, presence_penalty=None,
+                                      frequency_penalty=None):
         """``batch_generate_ids`` with continuous batching (moondream_amd/continuous.py): per-request ``max_tokens`` and EOS
         exit, freed KV slots refilled from the queue mid-decode; same greedy ids as the lockstep path.  ``temperature`` and
         ``top_p``: one float, or one per request (greedy and sampled requests share the decode steps).  ``return_logprobs``:
         (ids, logprobs, ranks) as ``batch_generate_ids`` returns them (``ContinuousEngine(logprobs=True)``); with
-        ``top_logprobs`` = k also its ``alternatives`` (``ContinuousEngine(logprobs=True, top_logprobs=k)``)."""
+        ``top_logprobs`` = k also its ``alternatives`` (``ContinuousEngine(logprobs=True, top_logprobs=k)``).  The three
+        penalties: one number or one per request (None: neutral), ``batch_generate_ids``' rule per request."""
         from .continuous import ContinuousEngine
+
+        check_penalties(repetition_penalty, presence_penalty, frequency_penalty, len(images))  # before the engine exists
 
         eng = ContinuousEngine(self, max_live, chunk, logprobs=bool(return_logprobs), top_logprobs=top_logprobs)
         return eng.generate(images, prompts, max_tokens, eos_id, ignore_eos, seeds, variant, temperature, top_p,
-                            return_logprobs=bool(return_logprobs))
+                            return_logprobs=bool(return_logprobs), repetition_penalty=repetition_penalty,
+                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
 
     def teacher_forced_logits(self, images, prompts: Sequence[Sequence[int]], forced_ids, gather_idx) -> torch.Tensor:
         """Parity instrument (tests / bench.py): the logits of every greedy decision when each sequence is FORCED to follow
@@ -1580,7 +1648,7 @@ class MoondreamModel:
 
     def score_ids(self, images: Sequence[Union[Image.Image, EncodedImage]], prompts: Sequence[Sequence[int]],
                   continuations: Sequence[Sequence[int]], share_prefix: bool = False, variant: Optional[str] = None,
-                  top_logprobs: Optional[int] = None):
+                  top_logprobs: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
         """Score GIVEN continuations: returns ``(logprobs, ranks)``, one list per row with one entry per token of
         ``continuations[i]`` -- the values ``batch_generate_ids(..., return_logprobs=True)`` attaches to a token it generates,
         for the tokens the caller supplies.  ``logprobs[i][j]`` is log softmax of the model's logits after
@@ -1599,8 +1667,13 @@ class MoondreamModel:
         ``top_logprobs`` = k in 1 .. 32: returns ``(logprobs, ranks, alternatives)``; ``alternatives[i][j]`` is the list of
         the k most probable live tokens of decision j as ``(token_id, logprob)`` pairs in rank order, as
         ``batch_generate_ids(..., top_logprobs=k)`` gives them: ONE md_topk_logprobs launch over the same logits and
-        suppression table, and the same copy to the host.  ValueError for a k outside 1 .. 32."""
+        suppression table, and the same copy to the host.  ValueError for a k outside 1 .. 32.  The penalty arguments of
+        ``batch_generate_ids`` are not served here (ValueError for a non-neutral one): the scorer makes no decode step, so
+        there is no history to penalise from -- scores are the model's own."""
         top_k = check_top_logprobs(top_logprobs, True)
+        refuse_penalties(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                              frequency_penalty=frequency_penalty), "score_ids (no decode step runs: scores are the model's own)",
+                         len(images))
         self._check_score_args(images, prompts, continuations)
         conts = [[int(t) for t in c] for c in continuations]
         seqs = [[int(t) for t in p] + c[:-1] for p, c in zip(prompts, conts)]
@@ -1646,7 +1719,8 @@ class MoondreamModel:
 
     pipeline_streams = int(os.environ.get("MD_PIPE_STREAMS", "2"))  # 2: decode on its own (priority) stream; 1: encode and decode in order on one stream
 
-    def batch_generate_ids_pipelined(self, batches, max_tokens: int = DEFAULT_MAX_TOKENS, ignore_eos: bool = False):
+    def batch_generate_ids_pipelined(self, batches, max_tokens: int = DEFAULT_MAX_TOKENS, ignore_eos: bool = False,
+                                     repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
         """Generator over an iterable of (images, prompt-id lists) batches; yields each batch's greedy ids in order, one
         decode group late (a group = two consecutive batches of <= 64 sequences decoded as ONE lockstep of <= 128 -- round 6,
         ``pair_decode`` -- or one batch).  Two HIP streams: the MFMA-bound encode (vision + prefill) of batch k+1 on one, the HBM-bound lockstep
@@ -1662,8 +1736,11 @@ class MoondreamModel:
             k+1 has been queued; nothing touches the default stream and no host array is copied from pageable memory
             (either makes the host wait for the device).
 
-        Per batch the result is identical to ``batch_generate_ids`` (same kernels, same order)."""
-        yield from self._pipelined_loop(batches, max_tokens, ignore_eos)
+        Per batch the result is identical to ``batch_generate_ids`` (same kernels, same order).  The penalty arguments of
+        that call are not served here: ValueError for a non-neutral one."""
+        refuse_penalties(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                              frequency_penalty=frequency_penalty), "the pipelined engine (its paired decode keeps no histories)")
+        return self._pipelined_loop(batches, max_tokens, ignore_eos)
 
     # Round 6: the decode of TWO consecutive batches runs as one lockstep decode (<= 128 sequences) when the library takes that
     # many rows in one pass over the weights (md_decode_step: 65 .. 128 rows on the 128 x 64 weight-streaming tile, same bits as
@@ -1793,11 +1870,12 @@ class MoondreamModel:
     def _sampling_kwargs(settings: Optional[dict]) -> dict:
         """``settings`` of the string API -> keyword arguments of ``batch_generate_ids``, with the REFERENCE'S defaults
         (moondream.py:50-53, read at :447-457): max_tokens 768, temperature 0.5, top_p 0.3.  ``settings["generator"]`` (an
-        extension) seeds the draws; ``{"temperature": 0}`` is greedy."""
+        extension) seeds the draws; ``{"temperature": 0}`` is greedy.  ``repetition_penalty`` / ``presence_penalty`` /
+        ``frequency_penalty`` (extensions; one number or one per row) pass through, neutral when absent."""
         st = settings or {}
         return dict(max_tokens=st.get("max_tokens", DEFAULT_MAX_TOKENS), variant=st.get("variant"), variants=st.get("variants"),
                     temperature=st.get("temperature", DEFAULT_TEMPERATURE), top_p=st.get("top_p", DEFAULT_TOP_P),
-                    generator=st.get("generator"))
+                    generator=st.get("generator"), **penalties_of(settings))
 
     def batch_caption(self, images, length: str = "normal", settings: Optional[dict] = None) -> List[str]:
         tpl = self.config.tokenizer.templates["caption"]
@@ -1867,11 +1945,15 @@ class MoondreamModel:
     def _generate_answer(self, prompt_tokens: torch.Tensor, pos: int, settings: Optional[dict] = None,
                          spatial_refs: Optional[SpatialRefs] = None, eos_id: Optional[int] = None, attn_mask=None,
                          causal: bool = False):
-        """Generator of text pieces.  reference: moondream.py:434-539."""
+        """Generator of text pieces.  reference: moondream.py:434-539.  ``settings`` may carry ``repetition_penalty`` /
+        ``presence_penalty`` / ``frequency_penalty`` (``batch_generate_ids``' rule, over this sequence's generated tokens):
+        every step's logits are penalised on the device before its pick, in the chunked greedy loop and in the per-token
+        sampled one alike."""
         settings = settings or {}
         max_tokens = settings.get("max_tokens", DEFAULT_MAX_TOKENS)
         temperature = settings.get("temperature", DEFAULT_TEMPERATURE)
         top_p = settings.get("top_p", DEFAULT_TOP_P)
+        penalties = check_penalties(*penalties_of(settings).values(), 1)
         lora = self._lora(settings)
         rows = _Rows(lora=lora)
         eos = eos_id if eos_id is not None else self.config.tokenizer.eos_id
@@ -1879,13 +1961,15 @@ class MoondreamModel:
         _, _, nxt, pos = self._prefill_prompt(prompt_tokens, pos, temperature, top_p, spatial_refs, attn_mask, lora=lora, causal=causal)
 
         def token_source():
+            with torch.inference_mode():
+                penalty = self._penalty_record(penalties)  # one history over the whole answer, empty now
             if temperature == 0 and lora is None:
                 done = 0
                 first = nxt.reshape(1).to(torch.int32)
                 cur_pos = pos
                 while done < max_tokens:
                     chunk = min(16, max_tokens - done)
-                    hist = self._decode_greedy(first, cur_pos, chunk, self.config.tokenizer.answer_id, 0, None)
+                    hist = self._decode_greedy(first, cur_pos, chunk, self.config.tokenizer.answer_id, 0, None, penalty=penalty)
                     toks = hist[:, 0].tolist()
                     self._check_b1_barriers()
                     for tok in toks[:-1]:
@@ -1906,6 +1990,8 @@ class MoondreamModel:
                     with torch.inference_mode():
                         _, logits = self._step_from_pieces(tok.reshape(1, 1), cur_pos, rows)
                         cur_pos += 1
+                        if penalty is not None:
+                            self._penalize(logits, tok, rows, penalty)
                         tok = self._pick(logits, temperature, top_p, self.config.tokenizer.answer_id)  # moondream.py:517
 
         def generator():
@@ -1945,7 +2031,9 @@ class MoondreamModel:
 
     def caption(self, image, length: Literal["normal", "short", "long"] = "normal", stream: bool = False,
                 settings: Optional[dict] = None):
-        """reference: moondream.py:625-651."""
+        """reference: moondream.py:625-651.  ``settings`` may carry ``repetition_penalty`` / ``presence_penalty`` /
+        ``frequency_penalty`` (an extension: ``batch_generate_ids``' rule over the caption's generated tokens)."""
+        check_penalties(*penalties_of(settings).values(), 1)  # host values: before any GPU work
         tpl = self.config.tokenizer.templates["caption"]
         if tpl is None:
             raise NotImplementedError("Model does not support captioning.")
@@ -1960,7 +2048,9 @@ class MoondreamModel:
     def query(self, image=None, question: str = None, reasoning: bool = False,
               spatial_refs: Optional[SpatialRefs] = None, stream: bool = False, settings: Optional[dict] = None):
         """reference: moondream.py:541-618, including the ``reasoning`` branch (thinking token -> _generate_reasoning
-        -> answer after a second suffix)."""
+        -> answer after a second suffix).  ``settings`` may carry the penalty settings as ``caption``'s may; not with
+        ``reasoning`` (ValueError)."""
+        check_penalties(*penalties_of(settings).values(), 1)  # host values: before any GPU work
         tpl = self.config.tokenizer.templates["query"]
         if tpl is None:
             raise NotImplementedError("Model does not support querying.")
@@ -1968,6 +2058,8 @@ class MoondreamModel:
             raise ValueError("question must be provided.")
         if spatial_refs and image is None:
             raise ValueError("spatial_refs can only be used with an image.")
+        if reasoning:
+            refuse_penalties(settings, "reasoning queries")
         if image is not None:
             enc = self.encode_image(image, settings)
             self.load_encoded_image(enc)
@@ -2355,8 +2447,10 @@ class MoondreamModel:
         return out
 
     def _check_reasoning_served(self, settings: Optional[dict]) -> None:
-        """What the batched reasoning query does not serve raises NotImplementedError, naming the reason."""
+        """What the batched reasoning query does not serve raises NotImplementedError, naming the reason (ValueError for
+        the penalty settings: a reasoning row's logits are masked per phase inside its own step)."""
         st = settings or {}
+        refuse_penalties(settings, "reasoning queries")
         if st.get("variant") is not None or st.get("variants") is not None:
             raise NotImplementedError("batched reasoning queries are not served with LoRA variants (variant / variants): "
                                       "use query(reasoning=True) per image")
@@ -2411,6 +2505,7 @@ class MoondreamModel:
 
     def _batch_detect_like(self, images, objects: Sequence[str], kind: str, include_size: bool, settings: Optional[dict],
                            share_prefix: bool = False):
+        refuse_penalties(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
         tpl = self.config.tokenizer.templates[kind]
         if tpl is None:
             raise NotImplementedError(f"Model does not support {kind}.")
@@ -2443,6 +2538,7 @@ class MoondreamModel:
         ``{"answer": batch_query([encode_image(image)] * N, questions)[i]}``, in the bf16 mode and in the fp8 KV mode.  A LoRA
         ``variant`` (settings) takes the copy path, with the same results.  With reasoning: ``query_many_reasoning``."""
         prompts = self._query_prompts(questions)
+        check_penalties(*penalties_of(settings).values(), len(prompts))  # host values: before any GPU work
         enc = self.encode_image(image, settings)
         ids = self.batch_generate_ids([enc] * len(prompts), prompts, share_prefix=True, **self._sampling_kwargs(settings))
         return [{"answer": self.tokenizer.decode(s)} for s in ids]
@@ -2481,12 +2577,14 @@ class MoondreamModel:
     def detect_many(self, image, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
         """``detect`` of many objects in ONE image over a single copy of its KV prefix.  Element i ==
         ``batch_detect([encode_image(image)] * N, objects)[i]`` (fp8 KV mode included).  LoRA variant: the copy path, same results."""
+        refuse_penalties(settings, "detect: its loop decodes coordinates, not tokens picked from logits")
         enc = self.encode_image(image, settings)
         return [{"objects": o} for o in self._batch_detect_like([enc] * len(objects), objects, "detect", True, settings, True)]
 
     def point_many(self, image, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
         """``point`` for many objects in ONE image over a single copy of its KV prefix.  Element i ==
         ``batch_point([encode_image(image)] * N, objects)[i]`` (fp8 KV mode included).  LoRA variant: the copy path, same results."""
+        refuse_penalties(settings, "point: its loop decodes coordinates, not tokens picked from logits")
         enc = self.encode_image(image, settings)
         return [{"points": o} for o in self._batch_detect_like([enc] * len(objects), objects, "point", False, settings, True)]
 
@@ -2498,6 +2596,7 @@ class MoondreamModel:
         only the first batch's tiling is exposed.  Results are identical to calling ``batch_detect`` per batch."""
         if kind not in ("detect", "point"):
             raise ValueError("kind must be 'detect' or 'point'")
+        refuse_penalties(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
         run = self.batch_detect if kind == "detect" else self.batch_point
         it = iter(batches)
         cur = next(it, None)
