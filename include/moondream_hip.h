@@ -515,6 +515,23 @@ md_status md_region_pick_encode(const void* logits, int64_t ld, int32_t batch, i
                                 int32_t n_bins, const void* value_table, const void* feat_w, int32_t half,
                                 int32_t* bins, int64_t ld_bins, void* feats, int64_t ld_feats, void* stream);
 
+/* md_region_pick_encode with a confidence per pick.  bins and feats: md_region_pick_encode's on the same inputs, bit for bit
+ * (ties -> lowest bin, an all-NaN group -> bin 0).  logprobs fp32 [batch][ld_logprobs]: for group g of row b, with x the
+ * group's bf16 logits as fp32, p = bins[b][g] and m = x[p],
+ *     S = sum over every bin i of exp(x[i] - m),   W = the same sum over the bins with |i - p| <= window, inside [0, n_bins),
+ *     logprobs[b][g] = log(W) - log(S):
+ *   the log of the probability mass the head put within `window` bins of its pick.  window = 0: W is exactly 1 and the value is
+ *   the log-softmax of the picked bin.  window >= n_bins - 1: W and S are one sum and the value is exactly 0.0f.  A -inf logit
+ *   adds 0.  A NaN anywhere in the group, or a group whose maximum is not finite, gives NaN for that group.
+ * One workgroup per row, a row's result independent of the rows beside it; the summation order depends on n_bins alone
+ * (csrc/sampling_region.hip).  Plain loads: no alignment demand on n_bins, ld, ld_bins or ld_logprobs.  No host sync, no
+ * allocation: capturable.
+ * MD_ERR_INVALID_ARG: what md_region_pick_encode refuses, NULL logprobs, window < 0, ld_logprobs < n_groups. */
+md_status md_region_pick_encode_scored(const void* logits, int64_t ld, int32_t batch, int32_t n_groups,
+                                       int32_t n_bins, const void* value_table, const void* feat_w, int32_t half,
+                                       int32_t* bins, int64_t ld_bins, void* feats, int64_t ld_feats, int32_t window,
+                                       float* logprobs, int64_t ld_logprobs, void* stream);
+
 /* Overlap-crop stitch + adaptive average pool + concat with the global crop's
  * features (reference: moondream.py:213-226, image_crops.py:170-231 with
  * patch_size=1, vision.py:83-88).  feats: bf16 [1 + th*tw][g*g][dim] for ONE

@@ -84,6 +84,100 @@ __global__ __launch_bounds__(256) void region_pick_kernel(const bf16_t* __restri
   fourier_row(v, n_groups, w, half, feats + (int64_t)b * ldf);
 }
 
+// region_pick_kernel with a confidence per group (md_region_pick_encode_scored).  The pick is region_pick_kernel's own,
+// statement for statement (a kernel of its own: the reasoning step bakes region_pick_kernel into captured graphs), so bins
+// and features are bit-identical: ties -> lowest bin, an all-NaN group -> bin 0.  Then, per group, with m = x[pick] (the
+// group's maximum) in fp32 from the bf16 logits x:
+//   S = sum over all bins i of exp(x_i - m),   W = the same sum over the bins with |i - pick| <= window (clamped to the group),
+//   logprobs[b][g] = log(W) - log(S).
+// The group (2 KB at 1024 bins) is read twice, once for the pick and once for the sums, the second time from L2.
+// Summation order, a function of n_bins alone (never of the row or the row count), the same for S and for W:
+//   1. thread tid adds its strided share exp(x[tid + k * 256] - m), k = 0, 1, .. ascending, sequentially in fp32
+//      (n_t = ceil(n_bins / 256) terms: 4 at 1024 bins); W adds the term itself inside the window and +0.0f outside it;
+//   2. a 6-level xor butterfly over the wave's 64 lanes (offsets 32, 16, .., 1);
+//   3. thread 0 adds the 4 wave partials in wave order, ((p0 + p1) + p2) + p3.
+// So every term passes through at most (n_t - 1) + 6 + 3 additions.  Adding +0.0f changes nothing, so W is the fp32 sum of
+// the window's terms in S's order: with window = 0 it is exp(0) = 1 and the value is the log-softmax of the pick; with a
+// window that covers the group W and S are the same sequence of operations on the same numbers and the value is exactly
+// 0.0f.  A -inf logit adds exp(-inf) = 0.  A NaN in the group makes S, and the value, NaN (the pick skips it); so does a
+// group whose maximum is not finite.  Plain 2-byte loads: no alignment demand on n_bins or the strides.
+__global__ __launch_bounds__(256) void region_pick_scored_kernel(const bf16_t* __restrict__ logits, int64_t ld, int n_groups,
+                                                                 int n_bins, const bf16_t* __restrict__ table,
+                                                                 const bf16_t* __restrict__ w, int half,
+                                                                 int32_t* __restrict__ bins, int64_t ld_bins,
+                                                                 bf16_t* __restrict__ feats, int64_t ldf, int window,
+                                                                 float* __restrict__ logprobs, int64_t ld_lp) {
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  __shared__ float val[2];
+  __shared__ int picked;
+  __shared__ float part_s[4];
+  __shared__ float part_w[4];
+  const int b = blockIdx.x;
+  for (int g = 0; g < n_groups; ++g) {
+    const bf16_t* lr = logits + (int64_t)b * ld + (int64_t)g * n_bins;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < n_bins; i += 256) {
+      const float x = bf2f(lr[i]);
+      if (x > best || (x == best && i < bi)) {
+        best = x;
+        bi = i;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > best || (ov == best && oi < bi)) {
+        best = ov;
+        bi = oi;
+      }
+    }
+    if ((threadIdx.x & 63) == 0) {
+      sv[threadIdx.x >> 6] = best;
+      si[threadIdx.x >> 6] = bi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int wv = 1; wv < 4; ++wv)
+        if (sv[wv] > best || (sv[wv] == best && si[wv] < bi)) {
+          best = sv[wv];
+          bi = si[wv];
+        }
+      if (bi >= n_bins) bi = 0;  // all-NaN row
+      bins[(int64_t)b * ld_bins + g] = bi;
+      val[g] = bf2f(table[bi]);
+      picked = bi;
+    }
+    __syncthreads();
+    // ---- the sums, in the order documented above
+    const int pick = picked;
+    const float m = bf2f(lr[pick]);
+    const int lo = pick - min(window, pick), hi = pick + min(window, n_bins - 1 - pick);  // no overflow for any window >= 0
+    float s = 0.f, ws = 0.f;
+    for (int i = threadIdx.x; i < n_bins; i += 256) {
+      const float e = expf(bf2f(lr[i]) - m);
+      s = __fadd_rn(s, e);  // never fused with expf's last multiply: S and W add the same rounded term
+      ws = __fadd_rn(ws, (i >= lo && i <= hi) ? e : 0.f);
+    }
+    s = wave_sum(s);
+    ws = wave_sum(ws);
+    if ((threadIdx.x & 63) == 0) {
+      part_s[threadIdx.x >> 6] = s;
+      part_w[threadIdx.x >> 6] = ws;
+    }
+    __syncthreads();  // (also: every thread has read `picked` before thread 0 rewrites it for the next group)
+    if (threadIdx.x == 0) {
+      const float st = ((part_s[0] + part_s[1]) + part_s[2]) + part_s[3];
+      const float wt = ((part_w[0] + part_w[1]) + part_w[2]) + part_w[3];
+      logprobs[(int64_t)b * ld_lp + g] = logf(wt) - logf(st);
+    }
+  }
+  float v[2] = {val[0], n_groups == 2 ? val[1] : 0.f};
+  fourier_row(v, n_groups, w, half, feats + (int64_t)b * ldf);
+}
+
 // ---------------------------------------------------------------------------
 // temperature + top-p sampling of one token per sequence.
 //   z = bf16(logit / T);  p = bf16(softmax(z))                          moondream.py:526 (bf16 tensors, fp32 inside)
@@ -896,6 +990,19 @@ extern "C" md_status md_region_pick_encode(const void* logits, int64_t ld, int32
   MD_CHECK_ARG((n_groups == 1 || n_groups == 2) && ld >= (int64_t)n_groups * n_bins && ld_bins >= n_groups && ld_feats >= 2 * half);
   hipLaunchKernelGGL(region_pick_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits, ld, n_groups,
                      n_bins, (const bf16_t*)value_table, (const bf16_t*)feat_w, half, bins, ld_bins, (bf16_t*)feats, ld_feats);
+  return md_launch_status();
+}
+
+extern "C" md_status md_region_pick_encode_scored(const void* logits, int64_t ld, int32_t batch, int32_t n_groups,
+                                                  int32_t n_bins, const void* value_table, const void* feat_w, int32_t half,
+                                                  int32_t* bins, int64_t ld_bins, void* feats, int64_t ld_feats, int32_t window,
+                                                  float* logprobs, int64_t ld_logprobs, void* stream) {
+  MD_CHECK_ARG(logits && value_table && feat_w && bins && feats && batch > 0 && n_bins > 0);
+  MD_CHECK_ARG((n_groups == 1 || n_groups == 2) && ld >= (int64_t)n_groups * n_bins && ld_bins >= n_groups && ld_feats >= 2 * half);
+  MD_CHECK_ARG(logprobs && window >= 0 && ld_logprobs >= n_groups);
+  hipLaunchKernelGGL(region_pick_scored_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits, ld,
+                     n_groups, n_bins, (const bf16_t*)value_table, (const bf16_t*)feat_w, half, bins, ld_bins, (bf16_t*)feats,
+                     ld_feats, window, logprobs, ld_logprobs);
   return md_launch_status();
 }
 

@@ -33,6 +33,28 @@ def check_top_logprobs(top_logprobs: Optional[int], with_logprobs: bool) -> int:
     return k
 
 
+def check_score_settings(settings: Optional[dict], n_bins: int) -> Optional[int]:
+    """The ``return_scores`` / ``score_window`` entries of a detect / point ``settings`` dict -> the window (None: no scores).
+    ValueError for a ``return_scores`` that is not a bool, a ``score_window`` that is not an integer in 0 .. n_bins - 1, or one
+    given without ``return_scores``: host values only, before any GPU work."""
+    st = settings or {}
+    on = st.get("return_scores", False)
+    if not isinstance(on, bool):
+        raise ValueError(f"return_scores must be a bool, not {on!r}")
+    if "score_window" not in st:
+        return 0 if on else None
+    window = st["score_window"]
+    try:
+        w = -1 if isinstance(window, bool) else operator.index(window)
+    except TypeError:
+        w = -1
+    if not 0 <= w < n_bins:
+        raise ValueError(f"score_window must be an integer in 0 .. {n_bins - 1}, not {window!r}")
+    if not on:
+        raise ValueError("score_window widens the scores: it needs return_scores=True")
+    return w
+
+
 PENALTY_SETTINGS = ("repetition_penalty", "presence_penalty", "frequency_penalty")
 PENALTY_NEUTRAL = (1.0, 0.0, 0.0)
 

@@ -31,8 +31,8 @@ from PIL import Image
 from . import _lib
 from .config import MoondreamConfig
 from .crop_staging import CropStager, crop_workers, upload_unique
-from .decode_loop import (DecodeChunk, Penalty, ReasonChunk, Sampling, check_penalties, check_top_logprobs, penalties_of,
-                          refuse_penalties, run_chunk)
+from .decode_loop import (DecodeChunk, Penalty, ReasonChunk, Sampling, check_penalties, check_score_settings, check_top_logprobs,
+                          penalties_of, refuse_penalties, run_chunk)
 from .graph_store import GraphStore
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
@@ -2230,10 +2230,13 @@ class MoondreamModel:
         s = self.encode_size(torch.tensor(sizes, dtype=BF16)) if sizes else None
         return {"coords": c, "sizes": s}
 
-    def _region_pick_encode(self, hidden: torch.Tensor, which: str, bins_out: torch.Tensor) -> torch.Tensor:
+    def _region_pick_encode(self, hidden: torch.Tensor, which: str, bins_out: torch.Tensor,
+                            logprobs_out: Optional[torch.Tensor] = None, window: int = 0) -> torch.Tensor:
         """hidden [B, D] -> next embedding [B, D]: head MLP -> per-sequence argmax bin(s) (written to
         ``bins_out`` [B, 1|2], int32) -> value -> Fourier features -> encoder.  All on the device.
-        reference: moondream.py:672-677 (x), :682-687 (y), :693-713 (size)."""
+        reference: moondream.py:672-677 (x), :682-687 (y), :693-713 (size).
+        ``logprobs_out`` (fp32, the shape of ``bins_out``): the scored kernel instead -- the same bins and features, and
+        the log of the mass the head put within ``window`` bins of each pick (md_region_pick_encode_scored)."""
         r, tabs = self._region()
         b = hidden.shape[0]
         if which == "coord":
@@ -2246,6 +2249,17 @@ class MoondreamModel:
         half = fw.shape[1]
         feats = torch.empty(b, 2 * half, dtype=BF16, device=self._device)
         assert bins_out.dtype == torch.int32 and bins_out.stride(-1) == 1
+        if logprobs_out is not None:
+            assert logprobs_out.dtype == torch.float32 and logprobs_out.stride(-1) == 1 and logprobs_out.shape == bins_out.shape
+            _lib.check(
+                self.lib.md_region_pick_encode_scored(
+                    logits.data_ptr(), logits.stride(0), b, groups, n_bins, table.data_ptr(), fw.data_ptr(), half,
+                    bins_out.data_ptr(), bins_out.stride(0), feats.data_ptr(), feats.stride(0), window,
+                    logprobs_out.data_ptr(), logprobs_out.stride(0), self._stream(),
+                ),
+                "md_region_pick_encode_scored",
+            )
+            return self._lin(feats, enc)
         _lib.check(
             self.lib.md_region_pick_encode(
                 logits.data_ptr(), logits.stride(0), b, groups, n_bins, table.data_ptr(), fw.data_ptr(), half,
@@ -2256,9 +2270,17 @@ class MoondreamModel:
         return self._lin(feats, enc)
 
     def _points_loop(self, hidden: torch.Tensor, first: torch.Tensor, pos: Sequence[int], rows: Union[int, _Rows],
-                     include_size: bool, max_objects: int, run_all: bool = False) -> List[List[dict]]:
+                     include_size: bool, max_objects: int, run_all: bool = False, scores: Optional[Scores] = None,
+                     window: int = 0) -> Tuple[List[List[dict]], Optional[List[Optional[float]]]]:
         """The loop of moondream.py:653-733 for B sequences in lockstep.  hidden [B, D] = last prompt
-        position, first int32 [B] = the token after the prompt, pos[b] = next position, ``rows`` their routing."""
+        position, first int32 [B] = the token after the prompt, pos[b] = next position, ``rows`` their routing.
+        Returns (every row's objects, None), or with scores (.., every row's ``stop_logprob``).
+        ``scores`` (a record over [>= max_objects + 1, B] whose row 0 the prompt pass filled for ``first``): every object
+        dict gains ``"logprobs"`` and ``"score"``, and the second result is each row's ``stop_logprob``.  Row k + 1 of the
+        record takes the decision ``toks[k + 1]`` (one md_token_logprobs launch after the pick: the log-probability of the
+        PICKED token, so of eos in the row the decision ends), a plane laid out like ``bins`` takes what
+        md_region_pick_encode_scored writes at ``window``, and both travel in the one host copy with ``bins`` and ``toks``.
+        Without ``scores`` the launches are the ones of the loop without the feature."""
         b = hidden.shape[0]
         eos = self.config.tokenizer.eos_id
         n_bins = self.config.region.coord_out_dim
@@ -2268,6 +2290,8 @@ class MoondreamModel:
         bins = torch.zeros(max(1, max_objects), b, 4, dtype=torch.int32, device=self._device)
         toks = torch.full((max_objects + 1, b), eos, dtype=torch.int32, device=self._device)
         toks[0] = first
+        lps = torch.zeros(max(1, max_objects), b, 4, dtype=torch.float32, device=self._device) if scores is not None else None
+        lp_at = lambda k, c0, c1: {"logprobs_out": lps[k, :, c0:c1], "window": window} if lps is not None else {}
         pos_host = [int(p) for p in pos]
         pos_dev = torch.tensor(pos_host, dtype=torch.int32, device=self._device)
         hidden = hidden.reshape(b, -1).contiguous()
@@ -2288,22 +2312,32 @@ class MoondreamModel:
                 alive = (toks[: k + 1] != eos).all(dim=0)
                 if not bool(alive.any()):
                     break
-            step(self._region_pick_encode(hidden, "coord", bins[k, :, 0:1]))       # x -> y's hidden state
-            emb = self._region_pick_encode(hidden, "coord", bins[k, :, 1:2])      # y
+            step(self._region_pick_encode(hidden, "coord", bins[k, :, 0:1], **lp_at(k, 0, 1)))       # x -> y's hidden state
+            emb = self._region_pick_encode(hidden, "coord", bins[k, :, 1:2], **lp_at(k, 1, 2))      # y
             if include_size:
                 step(emb)
-                emb = self._region_pick_encode(hidden, "size", bins[k, :, 2:4])    # w, h
+                emb = self._region_pick_encode(hidden, "size", bins[k, :, 2:4], **lp_at(k, 2, 4))    # w, h
             step(emb)
-            toks[k + 1] = self._pick(self._lm_head(hidden.reshape(b, 1, -1)), 0.0, 0.0)  # next token: x again, or eos
+            logits = self._lm_head(hidden.reshape(b, 1, -1))
+            toks[k + 1] = self._pick(logits, 0.0, 0.0)  # next token: x again, or eos
+            if scores is not None:
+                self._token_logprobs(logits, toks[k + 1], -1, scores.logprob[k + 1], scores.rank[k + 1])
             n_done = k + 1
-        bins_h = bins[:n_done].cpu() if n_done else torch.zeros(0, b, 4, dtype=torch.int32)
-        toks_h = toks[: n_done + 1].cpu()
+        if scores is not None:  # bins, toks and both log-probability planes: ONE copy to the host
+            host = scores[: n_done + 1].to_host(bins[:n_done], toks[: n_done + 1], lps[:n_done].view(torch.int32))
+            bins_h, toks_h = (torch.from_numpy(a) for a in host.extra[:2])
+            lps_h, tok_lp = host.extra[2].view(np.float32).astype(np.float64), host.logprob.astype(np.float64)
+        else:
+            bins_h = bins[:n_done].cpu() if n_done else torch.zeros(0, b, 4, dtype=torch.int32)
+            toks_h = toks[: n_done + 1].cpu()
         # host floats exactly as the reference forms them (moondream.py:673,683,699-721)
         xc = (bins_h[..., 0].to(torch.int64) / n_bins)
         yc = (bins_h[..., 1].to(torch.int64) / n_bins)
         wv = torch.pow(2.0, (bins_h[..., 2].float() / 1023.0) * 10.0 - 10.0)
         hv = torch.pow(2.0, (bins_h[..., 3].float() / 1023.0) * 10.0 - 10.0)
         out: List[List[dict]] = []
+        stops: Optional[List[Optional[float]]] = [] if scores is not None else None
+        names = ("object", "x", "y", "w", "h") if include_size else ("object", "x", "y")
         for i in range(b):
             objs = []
             for k in range(n_done):
@@ -2315,8 +2349,15 @@ class MoondreamModel:
                     objs.append({"x_min": x - w / 2, "y_min": y - h / 2, "x_max": x + w / 2, "y_max": y + h / 2})
                 else:
                     objs.append({"x": x, "y": y})
+                if scores is not None:
+                    lp = dict(zip(names, [float(tok_lp[k, i])] + lps_h[k, i, : len(names) - 1].tolist()))
+                    objs[-1].update(logprobs=lp, score=math.exp(math.fsum(lp.values())))
+            if scores is not None:
+                # the decision after the last object: eos ends the list, or max_objects / the context did (then no decision does)
+                n = len(objs)  # <= n_done: toks_h has the row
+                stops.append(float(tok_lp[n, i]) if int(toks_h[n, i]) == eos else None)
             out.append(objs)
-        return out
+        return out, stops
 
     # ------------------------------------------------- reasoning queries in lockstep
     def _region_coord(self) -> _lib.MdRegionCoord:
@@ -2501,11 +2542,12 @@ class MoondreamModel:
         """reference: moondream.py:653-733 (B = 1 form of the lockstep loop; KV slot 0)."""
         with torch.inference_mode():
             first = next_token.reshape(1).to(device=self._device, dtype=torch.int32)
-            return self._points_loop(hidden.reshape(1, -1), first, [pos], 0, include_size, max_objects)[0]
+            return self._points_loop(hidden.reshape(1, -1), first, [pos], 0, include_size, max_objects)[0][0]
 
     def _batch_detect_like(self, images, objects: Sequence[str], kind: str, include_size: bool, settings: Optional[dict],
-                           share_prefix: bool = False):
-        refuse_penalties(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
+                           share_prefix: bool = False) -> List[dict]:
+        """``batch_detect`` / ``batch_point`` (and their one-image forms): the result dicts in the caller's order."""
+        window = self._check_detect_settings(settings, kind)
         tpl = self.config.tokenizer.templates[kind]
         if tpl is None:
             raise NotImplementedError(f"Model does not support {kind}.")
@@ -2516,20 +2558,48 @@ class MoondreamModel:
         marks: list = []
         mark = lambda name: self._mark(marks, name)
         with torch.inference_mode():
+            scores = None
+            if window is not None:  # row 0: the prompt pass's decision, row k + 1: the decision after object k
+                n_rows = max(0, min(max_objects, self.config.text.max_context)) + 1
+                scores = Scores.new((n_rows, len(prompts)), 0, self._device, fill=True)
             prep = self._prepare_sequences(images, prompts, mark, _Rows(lora=lora), share_prefix=share_prefix,
-                                           encode_settings=settings)
-            res = self._points_loop(prep.hidden_last, prep.first, prep.next_pos, prep.rows, include_size, max_objects,
-                                    run_all=bool((settings or {}).get("_run_all_objects", False)))
+                                           encode_settings=settings, scores=scores and scores[0])
+            res, stops = self._points_loop(prep.hidden_last, prep.first, prep.next_pos, prep.rows, include_size, max_objects,
+                                           run_all=bool((settings or {}).get("_run_all_objects", False)), scores=scores,
+                                           window=window or 0)
             mark("points_loop")
         self._phase_times(marks)
-        return prep.in_caller_order(res)
+        key = "objects" if include_size else "points"
+        if stops is None:
+            return [{key: o} for o in prep.in_caller_order(res)]
+        return [{key: o, "stop_logprob": s} for o, s in prep.in_caller_order(list(zip(res, stops)))]
+
+    def _check_detect_settings(self, settings: Optional[dict], kind: str) -> Optional[int]:
+        """The host checks of every detect / point call, before any GPU work: penalties are not served, and the score
+        settings (``check_score_settings``) -> the score window, None without ``return_scores``."""
+        refuse_penalties(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
+        return check_score_settings(settings, self.config.region.coord_out_dim)
 
     def batch_detect(self, images, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
-        """B (image, object) pairs in lockstep; element i == detect(images[i], objects[i])."""
-        return [{"objects": o} for o in self._batch_detect_like(images, objects, "detect", True, settings)]
+        """B (image, object) pairs in lockstep; element i == detect(images[i], objects[i]).
+
+        ``settings={"return_scores": True}`` (here and in ``detect``, ``batch_point`` / ``point``, ``detect_many`` /
+        ``point_many`` and ``batch_detect_pipelined``): every object dict gains ``"logprobs"`` -- ``"object"``, the
+        log-probability of the token that opened the object (the prompt pass's pick for the first, the decision after the
+        previous object for the others: the model's own distribution, md_token_logprobs), and ``"x"``, ``"y"`` (detect:
+        ``"w"``, ``"h"`` too), the log of the mass the region head put within ``score_window`` bins (default 0: on exactly
+        the picked bin) of each pick (md_region_pick_encode_scored) -- and ``"score"`` = exp(their sum), summed on the host in
+        float64: at window 0 the probability the model gave to exactly this object given everything before it.  Every
+        result dict gains ``"stop_logprob"``: log P(eos) at the decision that ended the list, None when ``max_objects`` or
+        the context ended it.  Objects stay in emission order; no box or point changes, and without the setting the
+        dicts, and the launches, are the ones of the call without the feature.  One launch more per object (the eos
+        decision's md_token_logprobs), the scored pick in place of the plain one, the same single copy to the host.
+        ValueError, before any GPU work: ``return_scores`` not a bool, ``score_window`` not an integer in
+        0 .. coord_out_dim - 1, or given without ``return_scores``."""
+        return self._batch_detect_like(images, objects, "detect", True, settings)
 
     def batch_point(self, images, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
-        return [{"points": o} for o in self._batch_detect_like(images, objects, "point", False, settings)]
+        return self._batch_detect_like(images, objects, "point", False, settings)
 
     # ------------------------------------------------ one image, many prompts
     def query_many(self, image, questions: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
@@ -2577,16 +2647,16 @@ class MoondreamModel:
     def detect_many(self, image, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
         """``detect`` of many objects in ONE image over a single copy of its KV prefix.  Element i ==
         ``batch_detect([encode_image(image)] * N, objects)[i]`` (fp8 KV mode included).  LoRA variant: the copy path, same results."""
-        refuse_penalties(settings, "detect: its loop decodes coordinates, not tokens picked from logits")
+        self._check_detect_settings(settings, "detect")
         enc = self.encode_image(image, settings)
-        return [{"objects": o} for o in self._batch_detect_like([enc] * len(objects), objects, "detect", True, settings, True)]
+        return self._batch_detect_like([enc] * len(objects), objects, "detect", True, settings, True)
 
     def point_many(self, image, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
         """``point`` for many objects in ONE image over a single copy of its KV prefix.  Element i ==
         ``batch_point([encode_image(image)] * N, objects)[i]`` (fp8 KV mode included).  LoRA variant: the copy path, same results."""
-        refuse_penalties(settings, "point: its loop decodes coordinates, not tokens picked from logits")
+        self._check_detect_settings(settings, "point")
         enc = self.encode_image(image, settings)
-        return [{"points": o} for o in self._batch_detect_like([enc] * len(objects), objects, "point", False, settings, True)]
+        return self._batch_detect_like([enc] * len(objects), objects, "point", False, settings, True)
 
     def batch_detect_pipelined(self, batches, settings: Optional[dict] = None, kind: str = "detect"):
         """Generator over an iterable of (images, objects) batches; yields ``batch_detect`` / ``batch_point`` (``kind``) of
@@ -2596,7 +2666,7 @@ class MoondreamModel:
         only the first batch's tiling is exposed.  Results are identical to calling ``batch_detect`` per batch."""
         if kind not in ("detect", "point"):
             raise ValueError("kind must be 'detect' or 'point'")
-        refuse_penalties(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
+        self._check_detect_settings(settings, kind)
         run = self.batch_detect if kind == "detect" else self.batch_point
         it = iter(batches)
         cur = next(it, None)
