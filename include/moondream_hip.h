@@ -501,6 +501,39 @@ md_status md_penalize_rows(void* logits, int64_t ld, int32_t batch, int32_t voca
                            const int32_t* slots, int32_t slot0, int32_t* hist, int32_t hist_cap, int32_t* hist_len,
                            const float* repetition, const float* presence, const float* frequency, void* stream);
 
+/* Constrained decoding: every row follows its own deterministic automaton over token ids; the call advances the row's state
+ * by the token it consumed and sets the logits of the tokens the new state forbids to bf16 -inf (0xFF80), so that the pick
+ * that follows cannot produce them.  logits bf16 [batch][ld], updated in place; one workgroup per row, a row's result
+ * independent of the rows beside it.  The table (the caller's device arrays, any number of automata concatenated):
+ *   row_ptr int32 [state_cap + 1], default_next int32 [state_cap], edge_tok / edge_next int32 [row_ptr[state_cap]]:
+ *   state q lists the edges row_ptr[q] .. row_ptr[q + 1], their tokens strictly ascending; a token that is not listed
+ *   goes to default_next[q].  A next value is a state id in [0, state_cap), MD_CONSTRAINT_FREE (the row is unconstrained
+ *   from here on) or MD_CONSTRAINT_FORBID (the token may not be produced in this state).
+ * state int32 [n_slots]: row r uses state[s], s = slots ? slots[r] : slot0 + r (two live rows of one launch never share one).
+ *   s < 0 (idle row), or q = state[s] < 0 (MD_CONSTRAINT_FREE, MD_CONSTRAINT_DEAD): nothing of the row is read or written
+ *     -- not its logits, not its state.
+ *   q >= state_cap: state[s] = MD_CONSTRAINT_DEAD, the logits untouched; nothing is indexed by q.
+ *   Advance (tokens_in != NULL): t = tokens_in[r], the token the row produced last.  q' = edge_next[e] when t is edge e of
+ *     state q (binary search), otherwise default_next[q].  t outside [0, vocab), q' == MD_CONSTRAINT_FORBID, or a q' that
+ *     is no next value (>= state_cap, < MD_CONSTRAINT_FORBID): q' = MD_CONSTRAINT_DEAD.  state[s] = q'; q' < 0: the logits
+ *     are untouched.  tokens_in == NULL: q' = q (the first token, picked from the prompt pass: nothing consumed yet).
+ *   Mask: logit[v] = 0xFF80 for every v in [0, vocab) whose next value in state q' -- its edge's, otherwise the default -- is
+ *     MD_CONSTRAINT_FORBID.  Every other bit of the row is unchanged; columns [vocab, ld) are never written.
+ * Cost: the logits are never loaded.  A default-allow state stores 2 bytes per listed forbidden token.  A default-forbid
+ * state builds a vocab-bit map of its allowed tokens in LDS and sweeps the row with stores alone, 16 bytes at a time
+ * wherever a whole 16-byte-aligned group is forbidden (csrc/sampling_region.hip).  No vocab % 8 / ld % 8 requirement.  No
+ * host sync, no allocation: capturable.  batch == 0: MD_OK, nothing launched.
+ * MD_ERR_INVALID_ARG: NULL logits / state / row_ptr / default_next / edge_tok / edge_next, batch < 0, vocab < 1, ld < vocab,
+ * state_cap < 1, vocab > MD_CONSTRAIN_VOCAB_MAX (the bit map lives in 32 KiB of LDS). */
+#define MD_CONSTRAIN_VOCAB_MAX 262144
+#define MD_CONSTRAINT_FREE (-1)
+#define MD_CONSTRAINT_DEAD (-2)
+#define MD_CONSTRAINT_FORBID (-3)
+md_status md_constrain_rows(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* tokens_in,
+                            const int32_t* slots, int32_t slot0, int32_t* state, const int32_t* row_ptr,
+                            const int32_t* default_next, const int32_t* edge_tok, const int32_t* edge_next,
+                            int32_t state_cap, void* stream);
+
 /* Region head, device resident (reference: region.py:12-71 inside the loop of moondream.py:653-733).
  * md_fourier_features: out[r] = [cos(f) | sin(f)], f = bf16(bf16(2 pi x[r, :in_dim]) . w[in_dim][half])
  *   (region.py:12-29; in_dim 1 for coordinates, 2 for sizes) -- the input of coord_encoder /

@@ -27,6 +27,7 @@ MD_HIDDEN_ALL, MD_HIDDEN_LAST, MD_HIDDEN_NONE = 0, 1, 2  # md_text_forward_trim:
 MD_CROPS_U8_HWC, MD_CROPS_BF16_CHW = 0, 1
 MD_TOPK_MAX = 32  # md_topk_logprobs: the most alternatives per decision
 MD_PENALTY_HIST_MAX = 4096  # md_penalize_rows: the longest history per row
+MD_CONSTRAIN_VOCAB_MAX = 262144  # md_constrain_rows: the largest vocabulary (its bit map lives in LDS)
 
 c_void_p, c_int32, c_int64, c_size_t, c_float = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float
 
@@ -234,6 +235,8 @@ SIGNATURES = {
                                    c_void_p]),
     "md_penalize_rows": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "md_constrain_rows": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_int32, c_void_p]),
     "md_fourier_features": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     "md_region_pick_encode": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                         c_void_p, c_int64, c_void_p, c_int64, c_void_p]),

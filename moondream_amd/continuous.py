@@ -25,7 +25,8 @@ from typing import Callable, Deque, Dict, Iterator, List, Optional, Sequence, Tu
 
 import numpy as np
 
-from .decode_loop import PENALTY_NEUTRAL, DecodeChunk, Penalty, Sampling, check_penalties, check_top_logprobs, run_chunk
+from .constraint import FREE, TokenAutomaton, pack
+from .decode_loop import PENALTY_NEUTRAL, Constraint, DecodeChunk, Penalty, Sampling, check_penalties, check_top_logprobs, run_chunk
 from .scores import HostScores, Scores
 
 DEFAULT_MAX_TOKENS = 768  # moondream.py (the reference's default, moondream.py:50-53)
@@ -33,6 +34,8 @@ DEFAULT_TOP_P = 0.3
 MAX_GRAPHS = 16  # captured decode chunks per (model, stream)
 IDLE_SLOT = -1
 MD_PENALTY_HIST_MAX = 4096  # include/moondream_hip.h
+DEFAULT_CONSTRAINT_STATES = 4096   # the engine's constraint table: states ...
+DEFAULT_CONSTRAINT_EDGES = 65536   # ... and edges, over all the distinct automata its requests ever use
 
 
 def row_buckets(max_live: int) -> List[int]:
@@ -76,6 +79,8 @@ class Request:
     ranks: List[int] = field(default_factory=list)
     alternatives: List[list] = field(default_factory=list)  # of ``ids`` too: k (token_id, logprob) pairs each (top_logprobs=k)
     penalties: Tuple[float, float, float] = PENALTY_NEUTRAL  # (repetition, presence, frequency): md_penalize_rows' rule
+    constraint: Optional[TokenAutomaton] = None  # what the request may generate (md_constrain_rows); None: anything
+    constraint_start: int = FREE  # its start state in the engine's table
 
     @property
     def remaining(self) -> int:
@@ -210,6 +215,19 @@ class SlotScheduler:
                 fresh[i] = r.slot
         return ChunkPlan(rows, bucket, n, slots, tokens, pos, fresh)
 
+    @staticmethod
+    def state_resets(plan: ChunkPlan, spare: int) -> Tuple[np.ndarray, np.ndarray]:
+        """The constraint states a chunk starts from: (slot int64 [bucket], state int32 [bucket]) -- a row whose request
+        takes its first decode step here (``plan.fresh``: its slot has just been refilled, and still holds the state its
+        last occupant left) gets its request's start state, FREE for a request without an automaton; every other row
+        writes FREE to the ``spare`` entry nobody reads."""
+        idx = np.where(plan.fresh >= 0, plan.fresh, spare).astype(np.int64)
+        val = np.full(plan.bucket, FREE, dtype=np.int32)
+        for i, r in enumerate(plan.rows):
+            if plan.fresh[i] >= 0:
+                val[i] = r.constraint_start
+        return idx, val
+
     def commit(self, plan: ChunkPlan, out: np.ndarray, logprobs: Optional[np.ndarray] = None,
                ranks: Optional[np.ndarray] = None, top_ids: Optional[np.ndarray] = None,
                top_logprobs: Optional[np.ndarray] = None) -> List[Request]:
@@ -299,10 +317,21 @@ class ContinuousEngine:
     one more pinned H2D copy that only chunks with a penalised row make, no synchronisation).  Such chunks run
     md_penalize_rows before each pick and are graphs of their own; chunks whose rows are all neutral take the graph of
     an engine without penalties.  A request's ids depend on its own settings and seed only; with ``logprobs`` its scores
-    are those of the penalised logits."""
+    are those of the penalised logits.
+
+    ``constraint`` per request (``submit``; a ``TokenAutomaton``, None: free): ``batch_generate_ids``' rule, and its greedy
+    ids bit for bit.  The engine owns ONE table of ``constraint_states`` states and ``constraint_edges`` edges for its
+    lifetime and a state per KV slot, all made on first use.  The first request that uses an automaton (by identity) has
+    it appended to the table: room is taken at ``submit`` (ValueError when the table is full), the rows are copied behind
+    the stream before the request's prefill.  A refilled slot's state is set to its request's start state (FREE for a
+    free request) in the request's first chunk (``SlotScheduler.state_resets``: two small pinned copies and one
+    index_copy_ on the stream, made by every chunk once the engine has seen a constraint).  Chunks with a constrained
+    row run md_constrain_rows before each pick and are graphs of their own; all others take the graph of an engine
+    without constraints."""
 
     def __init__(self, model, max_live: int = 64, chunk: int = 16, temperature: float = 0.0, top_p: float = DEFAULT_TOP_P,
-                 admit_threshold: Optional[int] = None, logprobs: bool = False, top_logprobs: Optional[int] = None):
+                 admit_threshold: Optional[int] = None, logprobs: bool = False, top_logprobs: Optional[int] = None,
+                 constraint_states: int = DEFAULT_CONSTRAINT_STATES, constraint_edges: int = DEFAULT_CONSTRAINT_EDGES):
         self.model = model
         self.logprobs = bool(logprobs)
         self.top_logprobs = check_top_logprobs(top_logprobs, self.logprobs)
@@ -314,6 +343,14 @@ class ContinuousEngine:
         t = model.config.text
         self.sched = SlotScheduler(self.max_live, t.max_context, self.chunk, admit_threshold)
         self._next_rid = 0
+        if int(constraint_states) < 1 or int(constraint_edges) < 1:
+            raise ValueError("constraint_states and constraint_edges must be >= 1")
+        self.constraint_states, self.constraint_edges = int(constraint_states), int(constraint_edges)
+        self._con_start: Dict[int, Tuple[TokenAutomaton, int]] = {}  # id(automaton) -> (it, its start state in the table)
+        self._con_used = [0, 0]    # states and edges taken
+        self._con_pending: List[TokenAutomaton] = []  # registered, rows not yet on the device (in table order)
+        self._con_uploaded = [0, 0]
+        self._con_table = None     # (row_ptr, default_next, edge_tok, edge_next, state int32 [max_live + 1]), made on first use
         self._penalty_hist = None  # (hist int32 [max_live + 1, max_context], hist_len int32 [max_live + 1]), made on first use
 
     @property
@@ -324,10 +361,12 @@ class ContinuousEngine:
     def submit(self, image, prompt_ids: Sequence[int], max_tokens: int = DEFAULT_MAX_TOKENS, eos_id: Optional[int] = None,
                seed: Optional[int] = None, ignore_eos: bool = False, variant: Optional[str] = None,
                temperature: Optional[float] = None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
-               presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None) -> int:
+               presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
+               constraint: Optional[TokenAutomaton] = None) -> int:
         """Queue one request; ``image`` is a PIL image or an EncodedImage.  ``eos_id`` None: the tokenizer's EOS
         (``ignore_eos``: none).  ``temperature`` / ``top_p`` None: the engine's.  The three penalties (None: neutral):
-        one number each, ``batch_generate_ids``' rule and validation.  Returns its id."""
+        one number each, ``batch_generate_ids``' rule and validation.  ``constraint``: one ``TokenAutomaton`` (None: free),
+        ``batch_generate_ids``' rule and validation; ValueError when the engine's table has no room for it.  Returns its id."""
         from PIL import Image
 
         from .moondream import EncodedImage
@@ -354,11 +393,31 @@ class ContinuousEngine:
             raise ValueError(f"image prefix + prompt ({prefix + len(prompt)} positions) do not fit the {t.max_context}-slot context")
         eos = None if ignore_eos else (self.model.config.tokenizer.eos_id if eos_id is None else int(eos_id))
         vidx = -1 if variant is None else self._variant_index(variant)
+        start = FREE if constraint is None else self._register_constraint(constraint)  # (last: nothing fails after it)
         rid = self._next_rid
         self._next_rid += 1
         self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed, variant=vidx, temperature=temp, top_p=tp,
-                                  penalties=pen[0] if pen else PENALTY_NEUTRAL))
+                                  penalties=pen[0] if pen else PENALTY_NEUTRAL, constraint=constraint, constraint_start=start))
         return rid
+
+    def _register_constraint(self, a: TokenAutomaton) -> int:
+        """The start state of ``a`` in the engine's table, taking room for it on first use (by identity; the engine keeps
+        the object).  Host values only: ValueError for what is no valid automaton of this model, or when the table is full."""
+        if not isinstance(a, TokenAutomaton):
+            raise ValueError(f"constraint must be a TokenAutomaton or None, not {a!r}")
+        known = self._con_start.get(id(a))
+        if known is not None:
+            return known[1]
+        a.validate(self.model.config.text.vocab_size, self.model.config.tokenizer.answer_id)
+        states, edges = self._con_used
+        if states + a.n_states > self.constraint_states or edges + a.n_edges > self.constraint_edges:
+            raise ValueError(f"the engine's constraint table is full: {states} + {a.n_states} states of {self.constraint_states}, "
+                             f"{edges} + {a.n_edges} edges of {self.constraint_edges} (ContinuousEngine(constraint_states=, "
+                             "constraint_edges=))")
+        self._con_start[id(a)] = (a, states)
+        self._con_used = [states + a.n_states, edges + a.n_edges]
+        self._con_pending.append(a)
+        return states
 
     def _variant_index(self, variant: str) -> int:
         """The bank index of a LoRA variant the model can resolve (registered, or in the on-disk cache); ValueError otherwise,
@@ -447,9 +506,11 @@ class ContinuousEngine:
                  top_p: Union[None, float, Sequence[float]] = None, return_logprobs: bool = False,
                  repetition_penalty: Union[None, float, Sequence[float]] = None,
                  presence_penalty: Union[None, float, Sequence[float]] = None,
-                 frequency_penalty: Union[None, float, Sequence[float]] = None):
+                 frequency_penalty: Union[None, float, Sequence[float]] = None,
+                 constraints: Union[None, TokenAutomaton, Sequence[Optional[TokenAutomaton]]] = None):
         """Ids for (images[i], prompts[i]) in input order; ``max_tokens`` one int or one per request, ``temperature`` and
-        ``top_p`` one float or one per request (None: the engine's), the three penalties likewise (None: neutral).  ``return_logprobs`` (an engine made with
+        ``top_p`` one float or one per request (None: the engine's), the three penalties likewise (None: neutral),
+        ``constraints`` one ``TokenAutomaton`` or one entry per request (None: free).  ``return_logprobs`` (an engine made with
         ``logprobs=True``): (ids, logprobs, ranks), each in input order; an engine with ``top_logprobs``: alternatives too."""
         if return_logprobs and not self.logprobs:
             raise ValueError("generate(return_logprobs=True) needs ContinuousEngine(..., logprobs=True)")
@@ -470,9 +531,12 @@ class ContinuousEngine:
             return x
 
         temps, tps = per_request(temperature, "temperature"), per_request(top_p, "top_p")
+        cons = [constraints] * n if constraints is None or isinstance(constraints, TokenAutomaton) else list(constraints)
+        if len(cons) != n:
+            raise ValueError(f"constraints: {len(cons)} entries for {n} requests (one TokenAutomaton, or one entry per request)")
         pens = check_penalties(repetition_penalty, presence_penalty, frequency_penalty, n) or [PENALTY_NEUTRAL] * n
-        rids = [self.submit(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant, temps[i], tps[i], *pens[i])
-                for i in range(n)]
+        rids = [self.submit(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant, temps[i], tps[i], *pens[i],
+                            constraint=cons[i]) for i in range(n)]
         if return_logprobs:  # (ids, logprobs, ranks), and alternatives on an engine with top_logprobs
             got3 = {rid: rest for rid, *rest in self.run(with_logprobs=True)}
             return tuple([got3[r][k] for r in rids] for k in range(4 if self.top_logprobs else 3))
@@ -531,8 +595,11 @@ class ContinuousEngine:
                 draws = [float(self._uniforms(r, 1)[0]) if r.temperature != 0 else 0.0 for r in part]
                 st_d = m._h2d(torch.tensor([[r.temperature for r in part], [r.top_p for r in part], draws], dtype=torch.float32))
                 pick = Sampling(st_d[0], st_d[1])
+            con = None
+            if any(r.constraint is not None for r in part):  # these rows' start states, beside the engine's table
+                con = self._constraint(m._h2d(torch.tensor([r.constraint_start for r in part], dtype=torch.int32)), by_slot=False)
             first[i0:i1] = m._first_token(m._lm_head(hidden[i0:i1]), pick, uniforms=st_d[2] if pick is not None else None,
-                                          scores=scores and scores[i0:i1])
+                                          scores=scores and scores[i0:i1], constraint=con)
         if scores is None:
             return [(f,) for f in first.tolist()]
         host = scores.to_host(first)  # the tokens and their scores in one copy
@@ -637,6 +704,44 @@ class ContinuousEngine:
 
         return self._penalty_hist + m._store.fixed("continuous_penalty", bucket, make)
 
+    def _constraint(self, state=None, by_slot: bool = True) -> Constraint:
+        """The engine's table as a ``Constraint`` record over ``state`` (None: the per-slot states), made on first use;
+        the rows of automata registered since the last call are appended first, by small pinned copies behind the stream."""
+        import torch
+
+        m = self.model
+        if self._con_table is None:
+            s, e = self.constraint_states, self.constraint_edges
+            z = lambda n, fill=0: torch.full((n,), fill, dtype=torch.int32, device=m.device)
+            self._con_table = (z(s + 1), z(s, FREE), z(e), z(e), z(self.max_live + 1, FREE))
+        row_ptr, default_next, edge_tok, edge_next, slot_state = self._con_table
+        if self._con_pending:
+            s0, e0 = self._con_uploaded
+            t = pack(self._con_pending, s0, e0)
+            up = lambda dst, at, src: dst[at : at + len(src)].copy_(m._h2d(torch.from_numpy(src))) if len(src) else None
+            up(row_ptr, s0 + 1, t.row_ptr[1:])  # (entry s0 is the end of what was there: e0, or the 0 the table starts with)
+            up(default_next, s0, t.default_next)
+            up(edge_tok, e0, t.edge_tok)
+            up(edge_next, e0, t.edge_next)
+            self._con_uploaded = [s0 + t.n_states, e0 + t.n_edges]
+            self._con_pending = []
+        return Constraint(row_ptr, default_next, edge_tok, edge_next, slot_state if state is None else state,
+                          self.constraint_states, by_slot=by_slot)
+
+    def _constraint_buffers(self, bucket: int):
+        """Per bucket, fixed addresses: the slots (int64 [bucket]) and start states (int32 [bucket]) of a chunk's state
+        resets, each with its pinned staging."""
+        import torch
+
+        def make():
+            with torch.inference_mode(False):
+                i_host = torch.zeros(bucket, dtype=torch.int64, pin_memory=True)
+                v_host = torch.zeros(bucket, dtype=torch.int32, pin_memory=True)
+            return (torch.zeros(bucket, dtype=torch.int64, device=self.model.device), i_host,
+                    torch.zeros(bucket, dtype=torch.int32, device=self.model.device), v_host)
+
+        return self.model._store.fixed("continuous_constraint", bucket, make)
+
     def _score_buffers(self, bucket: int):
         """The fixed-address ``Scores`` over (chunk, bucket) with the engine's k that a chunk's steps fill (``logprobs`` only)."""
         return self.model._store.fixed("continuous_scores", (self.chunk, bucket, self.top_logprobs),
@@ -691,6 +796,18 @@ class ContinuousEngine:
             rs_dev.copy_(rs_host, non_blocking=True)
             p_len.index_fill_(0, rs_dev, 0)
             penalty = Penalty(st_dev[:B], st_dev[B : 2 * B], st_dev[2 * B :], p_hist, p_len, p_hist.shape[1], by_slot=True)
+        constraint = None
+        if self._con_start:
+            # once the engine has seen an automaton every refilled slot's state is rewritten, a free request's too (FREE):
+            # a later chunk may run the constraint launch over this slot.  Only chunks with a constrained row launch it.
+            con = self._constraint()
+            i_dev, i_host, v_dev, v_host = self._constraint_buffers(B)
+            i_host.numpy()[:], v_host.numpy()[:] = SlotScheduler.state_resets(plan, self.max_live)
+            i_dev.copy_(i_host, non_blocking=True)
+            v_dev.copy_(v_host, non_blocking=True)
+            con.state.index_copy_(0, i_dev, v_dev)
+            if any(r.constraint is not None for r in plan.rows):
+                constraint = con
         scores = self._score_buffers(B) if self.logprobs else None  # (an idle or padding row's are never read: SlotScheduler.commit)
         # step i's routing: row i of the slot table; a LoRA row in the chunk: the chunk's row-variant table with it
         rows_of = lambda i: self._rows(slots_d[i], var_d if lora else None)
@@ -698,7 +815,8 @@ class ContinuousEngine:
         # nothing); the settings are device data, in the allocation of the uniforms
         pick = Sampling(u_dev[c * B : c * B + B], u_dev[c * B + B :]) if sample else None
         chunk = DecodeChunk(B, hist, pos_d, rows_of, m.config.tokenizer.answer_id, self._decode_ws_bytes(B), pick,
-                            u_dev[: c * B].view(c, B), penalty=penalty, **(scores.chunk_fields() if scores else {}))
+                            u_dev[: c * B].view(c, B), penalty=penalty, constraint=constraint,
+                            **(scores.chunk_fields() if scores else {}))
         stream = torch.cuda.current_stream(m.device).cuda_stream if m.use_graphs else None
         if run_chunk(m, chunk, n, "continuous", stream, lambda: m._store.count("continuous", stream) < MAX_GRAPHS):
             self.stats.graph_captures += 1

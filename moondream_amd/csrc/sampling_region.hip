@@ -962,6 +962,94 @@ __global__ __launch_bounds__(PENALTY_THREADS) void penalize_rows_kernel(
 }
 }  // namespace
 
+// ---------------------------------------------------------------------------
+// Constrained decoding: a deterministic automaton over token ids per row, advanced by the token the row consumed and
+// applied to the logits it picks from next (md_constrain_rows).  One workgroup per row.  Every thread reads the row's
+// state and walks the same (wave-uniform) binary search over the state's sorted edges, so nothing is broadcast; after a
+// barrier thread 0 stores the new state.  The mask only STORES bf16 -inf: the row is never loaded.
+//   default-allow state: one 2-byte store per listed forbidden token.
+//   default-forbid state: the edges that allow a token set its bit in a vocab-bit map in LDS; the sweep then walks the
+//     row in 16-byte groups aligned in MEMORY (the row may start anywhere: no ld % 8 requirement), one 16-byte store
+//     for a whole group without an allowed token, 2-byte stores in a group that has one and in the clipped groups at the
+//     row's two ends.
+namespace {
+constexpr int CONSTRAIN_THREADS = 256;
+constexpr bf16_t BF16_NEG_INF = 0xFF80;
+
+__global__ __launch_bounds__(CONSTRAIN_THREADS) void constrain_rows_kernel(
+    bf16_t* __restrict__ logits, int64_t ld, int vocab, const int32_t* __restrict__ tokens_in, const int32_t* __restrict__ slots,
+    int slot0, int32_t* state, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ default_next,
+    const int32_t* __restrict__ edge_tok, const int32_t* __restrict__ edge_next, int state_cap) {
+  extern __shared__ __attribute__((aligned(16))) unsigned constrain_allowed[];  // [ceil(vocab / 32)] bit v: token v allowed
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int slot = slots ? slots[r] : slot0 + r;
+  if (slot < 0) return;  // idle: nothing read, nothing written (the whole workgroup leaves, before any barrier)
+  int q = state[slot];
+  if (q < 0) return;  // FREE or DEAD: the row is left alone
+  __syncthreads();    // every thread has read the state before thread 0 replaces it
+  if (q >= state_cap) {  // no state of this table: never an index
+    if (tid == 0) state[slot] = MD_CONSTRAINT_DEAD;
+    return;
+  }
+  if (tokens_in) {  // ---- advance by the token the row consumed
+    const int t = tokens_in[r];
+    int nxt = default_next[q];
+    int lo = row_ptr[q], hi = row_ptr[q + 1];
+    while (lo < hi) {  // the first edge whose token is >= t
+      const int mid = (lo + hi) >> 1;
+      if (edge_tok[mid] < t) lo = mid + 1; else hi = mid;
+    }
+    if (lo < row_ptr[q + 1] && edge_tok[lo] == t) nxt = edge_next[lo];
+    // a token that is no id, a forbidden one, or a next value that is no state of this table: the row is dead
+    if (t < 0 || t >= vocab || nxt == MD_CONSTRAINT_FORBID || nxt >= state_cap || nxt < MD_CONSTRAINT_FORBID) nxt = MD_CONSTRAINT_DEAD;
+    q = nxt;
+    if (tid == 0) state[slot] = q;
+    if (q < 0) return;
+  }
+  // ---- mask the row for state q
+  bf16_t* lr = logits + (int64_t)r * ld;
+  const int e0 = row_ptr[q], e1 = row_ptr[q + 1];
+  if (default_next[q] != MD_CONSTRAINT_FORBID) {
+    for (int e = e0 + tid; e < e1; e += CONSTRAIN_THREADS) {
+      const int v = edge_tok[e];
+      if (edge_next[e] == MD_CONSTRAINT_FORBID && v >= 0 && v < vocab) lr[v] = BF16_NEG_INF;
+    }
+    return;
+  }
+  const int words = (vocab + 31) >> 5;
+  for (int w = tid; w < words; w += CONSTRAIN_THREADS) constrain_allowed[w] = 0u;
+  __syncthreads();
+  for (int e = e0 + tid; e < e1; e += CONSTRAIN_THREADS) {
+    const int v = edge_tok[e];
+    if (edge_next[e] != MD_CONSTRAINT_FORBID && v >= 0 && v < vocab) atomicOr(&constrain_allowed[v >> 5], 1u << (v & 31));
+  }
+  __syncthreads();
+  // group g covers the elements [8 g - a, 8 g - a + 8) of the row, a = the row's offset (in elements) into its 16-byte line
+  const int a = (int)(((uintptr_t)lr >> 1) & 7);
+  const int groups = (vocab + a + 7) >> 3;
+  const uint4 wide = make_uint4(0xFF80FF80u, 0xFF80FF80u, 0xFF80FF80u, 0xFF80FF80u);
+  for (int g = tid; g < groups; g += CONSTRAIN_THREADS) {
+    const int v0 = 8 * g - a;
+    if (v0 >= 0 && v0 + 8 <= vocab) {
+      const int w = v0 >> 5, sh = v0 & 31;
+      unsigned bits = constrain_allowed[w] >> sh;
+      if (sh > 24) bits |= constrain_allowed[w + 1] << (32 - sh);  // (v0 + 7 < vocab: word w + 1 exists)
+      bits &= 0xFFu;
+      if (bits == 0u) {
+        *reinterpret_cast<uint4*>(lr + v0) = wide;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (!((bits >> j) & 1u)) lr[v0 + j] = BF16_NEG_INF;
+      }
+    } else {  // clipped at one of the row's ends
+      for (int v = max(v0, 0); v < min(v0 + 8, vocab); ++v)
+        if (!((constrain_allowed[v >> 5] >> (v & 31)) & 1u)) lr[v] = BF16_NEG_INF;
+    }
+  }
+}
+}  // namespace
+
 // internal (api.hip): the mask that also advances pos
 md_status md_mask_logits_advance(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* ids, int32_t* pos,
                                  hipStream_t stream) {
@@ -1059,5 +1147,18 @@ extern "C" md_status md_penalize_rows(void* logits, int64_t ld, int32_t batch, i
   hipLaunchKernelGGL(penalize_rows_kernel, dim3(batch), dim3(PENALTY_THREADS), (size_t)table_cap * 8, (hipStream_t)stream,
                      (bf16_t*)logits, ld, vocab, tokens_in, slots, slot0, hist, hist_cap, hist_len, repetition, presence,
                      frequency, table_cap);
+  return md_launch_status();
+}
+
+extern "C" md_status md_constrain_rows(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* tokens_in,
+                                       const int32_t* slots, int32_t slot0, int32_t* state, const int32_t* row_ptr,
+                                       const int32_t* default_next, const int32_t* edge_tok, const int32_t* edge_next,
+                                       int32_t state_cap, void* stream) {
+  MD_CHECK_ARG(logits && state && row_ptr && default_next && edge_tok && edge_next);
+  MD_CHECK_ARG(batch >= 0 && vocab >= 1 && ld >= vocab && state_cap >= 1 && vocab <= MD_CONSTRAIN_VOCAB_MAX);
+  if (batch == 0) return MD_OK;
+  const size_t lds = (size_t)((vocab + 127) / 128) * 16;  // one bit per token, in whole 16-byte pieces: <= 32 KiB
+  hipLaunchKernelGGL(constrain_rows_kernel, dim3(batch), dim3(CONSTRAIN_THREADS), lds, (hipStream_t)stream, (bf16_t*)logits, ld,
+                     vocab, tokens_in, slots, slot0, state, row_ptr, default_next, edge_tok, edge_next, state_cap);
   return md_launch_status();
 }

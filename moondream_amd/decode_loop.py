@@ -1,8 +1,8 @@
 """What the lockstep loop (``MoondreamModel._decode_greedy_impl``) and the continuous engine (``ContinuousEngine._step``)
 share: the description of a chunk of consecutive decode steps over fixed buffers, and the one runner that launches it.
 ``run_chunk`` holds the only step body of the package -- decode step (or, for a reasoning query, the reasoning step), then
-the optional penalty launch, then the optional sampling pick, then the optional log-probability launch and the optional
-top-k launch -- and the only decode graph key.  No torch here: the runner moves no data, it orders launches."""
+the optional penalty launch, then the optional constraint launch, then the optional sampling pick, then the optional
+log-probability launch and the optional top-k launch -- and the only decode graph key.  No torch here: the runner moves no data, it orders launches."""
 from __future__ import annotations
 
 import math
@@ -126,6 +126,28 @@ class Penalty:
 
 
 @dataclass(frozen=True, eq=False)
+class Constraint:
+    """The constraint state of a chunk (md_constrain_rows), all device memory at fixed addresses.  ``row_ptr`` (int32
+    [state_cap + 1]), ``default_next`` (int32 [state_cap]), ``edge_tok`` and ``edge_next`` (int32 [edge_cap]) are the
+    packed table of the call's automata (moondream_amd/constraint.py: ``pack``).  ``state`` (int32 [n]) holds each row's
+    current state (FREE: an unconstrained row) and is advanced by every step: row r's entry is row r's own, or,
+    ``by_slot``, that of its KV slot ``rows.slots[r]`` (the continuous engine; a row of slot -1 is idle)."""
+
+    row_ptr: Any
+    default_next: Any
+    edge_tok: Any
+    edge_next: Any
+    state: Any
+    state_cap: int
+    by_slot: bool = False
+
+    def key(self) -> tuple:
+        """What a captured chunk bakes in of the constraint state: addresses, the capacity and whose state a row's is."""
+        return ("constraint",) + tuple(t.data_ptr() for t in (self.row_ptr, self.default_next, self.edge_tok, self.edge_next,
+                                                             self.state)) + (int(self.state_cap), bool(self.by_slot))
+
+
+@dataclass(frozen=True, eq=False)
 class Sampling:
     """How tokens are sampled (``None`` where one is expected: greedy): the reference's temperature / top-p rule with one
     uniform per (token, sequence).  Two floats are a whole call's settings: the uniforms come from ``generator`` (a device
@@ -192,7 +214,11 @@ class DecodeChunk:
     row's logits take its penalties (md_penalize_rows).  The fused step's own argmax was taken from the raw logits, so
     such a chunk always picks again -- with ``pick`` None by the argmax launch -- and the log-probabilities and
     alternatives are those of the PENALISED logits, the distribution the token was picked from before temperature and
-    top-p (every greedy token still has rank 0).  Not with ``b1`` or ``reason``."""
+    top-p (every greedy token still has rank 0).  Not with ``b1`` or ``reason``.
+    ``constraint`` (``Constraint``): after each step (and its penalties) and before its pick, every row's automaton is
+    advanced by the token the step consumed and the tokens its new state forbids lose their logits (md_constrain_rows).
+    Such a chunk always picks again too, and its log-probabilities and alternatives are those of the MASKED logits: a
+    greedy token has rank 0 and an alternative outside the allowed set carries -inf.  Not with ``b1`` or ``reason``."""
 
     b: int
     tokens: Any
@@ -208,6 +234,7 @@ class DecodeChunk:
     reason: Optional[ReasonChunk] = None
     topk: Optional[Tuple[Any, Any]] = None
     penalty: Optional[Penalty] = None
+    constraint: Optional[Constraint] = None
 
 
 def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_stream: Optional[int] = None,
@@ -216,7 +243,7 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     stream: the chunk is replayed from the graph captured for it on that stream, or, first, run eagerly and captured
     (``model._replay_or_capture``: its ``GraphStore``'s, ``may_capture`` too).  The key starts (``tag``, stream) and names everything
     the launches bake in.  Returns True when it captured.  Besides that, the model gives the buffers (_decode_logits, _workspace,
-    _kv_struct) and the launches (_decode_step, _decode_step_b1, _decode_step_reason, _penalize, _pick, _pick_rows, _token_logprobs, _topk_logprobs)."""
+    _kv_struct) and the launches (_decode_step, _decode_step_b1, _decode_step_reason, _penalize, _constrain, _pick, _pick_rows, _token_logprobs, _topk_logprobs)."""
     c = chunk
     pieces = c.step is not None
     assert c.reason is None or (not pieces and not c.b1 and c.logprobs is None and c.pick is not None and c.pick.per_row)
@@ -224,6 +251,7 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     assert not c.b1 or (c.b == 1 and c.pick is None)
     assert c.topk is None or c.logprobs is not None
     assert c.penalty is None or (not c.b1 and c.reason is None)
+    assert c.constraint is None or (not c.b1 and c.reason is None)
     if not pieces:
         logits = model._decode_logits(c.b)
         ws = model._workspace(c.ws_bytes, 2)
@@ -232,8 +260,8 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     lp, rk = c.logprobs if c.logprobs is not None else (None, None)
     tk_ids, tk_lp = c.topk if c.topk is not None else (None, None)
     by_row = c.pick is not None and c.pick.per_row
-    # penalised logits are picked from again: the fused step's argmax saw the raw ones
-    again = c.pick if c.pick is not None or c.penalty is None else Sampling(0.0, 0.0)
+    # penalised or masked logits are picked from again: the fused step's argmax saw the raw ones
+    again = c.pick if c.pick is not None or (c.penalty is None and c.constraint is None) else Sampling(0.0, 0.0)
 
     def body():
         for i in range(n):
@@ -250,6 +278,8 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
             lg = c.step(tok_in) if pieces else left
             if c.penalty is not None:  # tok_in joins each row's history, whose tokens' logits are penalised in place
                 model._penalize(lg, tok_in, c.rows_of(i), c.penalty)
+            if c.constraint is not None:  # tok_in advances each row's automaton, whose new state masks the logits in place
+                model._constrain(lg, tok_in, c.rows_of(i), c.constraint)
             # a fused step wrote its argmax to tok_out: a pick draws from the logits it left instead (of per-row settings,
             # a greedy row takes the same argmax again and an idle row keeps what is there)
             if by_row:
@@ -282,4 +312,6 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
         key += c.reason.key()
     if c.penalty is not None:  # and another with the penalty launches
         key += c.penalty.key()
+    if c.constraint is not None:  # and another with the constraint launches
+        key += c.constraint.key()
     return model._replay_or_capture(key, body, may_capture=may_capture)

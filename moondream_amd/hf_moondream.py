@@ -19,6 +19,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .config import MoondreamConfig
+from .constraint import refuse_constraints
 from .decode_loop import refuse_penalties
 from .moondream import MoondreamModel
 
@@ -71,8 +72,9 @@ class HfMoondream:
         """reference: hf_moondream.py:83-97 -- ``query(image, question)["answer"].strip()`` with the
         model's default sampling settings; ``tokenizer`` / ``chat_history`` / ``max_new_tokens`` are
         ignored there too.  Extension: ``settings=`` is forwarded to ``query`` (e.g. temperature 0); the penalty settings
-        are not part of this wrapper's calls (ValueError for a non-neutral one)."""
+        are not part of this wrapper's calls (ValueError for a non-neutral one), nor are ``constraints``."""
         refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
+        refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         answer = self.query(image_embeds, question, settings=kwargs.get("settings"))["answer"].strip()
         if result_queue is not None:
             result_queue.put(answer)
@@ -84,6 +86,7 @@ class HfMoondream:
         token counts share it), every sequence sampling with the same rule and its own uniforms (round 6; rounds 1-5 forced
         greedy).  ``settings={"temperature": 0}`` is the greedy form; ``max_new_tokens`` bounds the answers."""
         refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
+        refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         self._setup_caches()
         settings = dict(kwargs.get("settings") or {})
         settings.setdefault("max_tokens", kwargs.get("max_new_tokens", kwargs.get("max_tokens", 256)))
@@ -100,6 +103,7 @@ class HfMoondream:
         """reference: hf_moondream.py:112-142.  A prompt in the legacy "<image>\\n\\nQuestion: ..\\n\\nAnswer:"
         form is a ``query``; anything else is tokenised and continued as is after the image prefix."""
         refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
+        refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         q = extract_question(prompt)
         if q is not None:
             return [self.model_query(image_embeds, q)]

@@ -30,8 +30,9 @@ from PIL import Image
 
 from . import _lib
 from .config import MoondreamConfig
+from .constraint import FREE, TokenAutomaton, check_constraints, pack, pow2_at_least, refuse_constraints
 from .crop_staging import CropStager, crop_workers, upload_unique
-from .decode_loop import (DecodeChunk, Penalty, ReasonChunk, Sampling, check_penalties, check_score_settings, check_top_logprobs,
+from .decode_loop import (Constraint, DecodeChunk, Penalty, ReasonChunk, Sampling, check_penalties, check_score_settings, check_top_logprobs,
                           penalties_of, refuse_penalties, run_chunk)
 from .graph_store import GraphStore
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
@@ -182,6 +183,7 @@ class Prepared:
     next_pos: List[int]
     rows: _Rows                # the routing the decode loop must use
     sampling: Optional[Sampling]  # the caller's; on the shared route with ``row_perm`` set
+    constraint: Optional[Constraint] = None  # the rows' automata, each past its first token's mask (None: every row free)
 
     def in_caller_order(self, per_row: Sequence) -> list:
         out = [None] * len(self.order)
@@ -1054,6 +1056,62 @@ class MoondreamModel:
         hist_len.zero_()
         return Penalty(st[0], st[1], st[2], hist, hist_len, cap)
 
+    def _constrain(self, logits: torch.Tensor, tok_in: Optional[torch.Tensor], rows: "_Rows", con: Constraint, row0: int = 0):
+        """Every row's automaton in ``con`` is advanced by its consumed token ``tok_in[r]`` (device int32 [B]; None: nothing
+        consumed yet, the first token's mask) and the logits [B, V] of the tokens its new state forbids become -inf in
+        place: md_constrain_rows.  Row r's state is entry ``row0 + r``, or (``con.by_slot``) that of its KV slot in
+        ``rows``; an idle, free or dead row is left alone.  Nothing is allocated and nothing synchronises: capturable."""
+        b, v = logits.shape
+        assert tok_in is None or (tok_in.dtype == torch.int32 and tok_in.is_contiguous() and tok_in.numel() == b
+                                  and tok_in.device == logits.device)
+        for t in (con.row_ptr, con.default_next, con.edge_tok, con.edge_next, con.state):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == logits.device
+        assert con.row_ptr.numel() == con.state_cap + 1 and con.default_next.numel() == con.state_cap
+        slots = rows.slots if con.by_slot else None
+        assert slots is not None or con.state.numel() >= row0 + b
+        _lib.check(
+            self.lib.md_constrain_rows(logits.data_ptr(), logits.stride(0), b, v, tok_in.data_ptr() if tok_in is not None else None,
+                                       slots.data_ptr() if slots is not None else None, row0, con.state.data_ptr(),
+                                       con.row_ptr.data_ptr(), con.default_next.data_ptr(), con.edge_tok.data_ptr(),
+                                       con.edge_next.data_ptr(), con.state_cap, self._stream()),
+            "md_constrain_rows",
+        )
+
+    def _constraint_record(self, rows: Optional[Sequence[Optional[TokenAutomaton]]]) -> Optional[Constraint]:
+        """``check_constraints``' entries, one per row in the decode loop's row order -> the ``Constraint`` record of a
+        lockstep decode with every row in its start state and a free row FREE (None for None).  The call's DISTINCT automata
+        (by identity) are packed into one table.  The buffers are the store's, one set per (row count, state capacity,
+        edge capacity) with the capacities rounded up to powers of two: calls with tables of similar size share their
+        addresses and with them their captured chunks.  One pinned copy uploads states and table together."""
+        if rows is None:
+            return None
+        distinct: Dict[int, TokenAutomaton] = {}
+        for a in rows:
+            if a is not None:
+                distinct.setdefault(id(a), a)
+        table = pack(list(distinct.values()))
+        start = dict(zip(distinct, table.starts))
+        b, s_cap, e_cap = len(rows), pow2_at_least(table.n_states), pow2_at_least(table.n_edges)
+        buf = self._store.fixed("constraint", (b, s_cap, e_cap), lambda: torch.empty(
+            b + 2 * s_cap + 1 + 2 * e_cap, dtype=torch.int32, device=self._device))
+        host = np.zeros(buf.numel(), dtype=np.int32)
+        state, row_ptr, default_next, edge_tok, edge_next = np.split(host, np.cumsum([b, s_cap + 1, s_cap, e_cap]))
+        state[:] = [FREE if a is None else start[id(a)] for a in rows]
+        row_ptr[:] = table.n_edges  # the states past the table's own list nothing
+        row_ptr[: table.n_states + 1] = table.row_ptr
+        default_next[:] = FREE
+        default_next[: table.n_states] = table.default_next
+        edge_tok[: table.n_edges], edge_next[: table.n_edges] = table.edge_tok, table.edge_next
+        buf.copy_(self._h2d(torch.from_numpy(host)))
+        d_state, d_row_ptr, d_default, d_tok, d_next = torch.split(buf, [b, s_cap + 1, s_cap, e_cap, e_cap])
+        return Constraint(d_row_ptr, d_default, d_tok, d_next, d_state, s_cap)
+
+    def choice_constraint(self, strings: Sequence[str]) -> TokenAutomaton:
+        """The automaton that makes a request answer with exactly one of ``strings`` and then stop: each string's token
+        ids by the model's tokenizer, as a trie, each followed by ``eos_id`` (``TokenAutomaton.choices``).  For
+        ``constraints=`` / ``settings={"constraints": ...}`` of the generation calls."""
+        return TokenAutomaton.choices([list(self.tokenizer.encode(s).ids) for s in strings], self.config.tokenizer.eos_id)
+
     def _token_logprobs(self, logits: torch.Tensor, targets: torch.Tensor, suppress_id: int, logprob: torch.Tensor,
                         rank: torch.Tensor, suppress_rows: Optional[torch.Tensor] = None):
         """``logprob[r]`` (device fp32 [R]) and ``rank[r]`` (device int32 [R]) of token ``targets[r]`` (device int32 [R]) in row
@@ -1102,11 +1160,17 @@ class MoondreamModel:
             self._topk_logprobs(logits, gate, suppress_id, scores.top_ids, scores.top_logprobs, suppress_rows=suppress_rows)
 
     def _first_token(self, logits: torch.Tensor, pick: Optional[Sampling] = None, row_perm=None,
-                     uniforms: Optional[torch.Tensor] = None, scores: Optional[Scores] = None) -> torch.Tensor:
+                     uniforms: Optional[torch.Tensor] = None, scores: Optional[Scores] = None,
+                     constraint: Optional[Constraint] = None, row0: int = 0) -> torch.Tensor:
         """The first generated token of every row, int32 [B], from its prompt pass's logits [B, V]: the argmax (``pick``
         None), a draw with the call's settings (``row_perm``: the draw order of these rows) or with each row's own (and
         ``uniforms`` fp32 [B]).  Nothing is suppressed (moondream.py:313-318).  ``scores`` (a record over [B]): filled with
-        the decision's log-probability, rank and alternatives, unsuppressed like the pick."""
+        the decision's log-probability, rank and alternatives, unsuppressed like the pick.  ``constraint``: these rows are
+        rows ``row0 ..`` of the record -- the tokens their start states forbid lose their logits (in place) before the
+        pick, and the scores are those of the masked logits."""
+        if constraint is not None:
+            assert not constraint.by_slot
+            self._constrain(logits, None, _Rows(), constraint, row0)
         if pick is None:
             first = self._pick(logits, 0.0, 0.0)
         elif pick.per_row:
@@ -1154,7 +1218,7 @@ class MoondreamModel:
     def _decode_greedy_impl(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
                             rows: Union[int, _Rows] = 0, eos_id: Optional[int] = None, check_every: int = 16,
                             allow_b1: bool = True, sampling: Optional[Sampling] = None, scores: Optional[Scores] = None,
-                            penalty: Optional[Penalty] = None):
+                            penalty: Optional[Penalty] = None, constraint: Optional[Constraint] = None):
         """Device-resident decode loop: returns int32 [steps+1, B] (row 0 = ``first``).  ``sampling`` None: greedy.  Otherwise every
         step draws each sequence's token with the reference's rule (moondream.py:521-528: softmax(logits / T), _apply_top_p,
         multinomial) from the step's own logits on the device (md_sample_top_p), with one uniform per (step, sequence) taken
@@ -1170,7 +1234,10 @@ class MoondreamModel:
         alternatives: the launches after the step's pick, inside the captured graph) and changes no id for it.
         ``penalty``: the rows' penalty record (``_penalty_record``) -- every step extends the histories by the tokens it
         consumes (``first`` in its first step) and penalises its logits before the pick; the scores are then those of the
-        penalised logits.  Such a call decodes on the batched kernels, never on the single-sequence one."""
+        penalised logits.  Such a call decodes on the batched kernels, never on the single-sequence one.
+        ``constraint``: the rows' constraint record (``_constraint_record``), each row in the state ``first`` was picked
+        under -- every step advances the states by the tokens it consumes and masks its logits before the pick
+        (after the penalties); the scores are those of the masked logits.  Batched kernels only, like ``penalty``."""
         rows = _Rows.of(rows)
         b = first.shape[0]
         t = self.config.text
@@ -1208,7 +1275,7 @@ class MoondreamModel:
                 return self._step_from_pieces(tok_in.reshape(b, 1), pos_h, rows, pos_dev=pos_t)[1]
 
             chunk = DecodeChunk(b, hist, pos_t, lambda i: rows, suppress_id, pick=sampling or Sampling(0.0, 0.0), step=lora_step,
-                                penalty=penalty)
+                                penalty=penalty, constraint=constraint)
             graphs, uniforms = False, None
         else:
             need = self._decode_ws_bytes(rows, b)
@@ -1216,7 +1283,8 @@ class MoondreamModel:
             # library says this model / cache / device fits its static limits and its grid can be co-resident; anything else
             # decodes on the batched kernels.  Never from the pipelined engine (allow_b1 = False): a second stream's persistent
             # GEMMs could keep workgroups of the grid off the chip and its software barriers would time out.
-            b1 = (b == 1 and allow_b1 and sampling is None and penalty is None and self.single_sequence_kernel and rows.plain
+            b1 = (b == 1 and allow_b1 and sampling is None and penalty is None and constraint is None
+                  and self.single_sequence_kernel and rows.plain
                   and not bool(self.w.text.fp8)
                   and bool(self.lib.md_decode_step_b1_supported(C.byref(self.w.text), C.byref(self._kv_struct(rows.slot0)))))
             self._b1_used = b1
@@ -1224,7 +1292,8 @@ class MoondreamModel:
                 if self._b1_sync is None:
                     self._b1_sync = torch.zeros(4096, dtype=torch.int32, device=self._device)
                 need = max(need, self.lib.md_decode_step_b1_workspace_bytes(C.byref(self.w.text)))
-            chunk = DecodeChunk(b, hist, pos_t, lambda i: rows, suppress_id, need, sampling, b1=b1, penalty=penalty)
+            chunk = DecodeChunk(b, hist, pos_t, lambda i: rows, suppress_id, need, sampling, b1=b1, penalty=penalty,
+                                constraint=constraint)
             graphs = self.use_graphs
         # one graph = `per` consecutive steps over fixed buffers; eager chunks end where the all-done check is due
         per = max(1, min(check_every or 16, max_tokens)) if graphs else (check_every or max_tokens)
@@ -1286,14 +1355,16 @@ class MoondreamModel:
         return out
 
     def _prefill_groups(self, groups: Sequence[Tuple[int, int]], embed, pos: int, rows: _Rows, sampling: Optional[Sampling] = None,
-                        logits_capture: Optional[torch.Tensor] = None, scores: Optional[Scores] = None, hidden_sink=None):
+                        logits_capture: Optional[torch.Tensor] = None, scores: Optional[Scores] = None, hidden_sink=None,
+                        constraint: Optional[Constraint] = None):
         """One decoder pass per group [r0, r1) of equal-length prompts: ``embed(r0, r1)`` [r1-r0, T, D] goes through the decoder
         at position ``pos`` into the slots of ``rows.sub(r0, r1)``, then lm_head and the pick of the first token (``_first_token``;
         ``sampling`` None: argmax; a group draws in its rows' order among themselves in ``sampling.row_perm``).
         Returns (first int32 [B], hidden_last [B, D], next_pos list); the groups' logits go to ``logits_capture`` [B, V], each
         first decision's log-probability, rank and alternatives (unsuppressed, like the pick) to ``scores``, a record over [B].
         ``hidden_sink(r0, r1, hidden [r1-r0, T, D])``: the scorer's form -- every hidden row of the pass goes to the sink, and
-        no first token is picked (``first`` and ``hidden_last`` are not filled)."""
+        no first token is picked (``first`` and ``hidden_last`` are not filled).  ``constraint``: the rows' record, row r
+        its entry r -- every first token is picked under its row's start state (``_first_token``)."""
         b = groups[-1][1]
         first = torch.empty(b, dtype=torch.int32, device=self._device)
         hidden_last = torch.empty(b, self.config.text.dim, dtype=BF16, device=self._device)
@@ -1310,7 +1381,7 @@ class MoondreamModel:
                 logits_capture[r0:r1] = logits
             perm = sampling.row_perm[r0:r1] if sampling is not None and sampling.row_perm is not None else None
             first[r0:r1] = self._first_token(logits, sampling, perm - perm.min() if perm is not None else None,
-                                             scores=scores and scores[r0:r1])
+                                             scores=scores and scores[r0:r1], constraint=constraint, row0=r0)
             hidden_last[r0:r1] = hidden[:, -1, :]
         return first, hidden_last, next_pos
 
@@ -1349,7 +1420,8 @@ class MoondreamModel:
     def _prepare_sequences(self, images, prompts: Sequence[Sequence[int]], mark=None, rows: Union[int, _Rows] = 0,
                            fuse: bool = False, share_prefix: bool = False, variants: Optional[Sequence[int]] = None,
                            encode_settings: Optional[dict] = None, logits_capture: Optional[torch.Tensor] = None,
-                           sampling: Optional[Sampling] = None, scores: Optional[Scores] = None, hidden_sink=None) -> Prepared:
+                           sampling: Optional[Sampling] = None, scores: Optional[Scores] = None, hidden_sink=None,
+                           constraints: Optional[Sequence[Optional[TokenAutomaton]]] = None) -> Prepared:
         """Everything before the first generated token, for B (image, prompt-ids) pairs, as ``plan_rows`` lays them out
         (moondream_amd/shared_prefix.py): every image's KV prefix is placed (``_place_images``), then one prompt prefill per
         distinct length picks the first tokens.  Returns a ``Prepared``, rows in slot order.  The COPY route gives row r slot
@@ -1361,7 +1433,9 @@ class MoondreamModel:
         the device table is built in slot order here.  ``fuse``: an all-raw copy route takes the one-pass prefill below.
         ``sampling`` draws the first token as the reference's _prefill_prompt does (moondream.py:313-318; nothing suppressed
         there); None = argmax.
-        ``logits_capture`` / ``scores`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in slot order.  Must run under
+        ``logits_capture`` / ``scores`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in slot order.
+        ``constraints``: ``check_constraints``' entries in the CALLER's order; their record (``_constraint_record``, rows in
+        slot order) masks every first pick and goes to the decode loop in ``Prepared.constraint``.  Must run under
         torch.inference_mode()."""
         mark = mark or (lambda name: None)
         rows = _Rows.of(rows)
@@ -1398,11 +1472,13 @@ class MoondreamModel:
                 rows = self._shared_routing(plan, pos)
                 if sampling is not None:
                     sampling = replace(sampling, row_perm=torch.tensor(plan.copy_rank, dtype=torch.int64, device=self._device))
-        out = self._prefill_groups(plan.groups, embed, pos, rows, sampling, logits_capture, scores=scores, hidden_sink=hidden_sink)
+        constraint = self._constraint_record(constraints and [constraints[i] for i in plan.order])
+        out = self._prefill_groups(plan.groups, embed, pos, rows, sampling, logits_capture, scores=scores, hidden_sink=hidden_sink,
+                                   constraint=constraint)
         if fused:  # the one pass is both
             mark("image_prefill")
         mark("prompt_prefill")
-        return Prepared(plan.order, *out, rows, sampling)
+        return Prepared(plan.order, *out, rows, sampling, constraint)
 
     def _mark(self, marks: list, name: str):
         """Phase timing (``collect_timing``): an event on the current stream, named after the phase that ends there."""
@@ -1448,6 +1524,7 @@ class MoondreamModel:
         repetition_penalty: Union[float, Sequence[float]] = 1.0,
         presence_penalty: Union[float, Sequence[float]] = 0.0,
         frequency_penalty: Union[float, Sequence[float]] = 0.0,
+        constraints: Union[None, TokenAutomaton, Sequence[Optional[TokenAutomaton]]] = None,
     ):
         """Token ids for B (image, prompt-ids) pairs, decoded in lockstep; greedy by default.
 
@@ -1522,11 +1599,25 @@ class MoondreamModel:
         the fp8 modes: a step leaves bf16 logits in the same buffer in all of them); a lone penalised sequence decodes on
         the batched kernels.  ValueError, before any GPU work: a repetition penalty that is not finite and > 0, a
         presence or frequency penalty that is not finite, a list that is not one per row.
+
+        ``constraints``: one ``TokenAutomaton`` (moondream_amd/constraint.py) for every row, or a list with one entry per
+        row in the caller's order (None: the row is free).  A row's automaton starts in state 0 and is advanced by every
+        token the row generates; before each pick -- the first token's included -- the tokens its state forbids have
+        their logits set to -inf on the device (md_constrain_rows: one launch per step after the penalties and before the
+        pick, inside the captured chunk; the packed table and the rows' states live on the device), so neither the
+        argmax nor a sampled draw can produce them.  A row that reaches ``FREE`` is unconstrained from there on.  With
+        ``return_logprobs`` the log-probabilities, ranks and alternatives are those of the MASKED logits: a greedy token
+        has rank 0 and an alternative outside the allowed set carries -inf.  A free row's ids are those of the call
+        without the argument; with every row free the call is that call, launch for launch.  Served in every mode of
+        this call, like the penalties; a lone constrained sequence decodes on the batched kernels.  ValueError, before
+        any GPU work: a list that is not one per row, an entry that is no automaton, an automaton ``validate(vocab_size,
+        answer_id)`` refuses (a state that allows no token other than ``answer_id``, which generation suppresses).
         """
         top_k = check_top_logprobs(top_logprobs, return_logprobs)
         b = len(images)
         assert b == len(prompts) and b > 0
         penalties = check_penalties(repetition_penalty, presence_penalty, frequency_penalty, b)
+        constraints = self._check_constraints_of({"constraints": constraints}, b)
         multi_rows = None
         if variants is not None:
             if variant is not None:
@@ -1548,11 +1639,11 @@ class MoondreamModel:
             scores = Scores.new((rows_t, b), top_k, self._device, fill=True) if return_logprobs else None
             prep = self._prepare_sequences(images, prompts, mark, _Rows(lora=lora), fuse=True, share_prefix=share_prefix,
                                            variants=multi_rows, encode_settings={"variant": variant}, sampling=sampling,
-                                           scores=scores and scores[0])
+                                           scores=scores and scores[0], constraints=constraints)
             stop = None if ignore_eos else eos
             penalty = self._penalty_record(penalties and [penalties[i] for i in prep.order])  # rows in slot order
             hist = self._decode_greedy(prep.first, prep.pos, max_tokens, tk.answer_id, prep.rows, stop, sampling=prep.sampling,
-                                       scores=scores, penalty=penalty)
+                                       scores=scores, penalty=penalty, constraint=prep.constraint)
             mark("decode")
             host = scores and scores[: hist.shape[0]].to_host(hist)  # ids, logprobs, ranks, alternatives: ONE copy to the host
             cols = (host.extra[0].T if host else hist.t()).tolist()
@@ -1574,21 +1665,23 @@ class MoondreamModel:
                                       top_p: Union[float, Sequence[float]] = DEFAULT_TOP_P, seeds=None,
                                       variant: Optional[str] = None, return_logprobs: bool = False,
                                       top_logprobs: Optional[int] = None, repetition_penalty=None, presence_penalty=None,
-                                      frequency_penalty=None):
+                                      frequency_penalty=None, constraints=None):
         """``batch_generate_ids`` with continuous batching (moondream_amd/continuous.py): per-request ``max_tokens`` and EOS
         exit, freed KV slots refilled from the queue mid-decode; same greedy ids as the lockstep path.  ``temperature`` and
         ``top_p``: one float, or one per request (greedy and sampled requests share the decode steps).  ``return_logprobs``:
         (ids, logprobs, ranks) as ``batch_generate_ids`` returns them (``ContinuousEngine(logprobs=True)``); with
         ``top_logprobs`` = k also its ``alternatives`` (``ContinuousEngine(logprobs=True, top_logprobs=k)``).  The three
-        penalties: one number or one per request (None: neutral), ``batch_generate_ids``' rule per request."""
+        penalties: one number or one per request (None: neutral), ``batch_generate_ids``' rule per request.  ``constraints``:
+        one ``TokenAutomaton`` or one entry per request (None: free), ``batch_generate_ids``' rule and ids per request."""
         from .continuous import ContinuousEngine
 
         check_penalties(repetition_penalty, presence_penalty, frequency_penalty, len(images))  # before the engine exists
+        constraints = self._check_constraints_of({"constraints": constraints}, len(images))
 
         eng = ContinuousEngine(self, max_live, chunk, logprobs=bool(return_logprobs), top_logprobs=top_logprobs)
         return eng.generate(images, prompts, max_tokens, eos_id, ignore_eos, seeds, variant, temperature, top_p,
                             return_logprobs=bool(return_logprobs), repetition_penalty=repetition_penalty,
-                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
+                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, constraints=constraints)
 
     def teacher_forced_logits(self, images, prompts: Sequence[Sequence[int]], forced_ids, gather_idx) -> torch.Tensor:
         """Parity instrument (tests / bench.py): the logits of every greedy decision when each sequence is FORCED to follow
@@ -1648,7 +1741,8 @@ class MoondreamModel:
 
     def score_ids(self, images: Sequence[Union[Image.Image, EncodedImage]], prompts: Sequence[Sequence[int]],
                   continuations: Sequence[Sequence[int]], share_prefix: bool = False, variant: Optional[str] = None,
-                  top_logprobs: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+                  top_logprobs: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
+                  constraints=None):
         """Score GIVEN continuations: returns ``(logprobs, ranks)``, one list per row with one entry per token of
         ``continuations[i]`` -- the values ``batch_generate_ids(..., return_logprobs=True)`` attaches to a token it generates,
         for the tokens the caller supplies.  ``logprobs[i][j]`` is log softmax of the model's logits after
@@ -1669,8 +1763,9 @@ class MoondreamModel:
         ``batch_generate_ids(..., top_logprobs=k)`` gives them: ONE md_topk_logprobs launch over the same logits and
         suppression table, and the same copy to the host.  ValueError for a k outside 1 .. 32.  The penalty arguments of
         ``batch_generate_ids`` are not served here (ValueError for a non-neutral one): the scorer makes no decode step, so
-        there is no history to penalise from -- scores are the model's own."""
+        there is no history to penalise from -- scores are the model's own.  ``constraints`` likewise (ValueError)."""
         top_k = check_top_logprobs(top_logprobs, True)
+        refuse_constraints({"constraints": constraints}, "score_ids (no token is picked: scores are the model's own)")
         refuse_penalties(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                               frequency_penalty=frequency_penalty), "score_ids (no decode step runs: scores are the model's own)",
                          len(images))
@@ -1720,7 +1815,7 @@ class MoondreamModel:
     pipeline_streams = int(os.environ.get("MD_PIPE_STREAMS", "2"))  # 2: decode on its own (priority) stream; 1: encode and decode in order on one stream
 
     def batch_generate_ids_pipelined(self, batches, max_tokens: int = DEFAULT_MAX_TOKENS, ignore_eos: bool = False,
-                                     repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+                                     repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, constraints=None):
         """Generator over an iterable of (images, prompt-id lists) batches; yields each batch's greedy ids in order, one
         decode group late (a group = two consecutive batches of <= 64 sequences decoded as ONE lockstep of <= 128 -- round 6,
         ``pair_decode`` -- or one batch).  Two HIP streams: the MFMA-bound encode (vision + prefill) of batch k+1 on one, the HBM-bound lockstep
@@ -1737,7 +1832,8 @@ class MoondreamModel:
             (either makes the host wait for the device).
 
         Per batch the result is identical to ``batch_generate_ids`` (same kernels, same order).  The penalty arguments of
-        that call are not served here: ValueError for a non-neutral one."""
+        that call are not served here: ValueError for a non-neutral one; nor are ``constraints`` (ValueError)."""
+        refuse_constraints({"constraints": constraints}, "the pipelined engine (its paired decode keeps no automaton states)")
         refuse_penalties(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                               frequency_penalty=frequency_penalty), "the pipelined engine (its paired decode keeps no histories)")
         return self._pipelined_loop(batches, max_tokens, ignore_eos)
@@ -1866,16 +1962,24 @@ class MoondreamModel:
             yield [self._truncate(cols[i], eos, max_tokens) for i in range(i0, i0 + n)]
             i0 += n
 
+    def _check_constraints_of(self, settings: Optional[dict], n: int) -> Optional[List[Optional[TokenAutomaton]]]:
+        """``settings["constraints"]`` checked for ``n`` rows (``check_constraints``): host values, before any GPU work."""
+        constraints = (settings or {}).get("constraints")
+        if constraints is None:
+            return None
+        return check_constraints(constraints, n, self.config.text.vocab_size, self.config.tokenizer.answer_id)
+
     @staticmethod
     def _sampling_kwargs(settings: Optional[dict]) -> dict:
         """``settings`` of the string API -> keyword arguments of ``batch_generate_ids``, with the REFERENCE'S defaults
         (moondream.py:50-53, read at :447-457): max_tokens 768, temperature 0.5, top_p 0.3.  ``settings["generator"]`` (an
         extension) seeds the draws; ``{"temperature": 0}`` is greedy.  ``repetition_penalty`` / ``presence_penalty`` /
-        ``frequency_penalty`` (extensions; one number or one per row) pass through, neutral when absent."""
+        ``frequency_penalty`` (extensions; one number or one per row) pass through, neutral when absent, and so does
+        ``constraints`` (an extension: one ``TokenAutomaton`` or one entry per row; absent: every row free)."""
         st = settings or {}
         return dict(max_tokens=st.get("max_tokens", DEFAULT_MAX_TOKENS), variant=st.get("variant"), variants=st.get("variants"),
                     temperature=st.get("temperature", DEFAULT_TEMPERATURE), top_p=st.get("top_p", DEFAULT_TOP_P),
-                    generator=st.get("generator"), **penalties_of(settings))
+                    generator=st.get("generator"), constraints=st.get("constraints"), **penalties_of(settings))
 
     def batch_caption(self, images, length: str = "normal", settings: Optional[dict] = None) -> List[str]:
         tpl = self.config.tokenizer.templates["caption"]
@@ -1924,8 +2028,9 @@ class MoondreamModel:
 
     # ------------------------------------------------------- sequential API
     def _prefill_prompt(self, prompt_tokens: torch.Tensor, pos: int, temperature: float, top_p: float,
-                        spatial_refs: Optional[SpatialRefs] = None, attn_mask=None, lora=None, causal: bool = False):
-        """reference: moondream.py:280-321.  ``causal`` stands for the reference's
+                        spatial_refs: Optional[SpatialRefs] = None, attn_mask=None, lora=None, causal: bool = False,
+                        constraint: Optional[Constraint] = None):
+        """reference: moondream.py:280-321.  ``constraint``: the sequence's record, masking the first pick.  ``causal`` stands for the reference's
         ``attn_mask`` argument: the only non-default mask it ever passes is the plain
         lower-triangular one of a text-only query (moondream.py:571-575)."""
         self._select_kernels(1)  # a lone sequence's own tile policy, whatever an earlier (batch) call left in the structs
@@ -1939,7 +2044,7 @@ class MoondreamModel:
                     emb[ids.to(self._device) == self.config.tokenizer.size_id] = enc["sizes"]
             hidden = self._text_forward(emb, pos, _Rows(lora=lora if isinstance(lora, PackedLora) else None), causal=causal)
             logits = self._lm_head(hidden)
-            nxt = self._first_token(logits, Sampling(temperature, top_p) if temperature != 0 else None)
+            nxt = self._first_token(logits, Sampling(temperature, top_p) if temperature != 0 else None, constraint=constraint)
         return logits, hidden, nxt.reshape(1, 1), pos + ids.shape[1]
 
     def _generate_answer(self, prompt_tokens: torch.Tensor, pos: int, settings: Optional[dict] = None,
@@ -1948,17 +2053,22 @@ class MoondreamModel:
         """Generator of text pieces.  reference: moondream.py:434-539.  ``settings`` may carry ``repetition_penalty`` /
         ``presence_penalty`` / ``frequency_penalty`` (``batch_generate_ids``' rule, over this sequence's generated tokens):
         every step's logits are penalised on the device before its pick, in the chunked greedy loop and in the per-token
-        sampled one alike."""
+        sampled one alike; and ``constraints`` (one ``TokenAutomaton``: ``batch_generate_ids``' rule for this sequence,
+        the first token included)."""
         settings = settings or {}
         max_tokens = settings.get("max_tokens", DEFAULT_MAX_TOKENS)
         temperature = settings.get("temperature", DEFAULT_TEMPERATURE)
         top_p = settings.get("top_p", DEFAULT_TOP_P)
         penalties = check_penalties(*penalties_of(settings).values(), 1)
+        automata = self._check_constraints_of(settings, 1)
         lora = self._lora(settings)
         rows = _Rows(lora=lora)
         eos = eos_id if eos_id is not None else self.config.tokenizer.eos_id
         # decode steps attend to keys [0, pos] only, which both masks allow: the mask matters for the prompt
-        _, _, nxt, pos = self._prefill_prompt(prompt_tokens, pos, temperature, top_p, spatial_refs, attn_mask, lora=lora, causal=causal)
+        with torch.inference_mode():
+            constraint = self._constraint_record(automata)  # one state over the whole answer, at its start now
+        _, _, nxt, pos = self._prefill_prompt(prompt_tokens, pos, temperature, top_p, spatial_refs, attn_mask, lora=lora, causal=causal,
+                                              constraint=constraint)
 
         def token_source():
             with torch.inference_mode():
@@ -1969,7 +2079,8 @@ class MoondreamModel:
                 cur_pos = pos
                 while done < max_tokens:
                     chunk = min(16, max_tokens - done)
-                    hist = self._decode_greedy(first, cur_pos, chunk, self.config.tokenizer.answer_id, 0, None, penalty=penalty)
+                    hist = self._decode_greedy(first, cur_pos, chunk, self.config.tokenizer.answer_id, 0, None, penalty=penalty,
+                                               constraint=constraint)
                     toks = hist[:, 0].tolist()
                     self._check_b1_barriers()
                     for tok in toks[:-1]:
@@ -1992,6 +2103,8 @@ class MoondreamModel:
                         cur_pos += 1
                         if penalty is not None:
                             self._penalize(logits, tok, rows, penalty)
+                        if constraint is not None:
+                            self._constrain(logits, tok, rows, constraint)
                         tok = self._pick(logits, temperature, top_p, self.config.tokenizer.answer_id)  # moondream.py:517
 
         def generator():
@@ -2032,8 +2145,10 @@ class MoondreamModel:
     def caption(self, image, length: Literal["normal", "short", "long"] = "normal", stream: bool = False,
                 settings: Optional[dict] = None):
         """reference: moondream.py:625-651.  ``settings`` may carry ``repetition_penalty`` / ``presence_penalty`` /
-        ``frequency_penalty`` (an extension: ``batch_generate_ids``' rule over the caption's generated tokens)."""
+        ``frequency_penalty`` (an extension: ``batch_generate_ids``' rule over the caption's generated tokens) and
+        ``constraints`` (one ``TokenAutomaton``)."""
         check_penalties(*penalties_of(settings).values(), 1)  # host values: before any GPU work
+        self._check_constraints_of(settings, 1)
         tpl = self.config.tokenizer.templates["caption"]
         if tpl is None:
             raise NotImplementedError("Model does not support captioning.")
@@ -2048,9 +2163,10 @@ class MoondreamModel:
     def query(self, image=None, question: str = None, reasoning: bool = False,
               spatial_refs: Optional[SpatialRefs] = None, stream: bool = False, settings: Optional[dict] = None):
         """reference: moondream.py:541-618, including the ``reasoning`` branch (thinking token -> _generate_reasoning
-        -> answer after a second suffix).  ``settings`` may carry the penalty settings as ``caption``'s may; not with
-        ``reasoning`` (ValueError)."""
+        -> answer after a second suffix).  ``settings`` may carry the penalty settings and ``constraints`` as ``caption``'s
+        may; not with ``reasoning`` (ValueError)."""
         check_penalties(*penalties_of(settings).values(), 1)  # host values: before any GPU work
+        self._check_constraints_of(settings, 1)
         tpl = self.config.tokenizer.templates["query"]
         if tpl is None:
             raise NotImplementedError("Model does not support querying.")
@@ -2060,6 +2176,7 @@ class MoondreamModel:
             raise ValueError("spatial_refs can only be used with an image.")
         if reasoning:
             refuse_penalties(settings, "reasoning queries")
+            refuse_constraints(settings, "reasoning queries")
         if image is not None:
             enc = self.encode_image(image, settings)
             self.load_encoded_image(enc)
@@ -2492,6 +2609,7 @@ class MoondreamModel:
         the penalty settings: a reasoning row's logits are masked per phase inside its own step)."""
         st = settings or {}
         refuse_penalties(settings, "reasoning queries")
+        refuse_constraints(settings, "reasoning queries")
         if st.get("variant") is not None or st.get("variants") is not None:
             raise NotImplementedError("batched reasoning queries are not served with LoRA variants (variant / variants): "
                                       "use query(reasoning=True) per image")
@@ -2578,6 +2696,7 @@ class MoondreamModel:
         """The host checks of every detect / point call, before any GPU work: penalties are not served, and the score
         settings (``check_score_settings``) -> the score window, None without ``return_scores``."""
         refuse_penalties(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
+        refuse_constraints(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
         return check_score_settings(settings, self.config.region.coord_out_dim)
 
     def batch_detect(self, images, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
@@ -2609,6 +2728,7 @@ class MoondreamModel:
         ``variant`` (settings) takes the copy path, with the same results.  With reasoning: ``query_many_reasoning``."""
         prompts = self._query_prompts(questions)
         check_penalties(*penalties_of(settings).values(), len(prompts))  # host values: before any GPU work
+        self._check_constraints_of(settings, len(prompts))
         enc = self.encode_image(image, settings)
         ids = self.batch_generate_ids([enc] * len(prompts), prompts, share_prefix=True, **self._sampling_kwargs(settings))
         return [{"answer": self.tokenizer.decode(s)} for s in ids]
