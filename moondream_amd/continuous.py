@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import math
 from collections import deque
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Callable, Deque, Dict, Iterator, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -561,108 +561,74 @@ class ContinuousEngine:
 
         return torch.rand(n, dtype=torch.float32, generator=self._generator(r))
 
-    def _forward_slots(self, x, pos0: int, slots: List[int], variants: Optional[List[int]] = None, keep: str = "last"):
-        """x [k, T, D] -> the last hidden row of every sequence [k, 1, D] (``keep`` "none": nothing, an image prefill); K / V
-        rows written into ``slots``.  ``variants`` with a LoRA row: those per-row bank indices travel with the call."""
+    def _table(self, reqs: List[Request]):
+        """The routing of a call with one row per request of ``reqs``: their slots, and their variants when one of them has
+        one, in one H2D copy."""
         import torch
 
-        m = self.model
-        slots_d = m._h2d(torch.tensor(slots, dtype=torch.int32))
-        var_d = None
-        if variants is not None and any(v >= 0 for v in variants):
-            var_d = m._h2d(torch.tensor(variants, dtype=torch.int32))
-        hidden = m._text_forward(x, int(pos0), self._rows(slots_d, var_d), keep=keep)
-        self.stats.prefill_passes += 1
-        return hidden
-
-    def _first_tokens(self, hidden, reqs: List[Request]):
-        """hidden [k, 1, D], the last rows of a prefill -> the first token of each request from its last row, as _prepare_sequences picks it (argmax, or
-        top-p sampling with the request's own settings and first uniform: md_sample_rows over the group; no suppression).
-        lm_head in launches of <= 64 rows: the decode-regime kernels, whatever the admission size.  Returns one tuple per
-        request: (token,) and, of the same logits and unsuppressed like the pick, what ``SlotScheduler.start`` takes after it."""
-        import torch
-
-        m = self.model
-        k = len(reqs)
-        first = torch.empty(k, dtype=torch.int32, device=m.device)
-        scores = Scores.new((k,), self.top_logprobs, m.device) if self.logprobs else None
-        for i0 in range(0, k, 64):
-            part = reqs[i0 : i0 + 64]
-            i1 = i0 + len(part)
-            pick = st_d = None
-            if any(r.temperature != 0 for r in part):
-                # one H2D copy of [temperature | top_p | uniform] rows; a greedy request draws nothing
-                draws = [float(self._uniforms(r, 1)[0]) if r.temperature != 0 else 0.0 for r in part]
-                st_d = m._h2d(torch.tensor([[r.temperature for r in part], [r.top_p for r in part], draws], dtype=torch.float32))
-                pick = Sampling(st_d[0], st_d[1])
-            con = None
-            if any(r.constraint is not None for r in part):  # these rows' start states, beside the engine's table
-                con = self._constraint(m._h2d(torch.tensor([r.constraint_start for r in part], dtype=torch.int32)), by_slot=False)
-            first[i0:i1] = m._first_token(m._lm_head(hidden[i0:i1]), pick, uniforms=st_d[2] if pick is not None else None,
-                                          scores=scores and scores[i0:i1], constraint=con)
-        if scores is None:
-            return [(f,) for f in first.tolist()]
-        host = scores.to_host(first)  # the tokens and their scores in one copy
-        top = [zip(host.top_ids, host.top_logprobs)] if self.top_logprobs else []
-        return list(zip(host.extra[0].tolist(), host.logprob.tolist(), host.rank.tolist(), *top))
+        lora = any(r.variant >= 0 for r in reqs)
+        tab = self.model._h2d(torch.tensor([[r.slot for r in reqs]] + ([[r.variant for r in reqs]] if lora else []), dtype=torch.int32))
+        return self._rows(tab[0], tab[1] if lora else None)
 
     def _admit(self, reqs: List[Request]) -> List[Tuple[int, int]]:
-        """ViT over the admitted raw images as one batch, then the prefill into their slots with the choices of
-        _prepare_sequences: [bos | image | prompt] in one pass per prompt length when every image is raw and
-        ``fused_prefill`` is on; otherwise [bos | image] passes and EncodedImage slot copies, then one prompt pass per
-        (prefix, prompt length) in launches of <= 64 rows."""
+        """The prefill of ``reqs`` into their slots, through the pieces of ``MoondreamModel._prepare_sequences`` and with its
+        choices: [bos | image | prompt] in one pass per prompt length when every image is raw and ``fused_prefill`` is on;
+        otherwise ``_place_images`` (ONE ViT batch and ONE [bos | image] pass over the raw images, every EncodedImage loaded
+        into its request's slot), then the prompt passes per (prefix, prompt length).  The engine's own part is the shape
+        of the groups and the rows' records; its three launch rules, which keep a request's ids independent of what else
+        is admitted: a prompt pass of t <= 64 positions after a placed image has at most max(1, 64 // t) rows; lm_head and
+        the first pick run in cuts of at most 64 rows; a pass takes the variant table only if one of its rows has a variant.
+        Returns, per request, (first token, next position), then its (logprob, rank) with ``logprobs``, then its
+        alternatives' (ids, logprobs) with ``top_logprobs``."""
         import torch
         from PIL import Image
 
         m = self.model
-        tk = m.config.tokenizer
         m._select_kernels(2)  # (again: another call on the model may have run between two chunks of this generator)
-        raw = [i for i, r in enumerate(reqs) if isinstance(r.image, Image.Image)]
-        img_emb = m._run_vision_encoder_batch([reqs[i].image for i in raw]) if raw else None
-        emb_of = {i: j for j, i in enumerate(raw)}
-        firsts: Dict[int, tuple] = {}
-        pos_of: Dict[int, int] = {}
-
-        def groups(keyf):
-            g: Dict[object, List[int]] = {}
-            for i in range(len(reqs)):
-                g.setdefault(keyf(i), []).append(i)
-            return list(g.values())
-
-        if len(raw) == len(reqs) and m.fused_prefill:
-            for idx in groups(lambda i: len(reqs[i].prompt)):
-                k = len(idx)
-                bos = m._embed(torch.full((k, 1), tk.bos_id, dtype=torch.int32))
-                pe = m._embed(torch.tensor([reqs[i].prompt for i in idx], dtype=torch.int32))
-                x = torch.cat([bos, img_emb[[emb_of[i] for i in idx]], pe], dim=1)
-                hidden = self._forward_slots(x, 0, [reqs[i].slot for i in idx], [reqs[i].variant for i in idx])
-                first = self._first_tokens(hidden, [reqs[i] for i in idx])
-                for i, f in zip(idx, first):
-                    firsts[i], pos_of[i] = f, x.shape[1]
+        raw = [r for r in reqs if isinstance(r.image, Image.Image)]
+        fused = len(raw) == len(reqs) and m.fused_prefill
+        prefix = {r: 0 for r in reqs}  # a fused pass starts at the bos
+        if not fused:
+            placed = raw + [r for r in reqs if r not in raw]  # the raw rows first: one run, so one [bos | image] pass
+            got = m._place_images([r.image for r in placed], self._table(raw) if raw else None, lambda name: None,
+                                  slots=[r.slot for r in placed])
+            prefix = dict(zip(placed, got))
+            self.stats.prefill_passes += bool(raw)
+        by_key: Dict[Tuple[int, int], List[Request]] = {}  # in order of first appearance
+        for r in reqs:
+            by_key.setdefault((prefix[r], len(r.prompt)), []).append(r)
+        rows: List[Request] = []  # the admission's rows, every pass a range of them
+        groups, starts = [], []
+        for (p, t), members in by_key.items():
+            per = len(members) if fused or t > 64 else max(1, 64 // t)
+            for j0 in range(0, len(members), per):
+                groups.append((len(rows) + j0, len(rows) + min(j0 + per, len(members))))
+                starts.append(p)
+            rows += members
+        table = self._table(rows)
+        base = replace(table, variants=None, bank=None)
+        routes = [(table if any(r.variant >= 0 for r in rows[r0:r1]) else base).sub(r0, r1) for r0, r1 in groups]
+        pick = st = con = None
+        if any(r.temperature != 0 for r in rows):
+            # one H2D copy of [temperature | top_p | uniform] rows; a greedy request draws nothing
+            draws = [float(self._uniforms(r, 1)[0]) if r.temperature != 0 else 0.0 for r in rows]
+            st = m._h2d(torch.tensor([[r.temperature for r in rows], [r.top_p for r in rows], draws], dtype=torch.float32))
+            pick = Sampling(st[0], st[1])
+        if any(r.constraint is not None for r in rows):  # the rows' start states, beside the engine's table
+            con = self._constraint(m._h2d(torch.tensor([r.constraint_start for r in rows], dtype=torch.int32)), by_slot=False)
+        scores = Scores.new((len(rows),), self.top_logprobs, m.device) if self.logprobs else None
+        embed = m._sequence_embeddings([r.prompt for r in rows], [r.image for r in rows] if fused else None)
+        first, _, next_pos = m._prefill_groups(groups, embed, starts, routes, pick, scores=scores, constraint=con,
+                                               uniforms=st[2] if st is not None else None, head_rows=64)
+        self.stats.prefill_passes += len(groups)
+        if scores is None:
+            picked = [(f,) for f in first.tolist()]
         else:
-            prefix: Dict[int, int] = {}
-            if raw:
-                bos = m._embed(torch.full((len(raw), 1), tk.bos_id, dtype=torch.int32))
-                x = torch.cat([bos, img_emb], dim=1)
-                self._forward_slots(x, 0, [reqs[i].slot for i in raw], [reqs[i].variant for i in raw], keep="none")
-                for i in raw:
-                    prefix[i] = x.shape[1]
-            for i, r in enumerate(reqs):
-                if i not in prefix:
-                    m.load_encoded_image(r.image, r.slot)
-                    prefix[i] = int(r.image.pos)
-            for idx in groups(lambda i: (prefix[i], len(reqs[i].prompt))):
-                t = len(reqs[idx[0]].prompt)
-                per = max(1, 64 // t) if t <= 64 else len(idx)
-                for j0 in range(0, len(idx), per):
-                    sub = idx[j0 : j0 + per]
-                    pe = m._embed(torch.tensor([reqs[i].prompt for i in sub], dtype=torch.int32))
-                    hidden = self._forward_slots(pe, prefix[sub[0]], [reqs[i].slot for i in sub], [reqs[i].variant for i in sub])
-                    first = self._first_tokens(hidden, [reqs[i] for i in sub])
-                    for i, f in zip(sub, first):
-                        firsts[i], pos_of[i] = f, prefix[i] + t
-        # (first token, next position) per request; with ``logprobs`` also the first token's (logprob, rank)
-        return [(int(firsts[i][0]), pos_of[i]) + tuple(firsts[i][1:]) for i in range(len(reqs))]
+            host = scores.to_host(first)  # the tokens and their scores in one copy
+            top = [zip(host.top_ids, host.top_logprobs)] if self.top_logprobs else []
+            picked = list(zip(host.extra[0].tolist(), host.logprob.tolist(), host.rank.tolist(), *top))
+        started = {r: (int(f[0]), pos) + tuple(f[1:]) for r, f, pos in zip(rows, picked, next_pos)}
+        return [started[r] for r in reqs]
 
     def _buffers(self, bucket: int):
         """Fixed-address buffers of a (chunk, bucket): int32 device state [slots (chunk x bucket) | pos (bucket) | tokens ((chunk + 1) x

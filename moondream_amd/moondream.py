@@ -1354,12 +1354,17 @@ class MoondreamModel:
             out.append(tok)
         return out
 
-    def _prefill_groups(self, groups: Sequence[Tuple[int, int]], embed, pos: int, rows: _Rows, sampling: Optional[Sampling] = None,
+    def _prefill_groups(self, groups: Sequence[Tuple[int, int]], embed, pos: Union[int, Sequence[int]],
+                        rows: Union[_Rows, Sequence[_Rows]], sampling: Optional[Sampling] = None,
                         logits_capture: Optional[torch.Tensor] = None, scores: Optional[Scores] = None, hidden_sink=None,
-                        constraint: Optional[Constraint] = None):
+                        constraint: Optional[Constraint] = None, uniforms: Optional[torch.Tensor] = None,
+                        head_rows: Optional[int] = None):
         """One decoder pass per group [r0, r1) of equal-length prompts: ``embed(r0, r1)`` [r1-r0, T, D] goes through the decoder
-        at position ``pos`` into the slots of ``rows.sub(r0, r1)``, then lm_head and the pick of the first token (``_first_token``;
-        ``sampling`` None: argmax; a group draws in its rows' order among themselves in ``sampling.row_perm``).
+        at position ``pos`` (one int, or one per group) into the slots of ``rows.sub(r0, r1)`` (or of the group's own entry
+        of ``rows``, one routing per group, already cut), then lm_head and the pick of the first token (``_first_token``;
+        ``sampling`` None: argmax; a group draws in its rows' order among themselves in ``sampling.row_perm``; per-row
+        settings, fp32 [B] like their ``uniforms``, are cut like the rows).  ``head_rows``: lm_head, the pick and what goes
+        with it run in cuts of at most so many rows of a pass (None: the whole pass).
         Returns (first int32 [B], hidden_last [B, D], next_pos list); the groups' logits go to ``logits_capture`` [B, V], each
         first decision's log-probability, rank and alternatives (unsuppressed, like the pick) to ``scores``, a record over [B].
         ``hidden_sink(r0, r1, hidden [r1-r0, T, D])``: the scorer's form -- every hidden row of the pass goes to the sink, and
@@ -1369,44 +1374,68 @@ class MoondreamModel:
         first = torch.empty(b, dtype=torch.int32, device=self._device)
         hidden_last = torch.empty(b, self.config.text.dim, dtype=BF16, device=self._device)
         next_pos = [0] * b
-        for r0, r1 in groups:
+        pos_of = [pos] * len(groups) if isinstance(pos, int) else pos
+        rows_of = [rows.sub(r0, r1) for r0, r1 in groups] if isinstance(rows, _Rows) else rows
+        for (r0, r1), p, route in zip(groups, pos_of, rows_of):
             x = embed(r0, r1)
-            next_pos[r0:r1] = [pos + x.shape[1]] * (r1 - r0)
+            next_pos[r0:r1] = [p + x.shape[1]] * (r1 - r0)
             if hidden_sink is not None:
-                hidden_sink(r0, r1, self._text_forward(x, pos, rows.sub(r0, r1), keep="all"))
+                hidden_sink(r0, r1, self._text_forward(x, p, route, keep="all"))
                 continue
-            hidden = self._text_forward(x, pos, rows.sub(r0, r1), keep="last")  # [r1-r0, 1, D]
-            logits = self._lm_head(hidden)
-            if logits_capture is not None:
-                logits_capture[r0:r1] = logits
-            perm = sampling.row_perm[r0:r1] if sampling is not None and sampling.row_perm is not None else None
-            first[r0:r1] = self._first_token(logits, sampling, perm - perm.min() if perm is not None else None,
-                                             scores=scores and scores[r0:r1], constraint=constraint, row0=r0)
+            hidden = self._text_forward(x, p, route, keep="last")  # [r1-r0, 1, D]
+            cut = head_rows or r1 - r0
+            for c0 in range(r0, r1, cut):
+                c1 = min(r1, c0 + cut)
+                logits = self._lm_head(hidden[c0 - r0 : c1 - r0])
+                if logits_capture is not None:
+                    logits_capture[c0:c1] = logits
+                perm = sampling.row_perm[c0:c1] if sampling is not None and sampling.row_perm is not None else None
+                by_row = uniforms is not None  # the rows' own settings and draws
+                first[c0:c1] = self._first_token(
+                    logits, Sampling(sampling.temperature[c0:c1], sampling.top_p[c0:c1]) if by_row else sampling,
+                    perm - perm.min() if perm is not None else None, uniforms=uniforms[c0:c1] if by_row else None,
+                    scores=scores and scores[c0:c1], constraint=constraint, row0=c0)
             hidden_last[r0:r1] = hidden[:, -1, :]
         return first, hidden_last, next_pos
 
-    def _place_images(self, images, rows: _Rows, mark) -> int:
-        """Image k's KV prefix into slot k of ``rows``: the raw images go through ONE ViT batch and every run of consecutive
-        slots through one ``_prefill_images`` (which, like ``load_encoded_image``, also writes the slot's e4m3 rows in the fp8
-        KV mode); EncodedImages are loaded.  Returns the prefix length, the same for every image."""
+    def _place_images(self, images, rows: _Rows, mark, slots: Optional[Sequence[int]] = None) -> List[int]:
+        """Image k's KV prefix into row k's slot of ``rows``: the raw images go through ONE ViT batch and every run of
+        consecutive rows through one ``_prefill_images`` (which, like ``load_encoded_image``, also writes the slot's e4m3
+        rows in the fp8 KV mode); EncodedImages are loaded -- into slot k, or, when ``rows`` has a slot table, into
+        ``slots[k]``, its host copy.  Returns every image's prefix length."""
         raw = [k for k, im in enumerate(images) if not isinstance(im, EncodedImage)]
         for k in raw:
             if not isinstance(images[k], Image.Image):
                 raise ValueError("image must be a PIL Image or EncodedImage")
-        pos = None
+        pos = [None] * len(images)
         if raw:
             img_emb = self._run_vision_encoder_batch([images[k] for k in raw], mark)
             mark("vision")
             for j0, j1 in _runs(raw):
-                pos = self._prefill_images(img_emb[j0:j1], rows.sub(raw[j0], raw[j1 - 1] + 1))
+                pos[raw[j0] : raw[j1 - 1] + 1] = [self._prefill_images(img_emb[j0:j1], rows.sub(raw[j0], raw[j1 - 1] + 1))] * (j1 - j0)
             mark("image_prefill")
         for k, im in enumerate(images):
             if isinstance(im, EncodedImage):
-                if pos is not None and im.pos != pos:
-                    raise ValueError("EncodedImage with a different prefix length than the rest of the batch")
-                self.load_encoded_image(im, k)
-                pos = im.pos
+                self.load_encoded_image(im, k if slots is None else slots[k])
+                pos[k] = im.pos
         return pos
+
+    def _sequence_embeddings(self, prompts: Sequence[Sequence[int]], images=None, mark=None):
+        """``embed(r0, r1)`` [r1-r0, T, D] for ``_prefill_groups`` over rows whose prompts are ``prompts``: the prompts'
+        embeddings, for rows whose image prefix is in place -- or, with ``images`` (every row's own, all raw; ONE ViT
+        batch, now), the fused prefill's rows.  There image prefix and prompt go through the decoder in ONE pass per group
+        of equal-length prompts ([bos | 729 image embeddings | prompt] at position 0).  The attention kernels evaluate
+        the reference's mask rule per element (bidirectional inside the first 730 positions, causal after), so this is
+        the same computation as the reference's two passes (moondream.py:228-262 then 280-321) up to accumulation order
+        -- one pass over the weights saved (fused_prefill = False keeps the two passes)."""
+        embed_prompts = lambda r0, r1: self._embed(torch.tensor(prompts[r0:r1], dtype=torch.int32))
+        if images is None:
+            return embed_prompts
+        img_emb = self._run_vision_encoder_batch(images, mark)
+        if mark is not None:
+            mark("vision")
+        bos = self._embed(torch.full((len(images), 1), self.config.tokenizer.bos_id, dtype=torch.int32))
+        return lambda r0, r1: torch.cat([bos[r0:r1], img_emb[r0:r1], embed_prompts(r0, r1)], dim=1)
 
     def _shared_routing(self, plan: RowPlan, pos: int) -> _Rows:
         """The routing of a shared plan's rows over its prefix table (every prefix ``pos`` positions long), checked."""
@@ -1452,22 +1481,14 @@ class MoondreamModel:
         if variants is not None:
             rows = _Rows(variants=self._variant_table([variants[i] for i in plan.order]), bank=self._bank)
         mark("start")
-        embed_prompts = lambda r0, r1: self._embed(torch.tensor(prompts[r0:r1], dtype=torch.int32))
         fused = fuse and self.fused_prefill and not share and all(isinstance(im, Image.Image) for im in plan.placed)
-        if fused:
-            # Every image is raw: image prefix and prompt go through the decoder in ONE pass per group of equal-length
-            # prompts ([bos | 729 image embeddings | prompt] at position 0).  The attention kernels evaluate the
-            # reference's mask rule per element (bidirectional inside the first 730 positions, causal after), so this is
-            # the same computation as the reference's two passes (moondream.py:228-262 then 280-321) up to accumulation
-            # order -- one pass over the weights saved (fused_prefill = False keeps the two passes).
-            img_emb = self._run_vision_encoder_batch(plan.placed, mark)
-            mark("vision")
-            bos = self._embed(torch.full((b, 1), self.config.tokenizer.bos_id, dtype=torch.int32))
-            embed = lambda r0, r1: torch.cat([bos[r0:r1], img_emb[r0:r1], embed_prompts(r0, r1)], dim=1)
-            pos = 0
-        else:
-            embed = embed_prompts
-            pos = self._place_images(plan.placed, _Rows() if share else rows, mark)
+        embed = self._sequence_embeddings(prompts, plan.placed if fused else None, mark)
+        pos = 0  # (fused: the one pass starts at the bos)
+        if not fused:
+            prefix = set(self._place_images(plan.placed, _Rows() if share else rows, mark))
+            if len(prefix) > 1:
+                raise ValueError("EncodedImage with a different prefix length than the rest of the batch")
+            pos = prefix.pop()
             if share:
                 rows = self._shared_routing(plan, pos)
                 if sampling is not None:
