@@ -440,6 +440,28 @@ md_status md_sample_rows(const void* logits, int64_t ld, int32_t batch, int32_t 
                          const float* temperature, const float* top_p, const float* uniforms,
                          int32_t* next, void* probs_out, int64_t ld_probs, void* stream);
 
+/* md_sample_rows with two more truncation rules per row: top_k (device int32 [batch]) and min_p (device fp32 [batch]).
+ * A sampled row (temperature[b] > 0) forms z = bf16(logit / T) and p = bf16(softmax(z)) as md_sample_top_p does and takes
+ * the tokens in descending p, ties by ascending id.  Each rule keeps a prefix of that order, all three judged on the same
+ * unrenormalised p:
+ *   top_p[b]:  md_sample_top_p's rule, bit for bit;
+ *   top_k[b]:  the first top_k[b] tokens; inside the boundary value the lowest ids survive.  <= 0 or >= vocab: off;
+ *   min_p[b]:  the tokens with p >= bf16(min_p[b] * p_max), p_max the row's largest bf16 probability (what
+ *              `probs >= min_p * probs.max()` gives on a bf16 tensor); the best token always survives.  <= 0: off;
+ *              values above 1 act as 1.
+ * The survivors are the SHORTEST of the three prefixes; they are renormalised and drawn exactly as md_sample_top_p's:
+ * q = bf16(p / bf16(sum kept)), inverse CDF over token ids with uniforms[b].  (HF / vLLM renormalise after top-k before
+ * top-p; here the cuts do not depend on an order of application.)  A row with top_k[b] <= 0 and min_p[b] <= 0 carries the
+ * bits of md_sample_rows, next[b] and probs_out row alike.  temperature[b] == 0 (greedy: md_argmax_bf16's id) and < 0 (idle:
+ * nothing read or written) are md_sample_rows' paths and read neither setting.  The order is realised as there, by the
+ * histogram over bf16 patterns; the walk over it carries a token count next to the mass, the top-k boundary is the
+ * pattern at which the count reaches k, the min-p boundary the smallest occupied pattern >= the threshold's, and the row's
+ * boundary the largest of the three patterns with the smallest survivor count inside it.  One workgroup of 1024 per row,
+ * md_sample_rows' LDS.  The values in the arrays are the caller's contract; no host sync, no allocation: capturable. */
+md_status md_sample_rows_filtered(const void* logits, int64_t ld, int32_t batch, int32_t vocab, int32_t suppress_id,
+                                  const float* temperature, const float* top_p, const int32_t* top_k, const float* min_p,
+                                  const float* uniforms, int32_t* next, void* probs_out, int64_t ld_probs, void* stream);
+
 /* Log-probability and rank of ONE GIVEN token per row: targets[r] in row r of logits (bf16 [rows][ld]).  One workgroup per row.
  *   Live tokens: v is live unless v == suppress_id, suppress_id >= 0 and row r is suppressed; row r is suppressed when
  *     suppress_rows == NULL or suppress_rows[r] != 0 (int32 [rows]).  The rule of md_argmax_bf16 / md_sample_* (moondream.py:517),

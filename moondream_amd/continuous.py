@@ -26,7 +26,8 @@ from typing import Callable, Deque, Dict, Iterator, List, Optional, Sequence, Tu
 import numpy as np
 
 from .constraint import FREE, TokenAutomaton, pack
-from .decode_loop import PENALTY_NEUTRAL, Constraint, DecodeChunk, Penalty, Sampling, check_penalties, check_top_logprobs, run_chunk
+from .decode_loop import (FILTER_NEUTRAL, PENALTY_NEUTRAL, Constraint, DecodeChunk, Penalty, Sampling, check_filters, check_penalties,
+                          check_top_logprobs, run_chunk)
 from .scores import HostScores, Scores
 
 DEFAULT_MAX_TOKENS = 768  # moondream.py (the reference's default, moondream.py:50-53)
@@ -81,6 +82,13 @@ class Request:
     penalties: Tuple[float, float, float] = PENALTY_NEUTRAL  # (repetition, presence, frequency): md_penalize_rows' rule
     constraint: Optional[TokenAutomaton] = None  # what the request may generate (md_constrain_rows); None: anything
     constraint_start: int = FREE  # its start state in the engine's table
+    top_k: int = 0      # sampled rows only: the first top_k tokens of the descending order (0: off) ...
+    min_p: float = 0.0  # ... and the tokens of probability >= min_p * the best one's (0: off): md_sample_rows_filtered
+
+    @property
+    def filtered(self) -> bool:
+        """A sampled request with a non-neutral ``top_k`` / ``min_p`` (a greedy one ignores them)."""
+        return self.temperature != 0 and (self.top_k, self.min_p) != FILTER_NEUTRAL
 
     @property
     def remaining(self) -> int:
@@ -327,7 +335,13 @@ class ContinuousEngine:
     free request) in the request's first chunk (``SlotScheduler.state_resets``: two small pinned copies and one
     index_copy_ on the stream, made by every chunk once the engine has seen a constraint).  Chunks with a constrained
     row run md_constrain_rows before each pick and are graphs of their own; all others take the graph of an engine
-    without constraints."""
+    without constraints.
+
+    ``top_k`` / ``min_p`` per request (``submit``; None: off): ``batch_generate_ids``' rule for a sampled request, the
+    first token included.  They are stored per row next to temperature and top-p, in a per-bucket pair of fixed-address
+    tables (int32 / fp32, pinned staging: one more small copy each) that only chunks with a filtered row fill; such
+    chunks pick with md_sample_rows_filtered and are graphs of their own, all others are the chunks of an engine without
+    the settings.  A request's ids depend on its own settings and seed only."""
 
     def __init__(self, model, max_live: int = 64, chunk: int = 16, temperature: float = 0.0, top_p: float = DEFAULT_TOP_P,
                  admit_threshold: Optional[int] = None, logprobs: bool = False, top_logprobs: Optional[int] = None,
@@ -362,11 +376,12 @@ class ContinuousEngine:
                seed: Optional[int] = None, ignore_eos: bool = False, variant: Optional[str] = None,
                temperature: Optional[float] = None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-               constraint: Optional[TokenAutomaton] = None) -> int:
+               constraint: Optional[TokenAutomaton] = None, top_k: Optional[int] = None, min_p: Optional[float] = None) -> int:
         """Queue one request; ``image`` is a PIL image or an EncodedImage.  ``eos_id`` None: the tokenizer's EOS
         (``ignore_eos``: none).  ``temperature`` / ``top_p`` None: the engine's.  The three penalties (None: neutral):
         one number each, ``batch_generate_ids``' rule and validation.  ``constraint``: one ``TokenAutomaton`` (None: free),
-        ``batch_generate_ids``' rule and validation; ValueError when the engine's table has no room for it.  Returns its id."""
+        ``batch_generate_ids``' rule and validation; ValueError when the engine's table has no room for it.  ``top_k`` /
+        ``min_p`` (None: off): one value each, ``batch_generate_ids``' rule and validation.  Returns its id."""
         from PIL import Image
 
         from .moondream import EncodedImage
@@ -382,6 +397,10 @@ class ContinuousEngine:
             if isinstance(x, (list, tuple)):
                 raise ValueError(f"{name}: one number per request, not {x!r}")
         pen = check_penalties(repetition_penalty, presence_penalty, frequency_penalty, 1)
+        for name, x in (("top_k", top_k), ("min_p", min_p)):
+            if isinstance(x, (list, tuple)):
+                raise ValueError(f"{name}: one value per request, not {x!r}")
+        filt = check_filters(top_k, min_p, 1)
         if not isinstance(image, (Image.Image, EncodedImage)):
             raise ValueError("image must be a PIL Image or EncodedImage")
         prompt = [int(p) for p in prompt_ids]
@@ -397,7 +416,8 @@ class ContinuousEngine:
         rid = self._next_rid
         self._next_rid += 1
         self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed, variant=vidx, temperature=temp, top_p=tp,
-                                  penalties=pen[0] if pen else PENALTY_NEUTRAL, constraint=constraint, constraint_start=start))
+                                  penalties=pen[0] if pen else PENALTY_NEUTRAL, constraint=constraint, constraint_start=start,
+                                  top_k=filt[0][0] if filt else 0, min_p=filt[0][1] if filt else 0.0))
         return rid
 
     def _register_constraint(self, a: TokenAutomaton) -> int:
@@ -507,10 +527,12 @@ class ContinuousEngine:
                  repetition_penalty: Union[None, float, Sequence[float]] = None,
                  presence_penalty: Union[None, float, Sequence[float]] = None,
                  frequency_penalty: Union[None, float, Sequence[float]] = None,
-                 constraints: Union[None, TokenAutomaton, Sequence[Optional[TokenAutomaton]]] = None):
+                 constraints: Union[None, TokenAutomaton, Sequence[Optional[TokenAutomaton]]] = None,
+                 top_k: Union[None, int, Sequence[int]] = None, min_p: Union[None, float, Sequence[float]] = None):
         """Ids for (images[i], prompts[i]) in input order; ``max_tokens`` one int or one per request, ``temperature`` and
         ``top_p`` one float or one per request (None: the engine's), the three penalties likewise (None: neutral),
-        ``constraints`` one ``TokenAutomaton`` or one entry per request (None: free).  ``return_logprobs`` (an engine made with
+        ``constraints`` one ``TokenAutomaton`` or one entry per request (None: free), ``top_k`` / ``min_p`` one value or
+        one per request (None: off).  ``return_logprobs`` (an engine made with
         ``logprobs=True``): (ids, logprobs, ranks), each in input order; an engine with ``top_logprobs``: alternatives too."""
         if return_logprobs and not self.logprobs:
             raise ValueError("generate(return_logprobs=True) needs ContinuousEngine(..., logprobs=True)")
@@ -535,8 +557,9 @@ class ContinuousEngine:
         if len(cons) != n:
             raise ValueError(f"constraints: {len(cons)} entries for {n} requests (one TokenAutomaton, or one entry per request)")
         pens = check_penalties(repetition_penalty, presence_penalty, frequency_penalty, n) or [PENALTY_NEUTRAL] * n
+        filts = check_filters(top_k, min_p, n) or [FILTER_NEUTRAL] * n
         rids = [self.submit(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant, temps[i], tps[i], *pens[i],
-                            constraint=cons[i]) for i in range(n)]
+                            constraint=cons[i], top_k=filts[i][0], min_p=filts[i][1]) for i in range(n)]
         if return_logprobs:  # (ids, logprobs, ranks), and alternatives on an engine with top_logprobs
             got3 = {rid: rest for rid, *rest in self.run(with_logprobs=True)}
             return tuple([got3[r][k] for r in rids] for k in range(4 if self.top_logprobs else 3))
@@ -614,6 +637,9 @@ class ContinuousEngine:
             draws = [float(self._uniforms(r, 1)[0]) if r.temperature != 0 else 0.0 for r in rows]
             st = m._h2d(torch.tensor([[r.temperature for r in rows], [r.top_p for r in rows], draws], dtype=torch.float32))
             pick = Sampling(st[0], st[1])
+            if any(r.filtered for r in rows):  # two more rows of settings: the first token is cut too
+                pick = replace(pick, top_k=m._h2d(torch.tensor([min(r.top_k, 2 ** 31 - 1) for r in rows], dtype=torch.int32)),
+                               min_p=m._h2d(torch.tensor([r.min_p for r in rows], dtype=torch.float32)))
         if any(r.constraint is not None for r in rows):  # the rows' start states, beside the engine's table
             con = self._constraint(m._h2d(torch.tensor([r.constraint_start for r in rows], dtype=torch.int32)), by_slot=False)
         scores = Scores.new((len(rows),), self.top_logprobs, m.device) if self.logprobs else None
@@ -669,6 +695,20 @@ class ContinuousEngine:
                     torch.zeros(bucket, dtype=torch.int64, device=m.device), rs_host)
 
         return self._penalty_hist + m._store.fixed("continuous_penalty", bucket, make)
+
+    def _filter_buffers(self, bucket: int):
+        """Per bucket, fixed addresses: the rows' top_k (int32 [bucket]) and min_p (fp32 [bucket]), each with its pinned
+        staging -- what a chunk with a filtered row reads beside ``_buffers``' temperature and top-p."""
+        import torch
+
+        def make():
+            with torch.inference_mode(False):
+                k_host = torch.zeros(bucket, dtype=torch.int32, pin_memory=True)
+                m_host = torch.zeros(bucket, dtype=torch.float32, pin_memory=True)
+            return (torch.zeros(bucket, dtype=torch.int32, device=self.model.device), k_host,
+                    torch.zeros(bucket, dtype=torch.float32, device=self.model.device), m_host)
+
+        return self.model._store.fixed("continuous_filters", bucket, make)
 
     def _constraint(self, state=None, by_slot: bool = True) -> Constraint:
         """The engine's table as a ``Constraint`` record over ``state`` (None: the per-slot states), made on first use;
@@ -749,6 +789,16 @@ class ContinuousEngine:
                     k = min(n, r.remaining)
                     uh[:k, r_idx] = self._uniforms(r, k).numpy()
             u_dev.copy_(u_host, non_blocking=True)
+        filt = None
+        if any(r.filtered for r in plan.rows):  # (sampled rows: ``sample`` holds) the rows' cuts, padding rows off
+            k_dev, k_host, m_dev, m_host = self._filter_buffers(B)
+            kh, mh = k_host.numpy(), m_host.numpy()
+            kh[:], mh[:] = 0, 0.0
+            for r_idx, r in enumerate(plan.rows):
+                kh[r_idx], mh[r_idx] = min(r.top_k, 2 ** 31 - 1), r.min_p
+            k_dev.copy_(k_host, non_blocking=True)
+            m_dev.copy_(m_host, non_blocking=True)
+            filt = (k_dev, m_dev)
         penalty = None
         if any(r.penalties != PENALTY_NEUTRAL for r in plan.rows):
             # the rows' settings (padding rows neutral) and the slots whose history starts here, in two small copies behind
@@ -780,6 +830,8 @@ class ContinuousEngine:
         # a sampling row in the chunk: every row picks with its own settings (a greedy row its argmax again, an idle row
         # nothing); the settings are device data, in the allocation of the uniforms
         pick = Sampling(u_dev[c * B : c * B + B], u_dev[c * B + B :]) if sample else None
+        if filt is not None:  # ... and a filtered row: the launch that also cuts by each row's top_k / min_p
+            pick = replace(pick, top_k=filt[0], min_p=filt[1])
         chunk = DecodeChunk(B, hist, pos_d, rows_of, m.config.tokenizer.answer_id, self._decode_ws_bytes(B), pick,
                             u_dev[: c * B].view(c, B), penalty=penalty, constraint=constraint,
                             **(scores.chunk_fields() if scores else {}))

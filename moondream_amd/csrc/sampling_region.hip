@@ -212,16 +212,27 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 constexpr int SAMPLE_LDS = HIST_BINS * 4 + 16 * 4 + SAMPLE_THREADS * 4 + 16 * 4;  // histogram, wave partials, block scan, results
 
 // One row, one workgroup of SAMPLE_THREADS: lr the row's logits, u its uniform, next its token, pr its row of probs_out (or
-// nullptr).  The body of both sampling kernels; smem is the workgroup's SAMPLE_LDS bytes.
+// nullptr).  The body of the sampling kernels; smem is the workgroup's SAMPLE_LDS bytes.
+// FILTER (md_sample_rows_filtered): two more cuts of the same descending order, each a pair (boundary pattern, survivors
+// inside it) like the top-p cut, all three taken on the same unrenormalised p:
+//   top_k > 0 and < vocab: the first top_k tokens -- the walk carries a token COUNT next to the mass; the boundary is the
+//     pattern at which the running count reaches top_k, of which top_k - (count above it) tokens survive;
+//   min_p > 0: the tokens with p >= bf16(min_p * p_max) -- the boundary is the smallest occupied pattern >= that
+//     threshold's, kept whole (p_max: the largest occupied pattern, so the best token always survives).
+// The row's boundary is the LARGEST of the three patterns (the shortest prefix); where cuts share it, the smallest
+// survivor count.  With FILTER false nothing of this is compiled: the two older kernels are what they were.
+template <bool FILTER>
 __device__ __forceinline__ void sample_top_p_row(char* smem, const bf16_t* __restrict__ lr, int vocab, int suppress,
                                                  float temperature, float top_p, const float* __restrict__ u,
-                                                 int32_t* __restrict__ next, bf16_t* __restrict__ pr) {
+                                                 int32_t* __restrict__ next, bf16_t* __restrict__ pr, int top_k = 0,
+                                                 float min_p = 0.f) {
   unsigned* hist = (unsigned*)smem;                    // [HIST_BINS] counts per bf16 bit pattern
   float* red = (float*)(smem + HIST_BINS * 4);         // [16]
   float* scan = red + 16;                              // [SAMPLE_THREADS] block scans
-  int* shared_i = (int*)(scan + SAMPLE_THREADS);       // [8] boundary pattern, survivors in it, drawn token, ...
+  int* shared_i = (int*)(scan + SAMPLE_THREADS);       // [16] boundary pattern, survivors in it, drawn token, ...
   const int tid = threadIdx.x;
   const float inv_t = temperature;  // division, not a reciprocal multiply: the reference divides
+  if (FILTER && tid == 0) shared_i[5] = 0;  // the largest occupied pattern (the reductions below order it before its use)
 
   // ---- z = bf16(logit / T), softmax statistics
   float mx = -INFINITY;
@@ -251,10 +262,16 @@ __device__ __forceinline__ void sample_top_p_row(char* smem, const bf16_t* __res
   constexpr int PER = HIST_BINS / SAMPLE_THREADS;
   const int top_pat = HIST_BINS - 1 - tid * PER;  // this thread's largest pattern
   float mass = 0.f;
+  int cnt = 0, my_top = 0;  // FILTER: this thread's tokens of positive probability, its largest occupied pattern
   for (int k = 0; k < PER; ++k) {
     const int pat = top_pat - k;
     if (hist[pat]) mass += (float)hist[pat] * bf2f((bf16_t)pat);  // empty patterns include inf / NaN encodings
+    if (FILTER && hist[pat] && bf2f((bf16_t)pat) > 0.f) {  // the patterns the second walk visits
+      cnt += (int)hist[pat];
+      if (my_top == 0) my_top = pat;
+    }
   }
+  if (FILTER && my_top > 0) atomicMax(&shared_i[5], my_top);
   // exclusive prefix over threads (descending value order == ascending tid)
   scan[tid] = mass;
   __syncthreads();
@@ -265,16 +282,41 @@ __device__ __forceinline__ void sample_top_p_row(char* smem, const bf16_t* __res
     __syncthreads();
   }
   float before = scan[tid] - mass;  // mass of all strictly larger values owned by earlier threads
+  int cnt_before = 0;               // FILTER: tokens of all strictly larger values owned by earlier threads
+  if (FILTER) {
+    // the count's exclusive prefix: a shuffle scan per wave, then the 16 wave totals through `red` (free since block_sum)
+    int incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o, 64);
+      if ((tid & 63) >= o) incl += v;
+    }
+    int* wave_cnt = (int*)red;
+    if ((tid & 63) == 63) wave_cnt[tid >> 6] = incl;
+    __syncthreads();
+    cnt_before = incl - cnt;
+    for (int w = 0; w < (tid >> 6); ++w) cnt_before += wave_cnt[w];
+  }
   if (tid == 0) {
     shared_i[0] = HIST_BINS;  // boundary pattern: the SMALLEST value that still has a surviving token
     shared_i[1] = 0;          // how many tokens of that value survive
     shared_i[3] = -1;         // the drawn token
     shared_i[4] = -1;         // last survivor (fallback when rounding puts the target past the end)
+    if (FILTER) {
+      shared_i[6] = 0;          // top-k boundary pattern (0: no cut) ...
+      shared_i[7] = 0;          // ... and its survivors
+      shared_i[8] = HIST_BINS;  // min-p boundary pattern
+    }
   }
   __syncthreads();
+  // FILTER: the clamps -- k <= 0 or >= vocab is off, m <= 0 (or NaN) is off, m > 1 is 1
+  const int k_cut = (FILTER && top_k > 0 && top_k < vocab) ? top_k : 0;
+  const bool m_on = FILTER && min_p > 0.f;
+  int m_thr = 0;  // pattern of bf16(float(min_p) * p_max): positive bf16 patterns order as their values do
+  if (m_on) m_thr = (int)(f2bf(fminf(min_p, 1.f) * bf2f((bf16_t)shared_i[5])) & 0x7fffu);
   // `before` only grows as the values descend, so the values with survivors form a prefix of the
   // descending order and every value above the boundary survives whole
-  int my_b = HIST_BINS, my_n = 0;
+  int my_b = HIST_BINS, my_n = 0, my_m = HIST_BINS;
   const float tp16 = bf2f(f2bf(top_p));
   for (int k = 0; k < PER; ++k) {
     const int pat = top_pat - k;
@@ -294,15 +336,39 @@ __device__ __forceinline__ void sample_top_p_row(char* smem, const bf16_t* __res
         my_b = pat;
         my_n = lo + 1;
       }
+      if (FILTER) {
+        if (k_cut && cnt_before < k_cut && cnt_before + (int)c >= k_cut) {  // one pattern at most: the count only grows
+          shared_i[6] = pat;
+          shared_i[7] = k_cut - cnt_before;
+        }
+        cnt_before += (int)c;
+        if (m_on && pat >= m_thr) my_m = pat;  // descending walk: ends at this thread's smallest such pattern
+      }
     }
     if (c) before += (float)c * v;
   }
   if (my_b < HIST_BINS) atomicMin(&shared_i[0], my_b);
+  if (FILTER && my_m < HIST_BINS) atomicMin(&shared_i[8], my_m);
   __syncthreads();
-  const int bpat = shared_i[0];
-  if (my_b == bpat && bpat < HIST_BINS) shared_i[1] = my_n;  // every pattern has exactly one owner
+  const int tp_pat = shared_i[0];
+  if (my_b == tp_pat && tp_pat < HIST_BINS) shared_i[1] = my_n;  // every pattern has exactly one owner
   __syncthreads();
-  const int n_boundary = shared_i[1];
+  int bpat = tp_pat, n_boundary = shared_i[1];
+  if (FILTER) {  // the same values in every thread: the largest boundary, the smallest count inside it
+    const int k_pat = shared_i[6], k_n = shared_i[7];
+    if (k_pat > bpat || (k_pat == bpat && k_n < n_boundary)) {
+      bpat = k_pat;
+      n_boundary = k_n;
+    }
+    if (m_on) {
+      const int m_pat = shared_i[8];  // (an occupied pattern, or HIST_BINS: nothing reaches the threshold, nothing survives)
+      const int m_n = m_pat < HIST_BINS ? (int)hist[m_pat] : 0;
+      if (m_pat > bpat || (m_pat == bpat && m_n < n_boundary)) {
+        bpat = m_pat;
+        n_boundary = m_n;
+      }
+    }
+  }
 
   // ---- survivors: pattern > bpat, or pattern == bpat and among its n_boundary lowest ids.
   // Contiguous chunks per thread keep id order; two block scans (equal-count, kept mass).
@@ -430,8 +496,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_top_p_kernel(const bf16
                                                                       bf16_t* __restrict__ probs_out, int64_t ldp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int b = blockIdx.x;
-  sample_top_p_row(smem, logits + (int64_t)b * ld, vocab, suppress, temperature, top_p, uniforms + b, next + b,
-                   probs_out ? probs_out + (int64_t)b * ldp : nullptr);
+  sample_top_p_row<false>(smem, logits + (int64_t)b * ld, vocab, suppress, temperature, top_p, uniforms + b, next + b,
+                          probs_out ? probs_out + (int64_t)b * ldp : nullptr);
 }
 
 // per-row settings: temperature[b] > 0 samples the row with (temperature[b], top_p[b], uniforms[b]), == 0 takes its argmax,
@@ -451,8 +517,28 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const bf16_
     argmax_row(smem, lr, vocab, suppress, next + b);
     return;
   }
-  sample_top_p_row(smem, lr, vocab, suppress, t, top_p[b], uniforms + b, next + b,
-                   probs_out ? probs_out + (int64_t)b * ldp : nullptr);
+  sample_top_p_row<false>(smem, lr, vocab, suppress, t, top_p[b], uniforms + b, next + b,
+                          probs_out ? probs_out + (int64_t)b * ldp : nullptr);
+}
+
+// sample_rows_kernel with two more per-row settings, top_k[b] (int32) and min_p[b] (fp32): a sampled row is also cut to
+// its first top_k[b] tokens and to the tokens of probability >= bf16(min_p[b] * p_max) (sample_top_p_row<true>).  A row of
+// top_k[b] <= 0 (or >= vocab) and min_p[b] <= 0 carries the bits of sample_rows_kernel; greedy and idle rows read neither.
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_filtered_kernel(
+    const bf16_t* __restrict__ logits, int64_t ld, int vocab, int suppress, const float* __restrict__ temperature,
+    const float* __restrict__ top_p, const int32_t* __restrict__ top_k, const float* __restrict__ min_p,
+    const float* __restrict__ uniforms, int32_t* __restrict__ next, bf16_t* __restrict__ probs_out, int64_t ldp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int b = blockIdx.x;
+  const float t = temperature[b];
+  if (t < 0.f) return;  // idle: next[b], the probs_out row and the row's logits stay untouched
+  const bf16_t* lr = logits + (int64_t)b * ld;
+  if (t == 0.f) {
+    argmax_row(smem, lr, vocab, suppress, next + b);
+    return;
+  }
+  sample_top_p_row<true>(smem, lr, vocab, suppress, t, top_p[b], uniforms + b, next + b,
+                         probs_out ? probs_out + (int64_t)b * ldp : nullptr, top_k[b], min_p[b]);
 }
 
 // ---------------------------------------------------------------------------
@@ -1113,6 +1199,19 @@ extern "C" md_status md_sample_rows(const void* logits, int64_t ld, int32_t batc
   MD_TRY(md_ensure_dynamic_lds((const void*)sample_rows_kernel, SAMPLE_LDS));
   hipLaunchKernelGGL(sample_rows_kernel, dim3(batch), dim3(SAMPLE_THREADS), SAMPLE_LDS, (hipStream_t)stream, (const bf16_t*)logits,
                      ld, vocab, suppress_id, temperature, top_p, uniforms, next, (bf16_t*)probs_out, ld_probs);
+  return md_launch_status();
+}
+
+extern "C" md_status md_sample_rows_filtered(const void* logits, int64_t ld, int32_t batch, int32_t vocab, int32_t suppress_id,
+                                             const float* temperature, const float* top_p, const int32_t* top_k,
+                                             const float* min_p, const float* uniforms, int32_t* next, void* probs_out,
+                                             int64_t ld_probs, void* stream) {
+  MD_CHECK_ARG(logits && temperature && top_p && top_k && min_p && uniforms && next && batch > 0 && vocab > 0 && ld >= vocab);
+  MD_CHECK_ARG(probs_out == nullptr || ld_probs >= vocab);
+  MD_TRY(md_ensure_dynamic_lds((const void*)sample_rows_filtered_kernel, SAMPLE_LDS));
+  hipLaunchKernelGGL(sample_rows_filtered_kernel, dim3(batch), dim3(SAMPLE_THREADS), SAMPLE_LDS, (hipStream_t)stream,
+                     (const bf16_t*)logits, ld, vocab, suppress_id, temperature, top_p, top_k, min_p, uniforms, next,
+                     (bf16_t*)probs_out, ld_probs);
   return md_launch_status();
 }
 

@@ -103,6 +103,65 @@ def refuse_penalties(settings: Optional[dict], where: str, n: int = 1) -> None:
         raise ValueError(f"repetition_penalty / presence_penalty / frequency_penalty are not served by {where}")
 
 
+FILTER_SETTINGS = ("top_k", "min_p")
+FILTER_NEUTRAL = (0, 0.0)
+
+
+def check_filters(top_k, min_p, n: int) -> Optional[List[Tuple[int, float]]]:
+    """The ``top_k`` / ``min_p`` arguments of the generation calls, each one value or one per row (None: off) -> one
+    (top_k, min_p) pair per row, or None when every row is neutral (0, 0.0).  ValueError for a ``top_k`` that is not an
+    integer >= 0 (a bool is none), a ``min_p`` that is not finite or lies outside [0, 1], or a list that is not ``n`` long:
+    host values only, before any GPU work."""
+    cols = []
+    for name, x in zip(FILTER_SETTINGS, (top_k, min_p)):
+        try:
+            vals = [x] * n if x is None or isinstance(x, (numbers.Real, str)) else list(x)
+        except TypeError:
+            raise ValueError(f"{name} must be one value or one per row, not {x!r}") from None
+        if len(vals) != n:
+            raise ValueError(f"{name}: {len(vals)} values for {n} rows (one value, or one per row)")
+        col = []
+        for v in vals:
+            if v is None:
+                col.append(FILTER_NEUTRAL[len(cols)])
+            elif name == "top_k":
+                try:
+                    k = -1 if isinstance(v, bool) else operator.index(v)
+                except TypeError:
+                    k = -1
+                if not 0 <= k < 2 ** 31:
+                    raise ValueError(f"top_k must be an integer >= 0 (0: off), not {v!r}")
+                col.append(k)
+            else:
+                try:
+                    f = float("nan") if isinstance(v, (bool, str)) else float(v)
+                except (TypeError, ValueError):
+                    f = float("nan")
+                if not (math.isfinite(f) and 0.0 <= f <= 1.0):
+                    raise ValueError(f"min_p must be a number in [0, 1] (0: off), not {v!r}")
+                col.append(f)
+        cols.append(col)
+    rows = list(zip(*cols))
+    return None if all(r == FILTER_NEUTRAL for r in rows) else rows
+
+
+def filters_of(settings: Optional[dict]) -> dict:
+    """The ``top_k`` / ``min_p`` entries of a ``settings`` dict as keyword arguments of the generation calls (absent: off)."""
+    st = settings or {}
+    return {name: st.get(name, neutral) for name, neutral in zip(FILTER_SETTINGS, FILTER_NEUTRAL)}
+
+
+def refuse_filters(settings: Optional[dict], where: str, n: int = 1) -> None:
+    """An entry point that does not serve the sampling filters: ValueError naming ``where`` when ``settings`` carries a
+    non-neutral one (and the validation errors of ``check_filters`` for a value that is none)."""
+    st = filters_of(settings)
+    for name in FILTER_SETTINGS:  # a per-row list is judged by its values, whatever its length
+        if isinstance(st[name], (list, tuple)):
+            n = len(st[name])
+    if check_filters(st["top_k"], st["min_p"], n) is not None:
+        raise ValueError(f"top_k / min_p are not served by {where}")
+
+
 @dataclass(frozen=True, eq=False)
 class Penalty:
     """The penalty state of a chunk (md_penalize_rows), all device memory at fixed addresses.  ``repetition``, ``presence``
@@ -153,16 +212,25 @@ class Sampling:
     uniform per (token, sequence).  Two floats are a whole call's settings: the uniforms come from ``generator`` (a device
     generator; None: the device's default one) and row i draws the uniform of row ``row_perm[i]`` (device int64 [B]: the
     shared-prefix rows see the draws of the copy path's row order).  Two device fp32 [B] tensors are every row's own
-    settings (md_sample_rows): temperature > 0 samples, 0 takes the argmax, < 0 leaves the row alone."""
+    settings (md_sample_rows): temperature > 0 samples, 0 takes the argmax, < 0 leaves the row alone.  ``top_k`` (device
+    int32 [B]) and ``min_p`` (device fp32 [B]), with per-row settings only and both or neither: every sampled row is also cut
+    to its first ``top_k`` tokens and to the tokens of probability >= min_p * the best one's (md_sample_rows_filtered; 0:
+    off).  None, the default: the picks, launches and graph keys of a record without the fields."""
 
     temperature: Any
     top_p: Any
     generator: Any = None
     row_perm: Any = None
+    top_k: Any = None
+    min_p: Any = None
 
     @property
     def per_row(self) -> bool:
         return hasattr(self.temperature, "data_ptr")
+
+    @property
+    def filtered(self) -> bool:
+        return self.top_k is not None
 
 
 @dataclass(frozen=True, eq=False)
@@ -202,7 +270,8 @@ class DecodeChunk:
     ``tokens[i]`` and writes ``tokens[i + 1]`` (int32 [>= n + 1, b]); ``pos`` (int32 [b]) is advanced by the steps;
     ``rows_of(i)`` is the routing of step i (``_Rows``; ``rows_of(0)`` stands for the chunk in the graph key: the others
     differ in data at fixed addresses only).  ``pick`` None keeps each step's argmax; otherwise step i draws every row from
-    ``uniforms[i]`` (fp32 [>= n, b]) with the call's settings (``_pick``) or each row's own (``_pick_rows``).
+    ``uniforms[i]`` (fp32 [>= n, b]) with the call's settings (``_pick``) or each row's own (``_pick_rows``; a record with
+    ``top_k`` / ``min_p``: ``_pick_rows_filtered``, and the two addresses join the graph key).
     ``logprobs`` = (fp32, int32) planes [>= n, b]: row i takes the log-probability and rank of the tokens of step i.
     ``topk`` = (int32 ids, fp32 log-probabilities) planes [>= n, b, k]: row i takes the k alternatives of every row's
     decision in step i (md_topk_logprobs after the step's md_token_logprobs, gated by the step's tokens); with ``logprobs`` only.
@@ -243,7 +312,7 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     stream: the chunk is replayed from the graph captured for it on that stream, or, first, run eagerly and captured
     (``model._replay_or_capture``: its ``GraphStore``'s, ``may_capture`` too).  The key starts (``tag``, stream) and names everything
     the launches bake in.  Returns True when it captured.  Besides that, the model gives the buffers (_decode_logits, _workspace,
-    _kv_struct) and the launches (_decode_step, _decode_step_b1, _decode_step_reason, _penalize, _constrain, _pick, _pick_rows, _token_logprobs, _topk_logprobs)."""
+    _kv_struct) and the launches (_decode_step, _decode_step_b1, _decode_step_reason, _penalize, _constrain, _pick, _pick_rows, _pick_rows_filtered, _token_logprobs, _topk_logprobs)."""
     c = chunk
     pieces = c.step is not None
     assert c.reason is None or (not pieces and not c.b1 and c.logprobs is None and c.pick is not None and c.pick.per_row)
@@ -260,6 +329,13 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     lp, rk = c.logprobs if c.logprobs is not None else (None, None)
     tk_ids, tk_lp = c.topk if c.topk is not None else (None, None)
     by_row = c.pick is not None and c.pick.per_row
+    assert c.pick is None or not c.pick.filtered or (by_row and c.pick.min_p is not None)
+
+    def pick_rows(lg, suppress_id, u, out):  # every row's own settings; with the two filters the launch that applies them
+        if c.pick.filtered:
+            model._pick_rows_filtered(lg, c.pick.temperature, c.pick.top_p, c.pick.top_k, c.pick.min_p, suppress_id, u, out=out)
+        else:
+            model._pick_rows(lg, c.pick.temperature, c.pick.top_p, suppress_id, u, out=out)
     # penalised or masked logits are picked from again: the fused step's argmax saw the raw ones
     again = c.pick if c.pick is not None or (c.penalty is None and c.constraint is None) else Sampling(0.0, 0.0)
 
@@ -269,7 +345,7 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
             if c.reason is not None:
                 # the step masks its logits per row and leaves the pick to the per-row kernel, nothing suppressed there
                 model._decode_step_reason(c.rows_of(i), c.reason, i, tok_in, c.pos, c.b, logits, ws, kv)
-                model._pick_rows(left, c.pick.temperature, c.pick.top_p, -1, c.uniforms[i], out=tok_out)
+                pick_rows(left, -1, c.uniforms[i], tok_out)
                 continue
             if c.b1:
                 model._decode_step_b1(tok_in, tok_out, c.pos, c.suppress_id, logits, ws, kv)
@@ -283,7 +359,7 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
             # a fused step wrote its argmax to tok_out: a pick draws from the logits it left instead (of per-row settings,
             # a greedy row takes the same argmax again and an idle row keeps what is there)
             if by_row:
-                model._pick_rows(lg, c.pick.temperature, c.pick.top_p, c.suppress_id, c.uniforms[i], out=tok_out)
+                pick_rows(lg, c.suppress_id, c.uniforms[i], tok_out)
             elif again is not None:
                 model._pick(lg, again.temperature, again.top_p, c.suppress_id, again.generator,
                             uniforms=c.uniforms[i] if c.uniforms is not None else None, out=tok_out)
@@ -300,6 +376,8 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     # attention kernel a step bakes in; the routing's part carries the bank's generation (its ranks are launch shapes).
     if by_row:
         pick = ("rows", c.pick.temperature.data_ptr(), c.pick.top_p.data_ptr())
+        if c.pick.filtered:  # another launch: another graph; without the fields the key is what it was
+            pick += ("filtered", c.pick.top_k.data_ptr(), c.pick.min_p.data_ptr())
     else:
         pick = None if c.pick is None else (float(c.pick.temperature), float(c.pick.top_p))
     key = (tag, capture_stream, c.b, n, c.suppress_id, c.tokens.data_ptr(), c.pos.data_ptr(), ws.data_ptr(), kv.k, kv.k8 or 0,

@@ -20,7 +20,7 @@ import torch
 
 from .config import MoondreamConfig
 from .constraint import refuse_constraints
-from .decode_loop import refuse_penalties
+from .decode_loop import refuse_filters, refuse_penalties
 from .moondream import MoondreamModel
 
 
@@ -75,6 +75,7 @@ class HfMoondream:
         are not part of this wrapper's calls (ValueError for a non-neutral one), nor are ``constraints``."""
         refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
+        refuse_filters(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         answer = self.query(image_embeds, question, settings=kwargs.get("settings"))["answer"].strip()
         if result_queue is not None:
             result_queue.put(answer)
@@ -87,6 +88,7 @@ class HfMoondream:
         greedy).  ``settings={"temperature": 0}`` is the greedy form; ``max_new_tokens`` bounds the answers."""
         refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
+        refuse_filters(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         self._setup_caches()
         settings = dict(kwargs.get("settings") or {})
         settings.setdefault("max_tokens", kwargs.get("max_new_tokens", kwargs.get("max_tokens", 256)))
@@ -104,6 +106,7 @@ class HfMoondream:
         form is a ``query``; anything else is tokenised and continued as is after the image prefix."""
         refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
+        refuse_filters(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         q = extract_question(prompt)
         if q is not None:
             return [self.model_query(image_embeds, q)]

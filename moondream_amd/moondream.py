@@ -32,8 +32,8 @@ from . import _lib
 from .config import MoondreamConfig
 from .constraint import FREE, TokenAutomaton, check_constraints, pack, pow2_at_least, refuse_constraints
 from .crop_staging import CropStager, crop_workers, upload_unique
-from .decode_loop import (Constraint, DecodeChunk, Penalty, ReasonChunk, Sampling, check_penalties, check_score_settings, check_top_logprobs,
-                          penalties_of, refuse_penalties, run_chunk)
+from .decode_loop import (Constraint, DecodeChunk, Penalty, ReasonChunk, Sampling, check_filters, check_penalties, check_score_settings,
+                          check_top_logprobs, filters_of, penalties_of, refuse_filters, refuse_penalties, run_chunk)
 from .graph_store import GraphStore
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
@@ -1021,6 +1021,43 @@ class MoondreamModel:
         )
         return nxt
 
+    def _pick_rows_filtered(self, logits: torch.Tensor, temperature_dev: torch.Tensor, top_p_dev: torch.Tensor,
+                            top_k_dev: torch.Tensor, min_p_dev: torch.Tensor, suppress_id: int, uniforms: torch.Tensor,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``_pick_rows`` with every row's two further truncation rules (md_sample_rows_filtered): ``top_k_dev`` device int32
+        [B], ``min_p_dev`` device fp32 [B].  A sampled row keeps the shortest of its three prefixes of the descending
+        order -- top-p's, its first ``top_k`` tokens, the tokens of probability >= min_p * the best one's -- all judged on
+        the same unrenormalised distribution; a row of (0, 0) is ``_pick_rows``' row bit for bit; greedy and idle rows read
+        neither.  With ``out`` nothing is allocated (captured decode steps)."""
+        b, v = logits.shape
+        for t in (temperature_dev, top_p_dev, min_p_dev, uniforms):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == b and t.device == logits.device
+        assert top_k_dev.dtype == torch.int32 and top_k_dev.is_contiguous() and top_k_dev.numel() == b and top_k_dev.device == logits.device
+        nxt = out if out is not None else torch.empty(b, dtype=torch.int32, device=self._device)
+        _lib.check(
+            self.lib.md_sample_rows_filtered(logits.data_ptr(), logits.stride(0), b, v, suppress_id, temperature_dev.data_ptr(),
+                                             top_p_dev.data_ptr(), top_k_dev.data_ptr(), min_p_dev.data_ptr(), uniforms.data_ptr(),
+                                             nxt.data_ptr(), None, 0, self._stream()),
+            "md_sample_rows_filtered",
+        )
+        return nxt
+
+    def _filter_record(self, sampling: Optional[Sampling], rows: Optional[Sequence[Tuple[int, float]]]) -> Optional[Sampling]:
+        """A call's sampling settings with ``check_filters``' pairs, one per row in the decode loop's row order -> the
+        per-row ``Sampling`` record that carries them (every row the call's temperature and top-p, its own top-k and
+        min-p; the call's generator and draw order kept).  ``sampling`` itself for no pairs, or for a greedy call: the
+        filters cut a sampled row only.  The buffers are the store's, one set per row count: captured chunks keep their
+        addresses."""
+        if rows is None or sampling is None:
+            return sampling
+        b = len(rows)
+        f, k = self._store.fixed("filters", b, lambda: (torch.empty(3, b, dtype=torch.float32, device=self._device),
+                                                        torch.empty(b, dtype=torch.int32, device=self._device)))
+        f.copy_(self._h2d(torch.tensor([[float(sampling.temperature)] * b, [float(sampling.top_p)] * b, [r[1] for r in rows]],
+                                       dtype=torch.float32)))
+        k.copy_(self._h2d(torch.tensor([min(r[0], 2 ** 31 - 1) for r in rows], dtype=torch.int32)))
+        return replace(sampling, temperature=f[0], top_p=f[1], top_k=k, min_p=f[2])
+
     def _penalize(self, logits: torch.Tensor, tok_in: torch.Tensor, rows: "_Rows", pen: Penalty):
         """Every row's consumed token ``tok_in[r]`` (device int32 [B]) joins its history in ``pen`` and the logits [B, V] of
         the tokens in that history take the row's penalties in place: md_penalize_rows.  A row's history is its own, or
@@ -1164,7 +1201,7 @@ class MoondreamModel:
                      constraint: Optional[Constraint] = None, row0: int = 0) -> torch.Tensor:
         """The first generated token of every row, int32 [B], from its prompt pass's logits [B, V]: the argmax (``pick``
         None), a draw with the call's settings (``row_perm``: the draw order of these rows) or with each row's own (and
-        ``uniforms`` fp32 [B]).  Nothing is suppressed (moondream.py:313-318).  ``scores`` (a record over [B]): filled with
+        ``uniforms`` fp32 [B]; a record with ``top_k`` / ``min_p`` is filtered like any later token).  Nothing is suppressed (moondream.py:313-318).  ``scores`` (a record over [B]): filled with
         the decision's log-probability, rank and alternatives, unsuppressed like the pick.  ``constraint``: these rows are
         rows ``row0 ..`` of the record -- the tokens their start states forbid lose their logits (in place) before the
         pick, and the scores are those of the masked logits."""
@@ -1173,6 +1210,8 @@ class MoondreamModel:
             self._constrain(logits, None, _Rows(), constraint, row0)
         if pick is None:
             first = self._pick(logits, 0.0, 0.0)
+        elif pick.filtered:
+            first = self._pick_rows_filtered(logits, pick.temperature, pick.top_p, pick.top_k, pick.min_p, -1, uniforms)
         elif pick.per_row:
             first = self._pick_rows(logits, pick.temperature, pick.top_p, -1, uniforms)
         else:
@@ -1276,7 +1315,8 @@ class MoondreamModel:
 
             chunk = DecodeChunk(b, hist, pos_t, lambda i: rows, suppress_id, pick=sampling or Sampling(0.0, 0.0), step=lora_step,
                                 penalty=penalty, constraint=constraint)
-            graphs, uniforms = False, None
+            # (a per-row record -- top_k / min_p -- has no per-step draw of its own: it keeps the uniforms taken up front)
+            graphs, uniforms = False, uniforms if sampling is not None and sampling.per_row else None
         else:
             need = self._decode_ws_bytes(rows, b)
             # one sequence, greedy, plain contiguous routing: the whole step as ONE persistent launch (csrc/decode_b1.hip) when the
@@ -1363,7 +1403,8 @@ class MoondreamModel:
         at position ``pos`` (one int, or one per group) into the slots of ``rows.sub(r0, r1)`` (or of the group's own entry
         of ``rows``, one routing per group, already cut), then lm_head and the pick of the first token (``_first_token``;
         ``sampling`` None: argmax; a group draws in its rows' order among themselves in ``sampling.row_perm``; per-row
-        settings, fp32 [B] like their ``uniforms``, are cut like the rows).  ``head_rows``: lm_head, the pick and what goes
+        settings, fp32 [B] like their ``uniforms``, are cut like the rows; without ``uniforms`` such rows draw from
+        ``sampling.generator`` as the call's settings would).  ``head_rows``: lm_head, the pick and what goes
         with it run in cuts of at most so many rows of a pass (None: the whole pass).
         Returns (first int32 [B], hidden_last [B, D], next_pos list); the groups' logits go to ``logits_capture`` [B, V], each
         first decision's log-probability, rank and alternatives (unsuppressed, like the pick) to ``scores``, a record over [B].
@@ -1390,10 +1431,17 @@ class MoondreamModel:
                 if logits_capture is not None:
                     logits_capture[c0:c1] = logits
                 perm = sampling.row_perm[c0:c1] if sampling is not None and sampling.row_perm is not None else None
-                by_row = uniforms is not None  # the rows' own settings and draws
+                by_row = sampling is not None and sampling.per_row  # the rows' own settings and draws
+                cut_of = lambda t: t[c0:c1] if t is not None else None
+                draws = uniforms[c0:c1] if uniforms is not None else None
+                if by_row and draws is None:  # the call's generator: the draws ``_pick`` makes for these rows
+                    draws = torch.rand(c1 - c0, device=self._device, dtype=torch.float32, generator=sampling.generator)
+                    if perm is not None:
+                        draws = draws[perm - perm.min()].contiguous()
                 first[c0:c1] = self._first_token(
-                    logits, Sampling(sampling.temperature[c0:c1], sampling.top_p[c0:c1]) if by_row else sampling,
-                    perm - perm.min() if perm is not None else None, uniforms=uniforms[c0:c1] if by_row else None,
+                    logits, Sampling(sampling.temperature[c0:c1], sampling.top_p[c0:c1], top_k=cut_of(sampling.top_k),
+                                     min_p=cut_of(sampling.min_p)) if by_row else sampling,
+                    perm - perm.min() if perm is not None else None, uniforms=draws,
                     scores=scores and scores[c0:c1], constraint=constraint, row0=c0)
             hidden_last[r0:r1] = hidden[:, -1, :]
         return first, hidden_last, next_pos
@@ -1450,7 +1498,8 @@ class MoondreamModel:
                            fuse: bool = False, share_prefix: bool = False, variants: Optional[Sequence[int]] = None,
                            encode_settings: Optional[dict] = None, logits_capture: Optional[torch.Tensor] = None,
                            sampling: Optional[Sampling] = None, scores: Optional[Scores] = None, hidden_sink=None,
-                           constraints: Optional[Sequence[Optional[TokenAutomaton]]] = None) -> Prepared:
+                           constraints: Optional[Sequence[Optional[TokenAutomaton]]] = None,
+                           filters: Optional[Sequence[Tuple[int, float]]] = None) -> Prepared:
         """Everything before the first generated token, for B (image, prompt-ids) pairs, as ``plan_rows`` lays them out
         (moondream_amd/shared_prefix.py): every image's KV prefix is placed (``_place_images``), then one prompt prefill per
         distinct length picks the first tokens.  Returns a ``Prepared``, rows in slot order.  The COPY route gives row r slot
@@ -1464,7 +1513,9 @@ class MoondreamModel:
         there); None = argmax.
         ``logits_capture`` / ``scores`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in slot order.
         ``constraints``: ``check_constraints``' entries in the CALLER's order; their record (``_constraint_record``, rows in
-        slot order) masks every first pick and goes to the decode loop in ``Prepared.constraint``.  Must run under
+        slot order) masks every first pick and goes to the decode loop in ``Prepared.constraint``.  ``filters``:
+        ``check_filters``' pairs in the CALLER's order; a sampled call then picks with their per-row record
+        (``_filter_record``, rows in slot order), the first tokens too, and ``Prepared.sampling`` is that record.  Must run under
         torch.inference_mode()."""
         mark = mark or (lambda name: None)
         rows = _Rows.of(rows)
@@ -1494,6 +1545,7 @@ class MoondreamModel:
                 if sampling is not None:
                     sampling = replace(sampling, row_perm=torch.tensor(plan.copy_rank, dtype=torch.int64, device=self._device))
         constraint = self._constraint_record(constraints and [constraints[i] for i in plan.order])
+        sampling = self._filter_record(sampling, filters and [filters[i] for i in plan.order])
         out = self._prefill_groups(plan.groups, embed, pos, rows, sampling, logits_capture, scores=scores, hidden_sink=hidden_sink,
                                    constraint=constraint)
         if fused:  # the one pass is both
@@ -1546,6 +1598,8 @@ class MoondreamModel:
         presence_penalty: Union[float, Sequence[float]] = 0.0,
         frequency_penalty: Union[float, Sequence[float]] = 0.0,
         constraints: Union[None, TokenAutomaton, Sequence[Optional[TokenAutomaton]]] = None,
+        top_k: Union[int, Sequence[int]] = 0,
+        min_p: Union[float, Sequence[float]] = 0.0,
     ):
         """Token ids for B (image, prompt-ids) pairs, decoded in lockstep; greedy by default.
 
@@ -1633,7 +1687,24 @@ class MoondreamModel:
         this call, like the penalties; a lone constrained sequence decodes on the batched kernels.  ValueError, before
         any GPU work: a list that is not one per row, an entry that is no automaton, an automaton ``validate(vocab_size,
         answer_id)`` refuses (a state that allows no token other than ``answer_id``, which generation suppresses).
+
+        ``top_k`` / ``min_p``: one value, or one per row in the caller's order -- two more truncation rules of a SAMPLED
+        row, next to ``top_p``.  With the row's tokens in descending bf16 probability (ties by ascending id), ``top_k`` = k
+        keeps the first k (0, or k >= the vocabulary: off) and ``min_p`` = m keeps the tokens of probability >=
+        bf16(m * the best token's) (0: off; the best token always survives).  All three rules are judged on the SAME
+        unrenormalised distribution and the shortest prefix survives, renormalised and drawn as before -- unlike HF / vLLM,
+        which renormalise after top-k before top-p: here the cuts do not depend on an order, top-p stays the reference's
+        bit for bit, and a row of (0, 0) is the row without the arguments.  On the device (md_sample_rows_filtered: the
+        per-row pick, inside the captured chunk, the first token's included); they act after penalties and constraints,
+        on the logits the pick reads.  A non-neutral value moves the call onto the per-row pick with the same draws; a
+        greedy call (``temperature`` 0) accepts and ignores them; log-probabilities stay those of the unfiltered
+        temperature-1 distribution.  A row's ids depend on its own settings only; with every row neutral the call is the
+        one without the arguments, launch for launch.  Served in every mode of this call; a sampled LoRA ``variant`` call
+        with them draws from the uniforms taken up front (as every other mode does), not per step.  ValueError, before
+        any GPU work: a ``top_k`` that is not an integer >= 0, a ``min_p`` that is not finite or outside [0, 1], a list
+        that is not one per row.
         """
+        filters = check_filters(top_k, min_p, len(images))
         top_k = check_top_logprobs(top_logprobs, return_logprobs)
         b = len(images)
         assert b == len(prompts) and b > 0
@@ -1660,7 +1731,7 @@ class MoondreamModel:
             scores = Scores.new((rows_t, b), top_k, self._device, fill=True) if return_logprobs else None
             prep = self._prepare_sequences(images, prompts, mark, _Rows(lora=lora), fuse=True, share_prefix=share_prefix,
                                            variants=multi_rows, encode_settings={"variant": variant}, sampling=sampling,
-                                           scores=scores and scores[0], constraints=constraints)
+                                           scores=scores and scores[0], constraints=constraints, filters=filters)
             stop = None if ignore_eos else eos
             penalty = self._penalty_record(penalties and [penalties[i] for i in prep.order])  # rows in slot order
             hist = self._decode_greedy(prep.first, prep.pos, max_tokens, tk.answer_id, prep.rows, stop, sampling=prep.sampling,
@@ -1686,23 +1757,26 @@ class MoondreamModel:
                                       top_p: Union[float, Sequence[float]] = DEFAULT_TOP_P, seeds=None,
                                       variant: Optional[str] = None, return_logprobs: bool = False,
                                       top_logprobs: Optional[int] = None, repetition_penalty=None, presence_penalty=None,
-                                      frequency_penalty=None, constraints=None):
+                                      frequency_penalty=None, constraints=None, top_k=None, min_p=None):
         """``batch_generate_ids`` with continuous batching (moondream_amd/continuous.py): per-request ``max_tokens`` and EOS
         exit, freed KV slots refilled from the queue mid-decode; same greedy ids as the lockstep path.  ``temperature`` and
         ``top_p``: one float, or one per request (greedy and sampled requests share the decode steps).  ``return_logprobs``:
         (ids, logprobs, ranks) as ``batch_generate_ids`` returns them (``ContinuousEngine(logprobs=True)``); with
         ``top_logprobs`` = k also its ``alternatives`` (``ContinuousEngine(logprobs=True, top_logprobs=k)``).  The three
         penalties: one number or one per request (None: neutral), ``batch_generate_ids``' rule per request.  ``constraints``:
-        one ``TokenAutomaton`` or one entry per request (None: free), ``batch_generate_ids``' rule and ids per request."""
+        one ``TokenAutomaton`` or one entry per request (None: free), ``batch_generate_ids``' rule and ids per request.
+        ``top_k`` / ``min_p``: one value or one per request (None: off), ``batch_generate_ids``' rule per request."""
         from .continuous import ContinuousEngine
 
         check_penalties(repetition_penalty, presence_penalty, frequency_penalty, len(images))  # before the engine exists
+        check_filters(top_k, min_p, len(images))
         constraints = self._check_constraints_of({"constraints": constraints}, len(images))
 
         eng = ContinuousEngine(self, max_live, chunk, logprobs=bool(return_logprobs), top_logprobs=top_logprobs)
         return eng.generate(images, prompts, max_tokens, eos_id, ignore_eos, seeds, variant, temperature, top_p,
                             return_logprobs=bool(return_logprobs), repetition_penalty=repetition_penalty,
-                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, constraints=constraints)
+                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, constraints=constraints,
+                            top_k=top_k, min_p=min_p)
 
     def teacher_forced_logits(self, images, prompts: Sequence[Sequence[int]], forced_ids, gather_idx) -> torch.Tensor:
         """Parity instrument (tests / bench.py): the logits of every greedy decision when each sequence is FORCED to follow
@@ -1836,7 +1910,8 @@ class MoondreamModel:
     pipeline_streams = int(os.environ.get("MD_PIPE_STREAMS", "2"))  # 2: decode on its own (priority) stream; 1: encode and decode in order on one stream
 
     def batch_generate_ids_pipelined(self, batches, max_tokens: int = DEFAULT_MAX_TOKENS, ignore_eos: bool = False,
-                                     repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, constraints=None):
+                                     repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, constraints=None,
+                                     top_k=0, min_p=0.0):
         """Generator over an iterable of (images, prompt-id lists) batches; yields each batch's greedy ids in order, one
         decode group late (a group = two consecutive batches of <= 64 sequences decoded as ONE lockstep of <= 128 -- round 6,
         ``pair_decode`` -- or one batch).  Two HIP streams: the MFMA-bound encode (vision + prefill) of batch k+1 on one, the HBM-bound lockstep
@@ -1853,7 +1928,9 @@ class MoondreamModel:
             (either makes the host wait for the device).
 
         Per batch the result is identical to ``batch_generate_ids`` (same kernels, same order).  The penalty arguments of
-        that call are not served here: ValueError for a non-neutral one; nor are ``constraints`` (ValueError)."""
+        that call are not served here: ValueError for a non-neutral one; nor are ``constraints`` (ValueError), nor ``top_k`` /
+        ``min_p`` (ValueError for a non-neutral one: the engine decodes greedily)."""
+        refuse_filters(dict(top_k=top_k, min_p=min_p), "the pipelined engine (it decodes greedily: there is no sampled row to cut)")
         refuse_constraints({"constraints": constraints}, "the pipelined engine (its paired decode keeps no automaton states)")
         refuse_penalties(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                               frequency_penalty=frequency_penalty), "the pipelined engine (its paired decode keeps no histories)")
@@ -1996,11 +2073,13 @@ class MoondreamModel:
         (moondream.py:50-53, read at :447-457): max_tokens 768, temperature 0.5, top_p 0.3.  ``settings["generator"]`` (an
         extension) seeds the draws; ``{"temperature": 0}`` is greedy.  ``repetition_penalty`` / ``presence_penalty`` /
         ``frequency_penalty`` (extensions; one number or one per row) pass through, neutral when absent, and so does
-        ``constraints`` (an extension: one ``TokenAutomaton`` or one entry per row; absent: every row free)."""
+        ``constraints`` (an extension: one ``TokenAutomaton`` or one entry per row; absent: every row free), and ``top_k`` /
+        ``min_p`` (extensions: one value or one per row; absent: off)."""
         st = settings or {}
         return dict(max_tokens=st.get("max_tokens", DEFAULT_MAX_TOKENS), variant=st.get("variant"), variants=st.get("variants"),
                     temperature=st.get("temperature", DEFAULT_TEMPERATURE), top_p=st.get("top_p", DEFAULT_TOP_P),
-                    generator=st.get("generator"), constraints=st.get("constraints"), **penalties_of(settings))
+                    generator=st.get("generator"), constraints=st.get("constraints"), **penalties_of(settings),
+                    **filters_of(settings))
 
     def batch_caption(self, images, length: str = "normal", settings: Optional[dict] = None) -> List[str]:
         tpl = self.config.tokenizer.templates["caption"]
@@ -2050,8 +2129,9 @@ class MoondreamModel:
     # ------------------------------------------------------- sequential API
     def _prefill_prompt(self, prompt_tokens: torch.Tensor, pos: int, temperature: float, top_p: float,
                         spatial_refs: Optional[SpatialRefs] = None, attn_mask=None, lora=None, causal: bool = False,
-                        constraint: Optional[Constraint] = None):
-        """reference: moondream.py:280-321.  ``constraint``: the sequence's record, masking the first pick.  ``causal`` stands for the reference's
+                        constraint: Optional[Constraint] = None, filt: Optional[Sampling] = None):
+        """reference: moondream.py:280-321.  ``constraint``: the sequence's record, masking the first pick.  ``filt``: the
+        sequence's one-row record with ``top_k`` / ``min_p`` (``_filter_record``), cutting the first pick.  ``causal`` stands for the reference's
         ``attn_mask`` argument: the only non-default mask it ever passes is the plain
         lower-triangular one of a text-only query (moondream.py:571-575)."""
         self._select_kernels(1)  # a lone sequence's own tile policy, whatever an earlier (batch) call left in the structs
@@ -2065,7 +2145,11 @@ class MoondreamModel:
                     emb[ids.to(self._device) == self.config.tokenizer.size_id] = enc["sizes"]
             hidden = self._text_forward(emb, pos, _Rows(lora=lora if isinstance(lora, PackedLora) else None), causal=causal)
             logits = self._lm_head(hidden)
-            nxt = self._first_token(logits, Sampling(temperature, top_p) if temperature != 0 else None, constraint=constraint)
+            if filt is not None:  # the draw ``_pick`` makes, through the per-row pick
+                nxt = self._first_token(logits, filt, uniforms=torch.rand(1, device=self._device, dtype=torch.float32),
+                                        constraint=constraint)
+            else:
+                nxt = self._first_token(logits, Sampling(temperature, top_p) if temperature != 0 else None, constraint=constraint)
         return logits, hidden, nxt.reshape(1, 1), pos + ids.shape[1]
 
     def _generate_answer(self, prompt_tokens: torch.Tensor, pos: int, settings: Optional[dict] = None,
@@ -2075,12 +2159,14 @@ class MoondreamModel:
         ``presence_penalty`` / ``frequency_penalty`` (``batch_generate_ids``' rule, over this sequence's generated tokens):
         every step's logits are penalised on the device before its pick, in the chunked greedy loop and in the per-token
         sampled one alike; and ``constraints`` (one ``TokenAutomaton``: ``batch_generate_ids``' rule for this sequence,
-        the first token included)."""
+        the first token included); and ``top_k`` / ``min_p`` (``batch_generate_ids``' rule: a sampled answer's picks,
+        the first included, go through the per-row pick with one row)."""
         settings = settings or {}
         max_tokens = settings.get("max_tokens", DEFAULT_MAX_TOKENS)
         temperature = settings.get("temperature", DEFAULT_TEMPERATURE)
         top_p = settings.get("top_p", DEFAULT_TOP_P)
         penalties = check_penalties(*penalties_of(settings).values(), 1)
+        filters = check_filters(*filters_of(settings).values(), 1)
         automata = self._check_constraints_of(settings, 1)
         lora = self._lora(settings)
         rows = _Rows(lora=lora)
@@ -2088,8 +2174,9 @@ class MoondreamModel:
         # decode steps attend to keys [0, pos] only, which both masks allow: the mask matters for the prompt
         with torch.inference_mode():
             constraint = self._constraint_record(automata)  # one state over the whole answer, at its start now
+            filt = self._filter_record(Sampling(float(temperature), float(top_p)), filters) if filters and temperature != 0 else None
         _, _, nxt, pos = self._prefill_prompt(prompt_tokens, pos, temperature, top_p, spatial_refs, attn_mask, lora=lora, causal=causal,
-                                              constraint=constraint)
+                                              constraint=constraint, filt=filt)
 
         def token_source():
             with torch.inference_mode():
@@ -2126,7 +2213,12 @@ class MoondreamModel:
                             self._penalize(logits, tok, rows, penalty)
                         if constraint is not None:
                             self._constrain(logits, tok, rows, constraint)
-                        tok = self._pick(logits, temperature, top_p, self.config.tokenizer.answer_id)  # moondream.py:517
+                        if filt is not None:
+                            tok = self._pick_rows_filtered(logits, filt.temperature, filt.top_p, filt.top_k, filt.min_p,
+                                                           self.config.tokenizer.answer_id,
+                                                           torch.rand(1, device=self._device, dtype=torch.float32))
+                        else:
+                            tok = self._pick(logits, temperature, top_p, self.config.tokenizer.answer_id)  # moondream.py:517
 
         def generator():
             # streaming detokeniser: flush on newline, CJK, or up to the last space
@@ -2169,6 +2261,7 @@ class MoondreamModel:
         ``frequency_penalty`` (an extension: ``batch_generate_ids``' rule over the caption's generated tokens) and
         ``constraints`` (one ``TokenAutomaton``)."""
         check_penalties(*penalties_of(settings).values(), 1)  # host values: before any GPU work
+        check_filters(*filters_of(settings).values(), 1)
         self._check_constraints_of(settings, 1)
         tpl = self.config.tokenizer.templates["caption"]
         if tpl is None:
@@ -2187,6 +2280,7 @@ class MoondreamModel:
         -> answer after a second suffix).  ``settings`` may carry the penalty settings and ``constraints`` as ``caption``'s
         may; not with ``reasoning`` (ValueError)."""
         check_penalties(*penalties_of(settings).values(), 1)  # host values: before any GPU work
+        check_filters(*filters_of(settings).values(), 1)
         self._check_constraints_of(settings, 1)
         tpl = self.config.tokenizer.templates["query"]
         if tpl is None:
@@ -2198,6 +2292,7 @@ class MoondreamModel:
         if reasoning:
             refuse_penalties(settings, "reasoning queries")
             refuse_constraints(settings, "reasoning queries")
+            refuse_filters(settings, "reasoning queries (the reasoning loop picks with the call's temperature and top-p alone)")
         if image is not None:
             enc = self.encode_image(image, settings)
             self.load_encoded_image(enc)
@@ -2631,6 +2726,7 @@ class MoondreamModel:
         st = settings or {}
         refuse_penalties(settings, "reasoning queries")
         refuse_constraints(settings, "reasoning queries")
+        refuse_filters(settings, "reasoning queries (the reasoning loop picks with the call's temperature and top-p alone)")
         if st.get("variant") is not None or st.get("variants") is not None:
             raise NotImplementedError("batched reasoning queries are not served with LoRA variants (variant / variants): "
                                       "use query(reasoning=True) per image")
@@ -2718,6 +2814,7 @@ class MoondreamModel:
         settings (``check_score_settings``) -> the score window, None without ``return_scores``."""
         refuse_penalties(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
         refuse_constraints(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
+        refuse_filters(settings, f"{kind}: its loop decodes coordinates, not tokens sampled from logits")
         return check_score_settings(settings, self.config.region.coord_out_dim)
 
     def batch_detect(self, images, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
@@ -2749,6 +2846,7 @@ class MoondreamModel:
         ``variant`` (settings) takes the copy path, with the same results.  With reasoning: ``query_many_reasoning``."""
         prompts = self._query_prompts(questions)
         check_penalties(*penalties_of(settings).values(), len(prompts))  # host values: before any GPU work
+        check_filters(*filters_of(settings).values(), len(prompts))
         self._check_constraints_of(settings, len(prompts))
         enc = self.encode_image(image, settings)
         ids = self.batch_generate_ids([enc] * len(prompts), prompts, share_prefix=True, **self._sampling_kwargs(settings))
