@@ -759,6 +759,91 @@ md_status md_attention_decode_rope_f8_shared(const void* qkv, int64_t ld, void* 
 md_status md_kv_quantize_f8(const md_kv_cache* kv, int32_t n_layers, int32_t batch, int32_t n_heads, const int32_t* pos0,
                             int32_t pos_fixed, int32_t n_pos, void* stream);
 
+/* Beam search, the reorder: for every row r, key and value positions [from[r], to[r]) of EVERY layer and head are copied from
+ * slot src[r] to slot dst[r] of the bf16 slabs -- a surviving beam's KV tail goes where its child will read it.  src, dst,
+ * from, to: device int32 [rows].  One (row, layer, head, K|V) piece is one contiguous run of (to - from) * 128 bytes (head_dim
+ * 64); a workgroup of 256 moves the K and the V runs of every head of one (row, layer) with 16-byte loads and stores, up to
+ * four loads in flight per lane before their stores.  Run lengths are device data: the grid is n_layers x rows (1536
+ * workgroups at 2B with 64 rows; one per head would be 49152, most of them skipped copies), and a workgroup with nothing to
+ * do exits.
+ *   A row is skipped entirely when dst[r] < 0, src[r] < 0, src[r] == dst[r] or to[r] <= from[r] -- and, so that no address
+ *     outside the slabs is ever formed, when a slot is >= n_slots, from[r] < 0 or to[r] > kv->ctx.
+ *   Caller contract: no dst of a live row equals any live row's src, and live dst values are distinct; the launch then has no
+ *     read / write hazard.  md_beam_select's hand-off satisfies it by construction.
+ *   No byte outside the named runs is written.  No host sync, no allocation: capturable.  rows == 0: MD_OK, nothing launched.
+ * MD_ERR_INVALID_ARG: NULL kv / slabs / arrays, rows < 0, n_layers < 1, n_heads < 1, n_slots <= 0, slabs or strides that are
+ * not 16-byte multiples, batch_stride < n_heads * ctx * 64, n_slots * batch_stride > layer_stride, or a cache with the e4m3
+ * copy attached (kv->k8 / kv->v8: beam search is not served in the fp8 KV mode). */
+md_status md_kv_copy_tail(const md_kv_cache* kv, int32_t n_layers, int32_t n_heads, int32_t n_slots, int32_t rows,
+                          const int32_t* src, const int32_t* dst, const int32_t* from, const int32_t* to, void* stream);
+
+/* Beam search, the choice: the next num_beams beams of every request from num_beams x vocab candidates, the finished
+ * hypotheses' pool, the done rule and the KV slot hand-off, on the device.  Rows are groups x W, W = num_beams in 1 ..
+ * MD_BEAM_MAX (2W <= MD_TOPK_MAX); row r is beam r % W of group r / W.  Everything in md_beam_state is the CALLER's device
+ * memory, read and rewritten by the call:
+ *   cum fp32 [rows]        each beam's summed log-probability; -inf: a dead beam
+ *   cur int32 [rows]       the slot each beam decodes in (the slot table of the decode step); -1: an idle row
+ *   own int32 [rows][2]    the two slots a row owns (read only); cur[r] starts as own[r][0]
+ *   len int32 [groups]     the tokens the group's hypotheses hold (0 before the first decision)
+ *   done int32 [groups]    != 0: the group is finished
+ *   prefix_len int32 [groups]   (read only) the positions of the group's shared prefix
+ *   pool_n int32 [groups], pool_score fp32 / pool_sum fp32 / pool_parent int32 / pool_step int32 [groups][W]: the finished
+ *     hypotheses: normalised score h, raw sum s, the beam j whose continuation by eos it is, and len at that decision -- its
+ *     tokens are the pool_step tokens read back from beam pool_parent through parent planes pool_step - 1 .. 0
+ *   inv_norm fp32 [n_norm] (read only): inv_norm[n] = float32(1 / n ** length_penalty), the host's, computed in float64;
+ *     an index beyond the table reads its last entry
+ *   cand_ids int32 / cand_lp fp32 [rows][2W]: scratch, left holding the call's per-row candidates
+ * Row phase.  beams_in is W, or 1 for the first decision: group g then reads logits row g and beam 0 alone is live.  Entry i
+ *   of a live row j is what md_topk_logprobs(k = 2W) returns for the row's logits, ids and fp32 log-probabilities bit for bit
+ *   (the same device function; suppress_id / suppress_rows as there, suppress_rows indexed by the logits row).  A beam with
+ *   cum == -inf is not read.
+ * Group order.  Candidate (j, i) has score s = cum[j] + lp[j][i], one fp32 add; candidates of a dead beam and entries of id -1
+ *   do not exist.  Order: s descending, then j ascending, then i ascending.
+ * Walk over the first 2W candidates in that order, walk index w = 0, 1, ..; L = len[g] before the call:
+ *   token == eos_id (eos_id >= 0) and w < W: a finished hypothesis of score h = s * inv_norm[L + 1] (one fp32 multiply; no
+ *     powf, no divide) enters the pool -- appended while pool_n < W, otherwise it replaces the entry of lowest score (among
+ *     equal scores the one of highest index) and only if h is strictly greater;
+ *   token == eos_id and w >= W: dropped (the HF rule);
+ *   any other candidate is the next live beam n = 0, 1, .. until W are chosen: tokens_out[g*W+n] = token, parent[g*W+n] = j,
+ *     cum[g*W+n] = s.  Beams that are not filled are dead: cum = -inf, parent -1, cur -1 (an idle decode row) and
+ *     tokens_out 0 -- an id the next step's embedding lookup can read, which -1 is not; parent -1 is what marks the row.
+ * Done.  len[g] = L + 1.  The group is done when no live beam is left, or when the pool is full and either early_stopping or
+ *   cum[g*W] * inv_norm[L + 1] <= the pool's lowest score (HF's early_stopping=False test: the best live beam cannot beat
+ *   the worst finished one).  A group that becomes done has cur = -1 and src = dst = -1 in all its rows; later calls neither
+ *   read nor write anything of a done group.
+ * Slot hand-off, inside the group; every cur is read before any is written.  Child n with parent n keeps its slot and emits
+ *   src = dst = cur[n] (a skipped copy).  Child n with parent p != n emits src = cur[p] (before the call), dst = the one of
+ *   own[n] that is not cur[n], and cur[n] becomes it: a dst is never any row's current slot, which is md_kv_copy_tail's
+ *   contract.  from = prefix_len[g], to = prefix_len[g] + L (the position after the token the step consumed) are written for EVERY row of
+ *   a group that was not done at entry, dead rows included; a dead row has src = dst = cur = -1, which is what skips its copy.
+ * One launch of 1024 per row (the row phase), one wave per group (merge, walk, pool and hand-off from LDS).  NaN logits are
+ * out of contract.  No host sync, no allocation: capturable.  groups == 0: MD_OK, nothing launched.
+ * MD_ERR_INVALID_ARG: NULL logits / st / any array of st / tokens_out / parent / src / dst / from / to, groups < 0,
+ * num_beams outside 1 .. MD_BEAM_MAX, beams_in neither 1 nor num_beams, vocab < 1, ld < vocab, n_norm < 1, early_stopping
+ * neither 0 nor 1. */
+#define MD_BEAM_MAX 16
+typedef struct {
+  float* cum;
+  int32_t* cur;
+  const int32_t* own;
+  int32_t* len;
+  int32_t* done;
+  const int32_t* prefix_len;
+  int32_t* pool_n;
+  float* pool_score;
+  float* pool_sum;
+  int32_t* pool_parent;
+  int32_t* pool_step;
+  const float* inv_norm;
+  int32_t n_norm;
+  int32_t* cand_ids;
+  float* cand_lp;
+} md_beam_state;
+md_status md_beam_select(const void* logits, int64_t ld, int32_t groups, int32_t num_beams, int32_t beams_in, int32_t vocab,
+                         int32_t suppress_id, const int32_t* suppress_rows, int32_t eos_id, int32_t early_stopping,
+                         const md_beam_state* st, int32_t* tokens_out, int32_t* parent, int32_t* src, int32_t* dst,
+                         int32_t* from, int32_t* to, void* stream);
+
 size_t md_text_workspace_bytes(const md_text_model* m, int32_t batch, int32_t q_len);
 
 /* text_decoder over a block of q_len new tokens per sequence (reference:

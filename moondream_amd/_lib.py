@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libmoondream_hip.so")
-SOURCES = ["gemm_bf16.hip", "gemm_w4.hip", "gemm_fp8w.hip", "gemm_f8.hip", "quant_f8.hip", "attention_f8kv.hip", "decode_b1.hip", "attention.hip", "elementwise.hip", "sampling_region.hip", "lora_multi.hip", "api.hip"]
+SOURCES = ["gemm_bf16.hip", "gemm_w4.hip", "gemm_fp8w.hip", "gemm_f8.hip", "quant_f8.hip", "attention_f8kv.hip", "decode_b1.hip", "attention.hip", "elementwise.hip", "sampling_region.hip", "beam.hip", "lora_multi.hip", "api.hip"]
 
 MD_OK = 0
 ABI_VERSION = 5  # include/moondream_hip.h MD_ABI_VERSION
@@ -28,6 +28,7 @@ MD_CROPS_U8_HWC, MD_CROPS_BF16_CHW = 0, 1
 MD_TOPK_MAX = 32  # md_topk_logprobs: the most alternatives per decision
 MD_PENALTY_HIST_MAX = 4096  # md_penalize_rows: the longest history per row
 MD_CONSTRAIN_VOCAB_MAX = 262144  # md_constrain_rows: the largest vocabulary (its bit map lives in LDS)
+MD_BEAM_MAX = 16  # md_beam_select: the most beams per request (2 * MD_BEAM_MAX candidates per beam = MD_TOPK_MAX)
 
 c_void_p, c_int32, c_int64, c_size_t, c_float = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float
 
@@ -177,6 +178,13 @@ class MdReasonState(C.Structure):
                 ("size_id", c_int32), ("coord_id", c_int32), ("suffix_id", c_int32)]
 
 
+class MdBeamState(C.Structure):
+    _fields_ = [("cum", c_void_p), ("cur", c_void_p), ("own", c_void_p), ("len", c_void_p), ("done", c_void_p),
+                ("prefix_len", c_void_p), ("pool_n", c_void_p), ("pool_score", c_void_p), ("pool_sum", c_void_p),
+                ("pool_parent", c_void_p), ("pool_step", c_void_p), ("inv_norm", c_void_p), ("n_norm", c_int32),
+                ("cand_ids", c_void_p), ("cand_lp", c_void_p)]
+
+
 # name -> (restype, argtypes): every symbol include/moondream_hip.h declares
 P = C.POINTER
 SIGNATURES = {
@@ -239,6 +247,9 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "md_constrain_rows": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int32, c_void_p]),
+    "md_kv_copy_tail": (C.c_int, [P(MdKvCache), c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "md_beam_select": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                                 P(MdBeamState), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "md_fourier_features": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     "md_region_pick_encode": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                         c_void_p, c_int64, c_void_p, c_int64, c_void_p]),

@@ -707,10 +707,18 @@ __device__ __forceinline__ void topk_find_digit(const unsigned* hist, unsigned* 
   __syncthreads();
 }
 
-__global__ __launch_bounds__(TOPK_THREADS) void topk_logprobs_kernel(const bf16_t* __restrict__ logits, int64_t ld, int vocab,
-                                                                     int suppress_id, const int32_t* __restrict__ suppress_rows,
-                                                                     const int32_t* __restrict__ gate, int k,
-                                                                     int32_t* __restrict__ top_ids, float* __restrict__ top_logprobs) {
+// a row that is not computed: its k entries are -1 / NaN (whole workgroup)
+__device__ __forceinline__ void topk_row_off(int k, int32_t* __restrict__ out_id, float* __restrict__ out_lp) {
+  if ((int)threadIdx.x < k) {
+    out_id[threadIdx.x] = -1;
+    out_lp[threadIdx.x] = __builtin_nanf("");
+  }
+}
+
+// One row's k entries, by the whole workgroup of TOPK_THREADS: the body of md_topk_logprobs' kernel, and of the row phase of
+// md_beam_select (beam_rows_kernel), which is why the two agree bit for bit.  lr: the row; sup: the suppressed id or -1.
+__device__ __forceinline__ void topk_row(const bf16_t* __restrict__ lr, int vocab, int sup, int k, int32_t* __restrict__ out_id,
+                                         float* __restrict__ out_lp) {
   __shared__ unsigned hist[TOPK_HIST_WORDS];
   __shared__ unsigned cnt[256];
   __shared__ float red_max[TOPK_THREADS / 64];
@@ -721,22 +729,8 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_logprobs_kernel(const bf16_
   __shared__ int n_slots;
   __shared__ unsigned slot_key[MD_TOPK_MAX];
   __shared__ int slot_id[MD_TOPK_MAX];
-  const int r = blockIdx.x, tid = threadIdx.x;
-  int32_t* out_id = top_ids + (int64_t)r * k;
-  float* out_lp = top_logprobs + (int64_t)r * k;
+  const int tid = threadIdx.x;
   // every exit below is taken by the whole workgroup (per-row values), before or between barriers
-  if (gate) {
-    const int g = gate[r];
-    if (g < 0 || g >= vocab) {  // an idle / padding row: the logits row is not read
-      if (tid < k) {
-        out_id[tid] = -1;
-        out_lp[tid] = __builtin_nanf("");
-      }
-      return;
-    }
-  }
-  const int sup = (suppress_id >= 0 && (suppress_rows == nullptr || suppress_rows[r] != 0)) ? suppress_id : -1;
-  const bf16_t* lr = logits + (int64_t)r * ld;
   const int copy = tid & (TOPK_COPIES - 1);
 
   // ---- pass 1: maximum of the live logits (token_logprobs_kernel's reduction), histogram of the high byte
@@ -762,10 +756,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_logprobs_kernel(const bf16_
   const int hi = found[0], above_hi = found[1];
   const int n_take = min(k, found[3]);  // entries the row fills
   if (hi < 0) {                         // no live token at all (vocab 1, suppressed)
-    if (tid < k) {
-      out_id[tid] = -1;
-      out_lp[tid] = __builtin_nanf("");
-    }
+    topk_row_off(k, out_id, out_lp);
     return;
   }
 
@@ -872,6 +863,45 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_logprobs_kernel(const bf16_
     out_id[at] = id;  // a permutation of 0 .. n_take-1 (keys with ids are distinct), then the unfilled entries in place
     out_lp[at] = lp;
   }
+}
+
+__global__ __launch_bounds__(TOPK_THREADS) void topk_logprobs_kernel(const bf16_t* __restrict__ logits, int64_t ld, int vocab,
+                                                                     int suppress_id, const int32_t* __restrict__ suppress_rows,
+                                                                     const int32_t* __restrict__ gate, int k,
+                                                                     int32_t* __restrict__ top_ids, float* __restrict__ top_logprobs) {
+  const int r = blockIdx.x;
+  int32_t* out_id = top_ids + (int64_t)r * k;
+  float* out_lp = top_logprobs + (int64_t)r * k;
+  if (gate) {
+    const int g = gate[r];
+    if (g < 0 || g >= vocab) {  // an idle / padding row: the logits row is not read
+      topk_row_off(k, out_id, out_lp);
+      return;
+    }
+  }
+  const int sup = (suppress_id >= 0 && (suppress_rows == nullptr || suppress_rows[r] != 0)) ? suppress_id : -1;
+  topk_row(logits + (int64_t)r * ld, vocab, sup, k, out_id, out_lp);
+}
+
+// The row phase of md_beam_select (csrc/beam.hip): the 2W best continuations of every live beam, md_topk_logprobs' entries.
+// Row r is beam r % W of group r / W and reads logits row r (beams_in == W) or row r / W (beams_in == 1: the first decision,
+// beam 0 alone).  A done group's rows are neither read nor written; a dead beam's (cum == -inf) entries are -1 / NaN.
+__global__ __launch_bounds__(TOPK_THREADS) void beam_rows_kernel(const bf16_t* __restrict__ logits, int64_t ld, int vocab,
+                                                                 int suppress_id, const int32_t* __restrict__ suppress_rows, int W,
+                                                                 int beams_in, const float* __restrict__ cum,
+                                                                 const int32_t* __restrict__ done, int32_t* __restrict__ cand_ids,
+                                                                 float* __restrict__ cand_lp) {
+  const int r = blockIdx.x, g = r / W, j = r - g * W, k = 2 * W;
+  if (done[g] != 0) return;
+  int32_t* out_id = cand_ids + (int64_t)r * k;
+  float* out_lp = cand_lp + (int64_t)r * k;
+  if (j >= beams_in || cum[r] == -INFINITY) {
+    topk_row_off(k, out_id, out_lp);
+    return;
+  }
+  const int lrow = beams_in == 1 ? g : r;
+  const int sup = (suppress_id >= 0 && (suppress_rows == nullptr || suppress_rows[lrow] != 0)) ? suppress_id : -1;
+  topk_row(logits + (int64_t)lrow * ld, vocab, sup, k, out_id, out_lp);
 }
 
 // ---------------------------------------------------------------------------
@@ -1135,6 +1165,15 @@ __global__ __launch_bounds__(CONSTRAIN_THREADS) void constrain_rows_kernel(
   }
 }
 }  // namespace
+
+// internal (beam.hip): the row phase of md_beam_select
+md_status md_beam_rows(const void* logits, int64_t ld, int32_t rows, int32_t vocab, int32_t suppress_id,
+                       const int32_t* suppress_rows, int32_t num_beams, int32_t beams_in, const float* cum, const int32_t* done,
+                       int32_t* cand_ids, float* cand_lp, hipStream_t stream) {
+  hipLaunchKernelGGL(beam_rows_kernel, dim3(rows), dim3(TOPK_THREADS), 0, stream, (const bf16_t*)logits, ld, vocab, suppress_id,
+                     suppress_rows, num_beams, beams_in, cum, done, cand_ids, cand_lp);
+  return md_launch_status();
+}
 
 // internal (api.hip): the mask that also advances pos
 md_status md_mask_logits_advance(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* ids, int32_t* pos,

@@ -72,6 +72,11 @@ md_status md_pool_grid_concat(const void* global_feats, const void* grid_feats, 
 // sampling_region.hip: md_mask_logits_rows that also advances pos (pos == nullptr: the public form)
 md_status md_mask_logits_advance(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* ids, int32_t* pos,
                                  hipStream_t stream);
+// sampling_region.hip: the row phase of md_beam_select (csrc/beam.hip) -- md_topk_logprobs' entries, k = 2 * num_beams, for
+// every live beam (the kernel that shares md_topk_logprobs' device function)
+md_status md_beam_rows(const void* logits, int64_t ld, int32_t rows, int32_t vocab, int32_t suppress_id,
+                       const int32_t* suppress_rows, int32_t num_beams, int32_t beams_in, const float* cum, const int32_t* done,
+                       int32_t* cand_ids, float* cand_lp, hipStream_t stream);
 // lora_multi.hip
 md_status lora_bank_ok(const md_lora_bank* bank);
 int32_t md_lora_shrink_cols(const md_lora_bank* bank, int32_t pairs);

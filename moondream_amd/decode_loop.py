@@ -2,7 +2,7 @@
 share: the description of a chunk of consecutive decode steps over fixed buffers, and the one runner that launches it.
 ``run_chunk`` holds the only step body of the package -- decode step (or, for a reasoning query, the reasoning step), then
 the optional penalty launch, then the optional constraint launch, then the optional sampling pick, then the optional
-log-probability launch and the optional top-k launch -- and the only decode graph key.  No torch here: the runner moves no data, it orders launches."""
+log-probability launch and the optional top-k launch; or, for beam search, decode step, beam selection, KV tail copy -- and the only decode graph key.  No torch here: the runner moves no data, it orders launches."""
 from __future__ import annotations
 
 import math
@@ -207,6 +207,34 @@ class Constraint:
 
 
 @dataclass(frozen=True, eq=False)
+class Beam:
+    """The beam-search state of a chunk (md_beam_select, md_kv_copy_tail), all device memory at fixed addresses.  The
+    chunk's ``b`` rows are requests x ``num_beams`` beams.  ``state``: the library's struct over the caller's arrays
+    (``_lib.MdBeamState``: cum, cur, own, len, done, prefix_len, the pool, inv_norm, the candidate scratch) -- ``cur`` is
+    also the slot table of the steps' routing, so a beam changes the slot it decodes in without the launch changing.
+    ``parents`` (int32 [>= n, b]): step i writes plane i, the beam each row continues.  ``src`` / ``dst`` / ``frm`` /
+    ``to`` (int32 [b]): the hand-off md_beam_select emits and md_kv_copy_tail consumes in the same step.  ``eos_id`` < 0:
+    nothing ever finishes.  ``keep``: the tensors behind ``state`` (their addresses are the key)."""
+
+    num_beams: int
+    eos_id: int
+    early_stopping: bool
+    state: Any
+    parents: Any
+    src: Any
+    dst: Any
+    frm: Any
+    to: Any
+    n_slots: int
+    keep: Tuple[Any, ...] = ()
+
+    def key(self) -> tuple:
+        """What a captured chunk bakes in of the beam state: addresses, the width and the stopping rule."""
+        return ("beam", int(self.num_beams), int(self.eos_id), bool(self.early_stopping), int(self.n_slots)) + tuple(
+            t.data_ptr() for t in self.keep) + tuple(t.data_ptr() for t in (self.parents, self.src, self.dst, self.frm, self.to))
+
+
+@dataclass(frozen=True, eq=False)
 class Sampling:
     """How tokens are sampled (``None`` where one is expected: greedy): the reference's temperature / top-p rule with one
     uniform per (token, sequence).  Two floats are a whole call's settings: the uniforms come from ``generator`` (a device
@@ -287,7 +315,11 @@ class DecodeChunk:
     ``constraint`` (``Constraint``): after each step (and its penalties) and before its pick, every row's automaton is
     advanced by the token the step consumed and the tokens its new state forbids lose their logits (md_constrain_rows).
     Such a chunk always picks again too, and its log-probabilities and alternatives are those of the MASKED logits: a
-    greedy token has rank 0 and an alternative outside the allowed set carries -inf.  Not with ``b1`` or ``reason``."""
+    greedy token has rank 0 and an alternative outside the allowed set carries -inf.  Not with ``b1`` or ``reason``.
+    ``beam`` (``Beam``): beam search -- after each step md_beam_select chooses every request's next beams from the
+    logits the step left, writes their tokens to ``tokens[i + 1]`` (over the step's argmax) and their parents to plane i,
+    and md_kv_copy_tail moves each surviving beam's KV tail to the slot its child decodes in.  The routing's slot table
+    is the record's ``cur``.  Greedy, fused steps only: not with any other optional field."""
 
     b: int
     tokens: Any
@@ -304,6 +336,7 @@ class DecodeChunk:
     topk: Optional[Tuple[Any, Any]] = None
     penalty: Optional[Penalty] = None
     constraint: Optional[Constraint] = None
+    beam: Optional[Beam] = None
 
 
 def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_stream: Optional[int] = None,
@@ -312,7 +345,7 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     stream: the chunk is replayed from the graph captured for it on that stream, or, first, run eagerly and captured
     (``model._replay_or_capture``: its ``GraphStore``'s, ``may_capture`` too).  The key starts (``tag``, stream) and names everything
     the launches bake in.  Returns True when it captured.  Besides that, the model gives the buffers (_decode_logits, _workspace,
-    _kv_struct) and the launches (_decode_step, _decode_step_b1, _decode_step_reason, _penalize, _constrain, _pick, _pick_rows, _pick_rows_filtered, _token_logprobs, _topk_logprobs)."""
+    _kv_struct) and the launches (_decode_step, _decode_step_b1, _decode_step_reason, _penalize, _constrain, _pick, _pick_rows, _pick_rows_filtered, _token_logprobs, _topk_logprobs, _beam_select, _kv_copy_tail)."""
     c = chunk
     pieces = c.step is not None
     assert c.reason is None or (not pieces and not c.b1 and c.logprobs is None and c.pick is not None and c.pick.per_row)
@@ -321,6 +354,8 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     assert c.topk is None or c.logprobs is not None
     assert c.penalty is None or (not c.b1 and c.reason is None)
     assert c.constraint is None or (not c.b1 and c.reason is None)
+    assert c.beam is None or (not pieces and not c.b1 and c.reason is None and c.pick is None and c.logprobs is None
+                              and c.penalty is None and c.constraint is None)
     if not pieces:
         logits = model._decode_logits(c.b)
         ws = model._workspace(c.ws_bytes, 2)
@@ -352,6 +387,10 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
             elif not pieces:
                 model._decode_step(c.rows_of(i), tok_in, tok_out, c.pos, c.b, c.suppress_id, logits, ws, kv)
             lg = c.step(tok_in) if pieces else left
+            if c.beam is not None:  # the request's next beams over the step's argmax, then their KV tails to their slots
+                model._beam_select(lg, c.suppress_id, c.beam, c.beam.num_beams, tok_out, c.beam.parents[i])
+                model._kv_copy_tail(kv, c.beam)
+                continue
             if c.penalty is not None:  # tok_in joins each row's history, whose tokens' logits are penalised in place
                 model._penalize(lg, tok_in, c.rows_of(i), c.penalty)
             if c.constraint is not None:  # tok_in advances each row's automaton, whose new state masks the logits in place
@@ -392,4 +431,6 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
         key += c.penalty.key()
     if c.constraint is not None:  # and another with the constraint launches
         key += c.constraint.key()
+    if c.beam is not None:  # and another with the select and copy launches
+        key += c.beam.key()
     return model._replay_or_capture(key, body, may_capture=may_capture)

@@ -19,6 +19,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .config import MoondreamConfig
+from .beam import refuse_beams
 from .constraint import refuse_constraints
 from .decode_loop import refuse_filters, refuse_penalties
 from .moondream import MoondreamModel
@@ -76,6 +77,7 @@ class HfMoondream:
         refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_filters(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
+        refuse_beams(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         answer = self.query(image_embeds, question, settings=kwargs.get("settings"))["answer"].strip()
         if result_queue is not None:
             result_queue.put(answer)
@@ -89,6 +91,7 @@ class HfMoondream:
         refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_filters(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
+        refuse_beams(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         self._setup_caches()
         settings = dict(kwargs.get("settings") or {})
         settings.setdefault("max_tokens", kwargs.get("max_new_tokens", kwargs.get("max_tokens", 256)))
@@ -107,6 +110,7 @@ class HfMoondream:
         refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_filters(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
+        refuse_beams(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         q = extract_question(prompt)
         if q is not None:
             return [self.model_query(image_embeds, q)]

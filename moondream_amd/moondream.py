@@ -32,7 +32,8 @@ from . import _lib
 from .config import MoondreamConfig
 from .constraint import FREE, TokenAutomaton, check_constraints, pack, pow2_at_least, refuse_constraints
 from .crop_staging import CropStager, crop_workers, upload_unique
-from .decode_loop import (Constraint, DecodeChunk, Penalty, ReasonChunk, Sampling, check_filters, check_penalties, check_score_settings,
+from .beam import Hypothesis, beams_of, check_beams, finalize, inv_norm_table, refuse_beams
+from .decode_loop import (Beam, Constraint, DecodeChunk, Penalty, ReasonChunk, Sampling, check_filters, check_penalties, check_score_settings,
                           check_top_logprobs, filters_of, penalties_of, refuse_filters, refuse_penalties, run_chunk)
 from .graph_store import GraphStore
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
@@ -1189,6 +1190,35 @@ class MoondreamModel:
             "md_topk_logprobs",
         )
 
+    def _beam_select(self, logits: torch.Tensor, suppress_id: int, beam: Beam, beams_in: int, tokens_out: torch.Tensor,
+                     parents_out: torch.Tensor):
+        """One beam decision over ``logits`` (md_beam_select): [requests x num_beams, V], or, ``beams_in`` 1, the prompt
+        pass's [requests, V].  The next beams' tokens go to ``tokens_out`` and their parents to ``parents_out`` (int32
+        [requests x num_beams]); cum, pool, done flags and slot hand-off change in ``beam``'s arrays.  Nothing is allocated
+        and nothing synchronises: capturable."""
+        w = beam.num_beams
+        rows = tokens_out.numel()
+        assert logits.shape[0] * (w if beams_in == 1 else 1) >= rows and rows % w == 0 and parents_out.numel() == rows
+        for t in (tokens_out, parents_out, beam.src, beam.dst, beam.frm, beam.to):
+            assert t.is_contiguous() and t.dtype == torch.int32 and t.device == logits.device and t.numel() >= rows
+        _lib.check(
+            self.lib.md_beam_select(logits.data_ptr(), logits.stride(0), rows // w, w, beams_in, logits.shape[1], suppress_id, None,
+                                    beam.eos_id, int(beam.early_stopping), C.byref(beam.state), tokens_out.data_ptr(),
+                                    parents_out.data_ptr(), beam.src.data_ptr(), beam.dst.data_ptr(), beam.frm.data_ptr(),
+                                    beam.to.data_ptr(), self._stream()),
+            "md_beam_select",
+        )
+
+    def _kv_copy_tail(self, kv: _lib.MdKvCache, beam: Beam):
+        """The KV tails of the beams ``_beam_select`` just chose, each to the slot its child decodes in, every layer
+        (md_kv_copy_tail over the record's src / dst / from / to).  Capturable."""
+        t = self.config.text
+        _lib.check(
+            self.lib.md_kv_copy_tail(C.byref(kv), t.n_layers, t.n_kv_heads, beam.n_slots, beam.src.numel(), beam.src.data_ptr(),
+                                     beam.dst.data_ptr(), beam.frm.data_ptr(), beam.to.data_ptr(), self._stream()),
+            "md_kv_copy_tail",
+        )
+
     def _score(self, logits: torch.Tensor, targets: torch.Tensor, suppress_id: int, scores: Scores,
                gate: Optional[torch.Tensor] = None, suppress_rows: Optional[torch.Tensor] = None):
         """Fill ``scores`` (over [R]) for ``targets`` in ``logits`` [R, V]: ``_token_logprobs``, then ``_topk_logprobs`` if it has k."""
@@ -1751,6 +1781,184 @@ class MoondreamModel:
         out = tuple(prep.in_caller_order(per_row) for per_row in out)
         return out if return_logprobs else out[0]
 
+    BEAM_LOCKSTEP_ROWS = 128  # requests x num_beams one lockstep serves (the decode step's weight-stream regime); more: split
+
+    def batch_beam_search_ids(self, images: Sequence[Union[Image.Image, EncodedImage]], prompts: Sequence[Sequence[int]],
+                              num_beams: int, max_tokens: int = DEFAULT_MAX_TOKENS, eos_id: Optional[int] = None,
+                              ignore_eos: bool = False, length_penalty: float = 1.0, early_stopping: bool = False,
+                              num_return_sequences: int = 1) -> List[List[Hypothesis]]:
+        """Beam search over B (image, prompt-ids) pairs: per request, in the caller's order, its ``num_return_sequences``
+        best hypotheses, best first (``Hypothesis``: ``ids`` without the eos, ``score``, ``logprob``, ``finished``).
+
+        A request keeps ``num_beams`` = W hypotheses (1 .. 16).  Each decision takes, per beam, the 2W most probable next
+        tokens with their log-probabilities -- ``batch_generate_ids(top_logprobs=2W)``'s values bit for bit: temperature 1,
+        ``answer_id`` live at the first decision and suppressed afterwards -- adds them to the beam's summed
+        log-probability in fp32, and walks the 2W best of the W x 2W sums (ties: lower beam, then higher rank): an eos among
+        the first W finishes a hypothesis, which enters the request's pool of W with score ``logprob * float32(1 /
+        length ** length_penalty)`` (length counts the eos); an eos further down is dropped; the other candidates are the
+        next W beams.  A request is done when its pool is full and ``early_stopping``, or its best beam's score at the
+        current length cannot beat the pool's worst (HF's ``early_stopping=False`` rule).  At ``max_tokens`` every beam of a
+        request that is not done enters the pool as an unfinished hypothesis under the same rule.  ``ignore_eos``: nothing
+        finishes; every request runs to ``max_tokens``.  Beam rows are deterministic: there is no temperature / top-p / top-k
+        / min-p here.
+
+        On the device: each request's [image | prompt] is prefilled ONCE, into its own prefix slot, and its W
+        beams decode as rows that read that prefix and keep only their tails in slots of their own
+        (md_decode_step_shared).  After every step md_beam_select chooses the beams and md_kv_copy_tail moves each
+        surviving tail to the slot its child reads -- both inside the captured chunk (``compile()``); the host reads the
+        done flags once per chunk and the pools and planes once at the end.  The slab holds B x (1 + 2W) slots, sized up
+        front; a call of more than ``BEAM_LOCKSTEP_ROWS`` beam rows is split by requests.  A request's result does not
+        depend on the requests beside it wherever ``batch_generate_ids``' ids do not: bit for bit under
+        ``set_strict_batch_invariance``.  In the default mode ONE request with ``single_sequence_kernel`` on has its
+        prompt pass on the lone sequence's small-shape tiles, as ``batch_generate_ids([x])`` does, so its first decision
+        can differ from the same request's in a batch within bf16 accumulation-order noise; its decode steps, W > 1 rows,
+        run on the batched kernels with the pinned tiles either way.  The parent planes of the last call stay in
+        ``last_beam_trace``.
+
+        ValueError, before any GPU work: ``num_beams`` not an integer in 1 .. 16, ``num_return_sequences`` outside
+        1 .. num_beams, a ``length_penalty`` that is not finite, an ``early_stopping`` that is not a bool, ``max_tokens`` < 1,
+        an empty prompt, and the fp8 KV mode (the e4m3 copy of a moved tail is not kept; the fp8 / int4 WEIGHT streams are
+        served: the step is unchanged)."""
+        w, n_ret, lp, early = check_beams(num_beams, num_return_sequences, length_penalty, early_stopping)
+        b = len(images)
+        if b == 0 or b != len(prompts):
+            raise ValueError(f"batch_beam_search_ids: {b} images and {len(prompts)} prompts")
+        if any(len(p) == 0 for p in prompts):
+            raise ValueError("empty prompt")
+        if isinstance(max_tokens, bool) or int(max_tokens) < 1:
+            raise ValueError(f"max_tokens must be an integer >= 1, not {max_tokens!r}")
+        if self._kv8_scales is not None:
+            raise ValueError("beam search is not served in the fp8 KV mode (the e4m3 copy of a moved KV tail is not kept)")
+        eos = self.config.tokenizer.eos_id if eos_id is None else int(eos_id)
+        per = max(1, self.BEAM_LOCKSTEP_ROWS // w)
+        out: List[List[Hypothesis]] = []
+        for r0 in range(0, b, per):
+            out += self._beam_search(list(images[r0 : r0 + per]), [list(p) for p in prompts[r0 : r0 + per]], w, int(max_tokens),
+                                     -1 if ignore_eos else eos, lp, early, n_ret)
+        return out
+
+    def _beam_buffers(self, stream, groups: int, w: int) -> dict:
+        """The device arrays of a beam search over ``groups`` requests x ``w`` beams on ``stream``: made once per shape, so
+        that a later call of the shape replays the graphs that bake their addresses in."""
+        rows, dev = groups * w, self._device
+        i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
+        f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        return self._store.fixed("beam", (stream, groups, w), lambda: dict(
+            cum=f32(rows), cur=i32(rows), own=i32(rows, 2), len=i32(groups), done=i32(groups), prefix_len=i32(groups),
+            pool_n=i32(groups), pool_score=f32(groups, w), pool_sum=f32(groups, w), pool_parent=i32(groups, w),
+            pool_step=i32(groups, w), inv_norm=f32(self.config.text.max_context + 2), cand_ids=i32(rows, 2 * w),
+            cand_lp=f32(rows, 2 * w), src=i32(rows), dst=i32(rows), frm=i32(rows), to=i32(rows), prefix_slots=i32(rows),
+            prefix_len_rows=i32(rows), pos=i32(rows)))
+
+    def _beam_search(self, images, prompts, w: int, max_tokens: int, eos: int, length_penalty: float, early: bool,
+                     n_ret: int, check_every: int = 16) -> List[List[Hypothesis]]:
+        """``batch_beam_search_ids`` for requests that fit one lockstep (arguments checked; ``eos`` < 0: nothing finishes)."""
+        g, t = len(images), self.config.text
+        rows, n_slots = g * w, g * (1 + 2 * w)
+        tk = self.config.tokenizer
+        marks: list = []
+        mark = lambda name: self._mark(marks, name)
+        with torch.inference_mode():
+            self._ensure_batch(n_slots)  # the whole call's slab, before anything is placed in it
+            cap = torch.empty(g, t.vocab_size, dtype=BF16, device=self._device)
+            # request r (slot order) is prefilled, [image | prompt], into slot r: its beams' shared prefix
+            prep = self._prepare_sequences(images, prompts, mark, fuse=True, logits_capture=cap)
+            prefix = [int(p) for p in prep.next_pos]
+            # the steps run over requests x W rows: a lone request's beams are a batch, not the latency path of one
+            # sequence (its prompt pass, above, ran as a lone sequence's does: see the docstring of the public call)
+            self._select_kernels(rows)
+            steps_max = min(max_tokens, t.max_context - 1 - max(prefix))
+            if steps_max < 1:
+                raise ValueError("beam search: the prompt leaves no room in the context")
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            buf = self._beam_buffers(stream if self.use_graphs else None, g, w)
+            own = (g + 2 * np.arange(rows, dtype=np.int32)[:, None] + np.arange(2, dtype=np.int32)[None, :]).astype(np.int32)
+            cum0 = np.full(rows, -np.inf, dtype=np.float32)
+            cum0[::w] = 0.0
+            inv_norm = inv_norm_table(t.max_context + 2, length_penalty)
+            per_row = lambda xs: np.repeat(np.asarray(xs, dtype=np.int32), w)
+            init = dict(cum=cum0, cur=own[:, 0], own=own, prefix_len=np.asarray(prefix, np.int32), inv_norm=inv_norm,
+                        prefix_slots=per_row(range(g)), prefix_len_rows=per_row(prefix), pos=per_row(prefix))
+            for name, arr in init.items():
+                buf[name].copy_(self._h2d(torch.from_numpy(np.ascontiguousarray(arr))))
+            for name in ("len", "done", "pool_n", "pool_score", "pool_sum", "pool_parent", "pool_step"):
+                buf[name].zero_()
+            for name in ("src", "dst"):
+                buf[name].fill_(-1)
+            state = _lib.MdBeamState(*(buf[n].data_ptr() for n in ("cum", "cur", "own", "len", "done", "prefix_len", "pool_n",
+                                                                    "pool_score", "pool_sum", "pool_parent", "pool_step",
+                                                                    "inv_norm")), inv_norm.size, buf["cand_ids"].data_ptr(),
+                                     buf["cand_lp"].data_ptr())
+            keep = tuple(buf[n] for n in ("cum", "cur", "own", "len", "done", "prefix_len", "pool_n", "pool_score", "pool_sum",
+                                          "pool_parent", "pool_step", "inv_norm", "cand_ids", "cand_lp"))
+            hist = torch.zeros(steps_max, rows, dtype=torch.int32, device=self._device)
+            parents = torch.full((steps_max, rows), -1, dtype=torch.int32, device=self._device)
+            beam = Beam(w, eos, early, state, parents, buf["src"], buf["dst"], buf["frm"], buf["to"], n_slots, keep)
+            # decision 0, from the prompt pass's logits: one row per request, nothing suppressed, no tail to move yet
+            self._beam_select(cap, -1, beam, 1, hist[0], parents[0])
+            routing = _Rows(slots=buf["cur"], n_slots=n_slots, prefix_slots=buf["prefix_slots"], prefix_len=buf["prefix_len_rows"])
+            chunk = DecodeChunk(rows, hist, buf["pos"], lambda i: routing, tk.answer_id, self._decode_ws_bytes(routing, rows),
+                                beam=beam)
+            graphs = self.use_graphs
+            total = steps_max - 1  # decode steps: decision d >= 1 is step d - 1's
+            per = max(1, min(check_every, total)) if graphs else check_every
+            pos_base = buf["pos"].clone()
+            steps = 0
+            while steps < total:
+                n = min(per, total - steps)
+                if graphs:
+                    tok_buf, par_buf = self._store.fixed("beam-chunk", (stream, g, w, n), lambda: (
+                        torch.zeros(n + 1, rows, dtype=torch.int32, device=self._device),
+                        torch.zeros(n, rows, dtype=torch.int32, device=self._device)))
+                    tok_buf[0] = hist[steps]
+                    buf["pos"].copy_(pos_base + steps)
+                    part = replace(chunk, tokens=tok_buf, beam=replace(beam, parents=par_buf))
+                else:
+                    part = replace(chunk, tokens=hist[steps:], beam=replace(beam, parents=parents[steps + 1 :]))
+                run_chunk(self, part, n, tag="beam", capture_stream=stream if graphs else None)
+                if graphs:
+                    hist[steps + 1 : steps + n + 1] = tok_buf[1:]
+                    parents[steps + 1 : steps + n + 1] = par_buf
+                steps += n
+                if steps < total and bool(buf["done"].all()):  # the chunk's one host read
+                    break
+            mark("decode")
+            host = {n: buf[n].cpu().numpy() for n in ("cum", "len", "done", "pool_n", "pool_score", "pool_sum", "pool_parent",
+                                                      "pool_step")}
+            toks = hist[: steps + 1].cpu().numpy().reshape(steps + 1, g, w)
+            pars = parents[: steps + 1].cpu().numpy().reshape(steps + 1, g, w)
+        self._phase_times(marks)
+        self.last_beam_trace = {"tokens": toks[:, np.argsort(prep.order)], "parents": pars[:, np.argsort(prep.order)]}
+        per_slot = [finalize(w, n_ret, int(host["len"][r]), bool(host["done"][r]), host["cum"][r * w : (r + 1) * w],
+                             int(host["pool_n"][r]), host["pool_score"][r], host["pool_sum"][r], host["pool_parent"][r],
+                             host["pool_step"][r], toks[:, r], pars[:, r], inv_norm) for r in range(g)]
+        return prep.in_caller_order(per_slot)
+
+    def _beam_best_ids(self, images, prompts: Sequence[Sequence[int]], settings: Optional[dict],
+                       beams: Tuple[int, float, bool]) -> List[List[int]]:
+        """The string API's beam route: the best hypothesis's ids per request.  ``settings``' ``max_tokens`` applies; what
+        beam search does not serve is refused here, what it ignores (temperature, top_p, top_k, min_p: beam rows are
+        deterministic) is checked as ever and unused."""
+        st = settings or {}
+        where = "beam search (num_beams > 1)"
+        refuse_penalties(settings, where, len(images))
+        refuse_constraints(settings, where)
+        check_filters(*filters_of(settings).values(), len(images))
+        if st.get("variant") is not None or st.get("variants") is not None:
+            raise ValueError(f"LoRA variant / variants are not served by {where}")
+        w, lp, early = beams
+        hyps = self.batch_beam_search_ids(images, prompts, w, max_tokens=st.get("max_tokens", DEFAULT_MAX_TOKENS),
+                                          length_penalty=lp, early_stopping=early)
+        return [h[0].ids for h in hyps]
+
+    def _string_ids(self, images, prompts: Sequence[Sequence[int]], settings: Optional[dict], **kw) -> List[List[int]]:
+        """The ids behind ``batch_caption`` / ``batch_query`` / ``query_many``: ``batch_generate_ids`` with the settings'
+        sampling arguments (``kw``: its further ones), or, with ``settings["num_beams"]`` > 1, the best beam hypothesis."""
+        beams = beams_of(settings)
+        if beams is not None:
+            return self._beam_best_ids(images, prompts, settings, beams)
+        return self.batch_generate_ids(images, prompts, **kw, **self._sampling_kwargs(settings))
+
     def batch_generate_ids_continuous(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                                       eos_id: Optional[int] = None, ignore_eos: bool = False, max_live: int = 64, chunk: int = 16,
                                       temperature: Union[float, Sequence[float]] = 0.0,
@@ -2087,7 +2295,7 @@ class MoondreamModel:
             raise NotImplementedError("Model does not support captioning.")
         if length not in tpl:
             raise ValueError(f"Model does not support caption length '{length}'.")
-        ids = self.batch_generate_ids(images, [tpl[length]] * len(images), **self._sampling_kwargs(settings))
+        ids = self._string_ids(images, [tpl[length]] * len(images), settings)
         return [self.tokenizer.decode(s) for s in ids]
 
     def _query_prompts(self, questions: Sequence[str]) -> List[List[int]]:
@@ -2113,8 +2321,9 @@ class MoondreamModel:
         the same distribution per decision, other ids.  Not served, NotImplementedError: LoRA ``variant`` / ``variants``, the fp8
         modes, a query template whose suffix is not one token, a checkpoint without a region head."""
         if reasoning:
+            refuse_beams(settings, "reasoning queries")
             return self._reasoning_answers(self._batch_query_reasoning(images, questions, settings, share_prefix=False))
-        ids = self.batch_generate_ids(images, self._query_prompts(questions), **self._sampling_kwargs(settings))
+        ids = self._string_ids(images, self._query_prompts(questions), settings)
         return [self.tokenizer.decode(s) for s in ids]
 
     def batch_generate(self, images, prompts: Optional[Sequence[str]] = None, settings: Optional[dict] = None) -> List[str]:
@@ -2263,11 +2472,16 @@ class MoondreamModel:
         check_penalties(*penalties_of(settings).values(), 1)  # host values: before any GPU work
         check_filters(*filters_of(settings).values(), 1)
         self._check_constraints_of(settings, 1)
+        beams = beams_of(settings)
         tpl = self.config.tokenizer.templates["caption"]
         if tpl is None:
             raise NotImplementedError("Model does not support captioning.")
         if length not in tpl:
             raise ValueError(f"Model does not support caption length '{length}'.")
+        if beams is not None:  # beam search: the batched route's best hypothesis, as one string
+            if stream:
+                raise ValueError("num_beams > 1 (beam search) is not served with stream=True")
+            return {"caption": self.batch_caption([image], length, settings)[0]}
         enc = self.encode_image(image, settings)
         self.load_encoded_image(enc)
         prompt = torch.tensor([tpl[length]])
@@ -2289,6 +2503,13 @@ class MoondreamModel:
             raise ValueError("question must be provided.")
         if spatial_refs and image is None:
             raise ValueError("spatial_refs can only be used with an image.")
+        beams = beams_of(settings)
+        if beams is not None:  # beam search: the batched route's best hypothesis, as one string
+            if reasoning or stream:
+                raise ValueError("num_beams > 1 (beam search) is not served with reasoning=True or stream=True")
+            if image is None or spatial_refs:
+                raise ValueError("num_beams > 1 (beam search) is served for a query about an image, without spatial_refs")
+            return {"answer": self.batch_query([image], [question], settings)[0]}
         if reasoning:
             refuse_penalties(settings, "reasoning queries")
             refuse_constraints(settings, "reasoning queries")
@@ -2727,6 +2948,7 @@ class MoondreamModel:
         refuse_penalties(settings, "reasoning queries")
         refuse_constraints(settings, "reasoning queries")
         refuse_filters(settings, "reasoning queries (the reasoning loop picks with the call's temperature and top-p alone)")
+        refuse_beams(settings, "reasoning queries")
         if st.get("variant") is not None or st.get("variants") is not None:
             raise NotImplementedError("batched reasoning queries are not served with LoRA variants (variant / variants): "
                                       "use query(reasoning=True) per image")
@@ -2815,6 +3037,7 @@ class MoondreamModel:
         refuse_penalties(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
         refuse_constraints(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
         refuse_filters(settings, f"{kind}: its loop decodes coordinates, not tokens sampled from logits")
+        refuse_beams(settings, f"{kind}: its loop decodes coordinates, not token hypotheses")
         return check_score_settings(settings, self.config.region.coord_out_dim)
 
     def batch_detect(self, images, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
@@ -2848,8 +3071,9 @@ class MoondreamModel:
         check_penalties(*penalties_of(settings).values(), len(prompts))  # host values: before any GPU work
         check_filters(*filters_of(settings).values(), len(prompts))
         self._check_constraints_of(settings, len(prompts))
+        beams_of(settings)  # (checked before the image is encoded)
         enc = self.encode_image(image, settings)
-        ids = self.batch_generate_ids([enc] * len(prompts), prompts, share_prefix=True, **self._sampling_kwargs(settings))
+        ids = self._string_ids([enc] * len(prompts), prompts, settings, share_prefix=True)
         return [{"answer": self.tokenizer.decode(s)} for s in ids]
 
     def query_many_reasoning(self, image, questions: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
