@@ -647,6 +647,52 @@ md_status md_vit_encode(const md_vit_model* m, const void* crops, int32_t crops_
                         int32_t n_crops, void* out, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* Image preprocessing on the device: the crops the encoder takes (MD_CROPS_U8_HWC), cut from raw RGB images with Pillow's
+ * 8-bit LANCZOS resize restated as the integer arithmetic it is -- per output pixel a window [xmin, xmin + n) of taps with
+ * int32 coefficients at 22 fractional bits, ((1 << 21) + sum k * pixel) >> 22 in int32 (wrapping, as C's int) clamped to
+ * 0 .. 255, horizontally into a uint8 intermediate and then vertically.  With the tables of moondream_amd/resample.py the
+ * crops are byte for byte those of image_crops.overlap_crop_image on its PIL branch.
+ *   packed (device, 16-byte aligned, packed_bytes long): [descriptors | coefficient tables | raw RGB pixels], one upload.
+ *   The descriptors are n_images x MD_RESAMPLE_DESC_WORDS int64 at byte 0; offsets are bytes from `packed`:
+ *     0 src_h  1 src_w  2 tiles_h  3 tiles_w  4 crop0 (the image's first crop slot)  5 mode  6 pixels (uint8 [src_h][src_w][3],
+ *     a multiple of 16)  7 the image's intermediates (bytes from `workspace`)
+ *     8 + 12 * t .. : target t -- out_h, out_w, taps per row of the horizontal and of the vertical table, then the offsets
+ *     (multiples of 4) of the horizontal bounds int32 [out_w][2] = (xmin, n), the horizontal coefficients int32 [out_w][taps],
+ *     the vertical bounds [out_h][2] and the vertical coefficients [out_h][taps], then the target's first workgroup in the
+ *     horizontal and in the vertical launch.
+ *   mode MD_RESAMPLE_TWO_TARGETS: target 0 (crop x crop, the global crop) goes to slot crop0; target 1, of size
+ *     (tiles_h * window + 2 * margin_px) x (tiles_w * window + 2 * margin_px), is never stored as an image: each of its pixels
+ *     goes into every slot crop0 + 1 + ty * tiles_w + tx whose window [ty * window, ty * window + crop) x [tx * window, ..)
+ *     holds it.  MD_RESAMPLE_BOTH_SLOTS (tiling (1, 1): the global and the local crop are one computation): target 0 goes to
+ *     slots crop0 and crop0 + 1.  MD_RESAMPLE_ONE_SLOT: to crop0 alone (the caller encodes it once).
+ *   Canonical order is part of the contract and checked: crop0 and the intermediates' offsets are running sums over the
+ *     images (an image's intermediates: target 0's uint8 [src_h][pitch], then target 1's; pitch = out_w * 3 rounded up to
+ *     16), the workgroup prefixes are running sums of ceil(out_w * 3 / MD_RESAMPLE_H_SEG_BYTES) * ceil(src_h /
+ *     MD_RESAMPLE_H_ROWS) and of ceil(pitch / MD_RESAMPLE_V_SEG_BYTES) * ceil(out_h / MD_RESAMPLE_V_ROWS) over (image,
+ *     target), an absent target carrying its successor's; total_crops is the sum of the images' slots.
+ *   host_desc: the SAME descriptors in host memory: they are what is validated, before any launch -- every size, offset and
+ *     extent against packed_bytes, total_crops and workspace_bytes.  The tables' CONTENTS are device data: a window that
+ *     leaves the image or the staged span contributes nothing (no address outside the image, the workspace or crops_out is
+ *     formed), and the result is then not PIL's.
+ *   crops_out: uint8 [total_crops][crop][crop][3]; every byte of it is written, nothing outside it.
+ * Two launches over the whole chunk, each a flat list of workgroups over (image, target).  No host sync, no allocation.
+ * MD_ERR_INVALID_ARG: NULL or misaligned pointers, n_images outside 1 .. MD_RESAMPLE_MAX_IMAGES, crop != window + 2 *
+ * margin_px, a side outside 1 .. MD_RESAMPLE_MAX_SIDE, an unknown mode, target sizes that are not the geometry's, anything
+ * that is not in canonical order or reaches outside packed_bytes.  MD_ERR_WORKSPACE: workspace_bytes below
+ * md_image_resample_workspace_bytes.  MD_ERR_UNSUPPORTED: a horizontal scale whose staged span does not fit the LDS. */
+#define MD_RESAMPLE_DESC_WORDS 32
+#define MD_RESAMPLE_MAX_SIDE 16384
+#define MD_RESAMPLE_MAX_IMAGES 4096
+#define MD_RESAMPLE_H_SEG_BYTES 256
+#define MD_RESAMPLE_H_ROWS 4
+#define MD_RESAMPLE_V_SEG_BYTES 1024
+#define MD_RESAMPLE_V_ROWS 8
+enum { MD_RESAMPLE_TWO_TARGETS = 0, MD_RESAMPLE_BOTH_SLOTS = 1, MD_RESAMPLE_ONE_SLOT = 2 };
+size_t md_image_resample_workspace_bytes(const int64_t* host_desc, int32_t n_images);
+md_status md_image_resample_crops(const void* packed, size_t packed_bytes, const int64_t* host_desc, int32_t n_images,
+                                  int32_t crop, int32_t window, int32_t margin_px, void* crops_out, int32_t total_crops,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
 size_t md_vision_project_workspace_bytes(const md_vit_model* m, int32_t n_images);
 
 /* vision_projection for n_images images that all share one tiling

@@ -28,15 +28,15 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import _lib
+from . import _lib, resample
 from .config import MoondreamConfig
 from .constraint import FREE, TokenAutomaton, check_constraints, pack, pow2_at_least, refuse_constraints
-from .crop_staging import CropStager, crop_workers, upload_unique
+from .crop_staging import CropStager, crop_workers, plan_chunks, upload_unique
 from .beam import Hypothesis, beams_of, check_beams, finalize, inv_norm_table, refuse_beams
 from .decode_loop import (Beam, Constraint, DecodeChunk, Penalty, ReasonChunk, Sampling, check_filters, check_penalties, check_score_settings,
                           check_top_logprobs, filters_of, penalties_of, refuse_filters, refuse_penalties, run_chunk)
 from .graph_store import GraphStore
-from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops
+from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops, resize_backend
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
 from .lora import variant_state_dict
 from .scores import Scores
@@ -330,6 +330,9 @@ class MoondreamModel:
         self.fused_prefill = True
         # encode byte-identical crops of an image once (images that fit one crop: global == local); off = what the reference does
         self.dedup_identical_crops = False
+        # resize and tiling on the device (resample.py, md_image_resample_crops): the raw pixels are uploaded and the crops cut
+        # there, the same bytes as the host's PIL path.  Opt-in; prefetch_crops and the pipelined engines keep staging on the host
+        self._device_preprocess = False
         v = config.vision  # host tiling into pinned buffers: the ring, the pools and the batches staged ahead (crop_staging.py)
         self._staging = CropStager(partial(_count_crops, v), partial(_crop_into, v), (v.crop_size, v.crop_size, 3), _crop_pool_workers)
         if setup_caches:
@@ -849,13 +852,68 @@ class MoondreamModel:
         oc = overlap_crop_image(arr, max_crops=v.max_crops, overlap_margin=v.overlap_margin)
         return oc["crops"], tuple(oc["tiling"])
 
+    @property
+    def device_preprocess(self) -> bool:
+        """Resize and tile images on the device (PIL-exact; resample.py).  Off by default."""
+        return self._device_preprocess
+
+    @device_preprocess.setter
+    def device_preprocess(self, on: bool) -> None:
+        if on and resize_backend() != "pil":
+            raise ValueError("device_preprocess implements the PIL resize only and this process resizes with pyvips: "
+                             "start it with MOONDREAM_RESIZE=pil")
+        self._device_preprocess = bool(on)
+
+    def _device_plan(self, images: Sequence[Image.Image]):
+        """The images' resample.plan records when this call is preprocessed on the device, else None: the switch is off,
+        host crops of exactly these images were prefetched, or an image is outside the device path's limits."""
+        if not self._device_preprocess or tuple(id(im) for im in images) in self._staging.prefetched:
+            return None
+        return resample.plan([(im.size[1], im.size[0]) for im in images], self.config.vision)
+
+    def _encode_crops_on_device(self, images: Sequence[Image.Image], records, mark=None) -> torch.Tensor:
+        """The device form of the loop below: per ViT chunk ONE upload of [descriptors | tables | raw RGB pixels], the two
+        resample launches that cut the crops, the ViT."""
+        v, ring = self.config.vision, self._staging.ring
+        dedup = self.dedup_identical_crops
+        feat_parts = []
+        for ci, (i0, i1, _) in enumerate(plan_chunks([r.n_crops for r in records], self.vit_chunk_crops)):
+            lay = resample.layout(records[i0:i1], v, dedup=dedup)
+            with ring.take(lay.nbytes) as lease:  # taken over by its upload, or given back here
+                lay.write(lease.array((lay.nbytes,)),
+                          [np.asarray(im if im.mode == "RGB" else im.convert("RGB")) for im in images[i0:i1]])
+                if mark is not None and ci == 0:
+                    mark("host_tiling")  # (the same key as the host path: what the host does before the GPU has work)
+                packed = lease.upload(self._device)
+            crops = torch.empty(lay.out_crops, v.crop_size, v.crop_size, 3, dtype=torch.uint8, device=self._device)
+            ws = self._workspace(self.lib.md_image_resample_workspace_bytes(lay.desc.ctypes.data, i1 - i0))
+            crop, window, margin_px = resample.geometry(v)
+            _lib.check(
+                self.lib.md_image_resample_crops(
+                    packed.data_ptr(), packed.numel(), lay.desc.ctypes.data, i1 - i0, crop, window, margin_px,
+                    crops.data_ptr(), lay.out_crops, ws.data_ptr(), ws.numel(), self._stream(),
+                ),
+                "md_image_resample_crops",
+            )
+            f = self._vit_run(crops, _lib.MD_CROPS_U8_HWC)
+            if lay.expand is not None:
+                f = f[torch.tensor(lay.expand, dtype=torch.int64, device=self._device)]
+            feat_parts.append(f)
+        feats = feat_parts[0] if len(feat_parts) == 1 else torch.cat(feat_parts, dim=0)
+        # (_project_by_tiling reads an image's crop count and tiling: no host pixels exist on this path)
+        return self._project_by_tiling(feats, [(np.broadcast_to(np.uint8(0), (r.n_crops,)), r.tiling) for r in records])
+
     def _run_vision_encoder_batch(self, images: Sequence[Image.Image], mark=None, staged=None) -> torch.Tensor:
         """images -> [B,729,D] projected embeddings (reference: moondream.py:206-228, per image).
 
         Host tiling (PIL, reference image_crops.py:58-167) runs on a thread pool and is pipelined against the GPU
         (crop_staging.py): the ViT of image chunk k is enqueued (async) while the crops of chunk k+1 are still being cut.
-        ``staged``: these images' StagedBatch when the caller started it ahead; otherwise a prefetched one, or one made now."""
+        ``staged``: these images' StagedBatch when the caller started it ahead; otherwise a prefetched one, or one made now.
+        With ``device_preprocess`` on and nothing staged ahead, resize and tiling run on the device instead."""
         if staged is None:
+            records = self._device_plan(images)
+            if records is not None:
+                return self._encode_crops_on_device(list(images), records, mark)
             staged = self._staging.take(images, self.vit_chunk_crops)
         cropped: List[Tuple[np.ndarray, Tuple[int, int]]] = []
         feat_parts = []
