@@ -570,6 +570,26 @@ md_status md_region_pick_encode(const void* logits, int64_t ld, int32_t batch, i
                                 int32_t n_bins, const void* value_table, const void* feat_w, int32_t half,
                                 int32_t* bins, int64_t ld_bins, void* feats, int64_t ld_feats, void* stream);
 
+/* The spatial references of a batch of prompts (reference: region.py:96-136, placed by moondream.py:293-301): ONE launch
+ * encodes every reference TOKEN of a call and stores it into its row of the prompt embeddings.
+ * desc int32 [n][4], 16-byte aligned, one descriptor per token: {dst, kind, v0, v1} -- kind 0: a coordinate (value v0,
+ * the coord_* operands), kind 1: a size (values v0, v1, the size_* operands); a value is a bf16 bit pattern in the low 16
+ * bits.  For every descriptor, with row = dst - dst0 in [0, rows):
+ *     feat = md_fourier_features' row of the value(s) (bit for bit),
+ *     emb[row][j] = bf16(b[j] + sum_k feat[k] * w[j][k])    for j < dim, accumulated in fp32.
+ * *_fw: the Fourier matrix bf16 [in_dim][*_feat / 2]; *_w: the encoder bf16 [dim][*_ldw], row-major, k < *_feat read;
+ * *_b: bf16 [dim].  emb bf16 [rows][ld].  A descriptor of another kind, or whose row lies outside [0, rows), stores
+ * nothing; nothing else of emb is written (plain vector stores, 8 bytes each); the caller keeps the dst values distinct.
+ * A token's result depends on its values and the operands alone -- not on n, its index in the table, dst or the other
+ * descriptors: a workgroup owns 16 descriptors and 64 columns (an encoder row is fetched once per 16 tokens) and sums in an
+ * order fixed by *_feat (csrc/sampling_region.hip).  No host sync, no allocation: capturable.
+ * MD_ERR_INVALID_ARG: a NULL pointer, n <= 0, rows <= 0, dim <= 0 or dim % 4, ld < dim or ld % 4, a *_feat <= 0, % 8 or
+ * > 2048, a *_ldw < *_feat or % 4, desc not 16-byte or an encoder / bias / emb pointer not 8-byte aligned. */
+md_status md_spatial_ref_embed(const int32_t* desc, int32_t n, const void* coord_fw, int32_t coord_feat,
+                               const void* coord_w, int64_t coord_ldw, const void* coord_b, const void* size_fw,
+                               int32_t size_feat, const void* size_w, int64_t size_ldw, const void* size_b, int32_t dim,
+                               void* emb, int64_t ld, int64_t dst0, int32_t rows, void* stream);
+
 /* md_region_pick_encode with a confidence per pick.  bins and feats: md_region_pick_encode's on the same inputs, bit for bit
  * (ties -> lowest bin, an all-NaN group -> bin 0).  logprobs fp32 [batch][ld_logprobs]: for group g of row b, with x the
  * group's bf16 logits as fp32, p = bins[b][g] and m = x[p],

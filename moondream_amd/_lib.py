@@ -256,6 +256,8 @@ SIGNATURES = {
                                         c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "md_region_pick_encode_scored": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                                c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p]),
+    "md_spatial_ref_embed": (C.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int32,
+                                       c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int32, c_void_p]),
     "md_stitch_pool_concat": (C.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "md_vit_workspace_bytes": (c_size_t, [P(MdVitModel), c_int32]),
     "md_vit_encode": (C.c_int, [P(MdVitModel), c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),

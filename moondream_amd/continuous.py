@@ -29,6 +29,7 @@ from .constraint import FREE, TokenAutomaton, pack
 from .decode_loop import (FILTER_NEUTRAL, PENALTY_NEUTRAL, Constraint, DecodeChunk, Penalty, Sampling, check_filters, check_penalties,
                           check_top_logprobs, run_chunk)
 from .scores import HostScores, Scores
+from .spatial import SpatialRecord, check_spatial_refs, spatial_prompt_ids
 
 DEFAULT_MAX_TOKENS = 768  # moondream.py (the reference's default, moondream.py:50-53)
 DEFAULT_TOP_P = 0.3
@@ -84,6 +85,7 @@ class Request:
     constraint_start: int = FREE  # its start state in the engine's table
     top_k: int = 0      # sampled rows only: the first top_k tokens of the descending order (0: off) ...
     min_p: float = 0.0  # ... and the tokens of probability >= min_p * the best one's (0: off): md_sample_rows_filtered
+    spatial: Optional[Tuple[int, list]] = None  # (position of the first placeholder in ``prompt``, the checked refs); None: no refs
 
     @property
     def filtered(self) -> bool:
@@ -376,12 +378,15 @@ class ContinuousEngine:
                seed: Optional[int] = None, ignore_eos: bool = False, variant: Optional[str] = None,
                temperature: Optional[float] = None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-               constraint: Optional[TokenAutomaton] = None, top_k: Optional[int] = None, min_p: Optional[float] = None) -> int:
+               constraint: Optional[TokenAutomaton] = None, top_k: Optional[int] = None, min_p: Optional[float] = None,
+               spatial: Optional[Tuple[int, list]] = None) -> int:
         """Queue one request; ``image`` is a PIL image or an EncodedImage.  ``eos_id`` None: the tokenizer's EOS
         (``ignore_eos``: none).  ``temperature`` / ``top_p`` None: the engine's.  The three penalties (None: neutral):
         one number each, ``batch_generate_ids``' rule and validation.  ``constraint``: one ``TokenAutomaton`` (None: free),
         ``batch_generate_ids``' rule and validation; ValueError when the engine's table has no room for it.  ``top_k`` /
-        ``min_p`` (None: off): one value each, ``batch_generate_ids``' rule and validation.  Returns its id."""
+        ``min_p`` (None: off): one value each, ``batch_generate_ids``' rule and validation.  ``spatial``: what
+        ``submit_query(spatial_refs=)`` builds -- (the position of the first placeholder in ``prompt_ids``, the checked
+        refs), encoded into the prompt embeddings at admission.  Returns its id."""
         from PIL import Image
 
         from .moondream import EncodedImage
@@ -417,7 +422,7 @@ class ContinuousEngine:
         self._next_rid += 1
         self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed, variant=vidx, temperature=temp, top_p=tp,
                                   penalties=pen[0] if pen else PENALTY_NEUTRAL, constraint=constraint, constraint_start=start,
-                                  top_k=filt[0][0] if filt else 0, min_p=filt[0][1] if filt else 0.0))
+                                  top_k=filt[0][0] if filt else 0, min_p=filt[0][1] if filt else 0.0, spatial=spatial))
         return rid
 
     def _register_constraint(self, a: TokenAutomaton) -> int:
@@ -459,13 +464,23 @@ class ContinuousEngine:
             raise ValueError(f"Model does not support caption length '{length}'.")
         return self.submit(image, tpl[length], **kw)
 
-    def submit_query(self, image, question: str, **kw) -> int:
-        """The prompt ``batch_query`` builds."""
-        tpl = self.model.config.tokenizer.templates["query"]
+    def submit_query(self, image, question: str, spatial_refs=None, **kw) -> int:
+        """The prompt ``batch_query`` builds.  ``spatial_refs``: the request's points ``(x, y)`` / boxes ``(x0, y0, x1,
+        y1)`` in front of the question, ``batch_query``'s rule and validation for one row; they are a property of the
+        request, encoded into its prompt embeddings when it is admitted (md_spatial_ref_embed, through the model's one
+        sequence preparation)."""
+        tk = self.model.config.tokenizer
+        tpl = tk.templates["query"]
         if tpl is None:
             raise NotImplementedError("Model does not support querying.")
-        prompt = list(tpl["prefix"]) + list(self.model.tokenizer.encode(question).ids) + list(tpl["suffix"]) + list(tpl["suffix"])
-        return self.submit(image, prompt, **kw)
+        q = list(self.model.tokenizer.encode(question).ids)
+        refs = []
+        if spatial_refs is not None:
+            rows = check_spatial_refs([spatial_refs], 1, [image is not None], [q], tk.coord_id, tk.size_id,
+                                      getattr(self.model.w, "region", None) is not None)
+            refs = rows[0] if rows else []
+        prompt = spatial_prompt_ids(tpl["prefix"], refs, q + list(tpl["suffix"]) + list(tpl["suffix"]), tk.coord_id, tk.size_id)
+        return self.submit(image, prompt, **kw, **({"spatial": (len(tpl["prefix"]), refs)} if refs else {}))
 
     # ---- running
     def run(self, with_logprobs: bool = False, with_alternatives: Optional[bool] = None) -> Iterator[tuple]:
@@ -643,7 +658,11 @@ class ContinuousEngine:
         if any(r.constraint is not None for r in rows):  # the rows' start states, beside the engine's table
             con = self._constraint(m._h2d(torch.tensor([r.constraint_start for r in rows], dtype=torch.int32)), by_slot=False)
         scores = Scores.new((len(rows),), self.top_logprobs, m.device) if self.logprobs else None
-        embed = m._sequence_embeddings([r.prompt for r in rows], [r.image for r in rows] if fused else None)
+        spatial = None
+        if any(r.spatial for r in rows):  # the rows' references: one record, one upload, one launch per pass
+            spatial = SpatialRecord.build([r.spatial[1] if r.spatial else [] for r in rows],
+                                          [r.spatial[0] if r.spatial else 0 for r in rows], [len(r.prompt) for r in rows])
+        embed = m._sequence_embeddings([r.prompt for r in rows], [r.image for r in rows] if fused else None, spatial=spatial)
         first, _, next_pos = m._prefill_groups(groups, embed, starts, routes, pick, scores=scores, constraint=con,
                                                uniforms=st[2] if st is not None else None, head_rows=64)
         self.stats.prefill_passes += len(groups)

@@ -179,6 +179,125 @@ __global__ __launch_bounds__(256) void region_pick_scored_kernel(const bf16_t* _
 }
 
 // ---------------------------------------------------------------------------
+// Spatial references of a batch of prompts (reference: region.py:96-136 + moondream.py:293-301): every reference
+// TOKEN of a call -- a coordinate (one value, coord_encoder) or a size (two values, size_encoder) -- is encoded and
+// stored into its row of the prompt embeddings in ONE launch.
+//   feat = fourier_row(values)                       (bf16, in LDS: md_fourier_features' bits)
+//   emb[dst][n] = bf16(bias[n] + sum_k feat[k] * W[n][k])                 (fp32)
+// A workgroup owns SREF_TOKENS descriptors and SREF_COLS output columns, so an encoder row is fetched once per 16
+// tokens.  A wave takes 16 of the columns, one at a time: its 64 lanes split K (4 consecutive k per lane and trip of
+// 256), each lane keeps one partial sum per token, and a halving butterfly (lane ^ 32, 16, 8, 4: half of the tokens
+// stay on either side; then ^ 2, ^ 1) leaves token (lane >> 2)'s total on its four lanes.  The order of every
+// addition is a function of K alone: fp32 addition commutes, so which side of an exchange a token stays on -- its
+// place in the group -- does not change a bit, and neither do the table's length, the token's index or dst.
+constexpr int SREF_TOKENS = 16;
+constexpr int SREF_COLS = 64;
+constexpr int SREF_THREADS = 256;
+
+struct SpatialRefArgs {
+  const int32_t* desc;  // [n][4]: dst, kind (0 coordinate, 1 size), value bits, value bits
+  int n;
+  const bf16_t *fw0, *w0, *b0, *fw1, *w1, *b1;  // Fourier matrix, encoder, bias of either kind
+  int feat0, feat1, feat_max;
+  int64_t ldw0, ldw1;
+  int dim;
+  bf16_t* emb;
+  int64_t ld, dst0;
+  int rows;
+};
+
+template <int H>
+__device__ __forceinline__ void sref_fold(const float* in, float* out, int lane) {
+  const bool hi = (lane & (4 * H)) != 0;  // H = 8, 4, 2, 1 tokens kept: lanes ^ 32, 16, 8, 4
+#pragma unroll
+  for (int j = 0; j < H; ++j) {
+    const float keep = hi ? in[j + H] : in[j];
+    const float send = hi ? in[j] : in[j + H];
+    out[j] = keep + __shfl_xor(send, 4 * H, 64);
+  }
+}
+
+__global__ __launch_bounds__(SREF_THREADS) void spatial_ref_embed_kernel(SpatialRefArgs a) {
+  extern __shared__ __attribute__((aligned(16))) bf16_t sref_feat[];  // [SREF_TOKENS][feat_max]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int t0 = blockIdx.x * SREF_TOKENS;
+  const int nt = min(SREF_TOKENS, a.n - t0);
+  const int4* desc = reinterpret_cast<const int4*>(a.desc) + t0;
+
+  // zero fill: every LDS word a pass reads is defined.  In the pass of the OTHER kind a token's row holds what it has
+  // (a coordinate's features then zeros; the head of a size's features): that lane sum is meaningless and is never
+  // stored -- only tokens of the pass's kind (`live`) store.
+  for (int i = tid; i < SREF_TOKENS * a.feat_max / 8; i += SREF_THREADS) reinterpret_cast<uint4*>(sref_feat)[i] = uint4{0, 0, 0, 0};
+  __syncthreads();
+  unsigned live0 = 0u, live1 = 0u;  // the group's tokens of either kind whose destination lies inside the tensor
+  for (int t = 0; t < nt; ++t) {
+    const int4 d = desc[t];  // the same for every thread
+    const int64_t row = (int64_t)d.x - a.dst0;
+    if ((d.y != 0 && d.y != 1) || row < 0 || row >= a.rows) continue;
+    if (d.y) live1 |= 1u << t; else live0 |= 1u << t;
+    const float v[2] = {bf2f((bf16_t)d.z), bf2f((bf16_t)d.w)};
+    fourier_row(v, d.y + 1, d.y ? a.fw1 : a.fw0, (d.y ? a.feat1 : a.feat0) / 2, sref_feat + t * a.feat_max);
+  }
+  __syncthreads();
+
+  const int slot = lane >> 2, part = lane & 3;                       // after the butterfly: the lane's token, and
+  const int col4 = blockIdx.y * SREF_COLS + wave * 16 + part * 4;    // the four columns it stores
+  for (int p = 0; p < 2; ++p) {
+    const unsigned live = p ? live1 : live0;
+    if (!live) continue;
+    const bf16_t* w = p ? a.w1 : a.w0;
+    const int64_t ldw = p ? a.ldw1 : a.ldw0;
+    const int K = p ? a.feat1 : a.feat0;
+    float res[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      res[i] = 0.f;
+      for (int c = 0; c < 4; ++c) {
+        const int col = blockIdx.y * SREF_COLS + wave * 16 + c * 4 + i;  // the same for the whole wave
+        float acc[SREF_TOKENS];
+#pragma unroll
+        for (int t = 0; t < SREF_TOKENS; ++t) acc[t] = 0.f;
+        if (col < a.dim) {
+          for (int k0 = lane * 4; k0 < K; k0 += 256) {
+            const uint2 wv = *reinterpret_cast<const uint2*>(w + (int64_t)col * ldw + k0);
+            const float wk[4] = {bf2f((bf16_t)(wv.x & 0xffffu)), bf2f((bf16_t)(wv.x >> 16)), bf2f((bf16_t)(wv.y & 0xffffu)),
+                                 bf2f((bf16_t)(wv.y >> 16))};
+#pragma unroll
+            for (int t = 0; t < SREF_TOKENS; ++t) {
+              const uint2 fv = *reinterpret_cast<const uint2*>(sref_feat + t * a.feat_max + k0);
+              acc[t] += bf2f((bf16_t)(fv.x & 0xffffu)) * wk[0];
+              acc[t] += bf2f((bf16_t)(fv.x >> 16)) * wk[1];
+              acc[t] += bf2f((bf16_t)(fv.y & 0xffffu)) * wk[2];
+              acc[t] += bf2f((bf16_t)(fv.y >> 16)) * wk[3];
+            }
+          }
+        }
+        float a8[8], a4[4], a2[2], a1[1];
+        sref_fold<8>(acc, a8, lane);
+        sref_fold<4>(a8, a4, lane);
+        sref_fold<2>(a4, a2, lane);
+        sref_fold<1>(a2, a1, lane);
+        float s = a1[0];
+        s += __shfl_xor(s, 2, 64);
+        s += __shfl_xor(s, 1, 64);
+        if (part == c) res[i] = s;
+      }
+    }
+    if (((live >> slot) & 1u) && col4 < a.dim) {  // dim % 4 == 0: four columns are inside together
+      const bf16_t* b = (p ? a.b1 : a.b0) + col4;
+      const uint2 bv = *reinterpret_cast<const uint2*>(b);
+      const float o0 = bf2f((bf16_t)(bv.x & 0xffffu)) + res[0], o1 = bf2f((bf16_t)(bv.x >> 16)) + res[1];
+      const float o2 = bf2f((bf16_t)(bv.y & 0xffffu)) + res[2], o3 = bf2f((bf16_t)(bv.y >> 16)) + res[3];
+      uint2 o;
+      o.x = (uint32_t)f2bf(o0) | ((uint32_t)f2bf(o1) << 16);
+      o.y = (uint32_t)f2bf(o2) | ((uint32_t)f2bf(o3) << 16);
+      const int64_t row = (int64_t)desc[slot].x - a.dst0;
+      *reinterpret_cast<uint2*>(a.emb + row * a.ld + col4) = o;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // temperature + top-p sampling of one token per sequence.
 //   z = bf16(logit / T);  p = bf16(softmax(z))                          moondream.py:526 (bf16 tensors, fp32 inside)
 //   in descending-p order keep the tokens whose preceding mass is <= top_p (evaluated with the
@@ -1216,6 +1335,27 @@ extern "C" md_status md_region_pick_encode_scored(const void* logits, int64_t ld
   hipLaunchKernelGGL(region_pick_scored_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits, ld,
                      n_groups, n_bins, (const bf16_t*)value_table, (const bf16_t*)feat_w, half, bins, ld_bins, (bf16_t*)feats,
                      ld_feats, window, logprobs, ld_logprobs);
+  return md_launch_status();
+}
+
+extern "C" md_status md_spatial_ref_embed(const int32_t* desc, int32_t n, const void* coord_fw, int32_t coord_feat,
+                                          const void* coord_w, int64_t coord_ldw, const void* coord_b, const void* size_fw,
+                                          int32_t size_feat, const void* size_w, int64_t size_ldw, const void* size_b,
+                                          int32_t dim, void* emb, int64_t ld, int64_t dst0, int32_t rows, void* stream) {
+  MD_CHECK_ARG(desc && coord_fw && coord_w && coord_b && size_fw && size_w && size_b && emb);
+  MD_CHECK_ARG(n > 0 && rows > 0 && dim > 0 && dim % 4 == 0 && ld >= dim && ld % 4 == 0);
+  MD_CHECK_ARG(coord_feat > 0 && coord_feat % 8 == 0 && size_feat > 0 && size_feat % 8 == 0);
+  MD_CHECK_ARG(coord_ldw >= coord_feat && coord_ldw % 4 == 0 && size_ldw >= size_feat && size_ldw % 4 == 0);
+  const int feat_max = coord_feat > size_feat ? coord_feat : size_feat;
+  MD_CHECK_ARG(feat_max <= 2048);  // the group's features live in LDS: 16 rows of feat_max bf16, <= 64 KiB
+  MD_CHECK_ARG((uintptr_t)desc % 16 == 0);  // 16-byte descriptors, 8-byte pieces of the weights and of the rows
+  MD_CHECK_ARG(((uintptr_t)coord_w | (uintptr_t)coord_b | (uintptr_t)size_w | (uintptr_t)size_b | (uintptr_t)emb) % 8 == 0);
+  SpatialRefArgs a{desc, n, (const bf16_t*)coord_fw, (const bf16_t*)coord_w, (const bf16_t*)coord_b, (const bf16_t*)size_fw,
+                   (const bf16_t*)size_w, (const bf16_t*)size_b, coord_feat, size_feat, feat_max, coord_ldw, size_ldw, dim,
+                   (bf16_t*)emb, ld, dst0, rows};
+  const size_t lds = (size_t)SREF_TOKENS * feat_max * sizeof(bf16_t);
+  hipLaunchKernelGGL(spatial_ref_embed_kernel, dim3((n + SREF_TOKENS - 1) / SREF_TOKENS, (dim + SREF_COLS - 1) / SREF_COLS),
+                     dim3(SREF_THREADS), lds, (hipStream_t)stream, a);
   return md_launch_status();
 }
 

@@ -22,6 +22,7 @@ from .config import MoondreamConfig
 from .beam import refuse_beams
 from .constraint import refuse_constraints
 from .decode_loop import refuse_filters, refuse_penalties
+from .spatial import refs_of, refuse_spatial_refs
 from .moondream import MoondreamModel
 
 
@@ -73,11 +74,12 @@ class HfMoondream:
         """reference: hf_moondream.py:83-97 -- ``query(image, question)["answer"].strip()`` with the
         model's default sampling settings; ``tokenizer`` / ``chat_history`` / ``max_new_tokens`` are
         ignored there too.  Extension: ``settings=`` is forwarded to ``query`` (e.g. temperature 0); the penalty settings
-        are not part of this wrapper's calls (ValueError for a non-neutral one), nor are ``constraints``."""
+        are not part of this wrapper's calls (ValueError for a non-neutral one), nor are ``constraints`` or ``spatial_refs``."""
         refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_filters(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_beams(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
+        refuse_spatial_refs(refs_of(kwargs.get("settings"), kwargs.get("spatial_refs")), "HfMoondream's own calls (use MoondreamModel's)")
         answer = self.query(image_embeds, question, settings=kwargs.get("settings"))["answer"].strip()
         if result_queue is not None:
             result_queue.put(answer)
@@ -92,6 +94,7 @@ class HfMoondream:
         refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_filters(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_beams(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
+        refuse_spatial_refs(refs_of(kwargs.get("settings"), kwargs.get("spatial_refs")), "HfMoondream's own calls (use MoondreamModel's)")
         self._setup_caches()
         settings = dict(kwargs.get("settings") or {})
         settings.setdefault("max_tokens", kwargs.get("max_new_tokens", kwargs.get("max_tokens", 256)))
@@ -111,6 +114,7 @@ class HfMoondream:
         refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_filters(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
         refuse_beams(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
+        refuse_spatial_refs(refs_of(kwargs.get("settings"), kwargs.get("spatial_refs")), "HfMoondream's own calls (use MoondreamModel's)")
         q = extract_question(prompt)
         if q is not None:
             return [self.model_query(image_embeds, q)]

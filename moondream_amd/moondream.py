@@ -41,6 +41,7 @@ from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
 from .lora import variant_state_dict
 from .scores import Scores
 from .shared_prefix import RowPlan, check_shared_table, plan_rows
+from .spatial import SpatialRecord, check_spatial_refs, refs_of, refuse_spatial_refs, spatial_prompt_ids
 from .weights import PackedLora, PackedLoraBank, PackedModel
 
 BF16 = torch.bfloat16
@@ -1556,22 +1557,58 @@ class MoondreamModel:
                 pos[k] = im.pos
         return pos
 
-    def _sequence_embeddings(self, prompts: Sequence[Sequence[int]], images=None, mark=None):
+    def _sequence_embeddings(self, prompts: Sequence[Sequence[int]], images=None, mark=None,
+                             spatial: Optional[SpatialRecord] = None):
         """``embed(r0, r1)`` [r1-r0, T, D] for ``_prefill_groups`` over rows whose prompts are ``prompts``: the prompts'
         embeddings, for rows whose image prefix is in place -- or, with ``images`` (every row's own, all raw; ONE ViT
         batch, now), the fused prefill's rows.  There image prefix and prompt go through the decoder in ONE pass per group
         of equal-length prompts ([bos | 729 image embeddings | prompt] at position 0).  The attention kernels evaluate
         the reference's mask rule per element (bidirectional inside the first 730 positions, causal after), so this is
         the same computation as the reference's two passes (moondream.py:228-262 then 280-321) up to accumulation order
-        -- one pass over the weights saved (fused_prefill = False keeps the two passes)."""
+        -- one pass over the weights saved (fused_prefill = False keeps the two passes).
+        ``spatial``: the rows' spatial references (moondream_amd/spatial.py), rows as in ``prompts``; its table goes to the
+        device once, here, and every ``embed(r0, r1)`` stores the encoded references of rows [r0, r1) over their
+        placeholder rows with one md_spatial_ref_embed launch -- no host synchronisation, no indexing by id.  None, or
+        a record without tokens: the embeddings, and the launches, of the call without it."""
         embed_prompts = lambda r0, r1: self._embed(torch.tensor(prompts[r0:r1], dtype=torch.int32))
+        if spatial is not None and not len(spatial):
+            spatial = None
         if images is None:
-            return embed_prompts
+            if spatial is None:
+                return embed_prompts
+            table = self._h2d(torch.from_numpy(spatial.table(0)))
+            return lambda r0, r1: self._spatial_embed(embed_prompts(r0, r1), spatial, table, r0, r1, 0)
         img_emb = self._run_vision_encoder_batch(images, mark)
         if mark is not None:
             mark("vision")
         bos = self._embed(torch.full((len(images), 1), self.config.tokenizer.bos_id, dtype=torch.int32))
-        return lambda r0, r1: torch.cat([bos[r0:r1], img_emb[r0:r1], embed_prompts(r0, r1)], dim=1)
+        fused = lambda r0, r1: torch.cat([bos[r0:r1], img_emb[r0:r1], embed_prompts(r0, r1)], dim=1)
+        if spatial is None:
+            return fused
+        lead = 1 + img_emb.shape[1]
+        table = self._h2d(torch.from_numpy(spatial.table(lead)))
+        return lambda r0, r1: self._spatial_embed(fused(r0, r1), spatial, table, r0, r1, lead)
+
+    def _spatial_embed(self, x: torch.Tensor, spatial: SpatialRecord, table: torch.Tensor, r0: int, r1: int, lead: int) -> torch.Tensor:
+        """The spatial references of rows [r0, r1) encoded into ``x`` [r1-r0, T, D], those rows' embeddings ([bos | image
+        | prompt] with ``lead`` positions in front of the prompt): ONE md_spatial_ref_embed launch over the rows'
+        descriptors of ``table`` (``SpatialRecord.table(lead)`` on the device), none when they have no reference."""
+        i0, i1 = spatial.span(r0, r1)
+        if i1 == i0:
+            return x
+        assert x.is_contiguous() and x.dtype == BF16 and x.shape[0] == r1 - r0 and x.shape[1] == lead + spatial.prompt_len[r0]
+        r, _ = self._region()
+        ce, se = r["coord_encoder"], r["size_encoder"]
+        d = x.shape[2]
+        assert (ce.n, se.n, ce.k, se.k) == (d, d, 2 * r["coord_features"].shape[1], 2 * r["size_features"].shape[1])
+        _lib.check(
+            self.lib.md_spatial_ref_embed(table.data_ptr() + 16 * i0, i1 - i0, r["coord_features"].data_ptr(), ce.k, ce.w.data_ptr(),
+                                          ce.k_pad, ce.b.data_ptr(), r["size_features"].data_ptr(), se.k, se.w.data_ptr(), se.k_pad,
+                                          se.b.data_ptr(), d, x.data_ptr(), d, spatial.dst0_of(r0, lead), x.shape[0] * x.shape[1],
+                                          self._stream()),
+            "md_spatial_ref_embed",
+        )
+        return x
 
     def _shared_routing(self, plan: RowPlan, pos: int) -> _Rows:
         """The routing of a shared plan's rows over its prefix table (every prefix ``pos`` positions long), checked."""
@@ -1587,7 +1624,8 @@ class MoondreamModel:
                            encode_settings: Optional[dict] = None, logits_capture: Optional[torch.Tensor] = None,
                            sampling: Optional[Sampling] = None, scores: Optional[Scores] = None, hidden_sink=None,
                            constraints: Optional[Sequence[Optional[TokenAutomaton]]] = None,
-                           filters: Optional[Sequence[Tuple[int, float]]] = None) -> Prepared:
+                           filters: Optional[Sequence[Tuple[int, float]]] = None,
+                           spatial: Optional[SpatialRecord] = None) -> Prepared:
         """Everything before the first generated token, for B (image, prompt-ids) pairs, as ``plan_rows`` lays them out
         (moondream_amd/shared_prefix.py): every image's KV prefix is placed (``_place_images``), then one prompt prefill per
         distinct length picks the first tokens.  Returns a ``Prepared``, rows in slot order.  The COPY route gives row r slot
@@ -1603,8 +1641,10 @@ class MoondreamModel:
         ``constraints``: ``check_constraints``' entries in the CALLER's order; their record (``_constraint_record``, rows in
         slot order) masks every first pick and goes to the decode loop in ``Prepared.constraint``.  ``filters``:
         ``check_filters``' pairs in the CALLER's order; a sampled call then picks with their per-row record
-        (``_filter_record``, rows in slot order), the first tokens too, and ``Prepared.sampling`` is that record.  Must run under
-        torch.inference_mode()."""
+        (``_filter_record``, rows in slot order), the first tokens too, and ``Prepared.sampling`` is that record.
+        ``spatial``: the rows' spatial references in the CALLER's order (their placeholders are in ``prompts``, so rows
+        group by their total length); reordered to slot order here and encoded into the prompt embeddings
+        (``_sequence_embeddings``).  Must run under torch.inference_mode()."""
         mark = mark or (lambda name: None)
         rows = _Rows.of(rows)
         share = share_prefix and variants is None and self._shares_prefix(rows.lora)
@@ -1621,7 +1661,8 @@ class MoondreamModel:
             rows = _Rows(variants=self._variant_table([variants[i] for i in plan.order]), bank=self._bank)
         mark("start")
         fused = fuse and self.fused_prefill and not share and all(isinstance(im, Image.Image) for im in plan.placed)
-        embed = self._sequence_embeddings(prompts, plan.placed if fused else None, mark)
+        embed = self._sequence_embeddings(prompts, plan.placed if fused else None, mark,
+                                          spatial=spatial.reorder(plan.order) if spatial is not None else None)
         pos = 0  # (fused: the one pass starts at the bos)
         if not fused:
             prefix = set(self._place_images(plan.placed, _Rows() if share else rows, mark))
@@ -1688,6 +1729,7 @@ class MoondreamModel:
         constraints: Union[None, TokenAutomaton, Sequence[Optional[TokenAutomaton]]] = None,
         top_k: Union[int, Sequence[int]] = 0,
         min_p: Union[float, Sequence[float]] = 0.0,
+        spatial: Optional[SpatialRecord] = None,
     ):
         """Token ids for B (image, prompt-ids) pairs, decoded in lockstep; greedy by default.
 
@@ -1791,7 +1833,14 @@ class MoondreamModel:
         with them draws from the uniforms taken up front (as every other mode does), not per step.  ValueError, before
         any GPU work: a ``top_k`` that is not an integer >= 0, a ``min_p`` that is not finite or outside [0, 1], a list
         that is not one per row.
+
+        ``spatial``: the rows' spatial references as a ``SpatialRecord`` (moondream_amd/spatial.py) in the caller's order,
+        for prompts that hold their placeholders -- what ``batch_query(spatial_refs=)`` builds.  Each reference token is
+        encoded on the device into its placeholder's row of the prompt embeddings (md_spatial_ref_embed: one launch per
+        prompt pass, nothing else changes); None, or a record without tokens: the call without the argument.
         """
+        if spatial is not None and spatial.n_rows != len(images):
+            raise ValueError(f"spatial: a record of {spatial.n_rows} rows for {len(images)} rows")
         filters = check_filters(top_k, min_p, len(images))
         top_k = check_top_logprobs(top_logprobs, return_logprobs)
         b = len(images)
@@ -1819,7 +1868,7 @@ class MoondreamModel:
             scores = Scores.new((rows_t, b), top_k, self._device, fill=True) if return_logprobs else None
             prep = self._prepare_sequences(images, prompts, mark, _Rows(lora=lora), fuse=True, share_prefix=share_prefix,
                                            variants=multi_rows, encode_settings={"variant": variant}, sampling=sampling,
-                                           scores=scores and scores[0], constraints=constraints, filters=filters)
+                                           scores=scores and scores[0], constraints=constraints, filters=filters, spatial=spatial)
             stop = None if ignore_eos else eos
             penalty = self._penalty_record(penalties and [penalties[i] for i in prep.order])  # rows in slot order
             hist = self._decode_greedy(prep.first, prep.pos, max_tokens, tk.answer_id, prep.rows, stop, sampling=prep.sampling,
@@ -2014,6 +2063,8 @@ class MoondreamModel:
         sampling arguments (``kw``: its further ones), or, with ``settings["num_beams"]`` > 1, the best beam hypothesis."""
         beams = beams_of(settings)
         if beams is not None:
+            if kw.get("spatial") is not None:  # (beam rows are prepared by a route that takes no record)
+                raise ValueError("num_beams > 1 (beam search) is not served with spatial_refs")
             return self._beam_best_ids(images, prompts, settings, beams)
         return self.batch_generate_ids(images, prompts, **kw, **self._sampling_kwargs(settings))
 
@@ -2103,7 +2154,7 @@ class MoondreamModel:
     def score_ids(self, images: Sequence[Union[Image.Image, EncodedImage]], prompts: Sequence[Sequence[int]],
                   continuations: Sequence[Sequence[int]], share_prefix: bool = False, variant: Optional[str] = None,
                   top_logprobs: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                  constraints=None):
+                  constraints=None, spatial_refs=None):
         """Score GIVEN continuations: returns ``(logprobs, ranks)``, one list per row with one entry per token of
         ``continuations[i]`` -- the values ``batch_generate_ids(..., return_logprobs=True)`` attaches to a token it generates,
         for the tokens the caller supplies.  ``logprobs[i][j]`` is log softmax of the model's logits after
@@ -2124,7 +2175,9 @@ class MoondreamModel:
         ``batch_generate_ids(..., top_logprobs=k)`` gives them: ONE md_topk_logprobs launch over the same logits and
         suppression table, and the same copy to the host.  ValueError for a k outside 1 .. 32.  The penalty arguments of
         ``batch_generate_ids`` are not served here (ValueError for a non-neutral one): the scorer makes no decode step, so
-        there is no history to penalise from -- scores are the model's own.  ``constraints`` likewise (ValueError)."""
+        there is no history to penalise from -- scores are the model's own.  ``constraints`` likewise (ValueError), and
+        ``spatial_refs`` (ValueError: the scorer's prompts carry no encoded references)."""
+        refuse_spatial_refs(spatial_refs, "score_ids / query_choices (the scorer's prompts carry no encoded references)")
         top_k = check_top_logprobs(top_logprobs, True)
         refuse_constraints({"constraints": constraints}, "score_ids (no token is picked: scores are the model's own)")
         refuse_penalties(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
@@ -2177,7 +2230,7 @@ class MoondreamModel:
 
     def batch_generate_ids_pipelined(self, batches, max_tokens: int = DEFAULT_MAX_TOKENS, ignore_eos: bool = False,
                                      repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, constraints=None,
-                                     top_k=0, min_p=0.0):
+                                     top_k=0, min_p=0.0, spatial_refs=None):
         """Generator over an iterable of (images, prompt-id lists) batches; yields each batch's greedy ids in order, one
         decode group late (a group = two consecutive batches of <= 64 sequences decoded as ONE lockstep of <= 128 -- round 6,
         ``pair_decode`` -- or one batch).  Two HIP streams: the MFMA-bound encode (vision + prefill) of batch k+1 on one, the HBM-bound lockstep
@@ -2195,7 +2248,8 @@ class MoondreamModel:
 
         Per batch the result is identical to ``batch_generate_ids`` (same kernels, same order).  The penalty arguments of
         that call are not served here: ValueError for a non-neutral one; nor are ``constraints`` (ValueError), nor ``top_k`` /
-        ``min_p`` (ValueError for a non-neutral one: the engine decodes greedily)."""
+        ``min_p`` (ValueError for a non-neutral one: the engine decodes greedily), nor ``spatial_refs`` (ValueError)."""
+        refuse_spatial_refs(spatial_refs, "the pipelined engine (its prefill arena embeds token ids alone)")
         refuse_filters(dict(top_k=top_k, min_p=min_p), "the pipelined engine (it decodes greedily: there is no sampled row to cut)")
         refuse_constraints({"constraints": constraints}, "the pipelined engine (its paired decode keeps no automaton states)")
         refuse_penalties(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
@@ -2366,7 +2420,30 @@ class MoondreamModel:
             for q in questions
         ]
 
-    def batch_query(self, images, questions: Sequence[str], settings: Optional[dict] = None, reasoning: bool = False):
+    def _query_prompts_spatial(self, images, questions: Sequence[str], spatial_refs, tail: Optional[Sequence[int]] = None):
+        """``(prompts, record)`` of a batched query with ``spatial_refs`` (one entry per row, checked here before any GPU
+        work: ``check_spatial_refs``): row i's prompt is ``query``'s, [prefix | placeholders | question | tail]
+        (moondream.py:577-604), and ``record`` the ``SpatialRecord`` of every reference token in the caller's order --
+        None when no row has a reference: the prompts are then those of the call without the argument.  ``tail`` None:
+        the plain query's, [suffix | suffix]."""
+        tk = self.config.tokenizer
+        tpl = tk.templates["query"]
+        if tpl is None:
+            raise NotImplementedError("Model does not support querying.")
+        tail = list(tpl["suffix"]) * 2 if tail is None else tail
+        if len(images) != len(questions):
+            raise ValueError("one question per image")
+        q_ids = [list(self.tokenizer.encode(q).ids) for q in questions]
+        rows = check_spatial_refs(spatial_refs, len(q_ids), [im is not None for im in images], q_ids, tk.coord_id, tk.size_id,
+                                  getattr(self.w, "region", None) is not None)
+        refs = rows or [[]] * len(q_ids)
+        prompts = [spatial_prompt_ids(tpl["prefix"], r, q + list(tail), tk.coord_id, tk.size_id) for r, q in zip(refs, q_ids)]
+        if rows is None:
+            return prompts, None
+        return prompts, SpatialRecord.build(rows, len(tpl["prefix"]), [len(p) for p in prompts])
+
+    def batch_query(self, images, questions: Sequence[str], settings: Optional[dict] = None, reasoning: bool = False,
+                    spatial_refs=None):
         """Answers for B (image, question) pairs in lockstep: a list of strings.
         ``reasoning=True``: a list of ``{"reasoning": {"text", "grounding"}, "answer": str}`` -- element i is what
         ``query(images[i], questions[i], reasoning=True, settings=settings)`` returns (reference: moondream.py:541-618), with
@@ -2377,12 +2454,38 @@ class MoondreamModel:
         ``set_strict_batch_invariance``).  A sampled row draws one uniform per step, taken up front from the call's generator
         on the device (the step that feeds the suffix token consumes a draw like any other), where ``query`` draws per token:
         the same distribution per decision, other ids.  Not served, NotImplementedError: LoRA ``variant`` / ``variants``, the fp8
-        modes, a query template whose suffix is not one token, a checkpoint without a region head."""
+        modes, a query template whose suffix is not one token, a checkpoint without a region head.
+
+        ``spatial_refs``: one entry per row -- None, an empty list, or a list of points ``(x, y)`` / boxes ``(x0, y0, x1,
+        y1)`` -- placed in front of the row's question as ``query(image, question, spatial_refs=refs)`` places them
+        (moondream.py:577-604): row i returns what that call returns, up to the rounding of the encoder's accumulation
+        order.  Every reference token of the call is encoded and stored into its placeholder's row of the prompt
+        embeddings on the device (md_spatial_ref_embed: one launch per prompt pass, no host synchronisation); rows group
+        by their total prompt length, placeholders included, and only the prompt embeddings change: shared prefixes,
+        ``variant`` / ``variants``, the fp8 modes, penalties, constraints, top-k / min-p and ``reasoning=True`` are served as
+        they are.  A row without refs is the row of the call without the argument; with no row having any, so is the
+        call, launch for launch.  (``settings["spatial_refs"]`` is read when the argument is absent.)  ValueError, before
+        any GPU work: not one entry per row, an entry that is no list of 2- / 4-tuples of finite numbers, a row whose
+        question's own tokens contain ``coord_id`` / ``size_id``, ``num_beams`` > 1; NotImplementedError: a checkpoint
+        without a region head.  Ranges are not checked (the reference checks none)."""
+        spatial_refs = refs_of(settings, spatial_refs)
         if reasoning:
             refuse_beams(settings, "reasoning queries")
-            return self._reasoning_answers(self._batch_query_reasoning(images, questions, settings, share_prefix=False))
-        ids = self._string_ids(images, self._query_prompts(questions), settings)
+            return self._reasoning_answers(self._batch_query_reasoning(images, questions, settings, share_prefix=False,
+                                                                       spatial_refs=spatial_refs))
+        if spatial_refs is None:
+            ids = self._string_ids(images, self._query_prompts(questions), settings)
+        else:
+            ids = self._string_ids_spatial(images, settings, self._query_prompts_spatial(images, questions, spatial_refs))
         return [self.tokenizer.decode(s) for s in ids]
+
+    def _string_ids_spatial(self, images, settings: Optional[dict], built, **kw) -> List[List[int]]:
+        """``_string_ids`` of a query with ``spatial_refs``: ``built`` = ``_query_prompts_spatial``'s (prompts, record);
+        beam search is not served with references (ValueError, before any GPU work)."""
+        prompts, spatial = built
+        if spatial is not None and beams_of(settings) is not None:
+            raise ValueError("num_beams > 1 (beam search) is not served with spatial_refs")
+        return self._string_ids(images, prompts, settings, **kw, **({"spatial": spatial} if spatial is not None else {}))
 
     def batch_generate(self, images, prompts: Optional[Sequence[str]] = None, settings: Optional[dict] = None) -> List[str]:
         """BASELINE.json's ``batch_generate``: captions when ``prompts`` is None, else answers, with the reference's sampling
@@ -3022,30 +3125,46 @@ class MoondreamModel:
             raise NotImplementedError("batched reasoning queries need a region head (grounding): checkpoint has no region head")
 
     def _batch_query_reasoning(self, images, questions: Sequence[str], settings: Optional[dict], share_prefix: bool,
-                               forced: Optional[torch.Tensor] = None) -> List[dict]:
+                               forced: Optional[torch.Tensor] = None, spatial_refs=None, built=None) -> List[dict]:
         """``batch_query(reasoning=True)`` / ``query_many_reasoning``: ``_reason_loop``'s rows in the caller's order.
-        ``forced`` [steps, B] in the caller's row order (tests)."""
+        ``forced`` [steps, B] in the caller's row order (tests).  ``spatial_refs``: one entry per row, in front of the
+        row's question as ``query(reasoning=True, spatial_refs=)`` places them; ``built``: their (prompts, record) when the
+        caller has made them already (``_reasoning_prompts_spatial``)."""
         self._check_reasoning_served(settings)
         if len(images) != len(questions) or not len(images):
             raise ValueError("batch_query: one question per image, at least one")
         tk = self.config.tokenizer
         tpl = tk.templates["query"]
+        spatial = built
+        if spatial is None and spatial_refs is not None:
+            spatial = self._reasoning_prompts_spatial(images, questions, spatial_refs)
         st = settings or {}
         max_tokens = st.get("max_tokens", DEFAULT_MAX_TOKENS)
         temperature, top_p = st.get("temperature", DEFAULT_TEMPERATURE), st.get("top_p", DEFAULT_TOP_P)
         # moondream.py:586-603: [prefix | question | suffix | thinking]
         prompts = [list(tpl["prefix"]) + list(self.tokenizer.encode(q).ids) + list(tpl["suffix"]) + [tk.thinking_id] for q in questions]
+        if spatial is not None:
+            prompts, spatial = spatial
         marks: list = []
         mark = lambda name: self._mark(marks, name)
         with torch.inference_mode():
             sampling = None if temperature == 0 else Sampling(float(temperature), float(top_p), st.get("generator"))
-            prep = self._prepare_sequences(images, prompts, mark, fuse=True, share_prefix=share_prefix, sampling=sampling)
+            prep = self._prepare_sequences(images, prompts, mark, fuse=True, share_prefix=share_prefix, sampling=sampling,
+                                           spatial=spatial)
             if forced is not None:
                 forced = forced.to(self._device)[:, torch.tensor(prep.order, device=self._device)]
             res = self._reason_loop(prep.hidden_last, prep.first, prep.next_pos, prep.rows, max_tokens, prep.sampling, forced)
             mark("reason_loop")
         self._phase_times(marks)
         return prep.in_caller_order(res)
+
+    def _reasoning_prompts_spatial(self, images, questions: Sequence[str], spatial_refs):
+        """``_query_prompts_spatial`` with the reasoning query's tail, [suffix | thinking] (moondream.py:593-603)."""
+        tk = self.config.tokenizer
+        tpl = tk.templates["query"]
+        if tpl is None:
+            raise NotImplementedError("Model does not support querying.")
+        return self._query_prompts_spatial(images, questions, spatial_refs, list(tpl["suffix"]) + [tk.thinking_id])
 
     def _reasoning_answers(self, rows: List[dict]) -> List[dict]:
         """``_reason_loop``'s rows in the shape ``query(reasoning=True)`` returns."""
@@ -3124,33 +3243,53 @@ class MoondreamModel:
         """Many questions about ONE image (reference pattern: encode_image once, then query per question,
         moondream.py:230-268,620-623), answered in one batch that reads a single copy of the image's KV prefix.  Element i ==
         ``{"answer": batch_query([encode_image(image)] * N, questions)[i]}``, in the bf16 mode and in the fp8 KV mode.  A LoRA
-        ``variant`` (settings) takes the copy path, with the same results.  With reasoning: ``query_many_reasoning``."""
-        prompts = self._query_prompts(questions)
+        ``variant`` (settings) takes the copy path, with the same results.  With reasoning: ``query_many_reasoning``.
+        ``settings["spatial_refs"]``: one entry per question, ``batch_query``'s ``spatial_refs`` (the three-parameter
+        signature is part of this call's contract) -- one image, N boxes and a question about each in one batch over one
+        copy of the image's prefix."""
+        spatial_refs = refs_of(settings)
+        built = None
+        if spatial_refs is not None:  # (built and checked, like everything below, before the image is encoded)
+            built = self._query_prompts_spatial([image] * len(questions), questions, spatial_refs)
+            if built[1] is not None and beams_of(settings) is not None:
+                raise ValueError("num_beams > 1 (beam search) is not served with spatial_refs")
+        prompts = built[0] if built is not None else self._query_prompts(questions)
         check_penalties(*penalties_of(settings).values(), len(prompts))  # host values: before any GPU work
         check_filters(*filters_of(settings).values(), len(prompts))
         self._check_constraints_of(settings, len(prompts))
         beams_of(settings)  # (checked before the image is encoded)
         enc = self.encode_image(image, settings)
-        ids = self._string_ids([enc] * len(prompts), prompts, settings, share_prefix=True)
+        if built is not None:
+            ids = self._string_ids_spatial([enc] * len(prompts), settings, built, share_prefix=True)
+        else:
+            ids = self._string_ids([enc] * len(prompts), prompts, settings, share_prefix=True)
         return [{"answer": self.tokenizer.decode(s)} for s in ids]
 
-    def query_many_reasoning(self, image, questions: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
+    def query_many_reasoning(self, image, questions: Sequence[str], settings: Optional[dict] = None, spatial_refs=None) -> List[dict]:
         """``query_many`` with reasoning: ``query(image, q, reasoning=True)`` for many questions about ONE image, in one
         lockstep batch over a single copy of the image's KV prefix.  Element i ==
         ``batch_query([encode_image(image)] * N, questions, settings, reasoning=True)[i]``; settings and refusals as there.
-        (A method of its own: ``query_many``'s three-parameter signature is part of its contract.)"""
+        (A method of its own: ``query_many``'s three-parameter signature is part of its contract.)  ``spatial_refs``: one
+        entry per question, as ``batch_query`` takes them."""
         self._check_reasoning_served(settings)
+        spatial_refs = refs_of(settings, spatial_refs)
+        built = None
+        if spatial_refs is not None:  # built and checked before the image is encoded
+            built = self._reasoning_prompts_spatial([image] * len(questions), questions, spatial_refs)
         enc = self.encode_image(image, settings)
-        return self._reasoning_answers(self._batch_query_reasoning([enc] * len(questions), questions, settings, share_prefix=True))
+        return self._reasoning_answers(self._batch_query_reasoning([enc] * len(questions), questions, settings, share_prefix=True,
+                                                                   built=built))
 
-    def query_choices(self, image, question: str, choices: Sequence[str], settings: Optional[dict] = None) -> dict:
+    def query_choices(self, image, question: str, choices: Sequence[str], settings: Optional[dict] = None, spatial_refs=None) -> dict:
         """Multiple choice: which of ``choices`` the model prefers as the answer to ``question`` about ONE image.  The image is
         encoded once; one row per choice over a single copy of its KV prefix (``score_ids`` with ``share_prefix``; a LoRA
         ``variant`` in ``settings`` takes the copy path, as in ``query_many``).  Every row's prompt is ``query``'s, its
         continuation the choice's tokens followed by ``eos_id`` -- a choice is scored as a COMPLETE answer.  No token is
         generated.  Returns ``{"logprobs": [sum per choice], "mean_logprobs": [sum / n_tokens], "per_token": [[..], ..],
         "best": argmax of logprobs, "best_normalized": argmax of mean_logprobs}`` (ties: the first choice).  The
-        log-probabilities are ``score_ids``': the model's own distribution at temperature 1, untruncated."""
+        log-probabilities are ``score_ids``': the model's own distribution at temperature 1, untruncated.  ``spatial_refs``
+        are not served here (ValueError)."""
+        refuse_spatial_refs(refs_of(settings, spatial_refs), "score_ids / query_choices (the scorer's prompts carry no encoded references)")
         choices = list(choices)
         if not choices:
             raise ValueError("query_choices: no choices")
