@@ -556,6 +556,44 @@ md_status md_constrain_rows(void* logits, int64_t ld, int32_t batch, int32_t voc
                             const int32_t* default_next, const int32_t* edge_tok, const int32_t* edge_next,
                             int32_t state_cap, void* stream);
 
+/* Compiling a byte-level DFA to the table above, on the device (csrc/automaton.hip).  The DFA: trans int32 [n_states][256],
+ * an entry a next state or -1 (dead; any entry outside [0, n_states) reads as dead), accept uint8 [n_states], start state 0.
+ * The vocabulary: token v spells tok_bytes[tok_off[v] .. tok_off[v + 1]) (tok_off int32 [vocab + 1], non-decreasing: the
+ * caller's contract; tok_bytes uint8 [n_bytes]); forbidden uint8 [vocab]: nonzero, the token is never allowed.  All device
+ * arrays.  The LIFT of state q and token v, next(q, v):
+ *   v == eos_id: MD_CONSTRAINT_FREE where accept[q], otherwise MD_CONSTRAINT_FORBID (whatever eos spells or forbidden says);
+ *   forbidden[v], a zero-length token, or a byte range outside [0, n_bytes): MD_CONSTRAINT_FORBID;
+ *   otherwise the state reached by walking v's bytes through trans from q, MD_CONSTRAINT_FORBID once a step is dead.
+ * md_automaton_lift: next int32 [nq][vocab] = next(q0 + i, v) for one slab of states, 1 <= nq <= MD_AUTOMATON_SLAB,
+ *   q0 + nq <= n_states.
+ * md_automaton_count: for every state q, default_next[q] = the most frequent of next(q, 0 .. vocab - 1), ties to the smallest
+ *   value as a signed integer (FORBID < FREE < state 0 < ..); row_ptr int32 [n_states + 1] = the exclusive scan of the
+ *   numbers of tokens whose next value differs from the default, row_ptr[n_states] the total.
+ * md_automaton_fill: with default_next / row_ptr as md_automaton_count left them and edge_tok / edge_next int32 [edge_cap],
+ *   edge_cap >= row_ptr[n_states] (the caller reads that one number in between): state q's edges at row_ptr[q] ..
+ *   row_ptr[q + 1] are exactly the tokens whose next value differs from default_next[q], strictly ascending, with that
+ *   value.  Nothing is written at or beyond edge_cap.  edge_cap == 0: MD_OK, nothing launched (the arrays may be NULL).
+ * The four arrays are then a table md_constrain_rows reads with state_cap = n_states.  Exact: integers only, the same
+ * result on every run.  count and fill lift the states in slabs of MD_AUTOMATON_SLAB into ws (fill lifts again rather than
+ * keep n_states * vocab values), ws_bytes >= md_automaton_workspace_bytes(n_states, vocab) = min(n_states,
+ * MD_AUTOMATON_SLAB) * vocab * 4 (0 for sizes out of range).  No host sync, no allocation.
+ * MD_ERR_INVALID_ARG, before any launch: a NULL pointer, n_states outside [1, MD_AUTOMATON_STATES_MAX], vocab < 1,
+ * vocab > MD_CONSTRAIN_VOCAB_MAX, eos_id outside [0, vocab), n_bytes < 0, a slab outside the states, edge_cap < 0, ws_bytes
+ * too small. */
+#define MD_AUTOMATON_STATES_MAX 4096
+#define MD_AUTOMATON_SLAB 256
+size_t md_automaton_workspace_bytes(int32_t n_states, int32_t vocab);
+md_status md_automaton_lift(const int32_t* trans, const uint8_t* accept, int32_t n_states, const int32_t* tok_off,
+                            const uint8_t* tok_bytes, int64_t n_bytes, int32_t vocab, int32_t eos_id, const uint8_t* forbidden,
+                            int32_t q0, int32_t nq, int32_t* next, void* stream);
+md_status md_automaton_count(const int32_t* trans, const uint8_t* accept, int32_t n_states, const int32_t* tok_off,
+                             const uint8_t* tok_bytes, int64_t n_bytes, int32_t vocab, int32_t eos_id, const uint8_t* forbidden,
+                             int32_t* default_next, int32_t* row_ptr, void* ws, size_t ws_bytes, void* stream);
+md_status md_automaton_fill(const int32_t* trans, const uint8_t* accept, int32_t n_states, const int32_t* tok_off,
+                            const uint8_t* tok_bytes, int64_t n_bytes, int32_t vocab, int32_t eos_id, const uint8_t* forbidden,
+                            const int32_t* default_next, const int32_t* row_ptr, int32_t* edge_tok, int32_t* edge_next,
+                            int64_t edge_cap, void* ws, size_t ws_bytes, void* stream);
+
 /* Region head, device resident (reference: region.py:12-71 inside the loop of moondream.py:653-733).
  * md_fourier_features: out[r] = [cos(f) | sin(f)], f = bf16(bf16(2 pi x[r, :in_dim]) . w[in_dim][half])
  *   (region.py:12-29; in_dim 1 for coordinates, 2 for sizes) -- the input of coord_encoder /

@@ -19,15 +19,52 @@ FORBID = -3  # a next value: the token may not be produced in this state
 class TokenAutomaton:
     """States 0 .. S-1, start state 0.  ``edges[q]`` is the sorted list of distinct ``(token, next)`` pairs of state q and
     ``default[q]`` the next value of every token it does not list.  A next value is a state id, ``FREE`` or ``FORBID``.
-    Immutable once made; one object may serve many requests (the engines pack each distinct object once)."""
+    Immutable once made; one object may serve many requests (the engines pack each distinct object once).
 
-    __slots__ = ("edges", "default")
+    Two forms with one meaning: built from tuples (the constructor and the named constructors), or backed by the four
+    arrays of the table form (``from_arrays``: what the grammar compiler makes, hundreds of thousands of edges), whose
+    ``edges`` are materialised on first use only and whose ``validate`` / ``pack`` / ``next`` work on the arrays."""
+
+    __slots__ = ("_edges", "default", "_arr")
 
     def __init__(self, edges: Sequence[Sequence[Tuple[int, int]]], default: Sequence[int]):
         if len(edges) != len(default) or len(default) == 0:
             raise ValueError("TokenAutomaton: one edge list and one default per state, at least one state")
-        self.edges: Tuple[Tuple[Tuple[int, int], ...], ...] = tuple(tuple((int(t), int(n)) for t, n in e) for e in edges)
+        self._edges: Optional[Tuple[Tuple[Tuple[int, int], ...], ...]] = tuple(tuple((int(t), int(n)) for t, n in e) for e in edges)
         self.default: Tuple[int, ...] = tuple(int(d) for d in default)
+        self._arr: Optional[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]] = None
+
+    @classmethod
+    def from_arrays(cls, row_ptr, default_next, edge_tok, edge_next) -> "TokenAutomaton":
+        """The table form of ONE automaton (``PackedTable``'s arrays with start state 0): state q lists the edges
+        ``row_ptr[q] .. row_ptr[q + 1]``.  The arrays are copied to int32 and kept; ValueError for shapes that do not fit
+        together or a ``row_ptr`` that does not start at 0 or decreases (the values are ``validate``'s to check)."""
+        as32 = lambda x: np.ascontiguousarray(np.array(x, dtype=np.int32).reshape(-1))
+        row_ptr, default_next, edge_tok, edge_next = as32(row_ptr), as32(default_next), as32(edge_tok), as32(edge_next)
+        s = default_next.shape[0]
+        if s == 0 or row_ptr.shape[0] != s + 1:
+            raise ValueError("from_arrays: row_ptr has one entry more than default_next, at least one state")
+        if row_ptr[0] != 0 or np.any(np.diff(row_ptr) < 0) or row_ptr[-1] != edge_tok.shape[0] or edge_tok.shape != edge_next.shape:
+            raise ValueError("from_arrays: row_ptr runs from 0 to the number of edges without decreasing, one next value per edge")
+        a = cls.__new__(cls)
+        a._edges, a.default, a._arr = None, tuple(default_next.tolist()), (row_ptr, default_next, edge_tok, edge_next)
+        return a
+
+    @property
+    def edges(self) -> Tuple[Tuple[Tuple[int, int], ...], ...]:
+        if self._edges is None:
+            row_ptr, _, tok, nxt = self._arr
+            pairs = list(zip(tok.tolist(), nxt.tolist()))
+            self._edges = tuple(tuple(pairs[a:b]) for a, b in zip(row_ptr[:-1].tolist(), row_ptr[1:].tolist()))
+        return self._edges
+
+    def arrays(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """``(row_ptr, default_next, edge_tok, edge_next)``, int32: the kept arrays of the array-backed form, made from the
+        tuples otherwise.  Not to be written to."""
+        if self._arr is not None:
+            return self._arr
+        p = pack([self])
+        return p.row_ptr, p.default_next, p.edge_tok, p.edge_next
 
     @property
     def n_states(self) -> int:
@@ -35,7 +72,7 @@ class TokenAutomaton:
 
     @property
     def n_edges(self) -> int:
-        return sum(len(e) for e in self.edges)
+        return int(self._arr[2].shape[0]) if self._arr is not None else sum(len(e) for e in self._edges)
 
     # ---- constructors
     @classmethod
@@ -92,7 +129,12 @@ class TokenAutomaton:
     # ---- semantics
     def next(self, state: int, token: int) -> int:
         """The next value of ``token`` in ``state`` (a state id, FREE or FORBID)."""
-        for t, n in self.edges[state]:
+        if self._arr is not None:
+            row_ptr, _, tok, nxt = self._arr
+            lo, hi = int(row_ptr[state]), int(row_ptr[state + 1])
+            i = lo + int(np.searchsorted(tok[lo:hi], token))
+            return int(nxt[i]) if i < hi and tok[i] == token else self.default[state]
+        for t, n in self._edges[state]:
             if t == token:
                 return n
         return self.default[state]
@@ -112,7 +154,9 @@ class TokenAutomaton:
         state, FREE or FORBID, and a state in which no token other than ``suppress_id`` (which the pick leaves out on
         its own) is allowed: its pick would see a row of -inf alone."""
         s = self.n_states
-        for q, (edges, d) in enumerate(zip(self.edges, self.default)):
+        if self._arr is not None:
+            return self._validate_arrays(int(vocab), int(suppress_id))
+        for q, (edges, d) in enumerate(zip(self._edges, self.default)):
             toks = [t for t, _ in edges]
             if any(b <= a for a, b in zip(toks, toks[1:])):
                 raise ValueError(f"state {q}: edges must be sorted by token and distinct")
@@ -130,6 +174,42 @@ class TokenAutomaton:
                 ok = gone < vocab
             if not ok:
                 raise ValueError(f"state {q} allows no token" + (f" other than {suppress_id}" if suppress_id >= 0 else ""))
+
+    def _validate_arrays(self, vocab: int, suppress_id: int) -> None:
+        """``validate`` for the array-backed form: the same checks in the same order per state, the first failing state's
+        message; no per-edge Python."""
+        row_ptr, dflt, tok, nxt = self._arr
+        s, e = self.n_states, tok.shape[0]
+        state_of = np.repeat(np.arange(s), np.diff(row_ptr))
+        big = s + 1
+        first = lambda bad_states: int(bad_states.min()) if bad_states.size else big
+        inner = np.ones(e, dtype=bool)  # edges that have a predecessor in their own state
+        inner[row_ptr[:-1][row_ptr[:-1] < e]] = False
+        unsorted = first(state_of[1:][inner[1:] & (tok[1:] <= tok[:-1])]) if e > 1 else big
+        # sorted states: the first and last token bound the rest
+        outside = first(state_of[(tok < 0) | (tok >= vocab)])
+        is_next = lambda n: ((n >= 0) & (n < s)) | (n == FREE) | (n == FORBID)
+        bad_next = min(first(state_of[~is_next(nxt)]), first(np.flatnonzero(~is_next(dflt))))
+        gone_edge = (nxt == FORBID) | (tok == suppress_id)
+        n_gone = np.bincount(state_of[gone_edge], minlength=s)
+        n_live = np.diff(row_ptr) - n_gone
+        has_sup = np.bincount(state_of[tok == suppress_id], minlength=s) > 0
+        gone_allow = n_gone + ((0 <= suppress_id < vocab) & ~has_sup)
+        ok = np.where(dflt == FORBID, n_live > 0, gone_allow < vocab)
+        none_left = first(np.flatnonzero(~ok))
+        q = min(unsorted, outside, bad_next, none_left)
+        if q == big:
+            return
+        if q == unsorted:
+            raise ValueError(f"state {q}: edges must be sorted by token and distinct")
+        if q == outside:
+            raise ValueError(f"state {q}: a token outside [0, {vocab})")
+        if q == bad_next:
+            lo, hi = int(row_ptr[q]), int(row_ptr[q + 1])
+            vals = np.concatenate([nxt[lo:hi], dflt[q : q + 1]])
+            n = int(vals[~is_next(vals)][0])
+            raise ValueError(f"state {q}: next value {n} is no state of {s}, FREE or FORBID")
+        raise ValueError(f"state {q} allows no token" + (f" other than {suppress_id}" if suppress_id >= 0 else ""))
 
 
 @dataclass(frozen=True)
@@ -161,7 +241,15 @@ def pack(automata: Sequence[TokenAutomaton], state0: int = 0, edge0: int = 0) ->
         base = state0 + len(default_next)
         starts.append(base)
         rebase = lambda n: n + base if n >= 0 else n
-        for edges, d in zip(a.edges, a.default):
+        if a._arr is not None:  # array-backed: whole arrays at a time (lists of ints, like the tuple form's)
+            a_ptr, a_default, a_tok, a_next = a._arr
+            e0 = edge0 + len(edge_tok)
+            edge_tok += a_tok.tolist()
+            edge_next += np.where(a_next >= 0, a_next + base, a_next).tolist()
+            default_next += np.where(a_default >= 0, a_default + base, a_default).tolist()
+            row_ptr += (a_ptr[1:] + e0).tolist()
+            continue
+        for edges, d in zip(a._edges, a.default):
             edge_tok += [t for t, _ in edges]
             edge_next += [rebase(n) for _, n in edges]
             default_next.append(rebase(d))
@@ -201,6 +289,25 @@ def refuse_constraints(settings: Optional[dict], where: str) -> None:
     c = (settings or {}).get("constraints")
     if c is not None and not (isinstance(c, (list, tuple)) and all(x is None for x in c)):
         raise ValueError(f"constraints are not served by {where}")
+    if grammar_of(settings) is not None:  # a pattern or a schema is a constraint yet to be compiled
+        raise ValueError(f"constraints are not served by {where}")
+
+
+GRAMMAR_KEYS = ("regex", "json_schema")  # settings that compile to ``constraints`` (moondream_amd/grammar.py)
+
+
+def grammar_of(settings: Optional[Mapping], constraint_key: str = "constraints") -> Optional[Tuple[str, object]]:
+    """``settings["regex"]`` / ``settings["json_schema"]`` -> ``(key, value)``, None without either.  ValueError for both at
+    once and for one of them together with ``settings[constraint_key]``: one constraint per call, given one way."""
+    st = settings or {}
+    found = [(k, st[k]) for k in GRAMMAR_KEYS if st.get(k) is not None]
+    if not found:
+        return None
+    if len(found) > 1:
+        raise ValueError("regex and json_schema are mutually exclusive: one grammar per call")
+    if st.get(constraint_key) is not None:
+        raise ValueError(f"{found[0][0]} and {constraint_key} are mutually exclusive: {found[0][0]} compiles to the call's constraint")
+    return found[0]
 
 
 def pow2_at_least(n: int, floor: int = 16) -> int:

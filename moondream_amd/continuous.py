@@ -25,7 +25,7 @@ from typing import Callable, Deque, Dict, Iterator, List, Optional, Sequence, Tu
 
 import numpy as np
 
-from .constraint import FREE, TokenAutomaton, pack
+from .constraint import FREE, TokenAutomaton, grammar_of, pack
 from .decode_loop import (FILTER_NEUTRAL, PENALTY_NEUTRAL, Constraint, DecodeChunk, Penalty, Sampling, check_filters, check_penalties,
                           check_top_logprobs, run_chunk)
 from .scores import HostScores, Scores
@@ -379,11 +379,15 @@ class ContinuousEngine:
                temperature: Optional[float] = None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
                constraint: Optional[TokenAutomaton] = None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-               spatial: Optional[Tuple[int, list]] = None) -> int:
+               spatial: Optional[Tuple[int, list]] = None, regex: Optional[str] = None, json_schema: Optional[dict] = None,
+               vocab_bytes: Optional[Sequence[bytes]] = None) -> int:
         """Queue one request; ``image`` is a PIL image or an EncodedImage.  ``eos_id`` None: the tokenizer's EOS
         (``ignore_eos``: none).  ``temperature`` / ``top_p`` None: the engine's.  The three penalties (None: neutral):
         one number each, ``batch_generate_ids``' rule and validation.  ``constraint``: one ``TokenAutomaton`` (None: free),
-        ``batch_generate_ids``' rule and validation; ValueError when the engine's table has no room for it.  ``top_k`` /
+        ``batch_generate_ids``' rule and validation; ValueError when the engine's table has no room for it.  ``regex`` /
+        ``json_schema`` (with ``vocab_bytes`` where the tokenizer spells no bytes): compiled by the model's
+        ``regex_constraint`` / ``json_constraint`` (cached there) into the request's ``constraint``; mutually exclusive with
+        each other and with ``constraint``.  A compiled automaton can be large: size the engine's table for it.  ``top_k`` /
         ``min_p`` (None: off): one value each, ``batch_generate_ids``' rule and validation.  ``spatial``: what
         ``submit_query(spatial_refs=)`` builds -- (the position of the first placeholder in ``prompt_ids``, the checked
         refs), encoded into the prompt embeddings at admission.  Returns its id."""
@@ -391,6 +395,7 @@ class ContinuousEngine:
 
         from .moondream import EncodedImage
 
+        found = grammar_of(dict(regex=regex, json_schema=json_schema, constraint=constraint), "constraint")  # before anything else
         temp = self.temperature if temperature is None else float(temperature)
         tp = self.top_p if top_p is None else float(top_p)
         if not (math.isfinite(temp) and temp >= 0):
@@ -417,6 +422,8 @@ class ContinuousEngine:
             raise ValueError(f"image prefix + prompt ({prefix + len(prompt)} positions) do not fit the {t.max_context}-slot context")
         eos = None if ignore_eos else (self.model.config.tokenizer.eos_id if eos_id is None else int(eos_id))
         vidx = -1 if variant is None else self._variant_index(variant)
+        if found is not None:  # (after every other check: this one compiles on the device)
+            constraint = self.model._grammar_constraint(*found, vocab_bytes)
         start = FREE if constraint is None else self._register_constraint(constraint)  # (last: nothing fails after it)
         rid = self._next_rid
         self._next_rid += 1

@@ -18,6 +18,7 @@ constructor raises.
 from __future__ import annotations
 
 import ctypes as C
+import json
 import math
 import os
 from dataclasses import dataclass, replace
@@ -28,9 +29,9 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import _lib, resample
+from . import _lib, grammar, resample
 from .config import MoondreamConfig
-from .constraint import FREE, TokenAutomaton, check_constraints, pack, pow2_at_least, refuse_constraints
+from .constraint import FREE, GRAMMAR_KEYS, TokenAutomaton, check_constraints, grammar_of, pack, pow2_at_least, refuse_constraints
 from .crop_staging import CropStager, crop_workers, plan_chunks, upload_unique
 from .beam import Hypothesis, beams_of, check_beams, finalize, inv_norm_table, refuse_beams
 from .decode_loop import (Beam, Constraint, DecodeChunk, Penalty, ReasonChunk, Sampling, check_filters, check_penalties, check_score_settings,
@@ -297,6 +298,8 @@ class MoondreamModel:
         if self._device.type != "cuda":
             raise _lib.MoondreamHipError("MoondreamModel needs a GPU device; there is no CPU path")
         self.tokenizer = tokenizer if tokenizer is not None else _load_tokenizer()
+        self._own_vocab_bytes: Optional[List[bytes]] = None  # the tokenizer's vocabulary as bytes (regex_constraint)
+        self._grammar_cache: Dict[tuple, tuple] = {}  # (kind, pattern, id(vocabulary)) -> (vocabulary, TokenAutomaton)
         self.w = PackedModel(config, state_dict, self._device)
         # the checkpoint's own 4-bit weight stream for the decode regime (enable_int4_decode): exact but OPT-IN -- the in-register
         # dequantisation is VALU-bound today (0.82x the bf16 stream's decode phase at B = 64, profiles/r04_int4_weight_stream.txt)
@@ -1209,6 +1212,56 @@ class MoondreamModel:
         ``constraints=`` / ``settings={"constraints": ...}`` of the generation calls."""
         return TokenAutomaton.choices([list(self.tokenizer.encode(s).ids) for s in strings], self.config.tokenizer.eos_id)
 
+    def regex_constraint(self, pattern: str, vocab_bytes: Optional[Sequence[bytes]] = None) -> TokenAutomaton:
+        """The automaton under which a request's output spells a full match of ``pattern`` and may stop (eos) only where
+        the pattern is complete (moondream_amd/grammar.py: ``compile_regex``; the DFA on the host, the lift over the
+        vocabulary on the device).  ``vocab_bytes[v]``: the bytes token v spells, one entry per id of the model's
+        vocabulary; None: derived from the model's ``tokenizers.Tokenizer`` (``get_vocab()`` and the GPT-2 byte table).
+        The tokenizer's special ids and ``answer_id`` are never allowed.  Cached per (pattern, vocabulary object).
+        ValueError for what ``regex_to_dfa`` refuses, a vocabulary of the wrong length, the ``IdTokenizer`` stand-in without
+        ``vocab_bytes``, and a pattern this vocabulary cannot spell."""
+        return self._grammar_constraint("regex", pattern, vocab_bytes)
+
+    def json_constraint(self, schema: dict, vocab_bytes: Optional[Sequence[bytes]] = None) -> TokenAutomaton:
+        """``regex_constraint`` for the compact JSON documents of ``schema`` (``json_schema_to_regex``: its supported subset)."""
+        return self._grammar_constraint("json_schema", schema, vocab_bytes)
+
+    def _grammar_constraint(self, kind: str, value, vocab_bytes: Optional[Sequence[bytes]]) -> TokenAutomaton:
+        tk, v = self.config.tokenizer, self.config.text.vocab_size
+        if vocab_bytes is None:
+            if isinstance(self.tokenizer, IdTokenizer):
+                raise ValueError(f"{kind}: the IdTokenizer stand-in spells no bytes; pass vocab_bytes (one bytes object per token id)")
+            if self._own_vocab_bytes is None:
+                self._own_vocab_bytes = grammar.vocab_bytes_of(self.tokenizer, v)
+            vocab_bytes = self._own_vocab_bytes
+        if len(vocab_bytes) != v:
+            raise ValueError(f"vocab_bytes: {len(vocab_bytes)} entries for a vocabulary of {v}")
+        if kind == "regex":
+            if not isinstance(value, str):
+                raise ValueError(f"regex must be a str, not {value!r}")
+            pattern, key = value, value
+        else:
+            pattern = grammar.json_schema_to_regex(value)
+            key = json.dumps(value)
+        hit = self._grammar_cache.get((kind, key, id(vocab_bytes)))
+        if hit is not None and hit[0] is vocab_bytes:
+            return hit[1]
+        special = {tk.bos_id, tk.answer_id, tk.thinking_id, tk.coord_id, tk.size_id, tk.start_ground_points_id, tk.end_ground_id}
+        a = grammar.compile_dfa(grammar.regex_to_dfa(pattern), vocab_bytes, tk.eos_id, sorted(i for i in special if 0 <= i < v),
+                                self._device, f"the pattern {pattern[:60]!r}" if kind == "regex" else "the JSON schema")
+        self._grammar_cache[(kind, key, id(vocab_bytes))] = (vocab_bytes, a)  # (the vocabulary is kept: its id stays its own)
+        return a
+
+    def _grammar_settings(self, settings: Optional[dict]) -> Optional[dict]:
+        """``settings`` with ``regex`` / ``json_schema`` (and ``vocab_bytes``) compiled into ``constraints``; unchanged without
+        them.  ValueError for both at once and for either beside ``constraints``: before anything is compiled."""
+        found = grammar_of(settings)
+        if found is None:
+            return settings
+        rest = {k: x for k, x in settings.items() if k not in GRAMMAR_KEYS + ("vocab_bytes",)}
+        rest["constraints"] = self._grammar_constraint(*found, settings.get("vocab_bytes"))
+        return rest
+
     def _token_logprobs(self, logits: torch.Tensor, targets: torch.Tensor, suppress_id: int, logprob: torch.Tensor,
                         rank: torch.Tensor, suppress_rows: Optional[torch.Tensor] = None):
         """``logprob[r]`` (device fp32 [R]) and ``rank[r]`` (device int32 [R]) of token ``targets[r]`` (device int32 [R]) in row
@@ -2066,7 +2119,7 @@ class MoondreamModel:
             if kw.get("spatial") is not None:  # (beam rows are prepared by a route that takes no record)
                 raise ValueError("num_beams > 1 (beam search) is not served with spatial_refs")
             return self._beam_best_ids(images, prompts, settings, beams)
-        return self.batch_generate_ids(images, prompts, **kw, **self._sampling_kwargs(settings))
+        return self.batch_generate_ids(images, prompts, **kw, **self._sampling_kwargs(self._grammar_settings(settings)))
 
     def batch_generate_ids_continuous(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                                       eos_id: Optional[int] = None, ignore_eos: bool = False, max_live: int = 64, chunk: int = 16,
@@ -2381,8 +2434,10 @@ class MoondreamModel:
             i0 += n
 
     def _check_constraints_of(self, settings: Optional[dict], n: int) -> Optional[List[Optional[TokenAutomaton]]]:
-        """``settings["constraints"]`` checked for ``n`` rows (``check_constraints``): host values, before any GPU work."""
-        constraints = (settings or {}).get("constraints")
+        """``settings["constraints"]`` checked for ``n`` rows (``check_constraints``): host values, before any GPU work --
+        but for ``settings["regex"]`` / ``settings["json_schema"]``, which are compiled (once: ``_grammar_constraint``
+        caches) into the one automaton of every row, after their own argument checks."""
+        constraints = (self._grammar_settings(settings) or {}).get("constraints")
         if constraints is None:
             return None
         return check_constraints(constraints, n, self.config.text.vocab_size, self.config.tokenizer.answer_id)
