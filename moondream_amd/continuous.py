@@ -25,10 +25,10 @@ from typing import Callable, Deque, Dict, Iterator, List, Optional, Sequence, Tu
 
 import numpy as np
 
-from .constraint import FREE, TokenAutomaton, grammar_of, pack
-from .decode_loop import (FILTER_NEUTRAL, PENALTY_NEUTRAL, Constraint, DecodeChunk, Penalty, Sampling, check_filters, check_penalties,
-                          check_top_logprobs, run_chunk)
+from .constraint import FREE, TokenAutomaton, check_constraints, grammar_of, pack
+from .decode_loop import PENALTY_NEUTRAL, Constraint, DecodeChunk, Penalty, Sampling, check_top_logprobs, run_chunk
 from .scores import HostScores, Scores
+from .settings import CallSettings, RowSettings
 from .spatial import SpatialRecord, check_spatial_refs, spatial_prompt_ids
 
 DEFAULT_MAX_TOKENS = 768  # moondream.py (the reference's default, moondream.py:50-53)
@@ -75,22 +75,12 @@ class Request:
     done: bool = False
     generator: object = None
     variant: int = -1  # index in the model's LoRA bank (md_lora_bank); -1: the base model
-    temperature: float = 0.0  # 0: greedy (the request draws nothing from its generator)
-    top_p: float = DEFAULT_TOP_P
+    settings: RowSettings = RowSettings()  # what it decodes with (moondream_amd/settings.py); a greedy request draws nothing
     logprobs: List[float] = field(default_factory=list)  # of ``ids``, entry for entry (an engine with logprobs=True)
     ranks: List[int] = field(default_factory=list)
     alternatives: List[list] = field(default_factory=list)  # of ``ids`` too: k (token_id, logprob) pairs each (top_logprobs=k)
-    penalties: Tuple[float, float, float] = PENALTY_NEUTRAL  # (repetition, presence, frequency): md_penalize_rows' rule
-    constraint: Optional[TokenAutomaton] = None  # what the request may generate (md_constrain_rows); None: anything
-    constraint_start: int = FREE  # its start state in the engine's table
-    top_k: int = 0      # sampled rows only: the first top_k tokens of the descending order (0: off) ...
-    min_p: float = 0.0  # ... and the tokens of probability >= min_p * the best one's (0: off): md_sample_rows_filtered
+    constraint_start: int = FREE  # the start state of its automaton in the engine's table
     spatial: Optional[Tuple[int, list]] = None  # (position of the first placeholder in ``prompt``, the checked refs); None: no refs
-
-    @property
-    def filtered(self) -> bool:
-        """A sampled request with a non-neutral ``top_k`` / ``min_p`` (a greedy one ignores them)."""
-        return self.temperature != 0 and (self.top_k, self.min_p) != FILTER_NEUTRAL
 
     @property
     def remaining(self) -> int:
@@ -391,26 +381,39 @@ class ContinuousEngine:
         ``min_p`` (None: off): one value each, ``batch_generate_ids``' rule and validation.  ``spatial``: what
         ``submit_query(spatial_refs=)`` builds -- (the position of the first placeholder in ``prompt_ids``, the checked
         refs), encoded into the prompt embeddings at admission.  Returns its id."""
-        from PIL import Image
-
-        from .moondream import EncodedImage
-
         found = grammar_of(dict(regex=regex, json_schema=json_schema, constraint=constraint), "constraint")  # before anything else
+        temp, tp = self._draw_settings(temperature, top_p)
+        for name, x in (("repetition_penalty", repetition_penalty), ("presence_penalty", presence_penalty),
+                        ("frequency_penalty", frequency_penalty)):
+            if isinstance(x, (list, tuple)):
+                raise ValueError(f"{name}: one number per request, not {x!r}")
+        for name, x in (("top_k", top_k), ("min_p", min_p)):
+            if isinstance(x, (list, tuple)):
+                raise ValueError(f"{name}: one value per request, not {x!r}")
+        row = CallSettings.of(1, None, temperature=temp, top_p=tp, repetition_penalty=repetition_penalty,
+                              presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, top_k=top_k, min_p=min_p).rows[0]
+        return self._enqueue(image, prompt_ids, max_tokens, eos_id, seed, ignore_eos, variant, replace(row, constraint=constraint),
+                             spatial, found, vocab_bytes)
+
+    def _draw_settings(self, temperature, top_p) -> Tuple[float, float]:
+        """A request's temperature and top-p (None: the engine's), in range: ValueError otherwise."""
         temp = self.temperature if temperature is None else float(temperature)
         tp = self.top_p if top_p is None else float(top_p)
         if not (math.isfinite(temp) and temp >= 0):
             raise ValueError(f"temperature must be finite and >= 0 (0: greedy), not {temp}")
         if not (math.isfinite(tp) and 0 < tp <= 1):
             raise ValueError(f"top_p must be in (0, 1], not {tp}")
-        for name, x in (("repetition_penalty", repetition_penalty), ("presence_penalty", presence_penalty),
-                        ("frequency_penalty", frequency_penalty)):
-            if isinstance(x, (list, tuple)):
-                raise ValueError(f"{name}: one number per request, not {x!r}")
-        pen = check_penalties(repetition_penalty, presence_penalty, frequency_penalty, 1)
-        for name, x in (("top_k", top_k), ("min_p", min_p)):
-            if isinstance(x, (list, tuple)):
-                raise ValueError(f"{name}: one value per request, not {x!r}")
-        filt = check_filters(top_k, min_p, 1)
+        return temp, tp
+
+    def _enqueue(self, image, prompt_ids: Sequence[int], max_tokens: int, eos_id: Optional[int], seed: Optional[int],
+                 ignore_eos: bool, variant: Optional[str], row: RowSettings, spatial=None, grammar=None, vocab_bytes=None) -> int:
+        """Queue one request whose settings are parsed (``row``: its record; ``grammar``: ``grammar_of``'s pair, compiled
+        here into the record's automaton): the checks of the request itself, then, last, what takes room in the engine's
+        constraint table.  Returns its id."""
+        from PIL import Image
+
+        from .moondream import EncodedImage
+
         if not isinstance(image, (Image.Image, EncodedImage)):
             raise ValueError("image must be a PIL Image or EncodedImage")
         prompt = [int(p) for p in prompt_ids]
@@ -422,14 +425,13 @@ class ContinuousEngine:
             raise ValueError(f"image prefix + prompt ({prefix + len(prompt)} positions) do not fit the {t.max_context}-slot context")
         eos = None if ignore_eos else (self.model.config.tokenizer.eos_id if eos_id is None else int(eos_id))
         vidx = -1 if variant is None else self._variant_index(variant)
-        if found is not None:  # (after every other check: this one compiles on the device)
-            constraint = self.model._grammar_constraint(*found, vocab_bytes)
-        start = FREE if constraint is None else self._register_constraint(constraint)  # (last: nothing fails after it)
+        if grammar is not None:  # (after every other check: this one compiles on the device)
+            row = replace(row, constraint=self.model._grammar_constraint(*grammar, vocab_bytes))
+        start = FREE if row.constraint is None else self._register_constraint(row.constraint)  # (last: nothing fails after it)
         rid = self._next_rid
         self._next_rid += 1
-        self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed, variant=vidx, temperature=temp, top_p=tp,
-                                  penalties=pen[0] if pen else PENALTY_NEUTRAL, constraint=constraint, constraint_start=start,
-                                  top_k=filt[0][0] if filt else 0, min_p=filt[0][1] if filt else 0.0, spatial=spatial))
+        self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed, variant=vidx, settings=row, constraint_start=start,
+                                  spatial=spatial))
         return rid
 
     def _register_constraint(self, a: TokenAutomaton) -> int:
@@ -574,14 +576,15 @@ class ContinuousEngine:
                 raise ValueError(f"one {name} per request")
             return x
 
-        temps, tps = per_request(temperature, "temperature"), per_request(top_p, "top_p")
-        cons = [constraints] * n if constraints is None or isinstance(constraints, TokenAutomaton) else list(constraints)
-        if len(cons) != n:
-            raise ValueError(f"constraints: {len(cons)} entries for {n} requests (one TokenAutomaton, or one entry per request)")
-        pens = check_penalties(repetition_penalty, presence_penalty, frequency_penalty, n) or [PENALTY_NEUTRAL] * n
-        filts = check_filters(top_k, min_p, n) or [FILTER_NEUTRAL] * n
-        rids = [self.submit(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant, temps[i], tps[i], *pens[i],
-                            constraint=cons[i], top_k=filts[i][0], min_p=filts[i][1]) for i in range(n)]
+        draws = [self._draw_settings(*pair) for pair in zip(per_request(temperature, "temperature"), per_request(top_p, "top_p"))]
+        if isinstance(constraints, (list, tuple)) and len(constraints) != n:
+            raise ValueError(f"constraints: {len(constraints)} entries for {n} requests (one TokenAutomaton, or one entry per request)")
+        cfg = self.model.config
+        st = CallSettings.of(n, lambda c, k: check_constraints(c, k, cfg.text.vocab_size, cfg.tokenizer.answer_id),
+                             temperature=[d[0] for d in draws], top_p=[d[1] for d in draws], repetition_penalty=repetition_penalty,
+                             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, constraints=constraints,
+                             top_k=top_k, min_p=min_p)
+        rids = [self._enqueue(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant, st.rows[i]) for i in range(n)]
         if return_logprobs:  # (ids, logprobs, ranks), and alternatives on an engine with top_logprobs
             got3 = {rid: rest for rid, *rest in self.run(with_logprobs=True)}
             return tuple([got3[r][k] for r in rids] for k in range(4 if self.top_logprobs else 3))
@@ -654,15 +657,15 @@ class ContinuousEngine:
         base = replace(table, variants=None, bank=None)
         routes = [(table if any(r.variant >= 0 for r in rows[r0:r1]) else base).sub(r0, r1) for r0, r1 in groups]
         pick = st = con = None
-        if any(r.temperature != 0 for r in rows):
+        if any(r.settings.sampled for r in rows):
             # one H2D copy of [temperature | top_p | uniform] rows; a greedy request draws nothing
-            draws = [float(self._uniforms(r, 1)[0]) if r.temperature != 0 else 0.0 for r in rows]
-            st = m._h2d(torch.tensor([[r.temperature for r in rows], [r.top_p for r in rows], draws], dtype=torch.float32))
+            draws = [float(self._uniforms(r, 1)[0]) if r.settings.sampled else 0.0 for r in rows]
+            st = m._h2d(torch.tensor([[r.settings.temperature for r in rows], [r.settings.top_p for r in rows], draws], dtype=torch.float32))
             pick = Sampling(st[0], st[1])
-            if any(r.filtered for r in rows):  # two more rows of settings: the first token is cut too
-                pick = replace(pick, top_k=m._h2d(torch.tensor([min(r.top_k, 2 ** 31 - 1) for r in rows], dtype=torch.int32)),
-                               min_p=m._h2d(torch.tensor([r.min_p for r in rows], dtype=torch.float32)))
-        if any(r.constraint is not None for r in rows):  # the rows' start states, beside the engine's table
+            if any(r.settings.filtered for r in rows):  # two more rows of settings: the first token is cut too
+                pick = replace(pick, top_k=m._h2d(torch.tensor([r.settings.top_k for r in rows], dtype=torch.int32)),
+                               min_p=m._h2d(torch.tensor([r.settings.min_p for r in rows], dtype=torch.float32)))
+        if any(r.settings.constrained for r in rows):  # the rows' start states, beside the engine's table
             con = self._constraint(m._h2d(torch.tensor([r.constraint_start for r in rows], dtype=torch.int32)), by_slot=False)
         scores = Scores.new((len(rows),), self.top_logprobs, m.device) if self.logprobs else None
         spatial = None
@@ -802,7 +805,7 @@ class ContinuousEngine:
             hs[n_in:] = -1
             hs[n_in : n_in + len(row_var)] = row_var
             var_d.copy_(host[n_in:], non_blocking=True)
-        sample = any(r.temperature != 0 for r in plan.rows)
+        sample = any(r.settings.sampled for r in plan.rows)
         if sample:
             fh = u_host.numpy()
             uh, th, ph = fh[: c * B].reshape(c, B), fh[c * B : c * B + B], fh[c * B + B :]
@@ -810,29 +813,29 @@ class ContinuousEngine:
             th[:] = -1.0  # rows past the plan's are idle: md_sample_rows leaves them alone
             ph[:] = 1.0
             for r_idx, r in enumerate(plan.rows):
-                th[r_idx], ph[r_idx] = r.temperature, r.top_p
-                if r.temperature != 0:  # a greedy request draws nothing from its generator
+                th[r_idx], ph[r_idx] = r.settings.temperature, r.settings.top_p
+                if r.settings.sampled:  # a greedy request draws nothing from its generator
                     k = min(n, r.remaining)
                     uh[:k, r_idx] = self._uniforms(r, k).numpy()
             u_dev.copy_(u_host, non_blocking=True)
         filt = None
-        if any(r.filtered for r in plan.rows):  # (sampled rows: ``sample`` holds) the rows' cuts, padding rows off
+        if any(r.settings.filtered for r in plan.rows):  # (sampled rows: ``sample`` holds) the rows' cuts, padding rows off
             k_dev, k_host, m_dev, m_host = self._filter_buffers(B)
             kh, mh = k_host.numpy(), m_host.numpy()
             kh[:], mh[:] = 0, 0.0
             for r_idx, r in enumerate(plan.rows):
-                kh[r_idx], mh[r_idx] = min(r.top_k, 2 ** 31 - 1), r.min_p
+                kh[r_idx], mh[r_idx] = r.settings.top_k, r.settings.min_p  # (``check_filters``: top_k below 2^31)
             k_dev.copy_(k_host, non_blocking=True)
             m_dev.copy_(m_host, non_blocking=True)
             filt = (k_dev, m_dev)
         penalty = None
-        if any(r.penalties != PENALTY_NEUTRAL for r in plan.rows):
+        if any(r.settings.penalised for r in plan.rows):
             # the rows' settings (padding rows neutral) and the slots whose history starts here, in two small copies behind
             # the chunk's others; the lengths are zeroed on the stream, before the chunk's first launch
             p_hist, p_len, st_dev, st_host, rs_dev, rs_host = self._penalty_buffers(B)
             sh = st_host.numpy().reshape(3, B)
             sh[:] = np.asarray(PENALTY_NEUTRAL, dtype=np.float32)[:, None]
-            sh[:, : len(plan.rows)] = np.asarray([r.penalties for r in plan.rows], dtype=np.float32).T
+            sh[:, : len(plan.rows)] = np.asarray([r.settings.penalties for r in plan.rows], dtype=np.float32).T
             rs_host.numpy()[:] = np.where(plan.fresh >= 0, plan.fresh, self.max_live)
             st_dev.copy_(st_host, non_blocking=True)
             rs_dev.copy_(rs_host, non_blocking=True)
@@ -848,7 +851,7 @@ class ContinuousEngine:
             i_dev.copy_(i_host, non_blocking=True)
             v_dev.copy_(v_host, non_blocking=True)
             con.state.index_copy_(0, i_dev, v_dev)
-            if any(r.constraint is not None for r in plan.rows):
+            if any(r.settings.constrained for r in plan.rows):
                 constraint = con
         scores = self._score_buffers(B) if self.logprobs else None  # (an idle or padding row's are never read: SlotScheduler.commit)
         # step i's routing: row i of the slot table; a LoRA row in the chunk: the chunk's row-variant table with it

@@ -260,6 +260,27 @@ class Sampling:
     def filtered(self) -> bool:
         return self.top_k is not None
 
+    def cut(self, r0: int, r1: int) -> "Sampling":
+        """Rows [r0, r1) of a per-row record: its tensors cut like the rows.  The call's generator and draw order stay
+        behind: whoever cuts the rows cuts their draws."""
+        cut = lambda t: t[r0:r1] if t is not None else None
+        return Sampling(self.temperature[r0:r1], self.top_p[r0:r1], top_k=cut(self.top_k), min_p=cut(self.min_p))
+
+
+def pick_tokens(model, pick: Optional[Sampling], logits, suppress_id: int = -1, uniforms=None, out=None, row_perm=None):
+    """The one choice among the model's three pick launches, for logits [B, V] -> int32 [B] (``out``, or a new tensor).
+    ``pick`` None: the argmax (``_pick`` at temperature 0).  A record of two floats, the call's settings: ``_pick`` -- it
+    draws from ``uniforms``, or, without them, from the record's generator in the order ``row_perm``.  (The first token's
+    pick used to hand ``_pick`` no ``uniforms``; no caller gives it any with such a record, so its draws are the same.)
+    A per-row record: ``_pick_rows`` over ``uniforms`` fp32 [B], or, with ``top_k`` / ``min_p``, ``_pick_rows_filtered``."""
+    if pick is None:
+        pick = Sampling(0.0, 0.0)
+    if pick.filtered:
+        return model._pick_rows_filtered(logits, pick.temperature, pick.top_p, pick.top_k, pick.min_p, suppress_id, uniforms, out=out)
+    if pick.per_row:
+        return model._pick_rows(logits, pick.temperature, pick.top_p, suppress_id, uniforms, out=out)
+    return model._pick(logits, pick.temperature, pick.top_p, suppress_id, pick.generator, row_perm=row_perm, uniforms=uniforms, out=out)
+
 
 @dataclass(frozen=True, eq=False)
 class ReasonChunk:
@@ -365,14 +386,9 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     tk_ids, tk_lp = c.topk if c.topk is not None else (None, None)
     by_row = c.pick is not None and c.pick.per_row
     assert c.pick is None or not c.pick.filtered or (by_row and c.pick.min_p is not None)
-
-    def pick_rows(lg, suppress_id, u, out):  # every row's own settings; with the two filters the launch that applies them
-        if c.pick.filtered:
-            model._pick_rows_filtered(lg, c.pick.temperature, c.pick.top_p, c.pick.top_k, c.pick.min_p, suppress_id, u, out=out)
-        else:
-            model._pick_rows(lg, c.pick.temperature, c.pick.top_p, suppress_id, u, out=out)
-    # penalised or masked logits are picked from again: the fused step's argmax saw the raw ones
-    again = c.pick if c.pick is not None or (c.penalty is None and c.constraint is None) else Sampling(0.0, 0.0)
+    # penalised or masked logits are picked from again (greedy: by the argmax launch): the fused step's argmax saw the raw ones
+    again = c.pick is not None or c.penalty is not None or c.constraint is not None
+    draws = lambda i: c.uniforms[i] if c.uniforms is not None else None
 
     def body():
         for i in range(n):
@@ -380,7 +396,7 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
             if c.reason is not None:
                 # the step masks its logits per row and leaves the pick to the per-row kernel, nothing suppressed there
                 model._decode_step_reason(c.rows_of(i), c.reason, i, tok_in, c.pos, c.b, logits, ws, kv)
-                pick_rows(left, -1, c.uniforms[i], tok_out)
+                pick_tokens(model, c.pick, left, -1, draws(i), out=tok_out)
                 continue
             if c.b1:
                 model._decode_step_b1(tok_in, tok_out, c.pos, c.suppress_id, logits, ws, kv)
@@ -397,11 +413,8 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
                 model._constrain(lg, tok_in, c.rows_of(i), c.constraint)
             # a fused step wrote its argmax to tok_out: a pick draws from the logits it left instead (of per-row settings,
             # a greedy row takes the same argmax again and an idle row keeps what is there)
-            if by_row:
-                pick_rows(lg, c.suppress_id, c.uniforms[i], tok_out)
-            elif again is not None:
-                model._pick(lg, again.temperature, again.top_p, c.suppress_id, again.generator,
-                            uniforms=c.uniforms[i] if c.uniforms is not None else None, out=tok_out)
+            if again:
+                pick_tokens(model, c.pick, lg, c.suppress_id, draws(i), out=tok_out)
             if lp is not None:  # targets = the step's tokens
                 model._token_logprobs(lg, tok_out, c.suppress_id, lp[i], rk[i])
             if tk_ids is not None:  # the decision's alternatives; a row whose token is no id (idle) is not read

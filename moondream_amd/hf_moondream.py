@@ -19,11 +19,8 @@ from typing import List, Optional, Sequence
 import torch
 
 from .config import MoondreamConfig
-from .beam import refuse_beams
-from .constraint import refuse_constraints
-from .decode_loop import refuse_filters, refuse_penalties
-from .spatial import refs_of, refuse_spatial_refs
 from .moondream import MoondreamModel
+from .settings import FAMILIES, refuse_settings
 
 
 def extract_question(text: str) -> Optional[str]:
@@ -33,6 +30,14 @@ def extract_question(text: str) -> Optional[str]:
     if text.startswith(prefix) and text.endswith(suffix):
         return text[len(prefix) : -len(suffix)]
     return None
+
+
+def _refuse_extensions(kwargs: dict) -> None:
+    """The wrapper's own calls serve the reference's settings alone: ValueError for a penalty, a constraint, top-k / min-p,
+    beam search or spatial references among a call's keyword arguments."""
+    refuse_settings(kwargs.get("settings"), {None: "HfMoondream (use MoondreamModel's calls)",
+                                             "spatial_refs": "HfMoondream's own calls (use MoondreamModel's)"},
+                    FAMILIES, spatial_refs=kwargs.get("spatial_refs"))
 
 
 class HfMoondream:
@@ -75,11 +80,7 @@ class HfMoondream:
         model's default sampling settings; ``tokenizer`` / ``chat_history`` / ``max_new_tokens`` are
         ignored there too.  Extension: ``settings=`` is forwarded to ``query`` (e.g. temperature 0); the penalty settings
         are not part of this wrapper's calls (ValueError for a non-neutral one), nor are ``constraints`` or ``spatial_refs``."""
-        refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
-        refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
-        refuse_filters(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
-        refuse_beams(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
-        refuse_spatial_refs(refs_of(kwargs.get("settings"), kwargs.get("spatial_refs")), "HfMoondream's own calls (use MoondreamModel's)")
+        _refuse_extensions(kwargs)
         answer = self.query(image_embeds, question, settings=kwargs.get("settings"))["answer"].strip()
         if result_queue is not None:
             result_queue.put(answer)
@@ -90,11 +91,7 @@ class HfMoondream:
         (temperature 0.5, top_p 0.3: moondream.py:50-53).  Here: one lockstep decode over all pairs (questions of different
         token counts share it), every sequence sampling with the same rule and its own uniforms (round 6; rounds 1-5 forced
         greedy).  ``settings={"temperature": 0}`` is the greedy form; ``max_new_tokens`` bounds the answers."""
-        refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
-        refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
-        refuse_filters(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
-        refuse_beams(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
-        refuse_spatial_refs(refs_of(kwargs.get("settings"), kwargs.get("spatial_refs")), "HfMoondream's own calls (use MoondreamModel's)")
+        _refuse_extensions(kwargs)
         self._setup_caches()
         settings = dict(kwargs.get("settings") or {})
         settings.setdefault("max_tokens", kwargs.get("max_new_tokens", kwargs.get("max_tokens", 256)))
@@ -110,11 +107,7 @@ class HfMoondream:
     def generate(self, image_embeds, prompt, tokenizer=None, max_new_tokens=128, **kwargs) -> List[str]:
         """reference: hf_moondream.py:112-142.  A prompt in the legacy "<image>\\n\\nQuestion: ..\\n\\nAnswer:"
         form is a ``query``; anything else is tokenised and continued as is after the image prefix."""
-        refuse_penalties(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
-        refuse_constraints(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
-        refuse_filters(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
-        refuse_beams(kwargs.get("settings"), "HfMoondream (use MoondreamModel's calls)")
-        refuse_spatial_refs(refs_of(kwargs.get("settings"), kwargs.get("spatial_refs")), "HfMoondream's own calls (use MoondreamModel's)")
+        _refuse_extensions(kwargs)
         q = extract_question(prompt)
         if q is not None:
             return [self.model_query(image_embeds, q)]

@@ -31,25 +31,23 @@ from PIL import Image
 
 from . import _lib, grammar, resample
 from .config import MoondreamConfig
-from .constraint import FREE, GRAMMAR_KEYS, TokenAutomaton, check_constraints, grammar_of, pack, pow2_at_least, refuse_constraints
+from .constraint import FREE, TokenAutomaton, check_constraints, pack, pow2_at_least
 from .crop_staging import CropStager, crop_workers, plan_chunks, upload_unique
-from .beam import Hypothesis, beams_of, check_beams, finalize, inv_norm_table, refuse_beams
-from .decode_loop import (Beam, Constraint, DecodeChunk, Penalty, ReasonChunk, Sampling, check_filters, check_penalties, check_score_settings,
-                          check_top_logprobs, filters_of, penalties_of, refuse_filters, refuse_penalties, run_chunk)
+from .beam import Hypothesis, check_beams, finalize, inv_norm_table
+from .decode_loop import (Beam, Constraint, DecodeChunk, Penalty, ReasonChunk, Sampling, check_score_settings, check_top_logprobs,
+                          pick_tokens, run_chunk)
 from .graph_store import GraphStore
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops, resize_backend
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
 from .lora import variant_state_dict
 from .scores import Scores
+from .settings import DEFAULT_MAX_TOKENS, DEFAULT_TEMPERATURE, DEFAULT_TOP_P, CallSettings, refuse_settings
 from .shared_prefix import RowPlan, check_shared_table, plan_rows
-from .spatial import SpatialRecord, check_spatial_refs, refs_of, refuse_spatial_refs, spatial_prompt_ids
+from .spatial import SpatialRecord, check_spatial_refs, refs_of, spatial_prompt_ids
 from .weights import PackedLora, PackedLoraBank, PackedModel
 
 BF16 = torch.bfloat16
 
-DEFAULT_MAX_TOKENS = 768
-DEFAULT_TEMPERATURE = 0.5
-DEFAULT_TOP_P = 0.3
 DEFAULT_MAX_OBJECTS = 50
 
 SpatialRefs = List[Union[Tuple[float, float], Tuple[float, float, float, float]]]
@@ -185,8 +183,9 @@ class Prepared:
     hidden_last: torch.Tensor  # [B, D]: the prompt pass's last hidden row
     next_pos: List[int]
     rows: _Rows                # the routing the decode loop must use
-    sampling: Optional[Sampling]  # the caller's; on the shared route with ``row_perm`` set
+    sampling: Optional[Sampling]  # the call's pick (None: greedy); shared route: ``row_perm`` set; with top-k / min-p: per row
     constraint: Optional[Constraint] = None  # the rows' automata, each past its first token's mask (None: every row free)
+    penalty: Optional[Penalty] = None  # the rows' penalties, every history empty (None: every row neutral)
 
     def in_caller_order(self, per_row: Sequence) -> list:
         out = [None] * len(self.order)
@@ -1118,7 +1117,7 @@ class MoondreamModel:
                                                         torch.empty(b, dtype=torch.int32, device=self._device)))
         f.copy_(self._h2d(torch.tensor([[float(sampling.temperature)] * b, [float(sampling.top_p)] * b, [r[1] for r in rows]],
                                        dtype=torch.float32)))
-        k.copy_(self._h2d(torch.tensor([min(r[0], 2 ** 31 - 1) for r in rows], dtype=torch.int32)))
+        k.copy_(self._h2d(torch.tensor([r[0] for r in rows], dtype=torch.int32)))  # (``check_filters``: below 2^31)
         return replace(sampling, temperature=f[0], top_p=f[1], top_k=k, min_p=f[2])
 
     def _penalize(self, logits: torch.Tensor, tok_in: torch.Tensor, rows: "_Rows", pen: Penalty):
@@ -1252,16 +1251,6 @@ class MoondreamModel:
         self._grammar_cache[(kind, key, id(vocab_bytes))] = (vocab_bytes, a)  # (the vocabulary is kept: its id stays its own)
         return a
 
-    def _grammar_settings(self, settings: Optional[dict]) -> Optional[dict]:
-        """``settings`` with ``regex`` / ``json_schema`` (and ``vocab_bytes``) compiled into ``constraints``; unchanged without
-        them.  ValueError for both at once and for either beside ``constraints``: before anything is compiled."""
-        found = grammar_of(settings)
-        if found is None:
-            return settings
-        rest = {k: x for k, x in settings.items() if k not in GRAMMAR_KEYS + ("vocab_bytes",)}
-        rest["constraints"] = self._grammar_constraint(*found, settings.get("vocab_bytes"))
-        return rest
-
     def _token_logprobs(self, logits: torch.Tensor, targets: torch.Tensor, suppress_id: int, logprob: torch.Tensor,
                         rank: torch.Tensor, suppress_rows: Optional[torch.Tensor] = None):
         """``logprob[r]`` (device fp32 [R]) and ``rank[r]`` (device int32 [R]) of token ``targets[r]`` (device int32 [R]) in row
@@ -1350,14 +1339,7 @@ class MoondreamModel:
         if constraint is not None:
             assert not constraint.by_slot
             self._constrain(logits, None, _Rows(), constraint, row0)
-        if pick is None:
-            first = self._pick(logits, 0.0, 0.0)
-        elif pick.filtered:
-            first = self._pick_rows_filtered(logits, pick.temperature, pick.top_p, pick.top_k, pick.min_p, -1, uniforms)
-        elif pick.per_row:
-            first = self._pick_rows(logits, pick.temperature, pick.top_p, -1, uniforms)
-        else:
-            first = self._pick(logits, pick.temperature, pick.top_p, -1, pick.generator, row_perm=row_perm)
+        first = pick_tokens(self, pick, logits, -1, uniforms, row_perm=row_perm)
         if scores is not None:
             self._score(logits, first, -1, scores)
         return first
@@ -1574,17 +1556,14 @@ class MoondreamModel:
                     logits_capture[c0:c1] = logits
                 perm = sampling.row_perm[c0:c1] if sampling is not None and sampling.row_perm is not None else None
                 by_row = sampling is not None and sampling.per_row  # the rows' own settings and draws
-                cut_of = lambda t: t[c0:c1] if t is not None else None
                 draws = uniforms[c0:c1] if uniforms is not None else None
                 if by_row and draws is None:  # the call's generator: the draws ``_pick`` makes for these rows
                     draws = torch.rand(c1 - c0, device=self._device, dtype=torch.float32, generator=sampling.generator)
                     if perm is not None:
                         draws = draws[perm - perm.min()].contiguous()
-                first[c0:c1] = self._first_token(
-                    logits, Sampling(sampling.temperature[c0:c1], sampling.top_p[c0:c1], top_k=cut_of(sampling.top_k),
-                                     min_p=cut_of(sampling.min_p)) if by_row else sampling,
-                    perm - perm.min() if perm is not None else None, uniforms=draws,
-                    scores=scores and scores[c0:c1], constraint=constraint, row0=c0)
+                first[c0:c1] = self._first_token(logits, sampling.cut(c0, c1) if by_row else sampling,
+                                                 perm - perm.min() if perm is not None else None, uniforms=draws,
+                                                 scores=scores and scores[c0:c1], constraint=constraint, row0=c0)
             hidden_last[r0:r1] = hidden[:, -1, :]
         return first, hidden_last, next_pos
 
@@ -1675,9 +1654,7 @@ class MoondreamModel:
     def _prepare_sequences(self, images, prompts: Sequence[Sequence[int]], mark=None, rows: Union[int, _Rows] = 0,
                            fuse: bool = False, share_prefix: bool = False, variants: Optional[Sequence[int]] = None,
                            encode_settings: Optional[dict] = None, logits_capture: Optional[torch.Tensor] = None,
-                           sampling: Optional[Sampling] = None, scores: Optional[Scores] = None, hidden_sink=None,
-                           constraints: Optional[Sequence[Optional[TokenAutomaton]]] = None,
-                           filters: Optional[Sequence[Tuple[int, float]]] = None,
+                           settings: Optional[CallSettings] = None, scores: Optional[Scores] = None, hidden_sink=None,
                            spatial: Optional[SpatialRecord] = None) -> Prepared:
         """Everything before the first generated token, for B (image, prompt-ids) pairs, as ``plan_rows`` lays them out
         (moondream_amd/shared_prefix.py): every image's KV prefix is placed (``_place_images``), then one prompt prefill per
@@ -1688,13 +1665,13 @@ class MoondreamModel:
         (``row_perm``).  ``share_prefix`` that is not served shared runs the copy route over each distinct image's
         EncodedImage (``encode_settings``).  ``variants``: each row's bank index (-1: the base model) in the CALLER's order;
         the device table is built in slot order here.  ``fuse``: an all-raw copy route takes the one-pass prefill below.
-        ``sampling`` draws the first token as the reference's _prefill_prompt does (moondream.py:313-318; nothing suppressed
-        there); None = argmax.
+        ``settings``: the call's settings record (moondream_amd/settings.py), rows in the CALLER's order; None: greedy, every
+        row neutral.  Its three device records are built here, rows in slot order, and go to the decode loop in the
+        ``Prepared``: the pick (a sampled call draws the first token as the reference's _prefill_prompt does,
+        moondream.py:313-318, nothing suppressed there; with top-k / min-p through their per-row record,
+        ``_filter_record``), the constraint (``_constraint_record``: it masks every first pick) and, once the prompt
+        passes are queued, the penalties (``_penalty_record``: the first token is picked with an empty history).
         ``logits_capture`` / ``scores`` / ``hidden_sink``: as ``_prefill_groups`` takes them, in slot order.
-        ``constraints``: ``check_constraints``' entries in the CALLER's order; their record (``_constraint_record``, rows in
-        slot order) masks every first pick and goes to the decode loop in ``Prepared.constraint``.  ``filters``:
-        ``check_filters``' pairs in the CALLER's order; a sampled call then picks with their per-row record
-        (``_filter_record``, rows in slot order), the first tokens too, and ``Prepared.sampling`` is that record.
         ``spatial``: the rows' spatial references in the CALLER's order (their placeholders are in ``prompts``, so rows
         group by their total length); reordered to slot order here and encoded into the prompt embeddings
         (``_sequence_embeddings``).  Must run under torch.inference_mode()."""
@@ -1709,6 +1686,8 @@ class MoondreamModel:
         b = len(plan.order)
         self._select_kernels(b)
         prompts = [list(prompts[i]) for i in plan.order]
+        st = settings.reorder(plan.order) if settings is not None else None  # rows in slot order
+        sampling = Sampling(float(st.temperature), float(st.top_p), st.generator) if st is not None and st.temperature != 0 else None
         self._ensure_batch(plan.n_slots)
         if variants is not None:
             rows = _Rows(variants=self._variant_table([variants[i] for i in plan.order]), bank=self._bank)
@@ -1726,14 +1705,14 @@ class MoondreamModel:
                 rows = self._shared_routing(plan, pos)
                 if sampling is not None:
                     sampling = replace(sampling, row_perm=torch.tensor(plan.copy_rank, dtype=torch.int64, device=self._device))
-        constraint = self._constraint_record(constraints and [constraints[i] for i in plan.order])
-        sampling = self._filter_record(sampling, filters and [filters[i] for i in plan.order])
+        constraint = self._constraint_record(st and st.constraints)
+        sampling = self._filter_record(sampling, st and st.filters)
         out = self._prefill_groups(plan.groups, embed, pos, rows, sampling, logits_capture, scores=scores, hidden_sink=hidden_sink,
                                    constraint=constraint)
         if fused:  # the one pass is both
             mark("image_prefill")
         mark("prompt_prefill")
-        return Prepared(plan.order, *out, rows, sampling, constraint)
+        return Prepared(plan.order, *out, rows, sampling, constraint, self._penalty_record(st and st.penalties))
 
     def _mark(self, marks: list, name: str):
         """Phase timing (``collect_timing``): an event on the current stream, named after the phase that ends there."""
@@ -1894,12 +1873,22 @@ class MoondreamModel:
         """
         if spatial is not None and spatial.n_rows != len(images):
             raise ValueError(f"spatial: a record of {spatial.n_rows} rows for {len(images)} rows")
-        filters = check_filters(top_k, min_p, len(images))
-        top_k = check_top_logprobs(top_logprobs, return_logprobs)
-        b = len(images)
+        if temperature != 0:  # one value for the whole call (a list is a TypeError, as ever)
+            temperature, top_p = float(temperature), float(top_p)
+        st = CallSettings.of(len(images), self._check_automata, max_tokens=max_tokens,
+                             temperature=temperature, top_p=top_p, generator=generator, variant=variant, variants=variants,
+                             return_logprobs=return_logprobs, top_logprobs=top_logprobs, repetition_penalty=repetition_penalty,
+                             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, constraints=constraints,
+                             top_k=top_k, min_p=min_p)
+        return self._generate_ids(images, prompts, st, eos_id, ignore_eos, share_prefix, return_logprobs, spatial)
+
+    def _generate_ids(self, images, prompts: Sequence[Sequence[int]], st: CallSettings, eos_id: Optional[int] = None,
+                      ignore_eos: bool = False, share_prefix: bool = False, return_logprobs: bool = False,
+                      spatial: Optional[SpatialRecord] = None):
+        """``batch_generate_ids`` for a call whose settings are parsed: ``st`` is the call's settings record
+        (moondream_amd/settings.py), one row per image; everything else as there."""
+        b, max_tokens, variant, variants, top_k = len(images), st.max_tokens, st.variant, st.variants, st.top_logprobs
         assert b == len(prompts) and b > 0
-        penalties = check_penalties(repetition_penalty, presence_penalty, frequency_penalty, b)
-        constraints = self._check_constraints_of({"constraints": constraints}, b)
         multi_rows = None
         if variants is not None:
             if variant is not None:
@@ -1916,16 +1905,14 @@ class MoondreamModel:
         mark = lambda name: self._mark(marks, name)
         lora = self._lora({"variant": variant})
         with torch.inference_mode():
-            sampling = None if temperature == 0 else Sampling(float(temperature), float(top_p), generator)
             rows_t = max(0, min(max_tokens, self.config.text.max_context)) + 1  # row 0: the prefill's decision, then the loop's
             scores = Scores.new((rows_t, b), top_k, self._device, fill=True) if return_logprobs else None
             prep = self._prepare_sequences(images, prompts, mark, _Rows(lora=lora), fuse=True, share_prefix=share_prefix,
-                                           variants=multi_rows, encode_settings={"variant": variant}, sampling=sampling,
-                                           scores=scores and scores[0], constraints=constraints, filters=filters, spatial=spatial)
+                                           variants=multi_rows, encode_settings={"variant": variant}, settings=st,
+                                           scores=scores and scores[0], spatial=spatial)
             stop = None if ignore_eos else eos
-            penalty = self._penalty_record(penalties and [penalties[i] for i in prep.order])  # rows in slot order
             hist = self._decode_greedy(prep.first, prep.pos, max_tokens, tk.answer_id, prep.rows, stop, sampling=prep.sampling,
-                                       scores=scores, penalty=penalty, constraint=prep.constraint)
+                                       scores=scores, penalty=prep.penalty, constraint=prep.constraint)
             mark("decode")
             host = scores and scores[: hist.shape[0]].to_host(hist)  # ids, logprobs, ranks, alternatives: ONE copy to the host
             cols = (host.extra[0].T if host else hist.t()).tolist()
@@ -2098,12 +2085,10 @@ class MoondreamModel:
                        beams: Tuple[int, float, bool]) -> List[List[int]]:
         """The string API's beam route: the best hypothesis's ids per request.  ``settings``' ``max_tokens`` applies; what
         beam search does not serve is refused here, what it ignores (temperature, top_p, top_k, min_p: beam rows are
-        deterministic) is checked as ever and unused."""
+        deterministic) was checked with the call's settings and is unused."""
         st = settings or {}
         where = "beam search (num_beams > 1)"
-        refuse_penalties(settings, where, len(images))
-        refuse_constraints(settings, where)
-        check_filters(*filters_of(settings).values(), len(images))
+        refuse_settings(settings, where, ("penalties", "constraints"), len(images))
         if st.get("variant") is not None or st.get("variants") is not None:
             raise ValueError(f"LoRA variant / variants are not served by {where}")
         w, lp, early = beams
@@ -2111,15 +2096,26 @@ class MoondreamModel:
                                           length_penalty=lp, early_stopping=early)
         return [h[0].ids for h in hyps]
 
-    def _string_ids(self, images, prompts: Sequence[Sequence[int]], settings: Optional[dict], **kw) -> List[List[int]]:
-        """The ids behind ``batch_caption`` / ``batch_query`` / ``query_many``: ``batch_generate_ids`` with the settings'
-        sampling arguments (``kw``: its further ones), or, with ``settings["num_beams"]`` > 1, the best beam hypothesis."""
-        beams = beams_of(settings)
-        if beams is not None:
+    def _check_automata(self, constraints, n: int) -> Optional[List[Optional[TokenAutomaton]]]:
+        """``check_constraints`` for this model: its vocabulary, and ``answer_id``, which generation suppresses."""
+        return check_constraints(constraints, n, self.config.text.vocab_size, self.config.tokenizer.answer_id)
+
+    def _settings_of(self, settings: Optional[dict], n: int) -> CallSettings:
+        """The settings record of a string-API call over ``n`` rows (``CallSettings.of_settings``: every check, and last
+        the compilation of a ``regex`` / ``json_schema``): made once, by the public call, before any other GPU work."""
+        return CallSettings.of_settings(settings, n, self._check_automata, self._grammar_constraint)
+
+    def _string_ids(self, images, prompts: Sequence[Sequence[int]], settings: Optional[dict], st: Optional[CallSettings] = None,
+                    **kw) -> List[List[int]]:
+        """The ids behind ``batch_caption`` / ``batch_query`` / ``query_many``: ``_generate_ids`` with the record of
+        ``settings`` (``st``: the caller has made it already; ``kw``: the call's further arguments), or, with
+        ``settings["num_beams"]`` > 1, the best beam hypothesis."""
+        st = st or self._settings_of(settings, len(images))
+        if st.beams is not None:
             if kw.get("spatial") is not None:  # (beam rows are prepared by a route that takes no record)
                 raise ValueError("num_beams > 1 (beam search) is not served with spatial_refs")
-            return self._beam_best_ids(images, prompts, settings, beams)
-        return self.batch_generate_ids(images, prompts, **kw, **self._sampling_kwargs(self._grammar_settings(settings)))
+            return self._beam_best_ids(images, prompts, settings, st.beams)
+        return self._generate_ids(images, prompts, st, **kw)
 
     def batch_generate_ids_continuous(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                                       eos_id: Optional[int] = None, ignore_eos: bool = False, max_live: int = 64, chunk: int = 16,
@@ -2137,10 +2133,6 @@ class MoondreamModel:
         one ``TokenAutomaton`` or one entry per request (None: free), ``batch_generate_ids``' rule and ids per request.
         ``top_k`` / ``min_p``: one value or one per request (None: off), ``batch_generate_ids``' rule per request."""
         from .continuous import ContinuousEngine
-
-        check_penalties(repetition_penalty, presence_penalty, frequency_penalty, len(images))  # before the engine exists
-        check_filters(top_k, min_p, len(images))
-        constraints = self._check_constraints_of({"constraints": constraints}, len(images))
 
         eng = ContinuousEngine(self, max_live, chunk, logprobs=bool(return_logprobs), top_logprobs=top_logprobs)
         return eng.generate(images, prompts, max_tokens, eos_id, ignore_eos, seeds, variant, temperature, top_p,
@@ -2230,12 +2222,13 @@ class MoondreamModel:
         ``batch_generate_ids`` are not served here (ValueError for a non-neutral one): the scorer makes no decode step, so
         there is no history to penalise from -- scores are the model's own.  ``constraints`` likewise (ValueError), and
         ``spatial_refs`` (ValueError: the scorer's prompts carry no encoded references)."""
-        refuse_spatial_refs(spatial_refs, "score_ids / query_choices (the scorer's prompts carry no encoded references)")
+        refuse_settings(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                             constraints=constraints),
+                        {"spatial_refs": "score_ids / query_choices (the scorer's prompts carry no encoded references)",
+                         "constraints": "score_ids (no token is picked: scores are the model's own)",
+                         "penalties": "score_ids (no decode step runs: scores are the model's own)"},
+                        ("spatial_refs", "constraints", "penalties"), len(images), spatial_refs)
         top_k = check_top_logprobs(top_logprobs, True)
-        refuse_constraints({"constraints": constraints}, "score_ids (no token is picked: scores are the model's own)")
-        refuse_penalties(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                              frequency_penalty=frequency_penalty), "score_ids (no decode step runs: scores are the model's own)",
-                         len(images))
         self._check_score_args(images, prompts, continuations)
         conts = [[int(t) for t in c] for c in continuations]
         seqs = [[int(t) for t in p] + c[:-1] for p, c in zip(prompts, conts)]
@@ -2302,11 +2295,13 @@ class MoondreamModel:
         Per batch the result is identical to ``batch_generate_ids`` (same kernels, same order).  The penalty arguments of
         that call are not served here: ValueError for a non-neutral one; nor are ``constraints`` (ValueError), nor ``top_k`` /
         ``min_p`` (ValueError for a non-neutral one: the engine decodes greedily), nor ``spatial_refs`` (ValueError)."""
-        refuse_spatial_refs(spatial_refs, "the pipelined engine (its prefill arena embeds token ids alone)")
-        refuse_filters(dict(top_k=top_k, min_p=min_p), "the pipelined engine (it decodes greedily: there is no sampled row to cut)")
-        refuse_constraints({"constraints": constraints}, "the pipelined engine (its paired decode keeps no automaton states)")
-        refuse_penalties(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                              frequency_penalty=frequency_penalty), "the pipelined engine (its paired decode keeps no histories)")
+        refuse_settings(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                             constraints=constraints, top_k=top_k, min_p=min_p),
+                        {"spatial_refs": "the pipelined engine (its prefill arena embeds token ids alone)",
+                         "filters": "the pipelined engine (it decodes greedily: there is no sampled row to cut)",
+                         "constraints": "the pipelined engine (its paired decode keeps no automaton states)",
+                         "penalties": "the pipelined engine (its paired decode keeps no histories)"},
+                        ("spatial_refs", "filters", "constraints", "penalties"), spatial_refs=spatial_refs)
         return self._pipelined_loop(batches, max_tokens, ignore_eos)
 
     # Round 6: the decode of TWO consecutive batches runs as one lockstep decode (<= 128 sequences) when the library takes that
@@ -2433,29 +2428,6 @@ class MoondreamModel:
             yield [self._truncate(cols[i], eos, max_tokens) for i in range(i0, i0 + n)]
             i0 += n
 
-    def _check_constraints_of(self, settings: Optional[dict], n: int) -> Optional[List[Optional[TokenAutomaton]]]:
-        """``settings["constraints"]`` checked for ``n`` rows (``check_constraints``): host values, before any GPU work --
-        but for ``settings["regex"]`` / ``settings["json_schema"]``, which are compiled (once: ``_grammar_constraint``
-        caches) into the one automaton of every row, after their own argument checks."""
-        constraints = (self._grammar_settings(settings) or {}).get("constraints")
-        if constraints is None:
-            return None
-        return check_constraints(constraints, n, self.config.text.vocab_size, self.config.tokenizer.answer_id)
-
-    @staticmethod
-    def _sampling_kwargs(settings: Optional[dict]) -> dict:
-        """``settings`` of the string API -> keyword arguments of ``batch_generate_ids``, with the REFERENCE'S defaults
-        (moondream.py:50-53, read at :447-457): max_tokens 768, temperature 0.5, top_p 0.3.  ``settings["generator"]`` (an
-        extension) seeds the draws; ``{"temperature": 0}`` is greedy.  ``repetition_penalty`` / ``presence_penalty`` /
-        ``frequency_penalty`` (extensions; one number or one per row) pass through, neutral when absent, and so does
-        ``constraints`` (an extension: one ``TokenAutomaton`` or one entry per row; absent: every row free), and ``top_k`` /
-        ``min_p`` (extensions: one value or one per row; absent: off)."""
-        st = settings or {}
-        return dict(max_tokens=st.get("max_tokens", DEFAULT_MAX_TOKENS), variant=st.get("variant"), variants=st.get("variants"),
-                    temperature=st.get("temperature", DEFAULT_TEMPERATURE), top_p=st.get("top_p", DEFAULT_TOP_P),
-                    generator=st.get("generator"), constraints=st.get("constraints"), **penalties_of(settings),
-                    **filters_of(settings))
-
     def batch_caption(self, images, length: str = "normal", settings: Optional[dict] = None) -> List[str]:
         tpl = self.config.tokenizer.templates["caption"]
         if tpl is None:
@@ -2524,8 +2496,7 @@ class MoondreamModel:
         question's own tokens contain ``coord_id`` / ``size_id``, ``num_beams`` > 1; NotImplementedError: a checkpoint
         without a region head.  Ranges are not checked (the reference checks none)."""
         spatial_refs = refs_of(settings, spatial_refs)
-        if reasoning:
-            refuse_beams(settings, "reasoning queries")
+        if reasoning:  # (what the reasoning route does not serve is refused there: ``_check_reasoning_served``)
             return self._reasoning_answers(self._batch_query_reasoning(images, questions, settings, share_prefix=False,
                                                                        spatial_refs=spatial_refs))
         if spatial_refs is None:
@@ -2536,10 +2507,8 @@ class MoondreamModel:
 
     def _string_ids_spatial(self, images, settings: Optional[dict], built, **kw) -> List[List[int]]:
         """``_string_ids`` of a query with ``spatial_refs``: ``built`` = ``_query_prompts_spatial``'s (prompts, record);
-        beam search is not served with references (ValueError, before any GPU work)."""
+        beam search is not served with references (ValueError, before any GPU work: ``_string_ids``)."""
         prompts, spatial = built
-        if spatial is not None and beams_of(settings) is not None:
-            raise ValueError("num_beams > 1 (beam search) is not served with spatial_refs")
         return self._string_ids(images, prompts, settings, **kw, **({"spatial": spatial} if spatial is not None else {}))
 
     def batch_generate(self, images, prompts: Optional[Sequence[str]] = None, settings: Optional[dict] = None) -> List[str]:
@@ -2580,26 +2549,23 @@ class MoondreamModel:
     def _generate_answer(self, prompt_tokens: torch.Tensor, pos: int, settings: Optional[dict] = None,
                          spatial_refs: Optional[SpatialRefs] = None, eos_id: Optional[int] = None, attn_mask=None,
                          causal: bool = False):
-        """Generator of text pieces.  reference: moondream.py:434-539.  ``settings`` may carry ``repetition_penalty`` /
-        ``presence_penalty`` / ``frequency_penalty`` (``batch_generate_ids``' rule, over this sequence's generated tokens):
-        every step's logits are penalised on the device before its pick, in the chunked greedy loop and in the per-token
-        sampled one alike; and ``constraints`` (one ``TokenAutomaton``: ``batch_generate_ids``' rule for this sequence,
-        the first token included); and ``top_k`` / ``min_p`` (``batch_generate_ids``' rule: a sampled answer's picks,
-        the first included, go through the per-row pick with one row)."""
-        settings = settings or {}
-        max_tokens = settings.get("max_tokens", DEFAULT_MAX_TOKENS)
-        temperature = settings.get("temperature", DEFAULT_TEMPERATURE)
-        top_p = settings.get("top_p", DEFAULT_TOP_P)
-        penalties = check_penalties(*penalties_of(settings).values(), 1)
-        filters = check_filters(*filters_of(settings).values(), 1)
-        automata = self._check_constraints_of(settings, 1)
-        lora = self._lora(settings)
+        """Generator of text pieces.  reference: moondream.py:434-539.  ``settings``: the call's settings record with one
+        row (``caption`` / ``query`` have made it), or, as the reference's own callers give it, the dict it is made from.
+        The penalties (``batch_generate_ids``' rule, over this sequence's generated tokens) act on every step's logits
+        before its pick, in the chunked greedy loop and in the per-token sampled one alike; the constraint masks every
+        pick, the first included; with ``top_k`` / ``min_p`` a sampled answer's picks, the first included, go through the
+        per-row pick with one row."""
+        st = settings if isinstance(settings, CallSettings) else self._settings_of(settings, 1)
+        max_tokens, temperature, top_p = st.max_tokens, st.temperature, st.top_p
+        penalties, filters, automata = st.penalties, st.filters, st.constraints
+        lora = self._lora({"variant": st.variant})
         rows = _Rows(lora=lora)
         eos = eos_id if eos_id is not None else self.config.tokenizer.eos_id
         # decode steps attend to keys [0, pos] only, which both masks allow: the mask matters for the prompt
         with torch.inference_mode():
             constraint = self._constraint_record(automata)  # one state over the whole answer, at its start now
             filt = self._filter_record(Sampling(float(temperature), float(top_p)), filters) if filters and temperature != 0 else None
+        pick = filt or (Sampling(temperature, top_p) if temperature != 0 else None)  # of every token after the first
         _, _, nxt, pos = self._prefill_prompt(prompt_tokens, pos, temperature, top_p, spatial_refs, attn_mask, lora=lora, causal=causal,
                                               constraint=constraint, filt=filt)
 
@@ -2638,12 +2604,10 @@ class MoondreamModel:
                             self._penalize(logits, tok, rows, penalty)
                         if constraint is not None:
                             self._constrain(logits, tok, rows, constraint)
-                        if filt is not None:
-                            tok = self._pick_rows_filtered(logits, filt.temperature, filt.top_p, filt.top_k, filt.min_p,
-                                                           self.config.tokenizer.answer_id,
-                                                           torch.rand(1, device=self._device, dtype=torch.float32))
-                        else:
-                            tok = self._pick(logits, temperature, top_p, self.config.tokenizer.answer_id)  # moondream.py:517
+                        # moondream.py:517.  The call's settings draw inside ``_pick``, per step; a one-row record likewise,
+                        # here: these are the ids a sampled answer has always had
+                        tok = pick_tokens(self, pick, logits, self.config.tokenizer.answer_id,
+                                          torch.rand(1, device=self._device, dtype=torch.float32) if filt is not None else None)
 
         def generator():
             # streaming detokeniser: flush on newline, CJK, or up to the last space
@@ -2685,10 +2649,8 @@ class MoondreamModel:
         """reference: moondream.py:625-651.  ``settings`` may carry ``repetition_penalty`` / ``presence_penalty`` /
         ``frequency_penalty`` (an extension: ``batch_generate_ids``' rule over the caption's generated tokens) and
         ``constraints`` (one ``TokenAutomaton``)."""
-        check_penalties(*penalties_of(settings).values(), 1)  # host values: before any GPU work
-        check_filters(*filters_of(settings).values(), 1)
-        self._check_constraints_of(settings, 1)
-        beams = beams_of(settings)
+        st = self._settings_of(settings, 1)  # every check of the settings: before any other GPU work
+        beams = st.beams
         tpl = self.config.tokenizer.templates["caption"]
         if tpl is None:
             raise NotImplementedError("Model does not support captioning.")
@@ -2701,7 +2663,7 @@ class MoondreamModel:
         enc = self.encode_image(image, settings)
         self.load_encoded_image(enc)
         prompt = torch.tensor([tpl[length]])
-        gen = self._generate_answer(prompt, enc.pos, settings)
+        gen = self._generate_answer(prompt, enc.pos, st)
         return {"caption": gen} if stream else {"caption": "".join(list(gen))}
 
     def query(self, image=None, question: str = None, reasoning: bool = False,
@@ -2709,9 +2671,7 @@ class MoondreamModel:
         """reference: moondream.py:541-618, including the ``reasoning`` branch (thinking token -> _generate_reasoning
         -> answer after a second suffix).  ``settings`` may carry the penalty settings and ``constraints`` as ``caption``'s
         may; not with ``reasoning`` (ValueError)."""
-        check_penalties(*penalties_of(settings).values(), 1)  # host values: before any GPU work
-        check_filters(*filters_of(settings).values(), 1)
-        self._check_constraints_of(settings, 1)
+        st = self._settings_of(settings, 1)  # every check of the settings: before any other GPU work
         tpl = self.config.tokenizer.templates["query"]
         if tpl is None:
             raise NotImplementedError("Model does not support querying.")
@@ -2719,17 +2679,14 @@ class MoondreamModel:
             raise ValueError("question must be provided.")
         if spatial_refs and image is None:
             raise ValueError("spatial_refs can only be used with an image.")
-        beams = beams_of(settings)
-        if beams is not None:  # beam search: the batched route's best hypothesis, as one string
+        if st.beams is not None:  # beam search: the batched route's best hypothesis, as one string
             if reasoning or stream:
                 raise ValueError("num_beams > 1 (beam search) is not served with reasoning=True or stream=True")
             if image is None or spatial_refs:
                 raise ValueError("num_beams > 1 (beam search) is served for a query about an image, without spatial_refs")
             return {"answer": self.batch_query([image], [question], settings)[0]}
         if reasoning:
-            refuse_penalties(settings, "reasoning queries")
-            refuse_constraints(settings, "reasoning queries")
-            refuse_filters(settings, "reasoning queries (the reasoning loop picks with the call's temperature and top-p alone)")
+            self._refuse_for_reasoning(settings)
         if image is not None:
             enc = self.encode_image(image, settings)
             self.load_encoded_image(enc)
@@ -2751,10 +2708,10 @@ class MoondreamModel:
             prompt = prompt + [self.config.tokenizer.thinking_id]
             pos, text, grounding = self._generate_reasoning(torch.tensor([prompt]), pos, settings, spatial_refs, causal=causal)
             extra = {"reasoning": {"text": text, "grounding": grounding}}
-            gen = self._generate_answer(torch.tensor([list(tpl["suffix"])]), pos, settings, None, causal=causal)
+            gen = self._generate_answer(torch.tensor([list(tpl["suffix"])]), pos, st, None, causal=causal)
         else:
             prompt = prompt + list(tpl["suffix"])
-            gen = self._generate_answer(torch.tensor([prompt]), pos, settings, spatial_refs, causal=causal)
+            gen = self._generate_answer(torch.tensor([prompt]), pos, st, spatial_refs, causal=causal)
         return {**extra, "answer": gen} if stream else {**extra, "answer": "".join(list(gen))}
 
     def _generate_reasoning(self, prompt_tokens: torch.Tensor, pos: int, settings: Optional[dict] = None,
@@ -3157,14 +3114,17 @@ class MoondreamModel:
                         "pos": pos_list[r] + len(reasoning)})
         return out
 
+    @staticmethod
+    def _refuse_for_reasoning(settings: Optional[dict]) -> None:
+        """What no reasoning query serves, the one-image ``query(reasoning=True)`` and the batched ones alike: ValueError."""
+        refuse_settings(settings, {None: "reasoning queries", "filters": "reasoning queries (the reasoning loop picks with the "
+                                   "call's temperature and top-p alone)"})
+
     def _check_reasoning_served(self, settings: Optional[dict]) -> None:
         """What the batched reasoning query does not serve raises NotImplementedError, naming the reason (ValueError for
         the penalty settings: a reasoning row's logits are masked per phase inside its own step)."""
         st = settings or {}
-        refuse_penalties(settings, "reasoning queries")
-        refuse_constraints(settings, "reasoning queries")
-        refuse_filters(settings, "reasoning queries (the reasoning loop picks with the call's temperature and top-p alone)")
-        refuse_beams(settings, "reasoning queries")
+        self._refuse_for_reasoning(settings)
         if st.get("variant") is not None or st.get("variants") is not None:
             raise NotImplementedError("batched reasoning queries are not served with LoRA variants (variant / variants): "
                                       "use query(reasoning=True) per image")
@@ -3193,9 +3153,7 @@ class MoondreamModel:
         spatial = built
         if spatial is None and spatial_refs is not None:
             spatial = self._reasoning_prompts_spatial(images, questions, spatial_refs)
-        st = settings or {}
-        max_tokens = st.get("max_tokens", DEFAULT_MAX_TOKENS)
-        temperature, top_p = st.get("temperature", DEFAULT_TEMPERATURE), st.get("top_p", DEFAULT_TOP_P)
+        st = self._settings_of(settings, len(images))  # (what is left of them: everything else was refused above)
         # moondream.py:586-603: [prefix | question | suffix | thinking]
         prompts = [list(tpl["prefix"]) + list(self.tokenizer.encode(q).ids) + list(tpl["suffix"]) + [tk.thinking_id] for q in questions]
         if spatial is not None:
@@ -3203,12 +3161,10 @@ class MoondreamModel:
         marks: list = []
         mark = lambda name: self._mark(marks, name)
         with torch.inference_mode():
-            sampling = None if temperature == 0 else Sampling(float(temperature), float(top_p), st.get("generator"))
-            prep = self._prepare_sequences(images, prompts, mark, fuse=True, share_prefix=share_prefix, sampling=sampling,
-                                           spatial=spatial)
+            prep = self._prepare_sequences(images, prompts, mark, fuse=True, share_prefix=share_prefix, settings=st, spatial=spatial)
             if forced is not None:
                 forced = forced.to(self._device)[:, torch.tensor(prep.order, device=self._device)]
-            res = self._reason_loop(prep.hidden_last, prep.first, prep.next_pos, prep.rows, max_tokens, prep.sampling, forced)
+            res = self._reason_loop(prep.hidden_last, prep.first, prep.next_pos, prep.rows, st.max_tokens, prep.sampling, forced)
             mark("reason_loop")
         self._phase_times(marks)
         return prep.in_caller_order(res)
@@ -3266,10 +3222,9 @@ class MoondreamModel:
     def _check_detect_settings(self, settings: Optional[dict], kind: str) -> Optional[int]:
         """The host checks of every detect / point call, before any GPU work: penalties are not served, and the score
         settings (``check_score_settings``) -> the score window, None without ``return_scores``."""
-        refuse_penalties(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
-        refuse_constraints(settings, f"{kind}: its loop decodes coordinates, not tokens picked from logits")
-        refuse_filters(settings, f"{kind}: its loop decodes coordinates, not tokens sampled from logits")
-        refuse_beams(settings, f"{kind}: its loop decodes coordinates, not token hypotheses")
+        refuse_settings(settings, {None: f"{kind}: its loop decodes coordinates, not tokens picked from logits",
+                                   "filters": f"{kind}: its loop decodes coordinates, not tokens sampled from logits",
+                                   "beams": f"{kind}: its loop decodes coordinates, not token hypotheses"})
         return check_score_settings(settings, self.config.region.coord_out_dim)
 
     def batch_detect(self, images, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
@@ -3306,18 +3261,15 @@ class MoondreamModel:
         built = None
         if spatial_refs is not None:  # (built and checked, like everything below, before the image is encoded)
             built = self._query_prompts_spatial([image] * len(questions), questions, spatial_refs)
-            if built[1] is not None and beams_of(settings) is not None:
-                raise ValueError("num_beams > 1 (beam search) is not served with spatial_refs")
         prompts = built[0] if built is not None else self._query_prompts(questions)
-        check_penalties(*penalties_of(settings).values(), len(prompts))  # host values: before any GPU work
-        check_filters(*filters_of(settings).values(), len(prompts))
-        self._check_constraints_of(settings, len(prompts))
-        beams_of(settings)  # (checked before the image is encoded)
+        st = self._settings_of(settings, len(prompts))
+        if built is not None and built[1] is not None and st.beams is not None:
+            raise ValueError("num_beams > 1 (beam search) is not served with spatial_refs")
         enc = self.encode_image(image, settings)
         if built is not None:
-            ids = self._string_ids_spatial([enc] * len(prompts), settings, built, share_prefix=True)
+            ids = self._string_ids_spatial([enc] * len(prompts), settings, built, st=st, share_prefix=True)
         else:
-            ids = self._string_ids([enc] * len(prompts), prompts, settings, share_prefix=True)
+            ids = self._string_ids([enc] * len(prompts), prompts, settings, st, share_prefix=True)
         return [{"answer": self.tokenizer.decode(s)} for s in ids]
 
     def query_many_reasoning(self, image, questions: Sequence[str], settings: Optional[dict] = None, spatial_refs=None) -> List[dict]:
@@ -3344,7 +3296,8 @@ class MoondreamModel:
         "best": argmax of logprobs, "best_normalized": argmax of mean_logprobs}`` (ties: the first choice).  The
         log-probabilities are ``score_ids``': the model's own distribution at temperature 1, untruncated.  ``spatial_refs``
         are not served here (ValueError)."""
-        refuse_spatial_refs(refs_of(settings, spatial_refs), "score_ids / query_choices (the scorer's prompts carry no encoded references)")
+        refuse_settings(settings, "score_ids / query_choices (the scorer's prompts carry no encoded references)", ("spatial_refs",),
+                        spatial_refs=spatial_refs)
         choices = list(choices)
         if not choices:
             raise ValueError("query_choices: no choices")

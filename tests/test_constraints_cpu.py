@@ -18,6 +18,7 @@ from moondream_amd.constraint import (DEAD, FORBID, FREE, TokenAutomaton, check_
 from moondream_amd.continuous import Request, SlotScheduler
 from moondream_amd.decode_loop import Constraint, run_chunk
 from moondream_amd.hf_moondream import HfMoondream
+from moondream_amd.settings import RowSettings
 from test_decode_chunk_cpu import N, STREAM, assert_calls, expected_calls, make_chunk
 from test_logprobs_cpu import IMG, PREFIX, FakeEngine, FakeModel, host_model
 from test_penalties_cpu import PenaltyRecorder, expected_with_penalty
@@ -292,7 +293,8 @@ def test_scheduler_resets_a_refilled_slots_state():
     limits = [6, 3, 9, 2, 5]
     starts = [100, FREE, 200, 300, FREE]
     for rid, (n, st) in enumerate(zip(limits, starts)):
-        s.submit(Request(rid, IMG, [5], n, None, constraint=None if st == FREE else TokenAutomaton.sequence([1]), constraint_start=st))
+        s.submit(Request(rid, IMG, [5], n, None, settings=RowSettings(constraint=None if st == FREE else TokenAutomaton.sequence([1])),
+                         constraint_start=st))
     spare = 2
     state = np.full(3, 777, dtype=np.int64)  # slot 0, slot 1, the spare entry
     refills = 0
@@ -310,7 +312,7 @@ def test_scheduler_resets_a_refilled_slots_state():
         assert (idx[len(plan.rows) :] == spare).all() and (val[len(plan.rows) :] == FREE).all()
         state[idx] = val
         for r in plan.rows:
-            assert state[r.slot] == (FREE if r.constraint is None else r.constraint_start + r.steps), (r.rid, state)
+            assert state[r.slot] == (FREE if r.settings.constraint is None else r.constraint_start + r.steps), (r.rid, state)
         for row in plan.slots:  # a step of the stand-in automaton: a constrained state counts its tokens
             live = row[row >= 0]
             state[live] += state[live] >= 0
@@ -329,11 +331,11 @@ def test_engine_takes_a_constraint_per_request_and_packs_each_automaton_once():
     eng.submit(IMG, [5], max_tokens=2, constraint=a)
     eng.submit_caption(IMG, max_tokens=2, constraint=b)
     eng.submit_query(IMG, "5 6", max_tokens=2, constraint=a)
-    assert [(r.constraint, r.constraint_start) for r in eng.sched.queue] == [(None, FREE), (a, 0), (b, 3), (a, 0)]
+    assert [(r.settings.constraint, r.constraint_start) for r in eng.sched.queue] == [(None, FREE), (a, 0), (b, 3), (a, 0)]
     assert eng._con_used == [4, 5] and eng._con_pending == [a, b]
     list(eng.run())
     seen = []
-    eng._step = lambda plan: seen.extend((r.constraint, r.constraint_start) for r in plan.rows) or np.zeros((plan.n, plan.bucket), dtype=np.int32)
+    eng._step = lambda plan: seen.extend((r.settings.constraint, r.constraint_start) for r in plan.rows) or np.zeros((plan.n, plan.bucket), dtype=np.int32)
     eng.generate([IMG] * 2, [[5]] * 2, max_tokens=3, ignore_eos=True, constraints=[b, None])
     assert seen[:2] == [(b, 3), (None, FREE)] and eng._con_used == [4, 5]
     with pytest.raises(ValueError):

@@ -6,6 +6,7 @@ from PIL import Image
 
 from moondream_amd.config import get_config
 from moondream_amd.continuous import DEFAULT_TOP_P, ContinuousEngine, Request, SlotScheduler
+from moondream_amd.settings import RowSettings
 
 PREFIX = 730
 
@@ -59,12 +60,12 @@ def test_submit_defaults_to_the_engines_settings_and_accepts_the_edges():
     eng.submit(IMG, [5], temperature=0)              # greedy beside the engine's sampled default
     eng.submit(IMG, [5], temperature=2.5, top_p=1)   # top_p = 1 is inside (0, 1]
     eng.submit_caption(IMG, top_p=0.25)
-    got = [(r.temperature, r.top_p) for r in eng.sched.queue]
+    got = [(r.settings.temperature, r.settings.top_p) for r in eng.sched.queue]
     assert got == [(0.7, 0.9), (0.0, 0.9), (2.5, 1.0), (0.7, 0.25)]
     assert all(isinstance(x, float) for pair in got for x in pair)
     plain = FakeEngine(FakeModel(), max_live=2)
     plain.submit(IMG, [5])
-    assert (plain.sched.queue[0].temperature, plain.sched.queue[0].top_p) == (0.0, DEFAULT_TOP_P)
+    assert (plain.sched.queue[0].settings.temperature, plain.sched.queue[0].settings.top_p) == (0.0, DEFAULT_TOP_P)
 
 
 def test_generate_takes_one_setting_or_one_per_request():
@@ -76,10 +77,10 @@ def test_generate_takes_one_setting_or_one_per_request():
         assert not eng.sched.pending()  # nothing was queued
     temps = [0.0, 0.5, 4.0, 1.0, 0.0]
     ids = eng.generate([IMG] * n, [[5, 6]] * n, max_tokens=4, ignore_eos=True, temperature=temps, top_p=0.8)
-    assert sorted((r.rid, r.temperature, r.top_p) for r in eng.admitted) == [(i, temps[i], 0.8) for i in range(n)]
+    assert sorted((r.rid, r.settings.temperature, r.settings.top_p) for r in eng.admitted) == [(i, temps[i], 0.8) for i in range(n)]
     assert ids == [[stream(i, k) for k in range(4)] for i in range(n)]
     eng.generate([IMG] * 2, [[5]] * 2, max_tokens=2, ignore_eos=True, temperature=np.float32(0.5))
-    assert [(r.temperature, r.top_p) for r in eng.admitted] == [(0.5, DEFAULT_TOP_P)] * 2
+    assert [(r.settings.temperature, r.settings.top_p) for r in eng.admitted] == [(0.5, DEFAULT_TOP_P)] * 2
     # a bad value inside a sequence is the submit's ValueError
     with pytest.raises(ValueError):
         eng.generate([IMG] * 2, [[5]] * 2, max_tokens=2, temperature=[0.5, -1.0])
@@ -109,5 +110,5 @@ def test_plans_do_not_depend_on_the_settings():
         return log, done
 
     base = plans(lambda i: {})
-    mixed = plans(lambda i: {"temperature": [0.0, 0.5, 4.0][i % 3], "top_p": [0.3, 1.0][i % 2]})
+    mixed = plans(lambda i: {"settings": RowSettings(temperature=[0.0, 0.5, 4.0][i % 3], top_p=[0.3, 1.0][i % 2])})
     assert base == mixed and len(base[0]) > 4

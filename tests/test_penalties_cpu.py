@@ -252,12 +252,12 @@ def test_engine_takes_the_settings_per_request():
     eng = FakeEngine(FakeModel(), max_live=2, chunk=4)
     eng.submit(IMG, [5], max_tokens=2)
     eng.submit(IMG, [5], max_tokens=2, repetition_penalty=1.3, frequency_penalty=-0.5)
-    assert [r.penalties for r in eng.sched.queue] == [PENALTY_NEUTRAL, (1.3, 0.0, -0.5)]
+    assert [r.settings.penalties for r in eng.sched.queue] == [PENALTY_NEUTRAL, (1.3, 0.0, -0.5)]
     list(eng.run())
     eng.generate([IMG] * 3, [[5]] * 3, max_tokens=0, presence_penalty=[0.0, 1.0, 0.0], repetition_penalty=2)
     eng2 = FakeEngine(FakeModel(), max_live=2, chunk=4)
     seen = []
-    eng2._step = lambda plan: seen.extend(r.penalties for r in plan.rows) or np.zeros((plan.n, plan.bucket), dtype=np.int32)
+    eng2._step = lambda plan: seen.extend(r.settings.penalties for r in plan.rows) or np.zeros((plan.n, plan.bucket), dtype=np.int32)
     eng2.generate([IMG] * 2, [[5]] * 2, max_tokens=3, ignore_eos=True, presence_penalty=[0.0, 1.0], repetition_penalty=2)
     assert seen[:2] == [(2.0, 0.0, 0.0), (2.0, 1.0, 0.0)]
 

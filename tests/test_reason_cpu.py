@@ -202,22 +202,23 @@ def test_reasoning_refusals_name_their_reason():
 
 
 def test_batch_query_without_reasoning_is_the_old_call():
-    """reasoning=False: the same call into batch_generate_ids as before and a list of strings back."""
+    """reasoning=False: the same call into the generation route as before (``_generate_ids``, with the settings' record) and a
+    list of strings back."""
     model = stub_model()
     seen = {}
 
-    def fake_ids(images, prompts, **kw):
-        seen["prompts"], seen["kw"] = prompts, kw
+    def fake_ids(images, prompts, st, **kw):
+        seen["prompts"], seen["st"], seen["kw"] = prompts, st, kw
         return [[11, 12], [13]]
 
-    model.batch_generate_ids = fake_ids
+    model._generate_ids = fake_ids
     model.tokenizer = types.SimpleNamespace(encode=lambda q: types.SimpleNamespace(ids=[int(t) for t in q.split()]),
                                             decode=lambda ids: " ".join(str(i) for i in ids))
     for kw in ({}, {"reasoning": False}):
         out = model.batch_query([object(), object()], ["5 6", "7"], settings={"temperature": 0}, **kw)
         assert out == ["11 12", "13"] and all(isinstance(s, str) for s in out)
         assert seen["prompts"] == [[1, 381, 2, 5, 6, 3, 3], [1, 381, 2, 7, 3, 3]]  # suffix twice: no thinking token
-        assert seen["kw"]["temperature"] == 0 and "reasoning" not in seen["kw"]
+        assert seen["st"].temperature == 0 and len(seen["st"].rows) == 2 and "reasoning" not in seen["kw"]
 
 
 # ---------------------------------------------------------------- the chunk runner's reasoning branch

@@ -143,10 +143,10 @@ def test_engine_takes_the_settings_per_request():
     eng.submit(IMG, [5], max_tokens=2)
     eng.submit(IMG, [5], max_tokens=2, temperature=0.5, top_k=40, min_p=0.1)
     eng.submit(IMG, [5], max_tokens=2, top_k=40)  # greedy: accepted, and no filtered row
-    assert [(r.top_k, r.min_p, r.filtered) for r in eng.sched.queue] == [(0, 0.0, False), (40, 0.1, True), (40, 0.0, False)]
+    assert [(r.settings.top_k, r.settings.min_p, r.settings.filtered) for r in eng.sched.queue] == [(0, 0.0, False), (40, 0.1, True), (40, 0.0, False)]
     eng2 = FakeEngine(FakeModel(), max_live=2, chunk=4)
     seen = []
-    eng2._step = lambda plan: seen.extend((r.top_k, r.min_p) for r in plan.rows) or np.zeros((plan.n, plan.bucket), dtype=np.int32)
+    eng2._step = lambda plan: seen.extend((r.settings.top_k, r.settings.min_p) for r in plan.rows) or np.zeros((plan.n, plan.bucket), dtype=np.int32)
     eng2.generate([IMG] * 2, [[5]] * 2, max_tokens=3, ignore_eos=True, top_k=[0, 7], min_p=0.25)
     assert seen[:2] == [(0, 0.25), (7, 0.25)]
 
