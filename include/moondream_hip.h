@@ -474,7 +474,7 @@ md_status md_sample_rows_filtered(const void* logits, int64_t ld, int32_t batch,
  *     0 exactly when t is what md_argmax_bf16 returns for the row (ties go to the lowest id).
  *   t outside [0, vocab) (idle / padding rows): logprob[r] = NaN, rank[r] = -1, the logits row is not read.
  *   t the suppressed token of a suppressed row: logprob[r] = -inf, rank[r] = -1.
- * Two passes (max, then sum) in a summation order that depends on vocab alone (csrc/sampling_region.hip).  Plain loads: no
+ * Two passes (max, then sum) in a summation order that depends on vocab alone (csrc/logprobs.hip).  Plain loads: no
  * vocab % 8 / ld % 8 requirement.  No host sync, no allocation: capturable.  rows == 0: MD_OK, nothing launched.
  * MD_ERR_INVALID_ARG: NULL logits / targets / logprob, rows < 0, vocab <= 0, ld < vocab. */
 md_status md_token_logprobs(const void* logits, int64_t ld, int32_t rows, int32_t vocab, int32_t suppress_id,
@@ -490,7 +490,7 @@ md_status md_token_logprobs(const void* logits, int64_t ld, int32_t rows, int32_
  *   gate (int32 [rows], or NULL: every row): row r is computed iff 0 <= gate[r] < vocab -- the step's token, as targets gate
  *     md_token_logprobs.  A gated-off row is not read; its k entries are -1 / NaN.
  *   A row with fewer than k live tokens: the remaining entries are -1 / NaN.  A NaN logit is out of contract.
- * Selection by a two-level radix select over the 16-bit keys of the bf16 logits (csrc/sampling_region.hip), not k arg-max
+ * Selection by a two-level radix select over the 16-bit keys of the bf16 logits (csrc/logprobs.hip), not k arg-max
  * passes.  Plain loads: no vocab % 8 / ld % 8 requirement.  No host sync, no allocation: capturable.  rows == 0: MD_OK, nothing
  * launched.  MD_ERR_INVALID_ARG: NULL logits / top_ids / top_logprobs, k < 1, k > MD_TOPK_MAX, rows < 0, vocab < 1, ld < vocab. */
 #define MD_TOPK_MAX 32
@@ -513,7 +513,7 @@ md_status md_topk_logprobs(const void* logits, int64_t ld, int32_t rows, int32_t
  *     in fp32, every operation rounded on its own (no fused multiply-add), then logit[v] = bf16(x), round to nearest even.
  *     Each distinct token is updated exactly once however often it occurs; a -inf logit stays -inf.
  * Cost: the history's tokens are read once and one logit per distinct token is loaded and stored -- the row is never scanned
- * (an LDS hash table finds each distinct token with its count: csrc/sampling_region.hip).  Plain loads: no vocab % 8 / ld % 8
+ * (an LDS hash table finds each distinct token with its count: csrc/logits_edit.hip).  Plain loads: no vocab % 8 / ld % 8
  * requirement.  The values in the three arrays are the caller's contract (finite, repetition > 0).  No host sync, no
  * allocation: capturable.  batch == 0: MD_OK, nothing launched.
  * MD_ERR_INVALID_ARG: NULL logits / tokens_in / hist / hist_len / repetition / presence / frequency, batch < 0, vocab < 1,
@@ -543,7 +543,7 @@ md_status md_penalize_rows(void* logits, int64_t ld, int32_t batch, int32_t voca
  *     MD_CONSTRAINT_FORBID.  Every other bit of the row is unchanged; columns [vocab, ld) are never written.
  * Cost: the logits are never loaded.  A default-allow state stores 2 bytes per listed forbidden token.  A default-forbid
  * state builds a vocab-bit map of its allowed tokens in LDS and sweeps the row with stores alone, 16 bytes at a time
- * wherever a whole 16-byte-aligned group is forbidden (csrc/sampling_region.hip).  No vocab % 8 / ld % 8 requirement.  No
+ * wherever a whole 16-byte-aligned group is forbidden (csrc/logits_edit.hip).  No vocab % 8 / ld % 8 requirement.  No
  * host sync, no allocation: capturable.  batch == 0: MD_OK, nothing launched.
  * MD_ERR_INVALID_ARG: NULL logits / state / row_ptr / default_next / edge_tok / edge_next, batch < 0, vocab < 1, ld < vocab,
  * state_cap < 1, vocab > MD_CONSTRAIN_VOCAB_MAX (the bit map lives in 32 KiB of LDS). */
@@ -620,7 +620,7 @@ md_status md_region_pick_encode(const void* logits, int64_t ld, int32_t batch, i
  * nothing; nothing else of emb is written (plain vector stores, 8 bytes each); the caller keeps the dst values distinct.
  * A token's result depends on its values and the operands alone -- not on n, its index in the table, dst or the other
  * descriptors: a workgroup owns 16 descriptors and 64 columns (an encoder row is fetched once per 16 tokens) and sums in an
- * order fixed by *_feat (csrc/sampling_region.hip).  No host sync, no allocation: capturable.
+ * order fixed by *_feat (csrc/region.hip).  No host sync, no allocation: capturable.
  * MD_ERR_INVALID_ARG: a NULL pointer, n <= 0, rows <= 0, dim <= 0 or dim % 4, ld < dim or ld % 4, a *_feat <= 0, % 8 or
  * > 2048, a *_ldw < *_feat or % 4, desc not 16-byte or an encoder / bias / emb pointer not 8-byte aligned. */
 md_status md_spatial_ref_embed(const int32_t* desc, int32_t n, const void* coord_fw, int32_t coord_feat,
@@ -637,7 +637,7 @@ md_status md_spatial_ref_embed(const int32_t* desc, int32_t n, const void* coord
  *   the log-softmax of the picked bin.  window >= n_bins - 1: W and S are one sum and the value is exactly 0.0f.  A -inf logit
  *   adds 0.  A NaN anywhere in the group, or a group whose maximum is not finite, gives NaN for that group.
  * One workgroup per row, a row's result independent of the rows beside it; the summation order depends on n_bins alone
- * (csrc/sampling_region.hip).  Plain loads: no alignment demand on n_bins, ld, ld_bins or ld_logprobs.  No host sync, no
+ * (csrc/region.hip).  Plain loads: no alignment demand on n_bins, ld, ld_bins or ld_logprobs.  No host sync, no
  * allocation: capturable.
  * MD_ERR_INVALID_ARG: what md_region_pick_encode refuses, NULL logprobs, window < 0, ld_logprobs < n_groups. */
 md_status md_region_pick_encode_scored(const void* logits, int64_t ld, int32_t batch, int32_t n_groups,

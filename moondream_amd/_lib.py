@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libmoondream_hip.so")
-SOURCES = ["gemm_bf16.hip", "gemm_w4.hip", "gemm_fp8w.hip", "gemm_f8.hip", "quant_f8.hip", "attention_f8kv.hip", "decode_b1.hip", "attention.hip", "elementwise.hip", "sampling_region.hip", "beam.hip", "preprocess.hip", "lora_multi.hip", "automaton.hip", "api.hip"]
+SOURCES = ["gemm_bf16.hip", "gemm_w4.hip", "gemm_fp8w.hip", "gemm_f8.hip", "quant_f8.hip", "attention_f8kv.hip", "decode_b1.hip", "attention.hip", "elementwise.hip", "region.hip", "sampling.hip", "logprobs.hip", "logits_edit.hip", "beam.hip", "preprocess.hip", "lora_multi.hip", "automaton.hip", "api.hip"]
 
 MD_OK = 0
 ABI_VERSION = 5  # include/moondream_hip.h MD_ABI_VERSION
@@ -343,7 +343,7 @@ def hipcc_path() -> str:
 def build_library(force: bool = False, verbose: bool = True) -> str:
     """Compile csrc/*.hip for gfx950 into moondream_amd/libmoondream_hip.so."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("md_common.hpp", "gemm_internal.hpp", "text_internal.hpp")] + [os.path.join(REPO, "include", "moondream_hip.h")]
+    deps = srcs + [os.path.join(CSRC, h) for h in ("md_common.hpp", "gemm_internal.hpp", "text_internal.hpp", "row_reduce.hpp")] + [os.path.join(REPO, "include", "moondream_hip.h")]
     if not force and os.path.exists(LIB_PATH):
         if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps + [os.path.abspath(__file__)]):
             return LIB_PATH

@@ -1209,7 +1209,7 @@ extern "C" md_status md_decode_step_multi_lora(const md_text_model* m, const md_
   return decode_step_impl(m, tokens, next, pos, batch, rows, kv, suppress_id, logits, ld_logits, workspace, workspace_bytes, stream);
 }
 
-// ------------------------------------------------------------- reasoning queries in lockstep (csrc/sampling_region.hip)
+// ------------------------------------------------------------- reasoning queries in lockstep (csrc/logits_edit.hip)
 namespace {
 struct ReasonWs {
   void *ff, *logits, *feats, *coord_emb, *splitk;

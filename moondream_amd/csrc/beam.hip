@@ -1,7 +1,7 @@
 // Beam search on the device (include/moondream_hip.h: md_beam_select, md_kv_copy_tail): the group phase of the choice --
 // merge of the beams' ranked candidates, the walk that feeds the pool of finished hypotheses and picks the next beams, the
 // done rule and the KV slot hand-off -- and the copy that moves a surviving beam's KV tail to its child's slot.  The row
-// phase (every beam's 2W best continuations) is md_topk_logprobs' device function, launched from sampling_region.hip.
+// phase (every beam's 2W best continuations) is md_topk_logprobs' device function, launched from logprobs.hip.
 #include "text_internal.hpp"
 
 namespace {

@@ -2,6 +2,7 @@
 // + KV-slab write, token embedding gather, greedy argmax, crop stitch + pool.
 // All of them move 16 bytes per lane per access (8 bf16) and do their
 // arithmetic in fp32 with exactly one rounding to bf16 per reference op.
+#include "row_reduce.hpp"
 #include "text_internal.hpp"
 
 #include <algorithm>
@@ -365,35 +366,14 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const bf16_t* __restrict__
       const int idx = ch * 8 + e;
       float v = (e & 1) ? hi_bf(q[e >> 1]) : lo_bf(q[e >> 1]);
       if (idx == suppress) v = -INFINITY;
-      if (v > best || (v == best && idx < bi)) {
-        best = v;
-        bi = idx;
-      }
+      argmax_take(best, bi, v, idx);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) {
-      best = ov;
-      bi = oi;
-    }
-  }
-  if ((threadIdx.x & 63) == 0) {
-    sv[threadIdx.x >> 6] = best;
-    si[threadIdx.x >> 6] = bi;
-  }
-  __syncthreads();
+  // an all-NaN row selects nothing: id 0 rather than an out-of-range id that the next md_embed_tokens would use as a
+  // table index (block_argmax, row_reduce.hpp)
+  bi = block_argmax<16>(best, bi, vocab, sv, si);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < 16; ++w)
-      if (sv[w] > best || (sv[w] == best && si[w] < bi)) {
-        best = sv[w];
-        bi = si[w];
-      }
-    // an all-NaN row selects nothing: fall back to id 0 rather than an out-of-range id that the
-    // next md_embed_tokens would use as a table index
-    next[b] = (bi >= vocab) ? 0 : bi;
+    next[b] = bi;
     if (pos_inc) pos_inc[b] += 1;
   }
 }

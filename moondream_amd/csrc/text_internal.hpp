@@ -69,10 +69,10 @@ md_status md_stitch_pool_batched(const void* feats, void* out, int64_t ld_out, i
                                  int32_t dim, int32_t grid, int32_t margin, int32_t tiles_h, int32_t tiles_w, hipStream_t stream);
 md_status md_pool_grid_concat(const void* global_feats, const void* grid_feats, int32_t H, int32_t W, void* out, int64_t ld_out,
                               int32_t dim, int32_t grid, hipStream_t stream);
-// sampling_region.hip: md_mask_logits_rows that also advances pos (pos == nullptr: the public form)
+// logits_edit.hip: md_mask_logits_rows that also advances pos (pos == nullptr: the public form)
 md_status md_mask_logits_advance(void* logits, int64_t ld, int32_t batch, int32_t vocab, const int32_t* ids, int32_t* pos,
                                  hipStream_t stream);
-// sampling_region.hip: the row phase of md_beam_select (csrc/beam.hip) -- md_topk_logprobs' entries, k = 2 * num_beams, for
+// logprobs.hip: the row phase of md_beam_select (csrc/beam.hip) -- md_topk_logprobs' entries, k = 2 * num_beams, for
 // every live beam (the kernel that shares md_topk_logprobs' device function)
 md_status md_beam_rows(const void* logits, int64_t ld, int32_t rows, int32_t vocab, int32_t suppress_id,
                        const int32_t* suppress_rows, int32_t num_beams, int32_t beams_in, const float* cum, const int32_t* done,

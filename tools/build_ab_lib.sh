@@ -14,7 +14,10 @@ for f in $FILES; do git show $REV:moondream_amd/csrc/$f > $D/csrc/$f; done
 grep -q md_gemm_w4_residual_max_cols $D/csrc/gemm_w4.hip || echo 'int md_gemm_w4_residual_max_cols() { return 1 << 30; }' >> $D/csrc/gemm_w4.hip
 sed -i 's|#include "../../include/moondream_hip.h"|#include "'$PWD'/include/moondream_hip.h"|' $D/csrc/md_common.hpp
 objs=""
-for f in gemm_bf16 gemm_w4 gemm_fp8w attention elementwise sampling_region api; do
+# the translation units of the checked-out tree: _lib.SOURCES, the list build_library() compiles
+SOURCES=$(sed -n 's/^SOURCES = \[\(.*\)\]$/\1/p' moondream_amd/_lib.py | tr -d '",')
+[ -n "$SOURCES" ] || { echo "no SOURCES list in moondream_amd/_lib.py" >&2; exit 1; }
+for f in ${SOURCES//.hip/}; do
   extra="-mllvm -amdgpu-mfma-vgpr-form"; [ $f = gemm_w4 ] && extra=""
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast $extra -c $D/csrc/$f.hip -o $D/$f.o &
   objs="$objs $D/$f.o"
