@@ -594,6 +594,43 @@ md_status md_automaton_fill(const int32_t* trans, const uint8_t* accept, int32_t
                             const int32_t* default_next, const int32_t* row_ptr, int32_t* edge_tok, int32_t* edge_next,
                             int64_t edge_cap, void* ws, size_t ws_bytes, void* stream);
 
+/* Stop strings and stop token ids: every row feeds the token it just produced to its own matcher, and the first match is
+ * recorded in the row's result triple (csrc/stop.hip).  One thread per row; a row's result is independent of the rows beside it.
+ * tokens int32 [batch]: the tokens just picked.  Row r uses the words of slot s = slots ? slots[r] : slot0 + r (two live
+ * rows of one launch never share one).  All arrays are the caller's device arrays.
+ * The table, any number of stop sets' automata concatenated (moondream_amd/stop.py: pack): trans uint16 [state_cap][256] --
+ *   a complete byte-level Aho-Corasick DFA, goto and failure links folded in, so every (state, byte) has a next state;
+ *   match_len uint16 [state_cap]: the length of the longest stop string that is a suffix of the state's path, 0: none;
+ *   match_id int32 [state_cap]: that string's index in its stop set.  An entry of trans >= state_cap reads as state 0.
+ * The rows' stop ids: row s lists ids[id_ptr[s] .. id_ptr[s + 1]) (id_ptr int32 [n_slots + 1]; at most MD_STOP_IDS_MAX of
+ *   them are read; an entry of -1 matches nothing) and id_base int32 [n_slots] is the `which` of its first id (the number of
+ *   strings of its stop set).
+ * The vocabulary: token v spells tok_bytes[tok_off[v] .. tok_off[v + 1]) (tok_off int32 [vocab + 1], tok_bytes uint8 [n_bytes]:
+ *   the layout md_automaton_lift reads).  A token outside [0, vocab), or a byte range outside [0, n_bytes], spells nothing.
+ *   Both NULL: every token spells nothing (stop sets of ids alone).
+ * Per slot, int32 [n_slots] each: state (the row's DFA state; negative: the row has no stop set), n_tok and n_seen (the
+ *   tokens and bytes it has seen), and the result triple at / keep / which -- at is -1 until a match.
+ *   s < 0 (idle row) or state[s] < 0: nothing of the row is read or written.
+ *   Otherwise, with v = tokens[r], nt = n_tok[s], nb = n_seen[s]:  n_tok[s] = nt + 1 and n_seen[s] = nb + len(v) ALWAYS; and
+ *   while at[s] == -1:
+ *     1. v is the j-th of the row's stop ids:  at = nt, keep = nb, which = id_base[s] + j; no byte is walked.
+ *     2. otherwise v's bytes are walked through trans from state[s], and state[s] becomes the state reached.  At the FIRST
+ *        byte i (0-based) after which match_len[q] > 0:  at = nt, keep = nb + i + 1 - match_len[q], which = match_id[q] --
+ *        the earliest end, and among the strings ending at that byte the longest.  The walk stops there: state[s] is
+ *        the state q of the match, and it is not read again.
+ *   A row whose at[s] >= 0 only counts.  A token of zero bytes leaves the state alone.
+ * Cost: a chain of dependent trans loads, one per byte of the row's token; the bytes are fetched 16 at a time in front of
+ * it and match_len is read beside it.  Integers only.  No host sync, no allocation: capturable.  batch == 0: MD_OK, nothing launched.
+ * MD_ERR_INVALID_ARG: NULL tokens / trans / match_len / match_id / id_ptr / ids / id_base or a NULL state word array,
+ * batch < 0, state_cap outside [1, MD_STOP_STATES_MAX], one of tok_off / tok_bytes NULL alone, and with them vocab < 1 or n_bytes < 0. */
+#define MD_STOP_STATES_MAX 4096
+#define MD_STOP_IDS_MAX 16
+md_status md_stop_rows(const int32_t* tokens, int32_t batch, const int32_t* slots, int32_t slot0, const uint16_t* trans,
+                       const uint16_t* match_len, const int32_t* match_id, int32_t state_cap, const int32_t* id_ptr,
+                       const int32_t* ids, const int32_t* id_base, const int32_t* tok_off, const uint8_t* tok_bytes,
+                       int32_t vocab, int64_t n_bytes, int32_t* state, int32_t* n_tok, int32_t* n_seen, int32_t* at,
+                       int32_t* keep, int32_t* which, void* stream);
+
 /* Region head, device resident (reference: region.py:12-71 inside the loop of moondream.py:653-733).
  * md_fourier_features: out[r] = [cos(f) | sin(f)], f = bf16(bf16(2 pi x[r, :in_dim]) . w[in_dim][half])
  *   (region.py:12-29; in_dim 1 for coordinates, 2 for sizes) -- the input of coord_encoder /

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libmoondream_hip.so")
-SOURCES = ["gemm_bf16.hip", "gemm_w4.hip", "gemm_fp8w.hip", "gemm_f8.hip", "quant_f8.hip", "attention_f8kv.hip", "decode_b1.hip", "attention.hip", "elementwise.hip", "region.hip", "sampling.hip", "logprobs.hip", "logits_edit.hip", "beam.hip", "preprocess.hip", "lora_multi.hip", "automaton.hip", "api.hip"]
+SOURCES = ["gemm_bf16.hip", "gemm_w4.hip", "gemm_fp8w.hip", "gemm_f8.hip", "quant_f8.hip", "attention_f8kv.hip", "decode_b1.hip", "attention.hip", "elementwise.hip", "region.hip", "sampling.hip", "logprobs.hip", "logits_edit.hip", "beam.hip", "preprocess.hip", "lora_multi.hip", "automaton.hip", "stop.hip", "api.hip"]
 
 MD_OK = 0
 ABI_VERSION = 5  # include/moondream_hip.h MD_ABI_VERSION
@@ -29,6 +29,7 @@ MD_TOPK_MAX = 32  # md_topk_logprobs: the most alternatives per decision
 MD_PENALTY_HIST_MAX = 4096  # md_penalize_rows: the longest history per row
 MD_CONSTRAIN_VOCAB_MAX = 262144  # md_constrain_rows: the largest vocabulary (its bit map lives in LDS)
 MD_AUTOMATON_STATES_MAX, MD_AUTOMATON_SLAB = 4096, 256  # md_automaton_*: the largest DFA; the states lifted at a time
+MD_STOP_STATES_MAX, MD_STOP_IDS_MAX = 4096, 16  # md_stop_rows: the largest stop table; the most stop ids read per row
 MD_RESAMPLE_DESC_WORDS, MD_RESAMPLE_MAX_SIDE = 32, 16384  # md_image_resample_crops: int64 words per image; the longest side
 MD_BEAM_MAX = 16  # md_beam_select: the most beams per request (2 * MD_BEAM_MAX candidates per beam = MD_TOPK_MAX)
 
@@ -256,6 +257,8 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_size_t, c_void_p]),
     "md_automaton_fill": (C.c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "md_stop_rows": (C.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "md_kv_copy_tail": (C.c_int, [P(MdKvCache), c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "md_beam_select": (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
                                  P(MdBeamState), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

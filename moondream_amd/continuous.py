@@ -26,7 +26,9 @@ from typing import Callable, Deque, Dict, Iterator, List, Optional, Sequence, Tu
 import numpy as np
 
 from .constraint import FREE, TokenAutomaton, check_constraints, grammar_of, pack
-from .decode_loop import PENALTY_NEUTRAL, Constraint, DecodeChunk, Penalty, Sampling, check_top_logprobs, run_chunk
+from . import stop as stops
+from .stop import Finish
+from .decode_loop import PENALTY_NEUTRAL, Constraint, DecodeChunk, Penalty, Sampling, Stop, check_top_logprobs, run_chunk
 from .scores import HostScores, Scores
 from .settings import CallSettings, RowSettings
 from .spatial import SpatialRecord, check_spatial_refs, spatial_prompt_ids
@@ -37,6 +39,7 @@ MAX_GRAPHS = 16  # captured decode chunks per (model, stream)
 IDLE_SLOT = -1
 MD_PENALTY_HIST_MAX = 4096  # include/moondream_hip.h
 DEFAULT_CONSTRAINT_STATES = 4096   # the engine's constraint table: states ...
+DEFAULT_STOP_STATES = 1024         # the engine's stop table: DFA states over all the distinct stop sets its requests ever use
 DEFAULT_CONSTRAINT_EDGES = 65536   # ... and edges, over all the distinct automata its requests ever use
 
 
@@ -81,6 +84,10 @@ class Request:
     alternatives: List[list] = field(default_factory=list)  # of ``ids`` too: k (token_id, logprob) pairs each (top_logprobs=k)
     constraint_start: int = FREE  # the start state of its automaton in the engine's table
     spatial: Optional[Tuple[int, list]] = None  # (position of the first placeholder in ``prompt``, the checked refs); None: no refs
+    stop_start: int = stops.NO_STOP  # the root of its stop set's automaton in the engine's table (``settings.stop``)
+    include_stop_str: bool = False   # ``Finish.text_bytes`` counts the matched string too
+    stop_hit: Optional[Tuple[int, int, int]] = None  # the matcher's (at, keep, which) after the prefill's token
+    finish: Optional[Finish] = None  # how it ended, set when it retires
 
     @property
     def remaining(self) -> int:
@@ -123,8 +130,9 @@ class SlotScheduler:
 
     Admission: when at least ``admit_threshold`` slots are free, or nothing is live, the head of the queue takes free slots
     (a freed slot goes to the back of the free list: slots are reused first-in first-out).  A request retires when it
-    emits its ``eos_id`` (not part of its ids), when its ids reach ``max_tokens``, or when its next position reaches
-    ``max_context - 1``."""
+    emits its ``eos_id`` (not part of its ids), when its ids reach ``max_tokens``, when its next position reaches
+    ``max_context - 1``, or at the first match of its stop set (``commit``'s ``stop`` arrays, ``Request.stop_hit`` for the
+    prefill's token): in front of a stop id, behind the token a stop string completed in.  ``Request.finish`` says which."""
 
     def __init__(self, max_live: int, max_context: int, chunk: int = 16, admit_threshold: Optional[int] = None):
         if chunk < 1:
@@ -170,7 +178,15 @@ class SlotScheduler:
         req.last = int(first)
         if req.max_tokens <= 0 or (req.eos_id is not None and first == req.eos_id):
             req.ids = []
-            return self._retire(req)
+            return self._retire(req, Finish("length" if req.max_tokens <= 0 else "eos"))
+        if req.stop_hit is not None and req.stop_hit[0] == 0:  # the first token is a stop id, or completes a stop string
+            req.ids = []
+            fin = self._stopped(req, int(first), *req.stop_hit[1:])
+            if req.ids and logprob is not None:  # a stop string's token stays, with its scores
+                req.logprobs, req.ranks = [float(logprob)], [int(rank)]
+            if req.ids and alternatives is not None:
+                req.alternatives = [HostScores(logprob, rank, *alternatives).alternatives()]
+            return self._retire(req, fin)
         req.ids = [int(first)]
         if logprob is not None:
             req.logprobs, req.ranks = [float(logprob)], [int(rank)]
@@ -181,7 +197,19 @@ class SlotScheduler:
         self.live.append(req)
         return False
 
-    def _retire(self, req: Request) -> bool:
+    @staticmethod
+    def _stopped(req: Request, tok: int, keep: int, which: int) -> Finish:
+        """The request matched its stop set in token ``tok``: a stop string's token joins the ids (a token cannot be split),
+        a stop id does not (like eos).  Returns its ``Finish``."""
+        s = req.settings.stop
+        if which < len(s.strings):
+            req.ids.append(int(tok))
+            text = s.strings[which]
+            return Finish("stop", text, int(keep) + (len(text.encode("utf-8")) if req.include_stop_str else 0))
+        return Finish("stop", s.named(which))
+
+    def _retire(self, req: Request, finish: Optional[Finish] = None) -> bool:
+        req.finish = finish or Finish("length")
         req.done = True
         if req in self.live:
             self.live.remove(req)
@@ -230,8 +258,12 @@ class SlotScheduler:
 
     def commit(self, plan: ChunkPlan, out: np.ndarray, logprobs: Optional[np.ndarray] = None,
                ranks: Optional[np.ndarray] = None, top_ids: Optional[np.ndarray] = None,
-               top_logprobs: Optional[np.ndarray] = None) -> List[Request]:
-        """``out[i][r]``: the token row r produced in step i (``logprobs[i][r]`` / ``ranks[i][r]``: its values, and
+               top_logprobs: Optional[np.ndarray] = None,
+               stop: Optional[Tuple[np.ndarray, np.ndarray, np.ndarray]] = None) -> List[Request]:
+        """``stop`` = the chunk's (at, keep, which) arrays [bucket], row r's matcher result after the chunk (``at`` -1: no
+        match yet; the index counts the request's generated tokens, the prefill's being 0): a request whose ``at`` falls
+        inside the chunk retires there -- an eos in the same token wins, as in the lockstep call -- and its slot returns
+        to the pool.  ``out[i][r]``: the token row r produced in step i (``logprobs[i][r]`` / ``ranks[i][r]``: its values, and
         ``top_ids[i][r]`` / ``top_logprobs[i][r]`` [k]: the decision's alternatives, appended in step with the ids; idle and
         padding rows are never read).  Advances every row, retires the finished ones (their slots return to the pool) and
         returns them in row order."""
@@ -241,14 +273,24 @@ class SlotScheduler:
         finished = []
         host = HostScores(logprobs, ranks, top_ids, top_logprobs)
         for r_idx, r in enumerate(plan.rows):
-            fin = False
+            fin = None
+            at = int(stop[0][r_idx]) if stop is not None and r.settings.stop is not None else -1
+            g0 = len(r.ids)  # the generated index of the chunk's first token (nothing was cut so far: no eos, no match)
             for i in range(min(plan.n, r.remaining)):
                 tok = int(out[i][r_idx])
                 r.steps += 1
                 r.pos += 1
                 r.last = tok
                 if r.eos_id is not None and tok == r.eos_id:
-                    fin = True
+                    fin = Finish("eos")
+                    break
+                if at == g0 + i:
+                    fin = self._stopped(r, tok, int(stop[1][r_idx]), int(stop[2][r_idx]))
+                    if logprobs is not None and len(r.ids) > len(r.logprobs):  # a string's token keeps its scores
+                        r.logprobs.append(float(logprobs[i][r_idx]))
+                        r.ranks.append(int(ranks[i][r_idx]))
+                    if top_ids is not None and len(r.ids) > len(r.alternatives):
+                        r.alternatives.append(host.alternatives((i, r_idx)))
                     break
                 r.ids.append(tok)
                 if logprobs is not None:
@@ -257,10 +299,10 @@ class SlotScheduler:
                 if top_ids is not None:
                     r.alternatives.append(host.alternatives((i, r_idx)))
                 if r.steps >= r.step_limit:
-                    fin = True
+                    fin = Finish("length")
                     break
-            if fin:
-                self._retire(r)
+            if fin is not None:
+                self._retire(r, fin)
                 finished.append(r)
         return finished
 
@@ -269,7 +311,8 @@ class SlotScheduler:
         """Drive the schedule: ``admit(requests)`` prefills them and returns (first token, next position) per request,
         ``step(plan)`` runs a chunk and returns its tokens [n, bucket].  With log-probabilities: (first token, next position,
         logprob, rank) and (tokens, logprobs, ranks); with alternatives one more element, (top ids [k], top logprobs [k]),
-        and two more planes [n, bucket, k].  Yields requests in completion order."""
+        and two more planes [n, bucket, k].  A last element that is a dict holds ``commit``'s keyword arguments (``stop``).
+        Yields requests in completion order."""
         while self.pending():
             adm = self.take_admissions()
             if adm:
@@ -280,7 +323,8 @@ class SlotScheduler:
             if plan is None:
                 continue
             res = step(plan)
-            yield from (self.commit(plan, *res) if isinstance(res, tuple) else self.commit(plan, res))
+            res, kw = (res[:-1], res[-1]) if isinstance(res, tuple) and isinstance(res[-1], dict) else (res, {})
+            yield from (self.commit(plan, *res, **kw) if isinstance(res, tuple) else self.commit(plan, res, **kw))
 
 
 class ContinuousEngine:
@@ -333,11 +377,23 @@ class ContinuousEngine:
     first token included.  They are stored per row next to temperature and top-p, in a per-bucket pair of fixed-address
     tables (int32 / fp32, pinned staging: one more small copy each) that only chunks with a filtered row fill; such
     chunks pick with md_sample_rows_filtered and are graphs of their own, all others are the chunks of an engine without
-    the settings.  A request's ids depend on its own settings and seed only."""
+    the settings.  A request's ids depend on its own settings and seed only.
+
+    ``stop`` / ``stop_token_ids`` / ``include_stop_str_in_output`` per request (``submit``): ``batch_generate_ids``' rule,
+    ids and ``Finish`` per request (``Request.finish``, ``finishes``).  The engine owns ONE table of ``stop_states`` DFA
+    states for its lifetime, to which each distinct stop set (by its strings) is appended on first use -- room is taken at
+    ``submit`` (ValueError when the table is full) -- and six words, sixteen ids and an id base per KV SLOT, all made on
+    first use.  At admission, once the engine has seen a stop set, every admitted slot's words are reset (a request
+    without one gets a negative state: skipped) and ONE md_stop_rows launch feeds the prefill's tokens; chunks with a
+    row that has a stop set run md_stop_rows after each pick and are graphs of their own, all others take the graph of
+    an engine without stops.  The rows' (at, keep, which) come back in the chunk's copy of the ids, and
+    ``SlotScheduler.commit`` retires a request at its ``at``: the KV slot goes to the next queued request instead of
+    decoding to ``max_tokens``.  Stop strings need the bytes of every id: ONE vocabulary object per engine."""
 
     def __init__(self, model, max_live: int = 64, chunk: int = 16, temperature: float = 0.0, top_p: float = DEFAULT_TOP_P,
                  admit_threshold: Optional[int] = None, logprobs: bool = False, top_logprobs: Optional[int] = None,
-                 constraint_states: int = DEFAULT_CONSTRAINT_STATES, constraint_edges: int = DEFAULT_CONSTRAINT_EDGES):
+                 constraint_states: int = DEFAULT_CONSTRAINT_STATES, constraint_edges: int = DEFAULT_CONSTRAINT_EDGES,
+                 stop_states: int = DEFAULT_STOP_STATES):
         self.model = model
         self.logprobs = bool(logprobs)
         self.top_logprobs = check_top_logprobs(top_logprobs, self.logprobs)
@@ -357,6 +413,15 @@ class ContinuousEngine:
         self._con_pending: List[TokenAutomaton] = []  # registered, rows not yet on the device (in table order)
         self._con_uploaded = [0, 0]
         self._con_table = None     # (row_ptr, default_next, edge_tok, edge_next, state int32 [max_live + 1]), made on first use
+        if not 1 <= int(stop_states) <= stops.MD_STOP_STATES_MAX:
+            raise ValueError(f"stop_states must be in 1 .. {stops.MD_STOP_STATES_MAX}")
+        self.stop_states = int(stop_states)
+        self._stop_start: Dict[tuple, int] = {}  # a stop set's strings -> the root of its automaton in the table
+        self._stop_used = 0
+        self._stop_pending: List[Tuple[int, stops.PackedStops]] = []  # registered, states not yet on the device
+        self._stop_dev = None      # (trans int16, match_len int16, [match_id | id_ptr | ids | id_base | words] int32), made on first use
+        self._stop_vocab = None    # the ONE vocabulary object whose bytes the engine's stop strings are matched in
+        self.finishes: Dict[int, Finish] = {}  # rid -> how it ended, filled by ``run``
         self._penalty_hist = None  # (hist int32 [max_live + 1, max_context], hist_len int32 [max_live + 1]), made on first use
 
     @property
@@ -370,8 +435,12 @@ class ContinuousEngine:
                presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
                constraint: Optional[TokenAutomaton] = None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                spatial: Optional[Tuple[int, list]] = None, regex: Optional[str] = None, json_schema: Optional[dict] = None,
-               vocab_bytes: Optional[Sequence[bytes]] = None) -> int:
-        """Queue one request; ``image`` is a PIL image or an EncodedImage.  ``eos_id`` None: the tokenizer's EOS
+               vocab_bytes: Optional[Sequence[bytes]] = None, stop=None, stop_token_ids=None,
+               include_stop_str_in_output: bool = False) -> int:
+        """``stop`` (a str or a list of str) / ``stop_token_ids`` (a list of ids) / ``include_stop_str_in_output``:
+        ``batch_generate_ids``' rule and validation for one row (``vocab_bytes`` spells the ids for stop strings where the
+        tokenizer spells none); ValueError when the engine's stop table has no room for the set.
+        Queue one request; ``image`` is a PIL image or an EncodedImage.  ``eos_id`` None: the tokenizer's EOS
         (``ignore_eos``: none).  ``temperature`` / ``top_p`` None: the engine's.  The three penalties (None: neutral):
         one number each, ``batch_generate_ids``' rule and validation.  ``constraint``: one ``TokenAutomaton`` (None: free),
         ``batch_generate_ids``' rule and validation; ValueError when the engine's table has no room for it.  ``regex`` /
@@ -391,9 +460,11 @@ class ContinuousEngine:
             if isinstance(x, (list, tuple)):
                 raise ValueError(f"{name}: one value per request, not {x!r}")
         row = CallSettings.of(1, None, temperature=temp, top_p=tp, repetition_penalty=repetition_penalty,
-                              presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, top_k=top_k, min_p=min_p).rows[0]
+                              presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, top_k=top_k, min_p=min_p,
+                              stop=stop, stop_token_ids=stop_token_ids, include_stop_str_in_output=include_stop_str_in_output,
+                              vocab_size=self.model.config.text.vocab_size).rows[0]
         return self._enqueue(image, prompt_ids, max_tokens, eos_id, seed, ignore_eos, variant, replace(row, constraint=constraint),
-                             spatial, found, vocab_bytes)
+                             spatial, found, vocab_bytes, include_stop_str_in_output)
 
     def _draw_settings(self, temperature, top_p) -> Tuple[float, float]:
         """A request's temperature and top-p (None: the engine's), in range: ValueError otherwise."""
@@ -406,7 +477,8 @@ class ContinuousEngine:
         return temp, tp
 
     def _enqueue(self, image, prompt_ids: Sequence[int], max_tokens: int, eos_id: Optional[int], seed: Optional[int],
-                 ignore_eos: bool, variant: Optional[str], row: RowSettings, spatial=None, grammar=None, vocab_bytes=None) -> int:
+                 ignore_eos: bool, variant: Optional[str], row: RowSettings, spatial=None, grammar=None, vocab_bytes=None,
+                 include_stop_str: bool = False) -> int:
         """Queue one request whose settings are parsed (``row``: its record; ``grammar``: ``grammar_of``'s pair, compiled
         here into the record's automaton): the checks of the request itself, then, last, what takes room in the engine's
         constraint table.  Returns its id."""
@@ -427,11 +499,22 @@ class ContinuousEngine:
         vidx = -1 if variant is None else self._variant_index(variant)
         if grammar is not None:  # (after every other check: this one compiles on the device)
             row = replace(row, constraint=self.model._grammar_constraint(*grammar, vocab_bytes))
+        if row.stop is not None and row.stop.strings:  # (host only) the ONE vocabulary the engine's stop strings are spelled in
+            spell = self.model._vocab_bytes("stop", vocab_bytes)
+            if self._stop_vocab is not None and self._stop_vocab is not spell:
+                raise ValueError("stop: one vocab_bytes object per engine (its stop strings are matched in one vocabulary)")
+        if row.stop is not None:
+            self._check_stop_room(row.stop)
         start = FREE if row.constraint is None else self._register_constraint(row.constraint)  # (last: nothing fails after it)
+        stop_start = stops.NO_STOP
+        if row.stop is not None:
+            stop_start = self._register_stop(row.stop)
+            if row.stop.strings:
+                self._stop_vocab = spell
         rid = self._next_rid
         self._next_rid += 1
         self.sched.submit(Request(rid, image, prompt, int(max_tokens), eos, seed, variant=vidx, settings=row, constraint_start=start,
-                                  spatial=spatial))
+                                  spatial=spatial, stop_start=stop_start, include_stop_str=bool(include_stop_str)))
         return rid
 
     def _register_constraint(self, a: TokenAutomaton) -> int:
@@ -452,6 +535,88 @@ class ContinuousEngine:
         self._con_used = [states + a.n_states, edges + a.n_edges]
         self._con_pending.append(a)
         return states
+
+    def _check_stop_room(self, s: stops.StopSet) -> None:
+        """ValueError when the engine's stop table cannot take ``s`` (host values only; nothing is taken)."""
+        if s.strings in self._stop_start:
+            return
+        n = int(s.dfa()[1].shape[0])
+        if self._stop_used + n > self.stop_states:
+            raise ValueError(f"the engine's stop table is full: {self._stop_used} + {n} states of {self.stop_states} "
+                             "(ContinuousEngine(stop_states=))")
+
+    def _register_stop(self, s: stops.StopSet) -> int:
+        """The root of ``s``'s automaton in the engine's table, taking room for it on first use (by its strings: the ids
+        play no part in the automaton; a set of ids alone is the one-state automaton)."""
+        known = self._stop_start.get(s.strings)
+        if known is not None:
+            return known
+        self._check_stop_room(s)
+        t = stops.pack([s], self._stop_used)
+        self._stop_start[s.strings] = self._stop_used
+        self._stop_pending.append((self._stop_used, t))
+        self._stop_used += t.n_states
+        return self._stop_start[s.strings]
+
+    def _stop_record(self):
+        """The engine's stop table and per-slot words as a ``Stop`` record (``by_slot``), made on first use; the states of
+        stop sets registered since the last call are appended first, by small pinned copies behind the stream.  Slot
+        ``max_live`` is a spare nobody decodes in.  Row s's ids are ``ids[16 s .. 16 s + 16)``, -1 where it has fewer."""
+        import torch
+
+        m = self.model
+        n = self.max_live + 1
+        if self._stop_dev is None:
+            cap, k = self.stop_states, stops.STOP_IDS_MAX
+            i32 = torch.zeros(cap + (n + 1) + n * k + n + 6 * n, dtype=torch.int32, device=m.device)
+            mid, ptr, ids, base, words = torch.split(i32, [cap, n + 1, n * k, n, 6 * n])
+            mid.fill_(-1)
+            ptr.copy_(torch.arange(n + 1, dtype=torch.int32, device=m.device) * k)
+            ids.fill_(-1)
+            words = words.view(6, n)
+            words[0].fill_(stops.NO_STOP)
+            words[3].fill_(-1)
+            self._stop_dev = (torch.zeros(cap * 256, dtype=torch.int16, device=m.device),
+                              torch.zeros(cap, dtype=torch.int16, device=m.device), mid, ptr, ids, base, words)
+        trans, mlen, mid, ptr, ids, base, words = self._stop_dev
+        for s0, t in self._stop_pending:
+            up = lambda dst, at, src: dst[at : at + src.size].copy_(m._h2d(torch.from_numpy(np.ascontiguousarray(src).reshape(-1))))
+            up(trans, s0 * 256, t.trans.view(np.int16))
+            up(mlen, s0, t.match_len.view(np.int16))
+            up(mid, s0, t.match_id)
+        self._stop_pending = []
+        tok_off = tok_bytes = None
+        vocab = n_bytes = 0
+        if self._stop_vocab is not None:
+            tok_off, tok_bytes, n_bytes = m._vocab_on_device(self._stop_vocab)
+            vocab = m.config.text.vocab_size
+        return Stop(trans, mlen, mid, ptr, ids, base, tok_off, tok_bytes, vocab, n_bytes, words, self.stop_states, by_slot=True)
+
+    def _admit_stops(self, rows: List[Request], first, table):
+        """At admission, after the first tokens are picked: every admitted slot's matcher words are reset to its request's
+        (root state or NO_STOP, nothing seen, nothing matched; its ids and id base beside them) by one pinned copy and
+        three index copies on the stream, then ONE md_stop_rows launch feeds ``first`` (int32 [len(rows)], ``table``: the
+        rows' routing).  Returns the rows' (at, keep, which) as a device tensor [3, len(rows)] for the admission's host copy."""
+        import torch
+
+        m = self.model
+        rec = self._stop_record()
+        k, n = stops.STOP_IDS_MAX, len(rows)
+        host = np.zeros((7 + k, n), dtype=np.int32)  # [words (6) | id base | ids (k)] per column
+        host[7:] = -1
+        for c, r in enumerate(rows):
+            s = r.settings.stop
+            host[0, c], host[3, c], host[5, c] = r.stop_start, -1, -1
+            if s is not None:
+                host[6, c] = len(s.strings)
+                host[7 : 7 + len(s.token_ids), c] = s.token_ids
+        dev = m._h2d(torch.from_numpy(host))
+        idx = table.slots.to(torch.int64)
+        rec.words.index_copy_(1, idx, dev[:6])
+        rec.id_base.index_copy_(0, idx, dev[6])
+        rec.ids.view(-1, k).index_copy_(0, idx, dev[7:].t().contiguous())
+        m._stop_rows(first, table, rec)
+        return rec.words[3:6].index_select(1, idx)
 
     def _variant_index(self, variant: str) -> int:
         """The bank index of a LoRA variant the model can resolve (registered, or in the on-disk cache); ValueError otherwise,
@@ -509,6 +674,7 @@ class ContinuousEngine:
         with torch.inference_mode():
             self._prepare_run()
             for r in self.sched.run(self._admit, self._step):
+                self.finishes[r.rid] = r.finish
                 if not with_logprobs:
                     yield r.rid, list(r.ids)
                 else:
@@ -541,8 +707,14 @@ class ContinuousEngine:
         return _Rows(slots=slots, n_slots=self.max_live, variants=variants, bank=self.model._bank if variants is not None else None)
 
     def run_text(self) -> Iterator[Tuple[int, str]]:
+        """``run`` as text: the tokenizer's decoding of the ids; a request that stopped on a stop STRING returns the bytes
+        of its ids cut to ``Finish.text_bytes``, decoded as UTF-8 with ``errors="replace"``."""
         for rid, ids in self.run():
-            yield rid, self.model.tokenizer.decode(ids)
+            f = self.finishes.get(rid)
+            if f is not None and f.text_bytes is not None:
+                yield rid, stops.cut_text([self._stop_vocab[t] for t in ids], f).decode("utf-8", errors="replace")
+            else:
+                yield rid, self.model.tokenizer.decode(ids)
 
     def generate(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                  eos_id: Optional[int] = None, ignore_eos: bool = False, seeds: Optional[Sequence[Optional[int]]] = None,
@@ -552,8 +724,12 @@ class ContinuousEngine:
                  presence_penalty: Union[None, float, Sequence[float]] = None,
                  frequency_penalty: Union[None, float, Sequence[float]] = None,
                  constraints: Union[None, TokenAutomaton, Sequence[Optional[TokenAutomaton]]] = None,
-                 top_k: Union[None, int, Sequence[int]] = None, min_p: Union[None, float, Sequence[float]] = None):
-        """Ids for (images[i], prompts[i]) in input order; ``max_tokens`` one int or one per request, ``temperature`` and
+                 top_k: Union[None, int, Sequence[int]] = None, min_p: Union[None, float, Sequence[float]] = None,
+                 stop=None, stop_token_ids=None, include_stop_str_in_output: bool = False, vocab_bytes=None,
+                 return_finish: bool = False):
+        """``stop`` / ``stop_token_ids``: one value for every request or one entry per request, ``batch_generate_ids``'
+        forms and rule; ``return_finish`` appends the requests' ``Finish`` records, in input order, to the return value.
+        Ids for (images[i], prompts[i]) in input order; ``max_tokens`` one int or one per request, ``temperature`` and
         ``top_p`` one float or one per request (None: the engine's), the three penalties likewise (None: neutral),
         ``constraints`` one ``TokenAutomaton`` or one entry per request (None: free), ``top_k`` / ``min_p`` one value or
         one per request (None: off).  ``return_logprobs`` (an engine made with
@@ -583,13 +759,19 @@ class ContinuousEngine:
         st = CallSettings.of(n, lambda c, k: check_constraints(c, k, cfg.text.vocab_size, cfg.tokenizer.answer_id),
                              temperature=[d[0] for d in draws], top_p=[d[1] for d in draws], repetition_penalty=repetition_penalty,
                              presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, constraints=constraints,
-                             top_k=top_k, min_p=min_p)
-        rids = [self._enqueue(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant, st.rows[i]) for i in range(n)]
+                             top_k=top_k, min_p=min_p, stop=stop, stop_token_ids=stop_token_ids,
+                             include_stop_str_in_output=include_stop_str_in_output, vocab_size=cfg.text.vocab_size)
+        for s in dict.fromkeys(r.stop for r in st.rows if r.stop is not None):  # every request is checked before the first is queued
+            if s.strings:
+                self.model._vocab_bytes("stop", vocab_bytes)
+        rids = [self._enqueue(images[i], prompts[i], mt[i], eos_id, seeds[i], ignore_eos, variant, st.rows[i],
+                              vocab_bytes=vocab_bytes, include_stop_str=st.include_stop_str) for i in range(n)]
+        ends = lambda: ([self.finishes[r] for r in rids],) if return_finish else ()
         if return_logprobs:  # (ids, logprobs, ranks), and alternatives on an engine with top_logprobs
             got3 = {rid: rest for rid, *rest in self.run(with_logprobs=True)}
-            return tuple([got3[r][k] for r in rids] for k in range(4 if self.top_logprobs else 3))
+            return tuple([got3[r][k] for r in rids] for k in range(4 if self.top_logprobs else 3)) + ends()
         got = dict(self.run())
-        return [got[r] for r in rids]
+        return ([got[r] for r in rids],) + ends() if return_finish else [got[r] for r in rids]
 
     # ---- the GPU side of the schedule
     def _generator(self, r: Request):
@@ -676,12 +858,20 @@ class ContinuousEngine:
         first, _, next_pos = m._prefill_groups(groups, embed, starts, routes, pick, scores=scores, constraint=con,
                                                uniforms=st[2] if st is not None else None, head_rows=64)
         self.stats.prefill_passes += len(groups)
+        # once the engine has seen a stop set every admitted slot's matcher is reset, and the first tokens go through it
+        trip = self._admit_stops(rows, first, table) if self._stop_start else None
+        ride = (first,) if trip is None else (first, trip)
         if scores is None:
-            picked = [(f,) for f in first.tolist()]
+            flat = (first if trip is None else torch.cat([first, trip.reshape(-1)])).tolist()
+            picked = [(f,) for f in flat[: len(rows)]]
+            hits = np.asarray(flat[len(rows) :], dtype=np.int64).reshape(3, len(rows)) if trip is not None else None
         else:
-            host = scores.to_host(first)  # the tokens and their scores in one copy
+            host = scores.to_host(*ride)  # the tokens, the matchers' results and the scores in one copy
             top = [zip(host.top_ids, host.top_logprobs)] if self.top_logprobs else []
             picked = list(zip(host.extra[0].tolist(), host.logprob.tolist(), host.rank.tolist(), *top))
+            hits = host.extra[1] if trip is not None else None
+        for c, r in enumerate(rows):
+            r.stop_hit = tuple(int(x) for x in hits[:, c]) if hits is not None and r.settings.stop is not None else None
         started = {r: (int(f[0]), pos) + tuple(f[1:]) for r, f, pos in zip(rows, picked, next_pos)}
         return [started[r] for r in reqs]
 
@@ -853,6 +1043,9 @@ class ContinuousEngine:
             con.state.index_copy_(0, i_dev, v_dev)
             if any(r.settings.constrained for r in plan.rows):
                 constraint = con
+        stop = None
+        if any(r.settings.stop is not None for r in plan.rows):  # (their words were reset at admission)
+            stop = self._stop_record()
         scores = self._score_buffers(B) if self.logprobs else None  # (an idle or padding row's are never read: SlotScheduler.commit)
         # step i's routing: row i of the slot table; a LoRA row in the chunk: the chunk's row-variant table with it
         rows_of = lambda i: self._rows(slots_d[i], var_d if lora else None)
@@ -862,13 +1055,19 @@ class ContinuousEngine:
         if filt is not None:  # ... and a filtered row: the launch that also cuts by each row's top_k / min_p
             pick = replace(pick, top_k=filt[0], min_p=filt[1])
         chunk = DecodeChunk(B, hist, pos_d, rows_of, m.config.tokenizer.answer_id, self._decode_ws_bytes(B), pick,
-                            u_dev[: c * B].view(c, B), penalty=penalty, constraint=constraint,
+                            u_dev[: c * B].view(c, B), penalty=penalty, constraint=constraint, stop=stop,
                             **(scores.chunk_fields() if scores else {}))
         stream = torch.cuda.current_stream(m.device).cuda_stream if m.use_graphs else None
         if run_chunk(m, chunk, n, "continuous", stream, lambda: m._store.count("continuous", stream) < MAX_GRAPHS):
             self.stats.graph_captures += 1
-        out = hist[1 : n + 1].cpu().numpy()  # the chunk's D2H copy of the ids (the lockstep loop syncs here too)
+        kw = ()
+        if stop is None:
+            out = hist[1 : n + 1].cpu().numpy()  # the chunk's D2H copy of the ids (the lockstep loop syncs here too)
+        else:  # ... with the rows' (at, keep, which) behind them: step 0's slot table names every live row's slot
+            trip = stop.words[3:6].index_select(1, slots_d[0].to(torch.int64).clamp_(min=0))
+            flat = torch.cat([hist[1 : n + 1].reshape(-1), trip.reshape(-1)]).cpu().numpy()
+            out, kw = flat[: n * B].reshape(n, B), ({"stop": tuple(flat[n * B :].reshape(3, B))},)
         if scores is None:
-            return out
+            return (out,) + kw if kw else out
         host = scores[:n].to_host()  # ... and one more of the chunk's scores
-        return (out, host.logprob, host.rank) + ((host.top_ids, host.top_logprobs) if self.top_logprobs else ())
+        return (out, host.logprob, host.rank) + ((host.top_ids, host.top_logprobs) if self.top_logprobs else ()) + kw

@@ -2,7 +2,7 @@
 share: the description of a chunk of consecutive decode steps over fixed buffers, and the one runner that launches it.
 ``run_chunk`` holds the only step body of the package -- decode step (or, for a reasoning query, the reasoning step), then
 the optional penalty launch, then the optional constraint launch, then the optional sampling pick, then the optional
-log-probability launch and the optional top-k launch; or, for beam search, decode step, beam selection, KV tail copy -- and the only decode graph key.  No torch here: the runner moves no data, it orders launches."""
+stop-matcher launch, then the optional log-probability launch and the optional top-k launch; or, for beam search, decode step, beam selection, KV tail copy -- and the only decode graph key.  No torch here: the runner moves no data, it orders launches."""
 from __future__ import annotations
 
 import math
@@ -207,6 +207,42 @@ class Constraint:
 
 
 @dataclass(frozen=True, eq=False)
+class Stop:
+    """The stop-string / stop-id state of a chunk (md_stop_rows), all device memory at fixed addresses.  ``trans`` (uint16
+    [state_cap, 256]), ``match_len`` (uint16 [state_cap]) and ``match_id`` (int32 [state_cap]) are the packed table of the
+    call's stop sets (moondream_amd/stop.py: ``pack``).  ``id_ptr`` (int32 [n + 1]), ``ids`` and ``id_base`` (int32 [n])
+    are the rows' stop ids.  ``tok_off`` (int32 [vocab + 1]) / ``tok_bytes`` (uint8 [n_bytes]) spell the vocabulary (None:
+    stop sets of ids alone need no bytes).  ``words`` (int32 [6, n]) holds, per row, its DFA state (negative: no stop set),
+    the tokens and bytes it has seen and the result triple (at, keep, which) -- ``at`` -1 until the first match, all
+    three written once: row r's words are row r's own, or, ``by_slot``, those of its KV slot ``rows.slots[r]`` (the
+    continuous engine; a row of slot -1 is idle)."""
+
+    trans: Any
+    match_len: Any
+    match_id: Any
+    id_ptr: Any
+    ids: Any
+    id_base: Any
+    tok_off: Any
+    tok_bytes: Any
+    vocab: int
+    n_bytes: int
+    words: Any
+    state_cap: int
+    by_slot: bool = False
+
+    @property
+    def at(self):
+        return self.words[3]
+
+    def key(self) -> tuple:
+        """What a captured chunk bakes in of the stop state: addresses, the capacity and whose words a row's are."""
+        return ("stop",) + tuple(t.data_ptr() if t is not None else 0 for t in (
+            self.trans, self.match_len, self.match_id, self.id_ptr, self.ids, self.id_base, self.tok_off, self.tok_bytes,
+            self.words)) + (int(self.vocab), int(self.n_bytes), int(self.state_cap), bool(self.by_slot))
+
+
+@dataclass(frozen=True, eq=False)
 class Beam:
     """The beam-search state of a chunk (md_beam_select, md_kv_copy_tail), all device memory at fixed addresses.  The
     chunk's ``b`` rows are requests x ``num_beams`` beams.  ``state``: the library's struct over the caller's arrays
@@ -340,7 +376,11 @@ class DecodeChunk:
     ``beam`` (``Beam``): beam search -- after each step md_beam_select chooses every request's next beams from the
     logits the step left, writes their tokens to ``tokens[i + 1]`` (over the step's argmax) and their parents to plane i,
     and md_kv_copy_tail moves each surviving beam's KV tail to the slot its child decodes in.  The routing's slot table
-    is the record's ``cur``.  Greedy, fused steps only: not with any other optional field."""
+    is the record's ``cur``.  Greedy, fused steps only: not with any other optional field.
+    ``stop`` (``Stop``): after each step's pick and before its log-probability launches, every row's picked token
+    ``tokens[i + 1]`` goes through its stop matcher (md_stop_rows): each generated token exactly once, in order (the first
+    token, which the prompt pass picks, is fed by the caller before the first chunk).  The launch reads token ids only and
+    changes no logit and no pick.  Not with ``b1``, ``reason`` or ``beam``."""
 
     b: int
     tokens: Any
@@ -358,6 +398,7 @@ class DecodeChunk:
     penalty: Optional[Penalty] = None
     constraint: Optional[Constraint] = None
     beam: Optional[Beam] = None
+    stop: Optional[Stop] = None
 
 
 def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_stream: Optional[int] = None,
@@ -366,7 +407,7 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     stream: the chunk is replayed from the graph captured for it on that stream, or, first, run eagerly and captured
     (``model._replay_or_capture``: its ``GraphStore``'s, ``may_capture`` too).  The key starts (``tag``, stream) and names everything
     the launches bake in.  Returns True when it captured.  Besides that, the model gives the buffers (_decode_logits, _workspace,
-    _kv_struct) and the launches (_decode_step, _decode_step_b1, _decode_step_reason, _penalize, _constrain, _pick, _pick_rows, _pick_rows_filtered, _token_logprobs, _topk_logprobs, _beam_select, _kv_copy_tail)."""
+    _kv_struct) and the launches (_decode_step, _decode_step_b1, _decode_step_reason, _penalize, _constrain, _pick, _pick_rows, _pick_rows_filtered, _token_logprobs, _topk_logprobs, _beam_select, _kv_copy_tail, _stop_rows)."""
     c = chunk
     pieces = c.step is not None
     assert c.reason is None or (not pieces and not c.b1 and c.logprobs is None and c.pick is not None and c.pick.per_row)
@@ -377,6 +418,7 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
     assert c.constraint is None or (not c.b1 and c.reason is None)
     assert c.beam is None or (not pieces and not c.b1 and c.reason is None and c.pick is None and c.logprobs is None
                               and c.penalty is None and c.constraint is None)
+    assert c.stop is None or (not c.b1 and c.reason is None and c.beam is None)
     if not pieces:
         logits = model._decode_logits(c.b)
         ws = model._workspace(c.ws_bytes, 2)
@@ -415,6 +457,8 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
             # a greedy row takes the same argmax again and an idle row keeps what is there)
             if again:
                 pick_tokens(model, c.pick, lg, c.suppress_id, draws(i), out=tok_out)
+            if c.stop is not None:  # the picked token through each row's stop matcher: ids only, no logit is touched
+                model._stop_rows(tok_out, c.rows_of(i), c.stop)
             if lp is not None:  # targets = the step's tokens
                 model._token_logprobs(lg, tok_out, c.suppress_id, lp[i], rk[i])
             if tk_ids is not None:  # the decision's alternatives; a row whose token is no id (idle) is not read
@@ -446,4 +490,6 @@ def run_chunk(model, chunk: DecodeChunk, n: int, tag: str = "decode", capture_st
         key += c.constraint.key()
     if c.beam is not None:  # and another with the select and copy launches
         key += c.beam.key()
+    if c.stop is not None:  # and another with the stop launches; a chunk without them keeps its key
+        key += c.stop.key()
     return model._replay_or_capture(key, body, may_capture=may_capture)

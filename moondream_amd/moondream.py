@@ -30,18 +30,19 @@ import torch
 from PIL import Image
 
 from . import _lib, grammar, resample
+from . import stop as stops
 from .config import MoondreamConfig
 from .constraint import FREE, TokenAutomaton, check_constraints, pack, pow2_at_least
 from .crop_staging import CropStager, crop_workers, plan_chunks, upload_unique
 from .beam import Hypothesis, check_beams, finalize, inv_norm_table
-from .decode_loop import (Beam, Constraint, DecodeChunk, Penalty, ReasonChunk, Sampling, check_score_settings, check_top_logprobs,
-                          pick_tokens, run_chunk)
+from .decode_loop import (Beam, Constraint, DecodeChunk, Penalty, ReasonChunk, Sampling, Stop, check_score_settings,
+                          check_top_logprobs, pick_tokens, run_chunk)
 from .graph_store import GraphStore
 from .image_crops import crop_count, overlap_crop_image, reconstruct_from_crops, resize_backend
 from .integration import MASK_CAUSAL, MASK_PREFIX_LM, classify_attn_mask
 from .lora import variant_state_dict
 from .scores import Scores
-from .settings import DEFAULT_MAX_TOKENS, DEFAULT_TEMPERATURE, DEFAULT_TOP_P, CallSettings, refuse_settings
+from .settings import DEFAULT_MAX_TOKENS, DEFAULT_TEMPERATURE, DEFAULT_TOP_P, FAMILIES, CallSettings, refuse_settings
 from .shared_prefix import RowPlan, check_shared_table, plan_rows
 from .spatial import SpatialRecord, check_spatial_refs, refs_of, spatial_prompt_ids
 from .weights import PackedLora, PackedLoraBank, PackedModel
@@ -186,6 +187,8 @@ class Prepared:
     sampling: Optional[Sampling]  # the call's pick (None: greedy); shared route: ``row_perm`` set; with top-k / min-p: per row
     constraint: Optional[Constraint] = None  # the rows' automata, each past its first token's mask (None: every row free)
     penalty: Optional[Penalty] = None  # the rows' penalties, every history empty (None: every row neutral)
+    stop: Optional[Stop] = None  # the rows' stop matchers, nothing fed yet (None: no row has a stop set)
+    stop_sets: Optional[List[Optional[stops.StopSet]]] = None  # the rows' stop sets, in slot order like the record
 
     def in_caller_order(self, per_row: Sequence) -> list:
         out = [None] * len(self.order)
@@ -298,6 +301,7 @@ class MoondreamModel:
             raise _lib.MoondreamHipError("MoondreamModel needs a GPU device; there is no CPU path")
         self.tokenizer = tokenizer if tokenizer is not None else _load_tokenizer()
         self._own_vocab_bytes: Optional[List[bytes]] = None  # the tokenizer's vocabulary as bytes (regex_constraint)
+        self._vocab_dev_cache: Dict[int, tuple] = {}  # id(vocabulary) -> (vocabulary, tok_off, tok_bytes, n_bytes) on the device
         self._grammar_cache: Dict[tuple, tuple] = {}  # (kind, pattern, id(vocabulary)) -> (vocabulary, TokenAutomaton)
         self.w = PackedModel(config, state_dict, self._device)
         # the checkpoint's own 4-bit weight stream for the decode regime (enable_int4_decode): exact but OPT-IN -- the in-register
@@ -1225,8 +1229,11 @@ class MoondreamModel:
         """``regex_constraint`` for the compact JSON documents of ``schema`` (``json_schema_to_regex``: its supported subset)."""
         return self._grammar_constraint("json_schema", schema, vocab_bytes)
 
-    def _grammar_constraint(self, kind: str, value, vocab_bytes: Optional[Sequence[bytes]]) -> TokenAutomaton:
-        tk, v = self.config.tokenizer, self.config.text.vocab_size
+    def _vocab_bytes(self, kind: str, vocab_bytes: Optional[Sequence[bytes]]) -> Sequence[bytes]:
+        """The bytes of every id for ``kind`` ("regex", "json_schema", "stop"): ``vocab_bytes``, or, None, those of the
+        model's ``tokenizers.Tokenizer`` (derived once).  ValueError for the ``IdTokenizer`` stand-in without
+        ``vocab_bytes`` and for a vocabulary of the wrong length."""
+        v = self.config.text.vocab_size
         if vocab_bytes is None:
             if isinstance(self.tokenizer, IdTokenizer):
                 raise ValueError(f"{kind}: the IdTokenizer stand-in spells no bytes; pass vocab_bytes (one bytes object per token id)")
@@ -1235,6 +1242,85 @@ class MoondreamModel:
             vocab_bytes = self._own_vocab_bytes
         if len(vocab_bytes) != v:
             raise ValueError(f"vocab_bytes: {len(vocab_bytes)} entries for a vocabulary of {v}")
+        return vocab_bytes
+
+    def _vocab_on_device(self, vocab_bytes: Sequence[bytes]):
+        """``(tok_off int32 [V + 1], tok_bytes uint8, n_bytes)`` of ``grammar.vocab_arrays`` on the device, uploaded once
+        per vocabulary OBJECT (the object is kept, so that its id stays its own); the last four are kept."""
+        hit = self._vocab_dev_cache.get(id(vocab_bytes))
+        if hit is None or hit[0] is not vocab_bytes:
+            off, data = grammar.vocab_arrays(vocab_bytes)
+            hit = (vocab_bytes, self._h2d(torch.from_numpy(off)), self._h2d(torch.from_numpy(data.copy())), int(off[-1]))
+            while len(self._vocab_dev_cache) >= 4:  # bounded: a caller that makes a new list per call pins at most four
+                self._vocab_dev_cache.pop(next(iter(self._vocab_dev_cache)))
+            self._vocab_dev_cache[id(vocab_bytes)] = hit
+        return hit[1:]
+
+    def _stop_rows(self, tokens: torch.Tensor, rows: "_Rows", stop: Stop):
+        """Every row's just-picked token ``tokens[r]`` (device int32 [B]) goes through its stop matcher in ``stop``:
+        md_stop_rows.  A row's words are its own, or (``stop.by_slot``) those of its KV slot in ``rows``; an idle row and a
+        row without a stop set are left alone.  Nothing is allocated and nothing synchronises: capturable."""
+        b = tokens.numel()
+        assert tokens.dtype == torch.int32 and tokens.is_contiguous() and tokens.device == stop.words.device
+        w = stop.words
+        assert w.dtype == torch.int32 and w.is_contiguous() and w.shape[0] == 6
+        for t in (stop.match_id, stop.id_ptr, stop.ids, stop.id_base):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == w.device
+        assert stop.trans.numel() == stop.state_cap * 256 and stop.match_len.numel() == stop.state_cap and stop.match_id.numel() == stop.state_cap
+        assert stop.id_ptr.numel() == w.shape[1] + 1 and stop.id_base.numel() == w.shape[1]
+        slots = rows.slots if stop.by_slot else None
+        assert slots is not None or w.shape[1] >= b
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _lib.check(
+            self.lib.md_stop_rows(tokens.data_ptr(), b, ptr(slots), 0, stop.trans.data_ptr(), stop.match_len.data_ptr(),
+                                  stop.match_id.data_ptr(), stop.state_cap, stop.id_ptr.data_ptr(), stop.ids.data_ptr(),
+                                  stop.id_base.data_ptr(), ptr(stop.tok_off), ptr(stop.tok_bytes), stop.vocab, stop.n_bytes,
+                                  *(w[i].data_ptr() for i in range(6)), self._stream()),
+            "md_stop_rows",
+        )
+
+    def _stop_record(self, rows: Optional[Sequence[Optional[stops.StopSet]]], vocab_bytes=None) -> Optional[Stop]:
+        """``check_stops``' entries, one per row in the decode loop's row order -> the ``Stop`` record of a lockstep decode
+        with every row at its stop set's root, nothing seen and nothing matched (None for None).  The call's DISTINCT stop
+        sets are packed into one table (equal strings share states).  The buffers are the store's, one set per (row count,
+        state capacity) with the capacity rounded up to a power of two: calls whose stop strings differ but need tables of
+        similar size share the addresses and with them their captured chunks.  Stop strings need the bytes of every id
+        (``_vocab_bytes``; uploaded once per vocabulary object); stop sets of ids alone need none."""
+        if rows is None:
+            return None
+        distinct = list(dict.fromkeys(s for s in rows if s is not None))
+        table = stops.pack(distinct)
+        start = dict(zip(distinct, table.starts))
+        trans, match_len, match_id, cap = stops.padded(table)
+        b, ids_cap = len(rows), len(rows) * stops.STOP_IDS_MAX
+        tok_off = tok_bytes = None
+        vocab = n_bytes = 0
+        if any(s.strings for s in distinct):
+            tok_off, tok_bytes, n_bytes = self._vocab_on_device(self._vocab_bytes("stop", vocab_bytes))
+            vocab = self.config.text.vocab_size
+        d16, d32 = self._store.fixed("stop", (b, cap), lambda: (
+            torch.empty(cap * 257, dtype=torch.int16, device=self._device),
+            torch.empty(cap + (b + 1) + ids_cap + b + 6 * b, dtype=torch.int32, device=self._device)))
+        host = np.zeros(d32.numel(), dtype=np.int32)
+        h_mid, h_ptr, h_ids, h_base, h_words = np.split(host, np.cumsum([cap, b + 1, ids_cap, b]))
+        h_mid[:] = match_id
+        counts = [len(s.token_ids) if s is not None else 0 for s in rows]
+        h_ptr[1:] = np.cumsum(counts)
+        h_ids[:] = -1
+        h_ids[: int(h_ptr[-1])] = [t for s in rows if s is not None for t in s.token_ids]
+        h_base[:] = [len(s.strings) if s is not None else 0 for s in rows]
+        words = h_words.reshape(6, b)
+        words[0] = [start[s] if s is not None else stops.NO_STOP for s in rows]
+        words[3], words[5] = -1, -1
+        d16.copy_(self._h2d(torch.from_numpy(np.concatenate([trans.reshape(-1), match_len]).view(np.int16))))
+        d32.copy_(self._h2d(torch.from_numpy(host)))
+        d_trans, d_len = torch.split(d16, [cap * 256, cap])
+        d_mid, d_ptr, d_ids, d_base, d_words = torch.split(d32, [cap, b + 1, ids_cap, b, 6 * b])
+        return Stop(d_trans, d_len, d_mid, d_ptr, d_ids, d_base, tok_off, tok_bytes, vocab, n_bytes, d_words.view(6, b), cap)
+
+    def _grammar_constraint(self, kind: str, value, vocab_bytes: Optional[Sequence[bytes]]) -> TokenAutomaton:
+        tk, v = self.config.tokenizer, self.config.text.vocab_size
+        vocab_bytes = self._vocab_bytes(kind, vocab_bytes)
         if kind == "regex":
             if not isinstance(value, str):
                 raise ValueError(f"regex must be a str, not {value!r}")
@@ -1381,7 +1467,8 @@ class MoondreamModel:
     def _decode_greedy_impl(self, first: torch.Tensor, pos: Union[int, Sequence[int]], max_tokens: int, suppress_id: int,
                             rows: Union[int, _Rows] = 0, eos_id: Optional[int] = None, check_every: int = 16,
                             allow_b1: bool = True, sampling: Optional[Sampling] = None, scores: Optional[Scores] = None,
-                            penalty: Optional[Penalty] = None, constraint: Optional[Constraint] = None):
+                            penalty: Optional[Penalty] = None, constraint: Optional[Constraint] = None,
+                            stop: Optional[Stop] = None):
         """Device-resident decode loop: returns int32 [steps+1, B] (row 0 = ``first``).  ``sampling`` None: greedy.  Otherwise every
         step draws each sequence's token with the reference's rule (moondream.py:521-528: softmax(logits / T), _apply_top_p,
         multinomial) from the step's own logits on the device (md_sample_top_p), with one uniform per (step, sequence) taken
@@ -1400,7 +1487,11 @@ class MoondreamModel:
         penalised logits.  Such a call decodes on the batched kernels, never on the single-sequence one.
         ``constraint``: the rows' constraint record (``_constraint_record``), each row in the state ``first`` was picked
         under -- every step advances the states by the tokens it consumes and masks its logits before the pick
-        (after the penalties); the scores are those of the masked logits.  Batched kernels only, like ``penalty``."""
+        (after the penalties); the scores are those of the masked logits.  Batched kernels only, like ``penalty``.
+        ``stop``: the rows' stop record (``_stop_record``), nothing fed yet -- ``first`` goes through the matchers here, every
+        later token inside its step (md_stop_rows after the pick), and the all-done check counts a row that has matched as
+        done like one that has emitted its eos: one more small reduction at the same place, no further synchronisation.
+        The loop cuts nothing: the result triples stay in ``stop.words`` for the caller.  Batched kernels only."""
         rows = _Rows.of(rows)
         b = first.shape[0]
         t = self.config.text
@@ -1413,6 +1504,8 @@ class MoondreamModel:
         hist = torch.zeros(max_tokens + 1, b, dtype=torch.int32, device=self._device)
         hist[0] = first
         self._b1_used = False
+        if stop is not None:  # the prompt pass's token: the first one every matcher sees
+            self._stop_rows(hist[0], rows, stop)
         if max_tokens == 0:
             return hist
         pos_base = self._h2d(torch.tensor(pos_list, dtype=torch.int32))
@@ -1438,7 +1531,7 @@ class MoondreamModel:
                 return self._step_from_pieces(tok_in.reshape(b, 1), pos_h, rows, pos_dev=pos_t)[1]
 
             chunk = DecodeChunk(b, hist, pos_t, lambda i: rows, suppress_id, pick=sampling or Sampling(0.0, 0.0), step=lora_step,
-                                penalty=penalty, constraint=constraint)
+                                penalty=penalty, constraint=constraint, stop=stop)
             # (a per-row record -- top_k / min_p -- has no per-step draw of its own: it keeps the uniforms taken up front)
             graphs, uniforms = False, uniforms if sampling is not None and sampling.per_row else None
         else:
@@ -1447,7 +1540,7 @@ class MoondreamModel:
             # library says this model / cache / device fits its static limits and its grid can be co-resident; anything else
             # decodes on the batched kernels.  Never from the pipelined engine (allow_b1 = False): a second stream's persistent
             # GEMMs could keep workgroups of the grid off the chip and its software barriers would time out.
-            b1 = (b == 1 and allow_b1 and sampling is None and penalty is None and constraint is None
+            b1 = (b == 1 and allow_b1 and sampling is None and penalty is None and constraint is None and stop is None
                   and self.single_sequence_kernel and rows.plain
                   and not bool(self.w.text.fp8)
                   and bool(self.lib.md_decode_step_b1_supported(C.byref(self.w.text), C.byref(self._kv_struct(rows.slot0)))))
@@ -1457,7 +1550,7 @@ class MoondreamModel:
                     self._b1_sync = torch.zeros(4096, dtype=torch.int32, device=self._device)
                 need = max(need, self.lib.md_decode_step_b1_workspace_bytes(C.byref(self.w.text)))
             chunk = DecodeChunk(b, hist, pos_t, lambda i: rows, suppress_id, need, sampling, b1=b1, penalty=penalty,
-                                constraint=constraint)
+                                constraint=constraint, stop=stop)
             graphs = self.use_graphs
         # one graph = `per` consecutive steps over fixed buffers; eager chunks end where the all-done check is due
         per = max(1, min(check_every or 16, max_tokens)) if graphs else (check_every or max_tokens)
@@ -1487,7 +1580,13 @@ class MoondreamModel:
                 if scores is not None:
                     scores[steps + 1 : steps + n + 1].copy_(into)
             steps += n
-            if steps < max_tokens and eos_id is not None and bool((hist[: steps + 1] == eos_id).any(dim=0).all()):
+            if steps < max_tokens and stop is not None:  # a row is done at its eos or at its first stop match
+                done = stop.at[:b] >= 0
+                if eos_id is not None:
+                    done = done | (hist[: steps + 1] == eos_id).any(dim=0)
+                if bool(done.all()):
+                    break
+            elif steps < max_tokens and eos_id is not None and bool((hist[: steps + 1] == eos_id).any(dim=0).all()):
                 break  # every sequence has emitted its EOS
         return hist[: steps + 1]
 
@@ -1712,7 +1811,9 @@ class MoondreamModel:
         if fused:  # the one pass is both
             mark("image_prefill")
         mark("prompt_prefill")
-        return Prepared(plan.order, *out, rows, sampling, constraint, self._penalty_record(st and st.penalties))
+        stop_sets = st.stops if st is not None else None
+        return Prepared(plan.order, *out, rows, sampling, constraint, self._penalty_record(st and st.penalties),
+                        self._stop_record(stop_sets, st and st.stop_vocab_bytes), stop_sets)
 
     def _mark(self, marks: list, name: str):
         """Phase timing (``collect_timing``): an event on the current stream, named after the phase that ends there."""
@@ -1762,6 +1863,11 @@ class MoondreamModel:
         top_k: Union[int, Sequence[int]] = 0,
         min_p: Union[float, Sequence[float]] = 0.0,
         spatial: Optional[SpatialRecord] = None,
+        stop=None,
+        stop_token_ids=None,
+        include_stop_str_in_output: bool = False,
+        vocab_bytes: Optional[Sequence[bytes]] = None,
+        return_finish: bool = False,
     ):
         """Token ids for B (image, prompt-ids) pairs, decoded in lockstep; greedy by default.
 
@@ -1870,6 +1976,28 @@ class MoondreamModel:
         for prompts that hold their placeholders -- what ``batch_query(spatial_refs=)`` builds.  Each reference token is
         encoded on the device into its placeholder's row of the prompt embeddings (md_spatial_ref_embed: one launch per
         prompt pass, nothing else changes); None, or a record without tokens: the call without the argument.
+
+        ``stop`` / ``stop_token_ids``: the caller's own end condition, matched on the device (md_stop_rows: one launch per
+        step after the pick, inside the captured chunk; moondream_amd/stop.py).  ``stop``: one str, a list of str for
+        every row, or a list with one entry per row (None, a str or a list of str; a list that holds a None or a list is
+        read per row) -- up to 16 strings of 1 .. 64 bytes as UTF-8 per row.  ``stop_token_ids``: a list of ids for every
+        row, or one list (or None) per row, up to 16.  A row's ids end at the EARLIEST of: its eos (excluded, as ever), a
+        stop id (excluded like eos), the token in which a stop string completed -- INCLUDED, because a token cannot be
+        split: the earliest end wins, and among the strings that end at that byte the longest is named.  (vLLM cuts the
+        ids in front of that token when the string is excluded; here the ids keep it and ``Finish.text_bytes`` says where
+        the text ends.)  Log-probabilities, ranks and alternatives are cut to the ids' length.  The loop's all-done check
+        counts a matched row as done, so a call whose rows all stop early makes fewer steps.  Stop strings need the bytes
+        every id spells: ``vocab_bytes`` (one bytes object per id), None: the model's tokenizer's, as ``regex_constraint``
+        derives them; stop ids alone need none.  The launch reads token ids only: it changes no logit and no pick, a row
+        without a stop set returns the ids of the call without the arguments, and with no row having one the call is
+        that call, launch for launch.  Served in every mode of this call; a lone sequence with a stop set decodes on the
+        batched kernels.  ``return_finish``: one more element is appended to the return value (``ids`` alone becomes
+        ``(ids, finish)``): per row a ``Finish(reason, stop, text_bytes)`` -- "stop" / "eos" / "length", the matched string
+        or id, and, when a string matched, the number of bytes of the ids' text that are the output (those in front of
+        the string; with ``include_stop_str_in_output`` the string too).  ValueError, before any GPU work: an empty
+        string, one of more than 64 bytes, more than 16 entries, an entry of the wrong type, an id outside the
+        vocabulary, a per-row list of the wrong length, more than 4096 automaton states in all, and stop strings with
+        the ``IdTokenizer`` stand-in and no ``vocab_bytes``.
         """
         if spatial is not None and spatial.n_rows != len(images):
             raise ValueError(f"spatial: a record of {spatial.n_rows} rows for {len(images)} rows")
@@ -1879,14 +2007,18 @@ class MoondreamModel:
                              temperature=temperature, top_p=top_p, generator=generator, variant=variant, variants=variants,
                              return_logprobs=return_logprobs, top_logprobs=top_logprobs, repetition_penalty=repetition_penalty,
                              presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, constraints=constraints,
-                             top_k=top_k, min_p=min_p)
-        return self._generate_ids(images, prompts, st, eos_id, ignore_eos, share_prefix, return_logprobs, spatial)
+                             top_k=top_k, min_p=min_p, stop=stop, stop_token_ids=stop_token_ids,
+                             include_stop_str_in_output=include_stop_str_in_output, vocab_bytes=vocab_bytes,
+                             vocab_size=None if stop is None and stop_token_ids is None else self.config.text.vocab_size)
+        return self._generate_ids(images, prompts, st, eos_id, ignore_eos, share_prefix, return_logprobs, spatial, return_finish)
 
     def _generate_ids(self, images, prompts: Sequence[Sequence[int]], st: CallSettings, eos_id: Optional[int] = None,
                       ignore_eos: bool = False, share_prefix: bool = False, return_logprobs: bool = False,
-                      spatial: Optional[SpatialRecord] = None):
+                      spatial: Optional[SpatialRecord] = None, return_finish: bool = False):
         """``batch_generate_ids`` for a call whose settings are parsed: ``st`` is the call's settings record
         (moondream_amd/settings.py), one row per image; everything else as there."""
+        if st.stops is not None and any(s is not None and s.strings for s in st.stops):
+            self._vocab_bytes("stop", st.stop_vocab_bytes)  # (its errors: before any GPU work)
         b, max_tokens, variant, variants, top_k = len(images), st.max_tokens, st.variant, st.variants, st.top_logprobs
         assert b == len(prompts) and b > 0
         multi_rows = None
@@ -1912,21 +2044,42 @@ class MoondreamModel:
                                            scores=scores and scores[0], spatial=spatial)
             stop = None if ignore_eos else eos
             hist = self._decode_greedy(prep.first, prep.pos, max_tokens, tk.answer_id, prep.rows, stop, sampling=prep.sampling,
-                                       scores=scores, penalty=prep.penalty, constraint=prep.constraint)
+                                       scores=scores, penalty=prep.penalty, constraint=prep.constraint, stop=prep.stop)
             mark("decode")
-            host = scores and scores[: hist.shape[0]].to_host(hist)  # ids, logprobs, ranks, alternatives: ONE copy to the host
-            cols = (host.extra[0].T if host else hist.t()).tolist()
+            # the matchers' result triples travel with the history: ids [, triples], logprobs, ranks, alternatives in ONE copy
+            ride = (hist,) if prep.stop is None else (hist, prep.stop.words[3:6, :b])
+            host = scores and scores[: hist.shape[0]].to_host(*ride)
+            if host:
+                cols = host.extra[0].T.tolist()
+                triples = host.extra[1].T.tolist() if prep.stop is not None else None
+            elif prep.stop is not None:
+                both = torch.cat([hist, ride[1]]).t().tolist()
+                cols, triples = [c[:-3] for c in both], [c[-3:] for c in both]
+            else:
+                cols, triples = hist.t().tolist(), None
             if b == 1:
                 self._check_b1_barriers()
-            out = [[self._truncate(c, stop, max_tokens) for c in cols]]  # ids [, logprobs, ranks [, alternatives]] per slot
-            n = [len(ids) for ids in out[0]]  # _truncate keeps a leading run of the ids: the same run of their values
+            if triples is None and not return_finish:
+                out = [[self._truncate(c, stop, max_tokens) for c in cols]]  # ids [, logprobs, ranks [, alternatives]] per slot
+            else:  # the earliest of eos, a stop id (both excluded) and the token a stop string completed in (included)
+                ends = []
+                for r, c in enumerate(cols):
+                    n_gen = min(len(c), max_tokens)
+                    eos_at = c.index(stop, 0, n_gen) if stop is not None and stop in c[:n_gen] else None
+                    at, keep, which = triples[r] if triples is not None else (-1, 0, -1)
+                    ends.append(stops.finish_of(prep.stop_sets[r] if triples is not None else None, at, keep, which, n_gen,
+                                                st.include_stop_str, eos_at))
+                out = [[c[:n_ids] for c, (n_ids, _) in zip(cols, ends)]]
+            n = [len(ids) for ids in out[0]]  # a leading run of the ids is kept: the same run of their values
             if return_logprobs:
                 out += [[plane[: n[r], r].tolist() for r in range(b)] for plane in (host.logprob, host.rank)]
             if top_k:
                 out.append([host.alternatives((slice(n[r]), r)) for r in range(b)])
+            if return_finish:
+                out.append([f for _, f in ends])
         self._phase_times(marks)
         out = tuple(prep.in_caller_order(per_row) for per_row in out)
-        return out if return_logprobs else out[0]
+        return out if return_logprobs or return_finish else out[0]
 
     BEAM_LOCKSTEP_ROWS = 128  # requests x num_beams one lockstep serves (the decode step's weight-stream regime); more: split
 
@@ -2103,19 +2256,30 @@ class MoondreamModel:
     def _settings_of(self, settings: Optional[dict], n: int) -> CallSettings:
         """The settings record of a string-API call over ``n`` rows (``CallSettings.of_settings``: every check, and last
         the compilation of a ``regex`` / ``json_schema``): made once, by the public call, before any other GPU work."""
-        return CallSettings.of_settings(settings, n, self._check_automata, self._grammar_constraint)
+        with_stops = settings is not None and (settings.get("stop") is not None or settings.get("stop_token_ids") is not None)
+        return CallSettings.of_settings(settings, n, self._check_automata, self._grammar_constraint,
+                                        self.config.text.vocab_size if with_stops else None)
 
     def _string_ids(self, images, prompts: Sequence[Sequence[int]], settings: Optional[dict], st: Optional[CallSettings] = None,
-                    **kw) -> List[List[int]]:
+                    text: bool = False, **kw):
         """The ids behind ``batch_caption`` / ``batch_query`` / ``query_many``: ``_generate_ids`` with the record of
         ``settings`` (``st``: the caller has made it already; ``kw``: the call's further arguments), or, with
-        ``settings["num_beams"]`` > 1, the best beam hypothesis."""
+        ``settings["num_beams"]`` > 1, the best beam hypothesis.  ``text``: the rows' strings instead -- the tokenizer's
+        decoding of the ids, except for a row that stopped on a stop STRING (``settings["stop"]``): that row returns the
+        bytes of its ids cut to ``Finish.text_bytes``, decoded as UTF-8 with ``errors="replace"``."""
         st = st or self._settings_of(settings, len(images))
         if st.beams is not None:
             if kw.get("spatial") is not None:  # (beam rows are prepared by a route that takes no record)
                 raise ValueError("num_beams > 1 (beam search) is not served with spatial_refs")
-            return self._beam_best_ids(images, prompts, settings, st.beams)
-        return self._generate_ids(images, prompts, st, **kw)
+            ids = self._beam_best_ids(images, prompts, settings, st.beams)
+        elif text and st.stops is not None:
+            ids, ends = self._generate_ids(images, prompts, st, return_finish=True, **kw)
+            spell = self._vocab_bytes("stop", st.stop_vocab_bytes) if any(f.text_bytes is not None for f in ends) else None
+            return [self.tokenizer.decode(s) if f.text_bytes is None else
+                    stops.cut_text([spell[t] for t in s], f).decode("utf-8", errors="replace") for s, f in zip(ids, ends)]
+        else:
+            ids = self._generate_ids(images, prompts, st, **kw)
+        return [self.tokenizer.decode(s) for s in ids] if text else ids
 
     def batch_generate_ids_continuous(self, images, prompts: Sequence[Sequence[int]], max_tokens: Union[int, Sequence[int]] = DEFAULT_MAX_TOKENS,
                                       eos_id: Optional[int] = None, ignore_eos: bool = False, max_live: int = 64, chunk: int = 16,
@@ -2123,8 +2287,13 @@ class MoondreamModel:
                                       top_p: Union[float, Sequence[float]] = DEFAULT_TOP_P, seeds=None,
                                       variant: Optional[str] = None, return_logprobs: bool = False,
                                       top_logprobs: Optional[int] = None, repetition_penalty=None, presence_penalty=None,
-                                      frequency_penalty=None, constraints=None, top_k=None, min_p=None):
-        """``batch_generate_ids`` with continuous batching (moondream_amd/continuous.py): per-request ``max_tokens`` and EOS
+                                      frequency_penalty=None, constraints=None, top_k=None, min_p=None, stop=None,
+                                      stop_token_ids=None, include_stop_str_in_output: bool = False, vocab_bytes=None,
+                                      return_finish: bool = False, stop_states: Optional[int] = None):
+        """``stop`` / ``stop_token_ids`` / ``include_stop_str_in_output`` / ``vocab_bytes`` / ``return_finish``:
+        ``batch_generate_ids``' arguments, rule and return value per request; a request that matches gives its KV slot to
+        the next queued one (``stop_states``: the engine's table size, None: its default).
+        ``batch_generate_ids`` with continuous batching (moondream_amd/continuous.py): per-request ``max_tokens`` and EOS
         exit, freed KV slots refilled from the queue mid-decode; same greedy ids as the lockstep path.  ``temperature`` and
         ``top_p``: one float, or one per request (greedy and sampled requests share the decode steps).  ``return_logprobs``:
         (ids, logprobs, ranks) as ``batch_generate_ids`` returns them (``ContinuousEngine(logprobs=True)``); with
@@ -2134,11 +2303,13 @@ class MoondreamModel:
         ``top_k`` / ``min_p``: one value or one per request (None: off), ``batch_generate_ids``' rule per request."""
         from .continuous import ContinuousEngine
 
-        eng = ContinuousEngine(self, max_live, chunk, logprobs=bool(return_logprobs), top_logprobs=top_logprobs)
+        eng = ContinuousEngine(self, max_live, chunk, logprobs=bool(return_logprobs), top_logprobs=top_logprobs,
+                               **({} if stop_states is None else {"stop_states": stop_states}))
         return eng.generate(images, prompts, max_tokens, eos_id, ignore_eos, seeds, variant, temperature, top_p,
                             return_logprobs=bool(return_logprobs), repetition_penalty=repetition_penalty,
                             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, constraints=constraints,
-                            top_k=top_k, min_p=min_p)
+                            top_k=top_k, min_p=min_p, stop=stop, stop_token_ids=stop_token_ids,
+                            include_stop_str_in_output=include_stop_str_in_output, vocab_bytes=vocab_bytes, return_finish=return_finish)
 
     def teacher_forced_logits(self, images, prompts: Sequence[Sequence[int]], forced_ids, gather_idx) -> torch.Tensor:
         """Parity instrument (tests / bench.py): the logits of every greedy decision when each sequence is FORCED to follow
@@ -2199,7 +2370,7 @@ class MoondreamModel:
     def score_ids(self, images: Sequence[Union[Image.Image, EncodedImage]], prompts: Sequence[Sequence[int]],
                   continuations: Sequence[Sequence[int]], share_prefix: bool = False, variant: Optional[str] = None,
                   top_logprobs: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                  constraints=None, spatial_refs=None):
+                  constraints=None, spatial_refs=None, stop=None, stop_token_ids=None):
         """Score GIVEN continuations: returns ``(logprobs, ranks)``, one list per row with one entry per token of
         ``continuations[i]`` -- the values ``batch_generate_ids(..., return_logprobs=True)`` attaches to a token it generates,
         for the tokens the caller supplies.  ``logprobs[i][j]`` is log softmax of the model's logits after
@@ -2223,11 +2394,12 @@ class MoondreamModel:
         there is no history to penalise from -- scores are the model's own.  ``constraints`` likewise (ValueError), and
         ``spatial_refs`` (ValueError: the scorer's prompts carry no encoded references)."""
         refuse_settings(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                             constraints=constraints),
+                             constraints=constraints, stop=stop, stop_token_ids=stop_token_ids),
                         {"spatial_refs": "score_ids / query_choices (the scorer's prompts carry no encoded references)",
                          "constraints": "score_ids (no token is picked: scores are the model's own)",
-                         "penalties": "score_ids (no decode step runs: scores are the model's own)"},
-                        ("spatial_refs", "constraints", "penalties"), len(images), spatial_refs)
+                         "penalties": "score_ids (no decode step runs: scores are the model's own)",
+                         "stops": "score_ids (no token is generated: the continuations are the caller's)"},
+                        ("spatial_refs", "constraints", "penalties", "stops"), len(images), spatial_refs)
         top_k = check_top_logprobs(top_logprobs, True)
         self._check_score_args(images, prompts, continuations)
         conts = [[int(t) for t in c] for c in continuations]
@@ -2276,7 +2448,7 @@ class MoondreamModel:
 
     def batch_generate_ids_pipelined(self, batches, max_tokens: int = DEFAULT_MAX_TOKENS, ignore_eos: bool = False,
                                      repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, constraints=None,
-                                     top_k=0, min_p=0.0, spatial_refs=None):
+                                     top_k=0, min_p=0.0, spatial_refs=None, stop=None, stop_token_ids=None):
         """Generator over an iterable of (images, prompt-id lists) batches; yields each batch's greedy ids in order, one
         decode group late (a group = two consecutive batches of <= 64 sequences decoded as ONE lockstep of <= 128 -- round 6,
         ``pair_decode`` -- or one batch).  Two HIP streams: the MFMA-bound encode (vision + prefill) of batch k+1 on one, the HBM-bound lockstep
@@ -2296,12 +2468,13 @@ class MoondreamModel:
         that call are not served here: ValueError for a non-neutral one; nor are ``constraints`` (ValueError), nor ``top_k`` /
         ``min_p`` (ValueError for a non-neutral one: the engine decodes greedily), nor ``spatial_refs`` (ValueError)."""
         refuse_settings(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                             constraints=constraints, top_k=top_k, min_p=min_p),
+                             constraints=constraints, top_k=top_k, min_p=min_p, stop=stop, stop_token_ids=stop_token_ids),
                         {"spatial_refs": "the pipelined engine (its prefill arena embeds token ids alone)",
+                         "stops": "the pipelined engine (its paired decode keeps no matcher states)",
                          "filters": "the pipelined engine (it decodes greedily: there is no sampled row to cut)",
                          "constraints": "the pipelined engine (its paired decode keeps no automaton states)",
                          "penalties": "the pipelined engine (its paired decode keeps no histories)"},
-                        ("spatial_refs", "filters", "constraints", "penalties"), spatial_refs=spatial_refs)
+                        ("spatial_refs", "filters", "constraints", "penalties", "stops"), spatial_refs=spatial_refs)
         return self._pipelined_loop(batches, max_tokens, ignore_eos)
 
     # Round 6: the decode of TWO consecutive batches runs as one lockstep decode (<= 128 sequences) when the library takes that
@@ -2434,8 +2607,7 @@ class MoondreamModel:
             raise NotImplementedError("Model does not support captioning.")
         if length not in tpl:
             raise ValueError(f"Model does not support caption length '{length}'.")
-        ids = self._string_ids(images, [tpl[length]] * len(images), settings)
-        return [self.tokenizer.decode(s) for s in ids]
+        return self._string_ids(images, [tpl[length]] * len(images), settings, text=True)
 
     def _query_prompts(self, questions: Sequence[str]) -> List[List[int]]:
         """The prompt ids of ``batch_query`` / ``query_many``."""
@@ -2500,12 +2672,10 @@ class MoondreamModel:
             return self._reasoning_answers(self._batch_query_reasoning(images, questions, settings, share_prefix=False,
                                                                        spatial_refs=spatial_refs))
         if spatial_refs is None:
-            ids = self._string_ids(images, self._query_prompts(questions), settings)
-        else:
-            ids = self._string_ids_spatial(images, settings, self._query_prompts_spatial(images, questions, spatial_refs))
-        return [self.tokenizer.decode(s) for s in ids]
+            return self._string_ids(images, self._query_prompts(questions), settings, text=True)
+        return self._string_ids_spatial(images, settings, self._query_prompts_spatial(images, questions, spatial_refs), text=True)
 
-    def _string_ids_spatial(self, images, settings: Optional[dict], built, **kw) -> List[List[int]]:
+    def _string_ids_spatial(self, images, settings: Optional[dict], built, **kw):
         """``_string_ids`` of a query with ``spatial_refs``: ``built`` = ``_query_prompts_spatial``'s (prompts, record);
         beam search is not served with references (ValueError, before any GPU work: ``_string_ids``)."""
         prompts, spatial = built
@@ -2556,6 +2726,9 @@ class MoondreamModel:
         pick, the first included; with ``top_k`` / ``min_p`` a sampled answer's picks, the first included, go through the
         per-row pick with one row."""
         st = settings if isinstance(settings, CallSettings) else self._settings_of(settings, 1)
+        if st.stops is not None:
+            raise ValueError("stop / stop_token_ids are not served by the single-sequence generator (caption / query route them "
+                             "to the batched loop)")
         max_tokens, temperature, top_p = st.max_tokens, st.temperature, st.top_p
         penalties, filters, automata = st.penalties, st.filters, st.constraints
         lora = self._lora({"variant": st.variant})
@@ -2660,6 +2833,10 @@ class MoondreamModel:
             if stream:
                 raise ValueError("num_beams > 1 (beam search) is not served with stream=True")
             return {"caption": self.batch_caption([image], length, settings)[0]}
+        if st.stops is not None:  # stop strings / ids: the batched route with one row (its loop carries the matcher)
+            if stream:
+                raise ValueError("stop / stop_token_ids are not served with stream=True")
+            return {"caption": self.batch_caption([image], length, settings)[0]}
         enc = self.encode_image(image, settings)
         self.load_encoded_image(enc)
         prompt = torch.tensor([tpl[length]])
@@ -2687,6 +2864,12 @@ class MoondreamModel:
             return {"answer": self.batch_query([image], [question], settings)[0]}
         if reasoning:
             self._refuse_for_reasoning(settings)
+        if st.stops is not None:  # stop strings / ids: the batched route with one row (its loop carries the matcher)
+            if stream:
+                raise ValueError("stop / stop_token_ids are not served with stream=True")
+            if image is None:
+                raise ValueError("stop / stop_token_ids are served for a query about an image")
+            return {"answer": self.batch_query([image], [question], settings, spatial_refs=[spatial_refs] if spatial_refs else None)[0]}
         if image is not None:
             enc = self.encode_image(image, settings)
             self.load_encoded_image(enc)
@@ -3118,7 +3301,7 @@ class MoondreamModel:
     def _refuse_for_reasoning(settings: Optional[dict]) -> None:
         """What no reasoning query serves, the one-image ``query(reasoning=True)`` and the batched ones alike: ValueError."""
         refuse_settings(settings, {None: "reasoning queries", "filters": "reasoning queries (the reasoning loop picks with the "
-                                   "call's temperature and top-p alone)"})
+                                   "call's temperature and top-p alone)"}, FAMILIES[:4] + ("stops",))
 
     def _check_reasoning_served(self, settings: Optional[dict]) -> None:
         """What the batched reasoning query does not serve raises NotImplementedError, naming the reason (ValueError for
@@ -3224,7 +3407,7 @@ class MoondreamModel:
         settings (``check_score_settings``) -> the score window, None without ``return_scores``."""
         refuse_settings(settings, {None: f"{kind}: its loop decodes coordinates, not tokens picked from logits",
                                    "filters": f"{kind}: its loop decodes coordinates, not tokens sampled from logits",
-                                   "beams": f"{kind}: its loop decodes coordinates, not token hypotheses"})
+                                   "beams": f"{kind}: its loop decodes coordinates, not token hypotheses"}, FAMILIES[:4] + ("stops",))
         return check_score_settings(settings, self.config.region.coord_out_dim)
 
     def batch_detect(self, images, objects: Sequence[str], settings: Optional[dict] = None) -> List[dict]:
@@ -3267,10 +3450,10 @@ class MoondreamModel:
             raise ValueError("num_beams > 1 (beam search) is not served with spatial_refs")
         enc = self.encode_image(image, settings)
         if built is not None:
-            ids = self._string_ids_spatial([enc] * len(prompts), settings, built, st=st, share_prefix=True)
+            texts = self._string_ids_spatial([enc] * len(prompts), settings, built, st=st, share_prefix=True, text=True)
         else:
-            ids = self._string_ids([enc] * len(prompts), prompts, settings, st, share_prefix=True)
-        return [{"answer": self.tokenizer.decode(s)} for s in ids]
+            texts = self._string_ids([enc] * len(prompts), prompts, settings, st, share_prefix=True, text=True)
+        return [{"answer": t} for t in texts]
 
     def query_many_reasoning(self, image, questions: Sequence[str], settings: Optional[dict] = None, spatial_refs=None) -> List[dict]:
         """``query_many`` with reasoning: ``query(image, q, reasoning=True)`` for many questions about ONE image, in one
